@@ -15,15 +15,21 @@ the torch.distributed mirror).  --exchange reduce | reduce_scatter sum private a
 frames-per-GPU x N frames.
 
 Also reported on the same JSON line:
-  end_to_end   : SURVEY.md 8(d)'s definition -- first H2D enqueue to D2H of the result complete, one burst in flight,
-                 median of 20 (frames in pinned host memory through mfsr_burst_*_host);
   roofline     : the warp+fuse launches (a group of up to four frames per launch), HIP-event timed around every launch inside the timed
                  region; frac = bytes a launch MUST move / time / 8 TB/s; "bound": "valu" with the VALU-issue ceiling
                  from the PMC instruction count; traffic = PMC HBM bytes; reference_structure = SURVEY's per-frame RMW
                  accounting (what the reference's kernel would move), labelled as such;
+and only with --full (runs of their own after the timed region; null on a plain run):
+  end_to_end   : SURVEY.md 8(d)'s definition -- first H2D enqueue to D2H of the result complete, one burst in flight,
+                 median of 20 (frames in pinned host memory through mfsr_burst_*_host);
+  roofline.isolated : (--async-fuse) the warp+fuse launches timed again back to back on one stream;
   cpu_baseline : the CPU oracle pipeline ("port" of the same algorithm; the reference's own CPU path is third-party
                  OpenCV BTVL1, absent here) timed on the host cores on a bounded sample of the same workload, plus the
                  flip-set parity classification of the HIP path against it on that sample (tests/flipset.py).
+
+--dump-outputs DIR writes the u16 HR image the last timed step returned as DIR/out16.npy (float32), or a fixed, seeded
+sample of it (DIR/out16_sample.npy) when the whole image would exceed DUMP_MAX_SAMPLES; the synthetic inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 
 Other modes (not the contract's `value`): --h2d (every burst's frames start in pinned host memory), --no-pair,
 --no-async-fuse, --unfused, --workload {1080p5_gray_x2, 4k16_rggb_x4, 8k8_rggb_x2}, and
@@ -52,6 +58,21 @@ WORKLOADS = {
 }
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 VALU_CLOCK_GHZ = 2.4    # MI355X peak engine clock
+DUMP_MAX_SAMPLES = 8 << 20   # --dump-outputs: at most 8 Mi float32 samples (32 MB)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(out_dir, out16):
+    """--dump-outputs: `out16` (numpy, int16 holding u16 bit patterns) as float32 -- exact for u16 -- whole if it has at most
+    DUMP_MAX_SAMPLES samples, else DUMP_MAX_SAMPLES samples at fixed, seeded flat positions (sorted, drawn with replacement)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = out16.view(np.uint16).reshape(-1)
+    if flat.size <= DUMP_MAX_SAMPLES:
+        np.save(os.path.join(out_dir, "out16.npy"), out16.view(np.uint16).astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.size, size=DUMP_MAX_SAMPLES))
+    np.save(os.path.join(out_dir, "out16_sample.npy"), flat[idx].astype(np.float32))
 
 
 def fuse_input_bytes_per_frame(W, H, s, mono):
@@ -220,7 +241,7 @@ def spawn_ranks(n, argv, extra_env=None, timeout_s=None):
     return rc, out0
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)    # 20 bursts of 8 ms: the clocks settle after the first few
@@ -249,10 +270,16 @@ def main():
                          "`bench.py --gpus N` -- spawn_ranks, environment, RCCL context, relayed line -- on a one-GPU box)")
     ap.add_argument("--fixed-halo", action="store_true", help="N > 1, stripes: keep the default 64-row raw halo of the exchange instead "
                     "of sizing it from the probe burst's measured flow")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the H2D->D2H end-to-end leg (median of 20 bursts)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs the headline figure does not need: the CPU oracle baseline "
+                         "with its parity check, the H2D->D2H end-to-end leg and (--async-fuse) the stand-alone warp+fuse leg; "
+                         "a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the u16 HR image of the last timed step to DIR as float32 .npy (a fixed, seeded sample if large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the H2D->D2H end-to-end leg (median of 20 bursts)")
     ap.add_argument("--no-isolated", action="store_true",
-                    help="skip the stand-alone warp+fuse leg (with --no-e2e --no-cpu-baseline a profile of the run then holds only "
+                    help="--full: skip the stand-alone warp+fuse leg (with --no-e2e --no-cpu-baseline a profile of the run then holds only "
                          "the bursts of the warm-up and the timed region: profiles/*_kernel_stats_timed_region.csv)")
     ap.add_argument("--cpu-sample-frames", type=int, default=4)
     ap.add_argument("--unfused", action="store_true", help="one launch per reference kernel (A/B against the fused path)")
@@ -270,7 +297,16 @@ def main():
     ap.add_argument("--h2d", action="store_true",
                     help="N=1 only: frames start in pinned HOST memory and stream through a 4-deep device ring on a copy "
                          "stream (the PCIe-inclusive rate quoted in DESIGN.md; `value` of the contract is the HBM-resident run)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_e2e = args.no_isolated = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.dist_impl == "auto":
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.dry_run_ranks:
@@ -497,7 +533,7 @@ def main():
 
     h2d = args.h2d and world == 1 and pipe is not None
     host = None
-    if world == 1 and pipe is not None:
+    if world == 1 and pipe is not None and (h2d or not args.no_e2e):
         order = sorted(frames.keys())
         host = [frames[k].cpu().pin_memory() for k in order]   # pinned host copies for --h2d / the end-to-end leg
 
@@ -661,7 +697,12 @@ def main():
         if h2d:
             last = pipe._out16_host
         if last is not None:
-            out16_sha = hashlib.sha256(last.cpu().numpy().tobytes()).hexdigest()[:16]
+            last_np = last.cpu().numpy()
+            out16_sha = hashlib.sha256(last_np.tobytes()).hexdigest()[:16]
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last_np)
+        elif args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs: this run's step returned no image on rank 0")
 
     if world > 1 and not fallback_local:
         t = torch.tensor([dt], dtype=torch.float64, device=ctl_dev)

@@ -6,7 +6,7 @@ tag=${1:-fuse}
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --steps 1 --warmup 0"
+B="python3 bench.py --full --no-cpu-baseline --steps 1 --warmup 0"
 i=0
 for grp in \
  "SQ_WAVES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_ANY" \

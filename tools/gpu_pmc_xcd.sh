@@ -18,5 +18,5 @@ for i,c in sorted(d.items(), key=lambda kv:int(kv[0])):
     b=32*c.get("TCC_EA0_RDREQ_32B_sum",0)+64*c.get("TCC_EA0_RDREQ_64B_sum",0)+128*c.get("TCC_EA0_RDREQ_128B_sum",0)
     print(sys.argv[2], "dispatch", i, f"-> {b/1e9:.3f} GB read")
 PY
-  for r in 1 2 3; do MFSR_XCD_REMAP=$v python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('remap$v', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['isolated']['avg_launch_ms'])"; done
+  for r in 1 2 3; do MFSR_XCD_REMAP=$v python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('remap$v', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['isolated']['avg_launch_ms'])"; done
 done

@@ -5,7 +5,7 @@ tag=${1:-trace}; shift || true
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > "$out/bench_trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > "$out/bench_trace.log" 2>&1
 f=$(find "$out/trace" -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY' | tee "$out/kernel_stats.txt"
 import csv,sys
