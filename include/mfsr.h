@@ -140,6 +140,18 @@ int mfsr_accumulateSuperResFullRows(int nFrames, const uint16_t* const* dataIn, 
                                     int strideOut, int strideMask, int accumulatorsUndefined, int rowBegin, int rowEnd,
                                     mfsr_stream_t stream);
 
+/* Zoom window: mfsr_accumulateSuperResFullRows on the HR rectangle [x0, x0+w) x [y0, y0+h) of the (scale*dimX) x (scale*dimY)
+ * grid, with imgOut / totalWeights holding THAT RECTANGLE ONLY (pointers = its pixel (x0, y0), pitch strideOut >= 12*w bytes,
+ * 16-byte aligned).  Every pixel of it gets exactly the whole-frame result; raw / certainty / shift buffers keep their
+ * whole-frame addressing and are read around the window.  x0, y0 multiples of 16; w, h multiples of 16 or reaching the
+ * frame's right / bottom edge; x0 = y0 = w = h = 0: the whole frame.  accumulatorsUndefined as for FullN (only the window's
+ * bytes are written).  Rows outside [0, h) and columns outside [0, w) of the buffers are never touched. */
+int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+                                      const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                      mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale,
+                                      int strideOut, int strideMask, int accumulatorsUndefined, int x0, int y0, int w, int h,
+                                      mfsr_stream_t stream);
+
 /* ---- B/E/H/I: kernel.cu --------------------------------------------------- */
 int mfsr_squaredSum(const float* inTiles, float* outValues, int maxShift, int tileSize, int tileCount,
                     mfsr_stream_t stream); /* :119 */
@@ -462,6 +474,13 @@ int mfsr_finishFusedRows(const mfsr_float3* finalImg, const mfsr_float3* weight,
                          int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
                          int outPitch, uint16_t* out16, int width, int height, float threshold, int applyGamma, float maxOut,
                          int rowOffset, int fullHeight, mfsr_stream_t stream);
+/* mfsr_finishFused on the window [colOffset, colOffset + width) x [rowOffset, rowOffset + height) of a fullWidth x fullHeight
+ * image (pointers = the window's first pixel; u/v window = that of the WHOLE image): bit-identical to that rectangle of the
+ * whole-image call */
+int mfsr_finishFusedWindow(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgPitch, const mfsr_float3* fallback,
+                           int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                           int outPitch, uint16_t* out16, int width, int height, float threshold, int applyGamma, float maxOut,
+                           int colOffset, int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream);
 
 /* ---- burst pipeline (the L3 driver the reference lacks; mirrors the CLI
  *      contract of finalProject/Project/multi_frame_sr.cpp:122-210) ---------- */
@@ -520,6 +539,20 @@ size_t mfsr_burst_workspace_bytes(const mfsr_config* cfg);
 size_t mfsr_burst_accumulator_bytes(const mfsr_config* cfg);
 int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void* workspace, size_t workspaceBytes);
 void mfsr_burst_destroy(mfsr_burst* b);
+
+/* ---- zoom windows: super-resolve the HR rectangle [x0, x0+w) x [y0, y0+h) of the (scale*width) x (scale*height) grid only.
+ * The windowed burst's accumulators, float image and u16 image are bit for bit that rectangle cut from the whole-frame burst
+ * (same config, frames and calls); its buffers are dense window-sized images: accumulators and outImg pitch 12*w bytes,
+ * out16 w*h*3.  The alignment stays whole-frame.  Constraints: x0, y0 multiples of 16; w, h multiples of 16 or reaching
+ * the right / bottom edge; inside the frame, not empty; x0 = y0 = w = h = 0 = the whole frame (the default).
+ * mfsr_window_check: host arithmetic only (no device call): MFSR_OK, MFSR_E_INVALID, MFSR_E_UNSUPPORTED (cfg->fused == 0). */
+int mfsr_window_check(const mfsr_config* cfg, int x0, int y0, int w, int h);
+/* between bursts only (MFSR_E_INVALID while frames are pending); takes effect from the next set_reference* on: add_frame,
+ * begin, flush, finish, the *_host calls, process_source and process_joint then work on window-sized buffers.  A window
+ * needs cfg.fused = 1 (MFSR_E_UNSUPPORTED otherwise). */
+int mfsr_burst_set_window(mfsr_burst* b, int x0, int y0, int w, int h);
+/* the window in effect (the whole frame: 0, 0, scale*width, scale*height) */
+int mfsr_burst_get_window(const mfsr_burst* b, int* x0, int* y0, int* w, int* h);
 /* Prepare the reference frame (tracking pyramid, half-res RGB, kernel
  * parameters, fallback image).  rawRef: dense u16 width x height on device. */
 int mfsr_burst_set_reference(mfsr_burst* b, const uint16_t* rawRef, mfsr_stream_t stream);
@@ -650,6 +683,9 @@ int mfsr_stream_push(mfsr_stream* s, const uint16_t* frame, mfsr_float3* outImg,
  * when none is left */
 int mfsr_stream_drain(mfsr_stream* s, mfsr_float3* outImg, uint16_t* out16, long long* produced, mfsr_stream_t stream);
 int mfsr_stream_reset(mfsr_stream* s);
+/* every output of the stream is the window (see mfsr_burst_set_window): before the first push or after mfsr_stream_reset.  The
+ * workspace is sized for the whole frame, so any window fits. */
+int mfsr_stream_set_window(mfsr_stream* s, int x0, int y0, int w, int h);
 
 /* ---- whole burst with the JOINT SHIFT MINIMISER (stage C; ShiftMinimizerKernels.cu:81-258) in the loop.  Besides every
  * (reference, k) pair the tracker measures every neighbouring pair (k, k+1); per tile the frame-to-frame shifts are the

@@ -78,19 +78,22 @@ extern "C" int mfsr_accumulateImages(const uint16_t* dataIn, mfsr_float3* imgOut
 // GEOM_CROP: the reference geometry (x2, output grid dimX x dimY over the central
 //            half of the frame).
 // GEOM_FULL: scale s, output grid (s*dimX) x (s*dimY) over the whole frame.
-template <int GEOM, bool FAST>
+// WIN: output columns [colBegin, colEnd) too, accumulators relative to (colBegin, rowBegin) (a window of the HR grid)
+template <int GEOM, bool FAST, bool WIN = false>
 __global__ void __launch_bounds__(256)
     k_accumulateSuperRes(const uint16_t* __restrict__ dataIn, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights,
                          const float4* __restrict__ certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts, Levels3 lv,
-                         int dimX, int dimY, int scale, int strideOut, int strideMask, int cfa, int rowBegin, int rowEnd)
+                         int dimX, int dimY, int scale, int strideOut, int strideMask, int cfa, int rowBegin, int rowEnd,
+                         int colBegin, int colEnd)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x + (WIN ? colBegin : 0);
     const int y = blockIdx.y * blockDim.y + threadIdx.y + rowBegin;  // [rowBegin, rowEnd): output row window of the launch
     const int outW = (GEOM == GEOM_CROP) ? dimX : dimX * scale;
     const int outH = (GEOM == GEOM_CROP) ? dimY : dimY * scale;
     if (x < 1 || y < 1 || x >= outW - 1 || y >= outH - 1 || y >= rowEnd) return;
+    if (WIN && x >= colEnd) return;
     accumulate_pixel_generic<GEOM, FAST>(x, y, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, lv, dimX,
-                                         dimY, scale, strideOut, strideMask, cfa);
+                                         dimY, scale, strideOut, strideMask, cfa, WIN ? colBegin : 0, WIN ? rowBegin : 0);
 }
 
 // 0: straight kernel with the ocml expf (tight parity tests); 1: straight kernel with
@@ -107,13 +110,15 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
-                                       int fresh, int rowBegin, int rowEnd, mfsr_stream_t stream);  // accumulate_fast.hip
+                                       int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
+                                       mfsr_stream_t stream);  // accumulate_fast.hip
 
 int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
-                                      int fresh, int rowBegin, int rowEnd, mfsr_stream_t stream);  // accumulate_fast.hip
+                                      int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
+                                      mfsr_stream_t stream);  // accumulate_fast.hip
 
 static int check_superres_args(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                                const mfsr_float4* certaintyMask, const mfsr_tex2d& kernelParam, const mfsr_tex2d& shifts,
@@ -142,42 +147,54 @@ extern "C" int mfsr_accumulateImagesSuperRes(const uint16_t* dataIn, mfsr_float3
     if (g_accumulate_fast)
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_CROP, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
                            (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, 2,
-                           strideOut, strideMask, mfsr_cfa_packed(), 0, dimY);
+                           strideOut, strideMask, mfsr_cfa_packed(), 0, dimY, 0, 0);
     else
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_CROP, false>), grid, block, 0, mfsr_s(stream), dataIn,
                            (pix3*)imgOut, (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX,
-                           dimY, 2, strideOut, strideMask, mfsr_cfa_packed(), 0, dimY);
+                           dimY, 2, strideOut, strideMask, mfsr_cfa_packed(), 0, dimY, 0, 0);
     return mfsr_launch_status("accumulateImagesSuperRes");
 }
 
-// one frame, HR row window [rowBegin, rowEnd) (whole frame: 0, scale*dimY)
-static int accumulate_full_rows(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
-                                const mfsr_float4* certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts,
-                                mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
-                                int strideMask, int rowBegin, int rowEnd, mfsr_stream_t stream)
+// one frame, HR window w (whole frame: 0, 0, scale*dimX, scale*dimY)
+static int accumulate_full_win(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+                               const mfsr_float4* certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts,
+                               mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
+                               int strideMask, const HrWindow& w, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(scale >= 1 && scale <= 8);
     int rc = check_superres_args(dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, dimX, dimY,
-                                 dimX * scale, strideOut, strideMask);
+                                 w.rel ? w.x1 - w.x0 : dimX * scale, strideOut, strideMask);
     if (rc) return rc;
     if (g_accumulate_fast == 2 && scale == 2 &&
         mfsr_try_launch_accumulate2x_strip(1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
-                                           blackLevel, dimX, dimY, strideOut, strideMask, 0, rowBegin, rowEnd, stream) == 1)
+                                           blackLevel, dimX, dimY, strideOut, strideMask, 0, w.y0, w.y1, w.x0, w.x1, w.rel,
+                                           stream) == 1)
         return mfsr_launch_status("accumulateSuperResFull(strip)");
     if (g_accumulate_fast == 2 && scale == 4 &&
         mfsr_try_launch_accumulate4x_tile(1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
-                                          blackLevel, dimX, dimY, strideOut, strideMask, 0, rowBegin, rowEnd, stream) == 1)
+                                          blackLevel, dimX, dimY, strideOut, strideMask, 0, w.y0, w.y1, w.x0, w.x1, w.rel,
+                                          stream) == 1)
         return mfsr_launch_status("accumulateSuperResFull(x4 tile)");
-    dim3 block(64, 4), grid(mfsr_cdiv((long long)dimX * scale, 64), mfsr_cdiv(rowEnd - rowBegin, 4));
+    const int rowBegin = w.y0, rowEnd = w.y1;
+    const bool win = w.rel && !(w.x0 == 0 && w.x1 == dimX * scale && w.y0 == 0);
+    dim3 block(64, 4), grid(win ? mfsr_cdiv(w.x1 - w.x0, 64) : mfsr_cdiv((long long)dimX * scale, 64), mfsr_cdiv(rowEnd - rowBegin, 4));
     const Levels3 lv = make_levels(whiteLevel, blackLevel);
-    if (g_accumulate_fast)
+    if (win && g_accumulate_fast)
+        hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, true, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
+                           (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
+                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, w.x0, w.x1);
+    else if (win)
+        hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, false, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
+                           (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
+                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, w.x0, w.x1);
+    else if (g_accumulate_fast)
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
                            (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
-                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd);
+                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, 0, 0);
     else
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, false>), grid, block, 0, mfsr_s(stream), dataIn,
                            (pix3*)imgOut, (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX,
-                           dimY, scale, strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd);
+                           dimY, scale, strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, 0, 0);
     return mfsr_launch_status("accumulateSuperResFull");
 }
 
@@ -186,8 +203,8 @@ extern "C" int mfsr_accumulateSuperResFull(const uint16_t* dataIn, mfsr_float3* 
                                            mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale,
                                            int strideOut, int strideMask, mfsr_stream_t stream)
 {
-    return accumulate_full_rows(dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY,
-                                scale, strideOut, strideMask, 0, scale * dimY, stream);
+    return accumulate_full_win(dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY,
+                               scale, strideOut, strideMask, HrWindow{0, 0, scale * dimX, scale * dimY, 0}, stream);
 }
 
 extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
@@ -224,6 +241,61 @@ extern "C" int mfsr_accumulateSuperResFull2(const uint16_t* dataIn0, const uint1
 // nFrames (1 .. MFSR_MAX_FUSE_GROUP) frames in one call; accumulatorsUndefined != 0: the planes are overwritten as if
 // they had been zeroed before the call (the first launch of a burst: saves the memset and the read of
 // both planes -- 0 + x == x, so the result equals the zeroed-and-accumulated one bit for bit).
+// Only the HR window w is touched: rows [y0, y1) (stripe-sharded bursts, whole-frame accumulators) or a rectangle with
+// window-relative accumulators (zoom windows); every pixel of it gets exactly what the whole-frame call gives it.  The
+// kernels are chosen from the frame's geometry, never from the window's.
+static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+                                const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
+                                int strideMask, int accumulatorsUndefined, const HrWindow& w, mfsr_stream_t stream)
+{
+    for (int n = 0; n < nFrames; n++) {
+        const int rc = check_superres_args(dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], dimX, dimY,
+                                           w.rel ? w.x1 - w.x0 : dimX * scale, strideOut, strideMask);
+        if (rc) return rc;
+    }
+    const int fresh = accumulatorsUndefined ? 1 : 0;
+    if (g_accumulate_fast == 2 && scale == 2) {
+        const int r = mfsr_try_launch_accumulate2x_strip(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+                                                         whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, w.y0, w.y1,
+                                                         w.x0, w.x1, w.rel, stream);
+        if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(strip)");
+        if (r < 0) return MFSR_E_INVALID;
+    }
+    if (g_accumulate_fast == 2 && scale == 4) {
+        const int r = mfsr_try_launch_accumulate4x_tile(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+                                                        whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, w.y0, w.y1,
+                                                        w.x0, w.x1, w.rel, stream);
+        if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(x4 tile)");
+        if (r < 0) return MFSR_E_INVALID;
+    }
+    if (nFrames > 2) {
+        // no kernel of this geometry takes the whole group: two frames, then the rest
+        const int rc = accumulate_group_win(2, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel,
+                                            dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined, w, stream);
+        if (rc) return rc;
+        return accumulate_group_win(nFrames - 2, dataIn + 2, imgOut, totalWeights, certaintyMask + 2, kernelParam, shifts + 2,
+                                    whiteLevel, blackLevel, dimX, dimY, scale, strideOut, strideMask, 0, w, stream);
+    }
+    if (fresh) {
+        if (w.rel) {
+            const size_t rowBytes = (size_t)(w.x1 - w.x0) * 12, rows = (size_t)(w.y1 - w.y0);
+            MFSR_HIP_TRY(hipMemset2DAsync(imgOut, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
+            MFSR_HIP_TRY(hipMemset2DAsync(totalWeights, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
+        } else {
+            const size_t off = (size_t)w.y0 * strideOut, bytes = (size_t)(w.y1 - w.y0) * strideOut;
+            MFSR_HIP_TRY(hipMemsetAsync((char*)imgOut + off, 0, bytes, mfsr_s(stream)));
+            MFSR_HIP_TRY(hipMemsetAsync((char*)totalWeights + off, 0, bytes, mfsr_s(stream)));
+        }
+    }
+    for (int n = 0; n < nFrames; n++) {
+        const int rc = accumulate_full_win(dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], whiteLevel,
+                                           blackLevel, dimX, dimY, scale, strideOut, strideMask, w, stream);
+        if (rc) return rc;
+    }
+    return MFSR_OK;
+}
+
 // Only HR rows [rowBegin, rowEnd) are touched (stripe-sharded bursts): rowBegin a multiple of 16, rowEnd a multiple
 // of 16 or the frame's last row + 1; every pixel of the window gets exactly what the whole-frame call gives it.
 extern "C" int mfsr_accumulateSuperResFullRows(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
@@ -237,47 +309,31 @@ extern "C" int mfsr_accumulateSuperResFullRows(int nFrames, const uint16_t* cons
     MFSR_REQUIRE(scale >= 1 && scale <= 8);
     const int hrH = scale * dimY;
     MFSR_REQUIRE(rowBegin >= 0 && rowBegin < rowEnd && rowEnd <= hrH && (rowBegin % 16) == 0 && ((rowEnd % 16) == 0 || rowEnd == hrH));
-    for (int n = 0; n < nFrames; n++) {
-        const int rc = check_superres_args(dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], dimX, dimY,
-                                           dimX * scale, strideOut, strideMask);
-        if (rc) return rc;
+    return accumulate_group_win(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
+                                dimY, scale, strideOut, strideMask, accumulatorsUndefined,
+                                HrWindow{0, rowBegin, scale * dimX, rowEnd, 0}, stream);
+}
+
+// the HR window [x0, x0+w) x [y0, y0+h) with window-relative accumulators (pitch strideOut >= 12 w, 16-byte aligned):
+// bit for bit that rectangle of the whole-frame call (mfsr_window_check states the constraints)
+extern "C" int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                                 mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
+                                                 mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
+                                                 mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
+                                                 int strideMask, int accumulatorsUndefined, int x0, int y0, int w, int h,
+                                                 mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= MFSR_MAX_FUSE_GROUP && dataIn && certaintyMask && shifts);
+    MFSR_REQUIRE(scale >= 1 && scale <= 8 && dimX > 0 && dimY > 0);
+    const int hrW = scale * dimX, hrH = scale * dimY;
+    if (w == 0 && h == 0 && x0 == 0 && y0 == 0) {
+        w = hrW;
+        h = hrH;
     }
-    const int fresh = accumulatorsUndefined ? 1 : 0;
-    if (g_accumulate_fast == 2 && scale == 2) {
-        const int r = mfsr_try_launch_accumulate2x_strip(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
-                                                         whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, rowBegin,
-                                                         rowEnd, stream);
-        if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(strip)");
-        if (r < 0) return MFSR_E_INVALID;
-    }
-    if (g_accumulate_fast == 2 && scale == 4) {
-        const int r = mfsr_try_launch_accumulate4x_tile(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
-                                                        whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, rowBegin,
-                                                        rowEnd, stream);
-        if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(x4 tile)");
-        if (r < 0) return MFSR_E_INVALID;
-    }
-    if (nFrames > 2) {
-        // no kernel of this geometry takes the whole group: two frames, then the rest
-        const int rc = mfsr_accumulateSuperResFullRows(2, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel,
-                                                       blackLevel, dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined,
-                                                       rowBegin, rowEnd, stream);
-        if (rc) return rc;
-        return mfsr_accumulateSuperResFullRows(nFrames - 2, dataIn + 2, imgOut, totalWeights, certaintyMask + 2, kernelParam,
-                                               shifts + 2, whiteLevel, blackLevel, dimX, dimY, scale, strideOut, strideMask, 0,
-                                               rowBegin, rowEnd, stream);
-    }
-    if (fresh) {
-        const size_t off = (size_t)rowBegin * strideOut, bytes = (size_t)(rowEnd - rowBegin) * strideOut;
-        MFSR_HIP_TRY(hipMemsetAsync((char*)imgOut + off, 0, bytes, mfsr_s(stream)));
-        MFSR_HIP_TRY(hipMemsetAsync((char*)totalWeights + off, 0, bytes, mfsr_s(stream)));
-    }
-    for (int n = 0; n < nFrames; n++) {
-        const int rc = accumulate_full_rows(dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], whiteLevel,
-                                            blackLevel, dimX, dimY, scale, strideOut, strideMask, rowBegin, rowEnd, stream);
-        if (rc) return rc;
-    }
-    return MFSR_OK;
+    MFSR_REQUIRE(mfsr_window_ok(hrW, hrH, x0, y0, w, h));
+    MFSR_REQUIRE((strideOut & 15) == 0 && ((uintptr_t)imgOut & 15) == 0 && ((uintptr_t)totalWeights & 15) == 0);
+    return accumulate_group_win(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
+                                dimY, scale, strideOut, strideMask, accumulatorsUndefined, HrWindow{x0, y0, x0 + w, y0 + h, 1}, stream);
 }
 
 extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,

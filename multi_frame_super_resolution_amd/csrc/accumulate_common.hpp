@@ -238,12 +238,58 @@ __device__ __forceinline__ void accumulate_pixel_generic(int x, int y, const uin
                                                          const float4* __restrict__ certaintyMask,
                                                          const mfsr_tex2d& kernelParam, const mfsr_tex2d& shifts,
                                                          const Levels3& lv, int dimX, int dimY, int scale, int strideOut,
-                                                         int strideMask, int cfa)
+                                                         int strideMask, int cfa, int accX0 = 0, int accY0 = 0)
 {
-    pix3 pixel = row_ptr(imgOut, strideOut, y)[x];
-    pix3 totalWeight = row_ptr(totalWeights, strideOut, y)[x];
+    // (accX0, accY0): HR pixel the accumulators' first element stands for (a window's origin; 0, 0 for whole-frame planes)
+    pix3 pixel = row_ptr(imgOut, strideOut, y - accY0)[x - accX0];
+    pix3 totalWeight = row_ptr(totalWeights, strideOut, y - accY0)[x - accX0];
     accumulate_pixel_core<GEOM, FAST, SUMS>(x, y, dataIn, certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale, strideMask,
                                       cfa, pixel, totalWeight);
-    row_ptr(imgOut, strideOut, y)[x] = pixel;
-    row_ptr(totalWeights, strideOut, y)[x] = totalWeight;
+    row_ptr(imgOut, strideOut, y - accY0)[x - accX0] = pixel;
+    row_ptr(totalWeights, strideOut, y - accY0)[x - accX0] = totalWeight;
+}
+
+// HR output window of a warp+fuse launch: pixels [x0, x1) x [y0, y1) of the whole-frame grid.  rel = 0: the accumulators are
+// the whole frame's (pointer = pixel (0, 0)); rel = 1: they hold the window only (pointer = pixel (x0, y0)).
+struct HrWindow {
+    int x0, y0, x1, y1;
+    int rel;
+};
+
+// the frame-border margin ring of the fast kernels (x in [1, M) or [hrW-M, hrW-1), y in [1, M) or [hrH-M, hrH-1)) cut to a
+// window: four rectangles enumerated back to back (start[r] = first thread index of rectangle r, start[4] = their total)
+struct MarginRects {
+    int x0[4], y0[4], w[4];
+    int start[5];
+    int accX0, accY0;  // origin of the window-relative accumulators
+};
+
+inline MarginRects margin_rects(int hrW, int hrH, int M, const HrWindow& w)
+{
+    const int r[4][4] = {{1, 1, hrW - 1, M}, {1, hrH - M, hrW - 1, hrH - 1}, {1, M, M, hrH - M}, {hrW - M, M, hrW - 1, hrH - M}};
+    MarginRects m{};
+    m.start[0] = 0;
+    for (int i = 0; i < 4; i++) {
+        const int x0 = r[i][0] > w.x0 ? r[i][0] : w.x0, x1 = r[i][2] < w.x1 ? r[i][2] : w.x1;
+        const int y0 = r[i][1] > w.y0 ? r[i][1] : w.y0, y1 = r[i][3] < w.y1 ? r[i][3] : w.y1;
+        const int cw = x1 > x0 ? x1 - x0 : 0, ch = y1 > y0 ? y1 - y0 : 0;
+        m.x0[i] = x0;
+        m.y0[i] = y0;
+        m.w[i] = cw > 0 ? cw : 1;
+        m.start[i + 1] = m.start[i] + cw * ch;
+    }
+    m.accX0 = w.x0;
+    m.accY0 = w.y0;
+    return m;
+}
+
+// thread index -> pixel of the window's margin rectangles; false past their end
+__device__ __forceinline__ bool margin_rect_pixel(const MarginRects& m, int idx, int& x, int& y)
+{
+    if (idx >= m.start[4]) return false;
+    const int i = idx < m.start[1] ? 0 : (idx < m.start[2] ? 1 : (idx < m.start[3] ? 2 : 3));
+    const int r = idx - m.start[i];
+    y = m.y0[i] + r / m.w[i];
+    x = m.x0[i] + r % m.w[i];
+    return true;
 }

@@ -399,13 +399,22 @@ __device__ __forceinline__ void strip_pixel(int X, int Y, int sx, int sy, float 
 
 // SCALE is a template parameter: the straight arithmetic takes floor((x + px + sx) / scale) twenty times per pixel, and an
 // integer division by a run-time value is ~40 instructions -- half of this kernel's work when the scale was a kernel argument
-template <int SCALE>
+// WIN: the part of the ring inside a window (MarginRects), accumulators relative to the window's origin
+template <int SCALE, bool WIN = false>
 __global__ void __launch_bounds__(256)
     k_accumulateMargin(const uint16_t* __restrict__ raw, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights,
                        const float4* __restrict__ certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts, Levels3 glv,
-                       int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBegin, int rowEnd)
+                       int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBegin, int rowEnd, MarginRects mr)
 {
     constexpr int scale = SCALE;
+    if constexpr (WIN) {
+        int x, y;
+        if (!margin_rect_pixel(mr, blockIdx.x * blockDim.x + threadIdx.x, x, y)) return;
+        accumulate_pixel_generic<GEOM_FULL, true, MARGIN_TAP_SUMS>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+                                                                   glv, dimX, dimY, scale, strideOut, strideMask, cfaPacked,
+                                                                   mr.accX0, mr.accY0);
+        return;
+    }
     const int hrW = scale * dimX, hrH = scale * dimY, M = STRIP_MARGIN;
     const int rowLen = hrW - 2;                    // x in [1, hrW-1)
     const int nTop = (M - 1) * rowLen;             // y in [1, M)
@@ -451,10 +460,11 @@ struct TileFrames {
 // parameters, then raw and certainty per tap) on 7.6 K wavefronts at 4K: one thread per (pixel, frame) -- 64 pixels x NF
 // frames per workgroup -- keeps the chain one frame long; the frames' sums (each taken from zero) meet in LDS and are
 // added to the accumulators in call order by the pixel's first thread, which reads and writes them once.
-template <int NF, int SCALE>
+template <int NF, int SCALE, bool WIN = false>
 __global__ void __launch_bounds__(64 * NF)
     k_accumulateMarginN(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
-                        Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBegin, int rowEnd)
+                        Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBegin, int rowEnd,
+                        MarginRects mr)
 {
     constexpr int scale = SCALE;
     __shared__ float sSum[NF][6][64];
@@ -466,7 +476,9 @@ __global__ void __launch_bounds__(64 * NF)
     const int lane = threadIdx.x, n = threadIdx.y;
     const int idx = blockIdx.x * 64 + lane;
     int x = 0, y = -1;
-    if (idx < nTop) {
+    if constexpr (WIN) {
+        if (!margin_rect_pixel(mr, idx, x, y)) y = -1;
+    } else if (idx < nTop) {
         y = 1 + idx / rowLen;
         x = 1 + idx % rowLen;
     } else if (idx < nTop + nBot) {
@@ -480,6 +492,7 @@ __global__ void __launch_bounds__(64 * NF)
         x = c < M - 1 ? 1 + c : hrW - M + (c - (M - 1));
     }
     const bool live = y >= rowBegin && y < rowEnd && y >= 0;
+    const int ax = WIN ? mr.accX0 : 0, ay = WIN ? mr.accY0 : 0;  // accumulator origin
     pix3 pixel = {0.0f, 0.0f, 0.0f}, totalWeight = {0.0f, 0.0f, 0.0f};
     if (live) {
         TileFrame F = fr.f[0];
@@ -497,8 +510,8 @@ __global__ void __launch_bounds__(64 * NF)
     sSum[n][5][lane] = totalWeight.z;
     __syncthreads();
     if (n == 0 && live) {
-        pix3 a = row_ptr(imgOut, strideOut, y)[x];
-        pix3 w = row_ptr(totalWeights, strideOut, y)[x];
+        pix3 a = row_ptr(imgOut, strideOut, y - ay)[x - ax];
+        pix3 w = row_ptr(totalWeights, strideOut, y - ay)[x - ax];
 #pragma unroll
         for (int m = 0; m < NF; m++) {
             a.x += sSum[m][0][lane];
@@ -508,8 +521,8 @@ __global__ void __launch_bounds__(64 * NF)
             w.y += sSum[m][4][lane];
             w.z += sSum[m][5][lane];
         }
-        row_ptr(imgOut, strideOut, y)[x] = a;
-        row_ptr(totalWeights, strideOut, y)[x] = w;
+        row_ptr(imgOut, strideOut, y - ay)[x - ax] = a;
+        row_ptr(totalWeights, strideOut, y - ay)[x - ax] = w;
     }
 }
 
@@ -640,20 +653,24 @@ __device__ __forceinline__ void strip_frame(int tx, int Y, int X0, const uint16_
 
 // Register-only strip kernel: serves every field resolution (FR) without LDS; NF frames add into the
 // accumulators while they sit in registers (one read-modify-write of HBM for both).
-template <int CFA, int FR, int NF>
+// WIN: the columns [wx0, wx1) of a window (colBlock0 = its first 256-pixel column block), accumulators relative to (wx0, wy0)
+template <int CFA, int FR, int NF, bool WIN = false>
 __global__ void __launch_bounds__(256)
     k_accumulate2xStrip(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
-                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBlock0)
+                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBlock0,
+                        int colBlock0, int wx0, int wx1, int wy0)
 {
-    const int tx = blockIdx.x * 64 + threadIdx.x;
+    const int tx = (blockIdx.x + (WIN ? colBlock0 : 0)) * 64 + threadIdx.x;
     const int Y = (blockIdx.y + rowBlock0) * 4 + threadIdx.y;
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     const int X0 = 4 * tx;
     if (X0 < STRIP_MARGIN || X0 >= hrW - STRIP_MARGIN || Y < STRIP_MARGIN || Y >= hrH - STRIP_MARGIN) return;
+    if (WIN && (X0 < wx0 || X0 >= wx1)) return;  // (window edges are multiples of 4 pixels: a strip is in or out)
 
     // accumulators: 4 pixels x 3 channels = 48 contiguous bytes per plane-set
-    float4* pP = (float4*)((char*)imgOut + (size_t)Y * strideOut + (size_t)X0 * 12);
-    float4* pW = (float4*)((char*)totalWeights + (size_t)Y * strideOut + (size_t)X0 * 12);
+    const size_t accOff = WIN ? (size_t)(Y - wy0) * strideOut + (size_t)(X0 - wx0) * 12 : (size_t)Y * strideOut + (size_t)X0 * 12;
+    float4* pP = (float4*)((char*)imgOut + accOff);
+    float4* pW = (float4*)((char*)totalWeights + accOff);
     float accP[12], accW[12];
     {
         const float4 a0 = pP[0], a1 = pP[1], a2 = pP[2];
@@ -729,11 +746,14 @@ __global__ void __launch_bounds__(256)
 
 // FR = HR pixels per kernel-parameter / flow texel: 4 (the Bayer pipeline: fields at LR/2) or 2 (the monochrome pipeline:
 // fields at LR; 130 x 4 texels per tile, four texel columns per strip); the certainty mask is at LR/2 either way.
-template <int CFA, int NF, int FR = 4>
+// WIN (a separate instantiation: the whole-frame kernels keep their code): only the tile columns from tileX0 on are launched,
+// the accumulators hold the window [wx0, wx1) x [wy0, ..) only, and the 16-byte accumulator chunks outside it are neither
+// staged nor written back (window edges are multiples of 16 pixels = 12 chunks: no chunk straddles one).
+template <int CFA, int NF, int FR = 4, bool WIN = false>
 __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR = 2: 41 / 49 KB of LDS, three workgroups per CU
     k_accumulate2xTile(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked,
-                       int tilesX, int tilesY, int tilesPerXcd, int fresh, int tileY0)
+                       int tilesX, int tilesY, int tilesPerXcd, int fresh, int tileY0, int tileX0, int wx0, int wx1, int wy0)
 {
     // XCD-aware tile order (tilesPerXcd > 0, the default since round 4).  Workgroups are dealt round-robin to the 8 XCDs
     // (workgroup i -> XCD i & 7), each with its own L2.  A 256 x 4 tile stages 66 x 3 field texels (kernel parameters, the
@@ -748,7 +768,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     const int pid = (int)blockIdx.x;
     const int tile = tilesPerXcd > 0 ? (pid & 7) * tilesPerXcd + (pid >> 3) : pid;  // tilesPerXcd == 0: launch order (A/B)
     if (tile >= tilesX * tilesY) return;  // whole workgroup (uniform), before any barrier
-    const int bIdYrel = tile / tilesX, bIdX = tile - bIdYrel * tilesX;
+    const int bIdYrel = tile / tilesX, bIdX = tile - bIdYrel * tilesX + (WIN ? tileX0 : 0);
     const int bIdY = bIdYrel + tileY0;  // tileY0: first tile row of this launch's HR row window
     static_assert(FR == 4 || FR == 2, "field resolution");
     constexpr int FC = 256 / FR + 2, FROWS = 4 / FR + 2;  // field texels a tile touches: 66 x 3 (FR = 4), 130 x 4 (FR = 2)
@@ -852,8 +872,12 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     const bool rowLive = Y >= STRIP_MARGIN && Y < hrH - STRIP_MARGIN;
     const size_t rowBytes = (size_t)hrW * 12;
     const size_t segByte = (size_t)bIdX * 3072;
-    char* gP = (char*)imgOut + (size_t)Y * strideOut + segByte;
-    char* gW = (char*)totalWeights + (size_t)Y * strideOut + segByte;
+    // WIN: g = the window row; chunk at frame-row byte gb lives at g + gb - winB0 if winB0 <= gb < winB1
+    const size_t winB0 = WIN ? (size_t)wx0 * 12 : 0, winB1 = WIN ? (size_t)wx1 * 12 : 0;
+    char* gP = WIN ? (char*)imgOut + (size_t)(Y - wy0) * strideOut : (char*)imgOut + (size_t)Y * strideOut + segByte;
+    char* gW = WIN ? (char*)totalWeights + (size_t)(Y - wy0) * strideOut : (char*)totalWeights + (size_t)Y * strideOut + segByte;
+    auto inWin = [&](size_t gb) { return !WIN || (gb >= winB0 && gb + 16 <= winB1); };
+    auto chunk = [&](char* g, size_t off) { return WIN ? g + (segByte + off - winB0) : g + off; };
     // plane-set g (this wave's row segment) -> LDS plane pl: zeroes on the first launch of a burst (the accumulators are
     // defined to be zero and are not read at all), else the asynchronous copy
     auto stage_plane = [&](char* g, int pl) {
@@ -863,8 +887,8 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                 sAcc[pl][ly][j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             } else {
                 const size_t off = (size_t)(j * 64 + lx) * 16;
-                if (segByte + off + 16 <= rowBytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + off),
+                if (segByte + off + 16 <= rowBytes && inWin(segByte + off))
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)chunk(g, off),
                                                      (__attribute__((address_space(3))) void*)&sAcc[pl][ly][j * 64], 16, 0, 0);
             }
         }
@@ -1152,7 +1176,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
             // stream: their (unchanged) chunks are not written back.  A fresh launch defines them (zero) instead.
             const size_t gb = segByte + off;
             const bool sideMargin = gb < (size_t)STRIP_MARGIN * 12 || gb + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
-            if (gb + 16 <= rowBytes && (fresh || !sideMargin)) *(float4*)(g + off) = sAcc[pl][ly][j * 64 + lx];
+            if (gb + 16 <= rowBytes && (fresh || !sideMargin) && inWin(gb)) *(float4*)chunk(g, off) = sAcc[pl][ly][j * 64 + lx];
         }
     };
     using Yes = std::true_type;
@@ -1300,13 +1324,14 @@ __device__ __forceinline__ void strip_pixel4(int X, int Y, int sx, int sy, float
 #define TILE4_WAVES2 3
 #endif
 // (three and four frames per launch: four workgroups per CU by the layout of TILE_LDS_ALIAS, see k_accumulate2xTile)
-template <int CFA, int NF>
+// WIN: as k_accumulate2xTile (window edges are multiples of 16 pixels = 12 chunks of a 512-pixel tile row)
+template <int CFA, int NF, bool WIN = false>
 __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALIAS_ON) ? 4 : TILE4_WAVES2)
     k_accumulate4xTile(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked,
-                       int tilesX, int fresh, int tileY0)
+                       int tilesX, int fresh, int tileY0, int tileX0, int wx0, int wx1, int wy0)
 {
-    const int bIdYrel = (int)blockIdx.x / tilesX, bIdX = (int)blockIdx.x - bIdYrel * tilesX;
+    const int bIdYrel = (int)blockIdx.x / tilesX, bIdX = (int)blockIdx.x - bIdYrel * tilesX + (WIN ? tileX0 : 0);
     const int bIdY = bIdYrel + tileY0;  // tileY0: first tile row of this launch's HR row window
     const int hrW = 4 * dimX, hrH = 4 * dimY;
     const int Y0 = 2 * bIdY;
@@ -1374,8 +1399,11 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
     // accumulator rows of the tile -> LDS (wave (r, h) brings half h of row r), asynchronously
     const size_t rowBytes = (size_t)hrW * 12;
     const size_t segByte = (size_t)bIdX * 6144 + (size_t)h * 3072;
-    char* gP = (char*)imgOut + (size_t)Y * strideOut + segByte;
-    char* gW = (char*)totalWeights + (size_t)Y * strideOut + segByte;
+    const size_t winB0 = WIN ? (size_t)wx0 * 12 : 0, winB1 = WIN ? (size_t)wx1 * 12 : 0;
+    char* gP = WIN ? (char*)imgOut + (size_t)(Y - wy0) * strideOut : (char*)imgOut + (size_t)Y * strideOut + segByte;
+    char* gW = WIN ? (char*)totalWeights + (size_t)(Y - wy0) * strideOut : (char*)totalWeights + (size_t)Y * strideOut + segByte;
+    auto inWin = [&](size_t gb) { return !WIN || (gb >= winB0 && gb + 16 <= winB1); };
+    auto chunk = [&](char* g, size_t off) { return WIN ? g + (segByte + off - winB0) : g + off; };
     auto stage_plane = [&](char* g, int pl) {
 #pragma unroll
         for (int j = 0; j < 3; j++) {
@@ -1383,8 +1411,8 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
                 sAcc[pl][r][h * 192 + j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             } else {
                 const size_t off = (size_t)(j * 64 + lx) * 16;
-                if (segByte + off + 16 <= rowBytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + off),
+                if (segByte + off + 16 <= rowBytes && inWin(segByte + off))
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)chunk(g, off),
                                                      (__attribute__((address_space(3))) void*)&sAcc[pl][r][h * 192 + j * 64], 16, 0, 0);
             }
         }
@@ -1609,9 +1637,9 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
         const size_t off = (size_t)(j * 64 + lx) * 16;
         const size_t g = segByte + off;  // side-margin chunks: see k_accumulate2xTile
         const bool sideMargin = g < (size_t)STRIP_MARGIN * 12 || g + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
-        if (g + 16 <= rowBytes && (fresh || !sideMargin)) {
-            *(float4*)(gP + off) = sAcc[0][r][h * 192 + j * 64 + lx];
-            *(float4*)(gW + off) = sAcc[1][r][h * 192 + j * 64 + lx];
+        if (g + 16 <= rowBytes && (fresh || !sideMargin) && inWin(g)) {
+            *(float4*)chunk(gP, off) = sAcc[0][r][h * 192 + j * 64 + lx];
+            *(float4*)chunk(gW, off) = sAcc[1][r][h * 192 + j * 64 + lx];
         }
     }
 }
@@ -1637,51 +1665,102 @@ bool tile_kernel_ok_fr2(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
            (dimX % 4) == 0 && (dimY % 4) == 0 && g_strip_use_tile == 1;
 }
 
+// the tile launch of a window: its first tile column (x0 / tileW) and how many it covers (whole frame: 0, all)
+struct WinLaunch {
+    bool on;              // window-relative accumulators (the WIN instantiations)
+    int tileX0, tilesX;   // tile columns of tileW HR pixels
+    int x0, x1, y0;
+};
+WinLaunch win_launch(const HrWindow& w, int hrW, int tileW)
+{
+    WinLaunch l;
+    l.on = w.rel && !(w.x0 == 0 && w.x1 == hrW && w.y0 == 0);
+    l.tileX0 = l.on ? w.x0 / tileW : 0;
+    l.tilesX = (l.on ? mfsr_cdiv(w.x1, tileW) : mfsr_cdiv(hrW, tileW)) - l.tileX0;
+    l.x0 = l.on ? w.x0 : 0;
+    l.x1 = l.on ? w.x1 : hrW;
+    l.y0 = l.on ? w.y0 : 0;
+    return l;
+}
+
 template <int CFA, int NF, int FR = 4>
 void launch_tile(dim3 grid, dim3 block, hipStream_t st, const TileFrames<NF>& fr, pix3* imgOut, pix3* tw, mfsr_tex2d kp,
-                 Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int fresh, int tileY0)
+                 Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int fresh, int tileY0,
+                 const WinLaunch& wl)
 {
     const int tilesX = (int)grid.x, tilesY = (int)grid.y;
+    // (a window: the XCD-aware order is taken over the window's tiles; the order does not change any pixel's bits)
     const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
     // occupancy probe (A/B only): unused dynamic LDS so that fewer workgroups fit a CU
     static const int ldsPad = [] {
         const char* e = getenv("MFSR_TILE_LDS_PAD");
         return e ? atoi(e) : 0;
     }();
-    hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR>), dim3(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY), block, ldsPad, st, fr,
-                       imgOut, tw, kp, glv, lv, dimX, dimY, strideOut, strideMask, cfaPacked, tilesX, tilesY, tilesPerXcd, fresh, tileY0);
+    const dim3 g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
+    if (wl.on)
+        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR, true>), g1, block, ldsPad, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+                           strideOut, strideMask, cfaPacked, tilesX, tilesY, tilesPerXcd, fresh, tileY0, wl.tileX0, wl.x0, wl.x1, wl.y0);
+    else
+        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR>), g1, block, ldsPad, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+                           strideOut, strideMask, cfaPacked, tilesX, tilesY, tilesPerXcd, fresh, tileY0, 0, 0, 0, 0);
+}
+
+template <int CFA, int FR, int NF>
+void launch_strip_regs_fr(dim3 grid, dim3 block, hipStream_t st, const TileFrames<NF>& fr, pix3* imgOut, pix3* tw, mfsr_tex2d kp,
+                          Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBlock0,
+                          const WinLaunch& wl)
+{
+    if (wl.on)
+        hipLaunchKernelGGL((k_accumulate2xStrip<CFA, FR, NF, true>), grid, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+                           strideOut, strideMask, cfaPacked, rowBlock0, wl.tileX0, wl.x0, wl.x1, wl.y0);
+    else
+        hipLaunchKernelGGL((k_accumulate2xStrip<CFA, FR, NF>), grid, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+                           strideOut, strideMask, cfaPacked, rowBlock0, 0, 0, 0, 0);
 }
 
 template <int CFA, int NF>
 void launch_strip_regs(dim3 grid, dim3 block, hipStream_t st, const TileFrames<NF>& fr, pix3* imgOut, pix3* tw, mfsr_tex2d kp,
-                       Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBlock0)
+                       Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBlock0,
+                       const WinLaunch& wl)
 {
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     bool same = true;
     for (int n = 0; n < NF; n++) same = same && kp.width == fr.f[n].shifts.width && kp.height == fr.f[n].shifts.height;
     if (same && kp.width * 4 == hrW && kp.height * 4 == hrH && kp.width >= 4)
-        hipLaunchKernelGGL((k_accumulate2xStrip<CFA, 4, NF>), grid, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
-                           strideOut, strideMask, cfaPacked, rowBlock0);
+        launch_strip_regs_fr<CFA, 4, NF>(grid, block, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY, strideOut, strideMask, cfaPacked,
+                                         rowBlock0, wl);
     else if (same && kp.width * 2 == hrW && kp.height * 2 == hrH && kp.width >= 4)
-        hipLaunchKernelGGL((k_accumulate2xStrip<CFA, 2, NF>), grid, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
-                           strideOut, strideMask, cfaPacked, rowBlock0);
+        launch_strip_regs_fr<CFA, 2, NF>(grid, block, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY, strideOut, strideMask, cfaPacked,
+                                         rowBlock0, wl);
     else
-        hipLaunchKernelGGL((k_accumulate2xStrip<CFA, 0, NF>), grid, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
-                           strideOut, strideMask, cfaPacked, rowBlock0);
+        launch_strip_regs_fr<CFA, 0, NF>(grid, block, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY, strideOut, strideMask, cfaPacked,
+                                         rowBlock0, wl);
+}
+
+// zero HR rows [r0, r1) x the launch's columns of the accumulators (one memset over whole rows when the pitch is the row's
+// size; a 2-D one otherwise, so that the bytes beyond a row -- or beyond a window's row -- are not touched)
+int zero_rows(mfsr_float3* imgOut, mfsr_float3* totalWeights, int strideOut, int r0, int r1, const WinLaunch& wl, hipStream_t st)
+{
+    const size_t rowB = (size_t)(wl.x1 - wl.x0) * 12, rows = (size_t)(r1 - r0);
+    for (int p2 = 0; p2 < 2; p2++) {
+        char* base = (p2 ? (char*)totalWeights : (char*)imgOut) + (size_t)(r0 - wl.y0) * strideOut;
+        const hipError_t e = rowB == (size_t)strideOut ? hipMemsetAsync(base, 0, rows * strideOut, st)
+                                                       : hipMemset2DAsync(base, strideOut, 0, rowB, rows, st);
+        if (e != hipSuccess) return -1;
+    }
+    return 0;
 }
 
 // fresh accumulators: the tile kernels write every row of their window outside the top and bottom margin bands
 // (rows [0, M) and [hrH - M, hrH)); zero the part of those bands that lies inside the window
-int zero_margin_bands(mfsr_float3* imgOut, mfsr_float3* totalWeights, int hrH, int strideOut, int rowBegin, int rowEnd, hipStream_t st)
+int zero_margin_bands(mfsr_float3* imgOut, mfsr_float3* totalWeights, int hrH, int strideOut, int rowBegin, int rowEnd,
+                      const WinLaunch& wl, hipStream_t st)
 {
     const int bands[2][2] = {{0, STRIP_MARGIN}, {hrH - STRIP_MARGIN, hrH}};
     for (int i = 0; i < 2; i++) {
         const int r0 = bands[i][0] > rowBegin ? bands[i][0] : rowBegin, r1 = bands[i][1] < rowEnd ? bands[i][1] : rowEnd;
         if (r1 <= r0) continue;
-        for (int p2 = 0; p2 < 2; p2++) {
-            char* base = p2 ? (char*)totalWeights : (char*)imgOut;
-            if (hipMemsetAsync(base + (size_t)r0 * strideOut, 0, (size_t)(r1 - r0) * strideOut, st) != hipSuccess) return -1;
-        }
+        if (zero_rows(imgOut, totalWeights, strideOut, r0, r1, wl, st) != 0) return -1;
     }
     return 0;
 }
@@ -1713,6 +1792,22 @@ MarginStream* margin_stream()
     return &m;
 }
 
+// the margin pixels of NF frames in one launch: the whole ring, or the part of it inside a window
+template <int NF, int SCALE>
+void launch_margin_n(hipStream_t st, const TileFrames<NF>& fr, pix3* pI, pix3* pT, mfsr_tex2d kp, Levels3 glv, int dimX, int dimY,
+                     int strideOut, int strideMask, int cp, int rowBegin, int rowEnd, const WinLaunch& wl, const MarginRects& mr)
+{
+    const int hrW = SCALE * dimX, hrH = SCALE * dimY, M = STRIP_MARGIN;
+    if (!wl.on) {
+        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
+        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, NF), 0, st, fr, pI, pT, kp, glv, dimX,
+                           dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    } else if (mr.start[4] > 0) {
+        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE, true>), dim3(mfsr_cdiv(mr.start[4], 64)), dim3(64, NF), 0, st, fr, pI, pT, kp,
+                           glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    }
+}
+
 void read_env_once()
 {
     static const bool env_read = [] {
@@ -1738,7 +1833,8 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
-                                       int fresh, int rowBegin, int rowEnd, mfsr_stream_t stream)
+                                       int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
+                                       mfsr_stream_t stream)
 {
     read_env_once();
     if (nFrames < 1 || nFrames > 4) return 0;
@@ -1760,9 +1856,12 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
         lv.invWhite[c] = 1.0f / wl[c];
     }
     const int hrW = 2 * dimX, hrH = 2 * dimY;
-    // HR row window [rowBegin, rowEnd): whole 4-row tile rows (the caller aligns it to 16 rows or the frame's end)
+    // HR row window [rowBegin, rowEnd): whole 4-row tile rows (the caller aligns it to 16 rows or the frame's end); columns
+    // [colBegin, colEnd): the 256-pixel tile columns that meet them
     const int rowBlock0 = rowBegin / 4, rowBlocks = mfsr_cdiv(rowEnd, 4) - rowBlock0;
-    dim3 block(64, 4), grid(mfsr_cdiv(hrW / 4, 64), rowBlocks);
+    const WinLaunch wlc = win_launch(HrWindow{colBegin, rowBegin, colEnd, rowEnd, relative}, hrW, 256);
+    dim3 block(64, 4), grid(wlc.tilesX, rowBlocks);
+    const MarginRects mr = margin_rects(hrW, hrH, STRIP_MARGIN, HrWindow{colBegin, rowBegin, colEnd, rowEnd, relative});
     hipStream_t st = mfsr_s(stream);
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
@@ -1782,11 +1881,9 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
     if (fresh) {
         if (tileFirst) {
             tileFresh = 1;
-            if (zero_margin_bands(imgOut, totalWeights, hrH, strideOut, rowBegin, rowEnd, st) != 0) return -1;
+            if (zero_margin_bands(imgOut, totalWeights, hrH, strideOut, rowBegin, rowEnd, wlc, st) != 0) return -1;
         } else {
-            const size_t off = (size_t)rowBegin * strideOut, bytes = (size_t)(rowEnd - rowBegin) * strideOut;
-            if (hipMemsetAsync((char*)imgOut + off, 0, bytes, st) != hipSuccess) return -1;
-            if (hipMemsetAsync((char*)totalWeights + off, 0, bytes, st) != hipSuccess) return -1;
+            if (zero_rows(imgOut, totalWeights, strideOut, rowBegin, rowEnd, wlc, st) != 0) return -1;
         }
     }
     // margin launches: on the side stream (forked here, joined after the last one) when a tile kernel leads the call
@@ -1796,9 +1893,14 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
     auto launch_margin = [&](int n) {
         const int M = STRIP_MARGIN;
         const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        hipLaunchKernelGGL(k_accumulateMargin<2>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                           (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                           rowBegin, rowEnd);
+        if (!wlc.on)
+            hipLaunchKernelGGL(k_accumulateMargin<2>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
+                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, mr);
+        else if (mr.start[4] > 0)  // only the part of the ring inside the window
+            hipLaunchKernelGGL((k_accumulateMargin<2, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
+                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, mr);
         if (msx && n == nFrames - 1) {
             (void)hipEventRecord(msx->join, msx->stream);
             (void)hipStreamWaitEvent(st, msx->join, 0);
@@ -1814,11 +1916,8 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
             fr.f[n].shifts = shifts[n];
         }
         launch_tile<CFA, NF>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, tileFresh,
-                             rowBlock0);
-        const int M = STRIP_MARGIN;
-        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        hipLaunchKernelGGL((k_accumulateMarginN<NF, 2>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, NF), 0, mst, fr, pI, pT, kernelParam, glv,
-                           dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd);
+                             rowBlock0, wlc);
+        launch_margin_n<NF, 2>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
         if (msx) {
             (void)hipEventRecord(msx->join, msx->stream);
             (void)hipStreamWaitEvent(st, msx->join, 0);
@@ -1834,15 +1933,12 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
                 fr.f[n].shifts = shifts[n];
             }
             launch_tile<kMono, NF, 2>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, tileFresh,
-                                      rowBlock0);
+                                      rowBlock0, wlc);
             if (NF == 1) {
                 launch_margin(0);
                 return;
             }
-            const int M = STRIP_MARGIN;
-            const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-            hipLaunchKernelGGL((k_accumulateMarginN<NF, 2>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, NF), 0, mst, fr, pI, pT, kernelParam, glv,
-                               dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd);
+            launch_margin_n<NF, 2>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
             if (msx) {
                 (void)hipEventRecord(msx->join, msx->stream);
                 (void)hipStreamWaitEvent(st, msx->join, 0);
@@ -1867,7 +1963,7 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
                 fr.f[n].shifts = shifts[n];                                                                            \
             }                                                                                                          \
             launch_strip_regs<pack_cfa(a, b, c, d), 2>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,  \
-                                                       strideOut, strideMask, cp, rowBlock0);                                    \
+                                                       strideOut, strideMask, cp, rowBlock0, wlc);                                \
             launch_margin(0);                                                                                          \
             launch_margin(1);                                                                                          \
         } else {                                                                                                       \
@@ -1877,10 +1973,10 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
             fr.f[0].shifts = shifts[0];                                                                                \
             if (tile_kernel_ok(kernelParam, shifts[0], dimX, dimY))                                                    \
                 launch_tile<pack_cfa(a, b, c, d), 1>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,    \
-                                                     strideOut, strideMask, cp, tileFresh, rowBlock0);                           \
+                                                     strideOut, strideMask, cp, tileFresh, rowBlock0, wlc);                       \
             else                                                                                                       \
                 launch_strip_regs<pack_cfa(a, b, c, d), 1>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX,    \
-                                                           dimY, strideOut, strideMask, cp, rowBlock0);                           \
+                                                           dimY, strideOut, strideMask, cp, rowBlock0, wlc);                       \
             launch_margin(0);                                                                                          \
         }                                                                                                              \
         return 1;
@@ -1902,7 +1998,8 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
-                                      int fresh, int rowBegin, int rowEnd, mfsr_stream_t stream)
+                                      int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
+                                      mfsr_stream_t stream)
 {
     read_env_once();
     if (nFrames < 1 || nFrames > 4 || !g_strip_use_tile) return 0;
@@ -1931,12 +2028,14 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
     const int cp = mfsr_cfa_packed();
-    // HR row window [rowBegin, rowEnd): whole 2-row tile rows
+    // HR row window [rowBegin, rowEnd): whole 2-row tile rows; columns [colBegin, colEnd): the 512-pixel tile columns that meet them
     const int tileY0 = rowBegin / 2;
-    const int tilesX = mfsr_cdiv(hrW, 512), tilesY = mfsr_cdiv(rowEnd, 2) - tileY0;
+    const WinLaunch wlc = win_launch(HrWindow{colBegin, rowBegin, colEnd, rowEnd, relative}, hrW, 512);
+    const MarginRects mr = margin_rects(hrW, hrH, STRIP_MARGIN, HrWindow{colBegin, rowBegin, colEnd, rowEnd, relative});
+    const int tilesX = wlc.tilesX, tilesY = mfsr_cdiv(rowEnd, 2) - tileY0;
     const dim3 block(64, 4), grid(tilesX * tilesY);
     if (fresh) {  // the top and bottom margin bands are the only rows the tile kernel does not write
-        if (zero_margin_bands(imgOut, totalWeights, hrH, strideOut, rowBegin, rowEnd, st) != 0) return -1;
+        if (zero_margin_bands(imgOut, totalWeights, hrH, strideOut, rowBegin, rowEnd, wlc, st) != 0) return -1;
     }
     MarginStream* msx = (g_margin_overlap && !fresh) ? margin_stream() : nullptr;
     if (msx && (hipEventRecord(msx->fork, st) != hipSuccess || hipStreamWaitEvent(msx->stream, msx->fork, 0) != hipSuccess)) msx = nullptr;
@@ -1944,9 +2043,14 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
     auto launch_margin = [&](int n) {
         const int M = STRIP_MARGIN;
         const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        hipLaunchKernelGGL(k_accumulateMargin<4>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                           (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                           rowBegin, rowEnd);
+        if (!wlc.on)
+            hipLaunchKernelGGL(k_accumulateMargin<4>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
+                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, mr);
+        else if (mr.start[4] > 0)
+            hipLaunchKernelGGL((k_accumulateMargin<4, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
+                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, mr);
         if (msx && n == nFrames - 1) {
             (void)hipEventRecord(msx->join, msx->stream);
             (void)hipStreamWaitEvent(st, msx->join, 0);
@@ -1961,16 +2065,17 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
             fr.f[n].mask = (const float4*)certaintyMask[n];
             fr.f[n].shifts = shifts[n];
         }
-        hipLaunchKernelGGL((k_accumulate4xTile<CFA, NF>), grid, block, 0, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut,
-                           strideMask, cp, tilesX, fresh ? 1 : 0, tileY0);
+        if (wlc.on)
+            hipLaunchKernelGGL((k_accumulate4xTile<CFA, NF, true>), grid, block, 0, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,
+                               strideOut, strideMask, cp, tilesX, fresh ? 1 : 0, tileY0, wlc.tileX0, wlc.x0, wlc.x1, wlc.y0);
+        else
+            hipLaunchKernelGGL((k_accumulate4xTile<CFA, NF>), grid, block, 0, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut,
+                               strideMask, cp, tilesX, fresh ? 1 : 0, tileY0, 0, 0, 0, 0);
         if (NF == 1) {
             launch_margin(0);
             return;
         }
-        const int M = STRIP_MARGIN;
-        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        hipLaunchKernelGGL((k_accumulateMarginN<NF, 4>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, NF), 0, mst, fr, pI, pT, kernelParam, glv,
-                           dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd);
+        launch_margin_n<NF, 4>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
         if (msx) {
             (void)hipEventRecord(msx->join, msx->stream);
             (void)hipStreamWaitEvent(st, msx->join, 0);

@@ -44,6 +44,18 @@ static inline int mfsr_launch_status(const char* what)
 }
 
 static inline hipStream_t mfsr_s(mfsr_stream_t s) { return (hipStream_t)s; }
+
+// an HR output window [x0, x0+w) x [y0, y0+h) of an hrW x hrH grid the fuse kernels take (host only): origin on the 16-pixel
+// grid, sides multiples of 16 unless they reach the frame's right / bottom edge, inside the frame, not empty
+static inline bool mfsr_window_ok(int hrW, int hrH, int x0, int y0, int w, int h)
+{
+    if (hrW <= 0 || hrH <= 0 || x0 < 0 || y0 < 0 || w <= 0 || h <= 0) return false;
+    if ((x0 % 16) != 0 || (y0 % 16) != 0) return false;
+    if ((long long)x0 + w > hrW || (long long)y0 + h > hrH) return false;
+    if ((w % 16) != 0 && x0 + w != hrW) return false;
+    if ((h % 16) != 0 && y0 + h != hrH) return false;
+    return true;
+}
 static inline unsigned mfsr_cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 // ---- CFA pattern: packed 4 x 8 bit, [y%2][x%2] -> bits ((y&1)*2+(x&1))*8 -----

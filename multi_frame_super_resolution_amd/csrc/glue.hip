@@ -583,7 +583,7 @@ __global__ void __launch_bounds__(256)
     k_finishFused(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
                   const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
                   pix3* __restrict__ outImg, int outPitch, uint16_t* __restrict__ out16, int width, int height,
-                  float threshold, int applyGamma, float maxOut, int rowOffset, int fullHeight)
+                  float threshold, int applyGamma, float maxOut, int rowOffset, int fullHeight, int colOffset, int fullWidth)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y * blockDim.y + threadIdx.y;
@@ -594,7 +594,8 @@ __global__ void __launch_bounds__(256)
     // ApplyWeighting reads the fallback only where a weight is under the threshold (kernel.cu:444-462): the resample (12
     // loads, two divisions, the bilinear mix: 40 % of this kernel's instructions) is skipped by the waves that need none
     if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
-        const float u = u0 + (u1 - u0) * (((float)x + 0.5f) / (float)width);
+        // (column x + colOffset of a fullWidth-column image likewise: a window's finish)
+        const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
         // row y of this launch is row y + rowOffset of a fullHeight-row image: the same float expression as the whole-image
         // launch evaluates for that row, so a stripe-wise finish is bit-identical to the whole one
         const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
@@ -617,6 +618,28 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// the window [colOffset, colOffset + width) x [rowOffset, rowOffset + height) of a fullWidth x fullHeight image whose fallback
+// window is (u0..u1, v0..v1); the image pointers are those of the window's first pixel
+extern "C" int mfsr_finishFusedWindow(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgPitch,
+                                      const mfsr_float3* fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0,
+                                      float v1, mfsr_float3* outImg, int outPitch, uint16_t* out16, int width, int height,
+                                      float threshold, int applyGamma, float maxOut, int colOffset, int rowOffset, int fullWidth,
+                                      int fullHeight, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(finalImg && weight && (outImg || out16) && width > 0 && height > 0);
+    MFSR_REQUIRE((long long)imgPitch >= 12LL * width && (imgPitch & 3) == 0);
+    if (outImg) MFSR_REQUIRE((long long)outPitch >= 12LL * width && (outPitch & 3) == 0);
+    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbPitch >= 12LL * fbW && (fbPitch & 3) == 0);
+    MFSR_REQUIRE(maxOut > 0 && maxOut <= 65535.0f);
+    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + height);
+    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + width);
+    dim3 block(64, 4), grid(mfsr_cdiv(width, 64), mfsr_cdiv(height, 4));
+    hipLaunchKernelGGL(k_finishFused, grid, block, 0, mfsr_s(stream), (const pix3*)finalImg, (const pix3*)weight, imgPitch,
+                       (const pix3*)fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outPitch, out16, width,
+                       height, threshold, applyGamma, maxOut, rowOffset, fullHeight, colOffset, fullWidth);
+    return mfsr_launch_status("finishFused");
+}
+
 // rows [rowOffset, rowOffset + height) of a fullHeight-row image whose fallback window is (u0..u1, v0..v1); the image
 // pointers are those of the first row of the stripe
 extern "C" int mfsr_finishFusedRows(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgPitch,
@@ -625,17 +648,8 @@ extern "C" int mfsr_finishFusedRows(const mfsr_float3* finalImg, const mfsr_floa
                                     float threshold, int applyGamma, float maxOut, int rowOffset, int fullHeight,
                                     mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out16) && width > 0 && height > 0);
-    MFSR_REQUIRE((long long)imgPitch >= 12LL * width && (imgPitch & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outPitch >= 12LL * width && (outPitch & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbPitch >= 12LL * fbW && (fbPitch & 3) == 0);
-    MFSR_REQUIRE(maxOut > 0 && maxOut <= 65535.0f);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + height);
-    dim3 block(64, 4), grid(mfsr_cdiv(width, 64), mfsr_cdiv(height, 4));
-    hipLaunchKernelGGL(k_finishFused, grid, block, 0, mfsr_s(stream), (const pix3*)finalImg, (const pix3*)weight, imgPitch,
-                       (const pix3*)fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outPitch, out16, width,
-                       height, threshold, applyGamma, maxOut, rowOffset, fullHeight);
-    return mfsr_launch_status("finishFused");
+    return mfsr_finishFusedWindow(finalImg, weight, imgPitch, fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, outImg, outPitch, out16,
+                                  width, height, threshold, applyGamma, maxOut, 0, rowOffset, width, fullHeight, stream);
 }
 
 extern "C" int mfsr_finishFused(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgPitch,

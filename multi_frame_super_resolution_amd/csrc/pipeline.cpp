@@ -354,6 +354,12 @@ struct mfsr_burst {
     // joint mode (stage C): tile shifts of the frame being aligned come from the minimiser instead of the tracker
     const Img* givenShifts;
     std::vector<float> jointHost;  // host staging of the joint mode's design matrix / pointer table (must outlive the copies)
+    // zoom window (mfsr_burst_set_window): the HR rectangle the fuse / finish work on, window-sized buffers; `win` is in
+    // effect, `winNext` is adopted by the next set_reference (on = false: the whole frame, whole-frame buffers)
+    struct Window {
+        bool on = false;
+        int x0 = 0, y0 = 0, w = 0, h = 0;
+    } win, winNext;
     // optional per-launch timing of the accumulate kernel (bench.py roofline leg)
     bool timing;
     int nEvents;
@@ -367,6 +373,31 @@ struct mfsr_burst {
     } while (0)
 
 static int flush_pending(mfsr_burst* b, mfsr_stream_t stream, bool materializeFresh = true);
+
+// extent of the burst's output (the window or the whole HR grid) and the bytes of one accumulator plane-set of it
+static int out_w(const mfsr_burst* b) { return b->win.on ? b->win.w : b->L.hrW; }
+static int out_h(const mfsr_burst* b) { return b->win.on ? b->win.h : b->L.hrH; }
+static size_t acc_bytes(const mfsr_burst* b) { return (size_t)12 * out_w(b) * out_h(b); }
+
+// stage G of n frames onto the burst's accumulators, output rows [r0, r1) of the burst's output (the window's rows when one is
+// set; the pointers are the accumulators' first pixel either way)
+static int fuse_group(mfsr_burst* b, int n, const uint16_t* const* raws, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+                      const mfsr_float4* const* masks, const mfsr_tex2d* flows, int maskPitch, int fresh, int r0, int r1,
+                      mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
+    const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
+    if (!b->win.on)
+        return mfsr_accumulateSuperResFullRows(n, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), flows, white, black, L.W, L.H,
+                                               c.scale, 12 * L.hrW, maskPitch, fresh, r0, r1, stream);
+    const int pitch = 12 * b->win.w;
+    const size_t off = (size_t)r0 * pitch;
+    return mfsr_accumulateSuperResFullWindow(n, raws, (mfsr_float3*)((char*)imgOut + off), (mfsr_float3*)((char*)totalWeights + off),
+                                             masks, as_tex(L.kparam4), flows, white, black, L.W, L.H, c.scale, pitch, maskPitch, fresh,
+                                             b->win.x0, b->win.y0 + r0, b->win.w, r1 - r0, stream);
+}
 
 
 extern "C" int mfsr_config_default(mfsr_config* cfg, int width, int height, int frames, int scale, int mono)
@@ -660,6 +691,13 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     const mfsr_config& c = b->cfg;
     Layout& L = b->L;
     MFSR_REQUIRE(hrRow0 >= 0 && hrRow1 > hrRow0 && hrRow1 <= L.hrH);
+    // a zoom window set since the last reference takes effect here: the products below are made for its rows
+    MFSR_REQUIRE(!b->winNext.on || (hrRow0 == 0 && hrRow1 == L.hrH));  // (a window is not combined with row stripes)
+    b->win = b->winNext;
+    if (b->win.on) {
+        hrRow0 = b->win.y0;
+        hrRow1 = b->win.y0 + b->win.h;
+    }
     const bool whole = (hrRow0 == 0 && hrRow1 == L.hrH) || !c.fused;  // (the unfused chain always makes whole images)
     TRY(wait_uploads(b, stream));
     if (!b->refPrepared) TRY(prepare_frame(b, rawRef, L.refHalf, L.refPyr, stream));
@@ -770,6 +808,49 @@ extern "C" int mfsr_burst_set_reference_rows(mfsr_burst* b, const uint16_t* rawR
     return set_reference_impl(b, rawRef, hrRow0, hrRow1, stream);
 }
 
+// ---- zoom windows ---------------------------------------------------------------------------------------------------------
+extern "C" int mfsr_window_check(const mfsr_config* cfg, int x0, int y0, int w, int h)
+{
+    MFSR_REQUIRE(cfg != nullptr);
+    TRY(validate(cfg));
+    const int hrW = cfg->width * cfg->scale, hrH = cfg->height * cfg->scale;
+    if (x0 == 0 && y0 == 0 && ((w == 0 && h == 0) || (w == hrW && h == hrH))) return MFSR_OK;  // the whole frame
+    if (!mfsr_window_ok(hrW, hrH, x0, y0, w, h)) return MFSR_E_INVALID;
+    if (!cfg->fused) return MFSR_E_UNSUPPORTED;  // (the unfused chain has no window kernels)
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_set_window(mfsr_burst* b, int x0, int y0, int w, int h)
+{
+    MFSR_REQUIRE(b != nullptr);
+    const int rc = mfsr_window_check(&b->cfg, x0, y0, w, h);
+    if (rc != MFSR_OK) return rc;
+    // between bursts only: a waiting frame would be fused into the other geometry
+    if (b->pend.n > 0 || b->heldHas) {
+        fprintf(stderr, "mfsr: mfsr_burst_set_window with frames pending (flush or finish the burst first)\n");
+        return MFSR_E_INVALID;
+    }
+    const Layout& L = b->L;
+    const bool whole = (x0 == 0 && y0 == 0 && w == 0 && h == 0) || (x0 == 0 && y0 == 0 && w == L.hrW && h == L.hrH);
+    b->winNext.on = !whole;
+    b->winNext.x0 = whole ? 0 : x0;
+    b->winNext.y0 = whole ? 0 : y0;
+    b->winNext.w = whole ? 0 : w;
+    b->winNext.h = whole ? 0 : h;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_get_window(const mfsr_burst* b, int* x0, int* y0, int* w, int* h)
+{
+    MFSR_REQUIRE(b && x0 && y0 && w && h);
+    const mfsr_burst::Window& v = b->winNext;
+    *x0 = v.on ? v.x0 : 0;
+    *y0 = v.on ? v.y0 : 0;
+    *w = v.on ? v.w : b->L.hrW;
+    *h = v.on ? v.h : b->L.hrH;
+    return MFSR_OK;
+}
+
 // B: coarse -> fine tile tracking of the moved pyramid against the reference
 static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream_t stream)
 {
@@ -870,7 +951,6 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
     TRY(align_deferred(b, callerStream));  // frames of the group that were waiting for their batch
     TRY(wait_uploads(b, callerStream));    // (a reference frame of the group is read by the fuse only)
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
     const mfsr_burst::Pending p = b->pend;
     b->pend.n = 0;
     const int n = p.n;
@@ -883,9 +963,6 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
         stream = (mfsr_stream_t)b->fuseStream;
         for (int i = 0; i < n; i++) MFSR_HIP_TRY(hipStreamWaitEvent(b->fuseStream, b->evAligned[p.slot[i]], 0));
     }
-    const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
-    const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
-    const int strideOut = 12 * L.hrW;
     TRY(mfsr_set_cfa_pattern(c.cfa));
     const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
     if (timed) {
@@ -905,13 +982,12 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
         const int freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
         if (b->fresh.has && !freshNow) {
             // begin(A, W) followed by a fuse into other accumulators: A and W still owe their zeroes
-            const size_t bytes = (size_t)12 * L.hrW * L.hrH;
+            const size_t bytes = acc_bytes(b);
             MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
             MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
         }
         b->fresh.has = false;
-        TRY(mfsr_accumulateSuperResFullN(n, p.raw, imgOut, totalWeights, masks, as_tex(L.kparam4), flows, white, black, L.W, L.H,
-                                         c.scale, strideOut, p.mask[0]->pitch, freshNow, stream));
+        TRY(fuse_group(b, n, p.raw, imgOut, totalWeights, masks, flows, p.mask[0]->pitch, freshNow, 0, out_h(b), stream));
     }
     if (timed) {
         MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
@@ -962,7 +1038,7 @@ static int flush_pending(mfsr_burst* b, mfsr_stream_t stream, bool materializeFr
 {
     if (materializeFresh && b->fresh.has && b->pend.n == 0 && !b->heldHas) {
         // mfsr_burst_begin with no frame fused since: the accumulators must read as zero
-        const size_t bytes = (size_t)12 * b->L.hrW * b->L.hrH;
+        const size_t bytes = acc_bytes(b);
         MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
         MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
         b->fresh.has = false;
@@ -1503,7 +1579,7 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
                                     mfsr_stream_t stream)
 {
     MFSR_REQUIRE(b && raws && flows && masks && imgOut && totalWeights && nFrames >= 1 && nFrames <= MFSR_MAX_FUSE_GROUP);
-    MFSR_REQUIRE(b->haveRef);
+    MFSR_REQUIRE(b->haveRef && !b->win.on);  // (row stripes of whole-frame accumulators)
     TRY(wait_ref_products(b, stream));
     const mfsr_config& c = b->cfg;
     Layout& L = b->L;
@@ -1597,7 +1673,12 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     TRY(flush_pending(b, stream));
     const mfsr_config& c = b->cfg;
     Layout& L = b->L;
-    const int pitch = 12 * L.hrW;
+    const int pitch = 12 * out_w(b);
+    if (c.fused && b->win.on) {
+        return mfsr_finishFusedWindow(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
+                                      0.0f, 1.0f, 0.0f, 1.0f, outImg, pitch, out16, b->win.w, b->win.h, c.weightThreshold,
+                                      c.applyGamma, 65535.0f, b->win.x0, b->win.y0, L.hrW, L.hrH, stream);
+    }
     if (c.fused) {
         return mfsr_finishFused(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
                                 0.0f, 1.0f, 0.0f, 1.0f, outImg, pitch, out16, L.hrW, L.hrH, c.weightThreshold,
@@ -1623,6 +1704,7 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     const mfsr_config& c = b->cfg;
     Layout& L = b->L;
     MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
+    MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     TRY(flush_pending(b, stream));
     const int pitch = 12 * L.hrW;
     const size_t off = (size_t)row0 * pitch;
@@ -1803,7 +1885,8 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // (only where the image is small against the burst -- x2: 199 MB down for 265 MB up.  At x4 the download, 796 MB, is as
     // long as the burst's compute: it has to start with the first band, or the NEXT burst's finish waits for it to leave
     // out16Dev: 18.1 instead of 17.0 ms per burst with two bands)
-    const double outBytes = (double)L.hrW * L.hrH * 6.0, inBytes = (double)L.W * L.H * 2.0 * c.frames;
+    const int oW = out_w(b), oH = out_h(b);  // the window's extent when one is set
+    const double outBytes = (double)oW * oH * 6.0, inBytes = (double)L.W * L.H * 2.0 * c.frames;
     if (b->hostBusy && nBandsBusy >= 1 && nBandsBusy < nBands && outBytes <= 1.5 * inBytes) nBands = nBandsBusy;
     bool heldGroup = b->pend.n > 0 && b->pend.imgOut == imgOut && b->pend.totalWeights == totalWeights && c.fused;
     if (b->heldHas && !(heldGroup && b->held.imgOut == imgOut && b->held.totalWeights == totalWeights)) {
@@ -1811,12 +1894,12 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         heldGroup = false;
     }
     if (!heldGroup) TRY(flush_pending(b, stream));  // (another accumulator pair, or the unfused chain: nothing to pipeline)
-    const size_t rowBytes = (size_t)L.hrW * 6;
+    const size_t rowBytes = (size_t)oW * 6;
     if (nBands == 1 && !heldGroup) {
         TRY(mfsr_burst_finish(b, imgOut, totalWeights, nullptr, out16Dev, stream));
         MFSR_HIP_TRY(hipEventRecord(b->evFinished, mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evFinished, 0));
-        MFSR_HIP_TRY(hipMemcpy2DAsync(out16Host, rowBytes, out16Dev, rowBytes, rowBytes, (size_t)L.hrH, hipMemcpyDeviceToHost,
+        MFSR_HIP_TRY(hipMemcpy2DAsync(out16Host, rowBytes, out16Dev, rowBytes, rowBytes, (size_t)oH, hipMemcpyDeviceToHost,
                                       b->downStream));
         MFSR_HIP_TRY(hipEventRecord(b->evDown, b->downStream));
         b->downRecorded = true;
@@ -1837,20 +1920,19 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         TRY(join_fuse(b, stream));  // the earlier groups' launches ran on the burst's own stream
         freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
         if (b->fresh.has && !freshNow) {
-            const size_t bytes = (size_t)12 * L.hrW * L.hrH;
+            const size_t bytes = acc_bytes(b);
             MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
             MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
         }
         b->fresh.has = false;
     }
-    const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
-    const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
-    const int tileRows = (L.hrH + 15) / 16;
+    // bands of output rows (window rows when a window is set: y0 is a multiple of 16, so are the bands' HR rows)
+    const int tileRows = (oH + 15) / 16;
     if (nBands > tileRows) nBands = tileRows;
     for (int i = 0; i < nBands; i++) {
         const int r0 = (int)((long long)tileRows * i / nBands) * 16;
         int r1 = (int)((long long)tileRows * (i + 1) / nBands) * 16;
-        if (r1 > L.hrH || i == nBands - 1) r1 = L.hrH;
+        if (r1 > oH || i == nBands - 1) r1 = oH;
         if (r1 <= r0) continue;
         if (heldGroup) {
             const mfsr_burst::Pending* gs[2] = {&p0, &p};
@@ -1864,17 +1946,17 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
                     masks[k] = (const mfsr_float4*)q.mask[k]->ptr;
                     flows[k] = as_tex(*q.flow[k]);
                 }
-                TRY(mfsr_accumulateSuperResFullRows(q.n, q.raw, const_cast<mfsr_float3*>(imgOut), const_cast<mfsr_float3*>(totalWeights),
-                                                    masks, as_tex(L.kparam4), flows, white, black, L.W, L.H, c.scale, 12 * L.hrW,
-                                                    q.mask[0]->pitch, fresh, r0, r1, stream));
+                TRY(fuse_group(b, q.n, q.raw, const_cast<mfsr_float3*>(imgOut), const_cast<mfsr_float3*>(totalWeights), masks, flows,
+                               q.mask[0]->pitch, fresh, r0, r1, stream));
                 fresh = 0;
             }
         }
-        const size_t off = (size_t)r0 * 12 * L.hrW;
-        TRY(mfsr_finishFusedRows((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                 12 * L.hrW, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                 nullptr, 12 * L.hrW, out16Dev + (size_t)r0 * L.hrW * 3, L.hrW, r1 - r0, c.weightThreshold,
-                                 c.applyGamma, 65535.0f, r0, L.hrH, stream));
+        const size_t off = (size_t)r0 * 12 * oW;
+        const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+        TRY(mfsr_finishFusedWindow((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                                   12 * oW, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                   nullptr, 12 * oW, out16Dev + (size_t)r0 * oW * 3, oW, r1 - r0, c.weightThreshold,
+                                   c.applyGamma, 65535.0f, x0, y0 + r0, L.hrW, L.hrH, stream));
         if (!b->evBand[i]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[i], hipEventDisableTiming));
         MFSR_HIP_TRY(hipEventRecord(b->evBand[i], mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[i], 0));
@@ -2210,6 +2292,13 @@ extern "C" int mfsr_stream_drain(mfsr_stream* s, mfsr_float3* outImg, uint16_t* 
     s->produced = j + 1;
     *produced = j;
     return MFSR_OK;
+}
+
+extern "C" int mfsr_stream_set_window(mfsr_stream* s, int x0, int y0, int w, int h)
+{
+    MFSR_REQUIRE(s != nullptr);
+    MFSR_REQUIRE(s->pushed == 0);  // before the first push or after mfsr_stream_reset
+    return mfsr_burst_set_window(s->b, x0, y0, w, h);  // every output's set_reference adopts it
 }
 
 extern "C" int mfsr_stream_reset(mfsr_stream* s)

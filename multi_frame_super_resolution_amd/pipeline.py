@@ -8,7 +8,7 @@ library.  No CPU fallback: constructing a pipeline without a HIP device raises.
 from __future__ import annotations
 
 import ctypes
-from typing import Iterable, Optional, Sequence
+from typing import Iterable, Optional, Sequence, Tuple
 
 import torch
 
@@ -21,15 +21,66 @@ def default_config(width: int, height: int, frames: int, scale: int = 2, mono: b
     return cfg
 
 
+WINDOW_GRID = 16  # zoom windows start on this HR grid and span multiples of it (or reach the frame's edge)
+
+
+def align_window(cfg: capi.Config, x: int, y: int, w: int, h: int) -> Tuple[int, int, int, int]:
+    """Smallest window the kernels take (mfsr_window_check) that covers the HR rectangle [x, x+w) x [y, y+h), clipped to
+    the frame: the origin rounded down to the 16-pixel grid, the far edges rounded up to it or to the frame's edge.
+    Pure Python (no device)."""
+    hr_w, hr_h = cfg.width * cfg.scale, cfg.height * cfg.scale
+    if w <= 0 or h <= 0:
+        raise ValueError("window must not be empty")
+    x1, y1 = min(x + w, hr_w), min(y + h, hr_h)
+    x, y = max(x, 0), max(y, 0)
+    if x >= x1 or y >= y1:
+        raise ValueError(f"window ({x}, {y}, {w}, {h}) lies outside the {hr_w}x{hr_h} output")
+    g = WINDOW_GRID
+    ax, ay = x // g * g, y // g * g
+    ax1, ay1 = min(-(-x1 // g) * g, hr_w), min(-(-y1 // g) * g, hr_h)
+    return ax, ay, ax1 - ax, ay1 - ay
+
+
+class _Window:
+    """A requested HR rectangle, the aligned window the library works on, and the crop of it the caller asked for."""
+
+    def __init__(self, cfg: capi.Config, window: Optional[Sequence[int]]):
+        hr_w, hr_h = cfg.width * cfg.scale, cfg.height * cfg.scale
+        if window is None:
+            self.aligned = (0, 0, hr_w, hr_h)
+            self.crop = (slice(None), slice(None))
+            self.on = False
+            return
+        x, y, w, h = (int(v) for v in window)
+        self.aligned = align_window(cfg, x, y, w, h)
+        ax, ay, aw, ah = self.aligned
+        cx, cy = max(x, 0), max(y, 0)
+        cx1, cy1 = min(x + w, hr_w), min(y + h, hr_h)
+        self.crop = (slice(cy - ay, cy1 - ay), slice(cx - ax, cx1 - ax))
+        self.on = self.aligned != (0, 0, hr_w, hr_h)
+
+    def apply(self, setter, handle):
+        if self.on:
+            setter(handle, *self.aligned)
+
+    def __call__(self, img: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        return None if img is None else img[self.crop]
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
 
-    def __init__(self, cfg: capi.Config, device: Optional[torch.device] = None):
+    def __init__(self, cfg: capi.Config, device: Optional[torch.device] = None, window: Optional[Sequence[int]] = None):
+        """window = (x, y, w, h): super-resolve only that rectangle of the HR output (a zoom).  Any rectangle: the library
+        works on the 16-pixel-aligned window around it (``align_window``; ``img_out`` / ``total_weights`` are that size) and
+        ``finish`` / ``process`` / ``process_host`` return exactly the rectangle asked for, bit for bit the same pixels as
+        the whole-frame burst.  Needs cfg.fused = 1."""
         if not torch.cuda.is_available():
             raise RuntimeError("multi_frame_super_resolution_amd needs a HIP device (MI355X); there is no CPU fallback")
         self.L = capi.lib()
         self.cfg = cfg
+        self.window = _Window(cfg, window)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.burst_workspace_bytes(ctypes.byref(cfg))
         if nbytes == 0:
@@ -39,15 +90,17 @@ class BurstPipeline:
             base = self.workspace.data_ptr()
             self._ws_ptr = (base + 255) // 256 * 256
             self.hr_w, self.hr_h = cfg.width * cfg.scale, cfg.height * cfg.scale
-            # accumulators: float3 HR, pitch 12*hrW (caller-owned, RMW across frames,
-            # reference DeBayerKernels.cu:306-307,374-375)
-            self._img_out = torch.zeros(self.hr_h, self.hr_w, 3, dtype=torch.float32, device=self.device)
+            # accumulators: float3 HR (the window's size when one is set), pitch 12*width (caller-owned, RMW across
+            # frames, reference DeBayerKernels.cu:306-307,374-375)
+            out_h, out_w = self.window.aligned[3], self.window.aligned[2]
+            self._img_out = torch.zeros(out_h, out_w, 3, dtype=torch.float32, device=self.device)
             self._total_weights = torch.zeros_like(self._img_out)
             self.out_img = torch.empty_like(self._img_out)
-            self.out16 = torch.empty(self.hr_h, self.hr_w, 3, dtype=torch.int16, device=self.device)
+            self.out16 = torch.empty(out_h, out_w, 3, dtype=torch.int16, device=self.device)
             handle = ctypes.c_void_p()
             self.L.burst_create(ctypes.byref(handle), ctypes.byref(cfg), self._ws_ptr, nbytes)
             self._h = handle
+            self.window.apply(self.L.burst_set_window, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -100,10 +153,11 @@ class BurstPipeline:
                                self._total_weights.data_ptr(), self._stream())
 
     def finish(self, want_float: bool = True, want_u16: bool = True):
+        """(float image, u16 image) of the burst: the whole HR frame, or the rectangle given as ``window``."""
         self.L.burst_finish(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(),
                             self.out_img.data_ptr() if want_float else None,
                             self.out16.data_ptr() if want_u16 else None, self._stream())
-        return (self.out_img if want_float else None), (self.out16 if want_u16 else None)
+        return self.window(self.out_img if want_float else None), self.window(self.out16 if want_u16 else None)
 
     def finish_rows(self, row0: int, rows: int) -> torch.Tensor:
         """Finish only HR rows [row0, row0+rows) (reduce-scatter mode); returns the
@@ -197,7 +251,7 @@ class BurstPipeline:
                 raise ValueError("host frames must be contiguous 16-bit CPU tensors of the configured size")
         if out16_host is None:
             if getattr(self, "_out16_host", None) is None:
-                self._out16_host = torch.empty(self.hr_h, self.hr_w, 3, dtype=torch.int16).pin_memory()
+                self._out16_host = torch.empty_like(self.out16, device="cpu").pin_memory()
             out16_host = self._out16_host
         st = self._stream()
         self.begin_burst()
@@ -212,7 +266,7 @@ class BurstPipeline:
                                         self._total_weights.data_ptr(), st)
         self.L.burst_finish_host(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), self.out16.data_ptr(),
                                  out16_host.data_ptr(), st)
-        return out16_host
+        return self.window(out16_host)
 
     def debug_views(self):
         """(flow, mask, kernel_param, tracking) descriptors of the last add_frame."""
@@ -240,13 +294,16 @@ class FrameStream:
     frame is uploaded and prepared once.  ``host_frames``: frames are pinned CPU tensors, uploaded by the library's
     copy stream."""
 
-    def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False):
+    def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
+                 window: Optional[Sequence[int]] = None):
+        """window: every output is that HR rectangle (see BurstPipeline)."""
         if not torch.cuda.is_available():
             raise RuntimeError("multi_frame_super_resolution_amd needs a HIP device (MI355X); there is no CPU fallback")
         self.L = capi.lib()
         self.cfg = cfg
         self.radius = radius
         self.host_frames = host_frames
+        self.window = _Window(cfg, window)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.stream_workspace_bytes(ctypes.byref(cfg), radius)
         if nbytes == 0:
@@ -255,10 +312,11 @@ class FrameStream:
             self.workspace = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
             base = (self.workspace.data_ptr() + 255) // 256 * 256
             self.hr_w, self.hr_h = cfg.width * cfg.scale, cfg.height * cfg.scale
-            self.out16 = torch.empty(self.hr_h, self.hr_w, 3, dtype=torch.int16, device=self.device)
+            self.out16 = torch.empty(self.window.aligned[3], self.window.aligned[2], 3, dtype=torch.int16, device=self.device)
             h = ctypes.c_void_p()
             self.L.stream_create(ctypes.byref(h), ctypes.byref(cfg), radius, 1 if host_frames else 0, base, nbytes)
             self._h = h
+            self.window.apply(self.L.stream_set_window, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -280,7 +338,7 @@ class FrameStream:
         produced = ctypes.c_longlong(-1)
         self.L.stream_push(self._h, frame.data_ptr(), None, self.out16.data_ptr(), ctypes.byref(produced),
                            torch.cuda.current_stream().cuda_stream)
-        return (produced.value, self.out16) if produced.value >= 0 else None
+        return (produced.value, self.window(self.out16)) if produced.value >= 0 else None
 
     def drain(self):
         """End of the stream: yields the outstanding (t, u16 HR image) outputs."""
@@ -289,7 +347,7 @@ class FrameStream:
             self.L.stream_drain(self._h, None, self.out16.data_ptr(), ctypes.byref(produced), torch.cuda.current_stream().cuda_stream)
             if produced.value < 0:
                 return
-            yield produced.value, self.out16
+            yield produced.value, self.window(self.out16)
 
 
 def view_as_tensor(t: capi.Tex2D, channels: int, device) -> torch.Tensor:
