@@ -159,6 +159,28 @@ int main(int argc, char** argv)
 
     int gpus = 1;
     if (const char* e = getenv("MFSR_GPUS")) gpus = atoi(e);
+    int selectCandidates = -1;  // MFSR_SELECT: < 0 = off (frame 0 is the reference, every frame is fused)
+    float keepRatio = 0.0f;
+    if (const char* e = getenv("MFSR_SELECT")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end != '\0' || v < 0 || v > 1000000) {
+            fprintf(stderr, "MFSR_SELECT=%s: a number of candidate frames (0 = all) expected\n", e);
+            return 1;
+        }
+        selectCandidates = (int)v;
+        if (const char* r = getenv("MFSR_KEEP_RATIO")) {
+            keepRatio = strtof(r, &end);
+            if (end == r || *end != '\0') {
+                fprintf(stderr, "MFSR_KEEP_RATIO=%s: a number in [0, 1] expected\n", r);
+                return 1;
+            }
+        }
+    }
+    if (selectCandidates >= 0 && gpus > 1) {
+        fprintf(stderr, "MFSR_SELECT is not supported with MFSR_GPUS > 1 (the multi-GPU burst takes frame 0 as its reference)\n");
+        return 1;
+    }
     if (gpus > 1) {
         // ---- the burst sharded over `gpus` GPUs from this one process ------------------------------------------------
         const bool virt = getenv("MFSR_VIRTUAL_RANKS") && getenv("MFSR_VIRTUAL_RANKS")[0] == '1';
@@ -246,6 +268,24 @@ int main(int argc, char** argv)
     mfsr_burst* b = nullptr;
     MFSR_OK_OR_DIE(mfsr_burst_create(&b, &cfg, ws, wsBytes));
 
+    // MFSR_SELECT: the sharpest frame becomes the reference and frames much softer than it are dropped, chosen once for the
+    // burst before the replays (mfsr_burst_select_frames); the report goes to stderr so that stdout stays the reference's
+    int reference = cfg.reference;
+    std::vector<int> ids;
+    for (int k = 0; k < num_images; k++) ids.push_back(k);
+    if (selectCandidates >= 0) {
+        long long* dsums = nullptr;
+        std::vector<int32_t> keep(num_images);
+        HIP_OK(hipMalloc((void**)&dsums, sizeof(long long) * num_images));
+        MFSR_OK_OR_DIE(mfsr_burst_select_frames(b, num_images, dframes.data(), selectCandidates, keepRatio, dsums, &reference,
+                                                keep.data(), nullptr, nullptr, nullptr));
+        HIP_OK(hipFree(dsums));
+        ids.clear();
+        for (int k = 0; k < num_images; k++)
+            if (keep[k]) ids.push_back(k);
+        fprintf(stderr, "reference %d, kept %d of %d\n", reference, (int)ids.size(), num_images);
+    }
+
     for (int rep = 0; rep < num_times; rep++) {
         if (rep == start_i) {
             HIP_OK(hipDeviceSynchronize());
@@ -253,9 +293,9 @@ int main(int argc, char** argv)
         }
         HIP_OK(hipMemsetAsync(imgOut, 0, accBytes, nullptr));
         HIP_OK(hipMemsetAsync(weights, 0, accBytes, nullptr));
-        MFSR_OK_OR_DIE(mfsr_burst_set_reference(b, dframes[cfg.reference], nullptr));
-        for (int k = 0; k < num_images; k++)
-            MFSR_OK_OR_DIE(mfsr_burst_add_frame(b, dframes[k], k == cfg.reference, (mfsr_float3*)imgOut,
+        MFSR_OK_OR_DIE(mfsr_burst_set_reference(b, dframes[reference], nullptr));
+        for (int k : ids)
+            MFSR_OK_OR_DIE(mfsr_burst_add_frame(b, dframes[k], k == reference, (mfsr_float3*)imgOut,
                                                 (mfsr_float3*)weights, nullptr));
         MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, (mfsr_float3*)outF,
                                          nullptr, nullptr));

@@ -713,6 +713,34 @@ typedef struct {
 int mfsr_burst_process_source(mfsr_burst* b, const mfsr_frame_source* src, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                               mfsr_float3* outImg, uint16_t* out16, int* framesUsed, mfsr_stream_t stream);
 
+/* ---- frame selection: score every frame of a burst by sharpness, take the sharpest as the reference and drop frames much
+ * softer than it (the base-frame choice of the handheld multi-frame SR method).
+ * Score of a raw frame: G(i, j) = raw(2i+ay, 2j+ax) + raw(2i+by, 2j+bx) with (ay, ax), (by, bx) the two quad positions whose
+ * CFA entry is MFSR_GREEN ((0,1) and (1,0) for mono; any other count of greens is invalid), gx / gy its 3x3 Sobel gradients,
+ * S = sum of gx^2 + gy^2 over the half-resolution rectangle rect = {x0, y0, x1, y1}: [x0, x1) x [y0, y1) with
+ * 1 <= x0 < x1 <= width/2 - 1, 1 <= y0 < y1 <= height/2 - 1 and at most 2^23 pixels.  Exact 64-bit integer arithmetic:
+ * bit-for-bit reproducible.
+ * mfsr_frameSharpness: frames = host array of nFrames DEVICE pointers (u16, rows `pitch` bytes apart, width and height even);
+ * sumsDev[0 .. nFrames) (device) := S of each frame (zeroed on the stream first).  Every argument is checked on the host
+ * before any device call (MFSR_E_INVALID).  cfa is ignored (may be NULL) when mono != 0. */
+int mfsr_frameSharpness(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, const int32_t cfa[4],
+                        int mono, const int32_t rect[4], long long* sumsDev, mfsr_stream_t stream);
+/* Host only (no device call).  reference := argmax of sums over frames [0, candidates) (candidates 0 or >= n: all frames;
+ * ties: the lowest index); keep[k] (may be NULL) := 1 iff k == reference or (double)sums[k] >= (double)keepRatio *
+ * (double)sums[reference], else 0.  keepRatio in [0, 1] (0 keeps every frame); anything else, NaN included, is invalid. */
+int mfsr_select_frames(int n, const long long* sums, int candidates, float keepRatio, int* reference, int32_t* keep);
+/* Score the burst's frames (device-resident, dense rows as for mfsr_burst_add_frame; 1 <= nFrames <= cfg.frames; CFA, mono and
+ * size from the burst's config), wait for the stream once and select (mfsr_select_frames).  sumsDev: nFrames device entries
+ * of caller scratch.  Host outputs: reference (required), keep[nFrames], sums[nFrames] and the scored rectangle rect[4]
+ * (each may be NULL).  Scored rectangle: without a zoom window [8, W/2-8) x [8, H/2-8), or [1, W/2-1) x [1, H/2-1) if that
+ * margin leaves nothing; with the window (x, y, w, h) of the next set_reference (mfsr_burst_set_window) at scale s its raw
+ * footprint in half resolution, [floor(x/2s), ceil((x+w)/2s)) and likewise in y, clipped to [1, W/2-1) x [1, H/2-1) (a
+ * footprint that the clip empties becomes the nearest scorable column / row).  Processes nothing: the caller then runs
+ * mfsr_burst_begin / set_reference(frames[reference]) / add_frame(kept frames in index order) / finish. */
+int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16_t* const* frames, int candidates, float keepRatio,
+                             long long* sumsDev, int* reference, int32_t* keep, long long* sums, int32_t rect[4],
+                             mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

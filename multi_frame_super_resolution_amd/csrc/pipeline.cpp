@@ -2037,6 +2037,78 @@ extern "C" int mfsr_burst_process_source(mfsr_burst* b, const mfsr_frame_source*
     return mfsr_burst_finish(b, imgOut, totalWeights, outImg, out16, stream);
 }
 
+// ---- frame selection: sharpness scores (csrc/select.hip) -> reference + kept frames ----------------------
+extern "C" int mfsr_select_frames(int n, const long long* sums, int candidates, float keepRatio, int* reference, int32_t* keep)
+{
+    MFSR_REQUIRE(n >= 1 && sums != nullptr && reference != nullptr && candidates >= 0);
+    MFSR_REQUIRE(keepRatio >= 0.0f && keepRatio <= 1.0f);  // (false for NaN)
+    const int m = (candidates == 0 || candidates >= n) ? n : candidates;
+    int r = 0;
+    for (int k = 1; k < m; k++)
+        if (sums[k] > sums[r]) r = k;  // ties: the lowest index
+    *reference = r;
+    if (keep) {
+        const double bar = (double)keepRatio * (double)sums[r];
+        for (int k = 0; k < n; k++) keep[k] = (k == r || (double)sums[k] >= bar) ? 1 : 0;
+    }
+    return MFSR_OK;
+}
+
+// the half-resolution rectangle mfsr_burst_select_frames scores: the whole frame less a margin, or the footprint of the zoom
+// window the next set_reference adopts
+static void select_rect(const mfsr_burst* b, int32_t r[4])
+{
+    const int hw = b->L.hw, hh = b->L.hh;
+    const mfsr_burst::Window& v = b->winNext;
+    if (!v.on) {
+        const bool margin = hw - 8 > 8 && hh - 8 > 8;
+        const int m = margin ? 8 : 1;
+        r[0] = m;
+        r[1] = m;
+        r[2] = hw - m;
+        r[3] = hh - m;
+        return;
+    }
+    const int s2 = 2 * b->cfg.scale;
+    int lo[2] = {v.x0 / s2, v.y0 / s2};
+    int hi[2] = {(v.x0 + v.w + s2 - 1) / s2, (v.y0 + v.h + s2 - 1) / s2};
+    const int lim[2] = {hw - 1, hh - 1};
+    for (int d = 0; d < 2; d++) {
+        lo[d] = lo[d] < 1 ? 1 : lo[d];
+        hi[d] = hi[d] > lim[d] ? lim[d] : hi[d];
+        if (hi[d] <= lo[d]) {  // the footprint lies in the unscorable ring: its nearest scorable column / row
+            lo[d] = lo[d] > lim[d] - 1 ? lim[d] - 1 : lo[d];
+            hi[d] = lo[d] + 1;
+        }
+    }
+    r[0] = lo[0];
+    r[1] = lo[1];
+    r[2] = hi[0];
+    r[3] = hi[1];
+}
+
+extern "C" int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16_t* const* frames, int candidates, float keepRatio,
+                                        long long* sumsDev, int* reference, int32_t* keep, long long* sums, int32_t rect[4],
+                                        mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && sumsDev && reference);
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= b->cfg.frames);
+    MFSR_REQUIRE(candidates >= 0 && keepRatio >= 0.0f && keepRatio <= 1.0f);
+    const mfsr_config& c = b->cfg;
+    int32_t r[4];
+    select_rect(b, r);
+    TRY(mfsr_frameSharpness(nFrames, frames, 2 * c.width, c.width, c.height, c.cfa, c.mono, r, sumsDev, stream));
+    std::vector<long long> host((size_t)nFrames);
+    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), sumsDev, sizeof(long long) * (size_t)nFrames, hipMemcpyDeviceToHost, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    std::vector<int32_t> k((size_t)nFrames);
+    TRY(mfsr_select_frames(nFrames, host.data(), candidates, keepRatio, reference, k.data()));
+    if (keep) memcpy(keep, k.data(), sizeof(int32_t) * (size_t)nFrames);
+    if (sums) memcpy(sums, host.data(), sizeof(long long) * (size_t)nFrames);
+    if (rect) memcpy(rect, r, sizeof(r));
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2d* mask, mfsr_tex2d* kernelParam,
                                       mfsr_tex2d* tracking)
 {

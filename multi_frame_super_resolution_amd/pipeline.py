@@ -8,6 +8,7 @@ library.  No CPU fallback: constructing a pipeline without a HIP device raises.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import Iterable, Optional, Sequence, Tuple
 
 import torch
@@ -65,6 +66,55 @@ class _Window:
 
     def __call__(self, img: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         return None if img is None else img[self.crop]
+
+
+Selection = namedtuple("Selection", "reference kept sums rect")
+Selection.__doc__ = """What BurstPipeline.process_selected chose: the reference frame, the kept frame indices (index order), the
+sharpness score of every frame (mfsr_frameSharpness) and the half-resolution rectangle (x0, y0, x1, y1) that was scored."""
+
+
+def sharpness_rect(cfg: capi.Config, window: Optional[Sequence[int]] = None) -> Tuple[int, int, int, int]:
+    """The half-resolution rectangle (x0, y0, x1, y1) mfsr_burst_select_frames scores: without a window the frame less an
+    8-pixel margin (1 pixel if 8 leave nothing); with an aligned zoom window (x, y, w, h) its raw footprint, clipped to the
+    scorable part [1, W/2-1) x [1, H/2-1).  Pure Python (no device)."""
+    hw, hh = cfg.width // 2, cfg.height // 2
+    if window is None:
+        m = 8 if hw - 8 > 8 and hh - 8 > 8 else 1
+        return m, m, hw - m, hh - m
+    x, y, w, h = (int(v) for v in window)
+    s2 = 2 * cfg.scale
+    lo, hi, lim = [x // s2, y // s2], [-(-(x + w) // s2), -(-(y + h) // s2)], [hw - 1, hh - 1]
+    for d in range(2):
+        lo[d], hi[d] = max(lo[d], 1), min(hi[d], lim[d])
+        if hi[d] <= lo[d]:
+            lo[d] = min(lo[d], lim[d] - 1)
+            hi[d] = lo[d] + 1
+    return lo[0], lo[1], hi[0], hi[1]
+
+
+def frame_sharpness(frames: Sequence[torch.Tensor], cfg: capi.Config,
+                    rect: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Sharpness score of every frame (mfsr_frameSharpness): an int64 device tensor, exact.  ``frames``: 16-bit [H, W]
+    device tensors of cfg's size, rows contiguous and all with the same row stride (pitched views are fine).  ``rect``:
+    the half-resolution rectangle (x0, y0, x1, y1) to score; None = the whole-frame rule of ``sharpness_rect``."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("frame_sharpness needs at least one frame")
+    dev = frames[0].device
+    pitch = frames[0].stride(0) * 2
+    for f in frames:
+        if (f.device != dev or not f.is_cuda or f.dtype not in (torch.int16, torch.uint16) or f.dim() != 2
+                or tuple(f.shape) != (cfg.height, cfg.width) or f.stride(1) != 1 or f.stride(0) * 2 != pitch):
+            raise ValueError(f"frames must be 16-bit {cfg.height}x{cfg.width} tensors on one HIP device with contiguous rows "
+                             "and one row stride")
+    r = sharpness_rect(cfg) if rect is None else tuple(int(v) for v in rect)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        sums = torch.empty(n, dtype=torch.int64, device=dev)
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+        capi.lib().frameSharpness(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0,
+                                  (ctypes.c_int32 * 4)(*r), sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return sums
 
 
 class BurstPipeline:
@@ -174,6 +224,30 @@ class BurstPipeline:
         ids = range(len(frames)) if frame_ids is None else frame_ids
         for k in ids:
             self.add_frame(frames[k], k == ref)
+        return self.finish()
+
+    def process_selected(self, frames: Sequence[torch.Tensor], candidates: int = 0, keep_ratio: float = 0.0):
+        """Whole burst with the reference chosen by sharpness (mfsr_burst_select_frames): the sharpest of the first
+        ``candidates`` frames (0 = all) is the reference, and only frames scoring at least ``keep_ratio`` times its score
+        are fused.  Then exactly what ``process`` does with that reference and those frames.  With a window the score is
+        taken over the window's footprint.  Returns (float image, u16 image) like ``process``; the choice is left in
+        ``self.selection`` (a ``Selection``)."""
+        n = len(frames)
+        for f in frames:
+            self._check_raw(f)
+        sums_dev = torch.empty(n, dtype=torch.int64, device=self.device)
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+        ref, keep = ctypes.c_int(-1), (ctypes.c_int32 * n)()
+        sums, rect = (ctypes.c_longlong * n)(), (ctypes.c_int32 * 4)()
+        self.L.burst_select_frames(self._h, n, ptrs, int(candidates), float(keep_ratio), sums_dev.data_ptr(), ctypes.byref(ref),
+                                   keep, sums, rect, self._stream())
+        r = ref.value
+        kept = [k for k in range(n) if keep[k]]
+        self.selection = Selection(r, kept, list(sums), tuple(rect))
+        self.begin_burst()
+        self.set_reference(frames[r])
+        for k in kept:
+            self.add_frame(frames[k], k == r)
         return self.finish()
 
     def host_sync(self):
