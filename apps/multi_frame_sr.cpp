@@ -20,6 +20,8 @@
 //     mfsr_dist_group (include/mfsr_dist.h) -- one worker thread per GPU inside the library, alignment sharded over
 //     frames, fuse over HR row stripes, peer copies over xGMI; the u16 result is bit-identical to the 1-GPU burst.
 //     MFSR_VIRTUAL_RANKS=1 puts all n ranks on device 0 (test rehearsal on a one-GPU box).
+//   * MFSR_DEFECTS=1 (with MFSR_DEFECT_THRESHOLD / MFSR_DEFECT_SPREAD / MFSR_DEFECT_VOTES) repairs hot / dead pixels found
+//     by a vote over the burst's frames before anything else; one GPU only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -177,6 +179,40 @@ int main(int argc, char** argv)
             }
         }
     }
+    // MFSR_DEFECTS=1: find the burst's hot / dead pixels by a vote over its frames and repair them in the raw frames first
+    bool defects = false;
+    int defThreshold = (int)whiteLevel / 64, defSpread = 2, defVotes = num_images / 2 + 1;
+    if (defVotes < (3 * num_images + 3) / 4) defVotes = (3 * num_images + 3) / 4;
+    if (defThreshold < 1) defThreshold = 1;
+    if (const char* e = getenv("MFSR_DEFECTS")) {
+        if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0) {
+            fprintf(stderr, "MFSR_DEFECTS=%s: 0 or 1 expected\n", e);
+            return 1;
+        }
+        defects = e[0] == '1';
+        const struct {
+            const char* name;
+            int* value;
+            long lo, hi;
+            const char* what;
+        } vars[3] = {{"MFSR_DEFECT_THRESHOLD", &defThreshold, 0, 65535, "a number in [0, 65535]"},
+                     {"MFSR_DEFECT_SPREAD", &defSpread, 0, 16, "a number in [0, 16]"},
+                     {"MFSR_DEFECT_VOTES", &defVotes, num_images / 2 + 1, num_images, "more than half of the frames, at most all"}};
+        for (const auto& v : vars)
+            if (const char* r = getenv(v.name)) {
+                char* end = nullptr;
+                const long x = strtol(r, &end, 10);
+                if (end == r || *end != '\0' || x < v.lo || x > v.hi) {
+                    fprintf(stderr, "%s=%s: %s expected\n", v.name, r, v.what);
+                    return 1;
+                }
+                *v.value = (int)x;
+            }
+    }
+    if (defects && gpus > 1) {
+        fprintf(stderr, "MFSR_DEFECTS is not supported with MFSR_GPUS > 1 (each rank holds only its own frames)\n");
+        return 1;
+    }
     if (selectCandidates >= 0 && gpus > 1) {
         fprintf(stderr, "MFSR_SELECT is not supported with MFSR_GPUS > 1 (the multi-GPU burst takes frame 0 as its reference)\n");
         return 1;
@@ -267,6 +303,21 @@ int main(int argc, char** argv)
     }
     mfsr_burst* b = nullptr;
     MFSR_OK_OR_DIE(mfsr_burst_create(&b, &cfg, ws, wsBytes));
+
+    // MFSR_DEFECTS: repaired once, in the device frames, before the selection and before the replays
+    // (mfsr_burst_repair_defects); the report goes to stderr so that stdout stays the reference's
+    if (defects) {
+        uint8_t* dmap = nullptr;
+        uint32_t* dcounts = nullptr;
+        uint32_t counts[2] = {0, 0};
+        HIP_OK(hipMalloc((void**)&dmap, (size_t)W * H));
+        HIP_OK(hipMalloc((void**)&dcounts, 2 * sizeof(uint32_t)));
+        MFSR_OK_OR_DIE(mfsr_burst_repair_defects(b, num_images, dframes.data(), defThreshold, defSpread, defVotes, dmap, dcounts,
+                                                 counts, nullptr));
+        HIP_OK(hipFree(dmap));
+        HIP_OK(hipFree(dcounts));
+        fprintf(stderr, "defects: %u hot, %u cold\n", counts[0], counts[1]);
+    }
 
     // MFSR_SELECT: the sharpest frame becomes the reference and frames much softer than it are dropped, chosen once for the
     // burst before the replays (mfsr_burst_select_frames); the report goes to stderr so that stdout stays the reference's

@@ -741,6 +741,36 @@ int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16_t* const* 
                              long long* sumsDev, int* reference, int32_t* keep, long long* sums, int32_t rect[4],
                              mfsr_stream_t stream);
 
+/* ---- defective pixels: hot / dead sensor pixels found by a vote over the frames of a burst, and repaired in the raw domain
+ * before anything else looks at the frames.  A deviation that stays on the same sensor pixel in most
+ * frames of a hand-held burst is the sensor, not the scene.  Exact integer arithmetic: bit-for-bit reproducible.
+ * Let d = 1 for mono, d = 2 for a Bayer mosaic (the same-colour lattice of every quad position).  For pixel (x, y) of a
+ * frame with value v: N8 = the up to eight pixels (x + i*d, y + j*d), i, j in {-1, 0, 1}, not both 0, inside the frame;
+ * hi = max N8, lo = min N8, margin = threshold + (((hi - lo) * spread) >> 2) in 32-bit integers; the frame casts a HOT vote
+ * if v > hi + margin and a COLD vote if v + margin < lo.  map(x, y) = 1 (hot) if the hot votes of all frames >= minVotes,
+ * else 2 (cold) if the cold votes >= minVotes, else 0.
+ * Arguments: 1 <= nFrames <= 64, 0 <= threshold <= 65535, 0 <= spread <= 16, nFrames/2 < minVotes <= nFrames (a pixel
+ * cannot be both), width and height >= 2d+1, pitch >= 2*width and even, mapPitch >= width; everything is checked on the
+ * host before any device call (MFSR_E_INVALID).  frames = host array of nFrames DEVICE pointers (u16, rows `pitch` bytes
+ * apart).
+ * mfsr_detectDefects: mapDev (device, rows mapPitch bytes apart; only the width bytes of a row are written) := the map;
+ * countsDev (device, may be NULL) := {hot pixels, cold pixels} of the map, zeroed on the stream first.  Frames are read only.
+ * mfsr_repairDefects, in place, under ANY map (a camera's calibration map is as good as a detected one): every pixel whose
+ * map entry is not 0 becomes, in each frame, the median of those of its N8 whose own map entry is 0: with n of them sorted
+ * ascending as s, s[n/2] for odd n, (s[n/2-1] + s[n/2] + 1) >> 1 for even n; unchanged for n = 0.  Pixels whose map entry
+ * is 0 are never written (flagged pixels are only written, unflagged ones only read: in place is safe). */
+int mfsr_detectDefects(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, int mono, int threshold,
+                       int spread, int minVotes, uint8_t* mapDev, int mapPitch, uint32_t* countsDev, mfsr_stream_t stream);
+int mfsr_repairDefects(int nFrames, uint16_t* const* frames, int pitch, int width, int height, int mono, const uint8_t* mapDev,
+                       int mapPitch, mfsr_stream_t stream);
+/* Detect and repair the defects of a burst's frames (device-resident, dense rows as for mfsr_burst_add_frame; size and mono
+ * from the burst's config; 1 <= nFrames <= 64), in place.  mapDev: width * height bytes of caller scratch (the dense map, left
+ * there for the caller); countsDev: 2 device entries of caller scratch, required if counts is given; counts (host, may be
+ * NULL) := {hot, cold} after one wait for the stream.  Processes nothing: the caller then runs the usual
+ * begin / set_reference / add_frame / finish, or mfsr_burst_select_frames first (repair goes before selection). */
+int mfsr_burst_repair_defects(mfsr_burst* b, int nFrames, uint16_t* const* frames, int threshold, int spread, int minVotes,
+                              uint8_t* mapDev, uint32_t* countsDev, uint32_t counts[2], mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

@@ -2109,6 +2109,24 @@ extern "C" int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16
     return MFSR_OK;
 }
 
+// ---- defective pixels: vote over the burst's frames, repair in place (csrc/defect.hip) -----------------------
+extern "C" int mfsr_burst_repair_defects(mfsr_burst* b, int nFrames, uint16_t* const* frames, int threshold, int spread,
+                                         int minVotes, uint8_t* mapDev, uint32_t* countsDev, uint32_t counts[2],
+                                         mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && mapDev);
+    MFSR_REQUIRE(counts == nullptr || countsDev != nullptr);
+    const mfsr_config& c = b->cfg;
+    TRY(mfsr_detectDefects(nFrames, frames, 2 * c.width, c.width, c.height, c.mono, threshold, spread, minVotes, mapDev, c.width,
+                           countsDev, stream));
+    TRY(mfsr_repairDefects(nFrames, frames, 2 * c.width, c.width, c.height, c.mono, mapDev, c.width, stream));
+    if (counts) {
+        MFSR_HIP_TRY(hipMemcpyAsync(counts, countsDev, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, mfsr_s(stream)));
+        MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    }
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2d* mask, mfsr_tex2d* kernelParam,
                                       mfsr_tex2d* tracking)
 {

@@ -117,6 +117,67 @@ def frame_sharpness(frames: Sequence[torch.Tensor], cfg: capi.Config,
     return sums
 
 
+def defect_defaults(cfg: capi.Config, n_frames: int) -> Tuple[int, int, int]:
+    """(threshold, spread, min_votes) the defect vote uses when none are given: a 64th of the white level, half the local
+    range of the neighbours on top of it (spread 2, in quarters), and three quarters of the frames but always a strict
+    majority.  Pure Python (no device)."""
+    threshold = max(1, int(max(cfg.white)) // 64)
+    min_votes = max(n_frames // 2 + 1, -(-3 * n_frames // 4))
+    return threshold, 2, min_votes
+
+
+def _raw_frames(frames: Sequence[torch.Tensor], cfg: capi.Config):
+    """Check a list of raw device frames (one device, one row stride); returns (device, pitch in bytes)."""
+    if not frames:
+        raise ValueError("at least one frame is needed")
+    dev = frames[0].device
+    pitch = frames[0].stride(0) * 2
+    for f in frames:
+        if (f.device != dev or not f.is_cuda or f.dtype not in (torch.int16, torch.uint16) or f.dim() != 2
+                or tuple(f.shape) != (cfg.height, cfg.width) or f.stride(1) != 1 or f.stride(0) * 2 != pitch):
+            raise ValueError(f"frames must be 16-bit {cfg.height}x{cfg.width} tensors on one HIP device with contiguous rows "
+                             "and one row stride")
+    return dev, pitch
+
+
+def detect_defects(frames: Sequence[torch.Tensor], cfg: capi.Config, threshold: Optional[int] = None, spread: int = 2,
+                   min_votes: Optional[int] = None):
+    """Defect map of a burst (mfsr_detectDefects): (uint8 [H, W] device tensor, 0 = good, 1 = hot, 2 = cold; (hot, cold)
+    pixel counts).  ``frames`` as for ``frame_sharpness`` (pitched views are fine); they are only read.  threshold /
+    min_votes None = ``defect_defaults``."""
+    frames = list(frames)
+    dev, pitch = _raw_frames(frames, cfg)
+    n = len(frames)
+    t0, _, v0 = defect_defaults(cfg, n)
+    threshold = t0 if threshold is None else int(threshold)
+    min_votes = v0 if min_votes is None else int(min_votes)
+    with torch.cuda.device(dev):
+        dmap = torch.empty(cfg.height, cfg.width, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+        capi.lib().detectDefects(n, ptrs, pitch, cfg.width, cfg.height, 1 if cfg.mono else 0, threshold, int(spread), min_votes,
+                                 dmap.data_ptr(), dmap.stride(0), counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        hot, cold = counts.cpu().tolist()
+    return dmap, (hot, cold)
+
+
+def repair_defects(frames: Sequence[torch.Tensor], defect_map: torch.Tensor, cfg: capi.Config):
+    """The frames repaired under ``defect_map`` (mfsr_repairDefects; any uint8 [H, W] device map, non-zero = defective): a
+    list of new contiguous tensors, the caller's frames stay untouched."""
+    frames = list(frames)
+    dev, _ = _raw_frames(frames, cfg)
+    if (defect_map.device != dev or defect_map.dtype != torch.uint8 or tuple(defect_map.shape) != (cfg.height, cfg.width)
+            or defect_map.stride(1) != 1):
+        raise ValueError(f"defect_map must be a uint8 {cfg.height}x{cfg.width} tensor on the frames' device with contiguous rows")
+    out = [f.clone(memory_format=torch.contiguous_format) for f in frames]
+    n = len(out)
+    with torch.cuda.device(dev):
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in out])
+        capi.lib().repairDefects(n, ptrs, 2 * cfg.width, cfg.width, cfg.height, 1 if cfg.mono else 0, defect_map.data_ptr(),
+                                 defect_map.stride(0), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -249,6 +310,30 @@ class BurstPipeline:
         for k in kept:
             self.add_frame(frames[k], k == r)
         return self.finish()
+
+    def process_repaired(self, frames: Sequence[torch.Tensor], threshold: Optional[int] = None, spread: int = 2,
+                         min_votes: Optional[int] = None, select: bool = False, candidates: int = 0, keep_ratio: float = 0.0):
+        """Whole burst with its defective pixels repaired first (mfsr_burst_repair_defects on clones: the caller's frames
+        stay untouched), then exactly ``process`` of the repaired frames, or ``process_selected`` (``candidates``,
+        ``keep_ratio``) with ``select=True``: repair goes before selection.  threshold / min_votes None =
+        ``defect_defaults``.  The (hot, cold) pixel counts are left in ``self.defects``, the map in ``self.defect_map``."""
+        n = len(frames)
+        for f in frames:
+            self._check_raw(f)
+        t0, _, v0 = defect_defaults(self.cfg, n)
+        threshold = t0 if threshold is None else int(threshold)
+        min_votes = v0 if min_votes is None else int(min_votes)
+        fixed = [f.clone() for f in frames]
+        self.defect_map = torch.empty(self.cfg.height, self.cfg.width, dtype=torch.uint8, device=self.device)
+        counts_dev = torch.empty(2, dtype=torch.int32, device=self.device)
+        counts = (ctypes.c_uint32 * 2)()
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fixed])
+        self.L.burst_repair_defects(self._h, n, ptrs, threshold, int(spread), min_votes, self.defect_map.data_ptr(),
+                                    counts_dev.data_ptr(), counts, self._stream())
+        self.defects = (int(counts[0]), int(counts[1]))
+        if select:
+            return self.process_selected(fixed, candidates, keep_ratio)
+        return self.process(fixed)
 
     def host_sync(self):
         """Block the host until the image of the last process_host has landed in host memory."""
