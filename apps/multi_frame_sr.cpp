@@ -22,6 +22,8 @@
 //     MFSR_VIRTUAL_RANKS=1 puts all n ranks on device 0 (test rehearsal on a one-GPU box).
 //   * MFSR_DEFECTS=1 (with MFSR_DEFECT_THRESHOLD / MFSR_DEFECT_SPREAD / MFSR_DEFECT_VOTES) repairs hot / dead pixels found
 //     by a vote over the burst's frames before anything else; one GPU only.
+//   * MFSR_EXPOSURE=1 (=rgb: one gain per colour) matches every frame's exposure to the reference's after the repair and the
+//     selection and prints one line per frame (Q16 gains, status) to stderr; one GPU only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -209,6 +211,19 @@ int main(int argc, char** argv)
                 *v.value = (int)x;
             }
     }
+    // MFSR_EXPOSURE=1: match every frame's exposure to the reference's (one gain per frame; =rgb: one per frame and colour)
+    int exposure = 0;  // 0 off, 1 common gain, 2 per colour
+    if (const char* e = getenv("MFSR_EXPOSURE")) {
+        if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0 && strcmp(e, "rgb") != 0) {
+            fprintf(stderr, "MFSR_EXPOSURE=%s: 0, 1 or rgb expected\n", e);
+            return 1;
+        }
+        exposure = e[0] == 'r' ? 2 : e[0] == '1' ? 1 : 0;
+    }
+    if (exposure && gpus > 1) {
+        fprintf(stderr, "MFSR_EXPOSURE is not supported with MFSR_GPUS > 1 (match the frames before sharding them)\n");
+        return 1;
+    }
     if (defects && gpus > 1) {
         fprintf(stderr, "MFSR_DEFECTS is not supported with MFSR_GPUS > 1 (each rank holds only its own frames)\n");
         return 1;
@@ -335,6 +350,21 @@ int main(int argc, char** argv)
         for (int k = 0; k < num_images; k++)
             if (keep[k]) ids.push_back(k);
         fprintf(stderr, "reference %d, kept %d of %d\n", reference, (int)ids.size(), num_images);
+    }
+
+    // MFSR_EXPOSURE: every frame's brightness matched to the reference's, once, in the device frames, after the repair and
+    // the selection and before the replays (mfsr_burst_match_exposure); the report goes to stderr
+    if (exposure) {
+        long long* dlevels = nullptr;
+        int32_t deadband = 0, minGain = 0, maxGain = 0;
+        std::vector<int32_t> gains(3 * (size_t)num_images), status(num_images);
+        HIP_OK(hipMalloc((void**)&dlevels, 5 * sizeof(long long) * num_images));
+        MFSR_OK_OR_DIE(mfsr_exposure_defaults(&cfg, nullptr, nullptr, nullptr, &deadband, &minGain, &maxGain, nullptr));
+        MFSR_OK_OR_DIE(mfsr_burst_match_exposure(b, num_images, dframes.data(), reference, exposure == 2, deadband, minGain, maxGain,
+                                                 dlevels, gains.data(), status.data(), nullptr, nullptr));
+        HIP_OK(hipFree(dlevels));
+        for (int k = 0; k < num_images; k++)
+            fprintf(stderr, "exposure: frame %d gain %d %d %d status %d\n", k, gains[3 * k], gains[3 * k + 1], gains[3 * k + 2], status[k]);
     }
 
     for (int rep = 0; rep < num_times; rep++) {

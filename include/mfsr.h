@@ -771,6 +771,63 @@ int mfsr_repairDefects(int nFrames, uint16_t* const* frames, int pitch, int widt
 int mfsr_burst_repair_defects(mfsr_burst* b, int nFrames, uint16_t* const* frames, int threshold, int spread, int minVotes,
                               uint8_t* mapDev, uint32_t* countsDev, uint32_t counts[2], mfsr_stream_t stream);
 
+/* ---- exposure matching: equalise the brightness of a burst's frames in the raw domain before alignment looks at them
+ * (auto-exposure drift, flicker of mains-powered light).  A global gain per frame (or per frame and
+ * colour) about the black level, measured from plain channel sums and applied in place.  Exact integer arithmetic:
+ * bit-for-bit reproducible.  Order of the raw-domain steps: repair defects, select the reference, match exposure to that
+ * reference, process.
+ * Let q = 2*(y&1) + (x&1) number the position of sample (x, y) inside its 2x2 quad (for mono too); black[q] integer black
+ * levels, 0 <= black[q] <= 65535; 0 < sat <= maxValue <= 65535; rect = {x0, y0, x1, y1} a half-resolution rectangle of quads
+ * [x0, x1) x [y0, y1) with the bounds of mfsr_frameSharpness (1 <= x0 < x1 <= width/2 - 1, likewise y; at most 2^23 quads).
+ * MEASURE.  A quad of frame k is usable if all four of its samples are < sat.  C[k] = number of usable quads in rect;
+ * S[k][q] = sum over the usable quads of max(v_q - black[q], 0).  64-bit integers, independent of the reduction order and of
+ * the launch shape.  (A quad, not a pixel, is the unit, so that the four sums always cover the same scene area.)
+ * GAIN (host only, unsigned 128-bit intermediates, no floating point).  colour(q) = cfa[q], which must be MFSR_RED, MFSR_GREEN
+ * or MFSR_BLUE; mono: all four positions are one class and perColour is ignored.  Common mode (perColour = 0): T[k][c] =
+ * S[k][0] + S[k][1] + S[k][2] + S[k][3] for every c; per-colour mode: T[k][c] = sum of S[k][q] over the positions with
+ * colour(q) = c.  gain[k][c] = floor((T[ref][c] * C[k] * 65536 + den/2) / den), den = T[k][c] * C[ref]: Q16, 65536 = 1.0,
+ * saturated at 2^31 - 1.  In common mode the three entries of gain[k] are equal; in per-colour mode the entry of a colour the
+ * CFA does not have is 65536 and takes no part below.
+ * status[k], tested in this order:
+ *   the reference: 1, gains 65536, never written;
+ *   2 unmeasurable: C[k] == 0, C[ref] == 0, or a T[k][c] or T[ref][c] that is needed is 0; gains reported as 65536;
+ *   1 within the deadband: every |gain[k][c] - 65536| <= deadband; gains reported as 65536;
+ *   3 out of range: some gain[k][c] outside [minGain, maxGain]; gains reported as computed;
+ *   0 matched.
+ * Only frames with status 0 are ever written.  0 <= deadband < 65536, 4096 <= minGain <= 65536 <= maxGain <= 1048576.
+ * APPLY (in place, frames with status 0 only).  Sample v at position q with b = black[q], g = gain[k][colour(q)] (mono:
+ * gain[k][0]): unchanged if v <= b or v >= sat (a clipped sample stays clipped: a darkened highlight would read as grey);
+ * otherwise min(b + (((v - b) * g + 32768) >> 16), maxValue) (the product needs more than 32 bits).
+ * Every argument is checked on the host before any device call (MFSR_E_INVALID).  frames = host array of nFrames DEVICE
+ * pointers (u16, rows `pitch` bytes apart, pitch >= 2*width and even, width and height even), 1 <= nFrames <= 64.
+ * mfsr_frameLevels: levelsDev[5*k + q] := S[k][q], levelsDev[5*k + 4] := C[k] (device, zeroed on the stream first).  Frames
+ * are read only. */
+int mfsr_frameLevels(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, const int32_t black[4], int sat,
+                     const int32_t rect[4], long long* levelsDev, mfsr_stream_t stream);
+/* Host only (no device call).  levels[5*n] as mfsr_frameLevels leaves them (each entry in [0, 2^48)); gains[3*n], status[n]. */
+int mfsr_exposure_gains(int n, const long long* levels, int reference, const int32_t cfa[4], int mono, int perColour, int deadband,
+                        int minGain, int maxGain, int32_t* gains, int32_t* status);
+/* gains[3*nFrames] and status[nFrames] are HOST arrays (they travel in the launch's argument table, like the frame
+ * pointers); the gains of a status-0 frame must lie in [4096, 1048576].  One launch for all status-0 frames; frames with
+ * status != 0, and the bytes of a row beyond its width samples, are never written. */
+int mfsr_applyGains(int nFrames, uint16_t* const* frames, int pitch, int width, int height, const int32_t cfa[4], int mono,
+                    const int32_t black[4], int sat, int maxValue, const int32_t* gains, const int32_t* status, mfsr_stream_t stream);
+/* The levels and bounds a burst uses when the caller has none of their own (host only): black[q] = cfg.black[colour(q)] rounded
+ * to nearest (mono: cfg.black[0]); sat = the smallest floor(cfg.black[c] + cfg.white[c]) over the three channels; maxValue =
+ * (int)cfg.maxVal; deadband = 164 (0.25 %, twice what a constant-exposure burst measures: DESIGN.md section 2.14); minGain =
+ * 16384, maxGain = 262144 (+-2 EV: beyond it a frame is no flicker victim); perColour = 0.  Every output may be NULL. */
+int mfsr_exposure_defaults(const mfsr_config* cfg, int32_t black[4], int32_t* sat, int32_t* maxValue, int32_t* deadband,
+                           int32_t* minGain, int32_t* maxGain, int32_t* perColour);
+/* Match the exposure of a burst's frames (device-resident, dense rows as for mfsr_burst_add_frame; 1 <= nFrames <= 64) to
+ * frames[reference], in place: mfsr_frameLevels, one wait for the stream, mfsr_exposure_gains, mfsr_applyGains.  black, sat and
+ * maxValue are those of mfsr_exposure_defaults; CFA, mono and size come from the burst's config; the rectangle is exactly the
+ * one mfsr_burst_select_frames scores (the window's footprint when a zoom window is set).  levelsDev: 5 * nFrames device
+ * entries of caller scratch.  Host outputs (each may be NULL): gains[3*nFrames], status[nFrames], levels[5*nFrames].
+ * Processes nothing: the caller then runs the usual begin / set_reference(frames[reference]) / add_frame / finish. */
+int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* const* frames, int reference, int perColour, int deadband,
+                              int minGain, int maxGain, long long* levelsDev, int32_t* gains, int32_t* status, long long* levels,
+                              mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

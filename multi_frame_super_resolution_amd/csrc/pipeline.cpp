@@ -23,6 +23,7 @@
 // a hipGraph.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -2124,6 +2125,59 @@ extern "C" int mfsr_burst_repair_defects(mfsr_burst* b, int nFrames, uint16_t* c
         MFSR_HIP_TRY(hipMemcpyAsync(counts, countsDev, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
     }
+    return MFSR_OK;
+}
+
+// ---- exposure matching: level sums of every frame, gains against the reference, applied in place
+//      (csrc/exposure.hip) ------------------------------------------------------------------------------------------------
+extern "C" int mfsr_exposure_defaults(const mfsr_config* cfg, int32_t black[4], int32_t* sat, int32_t* maxValue, int32_t* deadband,
+                                      int32_t* minGain, int32_t* maxGain, int32_t* perColour)
+{
+    MFSR_REQUIRE(cfg != nullptr);
+    if (black)
+        for (int q = 0; q < 4; q++) {
+            const int c = cfg->mono ? 0 : cfg->cfa[q];
+            MFSR_REQUIRE(c >= MFSR_RED && c <= MFSR_BLUE);
+            black[q] = (int32_t)floor((double)cfg->black[c] + 0.5);
+        }
+    if (sat) {
+        double s = floor((double)cfg->black[0] + (double)cfg->white[0]);
+        for (int c = 1; c < 3; c++) {
+            const double v = floor((double)cfg->black[c] + (double)cfg->white[c]);
+            s = v < s ? v : s;
+        }
+        *sat = (int32_t)s;
+    }
+    if (maxValue) *maxValue = (int32_t)cfg->maxVal;
+    if (deadband) *deadband = 164;
+    if (minGain) *minGain = 16384;
+    if (maxGain) *maxGain = 262144;
+    if (perColour) *perColour = 0;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* const* frames, int reference, int perColour,
+                                         int deadband, int minGain, int maxGain, long long* levelsDev, int32_t* gains,
+                                         int32_t* status, long long* levels, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && levelsDev);
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= 64 && reference >= 0 && reference < nFrames);
+    MFSR_REQUIRE(deadband >= 0 && deadband < 65536 && minGain >= 4096 && minGain <= 65536 && maxGain >= 65536 && maxGain <= 1048576);
+    const mfsr_config& c = b->cfg;
+    int32_t black[4], sat = 0, maxValue = 0, r[4];
+    TRY(mfsr_exposure_defaults(&c, black, &sat, &maxValue, nullptr, nullptr, nullptr, nullptr));
+    MFSR_REQUIRE(0 < sat && sat <= maxValue && maxValue <= 65535);
+    select_rect(b, r);
+    TRY(mfsr_frameLevels(nFrames, frames, 2 * c.width, c.width, c.height, black, sat, r, levelsDev, stream));
+    std::vector<long long> host(5 * (size_t)nFrames);
+    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), levelsDev, sizeof(long long) * host.size(), hipMemcpyDeviceToHost, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    std::vector<int32_t> g(3 * (size_t)nFrames), st((size_t)nFrames);
+    TRY(mfsr_exposure_gains(nFrames, host.data(), reference, c.cfa, c.mono, perColour, deadband, minGain, maxGain, g.data(), st.data()));
+    TRY(mfsr_applyGains(nFrames, frames, 2 * c.width, c.width, c.height, c.cfa, c.mono, black, sat, maxValue, g.data(), st.data(), stream));
+    if (gains) memcpy(gains, g.data(), sizeof(int32_t) * g.size());
+    if (status) memcpy(status, st.data(), sizeof(int32_t) * st.size());
+    if (levels) memcpy(levels, host.data(), sizeof(long long) * host.size());
     return MFSR_OK;
 }
 

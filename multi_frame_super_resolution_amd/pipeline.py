@@ -178,6 +178,87 @@ def repair_defects(frames: Sequence[torch.Tensor], defect_map: torch.Tensor, cfg
     return out
 
 
+Exposure = namedtuple("Exposure", "reference gains status levels gains_q16")
+Exposure.__doc__ = """What BurstPipeline.process_matched measured and applied: the frame the others were matched to, the gain of
+every frame and colour as floats (``gains_q16`` / 65536; [n][3]), the status of every frame (0 matched, 1 within the deadband or
+the reference, 2 unmeasurable, 3 out of range: only status 0 frames were changed), the level sums [n][5] (S[q], q = 0..3, and
+the usable-quad count C) and the raw Q16 gains."""
+
+ExposureDefaults = namedtuple("ExposureDefaults", "black sat max_value deadband min_gain max_gain per_colour")
+
+
+def exposure_defaults(cfg: capi.Config) -> ExposureDefaults:
+    """The levels and bounds of exposure matching when none are given (the rule of mfsr_exposure_defaults, restated): black
+    level of every quad position (its colour's cfg.black rounded to nearest; mono: cfg.black[0]), sat = the smallest
+    floor(black + white) of the channels, max_value = int(cfg.maxVal), deadband 164 (0.25 %), gains within [16384, 262144]
+    (+-2 EV), one common gain.  Pure Python (no device)."""
+    import math
+    colour = [0] * 4 if cfg.mono else [int(c) for c in cfg.cfa]
+    if any(c < 0 or c > 2 for c in colour):
+        raise ValueError("exposure matching needs a CFA of red, green and blue")
+    black = tuple(int(math.floor(float(cfg.black[c]) + 0.5)) for c in colour)
+    sat = min(int(math.floor(float(cfg.black[c]) + float(cfg.white[c]))) for c in range(3))
+    return ExposureDefaults(black, sat, int(cfg.maxVal), 164, 16384, 262144, False)
+
+
+def frame_levels(frames: Sequence[torch.Tensor], cfg: capi.Config, rect: Optional[Sequence[int]] = None,
+                 sat: Optional[int] = None) -> torch.Tensor:
+    """Level sums of every frame (mfsr_frameLevels): an int64 [n, 5] device tensor, exact -- per frame the sums S[q] of
+    max(v - black[q], 0) over the usable quads (all four samples < sat) of the half-resolution rectangle, q = 0..3, and the
+    number of usable quads.  ``frames`` as for ``frame_sharpness`` (pitched views are fine); they are only read.  rect None =
+    ``sharpness_rect(cfg)``; sat None = ``exposure_defaults``."""
+    frames = list(frames)
+    dev, pitch = _raw_frames(frames, cfg)
+    d = exposure_defaults(cfg)
+    r = sharpness_rect(cfg) if rect is None else tuple(int(v) for v in rect)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        levels = torch.empty(n, 5, dtype=torch.int64, device=dev)
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+        capi.lib().frameLevels(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*d.black),
+                               d.sat if sat is None else int(sat), (ctypes.c_int32 * 4)(*r), levels.data_ptr(),
+                               torch.cuda.current_stream().cuda_stream)
+    return levels
+
+
+def exposure_gains(levels, cfg: capi.Config, reference: int, per_colour: bool = False, deadband: Optional[int] = None,
+                   min_gain: Optional[int] = None, max_gain: Optional[int] = None):
+    """(gains, status) of mfsr_exposure_gains: Q16 gains [n][3] (65536 = 1.0) and the status of every frame, as lists of Python
+    ints.  ``levels``: [n, 5] integers (a tensor on any device, an array or nested lists).  Host only: no device is needed."""
+    if isinstance(levels, torch.Tensor):
+        levels = levels.cpu().tolist()
+    rows = [[int(v) for v in row] for row in levels]
+    n = len(rows)
+    if n == 0 or any(len(row) != 5 for row in rows):
+        raise ValueError("levels must be [n, 5] with n >= 1")
+    d = exposure_defaults(cfg)
+    flat = (ctypes.c_longlong * (5 * n))(*[v for row in rows for v in row])
+    gains, status = (ctypes.c_int32 * (3 * n))(), (ctypes.c_int32 * n)()
+    capi.lib().exposure_gains(n, flat, int(reference), (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0, 1 if per_colour else 0,
+                              d.deadband if deadband is None else int(deadband), d.min_gain if min_gain is None else int(min_gain),
+                              d.max_gain if max_gain is None else int(max_gain), gains, status)
+    return [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)], [int(s) for s in status]
+
+
+def apply_gains(frames: Sequence[torch.Tensor], gains, status, cfg: capi.Config):
+    """The frames with their gains applied (mfsr_applyGains; ``gains`` [n][3] Q16, ``status`` [n]: only status 0 frames
+    change): a list of new contiguous tensors, the caller's frames stay untouched."""
+    frames = list(frames)
+    dev, _ = _raw_frames(frames, cfg)
+    n = len(frames)
+    if len(gains) != n or len(status) != n:
+        raise ValueError("one gain triple and one status per frame are needed")
+    d = exposure_defaults(cfg)
+    out = [f.clone(memory_format=torch.contiguous_format) for f in frames]
+    with torch.cuda.device(dev):
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in out])
+        capi.lib().applyGains(n, ptrs, 2 * cfg.width, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0,
+                              (ctypes.c_int32 * 4)(*d.black), d.sat, d.max_value,
+                              (ctypes.c_int32 * (3 * n))(*[int(g) for row in gains for g in row]),
+                              (ctypes.c_int32 * n)(*[int(s) for s in status]), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -334,6 +415,58 @@ class BurstPipeline:
         if select:
             return self.process_selected(fixed, candidates, keep_ratio)
         return self.process(fixed)
+
+    def process_matched(self, frames: Sequence[torch.Tensor], select: bool = False, repair: bool = False, per_colour: bool = False,
+                        deadband: Optional[int] = None, min_gain: Optional[int] = None, max_gain: Optional[int] = None,
+                        candidates: int = 0, keep_ratio: float = 0.0, threshold: Optional[int] = None, spread: int = 2,
+                        min_votes: Optional[int] = None):
+        """Whole burst with the exposure of its frames matched to the reference first (mfsr_burst_match_exposure on clones:
+        the caller's frames stay untouched).  Order of the raw-domain steps: repair defects (``repair=True``; threshold /
+        spread / min_votes as for ``process_repaired``), select the reference and the kept frames (``select=True``;
+        candidates / keep_ratio as for ``process_selected``), match every frame to that reference, then the ordinary burst.
+        deadband / min_gain / max_gain None = ``exposure_defaults``; ``per_colour``: one gain per colour instead of one per
+        frame.  With a window the levels are measured over the window's footprint.  Returns (float image, u16 image) like
+        ``process``; the outcome is left in ``self.exposure`` (an ``Exposure``), and ``self.defects`` / ``self.defect_map`` /
+        ``self.selection`` are set by the steps that ran."""
+        n = len(frames)
+        for f in frames:
+            self._check_raw(f)
+        d = exposure_defaults(self.cfg)
+        work = [f.clone() for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in work])
+        if repair:
+            t0, _, v0 = defect_defaults(self.cfg, n)
+            self.defect_map = torch.empty(self.cfg.height, self.cfg.width, dtype=torch.uint8, device=self.device)
+            counts_dev = torch.empty(2, dtype=torch.int32, device=self.device)
+            counts = (ctypes.c_uint32 * 2)()
+            self.L.burst_repair_defects(self._h, n, ptrs, t0 if threshold is None else int(threshold), int(spread),
+                                        v0 if min_votes is None else int(min_votes), self.defect_map.data_ptr(),
+                                        counts_dev.data_ptr(), counts, self._stream())
+            self.defects = (int(counts[0]), int(counts[1]))
+        r, kept = self.cfg.reference, list(range(n))
+        if select:
+            sums_dev = torch.empty(n, dtype=torch.int64, device=self.device)
+            ref, keep = ctypes.c_int(-1), (ctypes.c_int32 * n)()
+            sums, rect = (ctypes.c_longlong * n)(), (ctypes.c_int32 * 4)()
+            self.L.burst_select_frames(self._h, n, ptrs, int(candidates), float(keep_ratio), sums_dev.data_ptr(), ctypes.byref(ref),
+                                       keep, sums, rect, self._stream())
+            r = ref.value
+            kept = [k for k in range(n) if keep[k]]
+            self.selection = Selection(r, kept, list(sums), tuple(rect))
+        levels_dev = torch.empty(n, 5, dtype=torch.int64, device=self.device)
+        gains, status, levels = (ctypes.c_int32 * (3 * n))(), (ctypes.c_int32 * n)(), (ctypes.c_longlong * (5 * n))()
+        self.L.burst_match_exposure(self._h, n, ptrs, r, 1 if per_colour else 0, d.deadband if deadband is None else int(deadband),
+                                    d.min_gain if min_gain is None else int(min_gain),
+                                    d.max_gain if max_gain is None else int(max_gain), levels_dev.data_ptr(), gains, status, levels,
+                                    self._stream())
+        q16 = [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)]
+        self.exposure = Exposure(r, [[g / 65536.0 for g in row] for row in q16], [int(s) for s in status],
+                                 [[int(levels[5 * k + i]) for i in range(5)] for k in range(n)], q16)
+        self.begin_burst()
+        self.set_reference(work[r])
+        for k in kept:
+            self.add_frame(work[k], k == r)
+        return self.finish()
 
     def host_sync(self):
         """Block the host until the image of the last process_host has landed in host memory."""
