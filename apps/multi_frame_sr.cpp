@@ -24,6 +24,9 @@
 //     by a vote over the burst's frames before anything else; one GPU only.
 //   * MFSR_EXPOSURE=1 (=rgb: one gain per colour) matches every frame's exposure to the reference's after the repair and the
 //     selection and prints one line per frame (Q16 gains, status) to stderr; one GPU only.
+//   * MFSR_NOISE=auto measures the noise model of the robustness stage (cfg.alpha, cfg.beta) on the input frames, after the
+//     steps above and before the burst is created, and prints `noise: alpha A beta B status S` to
+//     stderr (a status other than 0 keeps the defaults); MFSR_NOISE=alpha,beta sets the two values; one GPU only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -220,6 +223,28 @@ int main(int argc, char** argv)
         }
         exposure = e[0] == 'r' ? 2 : e[0] == '1' ? 1 : 0;
     }
+    // MFSR_NOISE=auto: calibrate cfg.alpha / cfg.beta on the input frames; MFSR_NOISE=alpha,beta: set them
+    int noiseMode = 0;  // 0 off, 1 auto, 2 given
+    if (const char* e = getenv("MFSR_NOISE")) {
+        if (strcmp(e, "auto") == 0)
+            noiseMode = 1;
+        else {
+            char *end = nullptr, *end2 = nullptr;
+            const float a = strtof(e, &end);
+            const float bt = (end != e && *end == ',') ? strtof(end + 1, &end2) : 0.0f;
+            if (end == e || *end != ',' || end2 == end + 1 || *end2 != '\0' || !(a > 0.0f) || !(bt >= 0.0f) || !(a < 1.0f) || !(bt < 1.0f)) {
+                fprintf(stderr, "MFSR_NOISE=%s: auto, or alpha,beta (0 < alpha < 1, 0 <= beta < 1) expected\n", e);
+                return 1;
+            }
+            cfg.alpha = a;
+            cfg.beta = bt;
+            noiseMode = 2;
+        }
+    }
+    if (noiseMode && gpus > 1) {
+        fprintf(stderr, "MFSR_NOISE is not supported with MFSR_GPUS > 1 (calibrate on one GPU and pass the values)\n");
+        return 1;
+    }
     if (exposure && gpus > 1) {
         fprintf(stderr, "MFSR_EXPOSURE is not supported with MFSR_GPUS > 1 (match the frames before sharding them)\n");
         return 1;
@@ -365,6 +390,25 @@ int main(int argc, char** argv)
         HIP_OK(hipFree(dlevels));
         for (int k = 0; k < num_images; k++)
             fprintf(stderr, "exposure: frame %d gain %d %d %d status %d\n", k, gains[3 * k], gains[3 * k + 1], gains[3 * k + 2], status[k]);
+    }
+
+    // MFSR_NOISE=auto: the noise model measured on the (repaired, matched) device frames; alpha and beta are construction-time
+    // configuration, so the burst is created again with them (mfsr_burst_calibrate_noise changes nothing itself)
+    if (noiseMode == 1) {
+        void* dscratch = nullptr;
+        float a = 0.0f, bt = 0.0f;
+        int32_t st = 0;
+        HIP_OK(hipMalloc(&dscratch, MFSR_NOISE_SCRATCH_BYTES));
+        MFSR_OK_OR_DIE(mfsr_burst_calibrate_noise(b, num_images, dframes.data(), dscratch, &a, &bt, &st, nullptr));
+        HIP_OK(hipFree(dscratch));
+        fprintf(stderr, "noise: alpha %g beta %g status %d\n", a, bt, st);
+        if (st == 0) {
+            cfg.alpha = a;
+            cfg.beta = bt;
+            mfsr_burst_destroy(b);
+            b = nullptr;
+            MFSR_OK_OR_DIE(mfsr_burst_create(&b, &cfg, ws, wsBytes));
+        }
     }
 
     for (int rep = 0; rep < num_times; rep++) {

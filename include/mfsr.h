@@ -828,6 +828,49 @@ int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* const* frame
                               int minGain, int maxGain, long long* levelsDev, int32_t* gains, int32_t* status, long long* levels,
                               mfsr_stream_t stream);
 
+/* ---- noise-model calibration: measure the affine noise model var = alpha * I + beta of the robustness model (cfg.alpha,
+ * cfg.beta) from raw frames of the sensor at the gain in use.  An exact-integer device stage and a small
+ * host fit.  Frames are read only; nothing here runs unless it is called.
+ * q = 2*(y&1) + (x&1) numbers the position of sample (x, y) inside its 2x2 quad (for mono too).  A BLOCK is 4x4 quads = 8x8
+ * raw samples; the block grid starts at the frame origin and has (width/8) x (height/8) blocks (a partial block at the right
+ * or bottom edge is not part of it).  Per position a block holds 16 samples p[r][c], r, c = 0..3.  rect = {bx0, by0, bx1, by1}
+ * is a rectangle of blocks [bx0, bx1) x [by0, by1) inside the grid, not empty.  0 < sat <= 65535, 0 <= black[q] < sat.
+ * STATS.  A block is usable iff all of its 64 samples are < sat.  Per usable block and position q:
+ *   S = sum of p;   D = sum over r of (p[r][0] - p[r][1])^2 + (p[r][2] - p[r][3])^2   (8 disjoint same-colour pairs; E[D] = 16 var)
+ *   level bin l = clamp(S - 16*black[q], 0, span - 1) * 64 / span (integer division), span = 16 * (sat - black[q]);
+ *   variance bin v = D for D < 16, else 16 + 8*(e - 4) + ((D >> (e - 3)) & 7) with e = floor(log2 D): 8 bins per octave, v <= 271.
+ * Summed over all frames of the call: hist[q][l][v] (u32, 4 x 64 x 272), levelSum[q][l] = sum of S, count[q][l] (both 64-bit,
+ * 4 x 64).  Integer arithmetic: independent of the reduction order and of the launch shape.  The three tables are device
+ * memory, zeroed on the stream first.  frames = host array of nFrames DEVICE pointers (u16, rows `pitch` bytes apart, pitch >=
+ * 2*width and even, width and height even), 1 <= nFrames <= 64; nFrames * blocks of rect < 2^31.  Every argument is checked on
+ * the host before any device call (MFSR_E_INVALID). */
+#define MFSR_NOISE_HIST_ENTRIES (4 * 64 * 272)
+#define MFSR_NOISE_LEVEL_ENTRIES (4 * 64)
+#define MFSR_NOISE_SCRATCH_BYTES (4 * MFSR_NOISE_HIST_ENTRIES + 16 * MFSR_NOISE_LEVEL_ENTRIES)
+int mfsr_noiseStats(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, const int32_t black[4], int sat,
+                    const int32_t rect[4], uint32_t* histDev, long long* levelSumDev, long long* countDev, mfsr_stream_t stream);
+/* FIT (host only, no device call, double precision).  The three tables as HOST arrays; white[q] > 0 the white level of
+ * position q; minBlocks >= 1.  Every (q, l) with count >= minBlocks gives one point: median = the value at rank count/2 of the
+ * row's histogram, linear inside the bin between the bin's lowest D and the next bin's; var = median / 14.6882 (D / (2 var) is
+ * chi-square with 8 degrees of freedom on a flat block, whose median is 7.3441); x = (levelSum / (16 count) - black[q]) /
+ * white[q]; y = max(var - 1/12, 0) / white[q]^2 (1/12: the quantiser's own variance).  One least-squares line y = alpha x + beta
+ * over the points of all four positions, weighted by count.  A negative beta is set to 0 and alpha refitted through the origin.
+ * *status: 0 ok; 2 unmeasurable (fewer than 4 points, or max x - min x < 1/8: alpha = beta = 0); 3 alpha <= 0 (values as
+ * fitted).  *points (may be NULL): the number of points. */
+int mfsr_noise_fit(const uint32_t* hist, const long long* levelSum, const long long* count, const int32_t black[4],
+                   const float white[4], int minBlocks, double* alpha, double* beta, int32_t* status, int32_t* points);
+/* The levels and bounds a burst uses (host only): black[q] and sat as mfsr_exposure_defaults; white[q] = cfg.white[colour(q)]
+ * (mono: cfg.white[0]); minBlocks = 200; rect = the whole block grid less one block of border (needs width, height >= 24).
+ * Every output may be NULL. */
+int mfsr_noise_defaults(const mfsr_config* cfg, int32_t black[4], float white[4], int32_t* sat, int32_t* minBlocks, int32_t rect[4]);
+/* mfsr_noiseStats over the given device frames (dense rows, the burst's size; 1 <= nFrames <= 64) with the defaults above, one
+ * wait for the stream, mfsr_noise_fit.  scratchDev: MFSR_NOISE_SCRATCH_BYTES of device memory, 8-byte aligned.  Changes nothing
+ * in the burst or in the frames: alpha and beta are construction-time configuration, so the caller writes them into the
+ * mfsr_config of the burst it creates next.  *alpha, *beta: as fitted (0 when *status is 2).  The frames should show flat areas
+ * at many levels (a chart, or a natural image with flat regions): pixel-scale texture reads as noise (section 2.15, limits). */
+int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint16_t* const* frames, void* scratchDev, float* alpha,
+                               float* beta, int32_t* status, mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

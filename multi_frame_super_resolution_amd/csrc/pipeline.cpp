@@ -2181,6 +2181,54 @@ extern "C" int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* c
     return MFSR_OK;
 }
 
+// ---- noise-model calibration: block statistics of the frames on the device, the fit on the host
+//      (csrc/noise.hip).  Nothing in the burst changes. -----------------------------------------------------------------
+extern "C" int mfsr_noise_defaults(const mfsr_config* cfg, int32_t black[4], float white[4], int32_t* sat, int32_t* minBlocks,
+                                   int32_t rect[4])
+{
+    MFSR_REQUIRE(cfg != nullptr);
+    TRY(mfsr_exposure_defaults(cfg, black, sat, nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (white)
+        for (int q = 0; q < 4; q++) {
+            const int c = cfg->mono ? 0 : cfg->cfa[q];
+            MFSR_REQUIRE(c >= MFSR_RED && c <= MFSR_BLUE);
+            white[q] = cfg->white[c];
+        }
+    if (minBlocks) *minBlocks = 200;
+    if (rect) {
+        MFSR_REQUIRE(cfg->width >= 24 && cfg->height >= 24);
+        rect[0] = rect[1] = 1;
+        rect[2] = cfg->width / 8 - 1;
+        rect[3] = cfg->height / 8 - 1;
+    }
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint16_t* const* frames, void* scratchDev, float* alpha,
+                                          float* beta, int32_t* status, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && scratchDev && alpha && beta && status);
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= 64 && ((uintptr_t)scratchDev & 7) == 0);
+    const mfsr_config& c = b->cfg;
+    int32_t black[4], sat = 0, minBlocks = 0, r[4];
+    float white[4];
+    TRY(mfsr_noise_defaults(&c, black, white, &sat, &minBlocks, r));
+    uint32_t* histDev = (uint32_t*)scratchDev;
+    long long* sumDev = (long long*)((char*)scratchDev + sizeof(uint32_t) * MFSR_NOISE_HIST_ENTRIES);
+    long long* countDev = sumDev + MFSR_NOISE_LEVEL_ENTRIES;
+    TRY(mfsr_noiseStats(nFrames, frames, 2 * c.width, c.width, c.height, black, sat, r, histDev, sumDev, countDev, stream));
+    std::vector<unsigned char> host(MFSR_NOISE_SCRATCH_BYTES);
+    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), scratchDev, host.size(), hipMemcpyDeviceToHost, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    const uint32_t* hist = (const uint32_t*)host.data();
+    const long long* sum = (const long long*)(host.data() + sizeof(uint32_t) * MFSR_NOISE_HIST_ENTRIES);
+    double a = 0, bt = 0;
+    TRY(mfsr_noise_fit(hist, sum, sum + MFSR_NOISE_LEVEL_ENTRIES, black, white, minBlocks, &a, &bt, status, nullptr));
+    *alpha = (float)a;
+    *beta = (float)bt;
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2d* mask, mfsr_tex2d* kernelParam,
                                       mfsr_tex2d* tracking)
 {

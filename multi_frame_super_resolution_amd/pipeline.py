@@ -259,6 +259,83 @@ def apply_gains(frames: Sequence[torch.Tensor], gains, status, cfg: capi.Config)
     return out
 
 
+NoiseDefaults = namedtuple("NoiseDefaults", "black white sat min_blocks rect")
+NoiseStats = namedtuple("NoiseStats", "hist level_sum count")
+NoiseStats.__doc__ = """The tables of mfsr_noiseStats as device tensors: hist int32 [4, 64, 272] (u32 bit patterns), level_sum and
+count int64 [4, 64]."""
+
+
+def noise_defaults(cfg: capi.Config) -> NoiseDefaults:
+    """The levels and bounds of noise calibration when none are given (the rule of mfsr_noise_defaults, restated): black and sat
+    as ``exposure_defaults``, white level of every quad position (its colour's cfg.white; mono: cfg.white[0]), min_blocks 200,
+    rect = the whole grid of 8x8-sample blocks less one block of border.  Pure Python (no device)."""
+    d = exposure_defaults(cfg)
+    colour = [0] * 4 if cfg.mono else [int(c) for c in cfg.cfa]
+    if cfg.width < 24 or cfg.height < 24:
+        raise ValueError("noise calibration needs frames of at least 24 x 24 samples")
+    return NoiseDefaults(d.black, tuple(float(cfg.white[c]) for c in colour), d.sat, 200,
+                         (1, 1, cfg.width // 8 - 1, cfg.height // 8 - 1))
+
+
+def noise_stats(frames: Sequence[torch.Tensor], cfg: capi.Config, rect: Optional[Sequence[int]] = None,
+                sat: Optional[int] = None) -> NoiseStats:
+    """Block statistics of raw frames (mfsr_noiseStats), exact: per quad position and level bin the histogram of the blocks'
+    pair-difference energies D, the sum of their level sums S and their number.  ``frames`` as for ``frame_sharpness`` (pitched
+    views are fine, at most 64); they are only read.  rect None / sat None = ``noise_defaults``; rect is (bx0, by0, bx1, by1) in
+    blocks of 8 x 8 samples."""
+    frames = list(frames)
+    dev, pitch = _raw_frames(frames, cfg)
+    d = noise_defaults(cfg)
+    r = d.rect if rect is None else tuple(int(v) for v in rect)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        hist = torch.empty(4, 64, 272, dtype=torch.int32, device=dev)
+        level_sum = torch.empty(4, 64, dtype=torch.int64, device=dev)
+        count = torch.empty(4, 64, dtype=torch.int64, device=dev)
+        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+        capi.lib().noiseStats(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*d.black),
+                              d.sat if sat is None else int(sat), (ctypes.c_int32 * 4)(*r), hist.data_ptr(), level_sum.data_ptr(),
+                              count.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return NoiseStats(hist, level_sum, count)
+
+
+def noise_fit(stats, cfg: capi.Config, min_blocks: Optional[int] = None):
+    """(alpha, beta, status, points) of mfsr_noise_fit on the tables of ``noise_stats`` (tensors on any device or arrays):
+    the least-squares line through (level, variance) of every well-filled level bin, as Python floats (doubles).  status 0 ok,
+    2 unmeasurable (alpha = beta = 0), 3 alpha <= 0.  Host only: no device is needed."""
+    import numpy as np
+
+    def host(t, dtype):
+        a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        return np.ascontiguousarray(a.view(dtype) if a.dtype.itemsize == np.dtype(dtype).itemsize else a.astype(dtype))
+
+    hist, level_sum, count = host(stats[0], np.uint32), host(stats[1], np.int64), host(stats[2], np.int64)
+    if hist.shape != (4, 64, 272) or level_sum.shape != (4, 64) or count.shape != (4, 64):
+        raise ValueError("stats must be (hist [4, 64, 272], level_sum [4, 64], count [4, 64])")
+    d = noise_defaults(cfg)
+    a, b = ctypes.c_double(), ctypes.c_double()
+    st, n = ctypes.c_int32(), ctypes.c_int32()
+    capi.lib().noise_fit(hist.ctypes.data, level_sum.ctypes.data, count.ctypes.data, (ctypes.c_int32 * 4)(*d.black),
+                         (ctypes.c_float * 4)(*d.white), d.min_blocks if min_blocks is None else int(min_blocks),
+                         ctypes.byref(a), ctypes.byref(b), ctypes.byref(st), ctypes.byref(n))
+    return a.value, b.value, st.value, n.value
+
+
+def calibrate_noise(frames: Sequence[torch.Tensor], cfg: capi.Config):
+    """(alpha, beta, status) of the noise model var = alpha * I + beta measured on raw device frames: ``noise_stats`` with the
+    defaults, then ``noise_fit``.  alpha and beta are construction-time configuration, so the use is two steps::
+
+        alpha, beta, status = calibrate_noise(chart_frames, cfg)
+        if status == 0:
+            cfg.alpha, cfg.beta = alpha, beta
+        pipe = BurstPipeline(cfg)
+
+    The frames must show flat areas at many levels (a chart capture per sensor gain, or a natural image with flat regions):
+    a single frame cannot tell pixel-scale texture from noise."""
+    a, b, st, _ = noise_fit(noise_stats(frames, cfg), cfg)
+    return a, b, st
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""

@@ -140,3 +140,24 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
         out.append(raw.contiguous())
     gt = scene[:, m:m + s * height, m:m + s * width].contiguous()
     return out, shifts, gt
+
+
+def make_chart_burst(width: int, height: int, frames: int, alpha: float, beta: float, mono: bool = False, seed: int = 1234,
+                     device="cpu", patch: int = 64, black: float = 256.0, white: float = 4095.0 - 256.0) -> List[torch.Tensor]:
+    """A noise-calibration chart: ``frames`` raw frames [H, W] (int16 holding u16 bit patterns) of one static scene of flat grey
+    patches, ``patch`` x ``patch`` raw samples each, whose levels cover 0.05 .. 0.95 evenly in a seeded random order (the part
+    of a patch the frame cuts off is simply missing).  No motion; the same noise (variance alpha*I + beta), quantisation and
+    clamp as ``make_burst``, and the same RGGB / mono layout -- every channel of a grey patch has the patch's level.  512x384
+    gives 8 x 6 = 48 patches."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    ny, nx = -(-height // patch), -(-width // patch)
+    n = ny * nx
+    levels = torch.linspace(0.05, 0.95, n, device=device) if n > 1 else torch.full((1,), 0.5, device=device)
+    levels = levels[torch.randperm(n, generator=gen, device=device)].reshape(ny, nx)
+    img = levels.repeat_interleave(patch, 0).repeat_interleave(patch, 1)[:height, :width].contiguous()
+    out = []
+    for _ in range(frames):
+        noisy = img + torch.randn(img.shape, generator=gen, device=device) * torch.sqrt(alpha * img + beta)
+        out.append(torch.round(noisy * white + black).clamp(0, 4095).to(torch.int16).contiguous())
+    return out
