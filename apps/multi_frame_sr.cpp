@@ -27,6 +27,8 @@
 //   * MFSR_NOISE=auto measures the noise model of the robustness stage (cfg.alpha, cfg.beta) on the input frames, after the
 //     steps above and before the burst is created, and prints `noise: alpha A beta B status S` to
 //     stderr (a status other than 0 keeps the defaults); MFSR_NOISE=alpha,beta sets the two values; one GPU only.
+//   * MFSR_MASK_ERODE=1|2 erodes every moved frame's certainty mask by that radius before the merge (ghost suppression,
+//     DESIGN.md section 2.16; 2 = the 5x5 minimum); works with MFSR_GPUS > 1.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -240,6 +242,15 @@ int main(int argc, char** argv)
             cfg.beta = bt;
             noiseMode = 2;
         }
+    }
+    // MFSR_MASK_ERODE=1|2: erode every moved frame's certainty mask by that radius before the merge (cfg.maskErode); it is
+    // part of the alignment stage, so a burst sharded over several GPUs takes it as well
+    if (const char* e = getenv("MFSR_MASK_ERODE")) {
+        if (strcmp(e, "0") != 0 && strcmp(e, "1") != 0 && strcmp(e, "2") != 0) {
+            fprintf(stderr, "MFSR_MASK_ERODE=%s: 0, 1 or 2 expected\n", e);
+            return 1;
+        }
+        cfg.maskErode = e[0] - '0';
     }
     if (noiseMode && gpus > 1) {
         fprintf(stderr, "MFSR_NOISE is not supported with MFSR_GPUS > 1 (calibrate on one GPU and pass the values)\n");

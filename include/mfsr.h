@@ -526,7 +526,9 @@ typedef struct {
     int32_t uploadRing;      /* > 0: the workspace holds this many device raw-frame slots (>= 3) + 2 reference slots and the
                                 burst owns a copy stream: mfsr_burst_*_host take frames from (pinned) HOST memory and upload
                                 them ahead of the compute (BASELINE configs[4]: double-buffered H2D) */
-    int32_t reserved[2];
+    int32_t maskErode;       /* 0 (default): off; 1, 2: radius of the erosion of every moved frame's certainty mask between
+                                stage F and stage G (mfsr_erodeMaskBatch; ghost suppression) */
+    int32_t reserved[1];
 } mfsr_config;
 
 typedef struct mfsr_burst mfsr_burst;
@@ -870,6 +872,28 @@ int mfsr_noise_defaults(const mfsr_config* cfg, int32_t black[4], float white[4]
  * at many levels (a chart, or a natural image with flat regions): pixel-scale texture reads as noise (section 2.15, limits). */
 int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint16_t* const* frames, void* scratchDev, float* alpha,
                                float* beta, int32_t* status, mfsr_stream_t stream);
+
+/* ---- ghost suppression: erosion of the certainty mask between stage F and stage G.  Stage F decides
+ * every cell on its own; at the rim of a moving object single cells pass although their neighbours fail, and the merge shows
+ * a faint outline of the object there.  The erosion replaces every colour certainty by its minimum over a (2r+1) x (2r+1)
+ * neighbourhood (r = 2: the 5x5 "additional robustness refinement" of the hand-held multi-frame super-resolution method).
+ * Mask: float4 cells, width x height, .x .y .z the colour certainties, .w the motion measure M, the one-cell ring zero.  For
+ * interior cells 1 <= x <= width-2, 1 <= y <= height-2:
+ *   out.c(x, y) = min over |i| <= r, |j| <= r of in.c(clamp(x+i, 1, width-2), clamp(y+j, 1, height-2)),  c = x, y, z, each alone
+ *   out.w(x, y) = in.w(x, y)
+ * The window is clamped to the interior (the zero ring takes part in no window: it would reject the frame's outer r cells);
+ * ring cells of the output are zero in all four components; bytes of a row beyond 16*width are never written.  Plain fminf
+ * semantics: stage F never writes a NaN into .x .y .z (fmaxf(fminf(.., 1), 0)), so the result is defined bit for bit and does
+ * not depend on the launch shape.
+ * One launch for nFrames (1 .. MFSR_MAX_FUSE_GROUP) masks; in[k] != out[k], no output overlaps an input or another output
+ * (not in place: a tile's halo would read cells a neighbour has already eroded); every argument is checked on the host before
+ * any device call (MFSR_E_INVALID: radius outside 1..2, width or height < 3, a pitch < 16*width or not a multiple of 16, null,
+ * misaligned or overlapping pointers, nFrames out of range).  Asynchronous on `stream`, allocates nothing: capturable.
+ * cfg.maskErode = r makes the burst pipeline do this to every moved frame's mask (the reference frame's all-ones mask is not
+ * touched); everything that consumes masks -- zoom windows, frame streams, the joint mode, stripe-sharded multi-GPU bursts --
+ * then gets the eroded ones. */
+int mfsr_erodeMaskBatch(int nFrames, const mfsr_float4* const* in, mfsr_float4* const* out, int width, int height,
+                        int inPitch, int outPitch, int radius, mfsr_stream_t stream);
 
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with

@@ -96,7 +96,7 @@ class Config(ctypes.Structure):
         ("weightThreshold", ctypes.c_float), ("applyGamma", ctypes.c_int32), ("fused", ctypes.c_int32),
         ("pairFrames", ctypes.c_int32), ("asyncFuse", ctypes.c_int32),
         ("preAlign", ctypes.c_int32), ("preAlignMaxAngle", ctypes.c_float), ("uploadRing", ctypes.c_int32),
-        ("reserved", ctypes.c_int32 * 2),
+        ("maskErode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 1),
     ]
 
 

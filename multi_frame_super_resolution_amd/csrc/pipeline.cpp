@@ -66,6 +66,7 @@ struct Layout {
     Img tmpA, tmpB;                          // float, tracking res
     Img flowBuf[2 * kRing];                  // float2, tracking res: per ring slot the two buffers of the LK ping-pong
     Img maskBuf[kRing];                      // float4, half res, one per ring slot
+    Img maskRaw[MFSR_MAX_FUSE_GROUP];        // cfg.maskErode > 0 only: stage F writes here, the erosion writes the slot's mask
     Img shifts[kMaxLevels], pre[kMaxLevels]; // float2, tile grids
     // unfused path scratch
     Img warped, Ix, Iy, It, rawf;
@@ -147,6 +148,7 @@ int validate(const mfsr_config* c)
     if (c->preAlign) MFSR_REQUIRE(c->preAlignMaxAngle >= 0.0f && c->preAlignMaxAngle <= 45.0f);
     MFSR_REQUIRE(c->uploadRing == 0 || (c->uploadRing >= 3 && c->uploadRing <= kMaxUploadRing));
     MFSR_REQUIRE(c->pairFrames >= 0 && c->pairFrames <= MFSR_MAX_FUSE_GROUP);
+    MFSR_REQUIRE(c->maskErode >= 0 && c->maskErode <= 2);
     return MFSR_OK;
 }
 
@@ -249,6 +251,9 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
     for (int i = 0; i < c->uploadRing; i++) L->rawRing[i] = (uint16_t*)b.take((size_t)L->W * L->H * 2);
     if (c->uploadRing > 0)
         for (int i = 0; i < 2; i++) L->refRaw[i] = (uint16_t*)b.take((size_t)L->W * L->H * 2);
+    // the erosion cannot run in place: one scratch mask per frame of a group, and only when the option is on
+    if (c->maskErode > 0)
+        for (int i = 0; i < mfsr_burst_group_size(c); i++) L->maskRaw[i] = b.image(L->hw, L->hh, 16);
     L->total = align_up(b.off, 256);
 }
 
@@ -1192,16 +1197,23 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
         other = t;
       }
       if (phases & ALIGN_POST) {
-        // F: robustness mask (the 1-px ring is never written by the kernel -> zero it)
+        // F: robustness mask (the 1-px ring is never written by the kernel -> zero it); with cfg.maskErode into the scratch
+        // mask, from which the erosion writes the slot's
+        Img* fOut = c.maskErode > 0 ? &L.maskRaw[0] : mask;
         if (c.fused) {
             TRY(mfsr_robustnessMaskFused((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
-                                         (mfsr_float4*)mask->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, mask->pitch, c.alpha,
+                                         (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch, c.alpha,
                                          c.beta, c.thresholdM, stream));
         } else {
-            TRY(mfsr_zeroRing_f32x4((mfsr_float4*)mask->ptr, mask->pitch, L.hw, L.hh, stream));
+            TRY(mfsr_zeroRing_f32x4((mfsr_float4*)fOut->ptr, fOut->pitch, L.hw, L.hh, stream));
             TRY(mfsr_ComputeRobustnessMask((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
-                                           (mfsr_float4*)mask->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, mask->pitch,
+                                           (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch,
                                            c.alpha, c.beta, c.thresholdM, stream));
+        }
+        if (c.maskErode > 0) {
+            const mfsr_float4* ein = (const mfsr_float4*)fOut->ptr;
+            mfsr_float4* eout = (mfsr_float4*)mask->ptr;
+            TRY(mfsr_erodeMaskBatch(1, &ein, &eout, L.hw, L.hh, fOut->pitch, mask->pitch, c.maskErode, stream));
         }
       }
     }
@@ -1381,7 +1393,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         for (int k = 0; k < m; k++) {
             const int slot = b->pend.slot[idx[mq[k]]];
             rf[k].movedHalf = (const mfsr_float3*)movHalf(mq[k]).ptr;
-            rf[k].mask = (mfsr_float4*)L.maskBuf[slot].ptr;
+            rf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
             rf[k].flow = (const mfsr_float2*)L.flowBuf[2 * slot + (c.lkIterations & 1)].ptr;  // where the ping-pong ends
         }
         const int rc = mfsr_robustnessMaskFusedBatch(m, rf, (const mfsr_float3*)L.refHalf.ptr, L.flowBuf[0].pitch, L.tw, L.th, L.hw, L.hh,
@@ -1390,6 +1402,15 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             maskBatch = false;  // (the straight robustness kernel was selected: frame by frame below)
         else if (rc)
             return rc;
+        if (maskBatch && c.maskErode > 0) {  // one erosion launch for the whole group
+            const mfsr_float4* ein[MFSR_MAX_FUSE_GROUP];
+            mfsr_float4* eout[MFSR_MAX_FUSE_GROUP];
+            for (int k = 0; k < m; k++) {
+                ein[k] = (const mfsr_float4*)L.maskRaw[k].ptr;
+                eout[k] = (mfsr_float4*)L.maskBuf[b->pend.slot[idx[mq[k]]]].ptr;
+            }
+            TRY(mfsr_erodeMaskBatch(m, ein, eout, L.hw, L.hh, L.maskRaw[0].pitch, L.maskBuf[0].pitch, c.maskErode, stream));
+        }
     }
     for (int q = 0; q < n; q++) {
         const int i = idx[q];

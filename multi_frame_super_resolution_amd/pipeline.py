@@ -336,6 +336,50 @@ def calibrate_noise(frames: Sequence[torch.Tensor], cfg: capi.Config):
     return a, b, st
 
 
+def erode_mask(masks, radius: int, out=None):
+    """Erosion of certainty masks (mfsr_erodeMaskBatch): every colour certainty (.x .y .z) becomes its
+    minimum over the (2*radius+1)^2 neighbourhood clamped to the interior, .w passes through, the one-cell ring is zero.
+    ``masks``: a float32 device tensor [h, w, 4] or [n, h, w, 4], or a sequence of [h, w, 4] tensors of one size; rows may be
+    pitched (a row stride that is a multiple of 4 floats), cells are dense.  ``out``: the same form as ``masks``, must not
+    overlap it; by default fresh dense tensors.  Returns ``out``.  radius 1 or 2; up to MFSR_MAX_FUSE_GROUP masks go into one
+    launch on the current stream.  What ``cfg.maskErode`` makes the burst pipeline do to every moved frame's mask."""
+    single = isinstance(masks, torch.Tensor) and masks.dim() == 3
+    ins = [masks] if single else list(masks)
+    if not ins:
+        raise ValueError("no masks")
+    h, w = int(ins[0].shape[0]), int(ins[0].shape[1])
+
+    def check(t, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4)
+                and t.stride(2) == 1 and t.stride(1) == 4 and t.device == ins[0].device):
+            raise ValueError(f"{what}: float32 device tensors [h, w, 4] of one size with dense cells expected")
+
+    for t in ins:
+        check(t, "masks")
+    if out is None:
+        res = torch.empty(len(ins), h, w, 4, dtype=torch.float32, device=ins[0].device)
+        outs = list(res) if not single else [res[0]]
+        ret = outs[0] if single else (res if isinstance(masks, torch.Tensor) else outs)
+    else:
+        outs = [out] if single else list(out)
+        if len(outs) != len(ins):
+            raise ValueError("out must have as many masks as the input")
+        for t in outs:
+            check(t, "out")
+        ret = out
+    in_pitch, out_pitch = ins[0].stride(0) * 4, outs[0].stride(0) * 4
+    if any(t.stride(0) * 4 != in_pitch for t in ins) or any(t.stride(0) * 4 != out_pitch for t in outs):
+        raise ValueError("all masks of a call share one row pitch")
+    G = 4  # MFSR_MAX_FUSE_GROUP
+    with torch.cuda.device(ins[0].device):
+        for k0 in range(0, len(ins), G):
+            n = min(G, len(ins) - k0)
+            P = ctypes.c_void_p * n
+            capi.lib().erodeMaskBatch(n, P(*[t.data_ptr() for t in ins[k0:k0 + n]]), P(*[t.data_ptr() for t in outs[k0:k0 + n]]),
+                                      w, h, in_pitch, out_pitch, int(radius), torch.cuda.current_stream().cuda_stream)
+    return ret
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""

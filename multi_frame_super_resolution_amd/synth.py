@@ -93,14 +93,16 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
                black: float = 256.0, white: float = 4095.0 - 256.0, shift_seed: Optional[int] = None,
                first_is_reference: bool = True,
                angles_deg: Optional[List[float]] = None,
-               keep: Optional[Sequence[int]] = None) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+               keep: Optional[Sequence[int]] = None, _composite=None) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
     """Returns (raw frames [H,W] int16 holding u16 bit patterns, shifts [N,2] in LR px, ground truth [3,sH,sW]).
 
     ``seed`` fixes the scene; ``shift_seed`` (default: same stream) fixes the per-frame shifts and
     noise, so ranks of a sharded burst can draw different frames of the SAME scene.  ``angles_deg`` (one per frame)
     additionally rotates frame k about the frame centre (needs cfg.preAlign beyond a degree or two).  ``keep``: only
     these frame numbers are rendered (the others come back as None) while the random stream advances as if all were -- a
-    rank of a sharded burst gets exactly the frames the one-GPU burst has at those positions."""
+    rank of a sharded burst gets exactly the frames the one-GPU burst has at those positions.  ``_composite(scene, k)``
+    (``make_moving_burst``): the HR scene frame k is rendered from (k = None: the ground truth's); it draws nothing from the
+    random stream."""
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     s = scale
@@ -125,10 +127,11 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
             continue
         tx, ty = float(shifts[k, 0]) * s, float(shifts[k, 1]) * s
         ang = float(angles_deg[k]) if angles_deg is not None else 0.0
+        src = scene if _composite is None else _composite(scene, k)
         if ang == 0.0:
-            sh = _shifted_crop(scene, tx, ty, m, s * height, s * width)
+            sh = _shifted_crop(src, tx, ty, m, s * height, s * width)
         else:
-            sh = _rotated(scene, tx, ty, ang)[:, m:m + s * height, m:m + s * width]
+            sh = _rotated(src, tx, ty, ang)[:, m:m + s * height, m:m + s * width]
         lr = F.avg_pool2d(sh[None], s)[0] if s > 1 else sh
         if noise:
             lr = lr + torch.randn(lr.shape, generator=gen, device=device) * torch.sqrt(alpha * lr + beta)
@@ -138,8 +141,56 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
             img = torch.gather(lr, 0, cfa_idx[None])[0]
         raw = torch.round(img * white + black).clamp(0, 4095).to(torch.int16)
         out.append(raw.contiguous())
-    gt = scene[:, m:m + s * height, m:m + s * width].contiguous()
+    gt = (scene if _composite is None else _composite(scene, None))[:, m:m + s * height, m:m + s * width].contiguous()
     return out, shifts, gt
+
+
+def make_moving_burst(width: int, height: int, frames: int, scale: int = 2, obj_size: Optional[Tuple[int, int]] = (24, 24),
+                      obj_start: Optional[Tuple[float, float]] = None, obj_step: Tuple[float, float] = (6.0, 0.0),
+                      obj_level: float = 0.9, obj_texture: float = 0.15, obj_seed: int = 99, **kwargs):
+    """``make_burst`` with something in the scene that moves: a textured rectangular patch of ``obj_size`` = (w, h) LR pixels,
+    composited into the HR scene BEFORE the per-frame shift, box average and noise, whose top-left corner is at
+    ``obj_start + k * obj_step`` (x, y in LR pixels of the reference frame's grid, rounded to the HR grid) in frame k.  Frame 0
+    is the reference (``first_is_reference``), so ``obj_start`` is where the ground truth shows the object; default: the
+    frame's centre.  The patch's luminance is ``obj_level`` + ``obj_texture`` * (uniform noise of one value per LR pixel - 0.5),
+    equal in the three channels, drawn from a generator of its own (``obj_seed``): the scene's random stream does not see it.
+    Every other argument is ``make_burst``'s; ``obj_size=None`` renders no object and returns exactly ``make_burst``'s frames.
+
+    Returns (frames, shifts, ground truth [3, sH, sW] with the object at the reference frame's position, footprints
+    [N, sH, sW] bool: the HR pixels of the ground truth's grid the object covers in frame k)."""
+    s = scale
+    m = 32 * s
+    device = kwargs.get("device", "cpu")
+    if obj_size is None:
+        out, shifts, gt = make_burst(width, height, frames, scale=scale, **kwargs)
+        return out, shifts, gt, torch.zeros(frames, s * height, s * width, dtype=torch.bool, device=device)
+    ow, oh = int(obj_size[0]), int(obj_size[1])
+    if obj_start is None:
+        obj_start = ((width - ow) / 2.0, (height - oh) / 2.0)
+    g = torch.Generator(device=device)
+    g.manual_seed(obj_seed)
+    lum = obj_level + obj_texture * (torch.rand(oh, ow, generator=g, device=device) - 0.5)
+    patch = lum.repeat_interleave(s, 0).repeat_interleave(s, 1).clamp(0.05, 0.95)[None].expand(3, -1, -1)
+
+    def corner(k):  # HR pixel of the object's top-left corner in frame k, on the cropped (ground truth) grid
+        return (int(round((obj_start[0] + k * obj_step[0]) * s)), int(round((obj_start[1] + k * obj_step[1]) * s)))
+
+    def composite(scene, k):
+        x, y = corner(0 if k is None else k)
+        x0, y0 = max(x + m, 0), max(y + m, 0)
+        x1, y1 = min(x + m + ow * s, scene.shape[2]), min(y + m + oh * s, scene.shape[1])
+        if x1 <= x0 or y1 <= y0:
+            return scene
+        c = scene.clone()
+        c[:, y0:y1, x0:x1] = patch[:, y0 - (y + m):y1 - (y + m), x0 - (x + m):x1 - (x + m)]
+        return c
+
+    out, shifts, gt = make_burst(width, height, frames, scale=scale, _composite=composite, **kwargs)
+    foot = torch.zeros(frames, s * height, s * width, dtype=torch.bool, device=device)
+    for k in range(frames):
+        x, y = corner(k)
+        foot[k, max(y, 0):max(min(y + oh * s, s * height), 0), max(x, 0):max(min(x + ow * s, s * width), 0)] = True
+    return out, shifts, gt, foot
 
 
 def make_chart_burst(width: int, height: int, frames: int, alpha: float, beta: float, mono: bool = False, seed: int = 1234,

@@ -17,6 +17,8 @@ if len(sys.argv) > 2:
     N = int(sys.argv[2])
 frames, _, _ = make_burst(W, H, N, scale=s, mono=False, seed=1236, device="cpu")
 cfg = default_config(W, H, N, s, False)
+if len(sys.argv) > 3:
+    cfg.maskErode = int(sys.argv[3])   # 1, 2: the statistics of the eroded masks
 h = run_hip(cfg, frames)
 tot = {}
 for k in range(N):
