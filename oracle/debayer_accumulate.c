@@ -1,7 +1,7 @@
 /*
  * oracle/debayer_accumulate.c -- CPU restatement of the reference's
  * test_opencv/DeBayerKernels.cu (rows A0-A3, G1, G2 of SURVEY.md section 8a).
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle_common.h).
+ * TEST INFRASTRUCTURE ONLY; PINNED TO THE REFERENCE (see oracle_common.h).
  *
  * One C function per reference kernel, same argument order and units (byte
  * pitches); the CUDA grid is replaced by plain loops over the guarded index

@@ -1,7 +1,7 @@
 /*
  * oracle/optical_flow.c -- CPU restatement of the reference's
  * test_opencv/opticalFlow.cu (rows D1-D4, E1 of SURVEY.md section 8a).
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle_common.h).
+ * TEST INFRASTRUCTURE ONLY; PINNED TO THE REFERENCE (see oracle_common.h).
  *
  * Texture conventions (the reference's host code is absent, so these are the
  * build's canonical choices): images are sampled MIRROR + linear,

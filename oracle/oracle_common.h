@@ -6,13 +6,16 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it,
  * and only as the checker.
  *
- * PARITY UNPINNED: the reference (zhongzisha/multi_frame_super_resolution)
- * ships no tests, golden vectors or expected outputs for this path, and its
- * .cu kernels cannot be built in this image without writing stand-ins for the
- * CUDA headers/toolchain (not allowed).  This oracle is therefore a
- * line-by-line restatement of the reference arithmetic (each function cites
- * the reference file:line it follows), pinned only by hand-derived
- * known-answer tests (tests/test_oracle_kat.py).
+ * PINNED TO THE REFERENCE: the reference (zhongzisha/multi_frame_super_resolution)
+ * ships no tests, golden vectors or expected outputs for this path.  This oracle
+ * is a line-by-line restatement of the reference arithmetic (each function cites
+ * the reference file:line it follows); tests/test_reference_pin_cpu.py compares
+ * every restated kernel, bit for bit, with the reference's own .cu text compiled
+ * for the host through oracle/refshim/ (oracle/_ref/libmfsr_ref.so, built by
+ * `make ref` where the reference's sources are present).
+ * What has no reference kernel (glue.c, prealign.c, the solver, the correlation,
+ * accumulateSuperResFull beyond x2) is held by the known-answer tests
+ * (tests/test_oracle_kat.py).  oracle/refshim/ must never include this header.
  *
  * Numerical conventions (see DESIGN.md "Canonical semantics"):
  *   - compiled with -ffp-contract=off: every * and + rounds separately, as the

@@ -1,7 +1,7 @@
 /*
  * oracle/robustness.c -- CPU restatement of the reference's
  * test_opencv/RobustnessModell.cu (row F1 of SURVEY.md section 8a).
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle_common.h).
+ * TEST INFRASTRUCTURE ONLY; PINNED TO THE REFERENCE (see oracle_common.h).
  */
 #include "oracle_common.h"
 

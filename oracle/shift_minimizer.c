@@ -3,7 +3,7 @@
  * test_opencv/ShiftMinimizerKernels.cu (rows C1-C6 of SURVEY.md section 8a)
  * plus the batched least-squares solve (row C4) that the reference delegates
  * to a host that is not in the repository.
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle_common.h).
+ * TEST INFRASTRUCTURE ONLY; PINNED TO THE REFERENCE (see oracle_common.h).
  */
 #include "oracle_common.h"
 

@@ -2,7 +2,7 @@
  * oracle/tile_tracker.c -- CPU restatement of the on-path kernels of the
  * reference's test_opencv/kernel.cu:116-891 (rows B1-B8, E2, E3, H1, H2, I1 of
  * SURVEY.md section 8a).
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle_common.h).
+ * TEST INFRASTRUCTURE ONLY; PINNED TO THE REFERENCE (see oracle_common.h).
  */
 #include <float.h>
 

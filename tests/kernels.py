@@ -7,15 +7,20 @@ C signatures differ only in spelling:
 
     F3(v)          float3 by value (HIP)        / const float[3] (oracle)
     F2(v)          float2 by value (HIP)        / two floats (oracle)
-    Tex(a, w, h)   mfsr_tex2d by value (HIP)    / ptr, pitch, w, h (oracle)
+    Tex(a, w, h)   mfsr_tex2d by value (HIP)    / ptr, pitch, w, h (oracle); address="clamp" | "mirror" is
+                   read by RefKernels only (the other two fix the mode per kernel)
     Host(a)        host array on both sides (e.g. filter taps)
 
 ``OracleKernels`` is test infrastructure; ``HipKernels`` is the product path
-(torch is used only to own device memory).
+(torch is used only to own device memory).  ``RefKernels`` runs the reference's
+own kernels, compiled for the host (oracle/_ref/libmfsr_ref.so, oracle/refshim/):
+what the reference leaves open -- block shape, texture address mode and filter
+variant -- are its parameters, with this project's decisions as defaults.
 """
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 
@@ -31,8 +36,9 @@ class F2:
 
 
 class Tex:
-    def __init__(self, arr, width=None, height=None, pitch=None):
+    def __init__(self, arr, width=None, height=None, pitch=None, address=None):
         self.arr = arr
+        self.address = address
         self.height = arr.shape[0] if height is None else height
         self.width = arr.shape[1] if width is None else width
         self.pitch = arr.strides[0] if pitch is None else pitch
@@ -137,3 +143,146 @@ class HipKernels:
                     h = h.view(np.uint16)
                 np.copyto(a, h)
         return rc
+
+
+# ---- the reference's kernels on the host ------------------------------------------------------------------------
+CLAMP, MIRROR = 0, 1
+# texture address modes per kernel, textures in argument order: this project's decisions
+REF_TEX_ADDRESS = {
+    "accumulateImagesSuperRes": (CLAMP, CLAMP),
+    "WarpingKernel": (CLAMP, MIRROR),
+    "CreateFlowFieldFromTiles": (CLAMP,),
+    "ComputeDerivativesKernel": (MIRROR, MIRROR),
+    "ComputeDerivatives2Kernel": (MIRROR,),
+    "ComputeRobustnessMask": (CLAMP,),
+}
+_REF_1D = {"squaredSum", "findMinimum", "conjugateComplexMulKernel", "copyShiftMatrix", "setPointers", "checkForOutliers"}
+_REF_TILE3D = {"normalizedCC", "convertToTilesOverlapBorder", "convertToTilesOverlapPreShift"}
+REF_ERRORS = {1: "__syncthreads() in a kernel run as a loop", 2: "dynamic shared memory request too large",
+              4: "write past the block's dynamic shared memory", 8: "bad block shape"}
+
+
+class RefMissing(RuntimeError):
+    pass
+
+
+class RefKernels:
+    """``call(name, *args, block=(bx, by, bz), filter="exact" | "fixed8")``: the same argument list as
+    ``OracleKernels.call``.  ``flat(name, *args)`` takes the oracle's C argument list (what ``oracle.bindings``
+    passes), so that an object of this class can stand in for the oracle inside ``oracle.pipeline``."""
+    name = "reference"
+
+    def __init__(self, path=None):
+        from oracle.bindings import _SCALAR, _parse
+        from oracle.refbuild import ref_lib_path
+
+        self.path = path or ref_lib_path()
+        if not os.path.exists(self.path):
+            raise RefMissing(self.path)
+        self.cdll = ctypes.CDLL(self.path)
+        self.fns = {}
+        for oname, (_, args) in _parse().items():
+            name = oname[len("orc_"):]
+            try:
+                fn = getattr(self.cdll, "ref_" + name)
+            except AttributeError:
+                continue
+            at = [ctypes.c_void_p if "*" in t else _SCALAR[t.replace("const", "").strip()] for t, _ in args]
+            if name != "set_cfa_pattern":
+                at += [ctypes.c_int] * (4 if name in REF_TEX_ADDRESS else 3)
+            fn.argtypes = at
+            fn.restype = ctypes.c_int
+            self.fns[name] = (fn, [n for _, n in args])
+
+    def has(self, name):
+        return name in self.fns
+
+    def default_block(self, name, flat):
+        names = self.fns[name][1]
+        if name in ("boxFilterWithBorderX", "boxFilterWithBorderY"):
+            side = flat[names.index("tileSize")] + 2 * flat[names.index("maxShift")]
+            return (side, 1, 1) if name.endswith("X") else (1, side, 1)   # the kernels' own constraint
+        if name in _REF_1D:
+            return (64, 1, 1)
+        if name in _REF_TILE3D:
+            return (8, 8, 2)
+        if name in ("concatenateShifts", "separateShifts"):
+            return (4, 4, 4)
+        return (16, 16, 1)
+
+    def flat(self, name, *flat, block=None, address=None, filter="exact"):
+        fn, _ = self.fns[name]
+        conv = []
+        for v in flat:
+            if isinstance(v, np.ndarray):
+                assert v.flags["C_CONTIGUOUS"], "reference arrays must be C-contiguous"
+                conv.append(v.ctypes.data)
+            else:
+                conv.append(v)
+        if name == "set_cfa_pattern":
+            return fn(*conv)
+        conv += list(block or self.default_block(name, flat))
+        if name in REF_TEX_ADDRESS:
+            modes = list(REF_TEX_ADDRESS[name])
+            for i, a in enumerate(address or ()):
+                if a is not None:
+                    modes[i] = {"clamp": CLAMP, "mirror": MIRROR}.get(a, a)
+            fbit = {"exact": 0, "fixed8": 1}[filter]
+            conv.append(sum((m | (fbit << 1)) << (4 * i) for i, m in enumerate(modes)))
+        rc = fn(*conv)
+        assert rc == 0, f"reference shim, {name}: " + ", ".join(v for k, v in REF_ERRORS.items() if rc & k)
+        return rc
+
+    def call(self, fname, *args, block=None, filter="exact"):
+        conv, address = [], []
+        for a in args:
+            if isinstance(a, F3):
+                conv.append(a.v)
+            elif isinstance(a, F2):
+                conv.extend([float(a.v[0]), float(a.v[1])])
+            elif isinstance(a, Tex):
+                conv.extend([a.arr, int(a.pitch), int(a.width), int(a.height)])
+                address.append(a.address)
+            elif isinstance(a, Host):
+                conv.append(a.arr)
+            else:
+                conv.append(a)
+        return self.flat(fname, *conv, block=block, address=address, filter=filter)
+
+    def set_cfa(self, pattern):
+        self.flat("set_cfa_pattern", np.asarray(pattern, np.int32))
+
+
+def load_ref_or_skip():
+    """What the ``ref`` fixture of the reference-pin test modules returns: the library; a failure when it is missing although
+    the reference's sources are on this machine (build() should have made it); a skip when neither is here."""
+    import pytest
+
+    from oracle.refbuild import find_reference_dir
+    try:
+        return RefKernels()
+    except RefMissing as e:
+        if find_reference_dir() is not None:
+            pytest.fail(f"{e} is missing although the reference's sources are on this machine: run __graft_entry__.build()")
+        pytest.skip("neither oracle/_ref/libmfsr_ref.so nor the reference's sources are on this machine")
+
+
+class RefBackedOracle:
+    """Stands in for ``oracle.bindings.oracle()``: every function the reference library has is answered by the
+    reference's kernel, everything else (glue stages, solver, pre-alignment) by the oracle."""
+
+    def __init__(self, ref, oracle_obj):
+        self._ref, self._orc = ref, oracle_obj
+        self.answered = set()
+
+    def __getattr__(self, name):
+        ref, orc = self.__dict__["_ref"], self.__dict__["_orc"]
+        if name == "set_cfa_pattern":
+            def both(p):
+                ref.flat("set_cfa_pattern", p)
+                return orc.set_cfa_pattern(p)
+            return both
+        if ref.has(name):
+            self.__dict__["answered"].add(name)
+            return lambda *a: ref.flat(name, *a)
+        return getattr(orc, name)
