@@ -16,21 +16,16 @@
 //
 // k_defectRepair: a lane reads 16 map bytes; only lanes that see a flagged pixel do anything (per frame: the <= 8 unflagged
 // same-colour neighbours, a sorting network in registers, one 2-byte store).  Its cost is the read of the map.
-#include "common.hpp"
+#include "raw_stage.hpp"
 
 namespace {
 
-constexpr int kDefMaxFrames = 64;  // frame pointers in one launch's argument table; also the counters' range (one byte)
 constexpr int kDefLanes = 64;
 constexpr int kDefWords = 2;                                      // packed words of one lane and row
 constexpr int kDefLaneCols = 2 * kDefWords;                       // columns of one lane: one 8-byte load per row
 constexpr int kDefStripCols = kDefLaneCols * (kDefLanes - 2);     // output columns of one wave's strip
 constexpr int kDefBand = 8;                                       // output rows of one wave's band
 constexpr int kDefWavesPerBlock = 4;
-
-struct DefFrames {
-    uint16_t* p[kDefMaxFrames];
-};
 
 struct DefGeom {
     int pitch;      // bytes
@@ -52,15 +47,6 @@ __device__ __forceinline__ uint32_t def_w(def_u16x2 v) { return __builtin_bit_ca
 __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) { return def_w(__builtin_elementwise_max(def_v(a), def_v(b))); }
 __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) { return def_w(__builtin_elementwise_min(def_v(a), def_v(b))); }
 __device__ __forceinline__ uint32_t pk_subsat(uint32_t a, uint32_t b) { return def_w(__builtin_elementwise_sub_sat(def_v(a), def_v(b))); }
-
-__device__ __forceinline__ uint32_t def_wshr1(uint32_t v)  // lane l <- lane l-1 (lane 0 <- 0)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t def_wshl1(uint32_t v)  // lane l <- lane l+1 (lane 63 <- 0)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true);
-}
 
 // row slot t of a band (t may lie d rows outside the frame): the mirror image about the centre row that uses it, clamped
 // (slots further out serve only rows that are not output)
@@ -106,7 +92,7 @@ static_assert(kDefWords == 2, "def_load and the map store move one lane's row as
 
 // D: lattice step (1 mono, 2 Bayer).  VEC: every frame pointer and the pitch are 8-byte aligned and width % 4 == 0.
 template <int D, bool VEC>
-__global__ __launch_bounds__(kDefWavesPerBlock * kDefLanes) __attribute__((amdgpu_waves_per_eu(3))) void k_defectVotes(DefFrames frames, DefGeom g, uint8_t* map,
+__global__ __launch_bounds__(kDefWavesPerBlock * kDefLanes) __attribute__((amdgpu_waves_per_eu(3))) void k_defectVotes(RawFrames frames, DefGeom g, uint8_t* map,
                                                                                 uint32_t* counts)
 {
     constexpr int kRows = kDefBand + 2 * D;  // row slots of a band: rows y0 - D .. y0 + kDefBand - 1 + D
@@ -167,10 +153,10 @@ __global__ __launch_bounds__(kDefWavesPerBlock * kDefLanes) __attribute__((amdgp
                 cmax[j + 1] = pk_max(vmax[j], ce[j]);
                 cmin[j + 1] = pk_min(vmin[j], ce[j]);
             }
-            cmax[0] = def_wshr1(cmax[kDefWords]);
-            cmin[0] = def_wshr1(cmin[kDefWords]);
-            cmax[kDefWords + 1] = def_wshl1(cmax[1]);
-            cmin[kDefWords + 1] = def_wshl1(cmin[1]);
+            cmax[0] = wave_shr1(cmax[kDefWords]);
+            cmin[0] = wave_shr1(cmin[kDefWords]);
+            cmax[kDefWords + 1] = wave_shl1(cmax[1]);
+            cmin[kDefWords + 1] = wave_shl1(cmin[1]);
 #pragma unroll
             for (int j = 0; j < kDefWords; j++) {
                 uint32_t lmax, rmax, lmin, rmin;  // column max / min at x - D and x + D of both halves
@@ -265,7 +251,7 @@ __device__ __forceinline__ void def_cswap(uint32_t& a, uint32_t& b)
 }
 
 // the new value of pixel (x, y) in every frame: the median of its unflagged same-colour neighbours
-__device__ void def_repair_pixel(const DefFrames& frames, const RepGeom& g, const uint8_t* map, int x, int y)
+__device__ void def_repair_pixel(const RawFramesMut& frames, const RepGeom& g, const uint8_t* map, int x, int y)
 {
     size_t off[8];   // byte offsets of the neighbours in a frame
     bool ok[8];
@@ -308,7 +294,7 @@ __device__ void def_repair_pixel(const DefFrames& frames, const RepGeom& g, cons
     }
 }
 
-__global__ __launch_bounds__(256) void k_defectRepair(DefFrames frames, RepGeom g, const uint8_t* map)
+__global__ __launch_bounds__(256) void k_defectRepair(RawFramesMut frames, RepGeom g, const uint8_t* map)
 {
     const int c16 = (g.width + 15) / 16;  // lanes of one row
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,15 +316,12 @@ __global__ __launch_bounds__(256) void k_defectRepair(DefFrames frames, RepGeom 
         if ((w[k >> 2] >> (8 * (k & 3))) & 0xffu) def_repair_pixel(frames, g, map, x0 + k, y);
 }
 
+// the frames of a vote or a repair: at most kRawMaxFrames (the vote counters hold one byte), any size from one lattice
+// neighbourhood (2d + 1) upwards, odd ones included
 bool def_common_ok(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, int mono)
 {
     const int d = mono ? 1 : 2;
-    if (nFrames < 1 || nFrames > kDefMaxFrames || frames == nullptr) return false;
-    if (width < 2 * d + 1 || height < 2 * d + 1) return false;
-    if ((long long)pitch < 2LL * width || (pitch % 2) != 0) return false;
-    for (int k = 0; k < nFrames; k++)
-        if (frames[k] == nullptr || ((uintptr_t)frames[k] & 1) != 0) return false;
-    return true;
+    return width >= 2 * d + 1 && height >= 2 * d + 1 && raw_frames_ok(nFrames, kRawMaxFrames, frames, pitch, width);
 }
 
 }  // namespace
@@ -354,12 +337,8 @@ extern "C" int mfsr_detectDefects(int nFrames, const uint16_t* const* frames, in
     MFSR_REQUIRE(mapDev != nullptr && mapPitch >= width);
     MFSR_REQUIRE(countsDev == nullptr || ((uintptr_t)countsDev & 3) == 0);
 
-    bool vec = (pitch % 8) == 0 && (width % kDefLaneCols) == 0;
-    DefFrames t = {};
-    for (int k = 0; k < nFrames; k++) {
-        t.p[k] = const_cast<uint16_t*>(frames[k]);  // (read only)
-        vec = vec && ((uintptr_t)frames[k] & 7) == 0;
-    }
+    const bool vec = raw_aligned(nFrames, frames, pitch, 8) && (width % kDefLaneCols) == 0;
+    const RawFrames t = raw_table(nFrames, frames);
     DefGeom g;
     g.pitch = pitch;
     g.width = width;
@@ -395,8 +374,7 @@ extern "C" int mfsr_repairDefects(int nFrames, uint16_t* const* frames, int pitc
     MFSR_REQUIRE(def_common_ok(nFrames, frames, pitch, width, height, mono));
     MFSR_REQUIRE(mapDev != nullptr && mapPitch >= width);
 
-    DefFrames t = {};
-    for (int k = 0; k < nFrames; k++) t.p[k] = frames[k];
+    const RawFramesMut t = raw_table(nFrames, frames);
     RepGeom g;
     g.pitch = pitch;
     g.width = width;

@@ -11,27 +11,19 @@
 //
 // k_applyGains: one lane per 16-byte aligned piece of a row (8 samples: one load, one store); the pieces a row's ends cut, and
 // the samples before the first aligned address, go sample by sample.  Only the status-0 frames are in the launch's table.
-#include "common.hpp"
+#include "raw_stage.hpp"
 
 namespace {
 
-constexpr int kExpMaxFrames = 64;                 // frame pointers in one launch's argument table
-constexpr int kLevLanes = 64;
-constexpr int kLevStripCols = 4 * kLevLanes;      // half-resolution columns of one wave's strip
+constexpr int kLevStripCols = 4 * kRawLanes;      // half-resolution columns of one wave's strip
 constexpr int kLevMinBandRows = 8;                // quad rows of one wave's band: at least this many,
 constexpr int kLevMaxBandRows = 8192;             // at most this many: 4 * 8192 * 65535 < 2^32 per lane and quantity
-constexpr int kLevChunk = 4;                      // rows loaded per step (two steps in flight)
 constexpr int kLevWavesPerBlock = 4;
-constexpr long long kLevMaxArea = 1LL << 23;      // as mfsr_frameSharpness: S < 2^39, C <= 2^23
-
-struct LevFrames {
-    const uint16_t* p[kExpMaxFrames];
-};
 
 struct LevGeom {
     int pitch;           // bytes
     int hw;              // half-resolution width
-    int x0, y0, x1, y1;  // half-resolution rectangle
+    int x0, y0, x1, y1;  // half-resolution rectangle (within kRawMaxArea: S < 2^39, C <= 2^23)
     int cs0;             // first column of strip 0 (a multiple of 4, <= x0)
     int bandRows;
     int nStrips, nBands;
@@ -39,44 +31,11 @@ struct LevGeom {
     int sat;
 };
 
-// quad rows 2r (a) and 2r+1 (b) of half-resolution columns col .. col+3: one 32-bit word per column, x = 0 in the low half.
-// Branch-free: a column outside the frame reads a clamped in-frame address instead (such columns are masked out of the sums).
-// VEC: one 16-byte load per row at col clamped to [0, hw - 4] -- exact for every column inside the frame when hw % 4 == 0.
-template <bool VEC>
-__device__ __forceinline__ void lev_load(const char* rowA, int pitch, int col, int hw, uint4& a, uint4& b)
-{
-    const char* rowB = rowA + pitch;
-    if (VEC) {
-        const size_t o = 4 * (size_t)clampi(col, 0, hw - 4);
-        a = *(const uint4*)(rowA + o);
-        b = *(const uint4*)(rowB + o);
-        return;
-    }
-    uint32_t wa[4], wb[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const size_t o = 4 * (size_t)clampi(col + j, 0, hw - 1);
-        const uint16_t* pa = (const uint16_t*)(rowA + o);
-        const uint16_t* pb = (const uint16_t*)(rowB + o);
-        wa[j] = (uint32_t)pa[0] | ((uint32_t)pa[1] << 16);
-        wb[j] = (uint32_t)pb[0] | ((uint32_t)pb[1] << 16);
-    }
-    a = make_uint4(wa[0], wa[1], wa[2], wa[3]);
-    b = make_uint4(wb[0], wb[1], wb[2], wb[3]);
-}
-
-__device__ __forceinline__ unsigned long long lev_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int o = kLevLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // VEC: every frame pointer and the pitch are 16-byte aligned and hw % 4 == 0 (16-byte loads); otherwise 16-bit loads
 template <bool VEC>
-__global__ __launch_bounds__(kLevWavesPerBlock * kLevLanes) void k_frameLevels(LevFrames frames, LevGeom g, unsigned long long* levels)
+__global__ __launch_bounds__(kLevWavesPerBlock * kRawLanes) void k_frameLevels(RawFrames frames, LevGeom g, unsigned long long* levels)
 {
-    const int lane = threadIdx.x & (kLevLanes - 1);
+    const int lane = threadIdx.x & (kRawLanes - 1);
     const int wave = blockIdx.x * kLevWavesPerBlock + (threadIdx.x >> 6);
     if (wave >= g.nStrips * g.nBands) return;  // (whole waves)
     const int strip = wave % g.nStrips, band = wave / g.nStrips;
@@ -95,16 +54,16 @@ __global__ __launch_bounds__(kLevWavesPerBlock * kLevLanes) void k_frameLevels(L
     const size_t step = (size_t)2 * g.pitch;  // one quad row = two raw rows
     // double-buffered chunks: the loads of chunk c+1 are in flight while chunk c is reduced (rows past the band re-read its
     // last row: every load is unconditional)
-    uint4 a[kLevChunk], b[kLevChunk];
+    uint4 a[kRawChunk], b[kRawChunk];
 #pragma unroll
-    for (int k = 0; k < kLevChunk; k++) lev_load<VEC>(row + (size_t)min(k, n - 1) * step, g.pitch, col, g.hw, a[k], b[k]);
-    for (int t0 = 0; t0 < n; t0 += kLevChunk) {
-        uint4 na[kLevChunk], nb[kLevChunk];
+    for (int k = 0; k < kRawChunk; k++) quad_rows_load<VEC>(row + (size_t)min(k, n - 1) * step, g.pitch, col, g.hw, a[k], b[k]);
+    for (int t0 = 0; t0 < n; t0 += kRawChunk) {
+        uint4 na[kRawChunk], nb[kRawChunk];
 #pragma unroll
-        for (int k = 0; k < kLevChunk; k++)
-            lev_load<VEC>(row + (size_t)min(t0 + kLevChunk + k, n - 1) * step, g.pitch, col, g.hw, na[k], nb[k]);
+        for (int k = 0; k < kRawChunk; k++)
+            quad_rows_load<VEC>(row + (size_t)min(t0 + kRawChunk + k, n - 1) * step, g.pitch, col, g.hw, na[k], nb[k]);
 #pragma unroll
-        for (int k = 0; k < kLevChunk; k++) {
+        for (int k = 0; k < kRawChunk; k++) {
             if (t0 + k >= n) break;
             const uint32_t wa[4] = {a[k].x, a[k].y, a[k].z, a[k].w}, wb[4] = {b[k].x, b[k].y, b[k].z, b[k].w};
 #pragma unroll
@@ -119,7 +78,7 @@ __global__ __launch_bounds__(kLevWavesPerBlock * kLevLanes) void k_frameLevels(L
             }
         }
 #pragma unroll
-        for (int k = 0; k < kLevChunk; k++) {
+        for (int k = 0; k < kRawChunk; k++) {
             a[k] = na[k];
             b[k] = nb[k];
         }
@@ -127,33 +86,14 @@ __global__ __launch_bounds__(kLevWavesPerBlock * kLevLanes) void k_frameLevels(L
     unsigned long long* out = levels + 5 * (size_t)blockIdx.y;
 #pragma unroll
     for (int q = 0; q < 5; q++) {
-        const unsigned long long t = lev_wave_sum(q < 4 ? s[q] : cnt);
+        const unsigned long long t = wave_sum<unsigned long long>(q < 4 ? s[q] : cnt);
         if (lane == 0 && t != 0) atomicAdd(&out[q], t);
     }
 }
 
-// workgroups of k_frameLevels the current device holds at once (CUs x occupancy), cached per device
-int lev_resident_blocks(bool vec)
-{
-    constexpr int kDevs = 64;
-    static int cache[2][kDevs];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) dev = -1;
-    if (dev >= 0 && cache[vec][dev] > 0) return cache[vec][dev];
-    int cus = 0, perCU = 0;
-    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const hipError_t e = vec ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_frameLevels<true>, kLevWavesPerBlock * kLevLanes, 0)
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_frameLevels<false>, kLevWavesPerBlock * kLevLanes, 0);
-    if (e != hipSuccess || perCU <= 0) perCU = 4;
-    const int r = cus * perCU;
-    if (dev >= 0) cache[vec][dev] = r;
-    return r;
-}
-
 // ---- apply ----------------------------------------------------------------------------------------------------------------
-struct GainFrames {
-    uint16_t* p[kExpMaxFrames];
-    int gain[kExpMaxFrames][4];  // Q16 gain of quad position q
+struct GainFrames : RawFramesMut {
+    int gain[kRawMaxFrames][4];  // Q16 gain of quad position q
 };
 
 struct GainGeom {
@@ -204,16 +144,6 @@ __global__ __launch_bounds__(256) void k_applyGains(GainFrames frames, GainGeom 
     }
 }
 
-bool exp_frames_ok(int nFrames, const uint16_t* const* frames, int pitch, int width, int height)
-{
-    if (nFrames < 1 || nFrames > kExpMaxFrames || frames == nullptr) return false;
-    if (width <= 0 || height <= 0 || (width % 2) != 0 || (height % 2) != 0) return false;
-    if ((long long)pitch < 2LL * width || (pitch % 2) != 0) return false;
-    for (int k = 0; k < nFrames; k++)
-        if (frames[k] == nullptr || ((uintptr_t)frames[k] & 1) != 0) return false;
-    return true;
-}
-
 bool exp_levels_ok(const int32_t black[4], int sat, int maxValue)
 {
     if (black == nullptr) return false;
@@ -236,30 +166,19 @@ bool exp_classes(const int32_t cfa[4], int mono, int cls[4])
     return true;
 }
 
-bool exp_bounds_ok(int deadband, int minGain, int maxGain)
-{
-    return deadband >= 0 && deadband < 65536 && minGain >= 4096 && minGain <= 65536 && maxGain >= 65536 && maxGain <= 1048576;
-}
-
 }  // namespace
 
 extern "C" int mfsr_frameLevels(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, const int32_t black[4],
                                 int sat, const int32_t rect[4], long long* levelsDev, mfsr_stream_t stream)
 {
     // host validation first: nothing below touches the device before every argument has passed
-    MFSR_REQUIRE(exp_frames_ok(nFrames, frames, pitch, width, height));
+    MFSR_REQUIRE(raw_even_ok(width, height) && raw_frames_ok(nFrames, kRawMaxFrames, frames, pitch, width));
     MFSR_REQUIRE(exp_levels_ok(black, sat, 65535));
-    MFSR_REQUIRE(rect != nullptr && levelsDev != nullptr && ((uintptr_t)levelsDev & 7) == 0);
-    const int hw = width / 2, hh = height / 2;
+    MFSR_REQUIRE(raw_half_rect_ok(rect, width, height) && levelsDev != nullptr && ((uintptr_t)levelsDev & 7) == 0);
+    const int hw = width / 2;
     const int x0 = rect[0], y0 = rect[1], x1 = rect[2], y1 = rect[3];
-    MFSR_REQUIRE(x0 >= 1 && x0 < x1 && x1 <= hw - 1 && y0 >= 1 && y0 < y1 && y1 <= hh - 1);
-    MFSR_REQUIRE((long long)(x1 - x0) * (y1 - y0) <= kLevMaxArea);
-    bool aligned16 = (pitch % 16) == 0 && hw % 4 == 0;
-    LevFrames t = {};
-    for (int k = 0; k < nFrames; k++) {
-        t.p[k] = frames[k];
-        aligned16 = aligned16 && ((uintptr_t)frames[k] & 15) == 0;
-    }
+    const bool aligned16 = raw_aligned(nFrames, frames, pitch, 16) && hw % 4 == 0;
+    const RawFrames t = raw_table(nFrames, frames);
 
     LevGeom g;
     g.pitch = pitch;
@@ -272,20 +191,15 @@ extern "C" int mfsr_frameLevels(int nFrames, const uint16_t* const* frames, int 
     g.nStrips = (int)mfsr_cdiv(x1 - g.cs0, kLevStripCols);
     for (int q = 0; q < 4; q++) g.black[q] = black[q];
     g.sat = sat;
-    // bands as short as keeps the launch within one round of resident workgroups (every wave then streams from the start to
-    // the end of the launch, no tail), within [kLevMinBandRows, kLevMaxBandRows]
-    const int rows = y1 - y0;
-    const int resident = lev_resident_blocks(aligned16);
-    const int wavesPerFrame = kLevWavesPerBlock * (resident / nFrames > 1 ? resident / nFrames : 1);
-    const int bands = wavesPerFrame / g.nStrips > 1 ? wavesPerFrame / g.nStrips : 1;
-    g.bandRows = (int)mfsr_cdiv(rows, bands);
-    g.bandRows = g.bandRows < kLevMinBandRows ? kLevMinBandRows : g.bandRows;
-    g.bandRows = g.bandRows > kLevMaxBandRows ? kLevMaxBandRows : g.bandRows;
-    g.nBands = (int)mfsr_cdiv(rows, g.bandRows);
+    const int threads = kLevWavesPerBlock * kRawLanes;
+    const int resident = aligned16 ? resident_blocks<k_frameLevels<true>>(threads) : resident_blocks<k_frameLevels<false>>(threads);
+    const RawBands bands = plan_bands(y1 - y0, g.nStrips, nFrames, resident, kLevWavesPerBlock, kLevMinBandRows, kLevMaxBandRows);
+    g.bandRows = bands.rows;
+    g.nBands = bands.n;
 
     MFSR_HIP_TRY(hipMemsetAsync(levelsDev, 0, 5 * sizeof(long long) * (size_t)nFrames, mfsr_s(stream)));
     const unsigned blocks = mfsr_cdiv((long long)g.nStrips * g.nBands, kLevWavesPerBlock);
-    const dim3 grid(blocks, (unsigned)nFrames), block(kLevWavesPerBlock * kLevLanes);
+    const dim3 grid(blocks, (unsigned)nFrames), block(threads);
     if (aligned16)
         hipLaunchKernelGGL(k_frameLevels<true>, grid, block, 0, mfsr_s(stream), t, g, (unsigned long long*)levelsDev);
     else
@@ -298,7 +212,7 @@ extern "C" int mfsr_exposure_gains(int n, const long long* levels, int reference
 {
     MFSR_REQUIRE(n >= 1 && levels != nullptr && gains != nullptr && status != nullptr);
     MFSR_REQUIRE(reference >= 0 && reference < n);
-    MFSR_REQUIRE(exp_bounds_ok(deadband, minGain, maxGain));
+    MFSR_REQUIRE(exposure_bounds_ok(deadband, minGain, maxGain));
     int cls[4];
     MFSR_REQUIRE(exp_classes(cfa, mono, cls));
     for (long long i = 0; i < 5LL * n; i++) MFSR_REQUIRE(levels[i] >= 0 && levels[i] < (1LL << 48));  // (products < 2^99)
@@ -367,7 +281,7 @@ extern "C" int mfsr_applyGains(int nFrames, uint16_t* const* frames, int pitch, 
                                const int32_t black[4], int sat, int maxValue, const int32_t* gains, const int32_t* status,
                                mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(exp_frames_ok(nFrames, frames, pitch, width, height));
+    MFSR_REQUIRE(raw_even_ok(width, height) && raw_frames_ok(nFrames, kRawMaxFrames, frames, pitch, width));
     MFSR_REQUIRE(exp_levels_ok(black, sat, maxValue));
     MFSR_REQUIRE(gains != nullptr && status != nullptr);
     int cls[4];

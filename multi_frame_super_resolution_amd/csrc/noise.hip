@@ -17,13 +17,12 @@
 // of a (q, level) row is the sum of the row's counters, taken in the same sweep.  Word w of a row holds bins w and w + 136, so
 // that the lanes of one atomic instruction address one contiguous run and the half of a row an image does not reach (its
 // variances span a few octaves) costs no instruction at all.
-#include "common.hpp"
+#include "raw_stage.hpp"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kNoiseMaxFrames = 64;
 constexpr int kNQ = 4, kNL = 64, kNV = 272;
 constexpr int kNRows = kNQ * kNL;              // (q, level) rows of the tables
 constexpr int kNRowWords = kNV / 2;            // 32-bit words of a row in LDS: bins w (low half) and w + 136 (high half)
@@ -31,10 +30,6 @@ constexpr int kNoiseThreads = 1024;
 constexpr int kNoiseWaves = kNoiseThreads / 64;
 constexpr int kNoiseMaxChunk = 65535;          // blocks per workgroup: a 16-bit counter cannot overflow
 constexpr double kChi2x2 = 14.6882;            // 2 x the median of chi-square with 8 degrees of freedom
-
-struct NoiseFrames {
-    const uint16_t* p[kNoiseMaxFrames];
-};
 
 struct NoiseGeom {
     int pitch;               // bytes
@@ -48,7 +43,7 @@ struct NoiseGeom {
 
 // raw rows 8*by .. 8*by + 7 of block i (one 16-byte piece each: 4 words, x even in the low half)
 template <bool VEC>
-__device__ __forceinline__ void noise_load(const NoiseFrames& frames, const NoiseGeom& g, unsigned i, uint4 r[8])
+__device__ __forceinline__ void noise_load(const RawFrames& frames, const NoiseGeom& g, unsigned i, uint4 r[8])
 {
     const unsigned perFrame = (unsigned)g.nbx * (unsigned)g.nby;
     const unsigned f = i / perFrame, j = i - f * perFrame;
@@ -67,16 +62,9 @@ __device__ __forceinline__ void noise_load(const NoiseFrames& frames, const Nois
     }
 }
 
-__device__ __forceinline__ uint32_t noise_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // VEC: every frame pointer and the pitch are 16-byte aligned (16-byte loads); otherwise 16-bit loads
 template <bool VEC>
-__global__ __launch_bounds__(kNoiseThreads) void k_noiseStats(NoiseFrames frames, NoiseGeom g, uint32_t* hist,
+__global__ __launch_bounds__(kNoiseThreads) void k_noiseStats(RawFrames frames, NoiseGeom g, uint32_t* hist,
                                                                unsigned long long* levelSum, unsigned long long* count)
 {
     __shared__ uint32_t sHist[kNRows * kNRowWords];
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(kNoiseThreads) void k_noiseStats(NoiseFrames frames
             const uint32_t row0 = __shfl(row, first), key0 = __shfl(key, first);
             const bool sameRow = __ballot(ok && row != row0) == 0, sameKey = __ballot(ok && key != key0) == 0;
             if (sameRow) {                                       // one level for the whole wave: one add of the wave's sum
-                const uint32_t s = noise_wave_sum(ok ? S[q] : 0u);
+                const uint32_t s = wave_sum(ok ? S[q] : 0u);
                 if (lane == first) atomicAdd(&sSum[row], (unsigned long long)s);
             } else if (ok)
                 atomicAdd(&sSum[row], (unsigned long long)S[q]);
@@ -165,7 +153,7 @@ __global__ __launch_bounds__(kNoiseThreads) void k_noiseStats(NoiseFrames frames
             if (hi) atomicAdd(&hist[(size_t)row * kNV + kNRowWords + w], hi);
             n += lo + hi;
         }
-        n = noise_wave_sum(n);
+        n = wave_sum(n);
         if (lane == 0 && n != 0) {
             atomicAdd(&count[row], (unsigned long long)n);
             atomicAdd(&levelSum[row], sSum[row]);
@@ -201,9 +189,7 @@ extern "C" int mfsr_noiseStats(int nFrames, const uint16_t* const* frames, int p
                                mfsr_stream_t stream)
 {
     // host validation first: nothing below touches the device before every argument has passed
-    MFSR_REQUIRE(nFrames >= 1 && nFrames <= kNoiseMaxFrames && frames != nullptr);
-    MFSR_REQUIRE(width > 0 && height > 0 && (width % 2) == 0 && (height % 2) == 0);
-    MFSR_REQUIRE((long long)pitch >= 2LL * width && (pitch % 2) == 0);
+    MFSR_REQUIRE(raw_even_ok(width, height) && raw_frames_ok(nFrames, kRawMaxFrames, frames, pitch, width));
     MFSR_REQUIRE(0 < sat && sat <= 65535 && black != nullptr);
     for (int q = 0; q < 4; q++) MFSR_REQUIRE(black[q] >= 0 && black[q] < sat);
     MFSR_REQUIRE(rect != nullptr && histDev != nullptr && levelSumDev != nullptr && countDev != nullptr);
@@ -211,13 +197,8 @@ extern "C" int mfsr_noiseStats(int nFrames, const uint16_t* const* frames, int p
     const int gw = width / 8, gh = height / 8;  // the block grid: a partial block at the right or bottom edge is not in it
     const int bx0 = rect[0], by0 = rect[1], bx1 = rect[2], by1 = rect[3];
     MFSR_REQUIRE(bx0 >= 0 && bx0 < bx1 && bx1 <= gw && by0 >= 0 && by0 < by1 && by1 <= gh);
-    bool aligned16 = (pitch % 16) == 0;
-    NoiseFrames t = {};
-    for (int k = 0; k < nFrames; k++) {
-        MFSR_REQUIRE(frames[k] != nullptr && ((uintptr_t)frames[k] & 1) == 0);
-        t.p[k] = frames[k];
-        aligned16 = aligned16 && ((uintptr_t)frames[k] & 15) == 0;
-    }
+    const bool aligned16 = raw_aligned(nFrames, frames, pitch, 16);
+    const RawFrames t = raw_table(nFrames, frames);
     const long long total = (long long)nFrames * (bx1 - bx0) * (by1 - by0);
     MFSR_REQUIRE(total < (1LL << 31));
 

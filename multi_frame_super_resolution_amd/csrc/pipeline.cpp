@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "raw_stage.hpp"
 
 namespace {
 
@@ -2109,6 +2110,14 @@ static void select_rect(const mfsr_burst* b, int32_t r[4])
     r[3] = hi[1];
 }
 
+// the result table of a raw-domain stage: `bytes` from the device to the host on this stream, complete on return
+static int download(void* host, const void* dev, size_t bytes, mfsr_stream_t stream)
+{
+    MFSR_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16_t* const* frames, int candidates, float keepRatio,
                                         long long* sumsDev, int* reference, int32_t* keep, long long* sums, int32_t rect[4],
                                         mfsr_stream_t stream)
@@ -2121,8 +2130,7 @@ extern "C" int mfsr_burst_select_frames(mfsr_burst* b, int nFrames, const uint16
     select_rect(b, r);
     TRY(mfsr_frameSharpness(nFrames, frames, 2 * c.width, c.width, c.height, c.cfa, c.mono, r, sumsDev, stream));
     std::vector<long long> host((size_t)nFrames);
-    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), sumsDev, sizeof(long long) * (size_t)nFrames, hipMemcpyDeviceToHost, mfsr_s(stream)));
-    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    TRY(download(host.data(), sumsDev, sizeof(long long) * host.size(), stream));
     std::vector<int32_t> k((size_t)nFrames);
     TRY(mfsr_select_frames(nFrames, host.data(), candidates, keepRatio, reference, k.data()));
     if (keep) memcpy(keep, k.data(), sizeof(int32_t) * (size_t)nFrames);
@@ -2142,10 +2150,7 @@ extern "C" int mfsr_burst_repair_defects(mfsr_burst* b, int nFrames, uint16_t* c
     TRY(mfsr_detectDefects(nFrames, frames, 2 * c.width, c.width, c.height, c.mono, threshold, spread, minVotes, mapDev, c.width,
                            countsDev, stream));
     TRY(mfsr_repairDefects(nFrames, frames, 2 * c.width, c.width, c.height, c.mono, mapDev, c.width, stream));
-    if (counts) {
-        MFSR_HIP_TRY(hipMemcpyAsync(counts, countsDev, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, mfsr_s(stream)));
-        MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
-    }
+    if (counts) TRY(download(counts, countsDev, 2 * sizeof(uint32_t), stream));
     return MFSR_OK;
 }
 
@@ -2183,7 +2188,7 @@ extern "C" int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* c
 {
     MFSR_REQUIRE(b && frames && levelsDev);
     MFSR_REQUIRE(nFrames >= 1 && nFrames <= 64 && reference >= 0 && reference < nFrames);
-    MFSR_REQUIRE(deadband >= 0 && deadband < 65536 && minGain >= 4096 && minGain <= 65536 && maxGain >= 65536 && maxGain <= 1048576);
+    MFSR_REQUIRE(exposure_bounds_ok(deadband, minGain, maxGain));
     const mfsr_config& c = b->cfg;
     int32_t black[4], sat = 0, maxValue = 0, r[4];
     TRY(mfsr_exposure_defaults(&c, black, &sat, &maxValue, nullptr, nullptr, nullptr, nullptr));
@@ -2191,8 +2196,7 @@ extern "C" int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* c
     select_rect(b, r);
     TRY(mfsr_frameLevels(nFrames, frames, 2 * c.width, c.width, c.height, black, sat, r, levelsDev, stream));
     std::vector<long long> host(5 * (size_t)nFrames);
-    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), levelsDev, sizeof(long long) * host.size(), hipMemcpyDeviceToHost, mfsr_s(stream)));
-    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    TRY(download(host.data(), levelsDev, sizeof(long long) * host.size(), stream));
     std::vector<int32_t> g(3 * (size_t)nFrames), st((size_t)nFrames);
     TRY(mfsr_exposure_gains(nFrames, host.data(), reference, c.cfa, c.mono, perColour, deadband, minGain, maxGain, g.data(), st.data()));
     TRY(mfsr_applyGains(nFrames, frames, 2 * c.width, c.width, c.height, c.cfa, c.mono, black, sat, maxValue, g.data(), st.data(), stream));
@@ -2239,8 +2243,7 @@ extern "C" int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint
     long long* countDev = sumDev + MFSR_NOISE_LEVEL_ENTRIES;
     TRY(mfsr_noiseStats(nFrames, frames, 2 * c.width, c.width, c.height, black, sat, r, histDev, sumDev, countDev, stream));
     std::vector<unsigned char> host(MFSR_NOISE_SCRATCH_BYTES);
-    MFSR_HIP_TRY(hipMemcpyAsync(host.data(), scratchDev, host.size(), hipMemcpyDeviceToHost, mfsr_s(stream)));
-    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    TRY(download(host.data(), scratchDev, host.size(), stream));
     const uint32_t* hist = (const uint32_t*)host.data();
     const long long* sum = (const long long*)(host.data() + sizeof(uint32_t) * MFSR_NOISE_HIST_ENTRIES);
     double a = 0, bt = 0;

@@ -92,40 +92,6 @@ def sharpness_rect(cfg: capi.Config, window: Optional[Sequence[int]] = None) -> 
     return lo[0], lo[1], hi[0], hi[1]
 
 
-def frame_sharpness(frames: Sequence[torch.Tensor], cfg: capi.Config,
-                    rect: Optional[Sequence[int]] = None) -> torch.Tensor:
-    """Sharpness score of every frame (mfsr_frameSharpness): an int64 device tensor, exact.  ``frames``: 16-bit [H, W]
-    device tensors of cfg's size, rows contiguous and all with the same row stride (pitched views are fine).  ``rect``:
-    the half-resolution rectangle (x0, y0, x1, y1) to score; None = the whole-frame rule of ``sharpness_rect``."""
-    frames = list(frames)
-    if not frames:
-        raise ValueError("frame_sharpness needs at least one frame")
-    dev = frames[0].device
-    pitch = frames[0].stride(0) * 2
-    for f in frames:
-        if (f.device != dev or not f.is_cuda or f.dtype not in (torch.int16, torch.uint16) or f.dim() != 2
-                or tuple(f.shape) != (cfg.height, cfg.width) or f.stride(1) != 1 or f.stride(0) * 2 != pitch):
-            raise ValueError(f"frames must be 16-bit {cfg.height}x{cfg.width} tensors on one HIP device with contiguous rows "
-                             "and one row stride")
-    r = sharpness_rect(cfg) if rect is None else tuple(int(v) for v in rect)
-    n = len(frames)
-    with torch.cuda.device(dev):
-        sums = torch.empty(n, dtype=torch.int64, device=dev)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        capi.lib().frameSharpness(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0,
-                                  (ctypes.c_int32 * 4)(*r), sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    return sums
-
-
-def defect_defaults(cfg: capi.Config, n_frames: int) -> Tuple[int, int, int]:
-    """(threshold, spread, min_votes) the defect vote uses when none are given: a 64th of the white level, half the local
-    range of the neighbours on top of it (spread 2, in quarters), and three quarters of the frames but always a strict
-    majority.  Pure Python (no device)."""
-    threshold = max(1, int(max(cfg.white)) // 64)
-    min_votes = max(n_frames // 2 + 1, -(-3 * n_frames // 4))
-    return threshold, 2, min_votes
-
-
 def _raw_frames(frames: Sequence[torch.Tensor], cfg: capi.Config):
     """Check a list of raw device frames (one device, one row stride); returns (device, pitch in bytes)."""
     if not frames:
@@ -138,6 +104,41 @@ def _raw_frames(frames: Sequence[torch.Tensor], cfg: capi.Config):
             raise ValueError(f"frames must be 16-bit {cfg.height}x{cfg.width} tensors on one HIP device with contiguous rows "
                              "and one row stride")
     return dev, pitch
+
+
+def _ptr_table(frames: Sequence[torch.Tensor]):
+    """The frame pointer table of a C-ABI call (``const uint16_t* const*``)."""
+    return (ctypes.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
+
+
+def _i4(seq):
+    """Four integers as the ``int32_t[4]`` of a C-ABI call (a CFA, black levels, a rectangle)."""
+    return (ctypes.c_int32 * 4)(*seq)
+
+
+def frame_sharpness(frames: Sequence[torch.Tensor], cfg: capi.Config,
+                    rect: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Sharpness score of every frame (mfsr_frameSharpness): an int64 device tensor, exact.  ``frames``: 16-bit [H, W]
+    device tensors of cfg's size, rows contiguous and all with the same row stride (pitched views are fine).  ``rect``:
+    the half-resolution rectangle (x0, y0, x1, y1) to score; None = the whole-frame rule of ``sharpness_rect``."""
+    frames = list(frames)
+    dev, pitch = _raw_frames(frames, cfg)
+    r = sharpness_rect(cfg) if rect is None else tuple(int(v) for v in rect)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        sums = torch.empty(n, dtype=torch.int64, device=dev)
+        capi.lib().frameSharpness(n, _ptr_table(frames), pitch, cfg.width, cfg.height, _i4(cfg.cfa), 1 if cfg.mono else 0, _i4(r),
+                                  sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return sums
+
+
+def defect_defaults(cfg: capi.Config, n_frames: int) -> Tuple[int, int, int]:
+    """(threshold, spread, min_votes) the defect vote uses when none are given: a 64th of the white level, half the local
+    range of the neighbours on top of it (spread 2, in quarters), and three quarters of the frames but always a strict
+    majority.  Pure Python (no device)."""
+    threshold = max(1, int(max(cfg.white)) // 64)
+    min_votes = max(n_frames // 2 + 1, -(-3 * n_frames // 4))
+    return threshold, 2, min_votes
 
 
 def detect_defects(frames: Sequence[torch.Tensor], cfg: capi.Config, threshold: Optional[int] = None, spread: int = 2,
@@ -154,8 +155,7 @@ def detect_defects(frames: Sequence[torch.Tensor], cfg: capi.Config, threshold: 
     with torch.cuda.device(dev):
         dmap = torch.empty(cfg.height, cfg.width, dtype=torch.uint8, device=dev)
         counts = torch.empty(2, dtype=torch.int32, device=dev)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        capi.lib().detectDefects(n, ptrs, pitch, cfg.width, cfg.height, 1 if cfg.mono else 0, threshold, int(spread), min_votes,
+        capi.lib().detectDefects(n, _ptr_table(frames), pitch, cfg.width, cfg.height, 1 if cfg.mono else 0, threshold, int(spread), min_votes,
                                  dmap.data_ptr(), dmap.stride(0), counts.data_ptr(), torch.cuda.current_stream().cuda_stream)
         hot, cold = counts.cpu().tolist()
     return dmap, (hot, cold)
@@ -170,10 +170,8 @@ def repair_defects(frames: Sequence[torch.Tensor], defect_map: torch.Tensor, cfg
             or defect_map.stride(1) != 1):
         raise ValueError(f"defect_map must be a uint8 {cfg.height}x{cfg.width} tensor on the frames' device with contiguous rows")
     out = [f.clone(memory_format=torch.contiguous_format) for f in frames]
-    n = len(out)
     with torch.cuda.device(dev):
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in out])
-        capi.lib().repairDefects(n, ptrs, 2 * cfg.width, cfg.width, cfg.height, 1 if cfg.mono else 0, defect_map.data_ptr(),
+        capi.lib().repairDefects(len(out), _ptr_table(out), 2 * cfg.width, cfg.width, cfg.height, 1 if cfg.mono else 0, defect_map.data_ptr(),
                                  defect_map.stride(0), torch.cuda.current_stream().cuda_stream)
     return out
 
@@ -214,10 +212,8 @@ def frame_levels(frames: Sequence[torch.Tensor], cfg: capi.Config, rect: Optiona
     n = len(frames)
     with torch.cuda.device(dev):
         levels = torch.empty(n, 5, dtype=torch.int64, device=dev)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        capi.lib().frameLevels(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*d.black),
-                               d.sat if sat is None else int(sat), (ctypes.c_int32 * 4)(*r), levels.data_ptr(),
-                               torch.cuda.current_stream().cuda_stream)
+        capi.lib().frameLevels(n, _ptr_table(frames), pitch, cfg.width, cfg.height, _i4(d.black),
+                               d.sat if sat is None else int(sat), _i4(r), levels.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return levels
 
 
@@ -234,7 +230,7 @@ def exposure_gains(levels, cfg: capi.Config, reference: int, per_colour: bool = 
     d = exposure_defaults(cfg)
     flat = (ctypes.c_longlong * (5 * n))(*[v for row in rows for v in row])
     gains, status = (ctypes.c_int32 * (3 * n))(), (ctypes.c_int32 * n)()
-    capi.lib().exposure_gains(n, flat, int(reference), (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0, 1 if per_colour else 0,
+    capi.lib().exposure_gains(n, flat, int(reference), _i4(cfg.cfa), 1 if cfg.mono else 0, 1 if per_colour else 0,
                               d.deadband if deadband is None else int(deadband), d.min_gain if min_gain is None else int(min_gain),
                               d.max_gain if max_gain is None else int(max_gain), gains, status)
     return [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)], [int(s) for s in status]
@@ -251,9 +247,8 @@ def apply_gains(frames: Sequence[torch.Tensor], gains, status, cfg: capi.Config)
     d = exposure_defaults(cfg)
     out = [f.clone(memory_format=torch.contiguous_format) for f in frames]
     with torch.cuda.device(dev):
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in out])
-        capi.lib().applyGains(n, ptrs, 2 * cfg.width, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*cfg.cfa), 1 if cfg.mono else 0,
-                              (ctypes.c_int32 * 4)(*d.black), d.sat, d.max_value,
+        capi.lib().applyGains(n, _ptr_table(out), 2 * cfg.width, cfg.width, cfg.height, _i4(cfg.cfa), 1 if cfg.mono else 0,
+                              _i4(d.black), d.sat, d.max_value,
                               (ctypes.c_int32 * (3 * n))(*[int(g) for row in gains for g in row]),
                               (ctypes.c_int32 * n)(*[int(s) for s in status]), torch.cuda.current_stream().cuda_stream)
     return out
@@ -292,10 +287,9 @@ def noise_stats(frames: Sequence[torch.Tensor], cfg: capi.Config, rect: Optional
         hist = torch.empty(4, 64, 272, dtype=torch.int32, device=dev)
         level_sum = torch.empty(4, 64, dtype=torch.int64, device=dev)
         count = torch.empty(4, 64, dtype=torch.int64, device=dev)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        capi.lib().noiseStats(n, ptrs, pitch, cfg.width, cfg.height, (ctypes.c_int32 * 4)(*d.black),
-                              d.sat if sat is None else int(sat), (ctypes.c_int32 * 4)(*r), hist.data_ptr(), level_sum.data_ptr(),
-                              count.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        capi.lib().noiseStats(n, _ptr_table(frames), pitch, cfg.width, cfg.height, _i4(d.black),
+                              d.sat if sat is None else int(sat), _i4(r), hist.data_ptr(), level_sum.data_ptr(), count.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream)
     return NoiseStats(hist, level_sum, count)
 
 
@@ -315,7 +309,7 @@ def noise_fit(stats, cfg: capi.Config, min_blocks: Optional[int] = None):
     d = noise_defaults(cfg)
     a, b = ctypes.c_double(), ctypes.c_double()
     st, n = ctypes.c_int32(), ctypes.c_int32()
-    capi.lib().noise_fit(hist.ctypes.data, level_sum.ctypes.data, count.ctypes.data, (ctypes.c_int32 * 4)(*d.black),
+    capi.lib().noise_fit(hist.ctypes.data, level_sum.ctypes.data, count.ctypes.data, _i4(d.black),
                          (ctypes.c_float * 4)(*d.white), d.min_blocks if min_blocks is None else int(min_blocks),
                          ctypes.byref(a), ctypes.byref(b), ctypes.byref(st), ctypes.byref(n))
     return a.value, b.value, st.value, n.value
@@ -479,15 +473,64 @@ class BurstPipeline:
                                  self.out16.data_ptr(), row0, rows, self._stream())
         return self.out16
 
+    # ---- the raw-domain steps, in the order DESIGN.md section 2.14 fixes: repair, select, match, then the burst.  ``work``:
+    #      checked frames the step may write (clones of the caller's) ----
+    def _checked(self, frames: Sequence[torch.Tensor], clone: bool):
+        for f in frames:
+            self._check_raw(f)
+        return [f.clone() for f in frames] if clone else list(frames)
+
+    def _repair(self, work, threshold: Optional[int], spread: int, min_votes: Optional[int]):
+        """mfsr_burst_repair_defects on ``work``, in place; sets ``defects`` and ``defect_map``."""
+        n = len(work)
+        t0, _, v0 = defect_defaults(self.cfg, n)
+        self.defect_map = torch.empty(self.cfg.height, self.cfg.width, dtype=torch.uint8, device=self.device)
+        counts_dev = torch.empty(2, dtype=torch.int32, device=self.device)
+        counts = (ctypes.c_uint32 * 2)()
+        self.L.burst_repair_defects(self._h, n, _ptr_table(work), t0 if threshold is None else int(threshold), int(spread),
+                                    v0 if min_votes is None else int(min_votes), self.defect_map.data_ptr(),
+                                    counts_dev.data_ptr(), counts, self._stream())
+        self.defects = (int(counts[0]), int(counts[1]))
+
+    def _select(self, work, candidates: int, keep_ratio: float):
+        """mfsr_burst_select_frames on ``work``: (reference, kept frame indices); sets ``selection``."""
+        n = len(work)
+        sums_dev = torch.empty(n, dtype=torch.int64, device=self.device)
+        ref, keep = ctypes.c_int(-1), (ctypes.c_int32 * n)()
+        sums, rect = (ctypes.c_longlong * n)(), (ctypes.c_int32 * 4)()
+        self.L.burst_select_frames(self._h, n, _ptr_table(work), int(candidates), float(keep_ratio), sums_dev.data_ptr(),
+                                   ctypes.byref(ref), keep, sums, rect, self._stream())
+        r = ref.value
+        kept = [k for k in range(n) if keep[k]]
+        self.selection = Selection(r, kept, list(sums), tuple(rect))
+        return r, kept
+
+    def _match(self, work, r: int, per_colour: bool, deadband: Optional[int], min_gain: Optional[int], max_gain: Optional[int]):
+        """mfsr_burst_match_exposure of ``work`` to frame ``r``, in place; sets ``exposure``."""
+        n = len(work)
+        d = exposure_defaults(self.cfg)
+        levels_dev = torch.empty(n, 5, dtype=torch.int64, device=self.device)
+        gains, status, levels = (ctypes.c_int32 * (3 * n))(), (ctypes.c_int32 * n)(), (ctypes.c_longlong * (5 * n))()
+        self.L.burst_match_exposure(self._h, n, _ptr_table(work), r, 1 if per_colour else 0,
+                                    d.deadband if deadband is None else int(deadband),
+                                    d.min_gain if min_gain is None else int(min_gain),
+                                    d.max_gain if max_gain is None else int(max_gain), levels_dev.data_ptr(), gains, status, levels,
+                                    self._stream())
+        q16 = [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)]
+        self.exposure = Exposure(r, [[g / 65536.0 for g in row] for row in q16], [int(s) for s in status],
+                                 [[int(levels[5 * k + i]) for i in range(5)] for k in range(n)], q16)
+
+    def _run(self, work, r: int, kept: Iterable[int]):
+        """The burst itself: reference products of frame ``r``, the ``kept`` frames, finish."""
+        self.begin_burst()
+        self.set_reference(work[r])
+        for k in kept:
+            self.add_frame(work[k], k == r)
+        return self.finish()
+
     def process(self, frames: Sequence[torch.Tensor], frame_ids: Optional[Iterable[int]] = None):
         """Whole burst on this device: reference products, every frame, finish."""
-        self.begin_burst()
-        ref = self.cfg.reference
-        self.set_reference(frames[ref])
-        ids = range(len(frames)) if frame_ids is None else frame_ids
-        for k in ids:
-            self.add_frame(frames[k], k == ref)
-        return self.finish()
+        return self._run(frames, self.cfg.reference, range(len(frames)) if frame_ids is None else frame_ids)
 
     def process_selected(self, frames: Sequence[torch.Tensor], candidates: int = 0, keep_ratio: float = 0.0):
         """Whole burst with the reference chosen by sharpness (mfsr_burst_select_frames): the sharpest of the first
@@ -495,23 +538,8 @@ class BurstPipeline:
         are fused.  Then exactly what ``process`` does with that reference and those frames.  With a window the score is
         taken over the window's footprint.  Returns (float image, u16 image) like ``process``; the choice is left in
         ``self.selection`` (a ``Selection``)."""
-        n = len(frames)
-        for f in frames:
-            self._check_raw(f)
-        sums_dev = torch.empty(n, dtype=torch.int64, device=self.device)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
-        ref, keep = ctypes.c_int(-1), (ctypes.c_int32 * n)()
-        sums, rect = (ctypes.c_longlong * n)(), (ctypes.c_int32 * 4)()
-        self.L.burst_select_frames(self._h, n, ptrs, int(candidates), float(keep_ratio), sums_dev.data_ptr(), ctypes.byref(ref),
-                                   keep, sums, rect, self._stream())
-        r = ref.value
-        kept = [k for k in range(n) if keep[k]]
-        self.selection = Selection(r, kept, list(sums), tuple(rect))
-        self.begin_burst()
-        self.set_reference(frames[r])
-        for k in kept:
-            self.add_frame(frames[k], k == r)
-        return self.finish()
+        work = self._checked(frames, clone=False)
+        return self._run(work, *self._select(work, candidates, keep_ratio))
 
     def process_repaired(self, frames: Sequence[torch.Tensor], threshold: Optional[int] = None, spread: int = 2,
                          min_votes: Optional[int] = None, select: bool = False, candidates: int = 0, keep_ratio: float = 0.0):
@@ -519,23 +547,10 @@ class BurstPipeline:
         stay untouched), then exactly ``process`` of the repaired frames, or ``process_selected`` (``candidates``,
         ``keep_ratio``) with ``select=True``: repair goes before selection.  threshold / min_votes None =
         ``defect_defaults``.  The (hot, cold) pixel counts are left in ``self.defects``, the map in ``self.defect_map``."""
-        n = len(frames)
-        for f in frames:
-            self._check_raw(f)
-        t0, _, v0 = defect_defaults(self.cfg, n)
-        threshold = t0 if threshold is None else int(threshold)
-        min_votes = v0 if min_votes is None else int(min_votes)
-        fixed = [f.clone() for f in frames]
-        self.defect_map = torch.empty(self.cfg.height, self.cfg.width, dtype=torch.uint8, device=self.device)
-        counts_dev = torch.empty(2, dtype=torch.int32, device=self.device)
-        counts = (ctypes.c_uint32 * 2)()
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in fixed])
-        self.L.burst_repair_defects(self._h, n, ptrs, threshold, int(spread), min_votes, self.defect_map.data_ptr(),
-                                    counts_dev.data_ptr(), counts, self._stream())
-        self.defects = (int(counts[0]), int(counts[1]))
-        if select:
-            return self.process_selected(fixed, candidates, keep_ratio)
-        return self.process(fixed)
+        work = self._checked(frames, clone=True)
+        self._repair(work, threshold, spread, min_votes)
+        r, kept = self._select(work, candidates, keep_ratio) if select else (self.cfg.reference, range(len(work)))
+        return self._run(work, r, kept)
 
     def process_matched(self, frames: Sequence[torch.Tensor], select: bool = False, repair: bool = False, per_colour: bool = False,
                         deadband: Optional[int] = None, min_gain: Optional[int] = None, max_gain: Optional[int] = None,
@@ -549,45 +564,12 @@ class BurstPipeline:
         frame.  With a window the levels are measured over the window's footprint.  Returns (float image, u16 image) like
         ``process``; the outcome is left in ``self.exposure`` (an ``Exposure``), and ``self.defects`` / ``self.defect_map`` /
         ``self.selection`` are set by the steps that ran."""
-        n = len(frames)
-        for f in frames:
-            self._check_raw(f)
-        d = exposure_defaults(self.cfg)
-        work = [f.clone() for f in frames]
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in work])
+        work = self._checked(frames, clone=True)
         if repair:
-            t0, _, v0 = defect_defaults(self.cfg, n)
-            self.defect_map = torch.empty(self.cfg.height, self.cfg.width, dtype=torch.uint8, device=self.device)
-            counts_dev = torch.empty(2, dtype=torch.int32, device=self.device)
-            counts = (ctypes.c_uint32 * 2)()
-            self.L.burst_repair_defects(self._h, n, ptrs, t0 if threshold is None else int(threshold), int(spread),
-                                        v0 if min_votes is None else int(min_votes), self.defect_map.data_ptr(),
-                                        counts_dev.data_ptr(), counts, self._stream())
-            self.defects = (int(counts[0]), int(counts[1]))
-        r, kept = self.cfg.reference, list(range(n))
-        if select:
-            sums_dev = torch.empty(n, dtype=torch.int64, device=self.device)
-            ref, keep = ctypes.c_int(-1), (ctypes.c_int32 * n)()
-            sums, rect = (ctypes.c_longlong * n)(), (ctypes.c_int32 * 4)()
-            self.L.burst_select_frames(self._h, n, ptrs, int(candidates), float(keep_ratio), sums_dev.data_ptr(), ctypes.byref(ref),
-                                       keep, sums, rect, self._stream())
-            r = ref.value
-            kept = [k for k in range(n) if keep[k]]
-            self.selection = Selection(r, kept, list(sums), tuple(rect))
-        levels_dev = torch.empty(n, 5, dtype=torch.int64, device=self.device)
-        gains, status, levels = (ctypes.c_int32 * (3 * n))(), (ctypes.c_int32 * n)(), (ctypes.c_longlong * (5 * n))()
-        self.L.burst_match_exposure(self._h, n, ptrs, r, 1 if per_colour else 0, d.deadband if deadband is None else int(deadband),
-                                    d.min_gain if min_gain is None else int(min_gain),
-                                    d.max_gain if max_gain is None else int(max_gain), levels_dev.data_ptr(), gains, status, levels,
-                                    self._stream())
-        q16 = [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)]
-        self.exposure = Exposure(r, [[g / 65536.0 for g in row] for row in q16], [int(s) for s in status],
-                                 [[int(levels[5 * k + i]) for i in range(5)] for k in range(n)], q16)
-        self.begin_burst()
-        self.set_reference(work[r])
-        for k in kept:
-            self.add_frame(work[k], k == r)
-        return self.finish()
+            self._repair(work, threshold, spread, min_votes)
+        r, kept = self._select(work, candidates, keep_ratio) if select else (self.cfg.reference, range(len(work)))
+        self._match(work, r, per_colour, deadband, min_gain, max_gain)
+        return self._run(work, r, kept)
 
     def host_sync(self):
         """Block the host until the image of the last process_host has landed in host memory."""
@@ -606,8 +588,7 @@ class BurstPipeline:
         if getattr(self, "_joint_ws", None) is None or self._joint_ws.numel() < nbytes + 256:
             self._joint_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
         base = (self._joint_ws.data_ptr() + 255) // 256 * 256
-        ptrs = (ctypes.c_void_p * len(frames))(*[f.data_ptr() for f in frames])
-        self.L.burst_process_joint(self._h, ptrs, base, nbytes, self._img_out.data_ptr(), self._total_weights.data_ptr(),
+        self.L.burst_process_joint(self._h, _ptr_table(frames), base, nbytes, self._img_out.data_ptr(), self._total_weights.data_ptr(),
                                    self._stream())
         return self.finish()
 
@@ -671,9 +652,7 @@ class BurstPipeline:
         ref = self.cfg.reference
         self.L.burst_set_reference_host(self._h, host_frames[ref].data_ptr(), st)
         # every copy queued before the first kernel: the copy engine then runs them back to back (mfsr_burst_prefetch_host)
-        n = len(host_frames)
-        ptrs = (ctypes.c_void_p * n)(*[f.data_ptr() for f in host_frames])
-        self.L.burst_prefetch_host(self._h, ptrs, n, st)
+        self.L.burst_prefetch_host(self._h, _ptr_table(host_frames), len(host_frames), st)
         for k, f in enumerate(host_frames):
             self.L.burst_add_frame_host(self._h, f.data_ptr(), 1 if k == ref else 0, self._img_out.data_ptr(),
                                         self._total_weights.data_ptr(), st)

@@ -71,6 +71,24 @@ def test_sums_equal_numpy_small(kind, pad, offset):
         _check(cfg, host, dev, rect, kind == "mono")
 
 
+# the even sizes the exposure tests sweep (test_exposure_gpu._SIZES): the score shares its loader and band planner with
+# mfsr_frameLevels.  6 x 6 is the smallest frame a rectangle fits in (hw = 3: no 16-byte loads, every lane but one clamped);
+# 2056 x 12 has five strips and one band
+_SIZES = [(70, 38), (258, 130), (1000, 602), (500, 8), (498, 60), (6, 6), (8, 6), (6, 16), (1032, 18), (1026, 40), (2056, 12)]
+
+
+@pytest.mark.parametrize("w,h", _SIZES)
+def test_geometry_noise(w, h):
+    cfg = _cfg(w, h)
+    hw, hh = w // 2, h // 2
+    # the whole scorable rectangle and the single quads at its two corners (one and the same where hw = 3 or hh = 3)
+    rects = list(dict.fromkeys([(1, 1, hw - 1, hh - 1), (1, 1, 2, 2), (hw - 2, hh - 2, hw - 1, hh - 1)]))
+    for pad, offset in ((0, 0), (8, 0), (3, 1)):
+        host, dev = _random_frames(3, w, h, seed=w * 7 + h, pad=pad, offset=offset)
+        for rect in rects:
+            _check(cfg, host, dev, rect)
+
+
 @pytest.mark.parametrize("n", [1, 5, 70])
 def test_sums_equal_numpy_frame_counts(n):
     W, H = 260, 196

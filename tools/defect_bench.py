@@ -15,12 +15,13 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools._stage_bench import timed
 
 
 def main():
@@ -61,29 +62,9 @@ def main():
     def fix():  # (after the first call the flagged pixels hold their neighbours' median: the work per call stays the same)
         L.repairDefects(N, ptrs, 2 * W, W, H, 0, dmap.data_ptr(), W, torch.cuda.current_stream().cuda_stream)
 
-    def timed(fn):
-        for _ in range(max(a.warmup, 1)):
-            fn()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(max(a.iters, 20)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(len(times)):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return statistics.median(times), min(times), e0.elapsed_time(e1) * 1e3 / len(times), len(times)
-
-    v_med, v_min, v_batch, iters = timed(vote)
+    v_med, v_min, v_batch, iters = timed(vote, max(a.warmup, 1), max(a.iters, 20))
     found = counts.cpu().tolist()
-    r_med, r_min, r_batch, _ = timed(fix)
+    r_med, r_min, r_batch, _ = timed(fix, max(a.warmup, 1), max(a.iters, 20))
     nbytes = 2 * W * H * N + W * H
     print(json.dumps({
         "width": W, "height": H, "frames": N, "threshold": threshold, "spread": spread, "min_votes": votes, "iters": iters,

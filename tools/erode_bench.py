@@ -24,6 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tools._stage_bench import timed
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
@@ -48,18 +50,6 @@ def main():
     w, h = W // 2, H // 2
     st = torch.cuda.current_stream().cuda_stream
 
-    def timed(fn, reps):
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1000.0 / reps
-
     # the robustness kernel on the same geometry: reference / moved half-resolution images, a smooth flow
     g = torch.Generator(device=dev)
     g.manual_seed(5)
@@ -74,13 +64,13 @@ def main():
     def robustness():
         L.robustnessMaskFusedBatch(n, rf, ref.data_ptr(), w * 8, w, h, w, h, w * 12, w * 16, cfg0.alpha, cfg0.beta, cfg0.thresholdM, st)
 
-    rob_us = timed(robustness, a.reps)
+    rob_us = timed(robustness, 5, a.reps, singles=False)[2]
     out = torch.empty_like(masks)
 
     def erode():
         erode_mask(masks, a.radius, out=out)
 
-    er_us = timed(erode, a.reps)
+    er_us = timed(erode, 5, a.reps, singles=False)[2]
     bytes_moved = 2 * 16 * w * h * n
 
     # whole bursts, maskErode 0 and 2 taking turns

@@ -21,26 +21,13 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-
-def bench_turns(parent: str, rounds: int):
-    for r in range(rounds):
-        for name, d in (("this tree", ROOT), ("parent", parent)):
-            p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3"], cwd=d,
-                               capture_output=True, text=True, timeout=600)
-            if p.returncode != 0:
-                raise SystemExit(f"bench.py of {name} failed ({p.returncode}):\n{p.stderr[-2000:]}")
-            line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
-            j = json.loads(line)
-            print(json.dumps({"bench": name, "round": r, "ms_per_step": j.get("ms_per_step"),
-                              "out16_sha256_16": j.get("out16_sha256_16")}), flush=True)
+from tools._stage_bench import bench_turns, timed
 
 
 def main():
@@ -79,26 +66,6 @@ def main():
     cfa, black, r4, s4 = I4(*cfg.cfa), I4(*d.black), I4(*d.rect), I4(*srect)
     L = capi.lib()
 
-    def timed(fn):
-        for _ in range(max(a.warmup, 1)):
-            fn()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(max(a.iters, 20)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(len(times)):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return statistics.median(times), min(times), e0.elapsed_time(e1) * 1e3 / len(times), len(times)
-
     nbytes = 2 * W * H * N
     for name, frames in bursts.items():
         ptrs = (ctypes.c_void_p * N)(*[f.data_ptr() for f in frames])
@@ -110,8 +77,8 @@ def main():
         def sharp():
             L.frameSharpness(N, ptrs, 2 * W, W, H, cfa, 0, s4, sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
 
-        s_med, s_min, s_batch, iters = timed(sharp)
-        n_med, n_min, n_batch, _ = timed(stats)
+        s_med, s_min, s_batch, iters = timed(sharp, max(a.warmup, 1), max(a.iters, 20))
+        n_med, n_min, n_batch, _ = timed(stats, max(a.warmup, 1), max(a.iters, 20))
         alpha, beta, status, points = noise_fit((hist, level_sum, count), cfg)
         print(json.dumps({
             "burst": name, "width": W, "height": H, "frames": N, "rect": list(d.rect), "black": list(d.black), "sat": d.sat,

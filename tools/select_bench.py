@@ -14,12 +14,13 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools._stage_bench import timed
 
 
 def main():
@@ -38,30 +39,13 @@ def main():
     cfg = default_config(W, H, N, 2, False)
     g = torch.Generator(device="cuda:0").manual_seed(1)
     frames = [torch.randint(0, 4096, (H, W), generator=g, device="cuda:0", dtype=torch.int32).to(torch.int16) for _ in range(N)]
-    for _ in range(max(a.warmup, 1)):
-        sums = frame_sharpness(frames, cfg)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(max(a.iters, 1)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        frame_sharpness(frames, cfg)
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) * 1e3)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(len(times)):
-        frame_sharpness(frames, cfg)
-    e1.record()
-    e1.synchronize()
-    batch = e0.elapsed_time(e1) * 1e3 / len(times)
+    med, fastest, batch, iters = timed(lambda: frame_sharpness(frames, cfg), max(a.warmup, 1), max(a.iters, 1))
+    sums = frame_sharpness(frames, cfg)
     nbytes = 2 * W * H * N
-    med = statistics.median(times)
     print(json.dumps({
-        "width": W, "height": H, "frames": N, "rect": list(sharpness_rect(cfg)), "iters": len(times),
+        "width": W, "height": H, "frames": N, "rect": list(sharpness_rect(cfg)), "iters": iters,
         "us_per_call_batched": round(batch, 2), "tb_per_s_batched": round(nbytes / batch / 1e6, 3),
-        "us_single_median": round(med, 2), "us_single_min": round(min(times), 2), "bytes": nbytes,
+        "us_single_median": round(med, 2), "us_single_min": round(fastest, 2), "bytes": nbytes,
         "tb_per_s_single_median": round(nbytes / med / 1e6, 3),
         "sums_head": [int(v) for v in sums.cpu()[:2]],
     }), flush=True)
