@@ -137,6 +137,39 @@ static bool read_pnm(const std::string& path, Image8& img)
     return true;
 }
 
+// binary PGM with 16-bit samples (maxval 65535, big-endian): a table of numbers, not a picture (MFSR_SHADING)
+[[maybe_unused]] static bool read_pgm16(const std::string& path, int& w, int& h, std::vector<uint16_t>& px)
+{
+    std::vector<uint8_t> buf;
+    if (!read_file(path, buf) || buf.size() < 8 || buf[0] != 'P' || buf[1] != '5') return false;
+    int vals[3], nv = 0;
+    size_t pos = 2;
+    while (nv < 3 && pos < buf.size()) {
+        while (pos < buf.size() && (buf[pos] == ' ' || buf[pos] == '\n' || buf[pos] == '\r' || buf[pos] == '\t')) pos++;
+        if (pos >= buf.size()) return false;
+        if (buf[pos] == '#') {
+            while (pos < buf.size() && buf[pos] != '\n') pos++;
+            continue;
+        }
+        if (buf[pos] < '0' || buf[pos] > '9') return false;
+        int v = 0;
+        while (pos < buf.size() && buf[pos] >= '0' && buf[pos] <= '9') {
+            v = v * 10 + (buf[pos++] - '0');
+            if (v > 65535) return false;
+        }
+        vals[nv++] = v;
+    }
+    pos++;  // the single white-space byte after maxval
+    if (nv != 3 || vals[2] != 65535 || vals[0] <= 0 || vals[1] <= 0 || pos > buf.size()) return false;
+    const size_t n = (size_t)vals[0] * vals[1];
+    if (pos + 2 * n > buf.size()) return false;
+    w = vals[0];
+    h = vals[1];
+    px.resize(n);
+    for (size_t i = 0; i < n; i++) px[i] = (uint16_t)(buf[pos + 2 * i] << 8 | buf[pos + 2 * i + 1]);
+    return true;
+}
+
 static bool read_jpeg(const std::string& path, Image8& img)
 {
     std::vector<uint8_t> buf;

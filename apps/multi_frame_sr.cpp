@@ -225,6 +225,47 @@ int main(int argc, char** argv)
         }
         exposure = e[0] == 'r' ? 2 : e[0] == '1' ? 1 : 0;
     }
+    // MFSR_SHADING=<16-bit binary PGM>: a lens-shading gain map, gw x 4*gh pixels (the four quad positions' planes stacked),
+    // Q12 (gain = value / 4096, never below 1.0); MFSR_SHADING_CELL=<cell in quads> (default: mfsr_shading_defaults)
+    std::vector<int32_t> shadingMap;
+    int shadingCell = 0, shadingGw = 0, shadingGh = 0;
+    if (const char* e = getenv("MFSR_SHADING")) {
+        int32_t cell = 0;
+        if (const char* r = getenv("MFSR_SHADING_CELL")) {
+            char* end = nullptr;
+            const long x = strtol(r, &end, 10);
+            if (end == r || *end != '\0' || x < 8 || x > 256 || (x & (x - 1)) != 0) {
+                fprintf(stderr, "MFSR_SHADING_CELL=%s: a power of two in [8, 256] expected\n", r);
+                return 1;
+            }
+            cell = (int32_t)x;
+        } else if (mfsr_shading_defaults(&cfg, nullptr, nullptr, nullptr, &cell, nullptr, nullptr) != MFSR_OK) {
+            fprintf(stderr, "MFSR_SHADING: frames of at least 18 x 18 samples expected\n");
+            return 1;
+        }
+        shadingCell = cell;
+        shadingGw = (W / 2 - 2 + cell) / cell + 1;
+        shadingGh = (H / 2 - 2 + cell) / cell + 1;
+        int mw = 0, mh = 0;
+        std::vector<uint16_t> px;
+        if (!read_pgm16(e, mw, mh, px)) {
+            fprintf(stderr, "MFSR_SHADING=%s: cannot read a binary PGM with 16-bit samples (maxval 65535)\n", e);
+            return 1;
+        }
+        if (mw != shadingGw || mh != 4 * shadingGh) {
+            fprintf(stderr, "MFSR_SHADING=%s: the map is %d x %d, but cell %d on %d x %d frames needs %d x %d (gw x 4*gh)\n", e, mw, mh,
+                    cell, W, H, shadingGw, 4 * shadingGh);
+            return 1;
+        }
+        shadingMap.resize(px.size());
+        for (size_t i = 0; i < px.size(); i++) {
+            if (px[i] < 4096) {
+                fprintf(stderr, "MFSR_SHADING=%s: value %d at map pixel %zu is below 4096 (Q12: a gain below 1.0)\n", e, (int)px[i], i);
+                return 1;
+            }
+            shadingMap[i] = (int32_t)px[i] * 16;
+        }
+    }
     // MFSR_NOISE=auto: calibrate cfg.alpha / cfg.beta on the input frames; MFSR_NOISE=alpha,beta: set them
     int noiseMode = 0;  // 0 off, 1 auto, 2 given
     if (const char* e = getenv("MFSR_NOISE")) {
@@ -258,6 +299,10 @@ int main(int argc, char** argv)
     }
     if (exposure && gpus > 1) {
         fprintf(stderr, "MFSR_EXPOSURE is not supported with MFSR_GPUS > 1 (match the frames before sharding them)\n");
+        return 1;
+    }
+    if (!shadingMap.empty() && gpus > 1) {
+        fprintf(stderr, "MFSR_SHADING is not supported with MFSR_GPUS > 1 (correct the frames before sharding them)\n");
         return 1;
     }
     if (defects && gpus > 1) {
@@ -368,6 +413,18 @@ int main(int argc, char** argv)
         HIP_OK(hipFree(dmap));
         HIP_OK(hipFree(dcounts));
         fprintf(stderr, "defects: %u hot, %u cold\n", counts[0], counts[1]);
+    }
+
+    // MFSR_SHADING: the gain map applied once, in the device frames, after the repair and before the selection
+    // (mfsr_burst_correct_shading); the report goes to stderr
+    if (!shadingMap.empty()) {
+        int32_t* dmapQ16 = nullptr;
+        HIP_OK(hipMalloc((void**)&dmapQ16, shadingMap.size() * sizeof(int32_t)));
+        HIP_OK(hipMemcpy(dmapQ16, shadingMap.data(), shadingMap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        MFSR_OK_OR_DIE(mfsr_burst_correct_shading(b, num_images, dframes.data(), dmapQ16, shadingCell, nullptr));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipFree(dmapQ16));
+        fprintf(stderr, "shading: map %dx%d cell %d\n", shadingGw, shadingGh, shadingCell);
     }
 
     // MFSR_SELECT: the sharpest frame becomes the reference and frames much softer than it are dropped, chosen once for the

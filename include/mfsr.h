@@ -830,6 +830,61 @@ int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* const* frame
                               int minGain, int maxGain, long long* levelsDev, int32_t* gains, int32_t* status, long long* levels,
                               mfsr_stream_t stream);
 
+/* ---- lens shading: vignetting and colour shading of the lens corrected in the raw domain with a flat-field gain map, before
+ * anything else but the defect repair looks at the frames.  Exact integer arithmetic: bit-for-bit
+ * reproducible.  Order of the raw-domain steps: repair defects, correct shading, select the reference, match exposure, process.
+ * THE MAP.  q = 2*(y&1) + (x&1) numbers the position of sample (x, y) inside its 2x2 quad (for mono too); X = x>>1, Y = y>>1 are
+ * its quad's half-resolution coordinates, hw = width/2, hh = height/2.  cell = 1<<k quads, 3 <= k <= 8.  The grid has gw =
+ * (hw - 2 + cell)/cell + 1 by gh = (hh - 2 + cell)/cell + 1 points (integer division); point (i, j) sits at quad (i*cell,
+ * j*cell), so the last point lies at or beyond the last quad.  map = int32 [4][gh][gw] in DEVICE memory, dense, 4-byte aligned:
+ * Q16 gains (65536 = 1.0), each in [4096, 1048576], G[q][j][i] the gain of position q at grid point (i, j).  The values are the
+ * caller's responsibility (they are not read back to be checked; a value outside the range gives an unspecified sample value,
+ * never an access outside the frame or the map); mfsr_shading_fit produces none outside it.
+ * Gain of quad (X, Y) at position q, with i = X>>k, fx = X & (cell-1), j = Y>>k, fy = Y & (cell-1), in 64-bit integers (the
+ * sum is below 2^37):
+ *   g = ((cell-fx)*(cell-fy)*G[q][j][i] + fx*(cell-fy)*G[q][j][i+1] + (cell-fx)*fy*G[q][j+1][i] + fx*fy*G[q][j+1][i+1]
+ *        + (1 << (2k-1))) >> 2k
+ * A term whose weight is 0 is not read: at X = (gw-1)*cell (fx = 0) column i+1 does not exist, likewise row j+1.
+ * APPLY (in place).  Sample v at position q with b = black[q]: unchanged if v <= b; otherwise min(b + (((v - b) * g + 32768)
+ * >> 16), maxValue), the arithmetic of mfsr_applyGains.  Unlike there, a clipped sample is multiplied too (there is no sat): a
+ * blown corner is "at least sat * g", and left at sat beside neighbours lifted above it a highlight would turn into a dark spot.
+ * Bytes of a row beyond its width samples are never written.  frames = host array of nFrames DEVICE pointers with the rules of
+ * mfsr_applyGains (1 <= nFrames <= 64, u16, rows `pitch` bytes apart, pitch >= 2*width and even, width and height even);
+ * 0 <= black[q] <= 65535, 0 < maxValue <= 65535.  Every argument is checked on the host before any device call
+ * (MFSR_E_INVALID). */
+int mfsr_applyShading(int nFrames, uint16_t* const* frames, int pitch, int width, int height, const int32_t* mapDev, int cell,
+                      const int32_t black[4], int maxValue, mfsr_stream_t stream);
+/* MEASURE a map from flat-field frames (a uniformly lit diffuser).  The BOX of grid point (i, j) is the quads with
+ * i*cell - cell/2 <= X < i*cell + cell/2 and likewise in Y, clipped to the frame: the boxes tile the frame, edge boxes are half
+ * or quarter size.  A quad is usable iff all four of its samples are < sat (the quad is the unit, as for mfsr_frameLevels).
+ * Over all frames of the call: sumsDev[q][j][i] = sum over the usable quads of the box of max(v_q - black[q], 0) (int64
+ * [4][gh][gw]), countsDev[j][i] = number of usable quads of the box (int64 [gh][gw]); device memory, 8-byte aligned, zeroed on
+ * the stream first.  Integers: independent of the reduction order and of the launch shape.  Frames as above, read only;
+ * 0 < sat <= 65535.  Every argument is checked on the host before any device call (MFSR_E_INVALID). */
+int mfsr_shadingStats(int nFrames, const uint16_t* const* frames, int pitch, int width, int height, int cell, const int32_t black[4],
+                      int sat, long long* sumsDev, long long* countsDev, mfsr_stream_t stream);
+/* FIT (host only, no device call, unsigned 128-bit intermediates, no floating point).  sums[4][gh][gw] and counts[gh][gw] as
+ * mfsr_shadingStats leaves them, in HOST memory (each entry in [0, 2^48)); map[4][gh][gw] (host) := the gains.  With p a grid
+ * point, S_q[p] and C[p] its sums and count: the ANCHOR a is the point with the largest mean level (S_0 + S_1 + S_2 + S_3)[p] /
+ * C[p], compared exactly by cross-multiplication, ties to the lowest index j*gw + i; map[q][p] = clamp(floor((S_q[a] * C[p] *
+ * 65536 + den/2) / den), 65536, maxGain), den = S_q[p] * C[a].  One anchor for all four positions: colour shading is corrected
+ * relative to the same spot.  *status: 2 unmeasurable (some C[p] < minQuads or some S_q[p] == 0: every gain 65536); 3 some gain
+ * was clamped at maxGain (the map is still returned); else 0.  minQuads >= 1, 65536 <= maxGain <= 1048576. */
+int mfsr_shading_fit(const long long* sums, const long long* counts, int gw, int gh, int minQuads, int maxGain, int32_t* map,
+                     int32_t* status);
+/* The levels and bounds a burst uses when the caller has none of their own (host only): black, sat and maxValue as
+ * mfsr_exposure_defaults; cell = the largest 1<<k, k <= 6, with cell <= min(width/2, height/2) - 1 (so that gw, gh >= 2), never
+ * below 8: frames smaller than 18 x 18 are refused when cell is asked for; minQuads = 64; maxGain = 524288 (3 stops).  Every
+ * output may be NULL. */
+int mfsr_shading_defaults(const mfsr_config* cfg, int32_t black[4], int32_t* sat, int32_t* maxValue, int32_t* cell, int32_t* minQuads,
+                          int32_t* maxGain);
+/* mfsr_applyShading on a burst's frames (device-resident, dense rows as for mfsr_burst_add_frame; 1 <= nFrames <= 64), in
+ * place, with black and maxValue of mfsr_shading_defaults and the size of the burst's config; cell <= 0: the cell of
+ * mfsr_shading_defaults.  Processes nothing: the caller then runs mfsr_burst_select_frames, mfsr_burst_match_exposure and the
+ * usual begin / set_reference / add_frame / finish (shading goes after the defect repair and before the selection). */
+int mfsr_burst_correct_shading(mfsr_burst* b, int nFrames, uint16_t* const* frames, const int32_t* mapDev, int cell,
+                               mfsr_stream_t stream);
+
 /* ---- noise-model calibration: measure the affine noise model var = alpha * I + beta of the robustness model (cfg.alpha,
  * cfg.beta) from raw frames of the sensor at the gain in use.  An exact-integer device stage and a small
  * host fit.  Frames are read only; nothing here runs unless it is called.

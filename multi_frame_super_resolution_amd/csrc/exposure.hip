@@ -103,16 +103,6 @@ struct GainGeom {
     int sat, maxValue;
 };
 
-// v (at quad position q's black level b, gain g = gh * 65536 + gl): (d * g + 32768) >> 16 = d * gh + ((d * gl + 32768) >> 16)
-// for d = v - b < 2^16 -- d * gl + 32768 < 2^32, so 32-bit arithmetic is exact where the product d * g is not
-__device__ __forceinline__ uint32_t gain_sample(uint32_t v, int b, int g, int sat, int maxValue)
-{
-    if ((int)v <= b || (int)v >= sat) return v;  // at or below black, or clipped: unchanged
-    const uint32_t d = v - (uint32_t)b;
-    const uint32_t r = (uint32_t)b + d * ((uint32_t)g >> 16) + ((d * ((uint32_t)g & 0xffffu) + 32768u) >> 16);
-    return min(r, (uint32_t)maxValue);
-}
-
 __global__ __launch_bounds__(256) void k_applyGains(GainFrames frames, GainGeom g)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;

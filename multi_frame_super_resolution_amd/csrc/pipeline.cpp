@@ -2206,6 +2206,34 @@ extern "C" int mfsr_burst_match_exposure(mfsr_burst* b, int nFrames, uint16_t* c
     return MFSR_OK;
 }
 
+// ---- lens shading: a flat-field gain map applied in place (csrc/shading.hip) -------------------------------
+extern "C" int mfsr_shading_defaults(const mfsr_config* cfg, int32_t black[4], int32_t* sat, int32_t* maxValue, int32_t* cell,
+                                     int32_t* minQuads, int32_t* maxGain)
+{
+    MFSR_REQUIRE(cfg != nullptr);
+    TRY(mfsr_exposure_defaults(cfg, black, sat, maxValue, nullptr, nullptr, nullptr, nullptr));
+    if (cell) {
+        const int m = (cfg->width < cfg->height ? cfg->width : cfg->height) / 2 - 1;
+        MFSR_REQUIRE(cfg->width % 2 == 0 && cfg->height % 2 == 0 && m >= 8);  // (18 x 18 samples: two grid points each way)
+        int c = 64;
+        while (c > m) c >>= 1;
+        *cell = c;
+    }
+    if (minQuads) *minQuads = 64;
+    if (maxGain) *maxGain = 524288;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_correct_shading(mfsr_burst* b, int nFrames, uint16_t* const* frames, const int32_t* mapDev, int cell,
+                                          mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && mapDev);
+    const mfsr_config& c = b->cfg;
+    int32_t black[4], maxValue = 0, defCell = 0;
+    TRY(mfsr_shading_defaults(&c, black, nullptr, &maxValue, cell > 0 ? nullptr : &defCell, nullptr, nullptr));
+    return mfsr_applyShading(nFrames, frames, 2 * c.width, c.width, c.height, mapDev, cell > 0 ? cell : defCell, black, maxValue, stream);
+}
+
 // ---- noise-model calibration: block statistics of the frames on the device, the fit on the host
 //      (csrc/noise.hip).  Nothing in the burst changes. -----------------------------------------------------------------
 extern "C" int mfsr_noise_defaults(const mfsr_config* cfg, int32_t black[4], float white[4], int32_t* sat, int32_t* minBlocks,

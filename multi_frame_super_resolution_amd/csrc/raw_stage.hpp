@@ -1,4 +1,4 @@
-// raw_stage.hpp -- what the raw-domain stages share (select.hip, exposure.hip, noise.hip, defect.hip):
+// raw_stage.hpp -- what the raw-domain stages share (select.hip, exposure.hip, noise.hip, defect.hip, shading.hip):
 // the frame table of a launch, the host checks of their entry points, the whole-wave exchanges, and for the two stages that
 // stream quad rows down strips and bands (k_frameSharpness, k_frameLevels) the loader and the band planner.  Internal: every
 // rule an entry point states in include/mfsr.h is composed from the checks here, and a check is shared only where the rule
@@ -123,6 +123,27 @@ __device__ __forceinline__ T wave_sum(T v)
 #pragma unroll
     for (int o = kRawLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+// the sum over each aligned group of `lanes` lanes (a power of two, 1 .. 64; the same in the whole wave), in every lane of the group
+template <typename T>
+__device__ __forceinline__ T wave_group_sum(T v, int lanes)
+{
+#pragma unroll
+    for (int o = kRawLanes / 2; o > 0; o >>= 1)
+        if (o < lanes) v += __shfl_xor(v, o);
+    return v;
+}
+
+// ---- a Q16 gain about the black level (k_applyGains, k_applyShading) -------------------------------------------------------------
+// v (at quad position q's black level b, gain g = gh * 65536 + gl): (d * g + 32768) >> 16 = d * gh + ((d * gl + 32768) >> 16)
+// for d = v - b < 2^16 -- d * gl + 32768 < 2^32, so 32-bit arithmetic is exact where the product d * g is not
+__device__ __forceinline__ uint32_t gain_sample(uint32_t v, int b, int g, int sat, int maxValue)
+{
+    if ((int)v <= b || (int)v >= sat) return v;  // at or below black, or clipped: unchanged
+    const uint32_t d = v - (uint32_t)b;
+    const uint32_t r = (uint32_t)b + d * ((uint32_t)g >> 16) + ((d * ((uint32_t)g & 0xffffu) + 32768u) >> 16);
+    return min(r, (uint32_t)maxValue);
 }
 
 // ---- quad rows ----------------------------------------------------------------------------------------------------------

@@ -330,6 +330,105 @@ def calibrate_noise(frames: Sequence[torch.Tensor], cfg: capi.Config):
     return a, b, st
 
 
+ShadingDefaults = namedtuple("ShadingDefaults", "black sat max_value cell min_quads max_gain")
+
+
+def shading_defaults(cfg: capi.Config) -> ShadingDefaults:
+    """The levels and bounds of lens-shading correction when none are given (the rule of mfsr_shading_defaults, restated): black,
+    sat and max_value as ``exposure_defaults``; cell = the largest power of two up to 64 that is at most min(W/2, H/2) - 1, never
+    below 8 (frames smaller than 18 x 18 are refused); min_quads 64; max_gain 524288 (3 stops).  Pure Python (no device)."""
+    d = exposure_defaults(cfg)
+    m = min(cfg.width, cfg.height) // 2 - 1
+    if cfg.width % 2 or cfg.height % 2 or m < 8:
+        raise ValueError("lens-shading correction needs frames of at least 18 x 18 samples, width and height even")
+    cell = 64
+    while cell > m:
+        cell //= 2
+    return ShadingDefaults(d.black, d.sat, d.max_value, cell, 64, 524288)
+
+
+def shading_grid(cfg: capi.Config, cell: Optional[int] = None) -> Tuple[int, int]:
+    """(gw, gh): the grid points of a gain map of cell ``cell`` quads (None = ``shading_defaults``) over cfg's frame; the map is
+    int32 [4, gh, gw].  Pure Python (no device)."""
+    cell = shading_defaults(cfg).cell if cell is None else int(cell)
+    if cell not in (8, 16, 32, 64, 128, 256):
+        raise ValueError("cell must be a power of two in [8, 256]")
+    return (cfg.width // 2 - 2 + cell) // cell + 1, (cfg.height // 2 - 2 + cell) // cell + 1
+
+
+def shading_stats(frames: Sequence[torch.Tensor], cfg: capi.Config, cell: Optional[int] = None, sat: Optional[int] = None):
+    """Box statistics of flat-field frames (mfsr_shadingStats), exact: (sums int64 [4, gh, gw], counts int64 [gh, gw]) device
+    tensors -- per grid point of the gain map the sums of max(v - black[q], 0) over the usable quads (all four samples < sat) of
+    its box in all frames, and their number.  ``frames`` as for ``frame_sharpness`` (pitched views are fine, at most 64); they
+    are only read.  cell None / sat None = ``shading_defaults``."""
+    frames = list(frames)
+    dev, pitch = _raw_frames(frames, cfg)
+    d = shading_defaults(cfg)
+    cell = d.cell if cell is None else int(cell)
+    gw, gh = shading_grid(cfg, cell)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        sums = torch.empty(4, gh, gw, dtype=torch.int64, device=dev)
+        counts = torch.empty(gh, gw, dtype=torch.int64, device=dev)
+        capi.lib().shadingStats(n, _ptr_table(frames), pitch, cfg.width, cfg.height, cell, _i4(d.black),
+                                d.sat if sat is None else int(sat), sums.data_ptr(), counts.data_ptr(),
+                                torch.cuda.current_stream().cuda_stream)
+    return sums, counts
+
+
+def shading_fit(sums, counts, min_quads: int = 64, max_gain: int = 524288):
+    """(map, status) of mfsr_shading_fit on the tables of ``shading_stats`` (tensors on any device or arrays): the Q16 gain map
+    as a numpy int32 array [4, gh, gw], relative to the brightest grid point.  status 0 ok, 2 unmeasurable (every gain 65536),
+    3 some gain was clamped at ``max_gain``.  Host only: no device is needed."""
+    import numpy as np
+
+    def host(t):
+        return np.ascontiguousarray((t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.int64))
+
+    s, c = host(sums), host(counts)
+    if s.ndim != 3 or s.shape[0] != 4 or c.shape != s.shape[1:]:
+        raise ValueError("sums must be [4, gh, gw] and counts [gh, gw]")
+    gh, gw = c.shape
+    gain_map = np.empty((4, gh, gw), dtype=np.int32)
+    st = ctypes.c_int32()
+    capi.lib().shading_fit(s.ctypes.data, c.ctypes.data, gw, gh, int(min_quads), int(max_gain), gain_map.ctypes.data, ctypes.byref(st))
+    return gain_map, st.value
+
+
+def calibrate_shading(flat_frames: Sequence[torch.Tensor], cfg: capi.Config, cell: Optional[int] = None):
+    """(gain map, status) measured on raw device frames of a uniformly lit diffuser: ``shading_stats``, then ``shading_fit``
+    with the defaults.  The map is an int32 [4, gh, gw] device tensor, what ``apply_shading`` and
+    ``BurstPipeline.process_shaded`` take; status as for ``shading_fit``."""
+    d = shading_defaults(cfg)
+    gain_map, st = shading_fit(*shading_stats(flat_frames, cfg, cell), min_quads=d.min_quads, max_gain=d.max_gain)
+    return torch.from_numpy(gain_map).to(flat_frames[0].device), st
+
+
+def _shading_map(gain_map: torch.Tensor, cfg: capi.Config, cell: Optional[int], dev) -> int:
+    """Check a gain map against cfg's frame and the cell (None = ``shading_defaults``); returns the cell."""
+    cell = shading_defaults(cfg).cell if cell is None else int(cell)
+    gw, gh = shading_grid(cfg, cell)
+    if (not isinstance(gain_map, torch.Tensor) or gain_map.device != dev or gain_map.dtype != torch.int32
+            or tuple(gain_map.shape) != (4, gh, gw) or not gain_map.is_contiguous()):
+        raise ValueError(f"gain_map must be a contiguous int32 [4, {gh}, {gw}] tensor on the frames' device (cell {cell})")
+    return cell
+
+
+def apply_shading(frames: Sequence[torch.Tensor], gain_map: torch.Tensor, cfg: capi.Config, cell: Optional[int] = None):
+    """The frames with the gain map applied (mfsr_applyShading; ``gain_map`` int32 [4, gh, gw] on the frames' device, Q16, every
+    value in [4096, 1048576] -- not checked): a list of new contiguous tensors, the caller's frames stay untouched.  cell None =
+    ``shading_defaults``."""
+    frames = list(frames)
+    dev, _ = _raw_frames(frames, cfg)
+    cell = _shading_map(gain_map, cfg, cell, dev)
+    d = shading_defaults(cfg)
+    out = [f.clone(memory_format=torch.contiguous_format) for f in frames]
+    with torch.cuda.device(dev):
+        capi.lib().applyShading(len(out), _ptr_table(out), 2 * cfg.width, cfg.width, cfg.height, gain_map.data_ptr(), cell,
+                                _i4(d.black), d.max_value, torch.cuda.current_stream().cuda_stream)
+    return out
+
+
 def erode_mask(masks, radius: int, out=None):
     """Erosion of certainty masks (mfsr_erodeMaskBatch): every colour certainty (.x .y .z) becomes its
     minimum over the (2*radius+1)^2 neighbourhood clamped to the interior, .w passes through, the one-cell ring is zero.
@@ -473,8 +572,8 @@ class BurstPipeline:
                                  self.out16.data_ptr(), row0, rows, self._stream())
         return self.out16
 
-    # ---- the raw-domain steps, in the order DESIGN.md section 2.14 fixes: repair, select, match, then the burst.  ``work``:
-    #      checked frames the step may write (clones of the caller's) ----
+    # ---- the raw-domain steps, in the order DESIGN.md sections 2.14 and 2.17 fix: repair, shade, select, match, then the burst.
+    #      ``work``: checked frames the step may write (clones of the caller's) ----
     def _checked(self, frames: Sequence[torch.Tensor], clone: bool):
         for f in frames:
             self._check_raw(f)
@@ -491,6 +590,11 @@ class BurstPipeline:
                                     v0 if min_votes is None else int(min_votes), self.defect_map.data_ptr(),
                                     counts_dev.data_ptr(), counts, self._stream())
         self.defects = (int(counts[0]), int(counts[1]))
+
+    def _shade(self, work, gain_map: torch.Tensor, cell: Optional[int]):
+        """mfsr_burst_correct_shading on ``work``, in place."""
+        cell = _shading_map(gain_map, self.cfg, cell, self.device)
+        self.L.burst_correct_shading(self._h, len(work), _ptr_table(work), gain_map.data_ptr(), cell, self._stream())
 
     def _select(self, work, candidates: int, keep_ratio: float):
         """mfsr_burst_select_frames on ``work``: (reference, kept frame indices); sets ``selection``."""
@@ -541,24 +645,38 @@ class BurstPipeline:
         work = self._checked(frames, clone=False)
         return self._run(work, *self._select(work, candidates, keep_ratio))
 
+    def process_shaded(self, frames: Sequence[torch.Tensor], gain_map: torch.Tensor, cell: Optional[int] = None):
+        """Whole burst with the lens shading corrected first (mfsr_burst_correct_shading on clones: the caller's frames stay
+        untouched), then exactly ``process`` of the corrected frames.  ``gain_map``: an int32 [4, gh, gw] device tensor of Q16
+        gains (``calibrate_shading``; ``shading_grid`` gives gw, gh); cell None = ``shading_defaults``."""
+        work = self._checked(frames, clone=True)
+        self._shade(work, gain_map, cell)
+        return self._run(work, self.cfg.reference, range(len(work)))
+
     def process_repaired(self, frames: Sequence[torch.Tensor], threshold: Optional[int] = None, spread: int = 2,
-                         min_votes: Optional[int] = None, select: bool = False, candidates: int = 0, keep_ratio: float = 0.0):
+                         min_votes: Optional[int] = None, select: bool = False, candidates: int = 0, keep_ratio: float = 0.0,
+                         shading: Optional[torch.Tensor] = None, shading_cell: Optional[int] = None):
         """Whole burst with its defective pixels repaired first (mfsr_burst_repair_defects on clones: the caller's frames
         stay untouched), then exactly ``process`` of the repaired frames, or ``process_selected`` (``candidates``,
         ``keep_ratio``) with ``select=True``: repair goes before selection.  threshold / min_votes None =
-        ``defect_defaults``.  The (hot, cold) pixel counts are left in ``self.defects``, the map in ``self.defect_map``."""
+        ``defect_defaults``.  The (hot, cold) pixel counts are left in ``self.defects``, the map in ``self.defect_map``.
+        ``shading`` (a gain map as for ``process_shaded``, with ``shading_cell``): the lens shading is corrected after the
+        repair and before the selection."""
         work = self._checked(frames, clone=True)
         self._repair(work, threshold, spread, min_votes)
+        if shading is not None:
+            self._shade(work, shading, shading_cell)
         r, kept = self._select(work, candidates, keep_ratio) if select else (self.cfg.reference, range(len(work)))
         return self._run(work, r, kept)
 
     def process_matched(self, frames: Sequence[torch.Tensor], select: bool = False, repair: bool = False, per_colour: bool = False,
                         deadband: Optional[int] = None, min_gain: Optional[int] = None, max_gain: Optional[int] = None,
                         candidates: int = 0, keep_ratio: float = 0.0, threshold: Optional[int] = None, spread: int = 2,
-                        min_votes: Optional[int] = None):
+                        min_votes: Optional[int] = None, shading: Optional[torch.Tensor] = None, shading_cell: Optional[int] = None):
         """Whole burst with the exposure of its frames matched to the reference first (mfsr_burst_match_exposure on clones:
         the caller's frames stay untouched).  Order of the raw-domain steps: repair defects (``repair=True``; threshold /
-        spread / min_votes as for ``process_repaired``), select the reference and the kept frames (``select=True``;
+        spread / min_votes as for ``process_repaired``), correct the lens shading (``shading`` = a gain map as for
+        ``process_shaded``, with ``shading_cell``), select the reference and the kept frames (``select=True``;
         candidates / keep_ratio as for ``process_selected``), match every frame to that reference, then the ordinary burst.
         deadband / min_gain / max_gain None = ``exposure_defaults``; ``per_colour``: one gain per colour instead of one per
         frame.  With a window the levels are measured over the window's footprint.  Returns (float image, u16 image) like
@@ -567,6 +685,8 @@ class BurstPipeline:
         work = self._checked(frames, clone=True)
         if repair:
             self._repair(work, threshold, spread, min_votes)
+        if shading is not None:
+            self._shade(work, shading, shading_cell)
         r, kept = self._select(work, candidates, keep_ratio) if select else (self.cfg.reference, range(len(work)))
         self._match(work, r, per_colour, deadband, min_gain, max_gain)
         return self._run(work, r, kept)

@@ -212,3 +212,36 @@ def make_chart_burst(width: int, height: int, frames: int, alpha: float, beta: f
         noisy = img + torch.randn(img.shape, generator=gen, device=device) * torch.sqrt(alpha * img + beta)
         out.append(torch.round(noisy * white + black).clamp(0, 4095).to(torch.int16).contiguous())
     return out
+
+
+def vignette(width: int, height: int, strength: float = 0.8, colour_tilt: float = 0.05, device="cpu") -> torch.Tensor:
+    """The transmission of a lens over a ``width`` x ``height`` RGGB sensor, a float64 [H, W] tensor in (0, 1]: 1 / (1 +
+    strength * r^2)^2 with r the distance from the frame centre in half-diagonals (r = 1 in the corners), times a colour shading
+    that grows with r^2: red samples lose ``colour_tilt`` at r = 1, blue samples gain it (green: none), normalised so that no
+    value exceeds 1.  Sensor coordinates: the same for every frame of a burst, whatever the scene does."""
+    yy, xx = torch.meshgrid(torch.arange(height, device=device, dtype=torch.float64),
+                            torch.arange(width, device=device, dtype=torch.float64), indexing="ij")
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    r2 = ((xx - cx) ** 2 + (yy - cy) ** 2) / (cx * cx + cy * cy)
+    colour = (yy.long() % 2) + (xx.long() % 2)  # RGGB: 0 red, 1 green, 2 blue
+    tilt = 1.0 + colour_tilt * (colour.double() - 1.0) * r2
+    v = tilt / (1.0 + strength * r2) ** 2
+    return v / v.max()
+
+
+def make_flat_burst(width: int, height: int, frames: int, level: float = 0.6, vignette: Optional[torch.Tensor] = None,
+                    alpha: float = 1e-4, beta: float = 1e-6, seed: int = 1234, device="cpu", black: float = 256.0,
+                    white: float = 4095.0 - 256.0) -> List[torch.Tensor]:
+    """Flat-field frames for ``calibrate_shading``: ``frames`` raw frames [H, W] (int16 holding u16 bit patterns) of a uniformly
+    lit diffuser at ``level`` seen through ``vignette`` (a [H, W] transmission as the function of that name makes it; None = no lens),
+    with the noise (variance alpha*I + beta at the shaded level I), quantisation and clamp of ``make_burst``."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    img = torch.full((height, width), float(level), dtype=torch.float64, device=device)
+    if vignette is not None:
+        img = img * vignette.to(device=device, dtype=torch.float64)
+    out = []
+    for _ in range(frames):
+        noisy = img + torch.randn(img.shape, generator=gen, device=device, dtype=torch.float64) * torch.sqrt(alpha * img + beta)
+        out.append(torch.round(noisy * white + black).clamp(0, 4095).to(torch.int16).contiguous())
+    return out
