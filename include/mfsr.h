@@ -528,7 +528,10 @@ typedef struct {
                                 them ahead of the compute (BASELINE configs[4]: double-buffered H2D) */
     int32_t maskErode;       /* 0 (default): off; 1, 2: radius of the erosion of every moved frame's certainty mask between
                                 stage F and stage G (mfsr_erodeMaskBatch; ghost suppression) */
-    int32_t reserved[1];
+    int32_t rawPacking;      /* 0 (default, MFSR_PACK_NONE): the host frames of mfsr_burst_*_host are uint16_t samples; MFSR_PACK_*:
+                                they are packed 10 / 12-bit rows (mfsr_unpackRaw), uploaded packed into one staging slot per upload
+                                slot and unpacked on the device.  Needs uploadRing > 0 and the packing's width rule (the last of
+                                the reserved ints: sizeof and every other offset are unchanged) */
 } mfsr_config;
 
 typedef struct mfsr_burst mfsr_burst;
@@ -599,7 +602,13 @@ int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_
  * slots inside the workspace, so that the upload of frame k+1.. overlaps the align+fuse of frame k (the reference
  * uploads its frames one blocking copy at a time, multi_frame_sr.cpp:167-174).  hostRaw must stay valid and unchanged
  * until the stream has passed the call's work; pinned memory (hipHostMalloc) is what makes the copies asynchronous.
- * add_frame_host(isReference) with the pointer last given to set_reference_host re-uses the uploaded reference. */
+ * add_frame_host(isReference) with the pointer last given to set_reference_host re-uses the uploaded reference.
+ * A host frame is `height` rows, mfsr_burst_set_host_row_bytes apart (default: dense).  With cfg.rawPacking != 0 the host
+ * pointers of set_reference_host / add_frame_host / prefetch_host mean PACKED BYTES in the layout of that packing (rows of
+ * mfsr_packed_row_bytes(cfg.rawPacking, width) bytes; the declarations keep their uint16_t type, cast the pointer): the
+ * library uploads the packed bytes and unpacks them on the device (mfsr_unpackRaw) before the first kernel that reads the
+ * frame; the result is bit for bit that of the burst of the unpacked samples.  Bytes of a row beyond the dense row size
+ * (line padding) do not cross the link. */
 int mfsr_burst_set_reference_host(mfsr_burst* b, const uint16_t* hostRaw, mfsr_stream_t stream);
 int mfsr_burst_add_frame_host(mfsr_burst* b, const uint16_t* hostRaw, int isReference, mfsr_float3* imgOut,
                               mfsr_float3* totalWeights, mfsr_stream_t stream);
@@ -613,10 +622,21 @@ int mfsr_burst_add_frame_host(mfsr_burst* b, const uint16_t* hostRaw, int isRefe
 int mfsr_burst_prefetch_host(mfsr_burst* b, const uint16_t* const* hostRaws, int nFrames, mfsr_stream_t stream);
 /* mfsr_burst_finish into out16Dev (device), then its D2H copy into out16Host on a stream the burst owns, so that the next
  * burst's uploads and kernels overlap the download (full-duplex PCIe).  out16Host is complete after
- * mfsr_burst_host_sync(b) (blocks the HOST on the download); out16Dev must not be written by the caller before that. */
+ * mfsr_burst_host_sync(b) (blocks the HOST on the download); out16Dev must not be written by the caller before that.
+ * A host burst (set_reference_host .. finish_host, packed or not) may be captured into a graph on `stream`: the uploads, the
+ * unpack and the download become nodes of it, finish_host joins the download back into `stream` (the image is in out16Host when
+ * a replay has completed; host_sync has nothing to wait for), and the host buffers are the graph's inputs and output.  Call
+ * mfsr_burst_host_sync and synchronise `stream` before the capture, and before a replay that follows eager host bursts of the
+ * same handle: a graph cannot wait for their copies. */
 int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, uint16_t* out16Dev,
                            uint16_t* out16Host, mfsr_stream_t stream);
 int mfsr_burst_host_sync(mfsr_burst* b);
+/* Row stride in bytes of the host frames of the following mfsr_burst_*_host calls; 0 = dense (the default).  The dense row is
+ * 2*width bytes of uint16_t samples, or mfsr_packed_row_bytes(cfg.rawPacking, width) of packed bytes; a larger stride is a host
+ * frame with padded lines (the padding is not uploaded).  Between bursts only: MFSR_E_INVALID while frames are pending, for a
+ * stride below the dense row size, for an odd stride of uint16_t rows, for a burst without an upload ring, and for a non-dense
+ * stride when the environment asks for 1-D uploads (MFSR_UPLOAD_1D=1).  Host arithmetic only, no device call. */
+int mfsr_burst_set_host_row_bytes(mfsr_burst* b, int rowBytes);
 /* ---- building blocks of stripe-sharded bursts (multi-GPU, include/mfsr_dist.h): a frame is ALIGNED on the rank that
  * holds it (flow field + certainty mask into caller buffers, no accumulation), the ranks exchange the rows of raw / flow /
  * mask their stripes need, and every rank FUSES all frames, in frame order, onto its own stripe of HR rows -- the
@@ -711,7 +731,8 @@ typedef struct {
     void* user;
 } mfsr_frame_source;
 /* reset, then pull up to cfg.frames frames (the first one is the reference: cfg.reference must be 0), fuse them and
- * finish into outImg / out16 (either may be NULL); *framesUsed = frames delivered.  imgOut / totalWeights: accumulators. */
+ * finish into outImg / out16 (either may be NULL); *framesUsed = frames delivered.  imgOut / totalWeights: accumulators.
+ * MFSR_E_INVALID for a burst created with cfg.rawPacking != 0: the source writes uint16_t samples into the slots itself. */
 int mfsr_burst_process_source(mfsr_burst* b, const mfsr_frame_source* src, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                               mfsr_float3* outImg, uint16_t* out16, int* framesUsed, mfsr_stream_t stream);
 
@@ -884,6 +905,33 @@ int mfsr_shading_defaults(const mfsr_config* cfg, int32_t black[4], int32_t* sat
  * usual begin / set_reference / add_frame / finish (shading goes after the defect repair and before the selection). */
 int mfsr_burst_correct_shading(mfsr_burst* b, int nFrames, uint16_t* const* frames, const int32_t* mapDev, int cell,
                                mfsr_stream_t stream);
+
+/* ---- packed raw frames: the 10 / 12-bit packings sensors and raw files deliver, widened on the device to the uint16_t samples
+ * every other entry point takes.  P is a sample and B a byte of ONE ROW; rows are independent and
+ * a row starts at a byte boundary (its first byte is B0 of its first group).
+ *   MFSR_PACK_MIPI10  4 samples in 5 bytes (CSI-2 RAW10):  B0 = P0>>2, B1 = P1>>2, B2 = P2>>2, B3 = P3>>2,
+ *                     B4 = (P0&3) | (P1&3)<<2 | (P2&3)<<4 | (P3&3)<<6
+ *   MFSR_PACK_MIPI12  2 samples in 3 bytes (CSI-2 RAW12):  B0 = P0>>4, B1 = P1>>4, B2 = (P0&15) | (P1&15)<<4
+ *   MFSR_PACK_BE10    4 samples in 5 bytes, big-endian bit stream (DNG / TIFF), first sample in the most significant bits:
+ *                     B0 = P0>>2, B1 = (P0&3)<<6 | P1>>4, B2 = (P1&15)<<4 | P2>>6, B3 = (P2&63)<<2 | P3>>8, B4 = P3&255
+ *   MFSR_PACK_BE12    2 samples in 3 bytes, big-endian bit stream:  B0 = P0>>4, B1 = (P0&15)<<4 | P1>>8, B2 = P1&255
+ * Samples come out as they are (0..1023 / 0..4095): no shift, no scaling; a burst's cfg.black / white / maxVal describe that
+ * range.  width is a multiple of 4 (10 bits) or 2 (12 bits); the dense row is width*bits/8 bytes.
+ * mfsr_packed_row_bytes: that size; host arithmetic; MFSR_E_INVALID (< 0) for an unknown packing (MFSR_PACK_NONE included) or
+ * a width that is not positive or breaks the rule.
+ * mfsr_unpackRaw: packed = host array of nFrames DEVICE pointers to packed frames (any alignment), rows rowBytes >= the dense
+ * row size apart (bytes of a row beyond the dense size are never read); frames = host array of nFrames DEVICE pointers (u16,
+ * 2-byte aligned, rows `pitch` bytes apart, pitch >= 2*width and even; bytes of a row beyond 2*width are never written);
+ * 1 <= nFrames <= 64, height >= 1.  One launch for all frames.  Source and destination must not overlap.  Every argument is
+ * checked on the host before any device call (MFSR_E_INVALID).  Exact: integers only. */
+#define MFSR_PACK_NONE 0
+#define MFSR_PACK_MIPI10 1
+#define MFSR_PACK_MIPI12 2
+#define MFSR_PACK_BE10 3
+#define MFSR_PACK_BE12 4
+int mfsr_packed_row_bytes(int packing, int width);
+int mfsr_unpackRaw(int nFrames, const uint8_t* const* packed, int rowBytes, int packing, uint16_t* const* frames, int pitch,
+                   int width, int height, mfsr_stream_t stream);
 
 /* ---- noise-model calibration: measure the affine noise model var = alpha * I + beta of the robustness model (cfg.alpha,
  * cfg.beta) from raw frames of the sensor at the gain in use.  An exact-integer device stage and a small

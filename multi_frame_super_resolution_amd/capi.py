@@ -99,6 +99,21 @@ class Config(ctypes.Structure):
         ("maskErode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 1),
     ]
 
+    # mfsr_config.rawPacking is the int that used to be reserved[0]: the ctypes field keeps its name (and so every offset),
+    # the header's name reads and writes it
+    @property
+    def rawPacking(self) -> int:
+        return self.reserved[0]
+
+    @rawPacking.setter
+    def rawPacking(self, packing: int):
+        self.reserved[0] = int(packing)
+
+
+# mfsr_config.rawPacking / mfsr_unpackRaw (include/mfsr.h: the layouts bit by bit)
+PACK_NONE, PACK_MIPI10, PACK_MIPI12, PACK_BE10, PACK_BE12 = 0, 1, 2, 3, 4
+PACK_BITS = {PACK_MIPI10: 10, PACK_MIPI12: 12, PACK_BE10: 10, PACK_BE12: 12}
+
 
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
@@ -195,7 +210,7 @@ class _Lib:
         full = raw.__name__ if hasattr(raw, "__name__") else name
         ret = self.protos[full][0]
         if ret != "int" or full in ("mfsr_version", "mfsr_device_count", "mfsr_gaussin_filter_1D", "mfsr_burst_group_size",
-                                     "mfsr_trackTilesFastSupported"):
+                                     "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes"):
             return raw
 
         def checked(*a):

@@ -88,6 +88,8 @@ struct Layout {
     // host-frame bursts (cfg.uploadRing): device slots the library uploads into
     uint16_t* rawRing[kMaxUploadRing];
     uint16_t* refRaw[2];
+    // cfg.rawPacking: the packed bytes of upload slot i as they came over the link ([ring], [ring + 1] = the reference slots)
+    uint8_t* stage[kMaxUploadRing + 2];
     size_t total;
 };
 
@@ -150,6 +152,8 @@ int validate(const mfsr_config* c)
     MFSR_REQUIRE(c->uploadRing == 0 || (c->uploadRing >= 3 && c->uploadRing <= kMaxUploadRing));
     MFSR_REQUIRE(c->pairFrames >= 0 && c->pairFrames <= MFSR_MAX_FUSE_GROUP);
     MFSR_REQUIRE(c->maskErode >= 0 && c->maskErode <= 2);
+    // packed host frames: the library's own uploads only, and rows of whole groups
+    if (c->rawPacking != MFSR_PACK_NONE) MFSR_REQUIRE(c->uploadRing > 0 && mfsr_packed_row_bytes(c->rawPacking, c->width) > 0);
     return MFSR_OK;
 }
 
@@ -255,6 +259,9 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
     // the erosion cannot run in place: one scratch mask per frame of a group, and only when the option is on
     if (c->maskErode > 0)
         for (int i = 0; i < mfsr_burst_group_size(c); i++) L->maskRaw[i] = b.image(L->hw, L->hh, 16);
+    if (c->rawPacking != MFSR_PACK_NONE)
+        for (int i = 0; i < c->uploadRing + 2; i++)
+            L->stage[i] = (uint8_t*)b.take((size_t)mfsr_packed_row_bytes(c->rawPacking, L->W) * L->H);
     L->total = align_up(b.off, 256);
 }
 
@@ -342,6 +349,16 @@ struct mfsr_burst {
     hipEvent_t evUp[kMaxUploadRing + 2];    // upload of the slot complete (copy stream); [ring..ring+1] = reference slots
     hipEvent_t evFree[kMaxUploadRing + 2];  // last consumer of the slot enqueued (compute / fuse stream)
     bool freeRecorded[kMaxUploadRing + 2];
+    hipStream_t freeOn[kMaxUploadRing + 2]; // the stream evFree was recorded on
+    int hostRowBytes;                       // row stride of the host frames (mfsr_burst_set_host_row_bytes); 0 = dense
+    // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
+    // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
+    unsigned long long hostEpoch;
+    hipEvent_t evEpoch;
+    // cfg.rawPacking: a slot's upload lands in L.stage[slot]; the compute stream unpacks it into the slot
+    hipEvent_t evUnp[kMaxUploadRing + 2];   // recorded on the compute stream after an unpack launch whose first slot this is
+    hipEvent_t unpDone[kMaxUploadRing + 2]; // the event (one of evUnp) after the launch that last read the slot's staging; or null
+    int unpQ[kMaxUploadRing + 2], nUnp;     // slots uploaded and not unpacked yet, in the order of their uploads
     // mfsr_burst_prefetch_host: frames whose upload is already enqueued, in order; consumed by add_frame_host
     struct Prefetched {
         const uint16_t* host;
@@ -561,17 +578,24 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->upPendingSlot = -1;
     b->nPrefetched = b->prefetchHead = 0;
     for (int i = 0; i < kMaxUploadRing + 2; i++) {
-        b->evUp[i] = b->evFree[i] = nullptr;
+        b->evUp[i] = b->evFree[i] = b->evUnp[i] = b->unpDone[i] = nullptr;
         b->freeRecorded[i] = false;
+        b->freeOn[i] = nullptr;
     }
+    b->hostRowBytes = 0;
+    b->nUnp = 0;
+    b->hostEpoch = 0;
+    b->evEpoch = nullptr;
     if (cfg->uploadRing > 0) {
         hipError_t e = hipStreamCreateWithFlags(&b->copyStream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->downStream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evFinished, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evDown, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evEpoch, hipEventDisableTiming);
         for (int i = 0; i < cfg->uploadRing + 2 && e == hipSuccess; i++) {
             e = hipEventCreateWithFlags(&b->evUp[i], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evFree[i], hipEventDisableTiming);
+            if (e == hipSuccess && cfg->rawPacking != MFSR_PACK_NONE) e = hipEventCreateWithFlags(&b->evUnp[i], hipEventDisableTiming);
         }
         if (e != hipSuccess) {
             mfsr_burst_destroy(b);
@@ -603,12 +627,14 @@ extern "C" void mfsr_burst_destroy(mfsr_burst* b)
     if (b->downStream) (void)hipStreamSynchronize(b->downStream);
     if (b->evFinished) (void)hipEventDestroy(b->evFinished);
     if (b->evDown) (void)hipEventDestroy(b->evDown);
+    if (b->evEpoch) (void)hipEventDestroy(b->evEpoch);
     for (int i = 0; i < 16; i++)
         if (b->evBand[i]) (void)hipEventDestroy(b->evBand[i]);
     if (b->downStream) (void)hipStreamDestroy(b->downStream);
     for (int i = 0; i < kMaxUploadRing + 2; i++) {
         if (b->evUp[i]) (void)hipEventDestroy(b->evUp[i]);
         if (b->evFree[i]) (void)hipEventDestroy(b->evFree[i]);
+        if (b->evUnp[i]) (void)hipEventDestroy(b->evUnp[i]);
     }
     if (b->copyStream) (void)hipStreamDestroy(b->copyStream);
     delete b;
@@ -646,12 +672,56 @@ extern "C" int mfsr_burst_timing_read(mfsr_burst* b, double* totalMs, int* launc
 }
 
 // host-frame bursts: `stream` is about to read raw frames the copy stream uploads -- wait for the last upload enqueued so far
+// (cfg.rawPacking: the frames then arrived packed, in the slots' staging buffers -- `stream` also unpacks them into the slots)
+static int unpack_uploaded(mfsr_burst* b, int lastSlot, mfsr_stream_t stream);
 static int wait_uploads(mfsr_burst* b, mfsr_stream_t stream)
 {
     if (b->upPending) {
         MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evUp[b->upPendingSlot], 0));
         b->upPending = false;
+        if (b->nUnp > 0) TRY(unpack_uploaded(b, b->upPendingSlot, stream));
     }
+    return MFSR_OK;
+}
+
+// the last consumer of upload slot `us` has been enqueued on `stream`: whoever writes the slot next waits for it
+static int record_free(mfsr_burst* b, int us, mfsr_stream_t stream)
+{
+    MFSR_HIP_TRY(hipEventRecord(b->evFree[us], mfsr_s(stream)));
+    b->freeRecorded[us] = true;
+    b->freeOn[us] = mfsr_s(stream);
+    return MFSR_OK;
+}
+
+// cfg.rawPacking: `stream` has waited for the upload of lastSlot, so every upload queued up to it has landed (the copy stream is
+// in order).  ONE mfsr_unpackRaw launch widens them from their staging buffers into their slots.  The slots' previous frames may
+// still be read on another stream (the fuse stream of cfg.asyncFuse): the launch waits for each slot's evFree -- the wait the copy
+// stream makes when it writes the slots itself.  The staging buffers may be refilled after the launch: the event recorded here.
+static int unpack_uploaded(mfsr_burst* b, int lastSlot, mfsr_stream_t stream)
+{
+    const Layout& L = b->L;
+    int n = 0;
+    while (n < b->nUnp && b->unpQ[n] != lastSlot) n++;
+    if (n == b->nUnp) return MFSR_OK;  // (unpacked already, with a later upload)
+    n++;
+    const uint8_t* packed[kMaxUploadRing + 2];
+    uint16_t* frames[kMaxUploadRing + 2];
+    for (int i = 0; i < n; i++) {
+        const int us = b->unpQ[i];
+        packed[i] = L.stage[us];
+        frames[i] = us < b->cfg.uploadRing ? L.rawRing[us] : L.refRaw[us - b->cfg.uploadRing];
+        if (b->freeRecorded[us]) {
+            if (b->freeOn[us] != mfsr_s(stream)) MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFree[us], 0));
+            b->freeRecorded[us] = false;
+        }
+    }
+    static_assert(kMaxUploadRing + 2 <= kRawMaxFrames, "one launch takes every upload slot");
+    TRY(mfsr_unpackRaw(n, packed, mfsr_packed_row_bytes(b->cfg.rawPacking, L.W), b->cfg.rawPacking, frames, 2 * L.W, L.W, L.H, stream));
+    hipEvent_t done = b->evUnp[b->unpQ[0]];
+    MFSR_HIP_TRY(hipEventRecord(done, mfsr_s(stream)));
+    for (int i = 0; i < n; i++) b->unpDone[b->unpQ[i]] = done;
+    for (int i = n; i < b->nUnp; i++) b->unpQ[i - n] = b->unpQ[i];
+    b->nUnp -= n;
     return MFSR_OK;
 }
 
@@ -1005,10 +1075,7 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
         // upload slots whose raw frame this launch was the last to read may be overwritten once it has run
         for (int j = 0; j < n; j++) {
             const int us = upload_slot_of(b, p.raw[j]);
-            if (us >= 0) {
-                MFSR_HIP_TRY(hipEventRecord(b->evFree[us], mfsr_s(stream)));
-                b->freeRecorded[us] = true;
-            }
+            if (us >= 0) TRY(record_free(b, us, stream));
         }
     }
     if (b->fuseStream) {
@@ -1742,9 +1809,79 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
 // ---- host-frame bursts (cfg.uploadRing) --------------------------------------------------------------------------
 // enqueue the upload of hostRaw into upload slot `us` on the copy stream (after the slot's last consumer) and make the
 // compute stream wait for it
+// A host burst captured into a graph.  The events that order one burst's copies against the burst before it (evFree, unpDone,
+// evDown) hold across calls, and an event recorded outside a capture cannot be waited for inside it, nor the other way round.
+// So every host entry point looks at the capture `stream` is in; when that is another one than at the last call (a capture
+// began, ended, or a second one began), the events of the old one are forgotten and the copy and the download stream are
+// forked off `stream` instead: they then follow everything enqueued on it so far, and inside a capture that wait is what
+// makes them part of the graph.  What a graph cannot see is work of an EAGER burst still in flight on those two streams:
+// mfsr_burst_host_sync before the capture, and before a replay that follows eager bursts of the same handle (mfsr.h).
+// Nothing is enqueued while the capture stays the same: the eager launch sequence is untouched.
+static int host_epoch(mfsr_burst* b, mfsr_stream_t stream, bool* capturing = nullptr)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    unsigned long long id = 0;
+    if (hipStreamGetCaptureInfo(mfsr_s(stream), &cap, &id) != hipSuccess) cap = hipStreamCaptureStatusNone;
+    const unsigned long long epoch = cap == hipStreamCaptureStatusActive ? (id ? id : ~0ull) : 0;
+    if (capturing) *capturing = epoch != 0;
+    if (epoch == b->hostEpoch) return MFSR_OK;
+    b->hostEpoch = epoch;
+    for (int i = 0; i < kMaxUploadRing + 2; i++) {
+        b->freeRecorded[i] = false;
+        b->unpDone[i] = nullptr;
+    }
+    b->downRecorded = false;
+    b->upPending = false;
+    b->nUnp = 0;
+    b->nPrefetched = b->prefetchHead = 0;
+    MFSR_HIP_TRY(hipEventRecord(b->evEpoch, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamWaitEvent(b->copyStream, b->evEpoch, 0));
+    MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evEpoch, 0));
+    return MFSR_OK;
+}
+
+// the end of a captured host burst: the download (and any announced copy no frame consumed) joins `stream`, so that the capture
+// can end; the image is in host memory when a replay of the graph has completed, and mfsr_burst_host_sync has nothing to wait for
+static int join_captured(mfsr_burst* b, mfsr_stream_t stream)
+{
+    MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evDown, 0));
+    MFSR_HIP_TRY(hipEventRecord(b->evEpoch, b->copyStream));
+    MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evEpoch, 0));
+    b->downRecorded = false;
+    return MFSR_OK;
+}
+
+// MFSR_UPLOAD_1D=1: the round-3 form of the uploads (A/B, see upload_into)
+static bool upload_1d()
+{
+    static const bool up1d = [] {
+        const char* e = getenv("MFSR_UPLOAD_1D");
+        return e && e[0] == '1';
+    }();
+    return up1d;
+}
+
 static int upload_into(mfsr_burst* b, int us, uint16_t* dst, const uint16_t* hostRaw, mfsr_stream_t stream)
 {
-    if (b->freeRecorded[us]) {
+    // a host row: rowBytes of samples (or of packed bytes), hostPitch apart
+    const bool isPacked = b->cfg.rawPacking != MFSR_PACK_NONE;
+    const size_t rowBytes = isPacked ? (size_t)mfsr_packed_row_bytes(b->cfg.rawPacking, b->L.W) : (size_t)b->L.W * 2;
+    const size_t hostPitch = b->hostRowBytes > 0 ? (size_t)b->hostRowBytes : rowBytes;
+    void* to = dst;
+    if (isPacked) {
+        // The copy writes the slot's STAGING buffer: it waits for the unpack that read the buffer's previous frame, not for the
+        // slot's consumers (the unpack waits for those, unpack_uploaded).  A slot whose unpack has not been enqueued yet is not
+        // refilled before it has.
+        for (int i = 0; i < b->nUnp; i++)
+            if (b->unpQ[i] == us) {
+                MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evUp[b->unpQ[b->nUnp - 1]], 0));
+                TRY(unpack_uploaded(b, b->unpQ[b->nUnp - 1], stream));
+                break;
+            }
+        if (b->unpDone[us]) MFSR_HIP_TRY(hipStreamWaitEvent(b->copyStream, b->unpDone[us], 0));
+        b->unpDone[us] = nullptr;
+        to = b->L.stage[us];
+    } else if (b->freeRecorded[us]) {
         MFSR_HIP_TRY(hipStreamWaitEvent(b->copyStream, b->evFree[us], 0));
         b->freeRecorded[us] = false;
     }
@@ -1753,16 +1890,14 @@ static int upload_into(mfsr_burst* b, int us, uint16_t* dst, const uint16_t* hos
     // 8.38 ms, the sum of the two directions alone -- while 2-D uploads and 2-D downloads overlap on the full-duplex link:
     // 4.85 ms = the uploads alone.  (A 1-D download would overlap too, but it is a blit kernel whose PCIe-bound stores slow
     // the fuse launches 4-5x.)  MFSR_UPLOAD_1D=1: the round-3 form (A/B).
-    static const bool up1d = [] {
-        const char* e = getenv("MFSR_UPLOAD_1D");
-        return e && e[0] == '1';
-    }();
-    if (up1d)
-        MFSR_HIP_TRY(hipMemcpyAsync(dst, hostRaw, (size_t)b->L.W * b->L.H * 2, hipMemcpyHostToDevice, b->copyStream));
+    // (Host rows farther apart than they are long -- mfsr_burst_set_host_row_bytes -- are the 2-D copy's source pitch: the
+    // padding of a line never crosses the link.)
+    if (upload_1d())
+        MFSR_HIP_TRY(hipMemcpyAsync(to, hostRaw, rowBytes * b->L.H, hipMemcpyHostToDevice, b->copyStream));
     else
-        MFSR_HIP_TRY(hipMemcpy2DAsync(dst, (size_t)b->L.W * 2, hostRaw, (size_t)b->L.W * 2, (size_t)b->L.W * 2, (size_t)b->L.H,
-                                      hipMemcpyHostToDevice, b->copyStream));
+        MFSR_HIP_TRY(hipMemcpy2DAsync(to, rowBytes, hostRaw, hostPitch, rowBytes, (size_t)b->L.H, hipMemcpyHostToDevice, b->copyStream));
     MFSR_HIP_TRY(hipEventRecord(b->evUp[us], b->copyStream));
+    if (isPacked) b->unpQ[b->nUnp++] = us;
     // the compute stream waits for it when the first kernel that reads an uploaded frame is about to be enqueued
     // (wait_uploads): ONE wait for the last upload of a group instead of one per frame -- a cross-queue wait costs the
     // compute queue ~15 us even when it is already satisfied (four in a row before a group's first kernel: 55-68 us in the
@@ -1777,7 +1912,9 @@ extern "C" int mfsr_burst_set_reference_host(mfsr_burst* b, const uint16_t* host
 {
     MFSR_REQUIRE(b && hostRaw);
     MFSR_REQUIRE(b->copyStream != nullptr);  // cfg.uploadRing > 0
+    TRY(host_epoch(b, stream));
     TRY(flush_pending(b, stream, false));    // a frame still waiting reads the previous reference's slots
+    b->nUnp = 0;                             // (packed frames the last burst announced and did not consume: never unpacked)
     static const bool adaptive = [] {
         const char* e = getenv("MFSR_HOST_ADAPTIVE");
         return !(e && e[0] == '0');
@@ -1795,10 +1932,7 @@ extern "C" int mfsr_burst_set_reference_host(mfsr_burst* b, const uint16_t* host
     // upload does not wait for the tail of the burst before this one, which is still being fused and downloaded when
     // bursts come back to back.  A burst that ended another way: the slot was last read by work already enqueued on the
     // compute stream.
-    if (!b->freeRecorded[us]) {
-        MFSR_HIP_TRY(hipEventRecord(b->evFree[us], mfsr_s(stream)));
-        b->freeRecorded[us] = true;
-    }
+    if (!b->freeRecorded[us]) TRY(record_free(b, us, stream));
     b->refSlot = us;
     b->nPrefetched = b->prefetchHead = 0;
     TRY(upload_into(b, us, b->L.refRaw[i], hostRaw, stream));
@@ -1812,6 +1946,7 @@ extern "C" int mfsr_burst_add_frame_host(mfsr_burst* b, const uint16_t* hostRaw,
 {
     MFSR_REQUIRE(b && hostRaw && imgOut && totalWeights);
     MFSR_REQUIRE(b->copyStream != nullptr);
+    TRY(host_epoch(b, stream));
     static const bool banded = [] {
         const char* e = getenv("MFSR_HOST_BANDS");
         return !(e && e[0] == '0');
@@ -1845,6 +1980,7 @@ extern "C" int mfsr_burst_prefetch_host(mfsr_burst* b, const uint16_t* const* ho
 {
     MFSR_REQUIRE(b && hostRaws && nFrames >= 0);
     MFSR_REQUIRE(b->copyStream != nullptr);
+    TRY(host_epoch(b, stream));
     b->nPrefetched = b->prefetchHead = 0;
     // only at the start of a burst: no frame may be waiting in a slot the copies would overwrite
     if (b->pend.n > 0 || b->heldHas) return MFSR_OK;
@@ -1875,8 +2011,7 @@ extern "C" int mfsr_burst_prefetch_host(mfsr_burst* b, const uint16_t* const* ho
 static int release_ref_slot(mfsr_burst* b, mfsr_stream_t stream)
 {
     if (b->refSlot >= 0) {
-        MFSR_HIP_TRY(hipEventRecord(b->evFree[b->refSlot], mfsr_s(stream)));
-        b->freeRecorded[b->refSlot] = true;
+        TRY(record_free(b, b->refSlot, stream));
         b->refSlot = -1;
     }
     return MFSR_OK;
@@ -1888,6 +2023,8 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(b && imgOut && totalWeights && out16Dev && out16Host);
     MFSR_REQUIRE(b->downStream != nullptr);  // cfg.uploadRing > 0
     MFSR_REQUIRE(b->haveRef);
+    bool capturing = false;
+    TRY(host_epoch(b, stream, &capturing));
     const mfsr_config& c = b->cfg;
     Layout& L = b->L;
     // the previous image may still be on its way to the host out of out16Dev
@@ -1926,6 +2063,8 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
                                       b->downStream));
         MFSR_HIP_TRY(hipEventRecord(b->evDown, b->downStream));
         b->downRecorded = true;
+        b->nUnp = 0;  // (packed frames that were announced and not consumed are never unpacked)
+        if (capturing) TRY(join_captured(b, stream));
         return release_ref_slot(b, stream);
     }
     mfsr_burst::Pending p = b->pend, p0;
@@ -1992,16 +2131,28 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
             const mfsr_burst::Pending& q = gi ? p : p0;
             for (int j = 0; j < q.n; j++) {
                 const int us = upload_slot_of(b, q.raw[j]);
-                if (us >= 0) {
-                    MFSR_HIP_TRY(hipEventRecord(b->evFree[us], mfsr_s(stream)));
-                    b->freeRecorded[us] = true;
-                }
+                if (us >= 0) TRY(record_free(b, us, stream));
             }
         }
     }
     MFSR_HIP_TRY(hipEventRecord(b->evDown, b->downStream));
     b->downRecorded = true;
+    b->nUnp = 0;  // (packed frames that were announced and not consumed are never unpacked)
+    if (capturing) TRY(join_captured(b, stream));
     return release_ref_slot(b, stream);
+}
+
+extern "C" int mfsr_burst_set_host_row_bytes(mfsr_burst* b, int rowBytes)
+{
+    MFSR_REQUIRE(b != nullptr && b->cfg.uploadRing > 0);
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    const bool isPacked = b->cfg.rawPacking != MFSR_PACK_NONE;
+    const int dense = isPacked ? mfsr_packed_row_bytes(b->cfg.rawPacking, b->L.W) : 2 * b->L.W;
+    MFSR_REQUIRE(rowBytes == 0 || rowBytes >= dense);
+    MFSR_REQUIRE(isPacked || (rowBytes % 2) == 0);             // uint16_t rows
+    MFSR_REQUIRE(rowBytes == 0 || rowBytes == dense || !upload_1d());
+    b->hostRowBytes = rowBytes;
+    return MFSR_OK;
 }
 
 extern "C" int mfsr_burst_host_sync(mfsr_burst* b)
@@ -2017,6 +2168,7 @@ extern "C" int mfsr_burst_process_source(mfsr_burst* b, const mfsr_frame_source*
 {
     MFSR_REQUIRE(b && src && src->next_frame && imgOut && totalWeights && (outImg || out16));
     MFSR_REQUIRE(b->copyStream != nullptr);  // cfg.uploadRing >= 3: the ring slots are the buffers the source fills
+    MFSR_REQUIRE(b->cfg.rawPacking == MFSR_PACK_NONE);  // the source writes uint16_t samples: no staging, no unpack
     MFSR_REQUIRE(b->cfg.reference == 0);
     if (framesUsed) *framesUsed = 0;
     if (src->reset) src->reset(src->user);

@@ -1,4 +1,4 @@
-// raw_stage.hpp -- what the raw-domain stages share (select.hip, exposure.hip, noise.hip, defect.hip, shading.hip):
+// raw_stage.hpp -- what the raw-domain stages share (select.hip, exposure.hip, noise.hip, defect.hip, shading.hip, unpack.hip):
 // the frame table of a launch, the host checks of their entry points, the whole-wave exchanges, and for the two stages that
 // stream quad rows down strips and bands (k_frameSharpness, k_frameLevels) the loader and the band planner.  Internal: every
 // rule an entry point states in include/mfsr.h is composed from the checks here, and a check is shared only where the rule
@@ -46,7 +46,8 @@ static inline bool raw_half_rect_ok(const int32_t rect[4], int width, int height
 }
 
 // every frame pointer and the pitch are multiples of `bytes`: the kernels' VEC decision
-static inline bool raw_aligned(int nFrames, const uint16_t* const* frames, int pitch, int bytes)
+template <typename T>
+static inline bool raw_aligned(int nFrames, T* const* frames, int pitch, int bytes)
 {
     bool ok = (pitch % bytes) == 0;
     for (int k = 0; k < nFrames; k++) ok = ok && ((uintptr_t)frames[k] % (uintptr_t)bytes) == 0;

@@ -429,6 +429,55 @@ def apply_shading(frames: Sequence[torch.Tensor], gain_map: torch.Tensor, cfg: c
     return out
 
 
+def packed_row_bytes(packing: int, width: int) -> int:
+    """Bytes of a dense packed row of ``width`` samples (mfsr_packed_row_bytes): width * bits / 8.  ValueError for an unknown
+    packing or a width that is not a whole number of groups (4 samples at 10 bits, 2 at 12)."""
+    n = capi.lib().raw["mfsr_packed_row_bytes"](int(packing), int(width))
+    if n < 0:
+        raise ValueError(f"packing {packing} does not take rows of {width} samples")
+    return n
+
+
+def unpack_raw(packed, packing: int, width: int, out=None):
+    """Packed 10 / 12-bit frames widened to 16-bit samples on the device (mfsr_unpackRaw; the layouts of
+    ``capi.PACK_*`` are stated in include/mfsr.h).  ``packed``: a uint8 device tensor [height, rowBytes] or a sequence of such
+    tensors of one shape and row stride, rowBytes >= ``packed_row_bytes(packing, width)`` (bytes beyond the dense row are line
+    padding and are not read); rows contiguous, the tensors may be pitched views at any byte offset.  ``out``: int16 / uint16
+    device tensors [height, width] (one, or a sequence), rows contiguous, one row stride; by default fresh dense uint16
+    tensors.  Samples come out as they are (0..1023 / 0..4095).  One launch per 64 frames on the current stream.  Returns
+    ``out`` (a tensor for a tensor, a list for a sequence)."""
+    single = isinstance(packed, torch.Tensor)
+    ins = [packed] if single else list(packed)
+    if not ins:
+        raise ValueError("at least one frame is needed")
+    dense = packed_row_bytes(packing, width)
+    dev, h, row_bytes = ins[0].device, int(ins[0].shape[0]), ins[0].stride(0)
+    for t in ins:
+        if not (t.is_cuda and t.device == dev and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[0] == h and h > 0
+                and t.shape[1] >= dense and t.stride(1) == 1 and t.stride(0) == row_bytes):
+            raise ValueError(f"packed frames must be uint8 [height, >= {dense}] tensors on one HIP device with contiguous rows "
+                             "and one row stride")
+    if out is None:
+        outs = [torch.empty(h, width, dtype=torch.uint16, device=dev) for _ in ins]
+        ret = outs[0] if single else outs
+    else:
+        outs = [out] if isinstance(out, torch.Tensor) else list(out)
+        ret = out
+        if len(outs) != len(ins):
+            raise ValueError("out must have as many frames as the input")
+    pitch = outs[0].stride(0) * 2
+    for t in outs:
+        if not (t.is_cuda and t.device == dev and t.dtype in (torch.int16, torch.uint16) and tuple(t.shape) == (h, width)
+                and t.stride(1) == 1 and t.stride(0) * 2 == pitch):
+            raise ValueError(f"out: 16-bit {h}x{width} tensors on the input's device with contiguous rows and one row stride")
+    with torch.cuda.device(dev):
+        for k0 in range(0, len(ins), 64):
+            n = min(64, len(ins) - k0)
+            capi.lib().unpackRaw(n, _ptr_table(ins[k0:k0 + n]), row_bytes, int(packing), _ptr_table(outs[k0:k0 + n]), pitch,
+                                 int(width), h, torch.cuda.current_stream().cuda_stream)
+    return ret
+
+
 def erode_mask(masks, radius: int, out=None):
     """Erosion of certainty masks (mfsr_erodeMaskBatch): every colour certainty (.x .y .z) becomes its
     minimum over the (2*radius+1)^2 neighbourhood clamped to the interior, .w passes through, the one-cell ring is zero.
@@ -756,13 +805,35 @@ class BurstPipeline:
     def process_host(self, host_frames: Sequence[torch.Tensor], out16_host: Optional[torch.Tensor] = None):
         """Whole burst from HOST frames (pin them: ``t.pin_memory()``) to the u16 HR image in host memory:
         mfsr_burst_set_reference_host / add_frame_host / finish_host.  Returns the (pinned) host image; it is complete
-        after ``host_sync()`` (the download runs on a stream of its own so that the next burst overlaps it)."""
+        after ``host_sync()`` (the download runs on a stream of its own so that the next burst overlaps it).
+        With ``cfg.rawPacking`` the frames are uint8 tensors [height, rowBytes] of packed bytes (``capi.PACK_*``, rowBytes >=
+        ``packed_row_bytes``: what lies beyond the dense row is line padding and is not uploaded); the library unpacks them on
+        the device.  Rows may be padded either way (views with a row stride larger than the row): one stride for the burst.
+        The call may be captured into a graph (``torch.cuda.graph``) after one eager call, ``host_sync()`` and a device
+        synchronisation: the uploads and the download are then nodes of the graph, the pinned host frames its inputs, and the
+        image is in host memory when a replay has completed."""
         if self.cfg.uploadRing <= 0:
             raise ValueError("cfg.uploadRing must be > 0 for host-frame bursts")
+        if not host_frames:
+            raise ValueError("at least one frame is needed")
+        if self.cfg.rawPacking:
+            dense, dtypes, elem = packed_row_bytes(self.cfg.rawPacking, self.cfg.width), (torch.uint8,), 1
+        else:
+            dense, dtypes, elem = 2 * self.cfg.width, (torch.int16, torch.uint16), 2
+        row_bytes = host_frames[0].stride(0) * elem if host_frames[0].dim() == 2 else -1
         for f in host_frames:
-            if f.is_cuda or f.dtype not in (torch.int16, torch.uint16) or not f.is_contiguous() or \
-                    tuple(f.shape) != (self.cfg.height, self.cfg.width):
-                raise ValueError("host frames must be contiguous 16-bit CPU tensors of the configured size")
+            ok = not f.is_cuda and f.dtype in dtypes and f.dim() == 2 and f.shape[0] == self.cfg.height and f.stride(1) == 1 \
+                and f.stride(0) * elem == row_bytes >= dense
+            if ok and self.cfg.rawPacking:
+                ok = f.shape[1] * elem >= dense
+            elif ok:
+                ok = f.shape[1] == self.cfg.width
+            if not ok:
+                raise ValueError("host frames must be CPU tensors with contiguous rows and one row stride: 16-bit of the configured "
+                                 f"size, or with cfg.rawPacking uint8 [height, >= {dense}]")
+        if row_bytes != getattr(self, "_host_row_bytes", dense):
+            self.L.burst_set_host_row_bytes(self._h, row_bytes)
+        self._host_row_bytes = row_bytes
         if out16_host is None:
             if getattr(self, "_out16_host", None) is None:
                 self._out16_host = torch.empty_like(self.out16, device="cpu").pin_memory()

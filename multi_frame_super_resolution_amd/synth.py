@@ -245,3 +245,50 @@ def make_flat_burst(width: int, height: int, frames: int, level: float = 0.6, vi
         noisy = img + torch.randn(img.shape, generator=gen, device=device, dtype=torch.float64) * torch.sqrt(alpha * img + beta)
         out.append(torch.round(noisy * white + black).clamp(0, 4095).to(torch.int16).contiguous())
     return out
+
+
+def pack_raw(frames, packing: int, row_bytes: Optional[int] = None):
+    """Pack 16-bit frames into the 10 / 12-bit layouts of ``capi.PACK_*`` (CPU only; the inverse of ``pipeline.unpack_raw``,
+    for tests and tools: the library itself has no packer).  ``frames``: an integer tensor [height, width] or a sequence of
+    them; every sample must fit the packing's bits and the width be a whole number of groups (4 samples at 10 bits, 2 at 12).
+    ``row_bytes``: the row stride of the result, at least width * bits / 8 (the default); the padding bytes are zero.
+    Returns uint8 CPU tensor(s) [height, row_bytes]: a tensor for a tensor, a list for a sequence."""
+    from .capi import PACK_BE10, PACK_BE12, PACK_BITS, PACK_MIPI10, PACK_MIPI12
+
+    if packing not in PACK_BITS:
+        raise ValueError(f"unknown packing {packing}")
+    bits = PACK_BITS[packing]
+    single = isinstance(frames, torch.Tensor)
+    out = []
+    for f in ([frames] if single else list(frames)):
+        if f.dim() != 2 or f.is_floating_point():
+            raise ValueError("frames must be integer tensors [height, width]")
+        p = f.cpu()
+        p = (p.view(torch.int16) if p.dtype == torch.uint16 else p).to(torch.int32) & 0xffff
+        h, w = p.shape
+        if w == 0 or w % (4 if bits == 10 else 2) != 0:
+            raise ValueError(f"width {w} is not a whole number of {bits}-bit groups")
+        if int(p.max()) >= (1 << bits):
+            raise ValueError(f"a sample does not fit {bits} bits")
+        dense = w * bits // 8
+        rb = dense if row_bytes is None else int(row_bytes)
+        if rb < dense:
+            raise ValueError(f"row_bytes {rb} is below the dense row size {dense}")
+        if bits == 10:
+            p0, p1, p2, p3 = (p[:, j::4] for j in range(4))
+            if packing == PACK_MIPI10:
+                b = [p0 >> 2, p1 >> 2, p2 >> 2, p3 >> 2, (p0 & 3) | (p1 & 3) << 2 | (p2 & 3) << 4 | (p3 & 3) << 6]
+            else:
+                assert packing == PACK_BE10
+                b = [p0 >> 2, (p0 & 3) << 6 | p1 >> 4, (p1 & 15) << 4 | p2 >> 6, (p2 & 63) << 2 | p3 >> 8, p3 & 255]
+        else:
+            p0, p1 = p[:, 0::2], p[:, 1::2]
+            if packing == PACK_MIPI12:
+                b = [p0 >> 4, p1 >> 4, (p0 & 15) | (p1 & 15) << 4]
+            else:
+                assert packing == PACK_BE12
+                b = [p0 >> 4, (p0 & 15) << 4 | p1 >> 8, p1 & 255]
+        rows = torch.zeros(h, rb, dtype=torch.uint8)
+        rows[:, :dense] = torch.stack(b, dim=2).reshape(h, dense).to(torch.uint8)
+        out.append(rows)
+    return out[0] if single else out
