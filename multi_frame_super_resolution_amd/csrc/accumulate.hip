@@ -283,9 +283,10 @@ static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr
             MFSR_HIP_TRY(hipMemset2DAsync(imgOut, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
             MFSR_HIP_TRY(hipMemset2DAsync(totalWeights, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
         } else {
-            const size_t off = (size_t)w.y0 * strideOut, bytes = (size_t)(w.y1 - w.y0) * strideOut;
-            MFSR_HIP_TRY(hipMemsetAsync((char*)imgOut + off, 0, bytes, mfsr_s(stream)));
-            MFSR_HIP_TRY(hipMemsetAsync((char*)totalWeights + off, 0, bytes, mfsr_s(stream)));
+            // the pixels of the rows only: the bytes between a row's end and the pitch are not the accumulators'
+            const size_t off = (size_t)w.y0 * strideOut, rowBytes = (size_t)dimX * scale * 12, rows = (size_t)(w.y1 - w.y0);
+            MFSR_HIP_TRY(hipMemset2DAsync((char*)imgOut + off, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
+            MFSR_HIP_TRY(hipMemset2DAsync((char*)totalWeights + off, strideOut, 0, rowBytes, rows, mfsr_s(stream)));
         }
     }
     for (int n = 0; n < nFrames; n++) {

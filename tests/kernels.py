@@ -84,6 +84,45 @@ class OracleKernels:
         self.o.set_cfa_pattern(np.asarray(pattern, np.int32))
 
 
+# ---- guarded device buffers ---------------------------------------------------------------------------------------
+# Every array a test hands to the HIP library lives in a larger device byte buffer [guard | data | guard] (tests/guards.py).
+# The guards hold 0xFF: NaN as float, 0xFFFF as uint16_t, -1 as int, so a read outside the array poisons what it feeds, and
+# a write outside it is found when the guards are read back.  The data offset is a multiple of 256 (what the entry points
+# may require of a pointer); the trailing guard starts at the first byte after the data.
+DEVICE_GUARD = 4096
+DEVICE_ALIGN = 256
+DEVICE_FILL = 0xFF
+
+
+def guarded_upload(arr: np.ndarray, dev="cuda:0"):
+    """-> (tensor_view, check): ``arr`` on the device between two guards, as a tensor of its shape and type (uint16 as
+    int16).  ``check(what, unchanged=False)`` downloads the buffer once and asserts that both guards are intact (naming
+    which one and the first changed byte) and, with ``unchanged``, that the data still equals what was uploaded."""
+    import torch
+
+    from tests.guards import check_bands, layout
+
+    a = np.ascontiguousarray(arr)
+    raw = a.reshape(-1).view(np.uint8)
+    off, total = layout(a.nbytes, DEVICE_GUARD, DEVICE_ALIGN)
+    big = np.full(total, DEVICE_FILL, np.uint8)
+    big[off:off + a.nbytes] = raw
+    d_big = torch.from_numpy(big).to(dev)
+    assert d_big.data_ptr() % DEVICE_ALIGN == 0
+    tdt = a.dtype if a.dtype != np.uint16 else np.dtype(np.int16)
+    view = d_big[off:off + a.nbytes].view(torch.from_numpy(np.zeros(1, tdt)).dtype).reshape(a.shape)
+    sent = raw.copy()
+
+    def check(what, unchanged=False):
+        h = d_big.cpu().numpy()
+        check_bands(h, off, a.nbytes, DEVICE_FILL, what)
+        if unchanged:
+            bad = np.flatnonzero(h[off:off + a.nbytes] != sent)
+            assert bad.size == 0, f"{what}: a read-only input was changed, first at byte {int(bad[0])}"
+
+    return view, check
+
+
 class HipKernels:
     name = "hip"
 
@@ -105,30 +144,27 @@ class HipKernels:
         torch = self.torch
         uploaded = {}
 
-        def up(a: np.ndarray):
+        def up(a: np.ndarray, index: int):
             key = id(a)
             if key not in uploaded:
                 assert a.flags["C_CONTIGUOUS"]
-                if a.dtype == np.uint16:
-                    t = torch.from_numpy(a.view(np.int16)).to(self.dev)
-                else:
-                    t = torch.from_numpy(a).to(self.dev)
-                uploaded[key] = (a, t)
+                t, check = guarded_upload(a, self.dev)
+                uploaded[key] = (a, t, check, index)
             return uploaded[key][1]
 
         conv = []
-        for a in args:
+        for i, a in enumerate(args):
             if isinstance(a, F3):
                 conv.append(self.capi.f3(a.v))
             elif isinstance(a, F2):
                 conv.append(self.capi.f2(a.v))
             elif isinstance(a, Tex):
-                t = up(a.arr)
+                t = up(a.arr, i)
                 conv.append(self.capi.Tex2D(t.data_ptr(), int(a.pitch), int(a.width), int(a.height)))
             elif isinstance(a, Host):
                 conv.append(a.arr.ctypes.data)
             elif isinstance(a, np.ndarray):
-                conv.append(up(a).data_ptr())
+                conv.append(up(a, i).data_ptr())
             elif a is None:
                 conv.append(None)
             else:
@@ -136,7 +172,9 @@ class HipKernels:
         conv.append(None)  # stream: default
         rc = getattr(self.L, fname)(*conv)
         torch.cuda.synchronize()
-        for a, t in uploaded.values():
+        for a, t, check, index in uploaded.values():
+            check(f"mfsr_{fname}, argument {index}", unchanged=not a.flags["WRITEABLE"])
+        for a, t, check, index in uploaded.values():
             if a.flags["WRITEABLE"]:
                 h = t.cpu().numpy()
                 if a.dtype == np.uint16:

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.kernels import F2, F3, Host, Tex, pitch_of
+from tests.kernels import F2, F3, Host, Tex, guarded_upload, pitch_of
 
 pytestmark = pytest.mark.gpu
 
@@ -277,12 +277,18 @@ def test_accumulate_groups_of_three_and_four(orc, hip, n, field, s, pat, fresh):
         ow[:] = 0
     for raw, m, sh in frames:
         orc.call("accumulateSuperResFull", raw, oi, ow, m, Tex(kp), Tex(sh), white, black, W, H, s, pitch_of(oi), pitch_of(m))
-    dev = hip.dev
-    d_raw = [torch.from_numpy(f[0].view(np.int16)).to(dev) for f in frames]
-    d_mask = [torch.from_numpy(f[1]).to(dev) for f in frames]
-    d_sh = [torch.from_numpy(f[2]).to(dev) for f in frames]
-    d_kp = torch.from_numpy(kp).to(dev)
-    d_i, d_w = torch.from_numpy(hi0).to(dev), torch.from_numpy(hw0).to(dev)
+    checks = []
+
+    def gup(a):
+        t, c = guarded_upload(a, hip.dev)
+        checks.append(c)
+        return t
+
+    d_raw = [gup(f[0]) for f in frames]
+    d_mask = [gup(f[1]) for f in frames]
+    d_sh = [gup(f[2]) for f in frames]
+    d_kp = gup(kp)
+    d_i, d_w = gup(hi0), gup(hw0)
     P = ctypes.c_void_p * n
     T = hip.capi.Tex2D * n
     shs = T(*[hip.capi.Tex2D(t.data_ptr(), fw * 8, fw, fh) for t in d_sh])
@@ -290,6 +296,8 @@ def test_accumulate_groups_of_three_and_four(orc, hip, n, field, s, pat, fresh):
                                   P(*[t.data_ptr() for t in d_mask]), hip.capi.Tex2D(d_kp.data_ptr(), fw * 16, fw, fh), shs,
                                   hip.capi.f3(white.v), hip.capi.f3(black.v), W, H, s, pitch_of(oi), pitch_of(frames[0][1]), fresh, None)
     torch.cuda.synchronize()
+    for i, c in enumerate(checks):
+        c(f"mfsr_accumulateSuperResFullN, buffer {i}", unchanged=i < len(checks) - 2)
     hi, hw_ = d_i.cpu().numpy(), d_w.cpu().numpy()
     np.testing.assert_allclose(hw_, ow, rtol=3e-5, atol=3e-5)
     np.testing.assert_allclose(hi, oi, rtol=3e-5, atol=3e-5)
@@ -298,13 +306,19 @@ def test_accumulate_groups_of_three_and_four(orc, hip, n, field, s, pat, fresh):
 
 def _accumulate_group_hip(hip, frames, kp, fw, fh, W, H, s, white, black, acc_i, acc_w, fresh):
     import torch
-    dev = hip.dev
     n = len(frames)
-    d_raw = [torch.from_numpy(f[0].view(np.int16)).to(dev) for f in frames]
-    d_mask = [torch.from_numpy(f[1]).to(dev) for f in frames]
-    d_sh = [torch.from_numpy(f[2]).to(dev) for f in frames]
-    d_kp = torch.from_numpy(kp).to(dev)
-    d_i, d_w = torch.from_numpy(acc_i).to(dev), torch.from_numpy(acc_w).to(dev)
+    checks = []
+
+    def gup(a):
+        t, c = guarded_upload(a, hip.dev)
+        checks.append(c)
+        return t
+
+    d_raw = [gup(f[0]) for f in frames]
+    d_mask = [gup(f[1]) for f in frames]
+    d_sh = [gup(f[2]) for f in frames]
+    d_kp = gup(kp)
+    d_i, d_w = gup(acc_i), gup(acc_w)
     P = ctypes.c_void_p * n
     T = hip.capi.Tex2D * n
     shs = T(*[hip.capi.Tex2D(t.data_ptr(), fw * 8, fw, fh) for t in d_sh])
@@ -312,6 +326,8 @@ def _accumulate_group_hip(hip, frames, kp, fw, fh, W, H, s, white, black, acc_i,
                                   P(*[t.data_ptr() for t in d_mask]), hip.capi.Tex2D(d_kp.data_ptr(), fw * 16, fw, fh), shs,
                                   hip.capi.f3(white.v), hip.capi.f3(black.v), W, H, s, pitch_of(acc_i), pitch_of(frames[0][1]), fresh, None)
     torch.cuda.synchronize()
+    for i, c in enumerate(checks):
+        c(f"mfsr_accumulateSuperResFullN, buffer {i}", unchanged=i < len(checks) - 2)
     return d_i.cpu().numpy(), d_w.cpu().numpy()
 
 
@@ -851,10 +867,17 @@ def test_minimizeShifts_driver(orc, hip):
         if (status < 0).all():
             break
     dev = "cuda:0"
-    tA, tms = torch.from_numpy(A0).to(dev), torch.from_numpy(meas).to(dev)
-    tone, topt = torch.zeros_like(torch.from_numpy(one)).to(dev), torch.zeros((tiles, 2, m), device=dev)
-    tinfo = torch.zeros(tiles, dtype=torch.int32, device=dev)
-    tstat = torch.zeros(tiles, dtype=torch.int32, device=dev)
+    checks = []
+
+    def gup(a):
+        t, c = guarded_upload(a, dev)
+        checks.append(c)
+        return t
+
+    tA, tms = gup(A0), gup(meas)
+    tone, topt = gup(np.zeros_like(one)), gup(np.zeros((tiles, 2, m), np.float32))
+    tinfo = gup(np.zeros(tiles, np.int32))
+    tstat = gup(np.zeros(tiles, np.int32))
     import ctypes
     nr = ctypes.c_int(0)
     hip.L.minimizeShifts(tA.data_ptr(), tms.data_ptr(), tone.data_ptr(), topt.data_ptr(), tstat.data_ptr(),
@@ -863,9 +886,9 @@ def test_minimizeShifts_driver(orc, hip):
     assert_bitexact(one, tone.cpu().numpy(), "minimizeShifts oneToOne")
     assert (tstat.cpu().numpy() == -1).all()
     # the same loop inside one launch, no host round trips (what the burst pipeline's joint mode uses)
-    fA, fms = torch.from_numpy(A0).to(dev), torch.from_numpy(meas).to(dev)
-    fone, fopt = torch.zeros_like(tone), torch.zeros_like(topt)
-    finfo, fstat = torch.full_like(tinfo, 5), torch.full_like(tstat, 5)
+    fA, fms = gup(A0), gup(meas)
+    fone, fopt = gup(np.zeros_like(one)), gup(np.zeros((tiles, 2, m), np.float32))
+    finfo, fstat = gup(np.full(tiles, 5, np.int32)), gup(np.full(tiles, 5, np.int32))
     hip.L.minimizeShiftsFused(fA.data_ptr(), fms.data_ptr(), fone.data_ptr(), fopt.data_ptr(), fstat.data_ptr(), finfo.data_ptr(),
                               tiles, n_img, m, None)
     torch.cuda.synchronize()
@@ -874,6 +897,8 @@ def test_minimizeShifts_driver(orc, hip):
     assert_bitexact(A, fA.cpu().numpy(), "minimizeShiftsFused shiftMatrix")
     assert_bitexact(ms, fms.cpu().numpy(), "minimizeShiftsFused measuredShifts")
     assert (fstat.cpu().numpy() == -1).all() and (finfo.cpu().numpy() == info).all()
+    for i, c in enumerate(checks):
+        c(f"mfsr_minimizeShifts / mfsr_minimizeShiftsFused, buffer {i}")
 
 
 def test_shift_glue_kernels(orc, hip):
@@ -913,20 +938,30 @@ def test_concatenate_separate_setPointers(hip):
     import torch
     dev = "cuda:0"
     m, tcx, tcy = 3, 5, 4
-    imgs = [torch.rand(tcy, tcx + i, 2, device=dev) for i in range(m)]
-    ptrs = torch.tensor([t.data_ptr() for t in imgs], dtype=torch.int64, device=dev)
-    pitches = torch.tensor([t.stride(0) * 4 for t in imgs], dtype=torch.int32, device=dev)
-    out = torch.zeros(tcy * tcx, m, 2, device=dev)
+    checks = []
+
+    def gup(a, readonly=False):
+        t, c = guarded_upload(a, dev)
+        checks.append((c, readonly))
+        return t
+
+    imgs = [gup(rng(47 + i).random((tcy, tcx + i, 2), dtype=np.float32), True) for i in range(m)]
+    ptrs = gup(np.array([t.data_ptr() for t in imgs], np.int64), True)
+    pitches = gup(np.array([t.stride(0) * 4 for t in imgs], np.int32), True)
+    out = gup(np.zeros((tcy * tcx, m, 2), np.float32))
     hip.L.concatenateShifts(ptrs.data_ptr(), pitches.data_ptr(), out.data_ptr(), m, tcx, tcy, None)
     torch.cuda.synchronize()
     for k in range(m):
         assert torch.equal(out[:, k].reshape(tcy, tcx, 2), imgs[k][:, :tcx])
-    back = [torch.zeros_like(t) for t in imgs]
-    bptrs = torch.tensor([t.data_ptr() for t in back], dtype=torch.int64, device=dev)
+    back = [gup(np.zeros(tuple(t.shape), np.float32)) for t in imgs]
+    bptrs = gup(np.array([t.data_ptr() for t in back], np.int64), True)
     hip.L.separateShifts(out.data_ptr(), bptrs.data_ptr(), pitches.data_ptr(), m, tcx, tcy, None)
     torch.cuda.synchronize()
     for k in range(m):
         assert torch.equal(back[k][:, :tcx], imgs[k][:, :tcx])
+        assert (back[k][:, tcx:] == 0).all()          # the columns past tileCountX of a wider image are not written
+    for i, (c, ro) in enumerate(checks):
+        c(f"mfsr_concatenateShifts / mfsr_separateShifts, buffer {i}", unchanged=ro)
     # setPointers: per-tile base addresses
     tiles, n_img, mm = 9, 4, 5
     n1 = n_img - 1

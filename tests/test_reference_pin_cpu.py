@@ -21,6 +21,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests.guards import Guard
 from tests.kernels import F2, F3, RefBackedOracle, Tex, load_ref_or_skip, pitch_of
 from tests.test_parity_kernels import (PATTERNS, RGGB, _accum_inputs, _design, _kernel_field, _paraboloid, _smooth_image, _tiles,
                                        assert_bitexact, rng)
@@ -31,34 +32,11 @@ BLOCKS_2D = [(16, 16, 1), (32, 8, 1)]
 BLOCKS_1D = [(64, 1, 1), (7, 1, 1)]
 BLOCKS_TILE = [(8, 8, 2), (16, 4, 1)]
 TS_PAIRS = [(16, 3), (32, 4), (32, 8)]
-PAD = 256
 
 
 @pytest.fixture(scope="module")
 def ref():
     return load_ref_or_skip()
-
-
-class Guard:
-    """Buffers that sit between two canary bands."""
-
-    def __init__(self):
-        self.bufs = []
-
-    def new(self, init):
-        init = np.ascontiguousarray(init)
-        big = np.full(init.nbytes + 2 * PAD, 0xA5, np.uint8)
-        v = big[PAD:PAD + init.nbytes].view(init.dtype).reshape(init.shape)
-        v[...] = init
-        self.bufs.append(big)
-        return v
-
-    def zeros(self, shape, dtype=np.float32):
-        return self.new(np.zeros(shape, dtype))
-
-    def check(self, what):
-        for big in self.bufs:
-            assert (big[:PAD] == 0xA5).all() and (big[-PAD:] == 0xA5).all(), f"{what}: write outside the buffer"
 
 
 def pin(orc, ref, fname, make, blocks=(None,), keep=None, **kw):
