@@ -1014,6 +1014,43 @@ int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2d* mask, mf
  * Valid while framesBack < 2 * MFSR_MAX_FUSE_GROUP (the ring of per-frame slots) and the burst has aligned that many;
  * MFSR_E_INVALID for a frame that is still waiting for its group (see above). */
 int mfsr_burst_debug_frame_views(mfsr_burst* b, int framesBack, mfsr_tex2d* flow, mfsr_tex2d* mask);
+/* Which of the driver's branches a burst took, for tests: plain host-side counters the burst driver increments where it
+ * chooses a kernel (csrc/pipeline.cpp), zeroed by mfsr_burst_create and mfsr_burst_begin.  They count LAUNCHES unless noted
+ * (a batched launch over several frames counts once), add no device work and read no environment variable.  A frame-batched
+ * group is counted when it is aligned (group complete, flush or finish), so read them after mfsr_burst_flush / finish. */
+typedef enum {
+    MFSR_PATH_PREPARE_FUSED = 0,   /* A1 + tracking pyramid: mfsr_prepareFrameFused (reference and moved frames) */
+    MFSR_PATH_PREPARE_CHAIN,       /* ... the kernel chain (monochrome, more than 17 prefilter taps, cfg.fused = 0) */
+    MFSR_PATH_PREPARE_BATCH,       /* ... mfsr_prepareFrameFusedBatch, one launch per aligned group */
+    MFSR_PATH_TRACK_FUSED_UP,      /* tile tracker, one per pyramid level: mfsr_trackTilesFusedUp (levels above the coarsest) */
+    MFSR_PATH_TRACK_FUSED_BASE,    /* ... mfsr_trackTilesFusedBase (the coarsest level) */
+    MFSR_PATH_TRACK_FUSED_BATCH,   /* ... mfsr_trackTilesFusedBatch, one launch per level and aligned group */
+    MFSR_PATH_TRACK_CHAIN,         /* ... the reference's kernel chain (cfg.fused = 0) */
+    MFSR_PATH_TRACK_FAST_PAIR,     /* tracker launches (any of the four above) whose (tileSize, maxShift) is a pair of the
+                                      compile-time kernel, mfsr_trackTilesFastSupported */
+    MFSR_PATH_TRACK_GENERIC_PAIR,  /* ... and those whose pair is not: the fused forms then run the generic LDS tracker */
+    MFSR_PATH_FLOW_WARPED,         /* flow field: mfsr_CreateFlowFieldWarped (flow + first warp) */
+    MFSR_PATH_FLOW_WARPED_BATCH,   /* ... mfsr_CreateFlowFieldWarpedBatch, one launch per aligned group */
+    MFSR_PATH_FLOW_BASE,           /* ... mfsr_CreateFlowFieldFromTilesBase (cfg.preAlign off the warped path) */
+    MFSR_PATH_FLOW_PLAIN,          /* ... mfsr_CreateFlowFieldFromTiles */
+    MFSR_PATH_LK_SWEEP_BATCH,      /* Lucas-Kanade iteration: mfsr_lucasKanadeSweepBatch over an aligned group */
+    MFSR_PATH_LK_SWEEP_SINGLE,     /* ... mfsr_lucasKanadeSweepBatch of one frame */
+    MFSR_PATH_LK_ITERATION_WARPED, /* ... mfsr_lucasKanadeIterationWarped (half windows the sweep refuses) */
+    MFSR_PATH_LK_ITERATION_FUSED,  /* ... mfsr_lucasKanadeIterationFused (off the warped path) */
+    MFSR_PATH_LK_CHAIN,            /* ... warp + derivatives + mfsr_lucasKanadeOptim (cfg.fused = 0) */
+    MFSR_PATH_SCALE_FLOW,          /* separate mfsr_scaleFlow passes */
+    MFSR_PATH_FRAMES_DEFERRED,     /* FRAMES (the reference included) registered for the frame-batched alignment */
+    MFSR_PATH_FRAMES_IMMEDIATE,    /* FRAMES aligned by the call that added them */
+    MFSR_PATH_ALIGN_BATCHES,       /* groups aligned as one batch */
+    MFSR_PATH_STAGE_BATCHES,       /* ... of them, groups whose per-frame stages ran as batched launches too */
+    MFSR_PATH_ROBUST_FUSED,        /* robustness mask: mfsr_robustnessMaskFused */
+    MFSR_PATH_ROBUST_BATCH,        /* ... mfsr_robustnessMaskFusedBatch, one launch per aligned group */
+    MFSR_PATH_ROBUST_CHAIN,        /* ... mfsr_zeroRing_f32x4 + mfsr_ComputeRobustnessMask (cfg.fused = 0) */
+    MFSR_PATH_COUNT
+} mfsr_path;
+/* copies min(capacity, MFSR_PATH_COUNT) counters into counts[] (indexed by mfsr_path) and stores MFSR_PATH_COUNT in *count;
+ * host memory only, no device call, no synchronisation */
+int mfsr_burst_debug_paths(const mfsr_burst* b, int32_t* counts, int capacity, int* count);
 /* global pre-alignment of the last add_frame (cfg.preAlign), copied to HOST memory; aligns a frame that is still waiting
  * for its group first, then synchronises the stream */
 int mfsr_burst_prealign_result(mfsr_burst* b, mfsr_prealign* hostOut, mfsr_stream_t stream);

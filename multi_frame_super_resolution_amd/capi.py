@@ -155,6 +155,20 @@ def parse_header(path: str = HEADER_PATH) -> Dict[str, Tuple[str, List[Tuple[str
     return protos
 
 
+def path_names(path: str = HEADER_PATH) -> List[str]:
+    """Names of the driver's path counters (``mfsr_burst_debug_paths``), in the order of the header's ``mfsr_path`` enum and
+    without its ``MFSR_PATH_`` prefix, lower case: ``prepare_fused``, ``track_fused_up``, ..."""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    m = re.search(r"typedef\s+enum\s*\{([^{}]*)\}\s*mfsr_path\s*;", text)
+    if not m:
+        raise ValueError("mfsr.h: enum mfsr_path not found")
+    names = [re.sub(r"\s*=.*", "", e).strip() for e in m.group(1).split(",")]
+    names = [n for n in names if n]
+    if names[-1] != "MFSR_PATH_COUNT" or any(not n.startswith("MFSR_PATH_") for n in names):
+        raise ValueError("mfsr.h: unexpected enumerators in mfsr_path")
+    return [n[len("MFSR_PATH_"):].lower() for n in names[:-1]]
+
+
 def _ctype_of(typ: str):
     if "*" in typ:
         return ctypes.c_void_p

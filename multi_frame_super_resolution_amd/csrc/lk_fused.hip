@@ -49,6 +49,16 @@ __device__ __forceinline__ int lk_mirror_index(int i, int n)
     return i >= n ? 2 * n - 1 - i : i;
 }
 
+// the same for any i: whatever a single reflection leaves outside the image is clamped to the edge.  k_lkIterationFused stages a
+// tile + (h+2) halo, but an updated pixel (h <= x < n - h) reads positions -2 .. n+1 only (window h + stencil 2), which one
+// reflection serves for n >= 2; positions further out feed pixels that are outside the image or in the h-ring that is copied
+// through, so their value is irrelevant and only has to be read inside the image -- images narrower than a tile + halo
+// (the tracking image of the smallest accepted frame is 32 x 32) run the same kernel, larger ones get the same bits
+__device__ __forceinline__ int lk_mirror_index_clamped(int i, int n)
+{
+    return clampi(lk_mirror_index(i, n), 0, n - 1);
+}
+
 // base[y][x] for images of less than 4 GB: the byte offset y * pitch + 4 x in 32 bits, added to the (wave-uniform) base
 // pointer by the load's own address mode -- instead of a 64-bit multiply-add per row pointer and a 64-bit add per element
 // (8 to 9 VALU instructions per row step of the sweep).  The launcher checks pitch * height < 2^32.
@@ -123,8 +133,8 @@ __global__ void __launch_bounds__(LK_TX * LK_TY)
     // are unrolled so that the loads of all rounds are in flight together.
     auto warp_one = [&](int i, bool active) {
         const int ly = i / BW, lx = i - ly * BW;
-        const int gx = lk_mirror_index(x0 + lx - h - 2, width);
-        const int gy = lk_mirror_index(y0 + ly - h - 2, height);
+        const int gx = lk_mirror_index_clamped(x0 + lx - h - 2, width);
+        const int gy = lk_mirror_index_clamped(y0 + ly - h - 2, height);
         if (PRE) {
             const float sv = row_ptr(sumIn, pitchSD, gy)[gx], dv = row_ptr(diffIn, pitchSD, gy)[gx];
             if (active) {
@@ -314,7 +324,7 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
     const int AWp = hasWide ? ((AW + 3) & ~3) : AW;  // as in the kernel: padded when h is a template parameter
     const size_t lds = sizeof(float) * ((size_t)2 * BW * BH + (size_t)5 * AWp * AH + (size_t)5 * TX * AH);
     if (lds > 160 * 1024) return MFSR_E_UNSUPPORTED;
-    MFSR_REQUIRE(width >= TX + 2 * h + 4 && height >= LK_TY + 2 * h + 4);  // reflection range of the halo
+    MFSR_REQUIRE(width >= 4 && height >= 4);  // (the +-2 stencil reflects once; the halo beyond it is clamped: lk_mirror_index_clamped)
     dim3 block(TX, LK_TY), grid(mfsr_cdiv(width, TX), mfsr_cdiv(height, LK_TY));
 #define LK_LAUNCH(HT, TXV)                                                                                             \
     do {                                                                                                               \

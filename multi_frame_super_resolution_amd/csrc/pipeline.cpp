@@ -136,10 +136,10 @@ int validate(const mfsr_config* c)
         MFSR_REQUIRE(c->tileSize[l] >= 4 && c->tileSize[l] <= 128 && c->maxShift[l] >= 1 && c->maxShift[l] <= 15);
         MFSR_REQUIRE(c->tileSize[l] > 2 * c->maxShift[l]);
         if (c->fused) {
-            // LDS need of one tile in mfsr_trackTilesFused (template + patch + row sums + distance image): fail at
-            // create, not at the first add_frame (tileSize >~ 90); cfg.fused = 0 serves larger tiles
+            // LDS need of one tile in mfsr_trackTilesFused (template + patch + row sums + distance image) against the CU's
+            // 160 KB: fail at create, not at the first add_frame (tileSize >~ 110); cfg.fused = 0 serves larger tiles
             const long long T = c->tileSize[l], S = c->maxShift[l], Lt = T + 2 * S, R = 2 * S + 1;
-            if (4 * (T * T + Lt * (Lt + 1) + 1 + Lt * R + R * R + 4) > 64 * 1024) {
+            if (4 * (T * T + Lt * (Lt + 1) + 1 + Lt * R + R * R + 4) > 160 * 1024) {
                 fprintf(stderr, "mfsr: tileSize %d / maxShift %d exceeds the fused tile tracker's LDS budget (use cfg.fused = 0)\n",
                         (int)T, (int)S);
                 return MFSR_E_UNSUPPORTED;
@@ -388,6 +388,8 @@ struct mfsr_burst {
     bool timing;
     int nEvents;
     hipEvent_t evStart[kMaxTimedLaunches], evStop[kMaxTimedLaunches];
+    // which branches the driver took since mfsr_burst_begin (mfsr_burst_debug_paths): host-side counters only
+    int32_t paths[MFSR_PATH_COUNT];
 };
 
 #define TRY(expr)                  \
@@ -604,6 +606,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     }
     b->haveRef = false;
     b->refStale = false;
+    memset(b->paths, 0, sizeof(b->paths));
     *out = b;
     return MFSR_OK;
 }
@@ -738,11 +741,13 @@ static int prepare_frame(mfsr_burst* b, const uint16_t* raw, Img& half, Img* pyr
         TRY(mfsr_prepareFrameFused(raw, (mfsr_float3*)half.ptr, half.pitch, maxValEff, L.hw, L.hh, (float*)pyr[0].ptr,
                                    pyr[0].pitch, nlev > 1 ? (float*)pyr[1].ptr : nullptr, nlev > 1 ? pyr[1].pitch : 0,
                                    b->taps, b->ntaps, stream));
+        b->paths[MFSR_PATH_PREPARE_FUSED]++;
         for (int i = 2; i < nlev; i++)
             TRY(mfsr_downsample2x((const float*)pyr[i - 1].ptr, pyr[i - 1].pitch, (float*)pyr[i].ptr, pyr[i].pitch, pyr[i].w,
                                   pyr[i].h, stream));
         return MFSR_OK;
     }
+    b->paths[MFSR_PATH_PREPARE_CHAIN]++;
     TRY(mfsr_deBayersSubSample3(raw, (mfsr_float3*)half.ptr, maxValEff, L.hw, L.hh, half.pitch, stream));
     if (c.mono)
         TRY(mfsr_u16ToFloat(raw, (float*)L.tmpA.ptr, L.tmpA.pitch, L.W, L.H, 1.0f / c.maxVal, stream));
@@ -941,6 +946,7 @@ static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream
         const int T = c.tileSize[l], S = c.maxShift[l];
         const int tiles = L.tcx[l] * L.tcy[l];
         const mfsr_float2* pre = nullptr;
+        b->paths[mfsr_trackTilesFastSupported(T, S) ? MFSR_PATH_TRACK_FAST_PAIR : MFSR_PATH_TRACK_GENERIC_PAIR]++;
         if (c.fused && l > 0) {
             // B8 folded into the tracker: the pre-shifts come straight from the previous level's shifts
             TRY(mfsr_trackTilesFusedUp((const float*)ref.ptr, (const float*)mov.ptr, (const mfsr_float2*)L.shifts[l - 1].ptr,
@@ -948,6 +954,7 @@ static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream
                                        c.tileSize[l - 1], (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, S,
                                        T, L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l], c.preAlign ? L.preResult : nullptr,
                                        1.0f / (float)c.levelFactor[l], stream));
+            b->paths[MFSR_PATH_TRACK_FUSED_UP]++;
             continue;
         }
         if (l > 0) {
@@ -961,7 +968,9 @@ static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream
                                          (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, S, T,
                                          L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l],
                                          c.preAlign ? L.preResult : nullptr, 1.0f / (float)c.levelFactor[l], stream));
+            b->paths[MFSR_PATH_TRACK_FUSED_BASE]++;
         } else {
+            b->paths[MFSR_PATH_TRACK_CHAIN]++;
             if (!pre) {
                 MFSR_HIP_TRY(hipMemsetAsync(L.pre[l].ptr, 0, (size_t)L.pre[l].pitch * L.pre[l].h, mfsr_s(stream)));
                 pre = (const mfsr_float2*)L.pre[l].ptr;
@@ -1185,9 +1194,11 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
                                            c.preAlign ? L.preResult : nullptr, (const float*)L.refPyr[0].ptr,
                                            (const float*)L.movPyr[0].ptr, L.refPyr[0].pitch, (float*)L.lkSum[0].ptr,
                                            (float*)L.lkDiff[0].ptr, L.lkSum[0].pitch, stream));
+            b->paths[MFSR_PATH_FLOW_WARPED]++;
         } else if (c.preAlign && c.fused) {
             TRY(mfsr_CreateFlowFieldFromTilesBase((mfsr_float2*)flow->ptr, as_tex(tileShifts), L.tw, L.th, flow->pitch,
                                                   L.preResult, stream));
+            b->paths[MFSR_PATH_FLOW_BASE]++;
         } else {
             mfsr_float2 base = zero2;
             float rot = 0.0f;
@@ -1198,6 +1209,7 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
             }
             TRY(mfsr_CreateFlowFieldFromTiles((mfsr_float2*)flow->ptr, as_tex(tileShifts), c.tileSize[last], L.tcx[last],
                                               L.tcy[last], L.tw, L.th, flow->pitch, base, rot, stream));
+            b->paths[MFSR_PATH_FLOW_PLAIN]++;
         }
       }
       if (phases & ALIGN_LK) {
@@ -1221,6 +1233,7 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
                                                            lastIt ? (float)L.flowScale : 1.0f, stream);
                 if (rcs != MFSR_E_UNSUPPORTED) {
                     if (rcs) return rcs;
+                    b->paths[MFSR_PATH_LK_SWEEP_SINGLE]++;
                     Img* t = flow;
                     flow = other;
                     other = t;
@@ -1232,6 +1245,7 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
                                                     lastIt ? nullptr : (float*)L.lkSum[out].ptr,
                                                     lastIt ? nullptr : (float*)L.lkDiff[out].ptr, L.lkSum[0].pitch, L.tw, L.th,
                                                     c.lkHalfWindow, c.lkMinDet, lastIt ? (float)L.flowScale : 1.0f, stream));
+                b->paths[MFSR_PATH_LK_ITERATION_WARPED]++;
                 Img* t = flow;
                 flow = other;
                 other = t;
@@ -1240,6 +1254,7 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
                                                    (const float*)L.refPyr[0].ptr, (const float*)L.movPyr[0].ptr,
                                                    L.refPyr[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
                                                    it == c.lkIterations - 1 ? (float)L.flowScale : 1.0f, stream));
+                b->paths[MFSR_PATH_LK_ITERATION_FUSED]++;
                 Img* t = flow;
                 flow = other;
                 other = t;
@@ -1254,10 +1269,13 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
                 TRY(mfsr_lucasKanadeOptim((mfsr_float2*)flow->ptr, (const float*)L.Ix.ptr, (const float*)L.Iy.ptr,
                                           (const float*)L.It.ptr, flow->pitch, L.Ix.pitch, L.tw, L.th, c.lkHalfWindow,
                                           c.lkMinDet, stream));
+                b->paths[MFSR_PATH_LK_CHAIN]++;
             }
         }
-        if (L.flowScale != 1 && !(c.fused && c.lkIterations > 0))  // the fused LK scales on its last iteration
+        if (L.flowScale != 1 && !(c.fused && c.lkIterations > 0)) {  // the fused LK scales on its last iteration
             TRY(mfsr_scaleFlow((mfsr_float2*)flow->ptr, flow->pitch, L.tw, L.th, (float)L.flowScale, stream));
+            b->paths[MFSR_PATH_SCALE_FLOW]++;
+        }
       } else if (c.fused && (c.lkIterations & 1)) {
         // the iterations ran elsewhere (align_group): an odd number of them leaves the flow in the slot's other buffer
         Img* t = flow;
@@ -1272,7 +1290,9 @@ static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int 
             TRY(mfsr_robustnessMaskFused((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
                                          (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch, c.alpha,
                                          c.beta, c.thresholdM, stream));
+            b->paths[MFSR_PATH_ROBUST_FUSED]++;
         } else {
+            b->paths[MFSR_PATH_ROBUST_CHAIN]++;
             TRY(mfsr_zeroRing_f32x4((mfsr_float4*)fOut->ptr, fOut->pitch, L.hw, L.hh, stream));
             TRY(mfsr_ComputeRobustnessMask((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
                                            (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch,
@@ -1329,6 +1349,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         if (b->pend.deferred[i]) idx[n++] = i;
     if (n == 0) return MFSR_OK;
     TRY(wait_uploads(b, stream));
+    b->paths[MFSR_PATH_ALIGN_BATCHES]++;
     // the moved-frame intermediates of batch position q (0: the Layout's own members, q > 0: align set q - 1)
     auto movHalf = [&](int q) -> Img& { return q == 0 ? L.movHalf : L.sets[q - 1].movHalf; };
     auto movPyr = [&](int q) -> Img* { return q == 0 ? L.movPyr : L.sets[q - 1].movPyr; };
@@ -1349,6 +1370,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     for (int q = 0; q < n; q++)
         if (!b->pend.isRef[idx[q]]) mq[m++] = q;
     if (stageBatch) {
+        b->paths[MFSR_PATH_STAGE_BATCHES]++;
         for (int q = 0; q < n; q++) {
             const int i = idx[q], slot = b->pend.slot[i];
             if (b->pend.isRef[i]) {  // identity flow, certainty 1 (and the slot wait) through the frame path
@@ -1373,6 +1395,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             }
             TRY(mfsr_prepareFrameFusedBatch(m, pf, L.movHalf.pitch, c.maxVal, L.hw, L.hh, L.movPyr[0].pitch, nlev > 1 ? L.movPyr[1].pitch : 0,
                                             b->taps, b->ntaps, stream));
+            b->paths[MFSR_PATH_PREPARE_BATCH]++;
             for (int k = 0; k < m; k++) {
                 Img* pyr = movPyr(mq[k]);
                 for (int i = 2; i < nlev; i++)
@@ -1395,6 +1418,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
                                               l > 0 ? c.tileSize[l - 1] : 0, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, c.maxShift[l],
                                               c.tileSize[l], L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l],
                                               1.0f / (float)c.levelFactor[l], stream));
+                b->paths[MFSR_PATH_TRACK_FUSED_BATCH]++;
+                b->paths[MFSR_PATH_TRACK_FAST_PAIR]++;  // (stageBatch: every level's pair is one of the compile-time tracker's)
             }
             // D1 + the first warp
             const int last = c.levels - 1;
@@ -1410,6 +1435,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             }
             TRY(mfsr_CreateFlowFieldWarpedBatch(m, ff, L.shifts[last].pitch, L.shifts[last].w, L.shifts[last].h, L.tw, L.th,
                                                 L.flowBuf[0].pitch, (const float*)L.refPyr[0].ptr, L.refPyr[0].pitch, L.lkSum[0].pitch, stream));
+            b->paths[MFSR_PATH_FLOW_WARPED_BATCH]++;
         }
     } else {
     // per-frame stages up to the flow field + first warp; frame q > 0 of the batch works in align set q - 1
@@ -1453,6 +1479,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             batched = false;  // (cannot happen after can_defer_alignment; kept as a safe fallback)
         else if (rc)
             return rc;
+        else
+            b->paths[MFSR_PATH_LK_SWEEP_BATCH]++;
     }
     // robustness masks (and, without the batch kernel, the iterations frame by frame)
     bool maskBatch = stageBatch && batched && m > 0;
@@ -1470,6 +1498,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             maskBatch = false;  // (the straight robustness kernel was selected: frame by frame below)
         else if (rc)
             return rc;
+        else
+            b->paths[MFSR_PATH_ROBUST_BATCH]++;
         if (maskBatch && c.maskErode > 0) {  // one erosion launch for the whole group
             const mfsr_float4* ein[MFSR_MAX_FUSE_GROUP];
             mfsr_float4* eout[MFSR_MAX_FUSE_GROUP];
@@ -1518,6 +1548,7 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     const int slot = b->frameCounter++ % kRing;
     Img *flow = nullptr, *mask = nullptr;
     const bool defer = can_defer_alignment(b);
+    b->paths[defer ? MFSR_PATH_FRAMES_DEFERRED : MFSR_PATH_FRAMES_IMMEDIATE]++;
     if (!defer) {
         TRY(align_deferred(b, stream));  // keep the alignment in frame order on the stream
         TRY(align_frame(b, raw, isReference, slot, &flow, &mask, stream));
@@ -1743,6 +1774,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
 {
     MFSR_REQUIRE(b && imgOut && totalWeights);
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
+    memset(b->paths, 0, sizeof(b->paths));
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
     b->fresh.totalWeights = totalWeights;
@@ -2444,6 +2476,15 @@ extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2
     if (mask) *mask = as_tex(*b->maskCur);
     if (kernelParam) *kernelParam = as_tex(b->L.kparam4);
     if (tracking) *tracking = as_tex(b->L.refPyr[0]);
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_debug_paths(const mfsr_burst* b, int32_t* counts, int capacity, int* count)
+{
+    MFSR_REQUIRE(b && counts && count && capacity >= 0);
+    const int n = capacity < (int)MFSR_PATH_COUNT ? capacity : (int)MFSR_PATH_COUNT;
+    for (int i = 0; i < n; i++) counts[i] = b->paths[i];
+    *count = (int)MFSR_PATH_COUNT;
     return MFSR_OK;
 }
 

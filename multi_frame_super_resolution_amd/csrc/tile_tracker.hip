@@ -1189,19 +1189,29 @@ static int track_tiles_fused_impl(const float* refImg, const float* movedImg, co
     int tilesPerWg = TRK_THREADS / (R * G) > 0 ? TRK_THREADS / (R * G) : 1;  // large search ranges: several rounds per tile
     while (tilesPerWg > 1 && sizeof(float) * (size_t)slotFloats * tilesPerWg > 56 * 1024) tilesPerWg--;
     const size_t lds = sizeof(float) * (size_t)slotFloats * tilesPerWg;
-    if (lds > 64 * 1024) return MFSR_E_UNSUPPORTED;
+    if (lds > 160 * 1024) return MFSR_E_UNSUPPORTED;
     const int tiles = tileCountX * tileCountY;
+    // (one tile of more than 64 KB, e.g. 64 + 2 * 15: the workgroup may take up to the CU's 160 KB once the kernel allows it)
 #define TRK_LAUNCH(N)                                                                                                  \
+    if (lds > 64 * 1024) {                                                                                             \
+        static bool attr_set = false;                                                                                  \
+        if (!attr_set) {                                                                                               \
+            MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_trackTilesFused<N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                             160 * 1024));                                                             \
+            attr_set = true;                                                                                           \
+        }                                                                                                              \
+    }                                                                                                                  \
     hipLaunchKernelGGL(k_trackTilesFused<N>, dim3(mfsr_cdiv(tiles, tilesPerWg)), dim3(TRK_THREADS), lds, mfsr_s(stream),  \
                        refImg, movedImg, (const float2*)preShift, preShiftPitch, (float2*)coordinates, coordinatesPitch, \
                        imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX, tileCountY, threshold,           \
                        refSquaredSums, tilesPerWg, base, baseInvScale, (const float2*)coarse, coarsePitch, up, upOldTile)
-    if (nsx == 1)
+    if (nsx == 1) {
         TRK_LAUNCH(1);
-    else if (nsx == 2)
+    } else if (nsx == 2) {
         TRK_LAUNCH(2);
-    else
+    } else {
         TRK_LAUNCH(3);
+    }
 #undef TRK_LAUNCH
     return mfsr_launch_status("trackTilesFused");
 }

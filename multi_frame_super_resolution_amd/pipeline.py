@@ -864,6 +864,17 @@ class BurstPipeline:
         self.L.burst_debug_frame_views(self._h, int(frames_back), ctypes.byref(f), ctypes.byref(m))
         return f, m
 
+    def debug_paths(self) -> dict:
+        """{name: count} of the driver branches taken since ``begin_burst`` (mfsr_burst_debug_paths; names:
+        ``capi.path_names()``).  Host-side counters of launches: read them after ``flush`` / ``finish``, when every frame of
+        the burst has been aligned."""
+        names = capi.path_names()
+        counts, n = (ctypes.c_int32 * len(names))(), ctypes.c_int(0)
+        self.L.burst_debug_paths(self._h, counts, len(names), ctypes.byref(n))
+        if n.value != len(names):
+            raise RuntimeError(f"libmfsr_hip.so counts {n.value} paths, include/mfsr.h names {len(names)}: rebuild the library")
+        return {k: int(v) for k, v in zip(names, counts)}
+
     def _check_raw(self, raw: torch.Tensor):
         if raw.device != self.device or raw.dtype not in (torch.int16, torch.uint16) or not raw.is_contiguous():
             raise ValueError("raw frame must be a contiguous 16-bit tensor on the pipeline's device")

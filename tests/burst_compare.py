@@ -41,7 +41,8 @@ def run_hip(cfg, frames, device="cuda:0", per_frame=True):
     _, _, kp_t, trk_t = pipe.debug_views()
     res = dict(out=out.cpu().numpy(), out16=out16.cpu().numpy().view(np.uint16), img_out=pipe.img_out.cpu().numpy(),
                tw=pipe.total_weights.cpu().numpy(), flows=flows, masks=masks, flow=flows[-1], mask=masks[-1],
-               kparam=view_as_tensor(kp_t, 4, dev).cpu().numpy(), tracking=view_as_tensor(trk_t, 1, dev).cpu().numpy()[..., 0])
+               kparam=view_as_tensor(kp_t, 4, dev).cpu().numpy(), tracking=view_as_tensor(trk_t, 1, dev).cpu().numpy()[..., 0],
+               paths=pipe.debug_paths())    # which branches the driver took for this burst (mfsr_burst_debug_paths)
     pipe.close()
     return res
 

@@ -403,8 +403,10 @@ def c_lkOptim(orc, hip, w, h, first):
         assert_bitexact(g[:hw], sh0[:hw], "ring rows")
 
 
-# 48- and 32-wide tiles of LK_TY = 16 rows; the halo's reflection range needs width >= 32 + 2 h + 4, height >= 16 + 2 h + 4
-LKF = [(42, 26), (47, 31), (48, 32), (49, 33), (65, 47), (97, 49), (131, 35)]
+# 48- and 32-wide tiles of LK_TY = 16 rows.  Below width 32 + 2 h + 4 or height 16 + 2 h + 4 the tile's halo reaches past one
+# reflection of the image (clamped: only the +-2 stencil about an updated pixel matters): the first three shapes, among them
+# the 32 x 32 tracking image of the smallest frame the pipeline accepts
+LKF = [(32, 32), (33, 20), (40, 17), (42, 26), (47, 31), (48, 32), (49, 33), (65, 47), (97, 49), (131, 35)]
 
 
 @case("lucasKanadeIterationFused", shp=LKF)
