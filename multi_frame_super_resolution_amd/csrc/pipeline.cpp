@@ -27,7 +27,6 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
-#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -51,6 +50,22 @@ struct Img {
     int w = 0, h = 0;
 };
 
+// what prepare_frame (+ mfsr_preAlignPyramid) makes from one raw frame; nothing of it depends on the reference
+struct FrameProducts {
+    uint16_t* raw;  // the frame itself where the owner keeps it (frame streams, joint mode); null in Layout
+    Img half;       // float3, half res
+    Img pyr[8];     // float, factor 1,2,4,.. (index = log2 factor)
+    void* prePyr;   // cfg.preAlign: search pyramid
+};
+
+// what aligning one moved frame against the reference writes besides its ring slot
+struct AlignScratch {
+    Img shifts[kMaxLevels];    // float2, tile grids
+    Img lkSum[2], lkDiff[2];   // fused LK: (warped + ref) / (warped - ref) handed from iteration to iteration
+    mfsr_prealign* preResult;  // cfg.preAlign: the frame's estimate (device memory)
+};
+
+// The workspace map.  make_layout writes it, nobody else: which frame a stage works on is an argument of the stage.
 struct Layout {
     // geometry
     int W, H, hw, hh, tw, th, hrW, hrH;
@@ -59,8 +74,11 @@ struct Layout {
     int tcx[kMaxLevels], tcy[kMaxLevels];    // tile counts per level
     int maxFactor;
     // buffers
-    Img refHalf, movHalf;                    // float3, half res
-    Img refPyr[8], movPyr[8];                // float, factor 1,2,4,.. (index = log2 factor)
+    // the reference's products; the moved frame's products and scratch of batch position q of a group (frame-batched
+    // alignment; frame-by-frame alignment works in [0]); nAlign of each are allocated
+    FrameProducts ref, mov[MFSR_MAX_FUSE_GROUP];
+    AlignScratch work[MFSR_MAX_FUSE_GROUP];
+    int nAlign;
     Img kparam4;                             // float4, tracking res
     Img tensor, tensorTmp, tensorSm;         // float3, tracking res
     Img fallback;                            // float3, W x H
@@ -68,23 +86,12 @@ struct Layout {
     Img flowBuf[2 * kRing];                  // float2, tracking res: per ring slot the two buffers of the LK ping-pong
     Img maskBuf[kRing];                      // float4, half res, one per ring slot
     Img maskRaw[MFSR_MAX_FUSE_GROUP];        // cfg.maskErode > 0 only: stage F writes here, the erosion writes the slot's mask
-    Img shifts[kMaxLevels], pre[kMaxLevels]; // float2, tile grids
+    Img pre[kMaxLevels];                     // float2, tile grids: the unfused tracker's upsampled pre-shifts
     // unfused path scratch
     Img warped, Ix, Iy, It, rawf;
-    Img lkSum[2], lkDiff[2];                 // fused LK: (warped + ref) / (warped - ref) handed from iteration to iteration
     float *refTiles, *movTiles, *cc, *boxX, *boxY, *sqsum, *dist;
     float* refSq[kMaxLevels];  // fused tracker: sum(ref^2) per tile and level, taken once per reference
-    // global pre-alignment (cfg.preAlign): search pyramids of the reference and the moved frame, workspace, result
-    void *preRefPyr, *preMovPyr, *preWork;
-    mfsr_prealign* preResult;
-    // frame-batched alignment (align_group): the moved frame's intermediates of frames 1 .. group-1 of a group (frame 0
-    // uses the members above); swapped in around the per-frame launches
-    struct AlignSet {
-        Img movHalf, movPyr[8], shifts[kMaxLevels], lkSum[2], lkDiff[2];
-        void* preMovPyr;
-        mfsr_prealign* preResult;
-    } sets[MFSR_MAX_FUSE_GROUP - 1];
-    int nSets;
+    void* preWork;             // global pre-alignment (cfg.preAlign): the search's workspace
     // host-frame bursts (cfg.uploadRing): device slots the library uploads into
     uint16_t* rawRing[kMaxUploadRing];
     uint16_t* refRaw[2];
@@ -157,9 +164,11 @@ int validate(const mfsr_config* c)
     return MFSR_OK;
 }
 
-void make_layout(const mfsr_config* c, char* base, Layout* L)
+Layout make_layout(const mfsr_config* c, char* base)
 {
-    memset((void*)L, 0, sizeof(*L));
+    Layout layout;
+    memset((void*)&layout, 0, sizeof(layout));
+    Layout* L = &layout;
     Bump b{base, 0};
     L->W = c->width;
     L->H = c->height;
@@ -173,11 +182,11 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
     L->maxFactor = c->levelFactor[0];
     const int nl = ilog2(L->maxFactor) + 1;
 
-    L->refHalf = b.image(L->hw, L->hh, 12);
-    L->movHalf = b.image(L->hw, L->hh, 12);
+    L->ref.half = b.image(L->hw, L->hh, 12);
+    L->mov[0].half = b.image(L->hw, L->hh, 12);
     for (int i = 0; i < nl; i++) {
-        L->refPyr[i] = b.image(L->tw >> i, L->th >> i, 4);
-        L->movPyr[i] = b.image(L->tw >> i, L->th >> i, 4);
+        L->ref.pyr[i] = b.image(L->tw >> i, L->th >> i, 4);
+        L->mov[0].pyr[i] = b.image(L->tw >> i, L->th >> i, 4);
     }
     L->kparam4 = b.image(L->tw, L->th, 16);
     L->tensor = b.image(L->tw, L->th, 12);
@@ -195,7 +204,7 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
         L->lh[l] = L->th / f;
         L->tcx[l] = L->lw[l] / c->tileSize[l] > 0 ? L->lw[l] / c->tileSize[l] : 1;
         L->tcy[l] = L->lh[l] / c->tileSize[l] > 0 ? L->lh[l] / c->tileSize[l] : 1;
-        L->shifts[l] = b.image(L->tcx[l], L->tcy[l], 8);
+        L->work[0].shifts[l] = b.image(L->tcx[l], L->tcy[l], 8);
         L->pre[l] = b.image(L->tcx[l], L->tcy[l], 8);
         const size_t tiles = (size_t)L->tcx[l] * L->tcy[l];
         const size_t Lt = (size_t)c->tileSize[l] + 2 * c->maxShift[l];
@@ -208,8 +217,8 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
     if (c->fused) {
         for (int l = 0; l < c->levels; l++) L->refSq[l] = (float*)b.take((size_t)L->tcx[l] * L->tcy[l] * 4);
         for (int i = 0; i < 2; i++) {
-            L->lkSum[i] = b.image(L->tw, L->th, 4);
-            L->lkDiff[i] = b.image(L->tw, L->th, 4);
+            L->work[0].lkSum[i] = b.image(L->tw, L->th, 4);
+            L->work[0].lkDiff[i] = b.image(L->tw, L->th, 4);
         }
     }
     L->Ix = b.image(L->tw, L->th, 4);  // (fused: the derivative images of the kernel-parameter chain, made on the fuse stream)
@@ -228,29 +237,26 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
     }
     if (c->preAlign) {
         const size_t pb = mfsr_preAlign_pyramid_bytes(L->tw, L->th);
-        L->preRefPyr = b.take(pb);
-        L->preMovPyr = b.take(pb);
+        L->ref.prePyr = b.take(pb);
+        L->mov[0].prePyr = b.take(pb);
         L->preWork = b.take(mfsr_preAlign_workspace_bytes(c->preAlignMaxAngle));
-        L->preResult = (mfsr_prealign*)b.take(sizeof(mfsr_prealign));
+        L->work[0].preResult = (mfsr_prealign*)b.take(sizeof(mfsr_prealign));
     }
-    L->nSets = 0;
-    if (c->fused && mfsr_burst_group_size(c) > 1) {
-        L->nSets = mfsr_burst_group_size(c) - 1;
-        for (int q = 0; q < L->nSets; q++) {
-            Layout::AlignSet& S = L->sets[q];
-            S.movHalf = b.image(L->hw, L->hh, 12);
-            for (int i = 0; i < nl; i++) S.movPyr[i] = b.image(L->tw >> i, L->th >> i, 4);
-            for (int l = 0; l < c->levels; l++) S.shifts[l] = b.image(L->tcx[l], L->tcy[l], 8);
-            for (int i = 0; i < 2; i++) {
-                S.lkSum[i] = b.image(L->tw, L->th, 4);
-                S.lkDiff[i] = b.image(L->tw, L->th, 4);
-            }
-            S.preMovPyr = nullptr;
-            S.preResult = nullptr;
-            if (c->preAlign) {
-                S.preMovPyr = b.take(mfsr_preAlign_pyramid_bytes(L->tw, L->th));
-                S.preResult = (mfsr_prealign*)b.take(sizeof(mfsr_prealign));
-            }
+    // frame-batched alignment: frames 1 .. group-1 of a group get intermediates of their own
+    L->nAlign = c->fused ? mfsr_burst_group_size(c) : 1;
+    for (int q = 1; q < L->nAlign; q++) {
+        FrameProducts& M = L->mov[q];
+        AlignScratch& S = L->work[q];
+        M.half = b.image(L->hw, L->hh, 12);
+        for (int i = 0; i < nl; i++) M.pyr[i] = b.image(L->tw >> i, L->th >> i, 4);
+        for (int l = 0; l < c->levels; l++) S.shifts[l] = b.image(L->tcx[l], L->tcy[l], 8);
+        for (int i = 0; i < 2; i++) {
+            S.lkSum[i] = b.image(L->tw, L->th, 4);
+            S.lkDiff[i] = b.image(L->tw, L->th, 4);
+        }
+        if (c->preAlign) {
+            M.prePyr = b.take(mfsr_preAlign_pyramid_bytes(L->tw, L->th));
+            S.preResult = (mfsr_prealign*)b.take(sizeof(mfsr_prealign));
         }
     }
     for (int i = 0; i < c->uploadRing; i++) L->rawRing[i] = (uint16_t*)b.take((size_t)L->W * L->H * 2);
@@ -263,20 +269,7 @@ void make_layout(const mfsr_config* c, char* base, Layout* L)
         for (int i = 0; i < c->uploadRing + 2; i++)
             L->stage[i] = (uint8_t*)b.take((size_t)mfsr_packed_row_bytes(c->rawPacking, L->W) * L->H);
     L->total = align_up(b.off, 256);
-}
-
-// exchange the moved-frame intermediates named by the Layout members with those of an align set
-void swap_set(Layout& L, Layout::AlignSet& S)
-{
-    std::swap(L.movHalf, S.movHalf);
-    for (int i = 0; i < 8; i++) std::swap(L.movPyr[i], S.movPyr[i]);
-    for (int l = 0; l < kMaxLevels; l++) std::swap(L.shifts[l], S.shifts[l]);
-    for (int i = 0; i < 2; i++) {
-        std::swap(L.lkSum[i], S.lkSum[i]);
-        std::swap(L.lkDiff[i], S.lkDiff[i]);
-    }
-    std::swap(L.preMovPyr, S.preMovPyr);
-    std::swap(L.preResult, S.preResult);
+    return layout;
 }
 
 mfsr_tex2d as_tex(const Img& im)
@@ -292,17 +285,19 @@ mfsr_tex2d as_tex(const Img& im)
 }  // namespace
 
 struct mfsr_burst {
+    mfsr_burst(const mfsr_config& c, char* workspace) : cfg(c), L(make_layout(&c, workspace)) {}
     mfsr_config cfg;
-    Layout L;
+    const Layout L;     // written by make_layout only
+    FrameProducts ref;  // the current reference's products: L.ref, or what the caller of set_reference_impl supplied
     float taps[99];
     int ntaps;
     float tensorTaps[99];
     int ntensorTaps;
-    Img* flowCur;  // flow of the last add_frame (raw-pixel units)
-    Img* maskCur;  // certainty mask of the last add_frame
+    const Img* flowCur;  // flow of the last add_frame (raw-pixel units)
+    const Img* maskCur;  // certainty mask of the last add_frame
     mfsr_prealign* preCur;  // pre-alignment estimate of the last aligned frame (cfg.preAlign; device memory)
     bool haveRef;
-    bool refStale;                      // the reference's alignment products were swapped away (process_joint): finish is
+    bool refStale;                      // `ref` names memory the burst does not own (process_joint's workspace): finish is
                                         // still valid, aligning another frame needs a new set_reference
     // frame grouping (cfg.pairFrames): aligned frames wait here until their group is complete, then the
     // group is fused in one pass over the accumulators; flush/finish fuses what is left of a group
@@ -310,8 +305,8 @@ struct mfsr_burst {
         int n;  // frames waiting (0 .. group - 1)
         int slot[MFSR_MAX_FUSE_GROUP];
         const uint16_t* raw[MFSR_MAX_FUSE_GROUP];
-        Img* flow[MFSR_MAX_FUSE_GROUP];
-        Img* mask[MFSR_MAX_FUSE_GROUP];
+        const Img* flow[MFSR_MAX_FUSE_GROUP];
+        const Img* mask[MFSR_MAX_FUSE_GROUP];
         bool deferred[MFSR_MAX_FUSE_GROUP];  // not aligned yet: align_deferred aligns the waiting frames as one batch
         int isRef[MFSR_MAX_FUSE_GROUP];
         mfsr_float3 *imgOut, *totalWeights;
@@ -337,7 +332,7 @@ struct mfsr_burst {
     hipEvent_t evRefStart, evRefDone;
     bool refOnFuse;                     // evRefDone is pending for consumers on other streams than fuseStream
     bool fusedOutstanding[kRing];       // evFused[slot] recorded and not yet waited for by the caller's stream
-    Img* slotFlow[kRing];               // which buffer of the slot's LK ping-pong pair holds the frame's final flow
+    const Img* slotFlow[kRing];         // which buffer of the slot's LK ping-pong pair holds the frame's final flow
     // host-frame bursts (cfg.uploadRing): copy stream, per-slot events, reference double buffer
     hipStream_t copyStream;
     hipStream_t downStream;                 // D2H of the finished image (mfsr_burst_finish_host), concurrent with the uploads
@@ -372,11 +367,6 @@ struct mfsr_burst {
     int upCounter, refCounter;
     const uint16_t* refHost;                // host pointer of the current reference and its device copy
     const uint16_t* refDev;
-    // mfsr_stream: the per-frame products (half-res RGB, tracking pyramid, search pyramid) of the next set_reference /
-    // add_frame are already in L.refHalf.. / L.movHalf.. (the stream keeps them per frame and swaps the descriptors in)
-    bool refPrepared, movPrepared;
-    // joint mode (stage C): tile shifts of the frame being aligned come from the minimiser instead of the tracker
-    const Img* givenShifts;
     std::vector<float> jointHost;  // host staging of the joint mode's design matrix / pointer table (must outlive the copies)
     // zoom window (mfsr_burst_set_window): the HR rectangle the fuse / finish work on, window-sized buffers; `win` is in
     // effect, `winNext` is adopted by the next set_reference (on = false: the whole frame, whole-frame buffers)
@@ -489,9 +479,7 @@ extern "C" int mfsr_config_default(mfsr_config* cfg, int width, int height, int 
 extern "C" size_t mfsr_burst_workspace_bytes(const mfsr_config* cfg)
 {
     if (validate(cfg) != MFSR_OK) return 0;
-    Layout L;
-    make_layout(cfg, nullptr, &L);
-    return L.total;
+    return make_layout(cfg, nullptr).total;
 }
 
 extern "C" size_t mfsr_burst_accumulator_bytes(const mfsr_config* cfg)
@@ -509,10 +497,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
         return MFSR_E_NODEVICE;
     }
     MFSR_REQUIRE(((uintptr_t)workspace & 255) == 0);
-    mfsr_burst* b = new (std::nothrow) mfsr_burst;
+    mfsr_burst* b = new (std::nothrow) mfsr_burst(*cfg, (char*)workspace);
     MFSR_REQUIRE(b != nullptr);
-    b->cfg = *cfg;
-    make_layout(cfg, (char*)workspace, &b->L);
     if (b->L.total > workspaceBytes) {
         fprintf(stderr, "mfsr: workspace too small: need %zu bytes, got %zu\n", b->L.total, workspaceBytes);
         delete b;
@@ -522,7 +508,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->ntensorTaps = mfsr_gaussin_filter_1D(cfg->sigmaTensor, b->tensorTaps);
     b->flowCur = &b->L.flowBuf[0];
     b->maskCur = &b->L.maskBuf[0];
-    b->preCur = b->L.preResult;
+    b->preCur = b->L.work[0].preResult;
+    b->ref = b->L.ref;
     b->pend.n = 0;
     b->group = mfsr_burst_group_size(&b->cfg);
     b->fresh.has = false;
@@ -561,8 +548,6 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
             return MFSR_E_NODEVICE;
         }
     }
-    b->refPrepared = b->movPrepared = false;
-    b->givenShifts = nullptr;
     b->copyStream = nullptr;
     b->downStream = nullptr;
     b->evFinished = b->evDown = nullptr;
@@ -729,10 +714,12 @@ static int unpack_uploaded(mfsr_burst* b, int lastSlot, mfsr_stream_t stream)
 }
 
 // A1 + tracking pyramid for one frame (shared by reference and moved frames)
-static int prepare_frame(mfsr_burst* b, const uint16_t* raw, Img& half, Img* pyr, mfsr_stream_t stream)
+static int prepare_frame(mfsr_burst* b, const uint16_t* raw, const FrameProducts& f, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
+    const Img& half = f.half;
+    const Img* pyr = f.pyr;
     TRY(mfsr_set_cfa_pattern(c.cfa));
     const float maxValEff = c.mono ? 2.0f * c.maxVal : c.maxVal;  // mono: 4 "greens" x 0.5 -> mean of the quad
     const int nlev = ilog2(L.maxFactor) + 1;
@@ -766,12 +753,14 @@ static int prepare_frame(mfsr_burst* b, const uint16_t* raw, Img& half, Img* pyr
 // (the whole grid for a single-GPU burst; a stripe for a rank of a multi-GPU burst: those two products are then made for
 // the rows the stripe reads plus the halo their stencils need -- every kernel below works on a row window of the images,
 // so the rows it makes are the bits the whole-image run makes)
-static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0, int hrRow1, mfsr_stream_t stream)
+// prepared: the frame's products, made by the caller (frame streams, joint mode) -- null: made here, into L.ref
+static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0, int hrRow1, mfsr_stream_t stream,
+                              const FrameProducts* prepared = nullptr)
 {
     MFSR_REQUIRE(b && rawRef);
     TRY(flush_pending(b, stream, false));  // a frame still waiting belongs to the previous reference
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     MFSR_REQUIRE(hrRow0 >= 0 && hrRow1 > hrRow0 && hrRow1 <= L.hrH);
     // a zoom window set since the last reference takes effect here: the products below are made for its rows
     MFSR_REQUIRE(!b->winNext.on || (hrRow0 == 0 && hrRow1 == L.hrH));  // (a window is not combined with row stripes)
@@ -782,18 +771,19 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     }
     const bool whole = (hrRow0 == 0 && hrRow1 == L.hrH) || !c.fused;  // (the unfused chain always makes whole images)
     TRY(wait_uploads(b, stream));
-    if (!b->refPrepared) TRY(prepare_frame(b, rawRef, L.refHalf, L.refPyr, stream));
+    b->ref = prepared ? *prepared : L.ref;
+    const FrameProducts& R = b->ref;
+    if (!prepared) TRY(prepare_frame(b, rawRef, R, stream));
     if (c.fused)
         for (int l = 0; l < c.levels; l++) {
-            const Img& ref = L.refPyr[ilog2(c.levelFactor[l])];
+            const Img& ref = R.pyr[ilog2(c.levelFactor[l])];
             TRY(mfsr_tileSquaredSums((const float*)ref.ptr, L.refSq[l], ref.w, ref.h, ref.pitch, c.maxShift[l], c.tileSize[l],
                                      L.tcx[l], L.tcy[l], stream));
         }
 
     if (c.preAlign) {
         TRY(mfsr_preAlign_init(L.preWork, c.preAlignMaxAngle, stream));
-        if (!b->refPrepared)
-            TRY(mfsr_preAlignPyramid((const float*)L.refPyr[0].ptr, L.tw, L.th, L.refPyr[0].pitch, L.preRefPyr, stream));
+        if (!prepared) TRY(mfsr_preAlignPyramid((const float*)R.pyr[0].ptr, L.tw, L.th, R.pyr[0].pitch, R.prePyr, stream));
     }
 
     // What follows is read by the fuse and the finish only, not by the alignment: with cfg.asyncFuse it runs on the burst's fuse
@@ -830,10 +820,10 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
             f1 = f1 > L.th ? L.th : f1;
         }
         const int fr = f1 - f0;
-        Img& ix = L.Ix;
-        Img& iy = L.Iy;
+        const Img& ix = L.Ix;
+        const Img& iy = L.Iy;
         auto rows = [&](const Img& im) { return (char*)im.ptr + (size_t)f0 * im.pitch; };
-        TRY(mfsr_ComputeDerivatives2Rows(L.tw, L.th, ix.pitch, (float*)ix.ptr, (float*)iy.ptr, as_tex(L.refPyr[0]), f0, fr, es));
+        TRY(mfsr_ComputeDerivatives2Rows(L.tw, L.th, ix.pitch, (float*)ix.ptr, (float*)iy.ptr, as_tex(R.pyr[0]), f0, fr, es));
         TRY(mfsr_ComputeStructureTensor((const float*)rows(ix), (const float*)rows(iy), (mfsr_float3*)rows(L.tensor), L.tw, fr, ix.pitch,
                                         L.tensor.pitch, es));
         TRY(mfsr_separableFilter((const float*)rows(L.tensor), L.tensor.pitch, (float*)rows(L.tensorTmp), (float*)rows(L.tensorSm),
@@ -933,41 +923,43 @@ extern "C" int mfsr_burst_get_window(const mfsr_burst* b, int* x0, int* y0, int*
     return MFSR_OK;
 }
 
-// B: coarse -> fine tile tracking of the moved pyramid against the reference
-static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream_t stream)
+// B: coarse -> fine tile tracking of the moved pyramid against the reference's (refSq: the reference's sum(ref^2) per tile and
+// level, fused tracker); the tile shifts of every level land in work.shifts
+static int track_tiles(mfsr_burst* b, const FrameProducts& refF, float* const* refSq, const FrameProducts& movF,
+                       const AlignScratch& work, const mfsr_prealign* hostBase, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     const mfsr_float2 zero2 = {0.0f, 0.0f};
     for (int l = 0; l < c.levels; l++) {
         const int pi = ilog2(c.levelFactor[l]);
-        const Img& ref = L.refPyr[pi];
-        const Img& mov = L.movPyr[pi];
+        const Img& ref = refF.pyr[pi];
+        const Img& mov = movF.pyr[pi];
         const int T = c.tileSize[l], S = c.maxShift[l];
         const int tiles = L.tcx[l] * L.tcy[l];
         const mfsr_float2* pre = nullptr;
         b->paths[mfsr_trackTilesFastSupported(T, S) ? MFSR_PATH_TRACK_FAST_PAIR : MFSR_PATH_TRACK_GENERIC_PAIR]++;
         if (c.fused && l > 0) {
             // B8 folded into the tracker: the pre-shifts come straight from the previous level's shifts
-            TRY(mfsr_trackTilesFusedUp((const float*)ref.ptr, (const float*)mov.ptr, (const mfsr_float2*)L.shifts[l - 1].ptr,
-                                       L.shifts[l - 1].pitch, c.levelFactor[l - 1], c.levelFactor[l], L.tcx[l - 1], L.tcy[l - 1],
-                                       c.tileSize[l - 1], (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, S,
-                                       T, L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l], c.preAlign ? L.preResult : nullptr,
+            TRY(mfsr_trackTilesFusedUp((const float*)ref.ptr, (const float*)mov.ptr, (const mfsr_float2*)work.shifts[l - 1].ptr,
+                                       work.shifts[l - 1].pitch, c.levelFactor[l - 1], c.levelFactor[l], L.tcx[l - 1], L.tcy[l - 1],
+                                       c.tileSize[l - 1], (mfsr_float2*)work.shifts[l].ptr, work.shifts[l].pitch, ref.w, ref.h, ref.pitch, S,
+                                       T, L.tcx[l], L.tcy[l], c.minimumThreshold, refSq[l], c.preAlign ? work.preResult : nullptr,
                                        1.0f / (float)c.levelFactor[l], stream));
             b->paths[MFSR_PATH_TRACK_FUSED_UP]++;
             continue;
         }
         if (l > 0) {
-            TRY(mfsr_UpSampleShifts((const mfsr_float2*)L.shifts[l - 1].ptr, (mfsr_float2*)L.pre[l].ptr,
-                                    L.shifts[l - 1].pitch, L.pre[l].pitch, c.levelFactor[l - 1], c.levelFactor[l],
+            TRY(mfsr_UpSampleShifts((const mfsr_float2*)work.shifts[l - 1].ptr, (mfsr_float2*)L.pre[l].ptr,
+                                    work.shifts[l - 1].pitch, L.pre[l].pitch, c.levelFactor[l - 1], c.levelFactor[l],
                                     L.tcx[l - 1], L.tcy[l - 1], L.tcx[l], L.tcy[l], c.tileSize[l - 1], T, stream));
             pre = (const mfsr_float2*)L.pre[l].ptr;
         }
         if (c.fused) {
             TRY(mfsr_trackTilesFusedBase((const float*)ref.ptr, (const float*)mov.ptr, pre, L.pre[l].pitch,
-                                         (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, S, T,
-                                         L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l],
-                                         c.preAlign ? L.preResult : nullptr, 1.0f / (float)c.levelFactor[l], stream));
+                                         (mfsr_float2*)work.shifts[l].ptr, work.shifts[l].pitch, ref.w, ref.h, ref.pitch, S, T,
+                                         L.tcx[l], L.tcy[l], c.minimumThreshold, refSq[l],
+                                         c.preAlign ? work.preResult : nullptr, 1.0f / (float)c.levelFactor[l], stream));
             b->paths[MFSR_PATH_TRACK_FUSED_BASE]++;
         } else {
             b->paths[MFSR_PATH_TRACK_CHAIN]++;
@@ -992,9 +984,9 @@ static int track_tiles(mfsr_burst* b, const mfsr_prealign* hostBase, mfsr_stream
             TRY(mfsr_boxFilterWithBorderX(L.movTiles, L.boxX, S, T, tiles, stream));
             TRY(mfsr_boxFilterWithBorderY(L.boxX, L.boxY, S, T, tiles, stream));
             TRY(mfsr_normalizedCC(L.cc, L.sqsum, L.boxY, L.dist, S, T, tiles, stream));
-            TRY(mfsr_findMinimum(L.dist, (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, S, tiles, L.tcx[l],
+            TRY(mfsr_findMinimum(L.dist, (mfsr_float2*)work.shifts[l].ptr, work.shifts[l].pitch, S, tiles, L.tcx[l],
                                  c.minimumThreshold, stream));
-            TRY(mfsr_addRoundedPreShift(pre, L.pre[l].pitch, (mfsr_float2*)L.shifts[l].ptr, L.shifts[l].pitch, L.tcx[l],
+            TRY(mfsr_addRoundedPreShift(pre, L.pre[l].pitch, (mfsr_float2*)work.shifts[l].ptr, work.shifts[l].pitch, L.tcx[l],
                                         L.tcy[l], stream));
         }
     }
@@ -1130,10 +1122,6 @@ static int flush_pending(mfsr_burst* b, mfsr_stream_t stream, bool materializeFr
     return join_fuse(b, stream);
 }
 
-// A1 + (I) + B + D + F of one frame into ring slot `slot`: *flowOut / *maskOut name the buffers that hold the result
-// phases: ALIGN_PRE = everything up to the flow field (+ first warp), ALIGN_LK = the Lucas-Kanade iterations, ALIGN_POST = the
-// robustness mask.  align_group runs PRE and POST frame by frame and the iterations of a whole group in one launch each.
-enum { ALIGN_PRE = 1, ALIGN_LK = 2, ALIGN_POST = 4, ALIGN_ALL = 7 };
 static bool lk_warped_path(const mfsr_burst* b)
 {
     // fused LK: the warped moved image travels from launch to launch (every pixel warped once per iteration, by the
@@ -1146,184 +1134,218 @@ static bool lk_warped_path(const mfsr_burst* b)
     return c.fused && lkWarped && c.lkIterations > 0 && b->L.tw >= 64 && b->L.th >= 32;
 }
 
-static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int slot, Img** flowOut, Img** maskOut,
-                       mfsr_stream_t stream, int phases = ALIGN_ALL)
+// Which buffer of the slot's LK ping-pong pair holds a frame's final flow.  Every fused iteration (sweep, warped or plain) writes
+// the pair's other buffer, so an odd number of them ends in buffer 1; the unfused chain updates buffer 0 in place; without
+// iterations the flow field stays where it was made, in buffer 0 -- as does a reference frame's identity flow.
+static const Img* final_flow(const mfsr_burst* b, int slot, int isReference)
 {
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    return &b->L.flowBuf[2 * slot + (!isReference && c.fused ? (c.lkIterations & 1) : 0)];
+}
+
+// One frame's alignment into ring slot `slot` is three stages.  mov / work: the frame's products and the scratch its alignment
+// writes; prepared: mov was made by the caller (frame streams, joint mode); suppliedShifts: tile shifts that replace the
+// tracker's (joint mode).
+// align_pre: A1 + tracking pyramid, (I) pre-alignment, B tracker, D1 flow field (+ first warp) -- everything up to the
+// Lucas-Kanade iterations; for the reference frame the identity flow and certainty 1, which is all of its alignment.
+static int align_pre(mfsr_burst* b, const uint16_t* raw, int isReference, int slot, const FrameProducts& mov, bool prepared,
+                     const AlignScratch& work, const Img* suppliedShifts, mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const FrameProducts& ref = b->ref;
     TRY(wait_uploads(b, stream));
     // the slot's buffers are free once the fuse that read them last has run
-    if ((phases & ALIGN_PRE) && b->fuseStream && b->fusedOutstanding[slot]) {
+    if (b->fuseStream && b->fusedOutstanding[slot]) {
         MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[slot], 0));
         b->fusedOutstanding[slot] = false;
     }
-    Img* flow = &L.flowBuf[2 * slot];
-    Img* other = &L.flowBuf[2 * slot + 1];
-    Img* mask = &L.maskBuf[slot];
-    const bool warped = lk_warped_path(b);
+    const Img* flow = &L.flowBuf[2 * slot];
     if (isReference) {
-        // identity flow, certainty 1
-        if (phases & ALIGN_PRE) {
-            MFSR_HIP_TRY(hipMemsetAsync(flow->ptr, 0, (size_t)flow->pitch * flow->h, mfsr_s(stream)));
-            TRY(mfsr_fill_f32((float*)mask->ptr, (size_t)mask->pitch / 4 * mask->h, 1.0f, stream));
-        }
-    } else {
-      if (phases & ALIGN_PRE) {
-        if (!b->movPrepared) TRY(prepare_frame(b, raw, L.movHalf, L.movPyr, stream));
-        // I: global pre-alignment (base shift + rotation of this frame against the reference), kept in device memory
-        mfsr_prealign hostBase;
-        const mfsr_prealign* hb = nullptr;
-        if (c.preAlign) {
-            if (!b->movPrepared)
-                TRY(mfsr_preAlignPyramid((const float*)L.movPyr[0].ptr, L.tw, L.th, L.movPyr[0].pitch, L.preMovPyr, stream));
-            TRY(mfsr_preAlign(L.preRefPyr, L.preMovPyr, L.tw, L.th, c.preAlignMaxAngle, L.preWork, L.preResult, stream));
-            b->preCur = L.preResult;  // (inside align_deferred this names the frame's align set: swap_set)
-            if (!c.fused) {
-                // the reference-shaped entry points take baseShift / baseRotation by value: one host round trip
-                MFSR_HIP_TRY(hipMemcpyAsync(&hostBase, L.preResult, sizeof(hostBase), hipMemcpyDeviceToHost, mfsr_s(stream)));
-                MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
-                hb = &hostBase;
-            }
-        }
-        if (!b->givenShifts) TRY(track_tiles(b, hb, stream));
-        const int last = c.levels - 1;
-        const Img& tileShifts = b->givenShifts ? *b->givenShifts : L.shifts[last];
-        const mfsr_float2 zero2 = {0.0f, 0.0f};
-        if (warped) {
-            TRY(mfsr_CreateFlowFieldWarped((mfsr_float2*)flow->ptr, as_tex(tileShifts), L.tw, L.th, flow->pitch, zero2, 0.0f,
-                                           c.preAlign ? L.preResult : nullptr, (const float*)L.refPyr[0].ptr,
-                                           (const float*)L.movPyr[0].ptr, L.refPyr[0].pitch, (float*)L.lkSum[0].ptr,
-                                           (float*)L.lkDiff[0].ptr, L.lkSum[0].pitch, stream));
-            b->paths[MFSR_PATH_FLOW_WARPED]++;
-        } else if (c.preAlign && c.fused) {
-            TRY(mfsr_CreateFlowFieldFromTilesBase((mfsr_float2*)flow->ptr, as_tex(tileShifts), L.tw, L.th, flow->pitch,
-                                                  L.preResult, stream));
-            b->paths[MFSR_PATH_FLOW_BASE]++;
-        } else {
-            mfsr_float2 base = zero2;
-            float rot = 0.0f;
-            if (hb) {
-                base.x = hb->shiftX;
-                base.y = hb->shiftY;
-                rot = hb->rotation;
-            }
-            TRY(mfsr_CreateFlowFieldFromTiles((mfsr_float2*)flow->ptr, as_tex(tileShifts), c.tileSize[last], L.tcx[last],
-                                              L.tcy[last], L.tw, L.th, flow->pitch, base, rot, stream));
-            b->paths[MFSR_PATH_FLOW_PLAIN]++;
-        }
-      }
-      if (phases & ALIGN_LK) {
-        for (int it = 0; it < c.lkIterations; it++) {
-            if (warped) {
-                const bool lastIt = it == c.lkIterations - 1;
-                const int in = it & 1, out = in ^ 1;
-                // the sweep kernel wherever it applies, also for a single frame: the frame-by-frame paths (frame streams,
-                // joint mode, mfsr_burst_align_frame of the multi-GPU layer, groups of one) then give the very bits of the
-                // frame-batched burst -- its result does not depend on how many frames share a launch
-                mfsr_lk_frame one;
-                one.shiftsIn = (const mfsr_float2*)flow->ptr;
-                one.shiftsOut = (mfsr_float2*)other->ptr;
-                one.movedImg = (const float*)L.movPyr[0].ptr;
-                one.sumIn = (const float*)L.lkSum[in].ptr;
-                one.diffIn = (const float*)L.lkDiff[in].ptr;
-                one.sumOut = lastIt ? nullptr : (float*)L.lkSum[out].ptr;
-                one.diffOut = lastIt ? nullptr : (float*)L.lkDiff[out].ptr;
-                const int rcs = mfsr_lucasKanadeSweepBatch(1, &one, (const float*)L.refPyr[0].ptr, flow->pitch, L.refPyr[0].pitch,
-                                                           L.lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
-                                                           lastIt ? (float)L.flowScale : 1.0f, stream);
-                if (rcs != MFSR_E_UNSUPPORTED) {
-                    if (rcs) return rcs;
-                    b->paths[MFSR_PATH_LK_SWEEP_SINGLE]++;
-                    Img* t = flow;
-                    flow = other;
-                    other = t;
-                    continue;
-                }
-                TRY(mfsr_lucasKanadeIterationWarped((const mfsr_float2*)flow->ptr, (mfsr_float2*)other->ptr, flow->pitch,
-                                                    (const float*)L.refPyr[0].ptr, (const float*)L.movPyr[0].ptr, L.refPyr[0].pitch,
-                                                    (const float*)L.lkSum[in].ptr, (const float*)L.lkDiff[in].ptr,
-                                                    lastIt ? nullptr : (float*)L.lkSum[out].ptr,
-                                                    lastIt ? nullptr : (float*)L.lkDiff[out].ptr, L.lkSum[0].pitch, L.tw, L.th,
-                                                    c.lkHalfWindow, c.lkMinDet, lastIt ? (float)L.flowScale : 1.0f, stream));
-                b->paths[MFSR_PATH_LK_ITERATION_WARPED]++;
-                Img* t = flow;
-                flow = other;
-                other = t;
-            } else if (c.fused) {
-                TRY(mfsr_lucasKanadeIterationFused((const mfsr_float2*)flow->ptr, (mfsr_float2*)other->ptr, flow->pitch,
-                                                   (const float*)L.refPyr[0].ptr, (const float*)L.movPyr[0].ptr,
-                                                   L.refPyr[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
-                                                   it == c.lkIterations - 1 ? (float)L.flowScale : 1.0f, stream));
-                b->paths[MFSR_PATH_LK_ITERATION_FUSED]++;
-                Img* t = flow;
-                flow = other;
-                other = t;
-            } else {
-                TRY(mfsr_WarpingKernel(L.tw, L.th, L.warped.pitch, as_tex(*flow), (float*)L.warped.ptr, as_tex(L.movPyr[0]),
-                                       stream));
-                // texSource = warped moved frame, texTarget = reference: the reference's stencil is
-                // minus the usual derivative (opticalFlow.cu:116-119) and Iz = source - target (:131),
-                // so this is the order for which `shift += UV` (:322-323) descends.
-                TRY(mfsr_ComputeDerivativesKernel(L.tw, L.th, L.Ix.pitch, (float*)L.Ix.ptr, (float*)L.Iy.ptr,
-                                                  (float*)L.It.ptr, as_tex(L.warped), as_tex(L.refPyr[0]), stream));
-                TRY(mfsr_lucasKanadeOptim((mfsr_float2*)flow->ptr, (const float*)L.Ix.ptr, (const float*)L.Iy.ptr,
-                                          (const float*)L.It.ptr, flow->pitch, L.Ix.pitch, L.tw, L.th, c.lkHalfWindow,
-                                          c.lkMinDet, stream));
-                b->paths[MFSR_PATH_LK_CHAIN]++;
-            }
-        }
-        if (L.flowScale != 1 && !(c.fused && c.lkIterations > 0)) {  // the fused LK scales on its last iteration
-            TRY(mfsr_scaleFlow((mfsr_float2*)flow->ptr, flow->pitch, L.tw, L.th, (float)L.flowScale, stream));
-            b->paths[MFSR_PATH_SCALE_FLOW]++;
-        }
-      } else if (c.fused && (c.lkIterations & 1)) {
-        // the iterations ran elsewhere (align_group): an odd number of them leaves the flow in the slot's other buffer
-        Img* t = flow;
-        flow = other;
-        other = t;
-      }
-      if (phases & ALIGN_POST) {
-        // F: robustness mask (the 1-px ring is never written by the kernel -> zero it); with cfg.maskErode into the scratch
-        // mask, from which the erosion writes the slot's
-        Img* fOut = c.maskErode > 0 ? &L.maskRaw[0] : mask;
-        if (c.fused) {
-            TRY(mfsr_robustnessMaskFused((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
-                                         (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch, c.alpha,
-                                         c.beta, c.thresholdM, stream));
-            b->paths[MFSR_PATH_ROBUST_FUSED]++;
-        } else {
-            b->paths[MFSR_PATH_ROBUST_CHAIN]++;
-            TRY(mfsr_zeroRing_f32x4((mfsr_float4*)fOut->ptr, fOut->pitch, L.hw, L.hh, stream));
-            TRY(mfsr_ComputeRobustnessMask((const mfsr_float3*)L.refHalf.ptr, (const mfsr_float3*)L.movHalf.ptr,
-                                           (mfsr_float4*)fOut->ptr, as_tex(*flow), L.hw, L.hh, L.refHalf.pitch, fOut->pitch,
-                                           c.alpha, c.beta, c.thresholdM, stream));
-        }
-        if (c.maskErode > 0) {
-            const mfsr_float4* ein = (const mfsr_float4*)fOut->ptr;
-            mfsr_float4* eout = (mfsr_float4*)mask->ptr;
-            TRY(mfsr_erodeMaskBatch(1, &ein, &eout, L.hw, L.hh, fOut->pitch, mask->pitch, c.maskErode, stream));
-        }
-      }
+        const Img* mask = &L.maskBuf[slot];
+        MFSR_HIP_TRY(hipMemsetAsync(flow->ptr, 0, (size_t)flow->pitch * flow->h, mfsr_s(stream)));
+        return mfsr_fill_f32((float*)mask->ptr, (size_t)mask->pitch / 4 * mask->h, 1.0f, stream);
     }
-    *flowOut = flow;
-    *maskOut = mask;
-    b->slotFlow[slot] = flow;  // mfsr_burst_debug_frame_views
+    if (!prepared) TRY(prepare_frame(b, raw, mov, stream));
+    // I: global pre-alignment (base shift + rotation of this frame against the reference), kept in device memory
+    mfsr_prealign hostBase;
+    const mfsr_prealign* hb = nullptr;
+    if (c.preAlign) {
+        if (!prepared) TRY(mfsr_preAlignPyramid((const float*)mov.pyr[0].ptr, L.tw, L.th, mov.pyr[0].pitch, mov.prePyr, stream));
+        TRY(mfsr_preAlign(ref.prePyr, mov.prePyr, L.tw, L.th, c.preAlignMaxAngle, L.preWork, work.preResult, stream));
+        b->preCur = work.preResult;
+        if (!c.fused) {
+            // the reference-shaped entry points take baseShift / baseRotation by value: one host round trip
+            MFSR_HIP_TRY(hipMemcpyAsync(&hostBase, work.preResult, sizeof(hostBase), hipMemcpyDeviceToHost, mfsr_s(stream)));
+            MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+            hb = &hostBase;
+        }
+    }
+    if (!suppliedShifts) TRY(track_tiles(b, ref, L.refSq, mov, work, hb, stream));
+    const int last = c.levels - 1;
+    const Img& tileShifts = suppliedShifts ? *suppliedShifts : work.shifts[last];
+    const mfsr_float2 zero2 = {0.0f, 0.0f};
+    if (lk_warped_path(b)) {
+        TRY(mfsr_CreateFlowFieldWarped((mfsr_float2*)flow->ptr, as_tex(tileShifts), L.tw, L.th, flow->pitch, zero2, 0.0f,
+                                       c.preAlign ? work.preResult : nullptr, (const float*)ref.pyr[0].ptr,
+                                       (const float*)mov.pyr[0].ptr, ref.pyr[0].pitch, (float*)work.lkSum[0].ptr,
+                                       (float*)work.lkDiff[0].ptr, work.lkSum[0].pitch, stream));
+        b->paths[MFSR_PATH_FLOW_WARPED]++;
+    } else if (c.preAlign && c.fused) {
+        TRY(mfsr_CreateFlowFieldFromTilesBase((mfsr_float2*)flow->ptr, as_tex(tileShifts), L.tw, L.th, flow->pitch, work.preResult,
+                                              stream));
+        b->paths[MFSR_PATH_FLOW_BASE]++;
+    } else {
+        mfsr_float2 base = zero2;
+        float rot = 0.0f;
+        if (hb) {
+            base.x = hb->shiftX;
+            base.y = hb->shiftY;
+            rot = hb->rotation;
+        }
+        TRY(mfsr_CreateFlowFieldFromTiles((mfsr_float2*)flow->ptr, as_tex(tileShifts), c.tileSize[last], L.tcx[last], L.tcy[last],
+                                          L.tw, L.th, flow->pitch, base, rot, stream));
+        b->paths[MFSR_PATH_FLOW_PLAIN]++;
+    }
     return MFSR_OK;
+}
+
+// align_lk: K, the Lucas-Kanade iterations of one moved frame, launch by launch; the flow ends in final_flow(b, slot, 0)
+static int align_lk(mfsr_burst* b, int slot, const FrameProducts& mov, const AlignScratch& work, mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const FrameProducts& ref = b->ref;
+    const bool warped = lk_warped_path(b);
+    for (int it = 0; it < c.lkIterations; it++) {
+        const bool lastIt = it == c.lkIterations - 1;
+        const int in = it & 1, out = in ^ 1;
+        const float scale = lastIt ? (float)L.flowScale : 1.0f;  // the fused LK scales on its last iteration
+        const Img* flow = &L.flowBuf[2 * slot + (c.fused ? in : 0)];
+        const Img* other = &L.flowBuf[2 * slot + out];
+        if (warped) {
+            // the sweep kernel wherever it applies, also for a single frame: the frame-by-frame paths (frame streams,
+            // joint mode, mfsr_burst_align_frame of the multi-GPU layer, groups of one) then give the very bits of the
+            // frame-batched burst -- its result does not depend on how many frames share a launch
+            mfsr_lk_frame one;
+            one.shiftsIn = (const mfsr_float2*)flow->ptr;
+            one.shiftsOut = (mfsr_float2*)other->ptr;
+            one.movedImg = (const float*)mov.pyr[0].ptr;
+            one.sumIn = (const float*)work.lkSum[in].ptr;
+            one.diffIn = (const float*)work.lkDiff[in].ptr;
+            one.sumOut = lastIt ? nullptr : (float*)work.lkSum[out].ptr;
+            one.diffOut = lastIt ? nullptr : (float*)work.lkDiff[out].ptr;
+            const int rcs = mfsr_lucasKanadeSweepBatch(1, &one, (const float*)ref.pyr[0].ptr, flow->pitch, ref.pyr[0].pitch,
+                                                       work.lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet, scale, stream);
+            if (rcs != MFSR_E_UNSUPPORTED) {
+                if (rcs) return rcs;
+                b->paths[MFSR_PATH_LK_SWEEP_SINGLE]++;
+                continue;
+            }
+            TRY(mfsr_lucasKanadeIterationWarped((const mfsr_float2*)flow->ptr, (mfsr_float2*)other->ptr, flow->pitch,
+                                                (const float*)ref.pyr[0].ptr, (const float*)mov.pyr[0].ptr, ref.pyr[0].pitch,
+                                                one.sumIn, one.diffIn, one.sumOut, one.diffOut, work.lkSum[0].pitch, L.tw, L.th,
+                                                c.lkHalfWindow, c.lkMinDet, scale, stream));
+            b->paths[MFSR_PATH_LK_ITERATION_WARPED]++;
+        } else if (c.fused) {
+            TRY(mfsr_lucasKanadeIterationFused((const mfsr_float2*)flow->ptr, (mfsr_float2*)other->ptr, flow->pitch,
+                                               (const float*)ref.pyr[0].ptr, (const float*)mov.pyr[0].ptr, ref.pyr[0].pitch, L.tw, L.th,
+                                               c.lkHalfWindow, c.lkMinDet, scale, stream));
+            b->paths[MFSR_PATH_LK_ITERATION_FUSED]++;
+        } else {
+            TRY(mfsr_WarpingKernel(L.tw, L.th, L.warped.pitch, as_tex(*flow), (float*)L.warped.ptr, as_tex(mov.pyr[0]), stream));
+            // texSource = warped moved frame, texTarget = reference: the reference's stencil is
+            // minus the usual derivative (opticalFlow.cu:116-119) and Iz = source - target (:131),
+            // so this is the order for which `shift += UV` (:322-323) descends.
+            TRY(mfsr_ComputeDerivativesKernel(L.tw, L.th, L.Ix.pitch, (float*)L.Ix.ptr, (float*)L.Iy.ptr, (float*)L.It.ptr,
+                                              as_tex(L.warped), as_tex(ref.pyr[0]), stream));
+            TRY(mfsr_lucasKanadeOptim((mfsr_float2*)flow->ptr, (const float*)L.Ix.ptr, (const float*)L.Iy.ptr, (const float*)L.It.ptr,
+                                      flow->pitch, L.Ix.pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet, stream));
+            b->paths[MFSR_PATH_LK_CHAIN]++;
+        }
+    }
+    if (L.flowScale != 1 && !(c.fused && c.lkIterations > 0)) {
+        const Img* flow = final_flow(b, slot, 0);
+        TRY(mfsr_scaleFlow((mfsr_float2*)flow->ptr, flow->pitch, L.tw, L.th, (float)L.flowScale, stream));
+        b->paths[MFSR_PATH_SCALE_FLOW]++;
+    }
+    return MFSR_OK;
+}
+
+// align_post: F, the robustness mask of one moved frame from its final flow (the 1-px ring is never written by the kernel ->
+// zero it); with cfg.maskErode into the scratch mask, from which the erosion writes the slot's
+static int align_post(mfsr_burst* b, int slot, const FrameProducts& mov, mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const FrameProducts& ref = b->ref;
+    const Img* flow = final_flow(b, slot, 0);
+    const Img* mask = &L.maskBuf[slot];
+    const Img* fOut = c.maskErode > 0 ? &L.maskRaw[0] : mask;
+    if (c.fused) {
+        TRY(mfsr_robustnessMaskFused((const mfsr_float3*)ref.half.ptr, (const mfsr_float3*)mov.half.ptr, (mfsr_float4*)fOut->ptr,
+                                     as_tex(*flow), L.hw, L.hh, ref.half.pitch, fOut->pitch, c.alpha, c.beta, c.thresholdM, stream));
+        b->paths[MFSR_PATH_ROBUST_FUSED]++;
+    } else {
+        b->paths[MFSR_PATH_ROBUST_CHAIN]++;
+        TRY(mfsr_zeroRing_f32x4((mfsr_float4*)fOut->ptr, fOut->pitch, L.hw, L.hh, stream));
+        TRY(mfsr_ComputeRobustnessMask((const mfsr_float3*)ref.half.ptr, (const mfsr_float3*)mov.half.ptr, (mfsr_float4*)fOut->ptr,
+                                       as_tex(*flow), L.hw, L.hh, ref.half.pitch, fOut->pitch, c.alpha, c.beta, c.thresholdM, stream));
+    }
+    if (c.maskErode > 0) {
+        const mfsr_float4* ein = (const mfsr_float4*)fOut->ptr;
+        mfsr_float4* eout = (mfsr_float4*)mask->ptr;
+        TRY(mfsr_erodeMaskBatch(1, &ein, &eout, L.hw, L.hh, fOut->pitch, mask->pitch, c.maskErode, stream));
+    }
+    return MFSR_OK;
+}
+
+// the flow and the mask of an aligned frame: where mfsr_burst_debug_frame_views and the fuse find them
+static void aligned_outputs(mfsr_burst* b, int slot, int isReference, const Img** flowOut, const Img** maskOut)
+{
+    *flowOut = b->slotFlow[slot] = final_flow(b, slot, isReference);
+    *maskOut = &b->L.maskBuf[slot];
+}
+
+// A1 + (I) + B + D + F of one frame into ring slot `slot`, in the burst's first set of per-frame intermediates (or from the
+// products / with the tile shifts the caller supplies): *flowOut / *maskOut name the buffers that hold the result
+static int align_frame(mfsr_burst* b, const uint16_t* raw, int isReference, int slot, const FrameProducts* prepared,
+                       const Img* suppliedShifts, const Img** flowOut, const Img** maskOut, mfsr_stream_t stream)
+{
+    const FrameProducts& mov = prepared ? *prepared : b->L.mov[0];
+    const AlignScratch& work = b->L.work[0];
+    TRY(align_pre(b, raw, isReference, slot, mov, prepared != nullptr, work, suppliedShifts, stream));
+    if (!isReference) {
+        TRY(align_lk(b, slot, mov, work, stream));
+        TRY(align_post(b, slot, mov, stream));
+    }
+    aligned_outputs(b, slot, isReference, flowOut, maskOut);
+    return MFSR_OK;
+}
+
+// MFSR_ALIGN_BATCH (A/B): 0 = every frame is aligned on its own; 1s = a group shares its Lucas-Kanade launches only; anything
+// else, or unset = a group shares every stage the batch kernels serve
+enum AlignBatch { ALIGN_BATCH_OFF, ALIGN_BATCH_LK, ALIGN_BATCH_STAGES };
+static AlignBatch align_batch_mode()
+{
+    static const AlignBatch mode = [] {
+        const char* e = getenv("MFSR_ALIGN_BATCH");
+        if (e && e[0] == '0') return ALIGN_BATCH_OFF;
+        return e && e[0] == '1' && e[1] == 's' ? ALIGN_BATCH_LK : ALIGN_BATCH_STAGES;
+    }();
+    return mode;
 }
 
 // Frame-batched alignment.  The frames of a fuse group are independent given the reference's products, and one frame's
 // alignment is a chain of small launches (prepare, two tracker levels, flow field, lkIterations x Lucas-Kanade, robustness:
 // 8 at the defaults, 10..30 us each at 4K) -- so add_frame only REGISTERS a frame while its group fills, and the group is
 // aligned as one batch when it is complete (or on flush / finish): the per-frame stages frame after frame into per-frame
-// intermediates (Layout::sets), every Lucas-Kanade iteration of all frames in ONE launch (mfsr_lucasKanadeSweepBatch).
+// intermediates (Layout::mov / Layout::work), every Lucas-Kanade iteration of all frames in ONE launch (mfsr_lucasKanadeSweepBatch).
 // Same kernels' arithmetic per frame as the frame-by-frame path except the sweep kernel's row-sum order (fp32 rounding of
-// the flow).  Frames whose intermediates the caller supplies (frame streams, the joint mode) take the frame-by-frame path.
-static bool can_defer_alignment(const mfsr_burst* b)
+// the flow).  Frames whose products or tile shifts the caller supplies (frame streams, the joint mode: `supplied`) take the
+// frame-by-frame path.
+static bool can_defer_alignment(const mfsr_burst* b, bool supplied)
 {
-    static const bool on = [] {
-        const char* e = getenv("MFSR_ALIGN_BATCH");
-        return !(e && e[0] == '0');
-    }();
     const mfsr_config& c = b->cfg;
     // (host bursts: frames are aligned one by one as they come off the PCIe link -- waiting for a whole group would leave
     // the GPU idle during the first uploads and would put the whole last group's alignment between the last upload and
@@ -1336,35 +1358,28 @@ static bool can_defer_alignment(const mfsr_burst* b)
     // back: b->hostBusy) batches every group: the GPU has work queued, so frame-by-frame launches buy no latency and cost
     // a tenth of the alignment's throughput
     const bool hostImmediate = b->holdLastGroup && !b->hostBusy && (b->framesSinceRef < b->group || !hostDefer);
-    return on && b->group > 1 && b->L.nSets >= b->group - 1 && lk_warped_path(b) && c.lkHalfWindow >= 1 && c.lkHalfWindow <= 7 &&
-           !b->movPrepared && !b->givenShifts && !hostImmediate;
+    return align_batch_mode() != ALIGN_BATCH_OFF && b->group > 1 && b->L.nAlign >= b->group && lk_warped_path(b) &&
+           c.lkHalfWindow >= 1 && c.lkHalfWindow <= 7 && !supplied && !hostImmediate;
 }
 
 static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
+    const FrameProducts& ref = b->ref;
     int idx[MFSR_MAX_FUSE_GROUP], n = 0;
     for (int i = 0; i < b->pend.n; i++)
         if (b->pend.deferred[i]) idx[n++] = i;
     if (n == 0) return MFSR_OK;
     TRY(wait_uploads(b, stream));
     b->paths[MFSR_PATH_ALIGN_BATCHES]++;
-    // the moved-frame intermediates of batch position q (0: the Layout's own members, q > 0: align set q - 1)
-    auto movHalf = [&](int q) -> Img& { return q == 0 ? L.movHalf : L.sets[q - 1].movHalf; };
-    auto movPyr = [&](int q) -> Img* { return q == 0 ? L.movPyr : L.sets[q - 1].movPyr; };
-    auto shiftsOf = [&](int q) -> Img* { return q == 0 ? L.shifts : L.sets[q - 1].shifts; };
-    auto lkSumOf = [&](int q) -> Img* { return q == 0 ? L.lkSum : L.sets[q - 1].lkSum; };
-    auto lkDiffOf = [&](int q) -> Img* { return q == 0 ? L.lkDiff : L.sets[q - 1].lkDiff; };
+    // The frame at batch position q works in L.mov[q] / L.work[q].
     // Every per-frame stage as ONE launch over the batch (gridDim.z = frame) where the default kernels apply: the fused prepare
     // kernel, the compile-time tracker at every level, the flow field + first warp, later the fused robustness kernel.
     // Anything else (monochrome frames, pre-alignment, other tile sizes) runs the same stages frame by frame.
-    static const bool stageBatchOn = [] {
-        const char* e = getenv("MFSR_ALIGN_BATCH");
-        return !(e && e[0] == '1' && e[1] == 's');  // MFSR_ALIGN_BATCH=1s: batch the Lucas-Kanade launches only (A/B)
-    }();
     const int nlev = ilog2(L.maxFactor) + 1;
-    bool stageBatch = stageBatchOn && c.fused && !c.mono && !c.preAlign && b->ntaps / 2 <= 8 && L.tw == L.hw && L.th == L.hh;
+    bool stageBatch = align_batch_mode() == ALIGN_BATCH_STAGES && c.fused && !c.mono && !c.preAlign && b->ntaps / 2 <= 8 &&
+                      L.tw == L.hw && L.th == L.hh;
     for (int l = 0; l < c.levels && stageBatch; l++) stageBatch = mfsr_trackTilesFastSupported(c.tileSize[l], c.maxShift[l]) != 0;
     int mq[MFSR_MAX_FUSE_GROUP], m = 0;  // batch positions of the moved (non-reference) frames
     for (int q = 0; q < n; q++)
@@ -1374,8 +1389,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         for (int q = 0; q < n; q++) {
             const int i = idx[q], slot = b->pend.slot[i];
             if (b->pend.isRef[i]) {  // identity flow, certainty 1 (and the slot wait) through the frame path
-                Img *flow = nullptr, *mask = nullptr;
-                TRY(align_frame(b, b->pend.raw[i], 1, slot, &flow, &mask, stream, ALIGN_PRE));
+                TRY(align_pre(b, b->pend.raw[i], 1, slot, L.mov[q], false, L.work[q], nullptr, stream));
             } else if (b->fuseStream && b->fusedOutstanding[slot]) {
                 // the slot's buffers are free once the fuse that read them last has run
                 MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[slot], 0));
@@ -1387,17 +1401,17 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             // A1 + luma + prefilter + first pyramid level
             mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
             for (int k = 0; k < m; k++) {
-                Img* pyr = movPyr(mq[k]);
+                const Img* pyr = L.mov[mq[k]].pyr;
                 pf[k].dataIn = b->pend.raw[idx[mq[k]]];
-                pf[k].halfOut = (mfsr_float3*)movHalf(mq[k]).ptr;
+                pf[k].halfOut = (mfsr_float3*)L.mov[mq[k]].half.ptr;
                 pf[k].pyr0 = (float*)pyr[0].ptr;
                 pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
             }
-            TRY(mfsr_prepareFrameFusedBatch(m, pf, L.movHalf.pitch, c.maxVal, L.hw, L.hh, L.movPyr[0].pitch, nlev > 1 ? L.movPyr[1].pitch : 0,
-                                            b->taps, b->ntaps, stream));
+            TRY(mfsr_prepareFrameFusedBatch(m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
+                                            nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream));
             b->paths[MFSR_PATH_PREPARE_BATCH]++;
             for (int k = 0; k < m; k++) {
-                Img* pyr = movPyr(mq[k]);
+                const Img* pyr = L.mov[mq[k]].pyr;
                 for (int i = 2; i < nlev; i++)
                     TRY(mfsr_downsample2x((const float*)pyr[i - 1].ptr, pyr[i - 1].pitch, (float*)pyr[i].ptr, pyr[i].pitch, pyr[i].w, pyr[i].h,
                                           stream));
@@ -1407,15 +1421,16 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
                 const int pi = ilog2(c.levelFactor[l]);
                 mfsr_track_frame tf[MFSR_MAX_FUSE_GROUP];
                 for (int k = 0; k < m; k++) {
-                    tf[k].movedImg = (const float*)movPyr(mq[k])[pi].ptr;
-                    tf[k].coarseShifts = l > 0 ? (const mfsr_float2*)shiftsOf(mq[k])[l - 1].ptr : nullptr;
-                    tf[k].coordinates = (mfsr_float2*)shiftsOf(mq[k])[l].ptr;
+                    tf[k].movedImg = (const float*)L.mov[mq[k]].pyr[pi].ptr;
+                    tf[k].coarseShifts = l > 0 ? (const mfsr_float2*)L.work[mq[k]].shifts[l - 1].ptr : nullptr;
+                    tf[k].coordinates = (mfsr_float2*)L.work[mq[k]].shifts[l].ptr;
                     tf[k].base = nullptr;
                 }
-                const Img& ref = L.refPyr[pi];
-                TRY(mfsr_trackTilesFusedBatch(m, tf, (const float*)ref.ptr, l > 0 ? L.shifts[l - 1].pitch : 0, l > 0 ? c.levelFactor[l - 1] : 0,
+                const Img& refImg = ref.pyr[pi];
+                const Img* shifts = L.work[0].shifts;  // (every frame's tile grids have these pitches)
+                TRY(mfsr_trackTilesFusedBatch(m, tf, (const float*)refImg.ptr, l > 0 ? shifts[l - 1].pitch : 0, l > 0 ? c.levelFactor[l - 1] : 0,
                                               c.levelFactor[l], l > 0 ? L.tcx[l - 1] : 0, l > 0 ? L.tcy[l - 1] : 0,
-                                              l > 0 ? c.tileSize[l - 1] : 0, L.shifts[l].pitch, ref.w, ref.h, ref.pitch, c.maxShift[l],
+                                              l > 0 ? c.tileSize[l - 1] : 0, shifts[l].pitch, refImg.w, refImg.h, refImg.pitch, c.maxShift[l],
                                               c.tileSize[l], L.tcx[l], L.tcy[l], c.minimumThreshold, L.refSq[l],
                                               1.0f / (float)c.levelFactor[l], stream));
                 b->paths[MFSR_PATH_TRACK_FUSED_BATCH]++;
@@ -1427,26 +1442,23 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             for (int k = 0; k < m; k++) {
                 const int slot = b->pend.slot[idx[mq[k]]];
                 ff[k].outImg = (mfsr_float2*)L.flowBuf[2 * slot].ptr;
-                ff[k].tileShifts = (const mfsr_float2*)shiftsOf(mq[k])[last].ptr;
+                ff[k].tileShifts = (const mfsr_float2*)L.work[mq[k]].shifts[last].ptr;
                 ff[k].base = nullptr;
-                ff[k].movedImg = (const float*)movPyr(mq[k])[0].ptr;
-                ff[k].sumOut = (float*)lkSumOf(mq[k])[0].ptr;
-                ff[k].diffOut = (float*)lkDiffOf(mq[k])[0].ptr;
+                ff[k].movedImg = (const float*)L.mov[mq[k]].pyr[0].ptr;
+                ff[k].sumOut = (float*)L.work[mq[k]].lkSum[0].ptr;
+                ff[k].diffOut = (float*)L.work[mq[k]].lkDiff[0].ptr;
             }
-            TRY(mfsr_CreateFlowFieldWarpedBatch(m, ff, L.shifts[last].pitch, L.shifts[last].w, L.shifts[last].h, L.tw, L.th,
-                                                L.flowBuf[0].pitch, (const float*)L.refPyr[0].ptr, L.refPyr[0].pitch, L.lkSum[0].pitch, stream));
+            const Img& grid = L.work[0].shifts[last];
+            TRY(mfsr_CreateFlowFieldWarpedBatch(m, ff, grid.pitch, grid.w, grid.h, L.tw, L.th, L.flowBuf[0].pitch,
+                                                (const float*)ref.pyr[0].ptr, ref.pyr[0].pitch, L.work[0].lkSum[0].pitch, stream));
             b->paths[MFSR_PATH_FLOW_WARPED_BATCH]++;
         }
     } else {
-    // per-frame stages up to the flow field + first warp; frame q > 0 of the batch works in align set q - 1
-    for (int q = 0; q < n; q++) {
-        const int i = idx[q];
-        if (q > 0) swap_set(L, L.sets[q - 1]);
-        Img *flow = nullptr, *mask = nullptr;
-        const int rc = align_frame(b, b->pend.raw[i], b->pend.isRef[i], b->pend.slot[i], &flow, &mask, stream, ALIGN_PRE);
-        if (q > 0) swap_set(L, L.sets[q - 1]);
-        if (rc) return rc;
-    }
+        // per-frame stages up to the flow field + first warp
+        for (int q = 0; q < n; q++) {
+            const int i = idx[q];
+            TRY(align_pre(b, b->pend.raw[i], b->pend.isRef[i], b->pend.slot[i], L.mov[q], false, L.work[q], nullptr, stream));
+        }
     }
     // every Lucas-Kanade iteration of the batch in one launch
     bool batched = true;
@@ -1459,12 +1471,10 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             const int i = idx[q];
             if (b->pend.isRef[i]) continue;
             const int slot = b->pend.slot[i];
-            const Img* sum = q == 0 ? L.lkSum : L.sets[q - 1].lkSum;
-            const Img* diff = q == 0 ? L.lkDiff : L.sets[q - 1].lkDiff;
-            const Img& mov = q == 0 ? L.movPyr[0] : L.sets[q - 1].movPyr[0];
+            const Img *sum = L.work[q].lkSum, *diff = L.work[q].lkDiff;
             fr[m].shiftsIn = (const mfsr_float2*)L.flowBuf[2 * slot + in].ptr;
             fr[m].shiftsOut = (mfsr_float2*)L.flowBuf[2 * slot + out].ptr;
-            fr[m].movedImg = (const float*)mov.ptr;
+            fr[m].movedImg = (const float*)L.mov[q].pyr[0].ptr;
             fr[m].sumIn = (const float*)sum[in].ptr;
             fr[m].diffIn = (const float*)diff[in].ptr;
             fr[m].sumOut = lastIt ? nullptr : (float*)sum[out].ptr;
@@ -1472,8 +1482,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             m++;
         }
         if (m == 0) break;
-        const int rc = mfsr_lucasKanadeSweepBatch(m, fr, (const float*)L.refPyr[0].ptr, L.flowBuf[0].pitch, L.refPyr[0].pitch,
-                                                  L.lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
+        const int rc = mfsr_lucasKanadeSweepBatch(m, fr, (const float*)ref.pyr[0].ptr, L.flowBuf[0].pitch, ref.pyr[0].pitch,
+                                                  L.work[0].lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
                                                   lastIt ? (float)L.flowScale : 1.0f, stream);
         if (rc == MFSR_E_UNSUPPORTED && it == 0)
             batched = false;  // (cannot happen after can_defer_alignment; kept as a safe fallback)
@@ -1488,12 +1498,12 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         mfsr_robustness_frame rf[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
             const int slot = b->pend.slot[idx[mq[k]]];
-            rf[k].movedHalf = (const mfsr_float3*)movHalf(mq[k]).ptr;
+            rf[k].movedHalf = (const mfsr_float3*)L.mov[mq[k]].half.ptr;
             rf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
-            rf[k].flow = (const mfsr_float2*)L.flowBuf[2 * slot + (c.lkIterations & 1)].ptr;  // where the ping-pong ends
+            rf[k].flow = (const mfsr_float2*)final_flow(b, slot, 0)->ptr;
         }
-        const int rc = mfsr_robustnessMaskFusedBatch(m, rf, (const mfsr_float3*)L.refHalf.ptr, L.flowBuf[0].pitch, L.tw, L.th, L.hw, L.hh,
-                                                     L.refHalf.pitch, L.maskBuf[0].pitch, c.alpha, c.beta, c.thresholdM, stream);
+        const int rc = mfsr_robustnessMaskFusedBatch(m, rf, (const mfsr_float3*)ref.half.ptr, L.flowBuf[0].pitch, L.tw, L.th, L.hw, L.hh,
+                                                     ref.half.pitch, L.maskBuf[0].pitch, c.alpha, c.beta, c.thresholdM, stream);
         if (rc == MFSR_E_UNSUPPORTED)
             maskBatch = false;  // (the straight robustness kernel was selected: frame by frame below)
         else if (rc)
@@ -1511,18 +1521,15 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         }
     }
     for (int q = 0; q < n; q++) {
-        const int i = idx[q];
-        if (q > 0) swap_set(L, L.sets[q - 1]);
-        Img *flow = nullptr, *mask = nullptr;
-        const int rc = align_frame(b, b->pend.raw[i], b->pend.isRef[i], b->pend.slot[i], &flow, &mask, stream,
-                                   maskBatch ? 0 : (batched ? ALIGN_POST : (ALIGN_LK | ALIGN_POST)));
-        if (q > 0) swap_set(L, L.sets[q - 1]);
-        if (rc) return rc;
-        b->pend.flow[i] = flow;
-        b->pend.mask[i] = mask;
+        const int i = idx[q], slot = b->pend.slot[i];
+        if (!b->pend.isRef[i]) {
+            if (!batched) TRY(align_lk(b, slot, L.mov[q], L.work[q], stream));
+            if (!maskBatch) TRY(align_post(b, slot, L.mov[q], stream));
+        }
+        aligned_outputs(b, slot, b->pend.isRef[i], &b->pend.flow[i], &b->pend.mask[i]);
         b->pend.deferred[i] = false;
-        b->flowCur = flow;
-        b->maskCur = mask;
+        b->flowCur = b->pend.flow[i];
+        b->maskCur = b->pend.mask[i];
         if (b->fuseStream) MFSR_HIP_TRY(hipEventRecord(b->evAligned[b->pend.slot[i]], mfsr_s(stream)));
     }
     return MFSR_OK;
@@ -1530,8 +1537,10 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
 
 // hostBurst: the frame belongs to a host-frame burst (mfsr_burst_add_frame_host), whose last groups wait for
 // mfsr_burst_finish_host; a frame added through mfsr_burst_add_frame never leaves a complete group waiting
+// prepared / suppliedShifts: the frame's products and its tile shifts where the caller has made them (frame streams, joint mode)
 static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, mfsr_float3* imgOut, mfsr_float3* totalWeights,
-                          bool hostBurst, mfsr_stream_t stream)
+                          bool hostBurst, mfsr_stream_t stream, const FrameProducts* prepared = nullptr,
+                          const Img* suppliedShifts = nullptr)
 {
     MFSR_REQUIRE(b && raw && imgOut && totalWeights);
     MFSR_REQUIRE(b->haveRef);
@@ -1546,12 +1555,12 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     if (b->pend.n >= b->group) TRY(accumulate_pending(b, stream));
     MFSR_REQUIRE(b->pend.n < MFSR_MAX_FUSE_GROUP);
     const int slot = b->frameCounter++ % kRing;
-    Img *flow = nullptr, *mask = nullptr;
-    const bool defer = can_defer_alignment(b);
+    const Img *flow = nullptr, *mask = nullptr;
+    const bool defer = can_defer_alignment(b, prepared || suppliedShifts);
     b->paths[defer ? MFSR_PATH_FRAMES_DEFERRED : MFSR_PATH_FRAMES_IMMEDIATE]++;
     if (!defer) {
         TRY(align_deferred(b, stream));  // keep the alignment in frame order on the stream
-        TRY(align_frame(b, raw, isReference, slot, &flow, &mask, stream));
+        TRY(align_frame(b, raw, isReference, slot, prepared, suppliedShifts, &flow, &mask, stream));
         b->flowCur = flow;
         b->maskCur = mask;
         if (b->fuseStream) MFSR_HIP_TRY(hipEventRecord(b->evAligned[slot], mfsr_s(stream)));
@@ -1625,13 +1634,13 @@ extern "C" int mfsr_burst_align_frame(mfsr_burst* b, const uint16_t* raw, int is
     MFSR_REQUIRE(b && raw && flowOut && maskOut);
     MFSR_REQUIRE(b->haveRef);
     MFSR_REQUIRE(!b->refStale);  // after mfsr_burst_process_joint: call mfsr_burst_set_reference first
-    Layout& L = b->L;
+    const Layout& L = b->L;
     MFSR_REQUIRE((long long)flowPitch >= 8LL * L.tw && (flowPitch & 7) == 0 && ((uintptr_t)flowOut & 7) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0 && ((uintptr_t)maskOut & 15) == 0);
     TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
     const int slot = b->frameCounter++ % kRing;
-    Img *flow = nullptr, *mask = nullptr;
-    TRY(align_frame(b, raw, isReference, slot, &flow, &mask, stream));
+    const Img *flow = nullptr, *mask = nullptr;
+    TRY(align_frame(b, raw, isReference, slot, nullptr, nullptr, &flow, &mask, stream));
     b->flowCur = flow;
     b->maskCur = mask;
     MFSR_HIP_TRY(hipMemcpy2DAsync(flowOut, flowPitch, flow->ptr, flow->pitch, (size_t)L.tw * 8, L.th, hipMemcpyDeviceToDevice,
@@ -1650,13 +1659,13 @@ extern "C" int mfsr_burst_align_frames(mfsr_burst* b, int nFrames, const uint16_
     MFSR_REQUIRE(b && raws && flowOut && maskOut && nFrames >= 0);
     MFSR_REQUIRE(b->haveRef && !b->refStale);
     MFSR_REQUIRE(b->pend.n == 0);  // no frame of an add_frame group may be waiting
-    Layout& L = b->L;
+    const Layout& L = b->L;
     MFSR_REQUIRE((long long)flowPitch >= 8LL * L.tw && (flowPitch & 7) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0);
     for (int k = 0; k < nFrames; k++)
         MFSR_REQUIRE(raws[k] && flowOut[k] && maskOut[k] && ((uintptr_t)flowOut[k] & 7) == 0 && ((uintptr_t)maskOut[k] & 15) == 0);
     TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
-    const bool batch = can_defer_alignment(b);
+    const bool batch = can_defer_alignment(b, false);
     const int per = batch ? b->group : 1;
     for (int k0 = 0; k0 < nFrames; k0 += per) {
         const int n = nFrames - k0 < per ? nFrames - k0 : per;
@@ -1670,7 +1679,7 @@ extern "C" int mfsr_burst_align_frames(mfsr_burst* b, int nFrames, const uint16_
             b->pend.flow[j] = nullptr;
             b->pend.mask[j] = nullptr;
             if (!batch) {
-                const int rc = align_frame(b, raws[k0 + j], isRef, slot, &b->pend.flow[j], &b->pend.mask[j], stream);
+                const int rc = align_frame(b, raws[k0 + j], isRef, slot, nullptr, nullptr, &b->pend.flow[j], &b->pend.mask[j], stream);
                 if (rc) {
                     b->pend.n = 0;
                     return rc;
@@ -1703,7 +1712,7 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
     MFSR_REQUIRE(b->haveRef && !b->win.on);  // (row stripes of whole-frame accumulators)
     TRY(wait_ref_products(b, stream));
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
     const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
     TRY(mfsr_set_cfa_pattern(c.cfa));
@@ -1794,7 +1803,7 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     MFSR_REQUIRE(b->haveRef);
     TRY(flush_pending(b, stream));
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     const int pitch = 12 * out_w(b);
     if (c.fused && b->win.on) {
         return mfsr_finishFusedWindow(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
@@ -1824,7 +1833,7 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(b && imgOut && totalWeights && (outImg || out16));
     MFSR_REQUIRE(b->haveRef);
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     TRY(flush_pending(b, stream));
@@ -2058,7 +2067,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     bool capturing = false;
     TRY(host_epoch(b, stream, &capturing));
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     // the previous image may still be on its way to the host out of out16Dev
     if (b->downRecorded) MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evDown, 0));
     static const int nBandsEnv = [] {
@@ -2475,7 +2484,7 @@ extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2
     if (flow) *flow = as_tex(*b->flowCur);
     if (mask) *mask = as_tex(*b->maskCur);
     if (kernelParam) *kernelParam = as_tex(b->L.kparam4);
-    if (tracking) *tracking = as_tex(b->L.refPyr[0]);
+    if (tracking) *tracking = as_tex(b->ref.pyr[0]);
     return MFSR_OK;
 }
 
@@ -2501,7 +2510,7 @@ extern "C" int mfsr_burst_debug_frame_views(mfsr_burst* b, int framesBack, mfsr_
 extern "C" int mfsr_burst_prealign_result(mfsr_burst* b, mfsr_prealign* hostOut, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(b && hostOut);
-    MFSR_REQUIRE(b->cfg.preAlign && b->L.preResult);
+    MFSR_REQUIRE(b->cfg.preAlign && b->preCur);
     TRY(align_deferred(b, stream));  // the last frame may still be waiting for its group: its estimate does not exist yet
     MFSR_HIP_TRY(hipMemcpyAsync(hostOut, b->preCur, sizeof(*hostOut), hipMemcpyDeviceToHost, mfsr_s(stream)));
     MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
@@ -2513,22 +2522,15 @@ extern "C" int mfsr_burst_prealign_result(mfsr_burst* b, mfsr_prealign* hostOut,
 // Output t fuses frames [t-R, t+R] (clipped to the stream) with frame t as the reference: what one mfsr_burst_* burst per
 // window computes.  A frame takes part in up to 2R+1 windows; its upload and its per-frame products that do not depend
 // on the reference (A1 half-resolution RGB, tracking pyramid, pre-alignment search pyramid) are made once, when it
-// arrives, and kept in a ring of 2R+1 entries; the burst context gets their descriptors swapped in.
+// arrives, and kept in a ring of 2R+1 entries; the burst context is handed them with every set_reference / add_frame.
 namespace {
-struct FrameProducts {
-    uint16_t* raw;
-    Img half;
-    Img pyr[8];
-    void* prePyr;
-};
 struct StreamLayout {
     size_t burstWs, accBytes, entryBytes;
     size_t offBurst, offImg, offTw, offEntries, total;
 };
 size_t stream_entry(const mfsr_config* c, char* base, FrameProducts* fp)
 {
-    Layout L;
-    make_layout(c, nullptr, &L);
+    const Layout L = make_layout(c, nullptr);
     Bump b{base, 0};
     const int nl = ilog2(L.maxFactor) + 1;
     FrameProducts tmp;
@@ -2543,8 +2545,7 @@ size_t stream_entry(const mfsr_config* c, char* base, FrameProducts* fp)
 int stream_layout(const mfsr_config* c, int radius, StreamLayout* S)
 {
     memset(S, 0, sizeof(*S));
-    Layout L;
-    make_layout(c, nullptr, &L);
+    const Layout L = make_layout(c, nullptr);
     S->burstWs = L.total;
     S->accBytes = (size_t)12 * L.hrW * L.hrH;
     S->entryBytes = stream_entry(c, nullptr, nullptr);
@@ -2651,28 +2652,13 @@ static int stream_window(mfsr_stream* s, long long j, long long lo, long long hi
                          mfsr_stream_t stream)
 {
     mfsr_burst* b = s->b;
-    Layout& L = b->L;
-    const int nl = ilog2(L.maxFactor) + 1;
-    auto use = [&](const FrameProducts& f, bool asRef) {
-        (asRef ? L.refHalf : L.movHalf) = f.half;
-        for (int i = 0; i < nl; i++) (asRef ? L.refPyr : L.movPyr)[i] = f.pyr[i];
-        (asRef ? L.preRefPyr : L.preMovPyr) = f.prePyr;
-    };
     const FrameProducts& ref = (*s->fp)[j % s->cap];
     TRY(mfsr_burst_begin(b, s->imgOut, s->totalWeights, stream));
-    use(ref, true);
-    b->refPrepared = true;
-    int rc = mfsr_burst_set_reference(b, ref.raw, stream);
-    b->refPrepared = false;
-    if (rc) return rc;
-    for (long long k = lo; k <= hi && rc == MFSR_OK; k++) {
+    TRY(set_reference_impl(b, ref.raw, 0, b->L.hrH, stream, &ref));
+    for (long long k = lo; k <= hi; k++) {
         const FrameProducts& f = (*s->fp)[k % s->cap];
-        use(f, false);
-        b->movPrepared = true;
-        rc = mfsr_burst_add_frame(b, f.raw, k == j, s->imgOut, s->totalWeights, stream);
-        b->movPrepared = false;
+        TRY(add_frame_impl(b, f.raw, k == j, s->imgOut, s->totalWeights, false, stream, &f));
     }
-    if (rc) return rc;
     TRY(mfsr_burst_finish(b, s->imgOut, s->totalWeights, outImg, out16, stream));
     if (s->copyStream) {
         MFSR_HIP_TRY(hipEventRecord(s->evWindow[j % 64], mfsr_s(stream)));
@@ -2688,7 +2674,7 @@ extern "C" int mfsr_stream_push(mfsr_stream* s, const uint16_t* frame, mfsr_floa
     MFSR_REQUIRE(s && frame && produced);
     *produced = -1;
     mfsr_burst* b = s->b;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     const long long t = s->pushed;
     FrameProducts& f = (*s->fp)[t % s->cap];
     const size_t rawBytes = (size_t)L.W * L.H * 2;
@@ -2706,7 +2692,7 @@ extern "C" int mfsr_stream_push(mfsr_stream* s, const uint16_t* frame, mfsr_floa
     }
     // per-frame products, once per frame
     TRY(mfsr_set_cfa_pattern(s->cfg.cfa));
-    TRY(prepare_frame(b, f.raw, f.half, f.pyr, stream));
+    TRY(prepare_frame(b, f.raw, f, stream));
     if (s->cfg.preAlign)
         TRY(mfsr_preAlignPyramid((const float*)f.pyr[0].ptr, L.tw, L.th, f.pyr[0].pitch, f.prePyr, stream));
     s->pushed = t + 1;
@@ -2792,8 +2778,7 @@ int joint_pairs(int N, int ref, int (*pairs)[2])
 void joint_layout(const mfsr_config* c, JointLayout* J)
 {
     memset(J, 0, sizeof(*J));
-    Layout L;
-    make_layout(c, nullptr, &L);
+    const Layout L = make_layout(c, nullptr);
     const int last = c->levels - 1;
     J->N = c->frames;
     J->n1 = c->frames - 1;
@@ -2843,7 +2828,7 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
 {
     MFSR_REQUIRE(b && frames && jointWorkspace && imgOut && totalWeights && ((uintptr_t)jointWorkspace & 255) == 0);
     const mfsr_config& c = b->cfg;
-    Layout& L = b->L;
+    const Layout& L = b->L;
     MFSR_REQUIRE(c.frames >= 2 && c.frames - 1 <= 63);
     if (c.preAlign || !c.fused) {
         fprintf(stderr, "mfsr: the joint mode needs cfg.fused = 1 and cfg.preAlign = 0 (the minimiser sums tracked shifts only)\n");
@@ -2857,7 +2842,7 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
     }
     for (int k = 0; k < c.frames; k++) MFSR_REQUIRE(frames[k] != nullptr);
     char* base = (char*)jointWorkspace;
-    const int N = c.frames, last = c.levels - 1, nl = ilog2(L.maxFactor) + 1;
+    const int N = c.frames, last = c.levels - 1;
     std::vector<FrameProducts> fp(N);
     TRY(mfsr_set_cfa_pattern(c.cfa));
     TRY(flush_pending(b, stream, false));
@@ -2865,37 +2850,8 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
     for (int k = 0; k < N; k++) {
         stream_entry(&c, base + J.offEntries + J.entryBytes * (size_t)k, &fp[k]);
         fp[k].raw = const_cast<uint16_t*>(frames[k]);  // read only
-        TRY(prepare_frame(b, frames[k], fp[k].half, fp[k].pyr, stream));
+        TRY(prepare_frame(b, frames[k], fp[k], stream));
     }
-    auto use = [&](const FrameProducts& f, bool asRef) {
-        (asRef ? L.refHalf : L.movHalf) = f.half;
-        for (int i = 0; i < nl; i++) (asRef ? L.refPyr : L.movPyr)[i] = f.pyr[i];
-    };
-    const Img savedRefHalf = L.refHalf, savedMovHalf = L.movHalf;
-    Img savedRefPyr[8], savedMovPyr[8];
-    float* savedRefSq[kMaxLevels];
-    for (int i = 0; i < 8; i++) {
-        savedRefPyr[i] = L.refPyr[i];
-        savedMovPyr[i] = L.movPyr[i];
-    }
-    for (int l = 0; l < kMaxLevels; l++) savedRefSq[l] = L.refSq[l];
-    auto restore = [&]() {
-        L.refHalf = savedRefHalf;
-        L.movHalf = savedMovHalf;
-        for (int i = 0; i < 8; i++) {
-            L.refPyr[i] = savedRefPyr[i];
-            L.movPyr[i] = savedMovPyr[i];
-        }
-        for (int l = 0; l < kMaxLevels; l++) L.refSq[l] = savedRefSq[l];
-        b->refPrepared = b->movPrepared = false;
-        b->givenShifts = nullptr;
-        b->refStale = true;  // L.refHalf / L.refPyr no longer belong to the reference set_reference saw
-    };
-    struct Guard {
-        decltype(restore)& r;
-        ~Guard() { r(); }
-    } guard{restore};
-
     // sum(ref^2) tables of every frame that is the first of a pair
     int pairs[2 * 64][2];
     const int m = joint_pairs(N, c.reference, pairs);
@@ -2905,25 +2861,25 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
         return (float*)(base + J.offRefSq + J.refSqBytes * (size_t)k + o);
     };
     std::vector<char> haveSq(N, 0);
+    const AlignScratch& work = L.work[0];  // (every pair is tracked in the burst's first scratch, one after the other)
     // B: every pair through the coarse -> fine tracker
     const float2* hostPtrs[2 * 64];
     int hostPitches[2 * 64];
     for (int p = 0; p < m; p++) {
         const int a = pairs[p][0], bb = pairs[p][1];
-        use(fp[a], true);
-        use(fp[bb], false);
+        float* refSq[kMaxLevels] = {};
         for (int l = 0; l < c.levels; l++) {
-            L.refSq[l] = refsq_of(a, l);
+            refSq[l] = refsq_of(a, l);
             if (!haveSq[a]) {
-                const Img& ref = L.refPyr[ilog2(c.levelFactor[l])];
-                TRY(mfsr_tileSquaredSums((const float*)ref.ptr, L.refSq[l], ref.w, ref.h, ref.pitch, c.maxShift[l], c.tileSize[l],
+                const Img& ref = fp[a].pyr[ilog2(c.levelFactor[l])];
+                TRY(mfsr_tileSquaredSums((const float*)ref.ptr, refSq[l], ref.w, ref.h, ref.pitch, c.maxShift[l], c.tileSize[l],
                                          L.tcx[l], L.tcy[l], stream));
             }
         }
         haveSq[a] = 1;
-        TRY(track_tiles(b, nullptr, stream));
+        TRY(track_tiles(b, fp[a], refSq, fp[bb], work, nullptr, stream));
         char* dst = base + J.offPairShifts + J.pairBytes * (size_t)p;
-        MFSR_HIP_TRY(hipMemcpy2DAsync(dst, J.pairPitch, L.shifts[last].ptr, L.shifts[last].pitch, (size_t)J.tcx * 8, J.tcy,
+        MFSR_HIP_TRY(hipMemcpy2DAsync(dst, J.pairPitch, work.shifts[last].ptr, work.shifts[last].pitch, (size_t)J.tcx * 8, J.tcy,
                                       hipMemcpyDeviceToDevice, mfsr_s(stream)));
         hostPtrs[p] = (const float2*)dst;
         hostPitches[p] = J.pairPitch;
@@ -2948,32 +2904,29 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
     mfsr_float2* oneToOne = (mfsr_float2*)(base + J.offOneToOne);
     TRY(mfsr_minimizeShiftsFused(dA, measured, oneToOne, (float*)(base + J.offOptimT), (int*)(base + J.offStatus),
                                  (int*)(base + J.offInfo), J.tiles, N, m, stream));
-    // D, F, G per frame with the minimiser's tile shifts
-    use(fp[c.reference], true);
-    for (int l = 0; l < c.levels; l++) L.refSq[l] = refsq_of(c.reference, l);  // (unused by the chain below; kept consistent)
-    b->refPrepared = true;
-    TRY(mfsr_burst_begin(b, imgOut, totalWeights, stream));
-    TRY(mfsr_burst_set_reference(b, frames[c.reference], stream));
-    // set_reference recomputed the reference's tile sums into L.refSq: harmless
+    // D, F, G per frame with the minimiser's tile shifts.  From set_reference on the burst's reference products are
+    // fp[c.reference], in the caller's joint workspace: whatever the outcome, the next frame needs a new set_reference
+    // (set_reference also takes the reference's tile sums again, into the burst's own table: same values, never read here)
     Img optimal;
     optimal.ptr = base + J.offOptimal;
     optimal.pitch = J.pairPitch;
     optimal.w = J.tcx;
     optimal.h = J.tcy;
-    for (int k = 0; k < N; k++) {
-        if (k != c.reference) {
-            TRY(mfsr_getOptimalShifts((mfsr_float2*)optimal.ptr, oneToOne, N, J.tcx, J.tcy, optimal.pitch, c.reference, k, stream));
-            use(fp[k], false);
-            b->movPrepared = true;
-            b->givenShifts = &optimal;
+    auto fuse = [&]() -> int {
+        TRY(mfsr_burst_begin(b, imgOut, totalWeights, stream));
+        TRY(set_reference_impl(b, frames[c.reference], 0, L.hrH, stream, &fp[c.reference]));
+        for (int k = 0; k < N; k++) {
+            const bool isRef = k == c.reference;
+            if (!isRef)
+                TRY(mfsr_getOptimalShifts((mfsr_float2*)optimal.ptr, oneToOne, N, J.tcx, J.tcy, optimal.pitch, c.reference, k, stream));
+            TRY(add_frame_impl(b, frames[k], isRef, imgOut, totalWeights, false, stream, isRef ? nullptr : &fp[k],
+                               isRef ? nullptr : &optimal));
         }
-        const int rc = mfsr_burst_add_frame(b, frames[k], k == c.reference, imgOut, totalWeights, stream);
-        b->movPrepared = false;
-        b->givenShifts = nullptr;
-        if (rc) return rc;
-    }
-    TRY(mfsr_burst_flush(b, stream));
-    return MFSR_OK;
+        return mfsr_burst_flush(b, stream);
+    };
+    const int rc = fuse();
+    b->refStale = true;
+    return rc;
 }
 
 // ---- C: joint shift minimiser driver (solve -> checkForOutliers until every tile

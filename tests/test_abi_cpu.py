@@ -219,3 +219,26 @@ def test_exact_division_check_is_host_only_and_agrees_with_numpy():
         q2 = (q.astype(np.float64) + rem.astype(np.float64) * np.float64(r)).astype(np.float32)
         assert np.array_equal(q2, x / dd), d
     assert L.mfsr_exactDivisionOk(0.0) == 0 and L.mfsr_exactDivisionOk(-5.0) == 0 and L.mfsr_exactDivisionOk(3.0e8) == 0
+
+
+def _layout_cases():
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_layout.json")))["cases"]
+
+
+@pytest.mark.parametrize("case", _layout_cases(), ids=lambda c: c["name"])
+def test_workspace_sizes_are_the_recorded_ones(case):
+    """A rank's workspace size is part of the ABI contract (callers allocate by it; the stream, joint and multi-GPU sizes derive
+    from it), and where make_layout places a buffer affects timing: the three host-only size functions give, byte for byte, what
+    tests/golden/workspace_layout.json recorded for eight configurations that switch every optional block of the layout (the
+    per-frame intermediates of a group, pre-alignment, mono geometry, the unfused scratch, erosion masks, upload ring, staging)."""
+    raw = capi.lib().raw
+    cfg = capi.Config()
+    assert raw["mfsr_config_default"](ctypes.byref(cfg), case["width"], case["height"], case["frames"], case["scale"], case["mono"]) == 0
+    for k, v in case["fields"].items():
+        assert hasattr(cfg, k), k
+        setattr(cfg, k, v)
+    got = dict(burst_workspace_bytes=raw["mfsr_burst_workspace_bytes"](ctypes.byref(cfg)),
+               stream_workspace_bytes_radius1=raw["mfsr_stream_workspace_bytes"](ctypes.byref(cfg), 1),
+               joint_workspace_bytes=raw["mfsr_burst_joint_workspace_bytes"](ctypes.byref(cfg)))
+    assert got == {k: case[k] for k in got}, case["name"]

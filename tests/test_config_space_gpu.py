@@ -137,6 +137,14 @@ CASES = {
     # global pre-alignment off the warped path: the one way to mfsr_CreateFlowFieldFromTilesBase (default trackers; without
     # Lucas-Kanade iterations the oracle's own flow is off by up to a pixel, so lkIterations = 0 cannot serve here)
     "prealign_below_w": _small(124, 64, dict(preAlign=1), both=dict(BELOW, flow_base=2, flow_plain=0)),
+    # global pre-alignment ON the warped path: the frames are deferred, but pre-alignment keeps the stages from batching -- the one
+    # way to the frame-by-frame stages INSIDE a deferred batch, where every frame of the group works in its own intermediates
+    # (moved half image, pyramids, search pyramid, estimate) and only the Lucas-Kanade launches are shared
+    "prealign_warped": _case(dict(preAlign=1),
+                             batched=dict(frames_deferred=5, align_batches=2, stage_batches=0, prepare_batch=0, flow_warped=4,
+                                          flow_warped_batch=0, lk_sweep_batch=6, robust_fused=4, robust_batch=0, track_fused_up=4,
+                                          track_fused_base=4),
+                             framewise=DEFAULT_FRAMEWISE),
     # the smallest legal frame: tracking image 32 x 32, the coarse level's 32-pixel tile on a 16 x 16 image
     "smallest": _small(64, 64, both=dict(BELOW, track_fused_up=2, track_fused_base=2, track_fast_pair=4)),
     "smallest_T16": _small(64, 64, dict(levels=1, levelFactor=(1,), tileSize=(16,), maxShift=(3,)),
@@ -148,7 +156,7 @@ CASES = {
 }
 
 # the same sweep through the other drivers (host bursts, zoom windows, frame streams): HIP against HIP, bit for bit
-DRIVER_CASES = ["lk_it2", "lk_hw8", "levels3", "T24S5", "sigma_trk_6"]
+DRIVER_CASES = ["lk_it2", "lk_hw8", "levels3", "T24S5", "sigma_trk_6", "prealign_warped"]
 REFERENCE = 1
 SEED = 20240611
 
@@ -292,6 +300,64 @@ def test_path_counters_restart_with_the_burst():
     pipe.begin_burst()
     assert set(pipe.debug_paths().values()) == {0}
     pipe.close()
+
+
+def _prealign_floats(pipe):
+    """(shiftX, shiftY, rotation) of mfsr_burst_prealign_result, as their bits"""
+    import ctypes
+    import struct
+    from multi_frame_super_resolution_amd import capi
+    pa = capi.PreAlign()
+    pipe.L.burst_prealign_result(pipe._h, ctypes.byref(pa), None)
+    return struct.pack("<3f", pa.shiftX, pa.shiftY, pa.rotation)
+
+
+def test_prealign_result_names_the_last_aligned_frame():
+    """mfsr_burst_prealign_result is the estimate of the frame aligned last.  `prealign_warped` cut to 4 frames with reference 0
+    is one group of four with pairFrames = 1: the last frame is aligned at batch position 3, in the last of the group's
+    per-frame intermediates.  The call after process() returns, bit for bit, the three floats of the frame-by-frame burst
+    (pairFrames = 0), where every frame is aligned in the same buffers.  (Batch position 0 is the reference frame here, which
+    has no estimate: the group's first entry is never written in this burst, so it cannot stand in for the last one.)"""
+    import torch
+    from multi_frame_super_resolution_amd.pipeline import BurstPipeline
+    frames = [f.to("cuda:0") for f in _burst_of("prealign_warped")[0][:4]]
+    got = {}
+    for pair in (1, 0):
+        pipe = BurstPipeline(_config("prealign_warped", pair, frames=4, reference=0), torch.device("cuda:0"))
+        pipe.process(frames)
+        got[pair] = _prealign_floats(pipe)
+        if pair:
+            assert pipe.debug_paths()["align_batches"] == 1 and pipe.debug_paths()["frames_deferred"] == 4
+        pipe.close()
+    print(f"prealign_result: pairFrames=1 {np.frombuffer(got[1], np.float32)}, pairFrames=0 {np.frombuffer(got[0], np.float32)}")
+    assert got[1] == got[0]
+
+
+def test_context_survives_joint_mode():
+    """After mfsr_burst_process_joint the reference's alignment products name the caller's joint workspace: add_frame without a
+    new reference is refused (invalid argument), and an ordinary process() on the same context -- which sets its reference
+    again -- gives the u16 image, the accumulators and the weights of a fresh context, bit for bit."""
+    import torch
+    from multi_frame_super_resolution_amd import capi
+    from multi_frame_super_resolution_amd.pipeline import BurstPipeline, default_config
+    dev = torch.device("cuda:0")
+    frames = [f.to(dev) for f in _burst_of("lk_it2")[0]]     # (the 256 x 192 x 5 burst every case of that size shares)
+    cfg = default_config(256, 192, 5, 2, False)
+    cfg.reference = REFERENCE
+    fresh = BurstPipeline(cfg, dev)
+    _, o16 = fresh.process(frames)
+    want = (o16.clone().cpu(), fresh.img_out.clone().cpu(), fresh.total_weights.clone().cpu())
+    fresh.close()
+    pipe = BurstPipeline(cfg, dev)
+    pipe.process_joint(frames)
+    with pytest.raises(capi.MfsrError) as e:
+        pipe.add_frame(frames[0], False)
+    assert e.value.code == -1     # MFSR_E_INVALID
+    _, o16 = pipe.process(frames)
+    got = (o16.cpu(), pipe.img_out.cpu(), pipe.total_weights.cpu())
+    pipe.close()
+    for i, what in enumerate(("u16 image", "accumulators", "weights")):
+        assert torch.equal(_bits(want[i]), _bits(got[i])), f"after process_joint: {what} differs from a fresh context's"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
