@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -293,6 +294,32 @@ int main(int argc, char** argv)
         }
         cfg.maskErode = e[0] - '0';
     }
+    // MFSR_CCM="m00,m01,...,m22": a 3x3 colour matrix (row-major, display RGB = matrix * camera RGB); the 8-bit image then comes
+    // out of the rendered finish (mfsr_burst_set_render, MFSR_OUT_RGB8) instead of the float image + mfsr_quantize
+    bool ccm = false;
+    mfsr_render render;
+    memset(&render, 0, sizeof(render));
+    if (const char* e = getenv("MFSR_CCM")) {
+        const char* p = e;
+        bool ok = true;
+        for (int i = 0; i < 9 && ok; i++) {
+            char* end = nullptr;
+            render.matrix[i] = strtof(p, &end);
+            ok = end != p && std::isfinite(render.matrix[i]) && fabsf(render.matrix[i]) <= 256.0f && *end == (i < 8 ? ',' : '\0');
+            p = end + 1;
+        }
+        if (!ok) {
+            fprintf(stderr, "MFSR_CCM=%s: nine finite coefficients m00,m01,...,m22 with |m| <= 256 expected\n", e);
+            return 1;
+        }
+        ccm = true;
+        render.format = MFSR_OUT_RGB8;
+        render.useMatrix = 1;
+    }
+    if (ccm && gpus > 1) {
+        fprintf(stderr, "MFSR_CCM is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
     if (noiseMode && gpus > 1) {
         fprintf(stderr, "MFSR_NOISE is not supported with MFSR_GPUS > 1 (calibrate on one GPU and pass the values)\n");
         return 1;
@@ -479,6 +506,9 @@ int main(int argc, char** argv)
         }
     }
 
+    HIP_OK(hipMalloc((void**)&d8, (size_t)hrW * hrH * 3));
+    HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
+    if (ccm) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
     for (int rep = 0; rep < num_times; rep++) {
         if (rep == start_i) {
             HIP_OK(hipDeviceSynchronize());
@@ -490,8 +520,12 @@ int main(int argc, char** argv)
         for (int k : ids)
             MFSR_OK_OR_DIE(mfsr_burst_add_frame(b, dframes[k], k == reference, (mfsr_float3*)imgOut,
                                                 (mfsr_float3*)weights, nullptr));
-        MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, (mfsr_float3*)outF,
-                                         nullptr, nullptr));
+        if (ccm)  // matrix + gamma + 8-bit store in the finish launch: the float image is neither written nor read again
+            MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights,
+                                             cfg.fused ? nullptr : (mfsr_float3*)outF, (uint16_t*)d8, nullptr));
+        else
+            MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, (mfsr_float3*)outF,
+                                             nullptr, nullptr));
     }
     HIP_OK(hipDeviceSynchronize());
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -499,9 +533,7 @@ int main(int argc, char** argv)
     printf("%g FPS\n", (double)(num_images * real_times) / sec);           // :206
 
     // result -> 8-bit RGB (D2H), then sharpenImg2 on the device
-    HIP_OK(hipMalloc((void**)&d8, (size_t)hrW * hrH * 3));
-    HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
-    MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));
+    if (!ccm) MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));
     MFSR_OK_OR_DIE(mfsr_sharpenImg2(d8, d8s, hrH, hrW, 3, hrW * 3, hrW * 3, nullptr));
     HIP_OK(hipMemcpy(h8.data(), d8, h8.size(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(h8s.data(), d8s, h8s.size(), hipMemcpyDeviceToHost));

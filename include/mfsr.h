@@ -998,6 +998,59 @@ int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint16_t* const
 int mfsr_erodeMaskBatch(int nFrames, const mfsr_float4* const* in, mfsr_float4* const* out, int width, int height,
                         int inPitch, int outPitch, int radius, mfsr_stream_t stream);
 
+/* ---- rendered output: colour matrix, tone curve and a display-format store inside the finish.
+ * A render description is something a burst carries; without one every entry point produces the bits and the launches it
+ * always did.  All arithmetic is float32, no contraction.  For an HR pixel, p is the value the plain finish holds after
+ * ApplyWeighting (with the fallback) and before its gamma:
+ *   1. matrix (useMatrix != 0):  c_k = isnan(p_k) ? 0 : fminf(fmaxf(p_k, 0), 65536);
+ *      q_i = (matrix[3i] * c_0 + matrix[3i+1] * c_1) + matrix[3i+2] * c_2  (row-major, this order of operations).  The nine
+ *      coefficients must be finite with |m| <= 256 (MFSR_E_INVALID otherwise): no inf or NaN can arise.  Else q = p.
+ *   2. tone.  toneLut != NULL: toneSize + 1 floats of DEVICE memory (4-byte aligned), 1 <= toneSize = N <= 65536:
+ *      v = isnan(q) ? 0 : clamp(q, 0, 1);  t = v * (float)N;  i = min((int)t, N - 1);  f = t - (float)i;
+ *      o = lut[i] + (lut[i+1] - lut[i]) * f.   Else with applyGamma the fixed sRGB curve of mfsr_GammasRGB; else o = q.
+ *   3. quantise, Q(o, max) = (int)(clamp(o, 0, 1) * max + 0.5f), NaN -> 0:
+ *      MFSR_OUT_RGB16    three uint16_t, max 65535, 6 bytes per pixel (rows and `out` 2-byte aligned)
+ *      MFSR_OUT_RGB8     three bytes, max 255, 3 bytes per pixel (any byte alignment of `out`, any row bytes >= 3 * w)
+ *      MFSR_OUT_RGBA8    bytes R, G, B, 255; 4 bytes per pixel (`out` 4-byte aligned, row bytes a multiple of 4)
+ *      MFSR_OUT_RGB10A2  one little-endian dword r | g<<10 | b<<20 | 3u<<30, max 1023 (alignment as RGBA8)
+ * The float image receives o, so the integer output is always the quantisation of the float output.  {MFSR_OUT_RGB16, no
+ * matrix, no LUT} is bit for bit the plain finish.  The LUT stays the caller's and must stay valid until the stream has
+ * passed the finish; the matrix is copied.  reserved: write zeros.
+ * mfsr_render_row_bytes: bytes of a dense row of widthPx pixels; host arithmetic; MFSR_E_INVALID (< 0) for an unknown format
+ * or a width that is not positive.
+ * mfsr_renderImage: steps 1-3 on an existing float image (rows inRowBytes apart); outImg may be NULL or == in (in place), out
+ * may be NULL when outImg is not.  mfsr_finishRendered: mfsr_finishFusedWindow with steps 1-3 in the same launch; it evaluates
+ * the same float expressions for the fallback coordinates, so a stripe or window of it is the crop of the whole.  Both check
+ * every argument on the host before any device call (MFSR_E_INVALID), are asynchronous on `stream` and allocate nothing. */
+#define MFSR_OUT_RGB16 0
+#define MFSR_OUT_RGB8 1
+#define MFSR_OUT_RGBA8 2
+#define MFSR_OUT_RGB10A2 3
+typedef struct {
+    int32_t format;       /* MFSR_OUT_* */
+    int32_t useMatrix;    /* 0: matrix[] is ignored */
+    float matrix[9];      /* row-major 3x3, display RGB = matrix * camera RGB */
+    const float* toneLut; /* device memory, toneSize + 1 floats; NULL: cfg.applyGamma decides */
+    int32_t toneSize;
+    int32_t reserved[3];
+} mfsr_render;
+int mfsr_render_row_bytes(int format, int widthPx);
+int mfsr_renderImage(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes,
+                     int w, int h, const mfsr_render* render, int applyGamma, mfsr_stream_t stream);
+int mfsr_finishRendered(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                        int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                        int outImgRowBytes, void* out, int outRowBytes, const mfsr_render* render, int w, int h, float threshold,
+                        int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream);
+/* The burst's render description (copied; NULL = off, the default).  Between bursts only: refused (MFSR_E_INVALID) while frames
+ * are pending, as mfsr_burst_set_host_row_bytes is.  With one set, the out16 / out16Dev / out16Host arguments of
+ * mfsr_burst_finish, _finish_rows, _finish_host, mfsr_burst_process_source, mfsr_burst_process_joint, mfsr_stream_push and
+ * mfsr_stream_drain mean rendered bytes with dense rows of mfsr_render_row_bytes(format, output width): the declarations keep
+ * their type and the caller casts.  finish_host downloads rows of that size.  cfg.fused = 0 runs its chain up to
+ * ApplyWeighting and then mfsr_renderImage.  The multi-GPU layer (mfsr_dist.h) never sets one. */
+int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render);
+/* the same for every output of a frame stream (between outputs: any time, a push completes its window before it returns) */
+int mfsr_stream_set_render(mfsr_stream* s, const mfsr_render* render);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

@@ -115,6 +115,17 @@ PACK_NONE, PACK_MIPI10, PACK_MIPI12, PACK_BE10, PACK_BE12 = 0, 1, 2, 3, 4
 PACK_BITS = {PACK_MIPI10: 10, PACK_MIPI12: 12, PACK_BE10: 10, PACK_BE12: 12}
 
 
+# mfsr_render.format (include/mfsr.h): bytes per pixel 6, 3, 4, 4
+OUT_RGB16, OUT_RGB8, OUT_RGBA8, OUT_RGB10A2 = 0, 1, 2, 3
+
+
+class Render(ctypes.Structure):
+    """mfsr_render (include/mfsr.h): the render description of a burst."""
+
+    _fields_ = [("format", ctypes.c_int32), ("useMatrix", ctypes.c_int32), ("matrix", ctypes.c_float * 9),
+                ("toneLut", ctypes.c_void_p), ("toneSize", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
@@ -224,7 +235,7 @@ class _Lib:
         full = raw.__name__ if hasattr(raw, "__name__") else name
         ret = self.protos[full][0]
         if ret != "int" or full in ("mfsr_version", "mfsr_device_count", "mfsr_gaussin_filter_1D", "mfsr_burst_group_size",
-                                     "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes"):
+                                     "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes", "mfsr_render_row_bytes"):
             return raw
 
         def checked(*a):

@@ -1,0 +1,48 @@
+// finish_common.hpp -- the pixel arithmetic of the burst's finish (stage H), shared by glue.hip (k_finishFused, k_quantize,
+// k_resampleFloat3) and render.hip (k_finishRendered, k_renderImage): one definition, so that the rendered finish holds the
+// same value as the plain one before its gamma, and quantises by the same rule.
+#pragma once
+
+#include "common.hpp"
+
+// bilinear fetch of a float3 image (clamp) -- shared with finishFused
+__device__ __forceinline__ pix3 sample_pix3(const pix3* __restrict__ in, int inPitch, int inW, int inH, float u, float v)
+{
+    const TexCoord c = tex_coord<ADDR_CLAMP>(inW, inH, u, v);
+    const pix3* r0 = row_ptr(in, inPitch, c.j0);
+    const pix3* r1 = row_ptr(in, inPitch, c.j1);
+    const pix3 t00 = r0[c.i0], t10 = r0[c.i1], t01 = r1[c.i0], t11 = r1[c.i1];
+    pix3 o;
+    o.x = lerp4(t00.x, t10.x, t01.x, t11.x, c.a, c.b);
+    o.y = lerp4(t00.y, t10.y, t01.y, t11.y, c.a, c.b);
+    o.z = lerp4(t00.z, t10.z, t01.z, t11.z, c.a, c.b);
+    return o;
+}
+
+__device__ __forceinline__ int quantize1(float f, float maxOut)
+{
+    if (isnan(f)) f = 0;
+    f = fmaxf(fminf(f, 1.0f), 0.0f);
+    return (int)(f * maxOut + 0.5f);
+}
+
+__device__ __forceinline__ float apply_weight_f(float inout, float val, float w, float threshold)
+{
+    // kernel.cu:447-456
+    if (w < threshold) {
+        val += inout;
+        w += 1;
+    }
+    inout = 0;
+    if (w != 0) inout = val / w;
+    return inout;
+}
+
+__device__ __forceinline__ float gamma_f(float v)
+{
+    // kernel.cu:380-390, :407-420
+    if (isnan(v)) v = 0;
+    v = fmaxf(fminf(v, 1.0f), 0.0f);
+    if (v <= 0.0031308f) return 12.92f * v;
+    return (1.0f + 0.055f) * powf(v, 1.0f / 2.4f) - 0.055f;
+}

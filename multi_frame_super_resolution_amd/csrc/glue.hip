@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "finish_common.hpp"
 
 extern "C" const char* mfsr_error_string(int code)
 {
@@ -373,20 +374,7 @@ extern "C" int mfsr_float3ToFloat4(const mfsr_float3* in, int inPitch, mfsr_floa
     return mfsr_launch_status("float3ToFloat4");
 }
 
-// bilinear fetch of a float3 image (clamp) -- shared with finishFused
-__device__ __forceinline__ pix3 sample_pix3(const pix3* __restrict__ in, int inPitch, int inW, int inH, float u, float v)
-{
-    const TexCoord c = tex_coord<ADDR_CLAMP>(inW, inH, u, v);
-    const pix3* r0 = row_ptr(in, inPitch, c.j0);
-    const pix3* r1 = row_ptr(in, inPitch, c.j1);
-    const pix3 t00 = r0[c.i0], t10 = r0[c.i1], t01 = r1[c.i0], t11 = r1[c.i1];
-    pix3 o;
-    o.x = lerp4(t00.x, t10.x, t01.x, t11.x, c.a, c.b);
-    o.y = lerp4(t00.y, t10.y, t01.y, t11.y, c.a, c.b);
-    o.z = lerp4(t00.z, t10.z, t01.z, t11.z, c.a, c.b);
-    return o;
-}
-
+// (sample_pix3, the bilinear fetch of a float3 image, quantize1, apply_weight_f and gamma_f: finish_common.hpp)
 __global__ void __launch_bounds__(256) k_resampleFloat3(const pix3* __restrict__ in, int inPitch, int inW, int inH,
                                                        pix3* __restrict__ out, int outPitch, int outW, int outH, float u0,
                                                        float u1, float v0, float v1)
@@ -409,13 +397,6 @@ extern "C" int mfsr_resampleFloat3(const mfsr_float3* in, int inPitch, int inW, 
     hipLaunchKernelGGL(k_resampleFloat3, grid, block, 0, mfsr_s(stream), (const pix3*)in, inPitch, inW, inH, (pix3*)out,
                        outPitch, outW, outH, u0, u1, v0, v1);
     return mfsr_launch_status("resampleFloat3");
-}
-
-__device__ __forceinline__ int quantize1(float f, float maxOut)
-{
-    if (isnan(f)) f = 0;
-    f = fmaxf(fminf(f, 1.0f), 0.0f);
-    return (int)(f * maxOut + 0.5f);
 }
 
 __global__ void __launch_bounds__(256) k_quantize(const pix3* __restrict__ in, int inPitch, uint16_t* __restrict__ out16,
@@ -558,27 +539,6 @@ extern "C" int mfsr_structureTensorFused(const float* img, int imgPitch, mfsr_fl
 }
 
 // ---- H1 (+fallback resample) + H2 + quantise in one launch ---------------------------
-__device__ __forceinline__ float apply_weight_f(float inout, float val, float w, float threshold)
-{
-    // kernel.cu:447-456
-    if (w < threshold) {
-        val += inout;
-        w += 1;
-    }
-    inout = 0;
-    if (w != 0) inout = val / w;
-    return inout;
-}
-
-__device__ __forceinline__ float gamma_f(float v)
-{
-    // kernel.cu:380-390, :407-420
-    if (isnan(v)) v = 0;
-    v = fmaxf(fminf(v, 1.0f), 0.0f);
-    if (v <= 0.0031308f) return 12.92f * v;
-    return (1.0f + 0.055f) * powf(v, 1.0f / 2.4f) - 0.055f;
-}
-
 __global__ void __launch_bounds__(256)
     k_finishFused(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
                   const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,

@@ -346,6 +346,9 @@ struct mfsr_burst {
     bool freeRecorded[kMaxUploadRing + 2];
     hipStream_t freeOn[kMaxUploadRing + 2]; // the stream evFree was recorded on
     int hostRowBytes;                       // row stride of the host frames (mfsr_burst_set_host_row_bytes); 0 = dense
+    // rendered output (mfsr_burst_set_render): the out16 arguments of the finishes are bytes of render.format
+    bool renderOn;
+    mfsr_render render;
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -570,6 +573,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
         b->freeOn[i] = nullptr;
     }
     b->hostRowBytes = 0;
+    b->renderOn = false;
     b->nUnp = 0;
     b->hostEpoch = 0;
     b->evEpoch = nullptr;
@@ -1796,6 +1800,45 @@ extern "C" int mfsr_burst_flush(mfsr_burst* b, mfsr_stream_t stream)
     return flush_pending(b, stream);
 }
 
+// ---- rendered output ---------------------------------------------------------------------------------
+// bytes of a dense row of the burst's integer output: rendered bytes of the format, or uint16_t RGB
+static size_t out_row_bytes(const mfsr_burst* b)
+{
+    return b->renderOn ? (size_t)mfsr_render_row_bytes(b->render.format, out_w(b)) : (size_t)out_w(b) * 6;
+}
+
+// the rendered finish of output rows [r0, r0 + rows) (rows of the window when one is set); pointers are those of the whole
+// images, `out` holds dense rendered rows
+static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
+                                void* out, int r0, int rows, mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const int oW = out_w(b), pitch = 12 * oW;
+    const int rowBytes = (int)out_row_bytes(b);
+    const size_t off = (size_t)r0 * pitch;
+    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    return mfsr_finishRendered((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                               pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                               outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
+                               out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, &b->render, oW, rows,
+                               c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
+}
+
+extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
+{
+    MFSR_REQUIRE(b != nullptr);
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    if (!render) {
+        b->renderOn = false;
+        return MFSR_OK;
+    }
+    TRY(mfsr_render_validate(render));
+    b->render = *render;
+    b->renderOn = true;
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights,
                                  mfsr_float3* outImg, uint16_t* out16, mfsr_stream_t stream)
 {
@@ -1805,6 +1848,16 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
     const int pitch = 12 * out_w(b);
+    if (b->renderOn && c.fused) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
+    if (b->renderOn) {
+        // the unfused chain up to ApplyWeighting, then the pixel body on the float image in place of GammasRGB + quantize
+        MFSR_REQUIRE(outImg != nullptr);
+        TRY(mfsr_resampleFloat3((const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, outImg, pitch, L.hrW, L.hrH,
+                                0.0f, 1.0f, 0.0f, 1.0f, stream));
+        TRY(mfsr_ApplyWeighting(outImg, imgOut, totalWeights, L.hrW, L.hrH, pitch, c.weightThreshold, stream));
+        return mfsr_renderImage(outImg, pitch, outImg, pitch, out16, (int)out_row_bytes(b), L.hrW, L.hrH, &b->render, c.applyGamma,
+                                stream);
+    }
     if (c.fused && b->win.on) {
         return mfsr_finishFusedWindow(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
                                       0.0f, 1.0f, 0.0f, 1.0f, outImg, pitch, out16, b->win.w, b->win.h, c.weightThreshold,
@@ -1837,6 +1890,7 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     TRY(flush_pending(b, stream));
+    if (b->renderOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
     const int pitch = 12 * L.hrW;
     const size_t off = (size_t)row0 * pitch;
     return mfsr_finishFusedRows((const mfsr_float3*)((const char*)imgOut + off),
@@ -2087,7 +2141,8 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // long as the burst's compute: it has to start with the first band, or the NEXT burst's finish waits for it to leave
     // out16Dev: 18.1 instead of 17.0 ms per burst with two bands)
     const int oW = out_w(b), oH = out_h(b);  // the window's extent when one is set
-    const double outBytes = (double)oW * oH * 6.0, inBytes = (double)L.W * L.H * 2.0 * c.frames;
+    const size_t rowBytes = out_row_bytes(b);  // rendered bytes when a render is set
+    const double outBytes = (double)rowBytes * oH, inBytes = (double)L.W * L.H * 2.0 * c.frames;
     if (b->hostBusy && nBandsBusy >= 1 && nBandsBusy < nBands && outBytes <= 1.5 * inBytes) nBands = nBandsBusy;
     bool heldGroup = b->pend.n > 0 && b->pend.imgOut == imgOut && b->pend.totalWeights == totalWeights && c.fused;
     if (b->heldHas && !(heldGroup && b->held.imgOut == imgOut && b->held.totalWeights == totalWeights)) {
@@ -2095,7 +2150,6 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         heldGroup = false;
     }
     if (!heldGroup) TRY(flush_pending(b, stream));  // (another accumulator pair, or the unfused chain: nothing to pipeline)
-    const size_t rowBytes = (size_t)oW * 6;
     if (nBands == 1 && !heldGroup) {
         TRY(mfsr_burst_finish(b, imgOut, totalWeights, nullptr, out16Dev, stream));
         MFSR_HIP_TRY(hipEventRecord(b->evFinished, mfsr_s(stream)));
@@ -2156,10 +2210,14 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         }
         const size_t off = (size_t)r0 * 12 * oW;
         const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
-        TRY(mfsr_finishFusedWindow((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                   12 * oW, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                   nullptr, 12 * oW, out16Dev + (size_t)r0 * oW * 3, oW, r1 - r0, c.weightThreshold,
-                                   c.applyGamma, 65535.0f, x0, y0 + r0, L.hrW, L.hrH, stream));
+        if (b->renderOn) {
+            TRY(finish_rendered_rows(b, imgOut, totalWeights, nullptr, out16Dev, r0, r1 - r0, stream));
+        } else {
+            TRY(mfsr_finishFusedWindow((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                                       12 * oW, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                       nullptr, 12 * oW, out16Dev + (size_t)r0 * oW * 3, oW, r1 - r0, c.weightThreshold,
+                                       c.applyGamma, 65535.0f, x0, y0 + r0, L.hrW, L.hrH, stream));
+        }
         if (!b->evBand[i]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[i], hipEventDisableTiming));
         MFSR_HIP_TRY(hipEventRecord(b->evBand[i], mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[i], 0));
@@ -2722,6 +2780,12 @@ extern "C" int mfsr_stream_set_window(mfsr_stream* s, int x0, int y0, int w, int
     MFSR_REQUIRE(s != nullptr);
     MFSR_REQUIRE(s->pushed == 0);  // before the first push or after mfsr_stream_reset
     return mfsr_burst_set_window(s->b, x0, y0, w, h);  // every output's set_reference adopts it
+}
+
+extern "C" int mfsr_stream_set_render(mfsr_stream* s, const mfsr_render* render)
+{
+    MFSR_REQUIRE(s != nullptr);
+    return mfsr_burst_set_render(s->b, render);  // every output's finish renders
 }
 
 extern "C" int mfsr_stream_reset(mfsr_stream* s)

@@ -522,6 +522,77 @@ def erode_mask(masks, radius: int, out=None):
     return ret
 
 
+# ---- rendered output (include/mfsr.h, mfsr_render) --------------------------------------------------
+def tone_lut_srgb(n: int = 4096) -> torch.Tensor:
+    """The sRGB curve sampled at k/n, k = 0..n, in float64 and rounded to float32: a CPU tensor of n + 1 floats for
+    ``set_render(tone_lut=...)``."""
+    if not 1 <= n <= 65536:
+        raise ValueError("1 <= n <= 65536")
+    v = torch.arange(n + 1, dtype=torch.float64) / n
+    return torch.where(v <= 0.0031308, 12.92 * v, 1.055 * v.clamp_min(1e-300) ** (1.0 / 2.4) - 0.055).to(torch.float32)
+
+
+def render_row_bytes(fmt: int, width: int) -> int:
+    """Bytes of a dense rendered row (mfsr_render_row_bytes); ValueError for an unknown format."""
+    n = capi.lib().raw["mfsr_render_row_bytes"](int(fmt), int(width))
+    if n < 0:
+        raise ValueError(f"unknown output format {fmt} or width {width}")
+    return n
+
+
+def _render_struct(fmt: int, matrix, tone_lut, device):
+    """(capi.Render, the device tensor of the table or None): the caller keeps the tensor alive as long as the struct is used."""
+    r = capi.Render()
+    r.format = int(fmt)
+    if matrix is not None:
+        m = [float(v) for v in torch.as_tensor(matrix, dtype=torch.float64).reshape(-1).tolist()]
+        if len(m) != 9:
+            raise ValueError("matrix: 3 x 3 coefficients, row-major")
+        r.useMatrix = 1
+        r.matrix = (ctypes.c_float * 9)(*m)
+    lut = None
+    if tone_lut is not None:
+        lut = torch.as_tensor(tone_lut).to(device=device, dtype=torch.float32).contiguous()
+        if lut.dim() != 1 or not 2 <= lut.numel() <= 65537:
+            raise ValueError("tone_lut: N + 1 floats, 1 <= N <= 65536")
+        r.toneLut = lut.data_ptr()
+        r.toneSize = lut.numel() - 1
+    return r, lut
+
+
+def _render_buffer(fmt: int, h: int, w: int, device) -> torch.Tensor:
+    """The tensor typed for the format: int16 [h, w, 3], uint8 [h, w, 3], uint8 [h, w, 4] or int32 [h, w]."""
+    if fmt == capi.OUT_RGB16:
+        return torch.empty(h, w, 3, dtype=torch.int16, device=device)
+    if fmt == capi.OUT_RGB8:
+        return torch.empty(h, w, 3, dtype=torch.uint8, device=device)
+    if fmt == capi.OUT_RGBA8:
+        return torch.empty(h, w, 4, dtype=torch.uint8, device=device)
+    if fmt == capi.OUT_RGB10A2:
+        return torch.empty(h, w, dtype=torch.int32, device=device)
+    raise ValueError(f"unknown output format {fmt}")
+
+
+def render_image(img: torch.Tensor, format: int = capi.OUT_RGB16, matrix=None, tone_lut=None, apply_gamma: bool = False,
+                 want_float: bool = False):
+    """Matrix, tone curve and quantisation of an existing float image [h, w, 3] on the device (mfsr_renderImage): the pixel
+    body of the rendered finish on its own.  Returns the tensor typed for the format, and with ``want_float`` also the float
+    image the integers quantise."""
+    if not (img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 3 and img.stride(2) == 1
+            and img.stride(1) == 3):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    with torch.cuda.device(img.device):
+        r, lut = _render_struct(format, matrix, tone_lut, img.device)
+        out = _render_buffer(format, h, w, img.device)
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if want_float else None
+        capi.lib().renderImage(img.data_ptr(), img.stride(0) * 4, fl.data_ptr() if want_float else None, 12 * w, out.data_ptr(),
+                               render_row_bytes(format, w), w, h, ctypes.byref(r), 1 if apply_gamma else 0,
+                               torch.cuda.current_stream().cuda_stream)
+        del lut  # (the launch is on the current stream: the caching allocator keeps the table until the stream has passed it)
+    return (out, fl) if want_float else out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -572,6 +643,24 @@ class BurstPipeline:
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
 
+    def set_render(self, format: Optional[int] = capi.OUT_RGB16, matrix=None, tone_lut=None):
+        """Render the output inside the finish (mfsr_burst_set_render): ``matrix`` = 3 x 3 colour matrix
+        (row-major, display = matrix * camera), ``tone_lut`` = N + 1 floats of a tone curve sampled at k/N (``tone_lut_srgb``;
+        without one cfg.applyGamma decides), ``format`` = ``capi.OUT_*``.  ``finish`` and ``process*`` then return the integer
+        image as a tensor typed for the format: int16 [h, w, 3], uint8 [h, w, 3], uint8 [h, w, 4] or int32 [h, w]; the float
+        image is the rendered one.  ``format=None`` turns rendering off.  Between bursts only."""
+        out_h, out_w = self.window.aligned[3], self.window.aligned[2]
+        with torch.cuda.device(self.device):
+            if format is None:
+                self.L.burst_set_render(self._h, None)
+                self._render_lut, fmt = None, capi.OUT_RGB16
+            else:
+                r, lut = _render_struct(format, matrix, tone_lut, self.device)
+                self.L.burst_set_render(self._h, ctypes.byref(r))
+                self._render_lut, fmt = lut, int(format)   # the table is the caller's memory: alive as long as the description
+            self.out16 = _render_buffer(fmt, out_h, out_w, self.device)
+            self._out16_host = None
+
     # With cfg.pairFrames (the default) add_frame defers the warp+fuse of every other frame until its
     # partner is aligned (mfsr.h, mfsr_burst_add_frame): readers of the accumulators flush first.
     def flush(self):
@@ -608,7 +697,8 @@ class BurstPipeline:
                                self._total_weights.data_ptr(), self._stream())
 
     def finish(self, want_float: bool = True, want_u16: bool = True):
-        """(float image, u16 image) of the burst: the whole HR frame, or the rectangle given as ``window``."""
+        """(float image, u16 image) of the burst: the whole HR frame, or the rectangle given as ``window``.  After
+        ``set_render`` the second one is the rendered image, typed for its format, and the float image the one it quantises."""
         self.L.burst_finish(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(),
                             self.out_img.data_ptr() if want_float else None,
                             self.out16.data_ptr() if want_u16 else None, self._stream())
@@ -616,7 +706,7 @@ class BurstPipeline:
 
     def finish_rows(self, row0: int, rows: int) -> torch.Tensor:
         """Finish only HR rows [row0, row0+rows) (reduce-scatter mode); returns the
-        full-size u16 buffer with that stripe filled."""
+        full-size u16 buffer (after ``set_render``: the rendered image's buffer) with that stripe filled."""
         self.L.burst_finish_rows(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), None,
                                  self.out16.data_ptr(), row0, rows, self._stream())
         return self.out16
@@ -889,8 +979,9 @@ class FrameStream:
     copy stream."""
 
     def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
-                 window: Optional[Sequence[int]] = None):
-        """window: every output is that HR rectangle (see BurstPipeline)."""
+                 window: Optional[Sequence[int]] = None, render: Optional[dict] = None):
+        """window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
+        ``BurstPipeline.set_render`` (format, matrix, tone_lut): every output is rendered, typed for the format."""
         if not torch.cuda.is_available():
             raise RuntimeError("multi_frame_super_resolution_amd needs a HIP device (MI355X); there is no CPU fallback")
         self.L = capi.lib()
@@ -911,6 +1002,11 @@ class FrameStream:
             self.L.stream_create(ctypes.byref(h), ctypes.byref(cfg), radius, 1 if host_frames else 0, base, nbytes)
             self._h = h
             self.window.apply(self.L.stream_set_window, self._h)
+            if render is not None:
+                fmt = int(render.get("format", capi.OUT_RGB16))
+                r, self._render_lut = _render_struct(fmt, render.get("matrix"), render.get("tone_lut"), self.device)
+                self.L.stream_set_render(self._h, ctypes.byref(r))
+                self.out16 = _render_buffer(fmt, self.window.aligned[3], self.window.aligned[2], self.device)
 
     def close(self):
         if getattr(self, "_h", None):
