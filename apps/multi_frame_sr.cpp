@@ -29,6 +29,8 @@
 //     stderr (a status other than 0 keeps the defaults); MFSR_NOISE=alpha,beta sets the two values; one GPU only.
 //   * MFSR_MASK_ERODE=1|2 erodes every moved frame's certainty mask by that radius before the merge (ghost suppression,
 //     DESIGN.md section 2.16; 2 = the 5x5 minimum); works with MFSR_GPUS > 1.
+//   * MFSR_SHARPEN="amount[,sigma[,radius[,threshold]]]" sharpens _sr_result inside the finish (an unsharp mask on the linear
+//     value), with or without MFSR_CCM; one GPU only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -316,6 +318,40 @@ int main(int argc, char** argv)
         render.format = MFSR_OUT_RGB8;
         render.useMatrix = 1;
     }
+    // MFSR_SHARPEN="amount[,sigma[,radius[,threshold]]]": an unsharp mask inside the finish, on the linear value before the
+    // matrix and the tone curve (mfsr_burst_set_sharpen; sigma 1, radius chosen from sigma, threshold 0 by default).  The 8-bit
+    // image then comes out of the sharpened finish, with or without MFSR_CCM; _sr2_result stays the sharpenImg2 pass of it.
+    bool sharpenOn = false;
+    mfsr_sharpen sharpen;
+    memset(&sharpen, 0, sizeof(sharpen));
+    if (const char* e = getenv("MFSR_SHARPEN")) {
+        float v[4] = {0.0f, 1.0f, 0.0f, 0.0f};  // amount, sigma, radius, threshold
+        const char* p = e;
+        bool ok = true;
+        for (int n = 0; ok; n++) {
+            char* end = nullptr;
+            v[n] = strtof(p, &end);
+            ok = end != p && std::isfinite(v[n]);
+            p = end;
+            if (!ok || *p == '\0') break;
+            ok = *p == ',' && n < 3;
+            p++;
+        }
+        ok = ok && *p == '\0' && v[2] >= 0.0f && v[2] <= 4.0f && v[2] == (float)(int)v[2] &&
+             mfsr_sharpen_gaussian(v[1], (int)v[2], v[0], v[3], &sharpen) == MFSR_OK;
+        if (!ok) {
+            fprintf(stderr, "MFSR_SHARPEN=%s: amount[,sigma[,radius[,threshold]]] expected: 0 <= amount <= 16, sigma > 0, radius 0..4, "
+                            "threshold >= 0\n", e);
+            return 1;
+        }
+        sharpenOn = true;
+        render.format = MFSR_OUT_RGB8;
+    }
+    const bool rendered = ccm || sharpenOn;  // the 8-bit image comes out of the finish launch
+    if (sharpenOn && gpus > 1) {
+        fprintf(stderr, "MFSR_SHARPEN is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
     if (ccm && gpus > 1) {
         fprintf(stderr, "MFSR_CCM is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
@@ -508,7 +544,8 @@ int main(int argc, char** argv)
 
     HIP_OK(hipMalloc((void**)&d8, (size_t)hrW * hrH * 3));
     HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
-    if (ccm) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
+    if (rendered) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
+    if (sharpenOn) MFSR_OK_OR_DIE(mfsr_burst_set_sharpen(b, &sharpen));
     for (int rep = 0; rep < num_times; rep++) {
         if (rep == start_i) {
             HIP_OK(hipDeviceSynchronize());
@@ -520,7 +557,8 @@ int main(int argc, char** argv)
         for (int k : ids)
             MFSR_OK_OR_DIE(mfsr_burst_add_frame(b, dframes[k], k == reference, (mfsr_float3*)imgOut,
                                                 (mfsr_float3*)weights, nullptr));
-        if (ccm)  // matrix + gamma + 8-bit store in the finish launch: the float image is neither written nor read again
+        if (rendered)  // (sharpening +) matrix + gamma + 8-bit store in the finish launch: the float image is neither written nor
+                       // read again
             MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights,
                                              cfg.fused ? nullptr : (mfsr_float3*)outF, (uint16_t*)d8, nullptr));
         else
@@ -533,7 +571,7 @@ int main(int argc, char** argv)
     printf("%g FPS\n", (double)(num_images * real_times) / sec);           // :206
 
     // result -> 8-bit RGB (D2H), then sharpenImg2 on the device
-    if (!ccm) MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));
+    if (!rendered) MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));
     MFSR_OK_OR_DIE(mfsr_sharpenImg2(d8, d8s, hrH, hrW, 3, hrW * 3, hrW * 3, nullptr));
     HIP_OK(hipMemcpy(h8.data(), d8, h8.size(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(h8s.data(), d8s, h8s.size(), hipMemcpyDeviceToHost));

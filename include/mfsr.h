@@ -311,6 +311,8 @@ int mfsr_zeroRing_f32x4(mfsr_float4* img, int pitch, int width, int height, mfsr
  * 1 = straight kernel, v_exp_f32; 2 (default) = additionally the restructured x2
  * strip kernel where it applies (scale 2, Bayer/mono CFA, 16-byte aligned accumulators). */
 int mfsr_set_accumulate_fast_exp(int enable);
+/* the selector's value (process-wide: a test that changes it puts back what it found) */
+int mfsr_get_accumulate_fast_exp(void);
 
 /* ---- fused MI355X kernels (same results as the chains they replace, within
  *      the tolerances stated in DESIGN.md) --------------------------------- */
@@ -1050,6 +1052,69 @@ int mfsr_finishRendered(const mfsr_float3* finalImg, const mfsr_float3* weight, 
 int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render);
 /* the same for every output of a frame stream (between outputs: any time, a push completes its window before it returns) */
 int mfsr_stream_set_render(mfsr_stream* s, const mfsr_render* render);
+
+/* ---- sharpening inside the finish: an unsharp mask on the linear float value, before matrix and tone (DESIGN.md section
+ * 2.20).  Off unless asked for; without a sharpen description every entry point produces the bits and the launches it always
+ * did.  All arithmetic is float32, no contraction.  For an HR pixel and each channel alone, p is the value section 2.19 calls
+ * p (after ApplyWeighting with the fallback, before gamma):
+ *   1. s = isnan(p) ? 0 : p
+ *   2. horizontal: h(x, y) = k0 * s(x, y); then for d = 1 .. R in this order  h = h + kd * (s(x-d, y) + s(x+d, y))
+ *   3. vertical:   the same expression on h along y gives b
+ *   4. e = s - b;  a = fabsf(e) - threshold;  g = a > 0 ? copysignf(a, e) : 0;  o = s + amount * g
+ *   5. o takes the place of p in steps 1-3 of the rendered output (matrix, tone, quantise); with no render description the
+ *      steps are those of {MFSR_OUT_RGB16, no matrix, no table}.
+ * Borders replicate: a coordinate outside the valid extent reads the nearest valid pixel (the extent is stated per entry point).
+ * An inf in the input is not cleaned: s - b can then be inf - inf = NaN (which step 4 treats as "no edge": g = 0) or +-inf in
+ * the R-neighbourhood of that pixel; the quantiser maps NaN to 0 and clamps inf as it always did.
+ * Every value of a description must be finite, 0 <= radius <= 4, |taps[d]| <= 4, 0 <= amount <= 16, threshold >= 0, reserved
+ * zero-filled; otherwise MFSR_E_INVALID.  radius == 0 or amount == 0 means off wherever a description is set on a handle.
+ * mfsr_sharpen_gaussian (host only) fills a description with Gaussian taps: w_d = exp(-d^2 / (2 sigma^2)) in double, divided by
+ * w_0 + 2 sum w_d in double, rounded to float; radius == 0 chooses min(4, max(1, (int)ceilf(2.5f * sigma))); sigma > 0, finite.
+ * mfsr_sharpen_tile: the output tile one workgroup owns (the sizes at which the kernels take another path). */
+typedef struct {
+    int32_t radius;      /* R, 1..4; 0 = off */
+    float taps[5];       /* k[0] centre, k[1..R]; k[d] for d > R ignored */
+    float amount;        /* 0 <= amount <= 16; 0 = off */
+    float threshold;     /* coring, >= 0, linear units */
+    int32_t reserved[4]; /* zeros */
+} mfsr_sharpen;
+int mfsr_sharpen_gaussian(float sigma, int radius, float amount, float threshold, mfsr_sharpen* out);
+int mfsr_sharpen_validate(const mfsr_sharpen* sharpen);
+int mfsr_sharpen_tile(int* tileW, int* tileH);
+/* Steps 1-5 on an existing float image; the valid extent is the image.  Neither outImg (the float value the integers quantise)
+ * nor out may overlap `in` (MFSR_E_INVALID: a stencil cannot run in place); outImg or out may be NULL, not both.  render may be NULL
+ * ({MFSR_OUT_RGB16, no matrix, no table}).  A description that is off (radius or amount 0) is refused: call mfsr_renderImage.
+ * mfsr_finishSharpened: mfsr_finishRendered with steps 1-4 in the same launch.  Columns are valid in [0, w) of the launch, rows
+ * in [-rowsAbove, h + rowsBelow) relative to the launch's first row (0 <= rowsAbove <= rowOffset, 0 <= rowsBelow <= fullHeight
+ * - rowOffset - h): the accumulator and weight rows in that range must be complete, finalImg / weight point at the launch's
+ * first row, and neither outImg nor out may overlap those rows (MFSR_E_INVALID; unlike mfsr_finishRendered, not in place).  So a
+ * stripe with rowsAbove = rowsBelow = R is the crop of the whole in its rows, and a window (w < fullWidth)
+ * clamps at its own left and right edges.  Both check every argument on the host before any device call, are asynchronous on
+ * `stream` and allocate nothing. */
+int mfsr_sharpenImage(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes,
+                      int w, int h, const mfsr_sharpen* sharpen, const mfsr_render* render, int applyGamma, mfsr_stream_t stream);
+int mfsr_finishSharpened(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                         int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                         int outImgRowBytes, void* out, int outRowBytes, const mfsr_render* render, int w, int h, float threshold,
+                         int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight, const mfsr_sharpen* sharpen,
+                         int rowsAbove, int rowsBelow, mfsr_stream_t stream);
+/* The burst's sharpen description (copied; NULL, radius == 0 or amount == 0 = off, the default).  Between bursts only, as
+ * mfsr_burst_set_render.  With one set, every finish of the burst goes through mfsr_finishSharpened: mfsr_burst_finish,
+ * _finish_rows, _finish_host, mfsr_burst_process_source, mfsr_burst_process_joint and the outputs of a stream; without a render
+ * description the integer output stays uint16_t RGB.  cfg.fused = 0 takes the same launch (the value the fused finish holds before
+ * its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting; a stencil cannot run in place on the chain's image, and
+ * the workspace holds no second one).  mfsr_burst_finish_rows passes rowsAbove = min(R, row0) and rowsBelow = min(R, H -
+ * row0 - rows): the caller must have fused those rows of the accumulators too.  mfsr_burst_finish_host finishes band i - 1
+ * after band i has been fused (the band count, the events and the download per band stay).  A window (mfsr_burst_set_window) is
+ * the image at this level: it clamps at the window's own edges, so pixels within R of a window edge that is not a frame edge
+ * differ from the whole-frame result (the Python layer grows the window by one 16-pixel ring and crops).  The multi-GPU layer
+ * (mfsr_dist.h) never sets one. */
+int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen);
+int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharpen);
+/* *finishes = the launches of mfsr_finishSharpened this burst has made since mfsr_burst_begin (host-side, as the counters of
+ * mfsr_burst_debug_paths: 1 for a resident burst, one per band for a host burst, 0 when off).  It is
+ * not an mfsr_path: those count branches that a configuration (mfsr_config) chooses, this one follows a setter. */
+int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes);
 
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with

@@ -126,6 +126,13 @@ class Render(ctypes.Structure):
                 ("toneLut", ctypes.c_void_p), ("toneSize", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
+class Sharpen(ctypes.Structure):
+    """mfsr_sharpen (include/mfsr.h): the unsharp mask of a sharpened finish."""
+
+    _fields_ = [("radius", ctypes.c_int32), ("taps", ctypes.c_float * 5), ("amount", ctypes.c_float),
+                ("threshold", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
@@ -235,7 +242,8 @@ class _Lib:
         full = raw.__name__ if hasattr(raw, "__name__") else name
         ret = self.protos[full][0]
         if ret != "int" or full in ("mfsr_version", "mfsr_device_count", "mfsr_gaussin_filter_1D", "mfsr_burst_group_size",
-                                     "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes", "mfsr_render_row_bytes"):
+                                     "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes", "mfsr_render_row_bytes",
+                                     "mfsr_get_accumulate_fast_exp"):
             return raw
 
         def checked(*a):

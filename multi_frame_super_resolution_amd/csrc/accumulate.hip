@@ -105,6 +105,7 @@ extern "C" int mfsr_set_accumulate_fast_exp(int enable)
     g_accumulate_fast = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
     return MFSR_OK;
 }
+extern "C" int mfsr_get_accumulate_fast_exp(void) { return g_accumulate_fast; }
 
 int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,

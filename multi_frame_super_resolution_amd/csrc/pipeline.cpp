@@ -349,6 +349,10 @@ struct mfsr_burst {
     // rendered output (mfsr_burst_set_render): the out16 arguments of the finishes are bytes of render.format
     bool renderOn;
     mfsr_render render;
+    // sharpening inside the finish (mfsr_burst_set_sharpen)
+    bool sharpenOn;
+    mfsr_sharpen sharpen;
+    int sharpenedFinishes;  // launches of mfsr_finishSharpened since mfsr_burst_begin (mfsr_burst_debug_sharpened)
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -574,6 +578,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     }
     b->hostRowBytes = 0;
     b->renderOn = false;
+    b->sharpenOn = false;
+    b->sharpenedFinishes = 0;
     b->nUnp = 0;
     b->hostEpoch = 0;
     b->evEpoch = nullptr;
@@ -1788,6 +1794,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     MFSR_REQUIRE(b && imgOut && totalWeights);
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
+    b->sharpenedFinishes = 0;
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
     b->fresh.totalWeights = totalWeights;
@@ -1825,6 +1832,55 @@ static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const 
                                c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
 }
 
+// the sharpened finish of output rows [r0, r0 + rows), as finish_rendered_rows; the rows [r0 - rowsAbove, r0 + rows + rowsBelow)
+// of the accumulators are complete.  Without a render description the integer output is uint16_t RGB.
+static int finish_sharpened_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
+                                 void* out, int r0, int rows, int rowsAbove, int rowsBelow, mfsr_stream_t stream)
+{
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    const int oW = out_w(b), pitch = 12 * oW;
+    const int rowBytes = (int)out_row_bytes(b);
+    const size_t off = (size_t)r0 * pitch;
+    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    b->sharpenedFinishes++;
+    return mfsr_finishSharpened((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                                pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
+                                out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : nullptr, oW,
+                                rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, &b->sharpen, rowsAbove, rowsBelow,
+                                stream);
+}
+
+// rows of the output above / below [r0, r0 + rows) that a sharpened finish of those rows reads
+static void sharpen_reach(const mfsr_burst* b, int r0, int rows, int* above, int* below)
+{
+    const int R = b->sharpen.radius, rest = out_h(b) - r0 - rows;
+    *above = R < r0 ? R : r0;
+    *below = R < rest ? R : rest;
+}
+
+extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen)
+{
+    MFSR_REQUIRE(b != nullptr);
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    if (!sharpen) {
+        b->sharpenOn = false;
+        return MFSR_OK;
+    }
+    TRY(mfsr_sharpen_validate(sharpen));
+    b->sharpen = *sharpen;
+    b->sharpenOn = sharpen->radius != 0 && sharpen->amount != 0.0f;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes)
+{
+    MFSR_REQUIRE(b && finishes);
+    *finishes = b->sharpenedFinishes;
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
 {
     MFSR_REQUIRE(b != nullptr);
@@ -1848,6 +1904,10 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
     const int pitch = 12 * out_w(b);
+    // cfg.fused = 0 too: the stencil cannot run in place on the chain's in/out image, and the value the fused finish holds
+    // before its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting (tests/test_parity_kernels.py::
+    // test_finishFused_equals_chain), so the unfused burst's sharpened finish is this launch as well: no second HR float image
+    if (b->sharpenOn) return finish_sharpened_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
     if (b->renderOn && c.fused) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
     if (b->renderOn) {
         // the unfused chain up to ApplyWeighting, then the pixel body on the float image in place of GammasRGB + quantize
@@ -1890,6 +1950,11 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     TRY(flush_pending(b, stream));
+    if (b->sharpenOn) {
+        int above, below;
+        sharpen_reach(b, row0, rows, &above, &below);
+        return finish_sharpened_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
+    }
     if (b->renderOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
     const int pitch = 12 * L.hrW;
     const size_t off = (size_t)row0 * pitch;
@@ -2186,6 +2251,20 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // bands of output rows (window rows when a window is set: y0 is a multiple of 16, so are the bands' HR rows)
     const int tileRows = (oH + 15) / 16;
     if (nBands > tileRows) nBands = tileRows;
+    // A sharpened band reads R <= 4 rows of its neighbours: band i - 1 is finished and downloaded after band i has been fused
+    // (every band but the last is a multiple of 16 rows), the last one after the loop.  lagR0 < 0: no band waits.
+    int lagI = -1, lagR0 = -1, lagR1 = -1;
+    auto finish_lagged = [&]() -> int {
+        int above, below;
+        sharpen_reach(b, lagR0, lagR1 - lagR0, &above, &below);
+        TRY(finish_sharpened_rows(b, imgOut, totalWeights, nullptr, out16Dev, lagR0, lagR1 - lagR0, above, below, stream));
+        if (!b->evBand[lagI]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[lagI], hipEventDisableTiming));
+        MFSR_HIP_TRY(hipEventRecord(b->evBand[lagI], mfsr_s(stream)));
+        MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[lagI], 0));
+        MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)lagR0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)lagR0 * rowBytes,
+                                      rowBytes, rowBytes, (size_t)(lagR1 - lagR0), hipMemcpyDeviceToHost, b->downStream));
+        return MFSR_OK;
+    };
     for (int i = 0; i < nBands; i++) {
         const int r0 = (int)((long long)tileRows * i / nBands) * 16;
         int r1 = (int)((long long)tileRows * (i + 1) / nBands) * 16;
@@ -2208,6 +2287,13 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
                 fresh = 0;
             }
         }
+        if (b->sharpenOn) {
+            if (lagR0 >= 0) TRY(finish_lagged());
+            lagI = i;
+            lagR0 = r0;
+            lagR1 = r1;
+            continue;
+        }
         const size_t off = (size_t)r0 * 12 * oW;
         const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
         if (b->renderOn) {
@@ -2224,6 +2310,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)r0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)r0 * rowBytes,
                                       rowBytes, rowBytes, (size_t)(r1 - r0), hipMemcpyDeviceToHost, b->downStream));
     }
+    if (lagR0 >= 0) TRY(finish_lagged());
     if (heldGroup && b->copyStream) {
         // upload slots whose raw frame these launches were the last to read
         for (int gi = 0; gi < 2; gi++) {
@@ -2786,6 +2873,12 @@ extern "C" int mfsr_stream_set_render(mfsr_stream* s, const mfsr_render* render)
 {
     MFSR_REQUIRE(s != nullptr);
     return mfsr_burst_set_render(s->b, render);  // every output's finish renders
+}
+
+extern "C" int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharpen)
+{
+    MFSR_REQUIRE(s != nullptr);
+    return mfsr_burst_set_sharpen(s->b, sharpen);  // every output's finish sharpens
 }
 
 extern "C" int mfsr_stream_reset(mfsr_stream* s)

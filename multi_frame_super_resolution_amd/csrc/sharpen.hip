@@ -1,0 +1,335 @@
+// sharpen.hip -- sharpening inside the finish: a separable unsharp mask on the linear float value the
+// finish holds, before the colour matrix and the tone curve, in the same launch as the finish and the display-format store
+// (mfsr_finishSharpened), and the same tile body on an existing float image (mfsr_sharpenImage).  gfx950, wave64.
+//
+// Every step is float32 + - * with -ffp-contract=off (the Makefile), so a numpy float32 restatement is bit-exact
+// (tests/sharpen_ref.py).
+//
+// A workgroup of 256 lanes owns a kTW x kTH tile of output pixels.  It stages s (the NaN-cleaned finish value) of the tile plus
+// a halo of R at clamped coordinates in LDS, runs the horizontal pass into a second LDS array (tile columns, tile + halo rows),
+// takes the vertical pass and the coring for the lane's pixels, and hands them to render_span as its src, so the store is that
+// of the rendered finish.
+// LDS is planar (one plane per channel) with rows of kTW + 2 * kMaxR = 72 (s) and kTW = 64 (h) floats; the tile's first column
+// sits at float kMaxR of an s row whatever R is, so that column 4 * k of the tile is 16-byte aligned in both arrays.  A wave of
+// a one-pixel-per-lane format reads 64 consecutive dwords of one row (no bank conflict in either 32-lane half).  An RGB8 lane
+// owns four consecutive columns: it reads them as one float4 per row, channel and tap (ds_read_b128; four dword reads would
+// put the 32 lanes of a half on 8 banks, a 4-way conflict), computes its four pixels, and then hands them to render_span.
+// R is a runtime argument: one set of kernels.
+#include "render_common.hpp"
+
+namespace {
+
+constexpr int kTW = 64, kTH = 16, kMaxR = 4, kLanes = 256;
+constexpr int kSW = kTW + 2 * kMaxR, kSH = kTH + 2 * kMaxR;  // the staged extent at R = 4
+
+struct SharpenArgs {
+    float k[kMaxR + 1];
+    float amount, threshold;
+    int R;
+    int yLo, yHi;  // valid rows [yLo, yHi] relative to the launch's first row
+};
+
+// N consecutive floats of an LDS row; N = 4: one 16-byte read (the address is 16-byte aligned, see the file's header)
+template <int N>
+__device__ __forceinline__ void load_span(const float* p, float (&v)[N])
+{
+    if constexpr (N == 4) {
+        const float4 q = *(const float4*)p;
+        v[0] = q.x;
+        v[1] = q.y;
+        v[2] = q.z;
+        v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = p[k];
+    }
+}
+
+// The tile of the workgroup at (tileX0, tileY0): fetch(x, y) is p of section 2.20 at a valid pixel of the launch.
+template <int FORMAT, class Fetch>
+__device__ __forceinline__ void sharpen_tile(const Fetch& fetch, float (*s_s)[kSH][kSW], float (*s_h)[kSH][kTW], pix3* outImg,
+                                             int outPitch, uint8_t* out, int outRowBytes, int width, int height,
+                                             const SharpenArgs& a, const RenderArgs& r, const float* lut)
+{
+    const int tid = threadIdx.x, R = a.R;
+    const int tileX0 = blockIdx.x * kTW, tileY0 = blockIdx.y * kTH;
+    const int sw = kTW + 2 * R, sh = kTH + 2 * R;
+    // 1. s of tile + halo at clamped coordinates (what lies beyond the image's last tile is staged too: clamped, never stored)
+    for (int i = tid; i < sw * sh; i += kLanes) {
+        const int ly = i / sw, lx = i - ly * sw;
+        const int gx = min(max(tileX0 + lx - R, 0), width - 1);
+        const int gy = min(max(tileY0 + ly - R, a.yLo), a.yHi);
+        const pix3 p = fetch(gx, gy);
+        const int c0 = lx + (kMaxR - R);  // (the tile's column 0 at float kMaxR of the row)
+        s_s[0][ly][c0] = isnan(p.x) ? 0.0f : p.x;
+        s_s[1][ly][c0] = isnan(p.y) ? 0.0f : p.y;
+        s_s[2][ly][c0] = isnan(p.z) ? 0.0f : p.z;
+    }
+    __syncthreads();
+    // 2. the horizontal pass on every staged row
+    for (int i = tid; i < kTW * sh; i += kLanes) {
+        const int ly = i / kTW, lx = i - ly * kTW;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float* row = &s_s[c][ly][lx + kMaxR];
+            float h = a.k[0] * row[0];
+            for (int d = 1; d <= R; d++) h = h + a.k[d] * (row[-d] + row[d]);
+            s_h[c][ly][lx] = h;
+        }
+    }
+    __syncthreads();
+    // 3. + 4. the lane's PPL pixels of one row, then the rendered finish's span with them as its src
+    constexpr int PPL = Fmt<FORMAT>::ppl, lanesX = kTW / PPL, rowsPerPass = kLanes / lanesX;
+    const int lx0 = (tid % lanesX) * PPL, x0 = tileX0 + lx0;
+    for (int ly = tid / lanesX; ly < kTH; ly += rowsPerPass) {
+        const int y = tileY0 + ly;
+        if (x0 >= width || y >= height) continue;
+        float o[PPL][3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float s[PPL], b[PPL];
+            load_span<PPL>(&s_s[c][ly + R][lx0 + kMaxR], s);
+            load_span<PPL>(&s_h[c][ly + R][lx0], b);
+#pragma unroll
+            for (int k = 0; k < PPL; k++) b[k] = a.k[0] * b[k];
+            for (int d = 1; d <= R; d++) {
+                float up[PPL], dn[PPL];
+                load_span<PPL>(&s_h[c][ly + R - d][lx0], up);
+                load_span<PPL>(&s_h[c][ly + R + d][lx0], dn);
+#pragma unroll
+                for (int k = 0; k < PPL; k++) b[k] = b[k] + a.k[d] * (up[k] + dn[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < PPL; k++) {
+                const float e = s[k] - b[k];
+                const float t = fabsf(e) - a.threshold;
+                const float g = t > 0.0f ? copysignf(t, e) : 0.0f;
+                o[k][c] = s[k] + a.amount * g;
+            }
+        }
+        auto src = [&](int x) {
+            pix3 q = {o[0][0], o[0][1], o[0][2]};
+#pragma unroll
+            for (int k = 1; k < PPL; k++)
+                if (x - x0 == k) q = {o[k][0], o[k][1], o[k][2]};
+            return q;
+        };
+        render_span<FORMAT>(src, outImg ? row_ptr(outImg, outPitch, y) : nullptr, out ? out + (size_t)outRowBytes * (size_t)y : nullptr,
+                            x0, width, r, lut);
+    }
+}
+
+template <int FORMAT, int LDS>
+__global__ void __launch_bounds__(kLanes)
+    k_sharpenImage(const pix3* __restrict__ in, int inPitch, pix3* __restrict__ outImg, int outPitch, uint8_t* __restrict__ out,
+                   int outRowBytes, int width, int height, SharpenArgs a, RenderArgs r)
+{
+    __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
+    __shared__ __attribute__((aligned(16))) float s_s[3][kSH][kSW];
+    __shared__ __attribute__((aligned(16))) float s_h[3][kSH][kTW];
+    const float* lut = stage_lut<LDS>(r, s_lut);
+    sharpen_tile<FORMAT>([&](int x, int y) { return row_ptr(in, inPitch, y)[x]; }, s_s, s_h, outImg, outPitch, out, outRowBytes,
+                         width, height, a, r, lut);
+}
+
+template <int FORMAT, int LDS>
+__global__ void __launch_bounds__(kLanes)
+    k_finishSharpened(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
+                      const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
+                      pix3* __restrict__ outImg, int outPitch, uint8_t* __restrict__ out, int outRowBytes, int width, int height,
+                      float threshold, int rowOffset, int fullHeight, int colOffset, int fullWidth, SharpenArgs a, RenderArgs r)
+{
+    __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
+    __shared__ __attribute__((aligned(16))) float s_s[3][kSH][kSW];
+    __shared__ __attribute__((aligned(16))) float s_h[3][kSH][kTW];
+    const float* lut = stage_lut<LDS>(r, s_lut);
+    // the body of k_finishRendered's src, expression for expression; y may be negative (rowsAbove): the pointers are 64-bit
+    auto fetch = [&](int x, int y) {
+        const pix3 val = *(const pix3*)((const char*)finalImg + (long long)imgPitch * y + 12LL * x);
+        const pix3 w = *(const pix3*)((const char*)weight + (long long)imgPitch * y + 12LL * x);
+        pix3 inout = {0.0f, 0.0f, 0.0f};
+        if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
+            const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
+            const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
+            inout = sample_pix3(fallback, fbPitch, fbW, fbH, u, v);
+        }
+        inout.x = apply_weight_f(inout.x, val.x, w.x, threshold);
+        inout.y = apply_weight_f(inout.y, val.y, w.y, threshold);
+        inout.z = apply_weight_f(inout.z, val.z, w.z, threshold);
+        return inout;
+    };
+    sharpen_tile<FORMAT>(fetch, s_s, s_h, outImg, outPitch, out, outRowBytes, width, height, a, r, lut);
+}
+
+// How the tone table is read here.  Measured at 7680 x 4320 with a 4096-interval table ("Sharpened
+// finish"): with the tile's 39 KB of LDS a staged table (32 KB more) halves the workgroups per CU, and RGB8 -- the one format
+// render.hip stages it for -- takes 621 / 904 us (R = 1 / 4) staged against 412 / 538 us through the cache.  So every format
+// reads the table through the cache; MFSR_RENDER_LUT=lds still forces the staged form (A/B, and the tests run both).
+bool sharpen_lut_in_lds(const mfsr_render* r)
+{
+    const char* e = getenv("MFSR_RENDER_LUT");
+    return e && strcmp(e, "lds") == 0 && lut_in_lds(r);
+}
+
+bool sharpen_on(const mfsr_sharpen* s) { return s->radius != 0 && s->amount != 0.0f; }
+
+SharpenArgs sharpen_args(const mfsr_sharpen* s, int yLo, int yHi)
+{
+    SharpenArgs a;
+    for (int d = 0; d <= kMaxR; d++) a.k[d] = d <= s->radius ? s->taps[d] : 0.0f;
+    a.amount = s->amount;
+    a.threshold = s->threshold;
+    a.R = s->radius;
+    a.yLo = yLo;
+    a.yHi = yHi;
+    return a;
+}
+
+// without a render description: the plain finish's steps
+mfsr_render plain_render()
+{
+    mfsr_render r;
+    memset(&r, 0, sizeof(r));
+    r.format = MFSR_OUT_RGB16;
+    return r;
+}
+
+bool ranges_overlap(const void* a, long long aBytes, const void* b, long long bBytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bBytes && b0 < a0 + (uintptr_t)aBytes;
+}
+
+}  // namespace
+
+#define SHARPEN_DISPATCH(KERNEL, format, lds, ...)                                                                          \
+    do {                                                                                                                    \
+        const dim3 block(kLanes);                                                                                           \
+        const dim3 grid(mfsr_cdiv(w, kTW), mfsr_cdiv(h, kTH));                                                              \
+        switch (((format) << 1) | ((lds) ? 1 : 0)) {                                                                        \
+            case 0: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 1: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 2: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
+            case 3: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
+            case 4: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 5: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 6: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;  \
+            default: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break; \
+        }                                                                                                                   \
+    } while (0)
+
+extern "C" int mfsr_sharpen_tile(int* tileW, int* tileH)
+{
+    MFSR_REQUIRE(tileW && tileH);
+    *tileW = kTW;
+    *tileH = kTH;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_sharpen_validate(const mfsr_sharpen* s)
+{
+    MFSR_REQUIRE(s != nullptr);
+    MFSR_REQUIRE(s->radius >= 0 && s->radius <= kMaxR);
+    for (int d = 0; d <= kMaxR; d++) MFSR_REQUIRE(std::isfinite(s->taps[d]) && fabsf(s->taps[d]) <= 4.0f);
+    MFSR_REQUIRE(std::isfinite(s->amount) && s->amount >= 0.0f && s->amount <= 16.0f);
+    MFSR_REQUIRE(std::isfinite(s->threshold) && s->threshold >= 0.0f);
+    for (int i = 0; i < 4; i++) MFSR_REQUIRE(s->reserved[i] == 0);
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_sharpen_gaussian(float sigma, int radius, float amount, float threshold, mfsr_sharpen* out)
+{
+    MFSR_REQUIRE(out != nullptr);
+    MFSR_REQUIRE(std::isfinite(sigma) && sigma > 0.0f);
+    MFSR_REQUIRE(radius >= 0 && radius <= kMaxR);
+    if (radius == 0) {
+        const int r = (int)ceilf(2.5f * sigma);
+        radius = r < 1 ? 1 : (r > kMaxR ? kMaxR : r);
+    }
+    mfsr_sharpen s;
+    memset(&s, 0, sizeof(s));
+    double w[kMaxR + 1], sum = 0.0;
+    for (int d = 0; d <= radius; d++) {
+        w[d] = exp(-(double)(d * d) / (2.0 * (double)sigma * (double)sigma));
+        sum += d ? 2.0 * w[d] : w[d];
+    }
+    for (int d = 0; d <= radius; d++) s.taps[d] = (float)(w[d] / sum);
+    s.radius = radius;
+    s.amount = amount;
+    s.threshold = threshold;
+    if (int rc = mfsr_sharpen_validate(&s)) return rc;
+    *out = s;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_sharpenImage(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* out,
+                                 int outRowBytes, int w, int h, const mfsr_sharpen* sharpen, const mfsr_render* render,
+                                 int applyGamma, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(in && (outImg || out) && w > 0 && h > 0);
+    MFSR_REQUIRE((long long)inRowBytes >= 12LL * w && (inRowBytes & 3) == 0 && ((uintptr_t)in & 3) == 0);
+    if (outImg) {
+        MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0 && ((uintptr_t)outImg & 3) == 0);
+        MFSR_REQUIRE(!ranges_overlap(in, (long long)inRowBytes * (h - 1) + 12LL * w, outImg, (long long)outImgRowBytes * (h - 1) + 12LL * w));
+    }
+    if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
+    MFSR_REQUIRE(sharpen_on(sharpen));
+    const mfsr_render plain = plain_render();
+    if (!render) render = &plain;
+    if (int rc = mfsr_render_validate(render)) return rc;
+    if (out) {
+        if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
+        MFSR_REQUIRE(!ranges_overlap(in, (long long)inRowBytes * (h - 1) + 12LL * w, out,
+                                     (long long)outRowBytes * (h - 1) + (long long)bytes_per_pixel(render->format) * w));
+    }
+    const RenderArgs ra = render_args(render, applyGamma);
+    const SharpenArgs sa = sharpen_args(sharpen, 0, h - 1);
+    const bool lds = sharpen_lut_in_lds(render);
+    SHARPEN_DISPATCH(k_sharpenImage, render->format, lds, (const pix3*)in, inRowBytes, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
+                     outRowBytes, w, h, sa, ra);
+    return mfsr_launch_status("sharpenImage");
+}
+
+extern "C" int mfsr_finishSharpened(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes,
+                                    const mfsr_float3* fallback, int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0,
+                                    float v1, mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes,
+                                    const mfsr_render* render, int w, int h, float threshold, int applyGamma, int colOffset,
+                                    int rowOffset, int fullWidth, int fullHeight, const mfsr_sharpen* sharpen, int rowsAbove,
+                                    int rowsBelow, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(finalImg && weight && (outImg || out) && w > 0 && h > 0);
+    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
+    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
+    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
+    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
+    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
+    MFSR_REQUIRE(rowsAbove >= 0 && rowsAbove <= rowOffset && rowsBelow >= 0 && rowsBelow <= fullHeight - rowOffset - h);
+    if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
+    MFSR_REQUIRE(sharpen_on(sharpen));
+    const mfsr_render plain = plain_render();
+    if (!render) render = &plain;
+    if (int rc = mfsr_render_validate(render)) return rc;
+    if (out)
+        if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
+    {
+        // a stencil: no output may overlap the accumulator or weight rows the launch reads (its own and the reach's)
+        const long long readBytes = (long long)imgRowBytes * (h - 1 + rowsAbove + rowsBelow) + 12LL * w;
+        const char* fin0 = (const char*)finalImg - (long long)imgRowBytes * rowsAbove;
+        const char* wt0 = (const char*)weight - (long long)imgRowBytes * rowsAbove;
+        if (outImg) {
+            const long long n = (long long)outImgRowBytes * (h - 1) + 12LL * w;
+            MFSR_REQUIRE(!ranges_overlap(fin0, readBytes, outImg, n) && !ranges_overlap(wt0, readBytes, outImg, n));
+        }
+        if (out) {
+            const long long n = (long long)outRowBytes * (h - 1) + (long long)bytes_per_pixel(render->format) * w;
+            MFSR_REQUIRE(!ranges_overlap(fin0, readBytes, out, n) && !ranges_overlap(wt0, readBytes, out, n));
+        }
+    }
+    const RenderArgs ra = render_args(render, applyGamma);
+    const SharpenArgs sa = sharpen_args(sharpen, -rowsAbove, h - 1 + rowsBelow);
+    const bool lds = sharpen_lut_in_lds(render);
+    SHARPEN_DISPATCH(k_finishSharpened, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes,
+                     (const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
+                     outRowBytes, w, h, threshold, rowOffset, fullHeight, colOffset, fullWidth, sa, ra);
+    return mfsr_launch_status("finishSharpened");
+}

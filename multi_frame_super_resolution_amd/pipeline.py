@@ -47,18 +47,35 @@ class _Window:
 
     def __init__(self, cfg: capi.Config, window: Optional[Sequence[int]]):
         hr_w, hr_h = cfg.width * cfg.scale, cfg.height * cfg.scale
+        self._frame = (hr_w, hr_h)
         if window is None:
             self.aligned = (0, 0, hr_w, hr_h)
             self.crop = (slice(None), slice(None))
             self.on = False
+            self._rect = None
             return
         x, y, w, h = (int(v) for v in window)
-        self.aligned = align_window(cfg, x, y, w, h)
-        ax, ay, aw, ah = self.aligned
-        cx, cy = max(x, 0), max(y, 0)
-        cx1, cy1 = min(x + w, hr_w), min(y + h, hr_h)
+        self._base = align_window(cfg, x, y, w, h)
+        self._rect = (max(x, 0), max(y, 0), min(x + w, hr_w), min(y + h, hr_h))
+        self.grow(0)
+
+    def grow(self, ring: int) -> bool:
+        """The aligned window grown by ``ring`` pixels (a multiple of 16) on every side and clipped to the frame, with the crop
+        that still returns the rectangle asked for: a stencil of up to ``ring`` pixels in the finish then sees the pixels the
+        whole-frame burst sees.  Returns whether the aligned window changed."""
+        if self._rect is None:
+            return False
+        hr_w, hr_h = self._frame
+        bx, by, bw, bh = self._base
+        ax, ay = max(bx - ring, 0), max(by - ring, 0)
+        ax1, ay1 = min(bx + bw + ring, hr_w), min(by + bh + ring, hr_h)
+        aligned = (ax, ay, ax1 - ax, ay1 - ay)
+        changed = aligned != getattr(self, "aligned", None)
+        self.aligned = aligned
+        cx, cy, cx1, cy1 = self._rect
         self.crop = (slice(cy - ay, cy1 - ay), slice(cx - ax, cx1 - ax))
         self.on = self.aligned != (0, 0, hr_w, hr_h)
+        return changed
 
     def apply(self, setter, handle):
         if self.on:
@@ -593,6 +610,64 @@ def render_image(img: torch.Tensor, format: int = capi.OUT_RGB16, matrix=None, t
     return (out, fl) if want_float else out
 
 
+# ---- sharpening inside the finish (include/mfsr.h, mfsr_sharpen) ----------------------------------------
+def sharpen_gaussian(sigma: float = 1.0, radius: int = 0, amount: float = 1.0, threshold: float = 0.0) -> capi.Sharpen:
+    """A sharpen description with Gaussian taps (mfsr_sharpen_gaussian; host arithmetic, no device): radius 0 chooses
+    min(4, max(1, ceil(2.5 sigma)))."""
+    s = capi.Sharpen()
+    if capi.lib().raw["mfsr_sharpen_gaussian"](float(sigma), int(radius), float(amount), float(threshold), ctypes.byref(s)) != 0:
+        raise ValueError("sharpen: sigma > 0, 0 <= radius <= 4, 0 <= amount <= 16, threshold >= 0, all finite")
+    return s
+
+
+def _sharpen_struct(amount, sigma=1.0, radius=0, threshold=0.0, taps=None) -> Optional[capi.Sharpen]:
+    """The description of ``BurstPipeline.set_sharpen``'s arguments; None = off."""
+    if amount is None:
+        return None
+    if taps is None:
+        return sharpen_gaussian(sigma, radius, amount, threshold)
+    k = [float(v) for v in taps]
+    if not 1 <= len(k) <= 5:
+        raise ValueError("taps: k[0] (centre), k[1..R], R <= 4")
+    s = capi.Sharpen()
+    s.radius = int(radius) if radius else len(k) - 1
+    if s.radius > len(k) - 1:
+        raise ValueError("taps: radius + 1 coefficients are needed")
+    s.taps = (ctypes.c_float * 5)(*(k + [0.0] * (5 - len(k))))
+    s.amount, s.threshold = float(amount), float(threshold)
+    if capi.lib().raw["mfsr_sharpen_validate"](ctypes.byref(s)) != 0:
+        raise ValueError("sharpen: |taps| <= 4, 0 <= amount <= 16, threshold >= 0, all finite")
+    return s
+
+
+def sharpen_image(img: torch.Tensor, amount: float = 1.0, sigma: float = 1.0, radius: int = 0, threshold: float = 0.0, taps=None,
+                  format: Optional[int] = None, matrix=None, tone_lut=None, apply_gamma: bool = False, want_float: bool = True):
+    """The unsharp mask of a sharpened finish on an existing linear float image [h, w, 3] on the device (mfsr_sharpenImage),
+    followed by the steps of ``render_image`` when ``format`` is given.  Returns the float image, or with ``format`` the tensor
+    typed for it (and with ``want_float`` the pair (integers, float image))."""
+    if not (img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 3 and img.stride(2) == 1
+            and img.stride(1) == 3):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    s = _sharpen_struct(amount, sigma, radius, threshold, taps)
+    if s is None or s.radius == 0 or s.amount == 0:
+        raise ValueError("sharpen_image: amount and radius must not be 0")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    with torch.cuda.device(img.device):
+        r, lut, out = None, None, None
+        if format is not None:
+            r, lut = _render_struct(format, matrix, tone_lut, img.device)
+            out = _render_buffer(format, h, w, img.device)
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if (want_float or out is None) else None
+        capi.lib().sharpenImage(img.data_ptr(), img.stride(0) * 4, None if fl is None else fl.data_ptr(), 12 * w,
+                                None if out is None else out.data_ptr(), 0 if out is None else render_row_bytes(format, w), w, h,
+                                ctypes.byref(s), None if r is None else ctypes.byref(r), 1 if apply_gamma else 0,
+                                torch.cuda.current_stream().cuda_stream)
+        del lut
+    if out is None:
+        return fl
+    return (out, fl) if want_float else out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -623,6 +698,7 @@ class BurstPipeline:
             self._total_weights = torch.zeros_like(self._img_out)
             self.out_img = torch.empty_like(self._img_out)
             self.out16 = torch.empty(out_h, out_w, 3, dtype=torch.int16, device=self.device)
+            self._fmt = capi.OUT_RGB16   # the format of out16 (set_render)
             handle = ctypes.c_void_p()
             self.L.burst_create(ctypes.byref(handle), ctypes.byref(cfg), self._ws_ptr, nbytes)
             self._h = handle
@@ -660,6 +736,35 @@ class BurstPipeline:
                 self._render_lut, fmt = lut, int(format)   # the table is the caller's memory: alive as long as the description
             self.out16 = _render_buffer(fmt, out_h, out_w, self.device)
             self._out16_host = None
+            self._fmt = fmt
+
+    def set_sharpen(self, amount: Optional[float] = None, sigma: float = 1.0, radius: int = 0, threshold: float = 0.0, taps=None):
+        """Sharpen inside the finish (mfsr_burst_set_sharpen): an unsharp mask of strength ``amount`` on
+        the linear float value, before the colour matrix and the tone curve, in the finish's own launch.  The blur is a
+        Gaussian of ``sigma`` (``radius`` 0 = chosen from sigma, at most 4), or the symmetric ``taps`` k[0], k[1..R];
+        differences below ``threshold`` (linear units) are left alone.  ``amount=None`` turns it off.  Between bursts only.
+        With a zoom window the library works on the aligned window grown by one 16-pixel ring (clipped to the frame), so the
+        rectangle asked for stays bit for bit the crop of the whole-frame sharpened result; ``img_out`` and
+        ``total_weights`` are reallocated at that size."""
+        s = _sharpen_struct(amount, sigma, radius, threshold, taps)
+        on = s is not None and s.radius != 0 and s.amount != 0
+        with torch.cuda.device(self.device):
+            self.L.burst_set_sharpen(self._h, None if s is None else ctypes.byref(s))
+            if self.window.grow(WINDOW_GRID if on else 0):
+                self.L.burst_set_window(self._h, *self.window.aligned)
+                out_h, out_w = self.window.aligned[3], self.window.aligned[2]
+                self._img_out = torch.zeros(out_h, out_w, 3, dtype=torch.float32, device=self.device)
+                self._total_weights = torch.zeros_like(self._img_out)
+                self.out_img = torch.empty_like(self._img_out)
+                self.out16 = _render_buffer(self._fmt, out_h, out_w, self.device)
+                self._out16_host = None
+
+    def sharpened_finishes(self) -> int:
+        """Launches of mfsr_finishSharpened since ``begin_burst`` (mfsr_burst_debug_sharpened): 1 for a resident burst, one per
+        band for a host burst, 0 when sharpening is off."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_sharpened(self._h, ctypes.byref(n))
+        return n.value
 
     # With cfg.pairFrames (the default) add_frame defers the warp+fuse of every other frame until its
     # partner is aligned (mfsr.h, mfsr_burst_add_frame): readers of the accumulators flush first.
@@ -979,9 +1084,12 @@ class FrameStream:
     copy stream."""
 
     def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
-                 window: Optional[Sequence[int]] = None, render: Optional[dict] = None):
+                 window: Optional[Sequence[int]] = None, render: Optional[dict] = None, sharpen: Optional[dict] = None):
         """window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
-        ``BurstPipeline.set_render`` (format, matrix, tone_lut): every output is rendered, typed for the format."""
+        ``BurstPipeline.set_render`` (format, matrix, tone_lut): every output is rendered, typed for the format.  sharpen: the
+        keyword arguments of ``BurstPipeline.set_sharpen``: every output is sharpened inside its finish; with a window the
+        library works on the aligned window grown by one 16-pixel ring, as ``BurstPipeline`` does, so the rectangle asked for
+        is the crop of the whole-frame sharpened output."""
         if not torch.cuda.is_available():
             raise RuntimeError("multi_frame_super_resolution_amd needs a HIP device (MI355X); there is no CPU fallback")
         self.L = capi.lib()
@@ -989,6 +1097,9 @@ class FrameStream:
         self.radius = radius
         self.host_frames = host_frames
         self.window = _Window(cfg, window)
+        sharp = None if sharpen is None else _sharpen_struct(**sharpen)
+        if sharp is not None and sharp.radius != 0 and sharp.amount != 0:
+            self.window.grow(WINDOW_GRID)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.stream_workspace_bytes(ctypes.byref(cfg), radius)
         if nbytes == 0:
@@ -1007,6 +1118,8 @@ class FrameStream:
                 r, self._render_lut = _render_struct(fmt, render.get("matrix"), render.get("tone_lut"), self.device)
                 self.L.stream_set_render(self._h, ctypes.byref(r))
                 self.out16 = _render_buffer(fmt, self.window.aligned[3], self.window.aligned[2], self.device)
+            if sharp is not None:
+                self.L.stream_set_sharpen(self._h, ctypes.byref(sharp))
 
     def close(self):
         if getattr(self, "_h", None):
