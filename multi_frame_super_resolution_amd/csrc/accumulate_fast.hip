@@ -230,17 +230,20 @@ __device__ __forceinline__ void strip_pixel_sites(const float (&C)[5][3], const 
 //    four values instead of one select per tap;
 //  * exponents from pre-scaled sums: 2 adds per weight instead of mul+2 adds+mul.
 // ~245 VALU instructions per pixel instead of ~330; sums re-associated again (fma), same tolerance.
-// PARITY = true (the LDS tile kernel): mval(jt, cell, 4 * e) returns the certainty of the colour at CFA position e =
-// (y parity << 1) | x parity of mask cell `cell` on tap row jt's mask row -- the certainty texels are staged in LDS in
-// CFA-position order, so "which channel does this site see" is an LDS ADDRESS (a few integer ops per pixel) instead of
-// three v_bitop3 selects per tap row and cell.
+// EP != 0 (the LDS tile kernel): the certainties are staged in LDS in CFA-position order, so "which channel does this site
+// see" is an LDS ADDRESS (a few integer ops per pixel) instead of three v_bitop3 selects per tap row and cell.
+//  EP == 4: one float4 texel per cell; mval(jt, cell, 4 * e) returns the certainty of the colour at CFA position e =
+//   (y parity << 1) | x parity of mask cell `cell` on tap row jt's mask row.
+//  EP > 4: one dword plane per CFA position, EP bytes apart; mval(jt, cell, ey, ex) with the byte offsets of the y parity
+//   (0 or 2 * EP) and of the x parity (0 or EP) -- a value that is 0 or c flips with `^ c` whatever c is.
 // strip_pixel_w: the pixel with its 13 tap weights given (they depend on the kernel parameters only, i.e. not on the
 // frame: a kernel that takes several frames per launch computes them once per pixel).
 // RawF: void rawf(int x0, int y0, float (&s)[3][3]) -> the 3x3 raw sites whose top left one is (x0, y0).
-template <int K, int CFA, bool PARITY = false, typename RawF, typename MaskF>
+template <int K, int CFA, int EP = 0, typename RawF, typename MaskF>
 __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, const float (&w)[13], RawF rawf, MaskF mval,
                                                const StripLevels& lv, float* accP, float* accW)
 {
+    static_assert(EP == 0 || EP >= 4, "EP: 0 (by channel), 4 (texels by CFA position) or the plane stride in bytes");
     const int qx = X + sx - 2, qy = Y + sy - 2;
     const int x0 = qx >> 1, y0 = qy >> 1;
     uint32_t mbx = 0u - (uint32_t)(qx & 1), mby = 0u - (uint32_t)(qy & 1);
@@ -273,6 +276,16 @@ __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, cons
     constexpr int cellLo = (K + 0 + 2) >> 2;
     auto cidx = [](int it) { return (((K + it + 2) >> 2) == ((K + 2) >> 2)) ? 0 : 1; };
 
+    // EP > 4: plane offsets of the x parity P / ~P and of the y parities Q, ~Q, Q ^ by, ~(Q ^ by)
+    uint32_t ex[2] = {0u, 0u}, ey[4] = {0u, 0u, 0u, 0u};
+    if constexpr (EP > 4) {
+        ex[0] = mP & (uint32_t)EP;
+        ex[1] = ex[0] ^ (uint32_t)EP;
+        ey[0] = mQ & (uint32_t)(2 * EP);
+        ey[1] = ey[0] ^ (uint32_t)(2 * EP);
+        ey[2] = mY13 & (uint32_t)(2 * EP);
+        ey[3] = ey[2] ^ (uint32_t)(2 * EP);
+    }
     float C[5][3];  // per tap row: w * certainty summed per site column
 #pragma unroll
     for (int jt = 0; jt < 5; jt++) {
@@ -282,7 +295,15 @@ __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, cons
         if (jt == 1) mya = mY13;
         if (jt == 3) mya = ~mY13;
         float Ee[2], Eo[2];  // certainty of the colour on even / odd site columns (relative to x0), per cell
-        if constexpr (PARITY) {
+        if constexpr (EP > 4) {
+            // y parity Q (rows 0, 4), ~Q (row 2), Q ^ by (row 1), ~(Q ^ by) (row 3); even site columns x parity P, odd ~P
+            const uint32_t eyj = ey[(jt == 0 || jt == 4) ? 0 : (jt == 2 ? 1 : (jt == 1 ? 2 : 3))];
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                Ee[c] = mval(jt, cellLo + c, eyj, ex[0]);
+                Eo[c] = mval(jt, cellLo + c, eyj, ex[1]);
+            }
+        } else if constexpr (EP == 4) {
             // CFA position of an even site column on this tap row: y parity Q (rows 0, 4), ~Q (row 2), Q ^ by (row 1),
             // ~(Q ^ by) (row 3); x parity P.  Odd site columns: x parity flipped.
             // (as byte offsets into the texel: the address is then a plain add)
@@ -368,7 +389,7 @@ __device__ __forceinline__ void tap_pair_sums(const float (&w)[13], float (&P)[3
         for (int i = 0; i < 4; i++) P[r][i] = W_(r, i) + W_(r, i + 1);
 }
 
-template <int K, int CFA, bool PARITY = false, typename MaskF>
+template <int K, int CFA, int EP = 0, typename MaskF>
 __device__ __forceinline__ void strip_pixel(int X, int Y, int sx, int sy, float kx, float ky, float kz,
                                              const uint16_t* __restrict__ raw, int dimX, MaskF mval,
                                              const StripLevels& lv, float* accP, float* accW)
@@ -382,7 +403,7 @@ __device__ __forceinline__ void strip_pixel(int X, int Y, int sx, int sy, float 
 #pragma unroll
             for (int i = 0; i < 3; i++) s[j][i] = (float)r[j * dimX + i];
     };
-    strip_pixel_w<K, CFA, PARITY>(X, Y, sx, sy, w, rawf, mval, lv, accP, accW);
+    strip_pixel_w<K, CFA, EP>(X, Y, sx, sy, w, rawf, mval, lv, accP, accW);
 }
 
 // Frame margin (HR pixels) that the strip/tile kernels leave to k_accumulateMargin: taps of
@@ -738,6 +759,31 @@ __global__ void __launch_bounds__(256)
 #ifndef TILE_SAT_PATH
 #define TILE_SAT_PATH 1
 #endif
+// Certainty staged as four dword planes, one per CFA position ([e][mask row][frame][column]), instead of one float4 texel
+// per cell ([frame][mask row][column]): a tap row's read is then at a 4-byte lane stride (every bank once per 32 lanes for
+// a wave-uniform parity, two-way at worst) where the texel layout's 16-byte stride put the lanes on 8 of the 32 banks
+// (four-way by construction), and the frame's offset (66 dwords per frame) fits the DS offset field.  Same LDS bytes.
+// 0: texels (A/B: 6.05 against 5.75 ms per burst at 4K x 16, profiles/r05_tile_layout_ab.txt).
+#ifndef TILE_CERT_PLANES
+#define TILE_CERT_PLANES 1
+#endif
+// pixel-major loop: the raw sites as one uniform frame pointer plus one 32-bit lane offset per site row (the loads take the
+// scalar-base form, no 64-bit VALU adds); 0: three uniform row pointers plus a zero-extended lane offset (A/B: 5.76 against
+// 5.75 ms per burst, inside the spread)
+#ifndef TILE_RAW_LANE32
+#define TILE_RAW_LANE32 1
+#endif
+// ALIAS pass 1 without the 16-bit range tests on the rounded flow (implied by the 8-bit window, see there); 0: A/B (6.00 ms)
+#ifndef TILE_ALIAS_IMPLIED
+#define TILE_ALIAS_IMPLIED 1
+#endif
+// pixel-major loop: black / white levels held in VGPRs (an fp32 op with an SGPR operand issues at 0.63x the rate,
+// profiles/r02_ubench_valu_ops.txt); 0: kernel-argument SGPRs.  Off: at the 128-register cap of the four-frame kernel the six
+// registers come back as spills (32 bytes of scratch against 8, 6 720 static VALU against 6 633) and the burst takes 6.13
+// instead of 5.75 ms.
+#ifndef TILE_LEVELS_VGPR
+#define TILE_LEVELS_VGPR 0
+#endif
 // (Measured and not kept: the nine raw sites of a body loaded one body ahead -- 161 VGPRs, the address arithmetic twice:
 // 0.96 against 0.876 ms per isolated launch.  The round trip of the raw loads is already hidden.)
 // NF frames per launch (1 to 4).  Everything that does not depend on the frame is done once for
@@ -783,6 +829,20 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     float2(*sF)[FROWS][FC] = ALIAS ? (float2(*)[FROWS][FC])((char*)&sAcc[PL - 1][0][0] + sizeof(float4) * FROWS * FC)
                                    : (float2(*)[FROWS][FC]) & sFown[0][0][0];
     __shared__ float4 sM[NF][3][TILE_COLS];
+    // TILE_CERT_PLANES: the same bytes as four planes [CFA position][mask row][frame][column]
+    float(*sMp)[3][NF][TILE_COLS] = (float(*)[3][NF][TILE_COLS]) & sM[0][0][0];
+    constexpr int EP = TILE_CERT_PLANES ? 3 * NF * TILE_COLS * 4 : 4;  // strip_pixel_w's layout argument
+    // stored by CFA position (y parity << 1 | x parity), not by channel: strip_pixel_w<EP> indexes it
+    auto stage_cert = [&](int n, int r, int c, const float (&mc)[3]) {
+        if constexpr (TILE_CERT_PLANES) {
+            sMp[0][r][n][c] = mc[Cfa<CFA>::col(0, 0)];
+            sMp[1][r][n][c] = mc[Cfa<CFA>::col(0, 1)];
+            sMp[2][r][n][c] = mc[Cfa<CFA>::col(1, 0)];
+            sMp[3][r][n][c] = mc[Cfa<CFA>::col(1, 1)];
+        } else {
+            sM[n][r][c] = make_float4(mc[Cfa<CFA>::col(0, 0)], mc[Cfa<CFA>::col(0, 1)], mc[Cfa<CFA>::col(1, 0)], mc[Cfa<CFA>::col(1, 1)]);
+        }
+    };
     __shared__ uint32_t sUnsat[3][TILE_COLS];  // bit n: frame n's certainty texel is not (1, 1, 1)  (TILE_SAT_PATH)
     __shared__ __attribute__((aligned(16))) float sColA[256];  // x fraction per HR column of the tile, -1 = not on the predicted texel
     __shared__ float sRowB[4];                                 // y fraction per HR row of the tile, -1 likewise
@@ -818,8 +878,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                 for (int n = 0; n < NF; n++) {
                     const float4 m = row_ptr(fr.f[n].mask, strideMask, clampi(gy, 0, mh - 1))[clampi(gx, 0, mw - 1)];
                     const float mc[3] = {sane(m.x), sane(m.y), sane(m.z)};
-                    sM[n][r][c] = make_float4(mc[Cfa<CFA>::col(0, 0)], mc[Cfa<CFA>::col(0, 1)], mc[Cfa<CFA>::col(1, 0)],
-                                              mc[Cfa<CFA>::col(1, 1)]);
+                    stage_cert(n, r, c, mc);
                     if (!(mc[0] == 1.0f && mc[1] == 1.0f && mc[2] == 1.0f)) unsat |= 1u << n;
                 }
                 sUnsat[r][c] = unsat;
@@ -837,10 +896,8 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
             for (int n = 0; n < NF; n++) {
                 sF[n][r][c] = row_ptr((const float2*)fr.f[n].shifts.ptr, fr.f[n].shifts.pitch, fy)[fx];
                 const float4 m = row_ptr(fr.f[n].mask, strideMask, clampi(gy, 0, mh - 1))[clampi(gx, 0, mw - 1)];
-                // stored by CFA position (y parity << 1 | x parity), not by channel: strip_pixel<PARITY> indexes it
                 const float mc[3] = {sane(m.x), sane(m.y), sane(m.z)};
-                sM[n][r][c] = make_float4(mc[Cfa<CFA>::col(0, 0)], mc[Cfa<CFA>::col(0, 1)], mc[Cfa<CFA>::col(1, 0)],
-                                          mc[Cfa<CFA>::col(1, 1)]);
+                stage_cert(n, r, c, mc);
                 if (!(mc[0] == 1.0f && mc[1] == 1.0f && mc[2] == 1.0f)) unsat |= 1u << n;
             }
             sUnsat[r][c] = unsat;
@@ -976,14 +1033,19 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                 const float uy = lerp4(Ft[0][ci].y, Ft[0][ci + 1].y, Ft[1][ci].y, Ft[1][ci + 1].y, av[k], b);
                 const int sx = round2i(ux * 2.0f), sy = round2i(uy * 2.0f);
                 const int qx = X0 + k + sx - 2, qy = Y + sy - 2;
-                // as below, with the rounded flow inside 16 signed bits (wilder strips take the straight arithmetic)
-                safe = safe && (uint32_t)(sx + (1 << 15)) < (2u << 15) && (uint32_t)(sy + (1 << 15)) < (2u << 15) &&
-                       (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
+                // as below, with the rounded flow inside 16 signed bits (wilder strips take the straight arithmetic).
+                // ALIAS: that test is implied by the 8-bit window below.  dx = sx - bsx taken modulo 2^32 passes
+                // dx + 128 < 256 only if sx is congruent to bsx + d with d in [-128, 127]; |bsx| <= 32000 puts bsx + d in
+                // [-32128, 32127], far from wrapping, so the int32 sx IS that value: inside 16 signed bits.  This holds for
+                // every int32 sx, saturated conversions of wild flow included.
+                if constexpr (!(ALIAS && TILE_ALIAS_IMPLIED))
+                    safe = safe && (uint32_t)(sx + (1 << 15)) < (2u << 15) && (uint32_t)(sy + (1 << 15)) < (2u << 15);
+                safe = safe && (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
                 if constexpr (ALIAS) {
-                    const int dx = sx - bsx[n], dy = sy - bsy[n];  // (no overflow: both inside 16 bits when it matters)
-                    safe = safe && (uint32_t)(dx + 128) < 256u && (uint32_t)(dy + 128) < 256u;
-                    sxy[n][0] |= ((uint32_t)dx & 0xffu) << (8 * k);
-                    sxy[n][1] |= ((uint32_t)dy & 0xffu) << (8 * k);
+                    const uint32_t dx = (uint32_t)sx - (uint32_t)bsx[n], dy = (uint32_t)sy - (uint32_t)bsy[n];
+                    safe = safe && dx + 128u < 256u && dy + 128u < 256u;
+                    sxy[n][0] |= (dx & 0xffu) << (8 * k);
+                    sxy[n][1] |= (dy & 0xffu) << (8 * k);
                 } else {
                     sxy[n][k] = ((uint32_t)sx & 0xffffu) | ((uint32_t)sy << 16);
                 }
@@ -999,14 +1061,43 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
         // Pass 2, per pixel: weights once, then frame after frame.  What the eight pixel-frame bodies share is taken
         // here once (each body is its own divergent region, the compiler does not hoist across them): the LDS address of
         // the certainty row each tap row reads, and the raw row bases (uniform: SGPR pairs, 32-bit lane offsets).
-        const float* mrow[5];
+        // Certainty rows.  TILE_CERT_PLANES: mrowA, opaque 32-bit LDS addresses -- the compiler would otherwise split sM's own
+        // address off them and add it back per read as a constant too large for the DS offset field, where frame and cell now
+        // fit.  Else: mrow, pointers into the texel layout.  Only one of the two is set and read.
+        typedef const __attribute__((address_space(3))) char* lds_cptr;
+        const float* mrow[5] = {};
+        uint32_t mrowA[5] = {};
 #pragma unroll
-        for (int jt = 0; jt < 5; jt++) mrow[jt] = (const float*)&sM[0][((ly + jt - 2) >> 2) + 1][lx];
-        const char* rawRow[NF][3];
+        for (int jt = 0; jt < 5; jt++) {
+            if constexpr (TILE_CERT_PLANES) {
+                mrowA[jt] = (uint32_t)(uintptr_t)(lds_cptr)&sMp[0][((ly + jt - 2) >> 2) + 1][0][lx];
+                asm volatile("" : "+v"(mrowA[jt]));
+            } else {
+                mrow[jt] = (const float*)&sM[0][((ly + jt - 2) >> 2) + 1][lx];
+            }
+        }
+        // Raw sites.  TILE_RAW_LANE32: rawBase, the frames' own pointers (opaque: kept in SGPR pairs, not fetched again by
+        // every body) and rawPitch, the bytes per raw row.  Else: rawRow, one pointer per frame and site row.
+        typedef const __attribute__((address_space(1))) char* glb_cptr;
+        const char* rawRow[NF][3] = {};
+        glb_cptr rawBase[NF] = {};
+        const uint32_t rawPitch = (uint32_t)dimX * 2u;
 #pragma unroll
-        for (int n = 0; n < NF; n++)
+        for (int n = 0; n < NF; n++) {
+            if constexpr (TILE_RAW_LANE32) {
+                rawBase[n] = (glb_cptr)fr.f[n].raw;
+                asm volatile("" : "+s"(rawBase[n]));
+            } else {
 #pragma unroll
-            for (int j = 0; j < 3; j++) rawRow[n][j] = (const char*)(fr.f[n].raw + (size_t)j * dimX);
+                for (int j = 0; j < 3; j++) rawRow[n][j] = (const char*)(fr.f[n].raw + (size_t)j * dimX);
+            }
+        }
+        // Levels.  TILE_LEVELS_VGPR: a copy held in VGPRs; else lvv is lv (kernel-argument SGPRs).
+        StripLevels lvv = lv;
+        if constexpr (TILE_LEVELS_VGPR) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) asm volatile("" : "+v"(lvv.black[c]), "+v"(lvv.invWhite[c]));
+        }
         // Frames whose certainty is exactly 1 on every texel this WAVE reads (its 66 texel columns on the two mask rows
         // its tap rows touch) take strip_pixel_sat: a wave-uniform (scalar) branch per frame, bit-identical results.
         uint32_t satW = 0;
@@ -1037,20 +1128,37 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                         const uint32_t boff = (uint32_t)(y0 * dimX + x0) * 2u;  // admitted strips: x0, y0 >= 0, inside the frame
 #pragma unroll
                         for (int j = 0; j < 3; j++) {
-                            const char* rb = rawRow[n][j] + (size_t)boff;
+                            if constexpr (TILE_RAW_LANE32) {
+                                // The whole offset in 32 bits, the lane part of the address is one VGPR: off <= (y0 + 2) * dimX * 2
+                                // + 2 * x0 lies inside the frame, and tile_kernel_ok() admits frames below 4 GiB only.  Opaque,
+                                // so that base + offset is formed in the body that loads -- both bodies of a frame take the same
+                                // sites, and an address hoisted above their branch reaches the loads as a 64-bit VGPR pair.
+                                uint32_t off = boff + (uint32_t)j * rawPitch;
+                                asm volatile("" : "+v"(off));
+                                glb_cptr rb = rawBase[n] + off;
 #pragma unroll
-                            for (int i = 0; i < 3; i++) sv[j][i] = (float)*(const uint16_t*)(rb + 2 * i);
+                                for (int i = 0; i < 3; i++)
+                                    sv[j][i] = (float)*(const __attribute__((address_space(1))) uint16_t*)(rb + 2 * i);
+                            } else {
+                                const char* rb = rawRow[n][j] + (size_t)boff;
+#pragma unroll
+                                for (int i = 0; i < 3; i++) sv[j][i] = (float)*(const uint16_t*)(rb + 2 * i);
+                            }
                         }
                     };
-                    auto mval = [&](int jt, int cell, int e4) {
-                        return *(const float*)((const char*)(mrow[jt] + n * (3 * TILE_COLS * 4) + cell * 4) + e4);
+                    auto mval = [&](int jt, int cell, auto... e) {
+                        if constexpr (TILE_CERT_PLANES)
+                            return *(const __attribute__((address_space(3))) float*)(uintptr_t)((mrowA[jt] + ... + e) +
+                                                                                                 (uint32_t)(n * TILE_COLS + cell) * 4u);
+                        else
+                            return *(const float*)((const char*)(mrow[jt] + n * (3 * TILE_COLS * 4) + cell * 4) + (e + ...));
                     };
                     const int sx = ALIAS ? bsx[n] + (int)(int8_t)(sxy[n][0] >> (8 * k)) : (int)(int16_t)(sxy[n][ALIAS ? 0 : k] & 0xffffu);
                     const int sy = ALIAS ? bsy[n] + (int)(int8_t)(sxy[n][1] >> (8 * k)) : (int)sxy[n][ALIAS ? 0 : k] >> 16;
                     if (TILE_SAT_PATH && ((satW >> n) & 1u))
-                        strip_pixel_sat<k, CFA>(X0 + k, Y, sx, sy, w, P, rawf, lv, aP, accW);
+                        strip_pixel_sat<k, CFA>(X0 + k, Y, sx, sy, w, P, rawf, lvv, aP, accW);
                     else
-                        strip_pixel_w<k, CFA, true>(X0 + k, Y, sx, sy, w, rawf, mval, lv, aP, accW);
+                        strip_pixel_w<k, CFA, EP>(X0 + k, Y, sx, sy, w, rawf, mval, lvv, aP, accW);
                 }
             }
             if (k == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the staged plane-set has landed (long ago)
@@ -1114,14 +1222,17 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
 #pragma unroll
             for (int k = 0; k < 4; k++) asm volatile("" : "+v"(kxa[k]), "+v"(kya[k]), "+v"(kza[k]));
             // certainty: LDS row of the mask row that tap row jt reads = ((ly + jt - 2) >> 2) + 1; column lx + cell
-            auto mval = [&](int jt, int cell, int e4) {
+            auto mval = [&](int jt, int cell, auto... e) {
                 const int mr = ((ly + jt - 2) >> 2) + 1;
-                return *(const float*)((const char*)&sM[n][mr][lx + cell] + e4);
+                if constexpr (TILE_CERT_PLANES)
+                    return *(const float*)((const char*)&sMp[0][mr][n][lx + cell] + (e + ...));
+                else
+                    return *(const float*)((const char*)&sM[n][mr][lx + cell] + (e + ...));
             };
-            strip_pixel<0, CFA, true>(X0 + 0, Y, sx[0], sy[0], kxa[0], kya[0], kza[0], raw, dimX, mval, lv, accP, accW);
-            strip_pixel<1, CFA, true>(X0 + 1, Y, sx[1], sy[1], kxa[1], kya[1], kza[1], raw, dimX, mval, lv, accP, accW);
-            strip_pixel<2, CFA, true>(X0 + 2, Y, sx[2], sy[2], kxa[2], kya[2], kza[2], raw, dimX, mval, lv, accP, accW);
-            strip_pixel<3, CFA, true>(X0 + 3, Y, sx[3], sy[3], kxa[3], kya[3], kza[3], raw, dimX, mval, lv, accP, accW);
+            strip_pixel<0, CFA, EP>(X0 + 0, Y, sx[0], sy[0], kxa[0], kya[0], kza[0], raw, dimX, mval, lv, accP, accW);
+            strip_pixel<1, CFA, EP>(X0 + 1, Y, sx[1], sy[1], kxa[1], kya[1], kza[1], raw, dimX, mval, lv, accP, accW);
+            strip_pixel<2, CFA, EP>(X0 + 2, Y, sx[2], sy[2], kxa[2], kya[2], kza[2], raw, dimX, mval, lv, accP, accW);
+            strip_pixel<3, CFA, EP>(X0 + 3, Y, sx[3], sy[3], kxa[3], kya[3], kza[3], raw, dimX, mval, lv, accP, accW);
         }
     }
     }
@@ -1653,8 +1764,9 @@ int g_strip_use_tile = 1;  // MFSR_STRIP_TILE: 0 register-only strip kernel, 1 L
 bool tile_kernel_ok(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
 {
     const int hrW = 2 * dimX, hrH = 2 * dimY;
+    // (the tile kernels address the raw sites with 32-bit byte offsets: frames below 4 GiB)
     return kp.width == sh.width && kp.height == sh.height && kp.width * 4 == hrW && kp.height * 4 == hrH && kp.width >= 4 &&
-           (dimX % 4) == 0 && (dimY % 4) == 0 && g_strip_use_tile == 1;
+           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && g_strip_use_tile == 1;
 }
 
 // the same for fields at HR/2 (the monochrome pipeline: tracking at the raw resolution)
@@ -1662,7 +1774,7 @@ bool tile_kernel_ok_fr2(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
 {
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     return kp.width == sh.width && kp.height == sh.height && kp.width * 2 == hrW && kp.height * 2 == hrH && kp.width >= 4 &&
-           (dimX % 4) == 0 && (dimY % 4) == 0 && g_strip_use_tile == 1;
+           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && g_strip_use_tile == 1;
 }
 
 // the tile launch of a window: its first tile column (x0 / tileW) and how many it covers (whole frame: 0, all)
