@@ -328,6 +328,11 @@ int mfsr_trackTilesFused(const float* refImg, const float* movedImg, const mfsr_
  * mfsr_trackTilesFused (refSquaredSums; NULL = taken inside the tracker). */
 int mfsr_tileSquaredSums(const float* refImg, float* outValues, int imgWidth, int imgHeight, int imgPitch, int maxShift,
                          int tileSize, int tileCountX, int tileCountY, mfsr_stream_t stream);
+/* ... of every tracker level in one launch (the kernel's time is one lane's chain of tileSize^2 dependent adds, which a
+ * launch per level pays per level): levels <= 4; the arrays are host memory, one entry per level; refImgs[l] = level l's
+ * image, outValues[l] = its tileCountX[l] * tileCountY[l] sums.  Bit-identical to mfsr_tileSquaredSums level by level. */
+int mfsr_tileSquaredSumsLevels(int levels, const mfsr_tex2d* refImgs, float* const* outValues, const int* maxShift,
+                               const int* tileSize, const int* tileCountX, const int* tileCountY, mfsr_stream_t stream);
 /* D2+D3+D4 for one Lucas-Kanade iteration in one launch (LDS-tiled warp,
  * derivative and separable window sums).  Flow is double-buffered: shiftsOut
  * must not alias shiftsIn (tile halos read neighbouring tiles' flow).  outScale
@@ -349,6 +354,27 @@ int mfsr_structureTensorFused(const float* img, int imgPitch, mfsr_float3* outIm
 /* A2+A3 (+u16 -> float) in one launch through an LDS green tile */
 int mfsr_deBayerFused(const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
                       mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream);
+/* ... which also stores zero in the 2-pixel ring of the image that A2 / A3 (and mfsr_deBayerFused) leave untouched: every
+ * pixel of outImage (float3; its width and height are those of the dense raw image) is written, as a cleared image followed
+ * by mfsr_deBayerFused holds it */
+int mfsr_deBayerFusedRing(const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
+                          mfsr_stream_t stream);
+/* E1 + E2 + the separable smoothing of the tensor + E3 + the float4 packing in one launch: rows [row0, row0 + rows) of the
+ * kernel-shape field (float4, .w = 0; `field` has the size of the tracking image `tex`) hold, bit for bit, what the
+ * whole-image chain mfsr_ComputeDerivatives2Kernel -> mfsr_ComputeStructureTensor -> mfsr_separableFilter(chan = 3) ->
+ * mfsr_ComputeKernelParam -> mfsr_float3ToFloat4 gives for them (mirror for the stencil and clamp for the smoothing at the
+ * IMAGE border, whatever the window); other rows are not touched.  MFSR_E_UNSUPPORTED (nothing launched) for ntaps / 2 > 5
+ * and for images smaller than one 64 x 16 tile. */
+int mfsr_kernelParamField(mfsr_tex2d tex, mfsr_tex2d field, int row0, int rows, const float* taps, int ntaps, float Dth,
+                          float Dtr, float kDetail, float kDenoise, float kStretch, float kShrink, mfsr_stream_t stream);
+/* For tests: the number of workgroups of all mfsr_kernelParamField launches since the last reset that took their derivatives
+ * from global memory instead of the LDS tile (same bits, slower; expected: 0 for every image size).  Synchronises with the
+ * device; reset != 0 zeroes the count after reading it. */
+int mfsr_kernelParamFieldFallbacks(int* count, int reset);
+/* 1 (default): mfsr_burst_set_reference makes the reference's products with mfsr_kernelParamField,
+ * mfsr_tileSquaredSumsLevels and mfsr_deBayerFusedRing (cfg.fused = 1); 0: with the kernel chain and a cleared fallback
+ * image.  Same bits either way.  Process-wide, like mfsr_set_robustness_fast. */
+int mfsr_set_reference_fused(int enable);
 /* H1 (+fallback resample) + H2 + quantise in one launch */
 int mfsr_finishFused(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgPitch, const mfsr_float3* fallback,
                      int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
@@ -1164,6 +1190,7 @@ typedef enum {
     MFSR_PATH_ROBUST_FUSED,        /* robustness mask: mfsr_robustnessMaskFused */
     MFSR_PATH_ROBUST_BATCH,        /* ... mfsr_robustnessMaskFusedBatch, one launch per aligned group */
     MFSR_PATH_ROBUST_CHAIN,        /* ... mfsr_zeroRing_f32x4 + mfsr_ComputeRobustnessMask (cfg.fused = 0) */
+    MFSR_PATH_REF_FIELD_FUSED,     /* reference's kernel-shape field: mfsr_kernelParamField (else the five-kernel chain) */
     MFSR_PATH_COUNT
 } mfsr_path;
 /* copies min(capacity, MFSR_PATH_COUNT) counters into counts[] (indexed by mfsr_path) and stores MFSR_PATH_COUNT in *count;

@@ -360,8 +360,10 @@ extern "C" int mfsr_deBayerRedBlueKernel(int width, int height, const float* img
 #define DBF_GW (DBF_TX + 2)
 #define DBF_GH (DBF_TY + 2)
 
-__global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFused(const uint16_t* __restrict__ raw, pix3* __restrict__ outImage,
-                                                                int strideOut, int width, int height, Lvl L, int cfa)
+// RING: a thread in the 2-pixel ring of the image, which A2 / A3 leave untouched, stores zero there instead
+template <bool RING>
+__device__ __forceinline__ void debayer_fused_tile(const uint16_t* __restrict__ raw, pix3* __restrict__ outImage, int strideOut, int width,
+                                                   int height, Lvl L, int cfa)
 {
     __shared__ float s_raw[DBF_RH][DBF_RW + 1];
     __shared__ float s_g[DBF_GH][DBF_GW + 1];
@@ -406,7 +408,13 @@ __global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFused(const uint16_t*
     }
     __syncthreads();
     const int x = x0 + threadIdx.x, y = y0 + threadIdx.y;
-    if (x >= width - 2 || x < 2 || y >= height - 2 || y < 2) return;
+    if (x >= width - 2 || x < 2 || y >= height - 2 || y < 2) {
+        if (RING && x < width && y < height) {
+            pix3 z = {0.0f, 0.0f, 0.0f};
+            row_ptr(outImage, strideOut, y)[x] = z;
+        }
+        return;
+    }
     auto GREENF = [&](int xx, int yy) { return s_g[yy - y0 + 1][xx - x0 + 1]; };
 #define RAWR(xx, yy) ((RAWF(xx, yy) - L.bp[0]) * L.sc[0])
 #define RAWB(xx, yy) ((RAWF(xx, yy) - L.bp[2]) * L.sc[2])
@@ -441,6 +449,18 @@ __global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFused(const uint16_t*
     row_ptr(outImage, strideOut, y)[x] = o;
 }
 
+__global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFused(const uint16_t* __restrict__ raw, pix3* __restrict__ outImage,
+                                                                int strideOut, int width, int height, Lvl L, int cfa)
+{
+    debayer_fused_tile<false>(raw, outImage, strideOut, width, height, L, cfa);
+}
+
+__global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFusedRing(const uint16_t* __restrict__ raw, pix3* __restrict__ outImage,
+                                                                    int strideOut, int width, int height, Lvl L, int cfa)
+{
+    debayer_fused_tile<true>(raw, outImage, strideOut, width, height, L, cfa);
+}
+
 extern "C" int mfsr_deBayerFused(const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
                                  mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
 {
@@ -450,4 +470,15 @@ extern "C" int mfsr_deBayerFused(const uint16_t* raw, mfsr_float3* outImage, int
     hipLaunchKernelGGL(k_deBayerFused, grid, block, 0, mfsr_s(stream), raw, (pix3*)outImage, strideOut, width, height,
                        make_lvl(blackPoint, scale), mfsr_cfa_packed());
     return mfsr_launch_status("deBayerFused");
+}
+
+// the same with the 2-pixel ring of the image written as zero: every pixel of outImage is stored, so the image needs no clear
+extern "C" int mfsr_deBayerFusedRing(const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
+                                     mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(raw && mfsr_tex_ok(outImage, 12) && outImage.width > 4 && outImage.height > 4 && (outImage.pitch & 3) == 0);
+    dim3 block(DBF_TX, DBF_TY), grid(mfsr_cdiv(outImage.width, DBF_TX), mfsr_cdiv(outImage.height, DBF_TY));
+    hipLaunchKernelGGL(k_deBayerFusedRing, grid, block, 0, mfsr_s(stream), raw, (pix3*)outImage.ptr, outImage.pitch, outImage.width,
+                       outImage.height, make_lvl(blackPoint, scale), mfsr_cfa_packed());
+    return mfsr_launch_status("deBayerFusedRing");
 }

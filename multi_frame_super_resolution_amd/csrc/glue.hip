@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "field_math.hpp"
 #include "finish_common.hpp"
 
 extern "C" const char* mfsr_error_string(int code)
@@ -214,10 +215,10 @@ __global__ void __launch_bounds__(256) k_filter1d(const float* __restrict__ in, 
     for (int t = 0; t < taps.n; t++) {
         if (ALONG_X) {
             const int xx = clampi(x + t - c0, 0, width - 1);
-            s += taps.t[t] * row_ptr(in, inPitch, y)[xx * chan + c];
+            s = filter_step(s, taps.t[t], row_ptr(in, inPitch, y)[xx * chan + c]);
         } else {
             const int yy = clampi(y + t - c0, 0, height - 1);
-            s += taps.t[t] * row_ptr(in, inPitch, yy)[xe];
+            s = filter_step(s, taps.t[t], row_ptr(in, inPitch, yy)[xe]);
         }
     }
     row_ptr(out, outPitch, y)[xe] = s;

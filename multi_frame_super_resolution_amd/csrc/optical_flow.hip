@@ -3,6 +3,7 @@
 // reference kernel.  Behavioural spec: reference test_opencv/opticalFlow.cu.
 // The fused single-launch LK iteration lives in lk_fused.hip.
 #include "common.hpp"
+#include "field_math.hpp"
 #include "lk_math.hpp"
 
 // ---- D2: WarpingKernel (opticalFlow.cu:28-44) ---------------------------------
@@ -111,15 +112,7 @@ extern "C" int mfsr_CreateFlowFieldFromTilesBase(mfsr_float2* outImg, mfsr_tex2d
 }
 
 // ---- D3/E1: 5-point derivatives (opticalFlow.cu:97-185) -----------------------
-__device__ __forceinline__ float deriv5(const mfsr_tex2d& t, float x, float y, float dx, float dy)
-{
-    float t0 = tex1<ADDR_MIRROR>(t, x + 2.0f * dx, y + 2.0f * dy);
-    t0 -= tex1<ADDR_MIRROR>(t, x + 1.0f * dx, y + 1.0f * dy) * 8.0f;
-    t0 += tex1<ADDR_MIRROR>(t, x - 1.0f * dx, y - 1.0f * dy) * 8.0f;
-    t0 -= tex1<ADDR_MIRROR>(t, x - 2.0f * dx, y - 2.0f * dy);
-    t0 /= 12.0f;
-    return t0;
-}
+// (deriv5, the stencil itself: field_math.hpp)
 
 __global__ void __launch_bounds__(256) k_ComputeDerivatives(int width, int height, int stride, float* __restrict__ Ix,
                                                            float* __restrict__ Iy, float* __restrict__ Iz,

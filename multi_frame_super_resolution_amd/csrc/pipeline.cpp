@@ -784,7 +784,18 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     b->ref = prepared ? *prepared : L.ref;
     const FrameProducts& R = b->ref;
     if (!prepared) TRY(prepare_frame(b, rawRef, R, stream));
-    if (c.fused)
+    const bool refFused = c.fused && mfsr_reference_fused();  // (mfsr_set_reference_fused(0): the launches this replaced, A/B)
+    // MFSR_REF_FUSED_PARTS: which parts of the fused setup run, for A/B of one part (1 kernel field, 2 tile sums, 4 ring debayer)
+    static const int refParts = [] {
+        const char* e = getenv("MFSR_REF_FUSED_PARTS");
+        return e ? atoi(e) : 7;
+    }();
+    const bool fusedField = refFused && (refParts & 1), fusedSums = refFused && (refParts & 2), fusedRing = refFused && (refParts & 4);
+    if (fusedSums) {
+        mfsr_tex2d lv[kMaxLevels];
+        for (int l = 0; l < c.levels; l++) lv[l] = as_tex(R.pyr[ilog2(c.levelFactor[l])]);
+        TRY(mfsr_tileSquaredSumsLevels(c.levels, lv, L.refSq, c.maxShift, c.tileSize, L.tcx, L.tcy, stream));
+    } else if (c.fused)
         for (int l = 0; l < c.levels; l++) {
             const Img& ref = R.pyr[ilog2(c.levelFactor[l])];
             TRY(mfsr_tileSquaredSums((const float*)ref.ptr, L.refSq[l], ref.w, ref.h, ref.pitch, c.maxShift[l], c.tileSize[l],
@@ -817,7 +828,9 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     // kernel.cu:766-772): a tensor that differs in its last bits (mfsr_structureTensorFused reads the texels directly
     // instead of blending them with the ~1e-7 weights an exact-float bilinear fetch at a texel centre has) moves the tap
     // exponents by up to 0.5 there, i.e. the accumulators by 1e-3 relative -- measured, tools/parity_audit.py.  So the
-    // fused pipeline also takes the bit-exact two-kernel chain here (+ ~10 us per burst).
+    // field is made with the arithmetic of the bit-exact kernel chain (field_math.hpp): in one launch by
+    // mfsr_kernelParamField, which keeps the five intermediates in LDS, or, where that kernel declines (more than 11
+    // tensor taps, an image below one of its tiles, mfsr_set_reference_fused(0), cfg.fused = 0), by the chain itself.
     {
         // field rows the fuse of HR rows [hrRow0, hrRow1) samples: floor((Y + .5) * th / hrH - .5) and the next one; the
         // smoothing reads taps / 2 more on either side (clamped at the IMAGE border only: the window carries that halo)
@@ -830,18 +843,28 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
             f1 = f1 > L.th ? L.th : f1;
         }
         const int fr = f1 - f0;
-        const Img& ix = L.Ix;
-        const Img& iy = L.Iy;
-        auto rows = [&](const Img& im) { return (char*)im.ptr + (size_t)f0 * im.pitch; };
-        TRY(mfsr_ComputeDerivatives2Rows(L.tw, L.th, ix.pitch, (float*)ix.ptr, (float*)iy.ptr, as_tex(R.pyr[0]), f0, fr, es));
-        TRY(mfsr_ComputeStructureTensor((const float*)rows(ix), (const float*)rows(iy), (mfsr_float3*)rows(L.tensor), L.tw, fr, ix.pitch,
-                                        L.tensor.pitch, es));
-        TRY(mfsr_separableFilter((const float*)rows(L.tensor), L.tensor.pitch, (float*)rows(L.tensorTmp), (float*)rows(L.tensorSm),
-                                 L.tensorSm.pitch, L.tw, fr, 3, b->tensorTaps, b->ntensorTaps, es));
-        TRY(mfsr_ComputeKernelParam((mfsr_float3*)rows(L.tensorSm), L.tw, fr, L.tensorSm.pitch, c.Dth, c.Dtr, c.kDetail, c.kDenoise,
-                                    c.kStretch, c.kShrink, es));
-        TRY(mfsr_float3ToFloat4((const mfsr_float3*)rows(L.tensorSm), L.tensorSm.pitch, (mfsr_float4*)rows(L.kparam4), L.kparam4.pitch,
-                                L.tw, fr, es));
+        int rcField = MFSR_E_UNSUPPORTED;
+        if (fusedField) {
+            rcField = mfsr_kernelParamField(as_tex(R.pyr[0]), as_tex(L.kparam4), f0, fr, b->tensorTaps, b->ntensorTaps, c.Dth, c.Dtr,
+                                            c.kDetail, c.kDenoise, c.kStretch, c.kShrink, es);
+            if (rcField != MFSR_E_UNSUPPORTED) TRY(rcField);
+        }
+        if (rcField == MFSR_OK) {
+            b->paths[MFSR_PATH_REF_FIELD_FUSED]++;
+        } else {
+            const Img& ix = L.Ix;
+            const Img& iy = L.Iy;
+            auto rows = [&](const Img& im) { return (char*)im.ptr + (size_t)f0 * im.pitch; };
+            TRY(mfsr_ComputeDerivatives2Rows(L.tw, L.th, ix.pitch, (float*)ix.ptr, (float*)iy.ptr, as_tex(R.pyr[0]), f0, fr, es));
+            TRY(mfsr_ComputeStructureTensor((const float*)rows(ix), (const float*)rows(iy), (mfsr_float3*)rows(L.tensor), L.tw, fr,
+                                            ix.pitch, L.tensor.pitch, es));
+            TRY(mfsr_separableFilter((const float*)rows(L.tensor), L.tensor.pitch, (float*)rows(L.tensorTmp),
+                                     (float*)rows(L.tensorSm), L.tensorSm.pitch, L.tw, fr, 3, b->tensorTaps, b->ntensorTaps, es));
+            TRY(mfsr_ComputeKernelParam((mfsr_float3*)rows(L.tensorSm), L.tw, fr, L.tensorSm.pitch, c.Dth, c.Dtr, c.kDetail,
+                                        c.kDenoise, c.kStretch, c.kShrink, es));
+            TRY(mfsr_float3ToFloat4((const mfsr_float3*)rows(L.tensorSm), L.tensorSm.pitch, (mfsr_float4*)rows(L.kparam4),
+                                    L.kparam4.pitch, L.tw, fr, es));
+        }
     }
 
     // A2 + A3: debayered reference = fallback image of ApplyWeighting (finish resamples it bilinearly: raw rows Y / s +- 1;
@@ -857,9 +880,16 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
         r1 = r1 > L.H ? L.H : r1;
     }
     char* fb = (char*)L.fallback.ptr + (size_t)r0 * L.fallback.pitch;
-    MFSR_HIP_TRY(hipMemsetAsync(fb, 0, (size_t)L.fallback.pitch * (r1 - r0), mfsr_s(es)));
+    // (the debayer kernels leave the 2-pixel ring of their image untouched: mfsr_deBayerFusedRing stores its zeros itself, the
+    // others take them from a cleared image.  The clear also zeroed the pitch padding behind each row; without it the padding
+    // keeps what the workspace held.  Nothing reads it: every consumer of the fallback image addresses pixels below L.W.)
+    if (!fusedRing) MFSR_HIP_TRY(hipMemsetAsync(fb, 0, (size_t)L.fallback.pitch * (r1 - r0), mfsr_s(es)));
     if (c.fused) {
-        TRY(mfsr_deBayerFused(rawRef + (size_t)r0 * L.W, (mfsr_float3*)fb, L.fallback.pitch, L.W, r1 - r0, bp, sc, es));
+        if (fusedRing) {
+            const mfsr_tex2d fbt = {fb, L.fallback.pitch, L.W, r1 - r0};
+            TRY(mfsr_deBayerFusedRing(rawRef + (size_t)r0 * L.W, fbt, bp, sc, es));
+        } else
+            TRY(mfsr_deBayerFused(rawRef + (size_t)r0 * L.W, (mfsr_float3*)fb, L.fallback.pitch, L.W, r1 - r0, bp, sc, es));
         if (es != stream) {
             MFSR_HIP_TRY(hipEventRecord(b->evRefDone, b->fuseStream));
             b->refOnFuse = true;

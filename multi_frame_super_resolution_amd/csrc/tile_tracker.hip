@@ -16,6 +16,7 @@
 
 #include <cstring>
 #include "common.hpp"
+#include "field_math.hpp"
 
 // ---- wavefront reductions -----------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v)
@@ -476,8 +477,7 @@ __global__ void __launch_bounds__(256) k_ComputeStructureTensor(const float* __r
     if (pxX >= imgWidth || pxY >= imgHeight) return;
     const float dx = row_ptr(imgDx, imgDxDyPitch, pxY)[pxX];
     const float dy = row_ptr(imgDy, imgDxDyPitch, pxY)[pxX];
-    pix3 val = {dx * dx, dy * dy, dx * dy};
-    row_ptr(outImg, imgOutPitch, pxY)[pxX] = val;
+    row_ptr(outImg, imgOutPitch, pxY)[pxX] = tensor_products(dx, dy);
 }
 
 extern "C" int mfsr_ComputeStructureTensor(const float* imgDx, const float* imgDy, mfsr_float3* outImg, int imgWidth,
@@ -493,41 +493,7 @@ extern "C" int mfsr_ComputeStructureTensor(const float* imgDx, const float* imgD
 }
 
 // ---- E3: ComputeKernelParam (kernel.cu:718-790) --------------------------------
-__device__ __forceinline__ pix3 kernel_param(pix3 grad, float Dth, float Dtr, float kDetail, float kDenoise,
-                                             float kStretch, float kShrink)
-{
-    const float a11 = grad.x, a22 = grad.y, a12 = grad.z;
-    const float help = sqrtf((a22 - a11) * (a22 - a11) + 4.0f * a12 * a12);
-    float c = 2.0f * a12;
-    float s = a22 - a11 + help;
-    const float norm = sqrtf(c * c + s * s);
-    if (norm > 0) {
-        c /= norm;
-        s /= norm;
-    } else {
-        c = 1;
-        s = 0;
-    }
-    const float lam1 = (a11 + a22 + help) / 2.0f;
-    const float lam2 = (a11 + a22 - help) / 2.0f;
-    const float A = 1 + sqrtf((lam1 - lam2) * (lam1 - lam2) / ((lam1 + lam2) * (lam1 + lam2)));
-    float D = 1 - sqrtf(lam1) / Dtr + Dth;
-    D = fmaxf(fminf(1.0f, D), 0.0f);
-    const float k1h = kDetail * kStretch * A;
-    const float k2h = kDetail / kShrink * A;
-    float k1 = ((1.0f - D) * k1h + D * kDetail * kDenoise);
-    float k2 = ((1.0f - D) * k2h + D * kDetail * kDenoise);
-    k1 *= k1;
-    k2 *= k2;
-    const float x2 = c, y2 = s, x1 = s, y1 = -c;
-    const float b11 = k1 * x1 * x1 + x2 * x2 * k2;
-    const float b12 = k1 * x1 * y1 + x2 * y2 * k2;
-    const float b22 = k1 * y1 * y1 + y2 * y2 * k2;
-    const float det = b11 * b22 - b12 * b12 + 0.0000000001f;
-    pix3 kernel = {b22 / det, b11 / det, -b12 / det};
-    return kernel;
-}
-
+// (kernel_param, the arithmetic of one pixel: field_math.hpp)
 __global__ void __launch_bounds__(256) k_ComputeKernelParam(pix3* __restrict__ kernelImg, int imgWidth, int imgHeight,
                                                            int imgOutPitch, float Dth, float Dtr, float kDetail,
                                                            float kDenoise, float kStretch, float kShrink)
@@ -1105,13 +1071,10 @@ __global__ void __launch_bounds__((TrkFast<T, S, TPW>::threads))
 }
 
 // sum(ref^2) per tile in the serial row-major order of squaredSum' (B3): once per reference frame
-__global__ void __launch_bounds__(64)
-    k_tileSquaredSums(const float* __restrict__ refImg, float* __restrict__ out, int imgWidth, int imgHeight, int imgPitch,
-                      int maxShift, int tileSize, int tileCountX, int tileCountY)
+__device__ __forceinline__ void tile_squared_sum(float* s_mem, const float* __restrict__ refImg, float* __restrict__ out, int imgWidth,
+                                                 int imgHeight, int imgPitch, int maxShift, int tileSize, int tileCountX, int tileIdx)
 {
-    extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int T = tileSize, S = maxShift;
-    const int tileIdx = blockIdx.x;
     const int tileIdxY = tileIdx / tileCountX, tileIdxX = tileIdx - tileIdxY * tileCountX;
     const float2 zero2 = make_float2(0.0f, 0.0f);
     for (int i = threadIdx.x; i < T * T; i += 64) {
@@ -1126,6 +1089,35 @@ __global__ void __launch_bounds__(64)
     }
 }
 
+__global__ void __launch_bounds__(64)
+    k_tileSquaredSums(const float* __restrict__ refImg, float* __restrict__ out, int imgWidth, int imgHeight, int imgPitch,
+                      int maxShift, int tileSize, int tileCountX, int tileCountY)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    tile_squared_sum(s_mem, refImg, out, imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX, blockIdx.x);
+}
+
+// the same for the tiles of every tracker level in one launch: the kernel's time is one lane's chain of T^2 dependent adds,
+// which a launch per level pays once per level
+#define TSS_MAX_LEVELS 4
+struct TileSumLevels {
+    const float* img[TSS_MAX_LEVELS];
+    float* out[TSS_MAX_LEVELS];
+    int width[TSS_MAX_LEVELS], height[TSS_MAX_LEVELS], pitch[TSS_MAX_LEVELS];
+    int maxShift[TSS_MAX_LEVELS], tileSize[TSS_MAX_LEVELS], tileCountX[TSS_MAX_LEVELS];
+    int firstTile[TSS_MAX_LEVELS + 1];  // blocks [firstTile[l], firstTile[l + 1]) are level l's tiles
+    int levels;
+};
+
+__global__ void __launch_bounds__(64) k_tileSquaredSumsLevels(TileSumLevels A)
+{
+    extern __shared__ __attribute__((aligned(16))) float s_mem[];
+    int l = 0;
+    while (l + 1 < A.levels && (int)blockIdx.x >= A.firstTile[l + 1]) l++;
+    tile_squared_sum(s_mem, A.img[l], A.out[l], A.width[l], A.height[l], A.pitch[l], A.maxShift[l], A.tileSize[l], A.tileCountX[l],
+                     (int)blockIdx.x - A.firstTile[l]);
+}
+
 extern "C" int mfsr_tileSquaredSums(const float* refImg, float* outValues, int imgWidth, int imgHeight, int imgPitch,
                                     int maxShift, int tileSize, int tileCountX, int tileCountY, mfsr_stream_t stream)
 {
@@ -1136,6 +1128,37 @@ extern "C" int mfsr_tileSquaredSums(const float* refImg, float* outValues, int i
                        mfsr_s(stream), refImg, outValues, imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX,
                        tileCountY);
     return mfsr_launch_status("tileSquaredSums");
+}
+
+extern "C" int mfsr_tileSquaredSumsLevels(int levels, const mfsr_tex2d* refImgs, float* const* outValues, const int* maxShift,
+                                          const int* tileSize, const int* tileCountX, const int* tileCountY, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(levels >= 1 && levels <= TSS_MAX_LEVELS && refImgs && outValues && maxShift && tileSize && tileCountX && tileCountY);
+    TileSumLevels A;
+    memset(&A, 0, sizeof(A));
+    int maxT = 0;
+    long long tiles = 0;
+    for (int l = 0; l < levels; l++) {
+        MFSR_REQUIRE(outValues[l] && mfsr_tex_ok(refImgs[l], 4) && (refImgs[l].pitch & 3) == 0);
+        MFSR_REQUIRE(maxShift[l] >= 1 && maxShift[l] <= 15 && tileSize[l] >= 4 && tileSize[l] <= 128 && tileCountX[l] > 0 &&
+                     tileCountY[l] > 0);
+        A.img[l] = (const float*)refImgs[l].ptr;
+        A.out[l] = outValues[l];
+        A.width[l] = refImgs[l].width;
+        A.height[l] = refImgs[l].height;
+        A.pitch[l] = refImgs[l].pitch;
+        A.maxShift[l] = maxShift[l];
+        A.tileSize[l] = tileSize[l];
+        A.tileCountX[l] = tileCountX[l];
+        A.firstTile[l] = (int)tiles;
+        tiles += (long long)tileCountX[l] * tileCountY[l];
+        MFSR_REQUIRE(tiles < (1LL << 31));
+        maxT = tileSize[l] > maxT ? tileSize[l] : maxT;
+    }
+    A.firstTile[levels] = (int)tiles;
+    A.levels = levels;
+    hipLaunchKernelGGL(k_tileSquaredSumsLevels, dim3((unsigned)tiles), dim3(64), sizeof(float) * maxT * maxT, mfsr_s(stream), A);
+    return mfsr_launch_status("tileSquaredSumsLevels");
 }
 
 static int track_tiles_fused_impl(const float* refImg, const float* movedImg, const mfsr_float2* preShift, int preShiftPitch,
