@@ -679,7 +679,8 @@ extern "C" int mfsr_fftshift(mfsr_float2* fft, int width, int height, mfsr_strea
 // L2 distance of every candidate shift (sx, sy) in [0, 2S]^2:
 //     D = sum(ref^2) + sum_window(moved^2) - 2*sum(ref*moved)
 // with every sum taken in the order the unfused chain uses (row-major serial for sum(ref^2);
-// per-row sums then the sum of rows for the correlation and the box term), so D is
+// per-row sums then the sum of rows for the correlation and the box term; the box term over 2*(T/2) columns and rows, which
+// is what the chain's box filters sum -- T - 1 for odd T), so D is
 // bit-identical to squaredSum'(serial)/boxFilter/normalizedCC fed by the direct correlation.
 //  * sum(ref^2) does not depend on the candidate or on the moved frame: it is taken once per
 //    reference (mfsr_tileSquaredSums) and passed in; without it one lane per tile takes it here.
@@ -712,6 +713,10 @@ __global__ void __launch_bounds__(TRK_THREADS)
     const int tid = threadIdx.x;
     const int tileCount = tileCountX * tileCountY;
     const int tile0 = blockIdx.x * tilesPerWg;
+    // taps of the box term per axis: boxFilterWithBorderX / Y sum shift = -T/2 .. T/2 - 1 (kernel.cu:177, :214), which is T
+    // terms for even T and T - 1 for odd T, starting at the candidate's own column / row either way (L/2 - T/2 = S).  The
+    // correlation and sum(ref^2) always take all T x T pixels (oracle/glue.c, kernel.cu:126-141).
+    const int TB = 2 * (T / 2);
     const float2 zero2 = make_float2(0.0f, 0.0f);
     // global pre-alignment of the moved frame (B2's baseShift / baseRotation, kernel.cu:358-368), read from device
     // memory: base shift in pixels of THIS pyramid level, cos/sin of the base rotation from the host-built table
@@ -778,7 +783,7 @@ __global__ void __launch_bounds__(TRK_THREADS)
             const int ry = j / R, sx = j - ry * R;
             const float* m = slot_mov(sl) + ry * Lp + sx;
             float a = 0;
-            for (int x = 0; x < T; x++) a += m[x] * m[x];
+            for (int x = 0; x < TB; x++) a += m[x] * m[x];
             slot_row(sl)[j] = a;
         } else if (refSq) {
             *slot_sq(sl) = refSq[tile0 + sl];
@@ -835,7 +840,7 @@ __global__ void __launch_bounds__(TRK_THREADS)
                 const int sx = sx0 + j;
                 if (sx < R) {
                     float box = 0;
-                    for (int y = 0; y < T; y++) box += rows[(sy + y) * R + sx];
+                    for (int y = 0; y < TB; y++) box += rows[(sy + y) * R + sx];
                     slot_dist(sl)[sy * R + sx] = sq + box - 2 * cc[j];
                 }
             }

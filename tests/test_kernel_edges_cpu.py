@@ -10,10 +10,13 @@ from tests import test_kernel_edges_gpu as edges
 
 PIPELINE = "burst / stream driver, covered by tests/test_pipeline_gpu.py"
 BATCH = "batched form, bit-compared with the single-frame call in tests/test_batch_kernels_gpu.py"
+TRACKER = ("tiles packed into workgroups: ragged sizes, every packing and padded pitches against the oracle chain in "
+           "tests/test_tracker_inputs_gpu.py")
 WINDOW = "zoom-window form, bit-compared with the cropped whole-frame call in tests/test_window_gpu.py"
 
 EXCLUDED = {
-    # tile tracker: the pitch is that of the whole image, the launch is one workgroup per tile (no partial blocks in x or y)
+    # tile tracker: the pitch is that of the whole image and the launch goes over tiles, not over pixel blocks; the fused trackers
+    # pack several tiles into a workgroup and have their own sweep (TRACKER)
     "mfsr_convertToTilesOverlapBorder": "one workgroup per tile; padded image pitch in test_parity_kernels.py::test_convertToTiles",
     "mfsr_convertToTilesOverlapPreShift": "one workgroup per tile; padded image pitch in test_parity_kernels.py::test_convertToTiles",
     "mfsr_findMinimum": "one thread per tile; padded output pitch in test_parity_kernels.py::test_findMinimum",
@@ -22,11 +25,11 @@ EXCLUDED = {
     "mfsr_concatenateShifts": "pointer-array ABI on the tile grid, test_parity_kernels.py::test_concatenate_separate_setPointers",
     "mfsr_separateShifts": "pointer-array ABI on the tile grid, test_parity_kernels.py::test_concatenate_separate_setPointers",
     "mfsr_addRoundedPreShift": "tile-grid kernel, used by test_parity_kernels.py::test_trackTilesFused_equals_chain",
-    "mfsr_trackTilesFused": "one workgroup per tile, test_parity_kernels.py::test_trackTilesFused_equals_chain",
-    "mfsr_trackTilesFusedBase": "one workgroup per tile, test_parity_kernels.py::test_trackTilesFused_equals_chain",
-    "mfsr_trackTilesFusedUp": "one workgroup per tile, test_parity_kernels.py::test_trackTilesFusedUp_equals_UpSampleShifts_then_tracker",
-    "mfsr_tileSquaredSums": "one workgroup per tile, test_parity_kernels.py::test_trackTilesFused_equals_chain",
-    "mfsr_trackTilesFusedBatch": BATCH,
+    "mfsr_trackTilesFused": TRACKER + "::test_every_geometry_row",
+    "mfsr_trackTilesFusedBase": TRACKER + "::test_every_geometry_row, ::test_rotated_base",
+    "mfsr_trackTilesFusedUp": TRACKER + "::test_half_integer_upsampled_shifts",
+    "mfsr_tileSquaredSums": TRACKER + "::test_every_geometry_row (against squaredSum at every row)",
+    "mfsr_trackTilesFusedBatch": TRACKER + "::test_batch_of_frames; " + BATCH,
     # Fourier helpers of the reference's tracker, not on the pipeline's path
     "mfsr_fourierFilter": "half-spectrum helper, test_parity_kernels.py::test_fourier_helpers",
     "mfsr_fftshift": "dense by contract (no pitch), test_parity_kernels.py::test_fourier_helpers",

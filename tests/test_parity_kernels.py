@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests.kernels import F2, F3, Host, Tex, guarded_upload, pitch_of
+from tests.tracker_ref import oracle_track
 
 pytestmark = pytest.mark.gpu
 
@@ -720,24 +721,7 @@ def test_trackTilesFused_equals_chain(orc, hip, T, S):
     ref = np.ascontiguousarray(base[8:8 + H, 8:8 + W])
     mov = np.ascontiguousarray(base[6:6 + H, 9:9 + W])  # moved(p + (-1,+2)) == ref(p)
     pre = r.uniform(-1.4, 1.4, (tcy, tcx, 2)).astype(np.float32)
-    z = F2([0, 0])
-    rt = np.zeros((n, L, L), np.float32)
-    mt = np.zeros((n, L, L), np.float32)
-    cc = np.zeros((n, L, L), np.float32)
-    bx = np.zeros((n, L, L), np.float32)
-    by = np.zeros((n, L, L), np.float32)
-    sq = np.zeros(n, np.float32)
-    dist = np.zeros((n, R, R), np.float32)
-    coord = np.zeros((tcy, tcx, 2), np.float32)
-    orc.call("convertToTilesOverlapBorder", ref, rt, W, H, pitch_of(ref), S, T, tcx, tcy, z, 0.0)
-    orc.call("convertToTilesOverlapPreShift", mov, mt, pre, pitch_of(pre), W, H, pitch_of(mov), S, T, tcx, tcy, z, 0.0)
-    orc.call("crossCorrelateTiles", rt, mt, cc, S, T, n)
-    orc.call("squaredSum", rt, sq, S, T, n)
-    orc.call("boxFilterWithBorderX", mt, bx, S, T, n)
-    orc.call("boxFilterWithBorderY", bx, by, S, T, n)
-    orc.call("normalizedCC", cc, sq, by, dist, S, T, n)
-    orc.call("findMinimum", dist, coord, pitch_of(coord), S, n, tcx, 0.0)
-    orc.call("addRoundedPreShift", pre, pitch_of(pre), coord, pitch_of(coord), tcx, tcy)
+    coord, _, sq, _ = oracle_track(orc, ref, mov, W, H, T, S, pre=pre, coord_pad=0)
     got = np.zeros((tcy, tcx, 2), np.float32)
     hip.call("trackTilesFused", ref, mov, pre, pitch_of(pre), got, pitch_of(got), W, H, pitch_of(ref), S, T, tcx, tcy, 0.0, None)
     assert_bitexact(coord, got, "trackTilesFused")
@@ -750,15 +734,7 @@ def test_trackTilesFused_equals_chain(orc, hip, T, S):
     assert_bitexact(coord, got2, "trackTilesFused(refSquaredSums)")
     # global pre-alignment without rotation (B2's baseShift, kernel.cu:358-368; cos = 1 and sin = 0 exactly), read by the
     # kernel from a device mfsr_prealign: same bits as the oracle chain with that base shift -- both kernels
-    bs = F2([3.0, -2.0])
-    orc.call("convertToTilesOverlapPreShift", mov, mt, pre, pitch_of(pre), W, H, pitch_of(mov), S, T, tcx, tcy, bs, 0.0)
-    orc.call("crossCorrelateTiles", rt, mt, cc, S, T, n)
-    orc.call("boxFilterWithBorderX", mt, bx, S, T, n)
-    orc.call("boxFilterWithBorderY", bx, by, S, T, n)
-    orc.call("normalizedCC", cc, sq, by, dist, S, T, n)
-    coordB = np.zeros((tcy, tcx, 2), np.float32)
-    orc.call("findMinimum", dist, coordB, pitch_of(coordB), S, n, tcx, 0.0)
-    orc.call("addRoundedPreShift", pre, pitch_of(pre), coordB, pitch_of(coordB), tcx, tcy)
+    coordB = oracle_track(orc, ref, mov, W, H, T, S, pre=pre, base=(3.0, -2.0, 0.0, 1.0), coord_pad=0)[0]
     assert not np.array_equal(coordB, coord)
     pa = np.zeros(12, np.float32)  # mfsr_prealign: shiftX, shiftY, rotation, cos, sin, 7 x int32
     pa[:5] = [3.0, -2.0, 0.0, 1.0, 0.0]
