@@ -1079,6 +1079,55 @@ int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render);
 /* the same for every output of a frame stream (between outputs: any time, a push completes its window before it returns) */
 int mfsr_stream_set_render(mfsr_stream* s, const mfsr_render* render);
 
+/* ---- two-plane YUV 4:2:0 output of the rendered finish: NV12 and P010.  Two more values of
+ * mfsr_render.format; for them reserved[0] carries the colour description: bits 0-1 the standard (MFSR_YUV_BT709 / _BT601 /
+ * _BT2020), bit 2 (MFSR_YUV_FULL) full range instead of limited range.  Any other bit, the standard value 3 or a non-zero
+ * reserved[1] / reserved[2] is MFSR_E_INVALID; zeros mean BT.709 limited range.  (For the four formats above reserved stays
+ * ignored.)  All arithmetic is float32, no contraction, in the order written; o is the pixel after steps 1-2 of the rendered
+ * output (matrix, tone), which is still what the float image receives:
+ *   1. c_k = isnan(o_k) ? 0 : fminf(fmaxf(o_k, 0), 1)
+ *   2. Y = (Kr*c0 + Kg*c1) + Kb*c2;  Cb = (c2 - Y) * Sb;  Cr = (c0 - Y) * Sr.  The five constants are the float32 roundings of
+ *      doubles: (Kr, Kb) = (0.2126, 0.0722) BT.709, (0.299, 0.114) BT.601, (0.2627, 0.0593) BT.2020; Kg = 1 - Kr - Kb,
+ *      Sb = 0.5 / (1 - Kb), Sr = 0.5 / (1 - Kr).
+ *   3. chroma of the 2 x 2 block with top-left pixel (x, y), x and y even:
+ *      C = ((C(x, y) + C(x+1, y)) + (C(x, y+1) + C(x+1, y+1))) * 0.25f.  This is the box mean, i.e. the chroma sample is sited
+ *      at the CENTRE of its four pixels (MPEG-1 / JPEG siting); left-cosited (MPEG-2) or filtered chroma is not offered.
+ *   4. codes, N = 8 (NV12) or 10 (P010), m = 2^(N-8), M = 2^N - 1: limited range yq = 16m + 219m*Y, cq = 128m + 224m*C; full
+ *      range yq = M*Y, cq = 2^(N-1) + M*C;  code = (int)(fminf(fmaxf(v, 0), M) + 0.5f).
+ *      MFSR_OUT_NV12 stores the byte, MFSR_OUT_P010 stores code << 6 as a little-endian uint16_t.
+ * Layout: a Y plane of h rows of w samples, and a chroma plane of h/2 rows of w/2 interleaved (Cb, Cr) pairs, so a chroma row
+ * has the bytes of a Y row: mfsr_render_row_bytes gives w (NV12) or 2w (P010).  w and h must be even and positive
+ * (MFSR_E_INVALID otherwise, also from mfsr_render_row_bytes for an odd width).  NV12 planes may have any byte alignment and
+ * any row bytes >= w; P010 planes are 2-byte aligned with even row bytes >= 2w.
+ * mfsr_render_image_bytes: the dense size of a rendered w x h image of any of the six formats, rowBytes * h or
+ * rowBytes * h * 3 / 2; host arithmetic; < 0 for an unknown format or an extent the format does not take.
+ * mfsr_renderImageYuv / mfsr_finishRenderedYuv: mfsr_renderImage / mfsr_finishRendered with the two plane pointers, each at
+ * the launch's first row (chroma row r/2 goes with Y rows r, r+1), in place of out.  outImg may be NULL or in place; outY and
+ * outUV are both given or both NULL, and at least one of outImg and the pair is given.  They refuse the four single-plane
+ * formats, as mfsr_renderImage, mfsr_finishRendered, mfsr_sharpenImage and mfsr_finishSharpened refuse these two.  Every
+ * argument is checked on the host before any device call (MFSR_E_INVALID); asynchronous on `stream`, nothing is allocated.
+ * Bursts and streams (mfsr_burst_set_render / mfsr_stream_set_render): wherever one output buffer is taken, the chroma plane
+ * follows the Y plane immediately -- chroma row r is "row" h + r of the same dense pitch, mfsr_render_image_bytes in all.
+ * mfsr_burst_finish_rows needs even row0 and rows and fills both row ranges; mfsr_burst_finish_host downloads each band's Y
+ * rows and chroma rows (one copy of 3h/2 rows when there is one band).  A window (x0, y0 multiples of 16) must have even
+ * extents, so its 2 x 2 blocks are the whole frame's and its output is the crop of both planes; an odd output width or height
+ * is refused at the finish.  A sharpen description together with a two-plane format is refused by whichever of
+ * mfsr_burst_set_render / mfsr_burst_set_sharpen comes second. */
+#define MFSR_OUT_NV12 16   /* 8-bit  Y plane, then interleaved Cb,Cr plane at half resolution in x and y */
+#define MFSR_OUT_P010 17   /* 16-bit little-endian words, the 10-bit code in bits 15..6 (code << 6), same planes */
+#define MFSR_YUV_BT709 0
+#define MFSR_YUV_BT601 1
+#define MFSR_YUV_BT2020 2
+#define MFSR_YUV_FULL 4
+long long mfsr_render_image_bytes(int format, int w, int h);
+int mfsr_renderImageYuv(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* outY, int yRowBytes,
+                        void* outUV, int uvRowBytes, int w, int h, const mfsr_render* render, int applyGamma, mfsr_stream_t stream);
+int mfsr_finishRenderedYuv(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                           int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                           int outImgRowBytes, void* outY, int yRowBytes, void* outUV, int uvRowBytes, const mfsr_render* render,
+                           int w, int h, float threshold, int applyGamma, int colOffset, int rowOffset, int fullWidth,
+                           int fullHeight, mfsr_stream_t stream);
+
 /* ---- sharpening inside the finish: an unsharp mask on the linear float value, before matrix and tone (DESIGN.md section
  * 2.20).  Off unless asked for; without a sharpen description every entry point produces the bits and the launches it always
  * did.  All arithmetic is float32, no contraction.  For an HR pixel and each channel alone, p is the value section 2.19 calls

@@ -117,6 +117,11 @@ PACK_BITS = {PACK_MIPI10: 10, PACK_MIPI12: 12, PACK_BE10: 10, PACK_BE12: 12}
 
 # mfsr_render.format (include/mfsr.h): bytes per pixel 6, 3, 4, 4
 OUT_RGB16, OUT_RGB8, OUT_RGBA8, OUT_RGB10A2 = 0, 1, 2, 3
+# two-plane YUV 4:2:0: a Y plane, then interleaved (Cb, Cr) at half resolution; 8-bit, and the 10-bit
+# code in bits 15..6 of 16-bit words.  mfsr_render.reserved[0] = YUV_BT* | YUV_FULL (0: BT.709 limited range)
+OUT_NV12, OUT_P010 = 16, 17
+YUV_FORMATS = (OUT_NV12, OUT_P010)
+YUV_BT709, YUV_BT601, YUV_BT2020, YUV_FULL = 0, 1, 2, 4
 
 
 class Render(ctypes.Structure):
@@ -138,7 +143,7 @@ _BY_VALUE = {
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
     "mfsr_stream_t": ctypes.c_void_p, "long long": ctypes.c_longlong,
 }
-_RET = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p,
+_RET = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p, "long long": ctypes.c_longlong,
         "mfsr_burst*": ctypes.c_void_p, "mfsr_dist*": ctypes.c_void_p}
 
 
@@ -153,7 +158,7 @@ def parse_header(path: str = HEADER_PATH) -> Dict[str, Tuple[str, List[Tuple[str
     text = re.sub(r"\{[^{}]*\}", " ", text)                    # struct / enum bodies
     protos = {}
     for stmt in text.split(";"):
-        m = re.match(r"^\s*((?:const\s+char\s*\*|mfsr_burst\s*\*|mfsr_dist\s*\*|int|size_t|void))\s+(mfsr_\w+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+        m = re.match(r"^\s*((?:const\s+char\s*\*|mfsr_burst\s*\*|mfsr_dist\s*\*|long\s+long|int|size_t|void))\s+(mfsr_\w+)\s*\((.*)\)\s*$", stmt, flags=re.S)
         if not m:
             continue
         ret = re.sub(r"\s+", " ", m.group(1)).replace(" *", "*").strip()

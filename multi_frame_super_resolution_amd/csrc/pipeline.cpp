@@ -1844,8 +1844,18 @@ static size_t out_row_bytes(const mfsr_burst* b)
     return b->renderOn ? (size_t)mfsr_render_row_bytes(b->render.format, out_w(b)) : (size_t)out_w(b) * 6;
 }
 
+// a two-plane 4:2:0 format: the output buffer holds out_h rows of Y, then out_h / 2 rows of chroma, one pitch
+static bool yuv_format(int format) { return format == MFSR_OUT_NV12 || format == MFSR_OUT_P010; }
+static bool yuv_on(const mfsr_burst* b) { return b->renderOn && yuv_format(b->render.format); }
+
+// bytes of the burst's dense integer output
+static size_t out_image_bytes(const mfsr_burst* b)
+{
+    return b->renderOn ? (size_t)mfsr_render_image_bytes(b->render.format, out_w(b), out_h(b)) : (size_t)out_w(b) * 6 * out_h(b);
+}
+
 // the rendered finish of output rows [r0, r0 + rows) (rows of the window when one is set); pointers are those of the whole
-// images, `out` holds dense rendered rows
+// images, `out` holds dense rendered rows (two-plane formats: both planes, so r0 and rows are even)
 static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
                                 void* out, int r0, int rows, mfsr_stream_t stream)
 {
@@ -1855,6 +1865,16 @@ static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const 
     const int rowBytes = (int)out_row_bytes(b);
     const size_t off = (size_t)r0 * pitch;
     const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    if (yuv_on(b)) {
+        MFSR_REQUIRE((oW & 1) == 0 && (out_h(b) & 1) == 0 && (r0 & 1) == 0 && (rows & 1) == 0);
+        char* y = out ? (char*)out + (size_t)r0 * rowBytes : nullptr;
+        char* uv = out ? (char*)out + ((size_t)out_h(b) + (size_t)(r0 / 2)) * rowBytes : nullptr;
+        return mfsr_finishRenderedYuv((const mfsr_float3*)((const char*)imgOut + off),
+                                      (const mfsr_float3*)((const char*)totalWeights + off), pitch, (const mfsr_float3*)L.fallback.ptr,
+                                      L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                      outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch, y, rowBytes, uv, rowBytes,
+                                      &b->render, oW, rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
+    }
     return mfsr_finishRendered((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
                                pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
                                outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
@@ -1899,8 +1919,10 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
         return MFSR_OK;
     }
     TRY(mfsr_sharpen_validate(sharpen));
+    const bool on = sharpen->radius != 0 && sharpen->amount != 0.0f;
+    MFSR_REQUIRE(!(on && yuv_on(b)));  // the sharpen tile kernel renders single rows: no two-plane output
     b->sharpen = *sharpen;
-    b->sharpenOn = sharpen->radius != 0 && sharpen->amount != 0.0f;
+    b->sharpenOn = on;
     return MFSR_OK;
 }
 
@@ -1920,6 +1942,7 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
         return MFSR_OK;
     }
     TRY(mfsr_render_validate(render));
+    MFSR_REQUIRE(!(b->sharpenOn && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen: whichever comes second)
     b->render = *render;
     b->renderOn = true;
     return MFSR_OK;
@@ -1945,6 +1968,12 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
         TRY(mfsr_resampleFloat3((const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, outImg, pitch, L.hrW, L.hrH,
                                 0.0f, 1.0f, 0.0f, 1.0f, stream));
         TRY(mfsr_ApplyWeighting(outImg, imgOut, totalWeights, L.hrW, L.hrH, pitch, c.weightThreshold, stream));
+        if (yuv_on(b)) {
+            const int rowBytes = (int)out_row_bytes(b);
+            return mfsr_renderImageYuv(outImg, pitch, outImg, pitch, out16, rowBytes,
+                                       out16 ? (char*)out16 + (size_t)L.hrH * rowBytes : nullptr, rowBytes, L.hrW, L.hrH, &b->render,
+                                       c.applyGamma, stream);
+        }
         return mfsr_renderImage(outImg, pitch, outImg, pitch, out16, (int)out_row_bytes(b), L.hrW, L.hrH, &b->render, c.applyGamma,
                                 stream);
     }
@@ -1979,6 +2008,7 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     const Layout& L = b->L;
     MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
+    if (yuv_on(b)) MFSR_REQUIRE((row0 & 1) == 0 && (rows & 1) == 0);  // whole 2 x 2 chroma blocks
     TRY(flush_pending(b, stream));
     if (b->sharpenOn) {
         int above, below;
@@ -2237,7 +2267,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // out16Dev: 18.1 instead of 17.0 ms per burst with two bands)
     const int oW = out_w(b), oH = out_h(b);  // the window's extent when one is set
     const size_t rowBytes = out_row_bytes(b);  // rendered bytes when a render is set
-    const double outBytes = (double)rowBytes * oH, inBytes = (double)L.W * L.H * 2.0 * c.frames;
+    const double outBytes = (double)out_image_bytes(b), inBytes = (double)L.W * L.H * 2.0 * c.frames;
     if (b->hostBusy && nBandsBusy >= 1 && nBandsBusy < nBands && outBytes <= 1.5 * inBytes) nBands = nBandsBusy;
     bool heldGroup = b->pend.n > 0 && b->pend.imgOut == imgOut && b->pend.totalWeights == totalWeights && c.fused;
     if (b->heldHas && !(heldGroup && b->held.imgOut == imgOut && b->held.totalWeights == totalWeights)) {
@@ -2249,8 +2279,9 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         TRY(mfsr_burst_finish(b, imgOut, totalWeights, nullptr, out16Dev, stream));
         MFSR_HIP_TRY(hipEventRecord(b->evFinished, mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evFinished, 0));
-        MFSR_HIP_TRY(hipMemcpy2DAsync(out16Host, rowBytes, out16Dev, rowBytes, rowBytes, (size_t)oH, hipMemcpyDeviceToHost,
-                                      b->downStream));
+        // (two-plane formats: the chroma rows follow the Y rows at the same pitch, one copy of 3 oH / 2 rows)
+        MFSR_HIP_TRY(hipMemcpy2DAsync(out16Host, rowBytes, out16Dev, rowBytes, rowBytes, yuv_on(b) ? (size_t)oH * 3 / 2 : (size_t)oH,
+                                      hipMemcpyDeviceToHost, b->downStream));
         MFSR_HIP_TRY(hipEventRecord(b->evDown, b->downStream));
         b->downRecorded = true;
         b->nUnp = 0;  // (packed frames that were announced and not consumed are never unpacked)
@@ -2339,6 +2370,11 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[i], 0));
         MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)r0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)r0 * rowBytes,
                                       rowBytes, rowBytes, (size_t)(r1 - r0), hipMemcpyDeviceToHost, b->downStream));
+        if (yuv_on(b)) {  // the band's chroma rows (r0 is a multiple of 16, r1 one or the even height)
+            const size_t c0 = ((size_t)oH + (size_t)(r0 / 2)) * rowBytes;
+            MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + c0, rowBytes, (const char*)out16Dev + c0, rowBytes, rowBytes,
+                                          (size_t)((r1 - r0) / 2), hipMemcpyDeviceToHost, b->downStream));
+        }
     }
     if (lagR0 >= 0) TRY(finish_lagged());
     if (heldGroup && b->copyStream) {

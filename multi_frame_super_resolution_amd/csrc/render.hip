@@ -60,15 +60,33 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
 
 extern "C" int mfsr_render_row_bytes(int format, int widthPx)
 {
+    if (yuv_format(format)) {  // a Y row; a chroma row of widthPx / 2 (Cb, Cr) pairs has the same bytes
+        const int bps = format == MFSR_OUT_NV12 ? 1 : 2;
+        if (widthPx <= 0 || (widthPx & 1) || (long long)bps * widthPx > 2147483647LL) return MFSR_E_INVALID;
+        return bps * widthPx;
+    }
     const int bpp = bytes_per_pixel(format);
     if (bpp < 0 || widthPx <= 0 || (long long)bpp * widthPx > 2147483647LL) return MFSR_E_INVALID;
     return bpp * widthPx;
 }
 
+extern "C" long long mfsr_render_image_bytes(int format, int w, int h)
+{
+    const int rowBytes = mfsr_render_row_bytes(format, w);
+    if (rowBytes < 0 || h <= 0) return MFSR_E_INVALID;
+    if (!yuv_format(format)) return (long long)rowBytes * h;
+    if (h & 1) return MFSR_E_INVALID;
+    return (long long)rowBytes * h * 3 / 2;
+}
+
 int mfsr_render_validate(const mfsr_render* r)
 {
     MFSR_REQUIRE(r != nullptr);
-    MFSR_REQUIRE(bytes_per_pixel(r->format) > 0);
+    if (yuv_format(r->format)) {  // reserved[0]: the colour description (MFSR_YUV_*)
+        MFSR_REQUIRE((r->reserved[0] & ~7) == 0 && (r->reserved[0] & 3) != 3 && r->reserved[1] == 0 && r->reserved[2] == 0);
+    } else {
+        MFSR_REQUIRE(bytes_per_pixel(r->format) > 0);
+    }
     if (r->useMatrix)
         for (int i = 0; i < 9; i++) MFSR_REQUIRE(std::isfinite(r->matrix[i]) && fabsf(r->matrix[i]) <= 256.0f);
     if (r->toneLut) MFSR_REQUIRE(r->toneSize >= 1 && r->toneSize <= 65536 && ((uintptr_t)r->toneLut & 3) == 0);
@@ -98,6 +116,7 @@ extern "C" int mfsr_renderImage(const mfsr_float3* in, int inRowBytes, mfsr_floa
     MFSR_REQUIRE((long long)inRowBytes >= 12LL * w && (inRowBytes & 3) == 0 && ((uintptr_t)in & 3) == 0);
     if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0 && ((uintptr_t)outImg & 3) == 0);
     if (int rc = mfsr_render_validate(render)) return rc;
+    MFSR_REQUIRE(!yuv_format(render->format));  // two planes: mfsr_renderImageYuv / mfsr_finishRenderedYuv
     if (out)
         if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
     const RenderArgs a = render_args(render, applyGamma);
@@ -120,6 +139,7 @@ extern "C" int mfsr_finishRendered(const mfsr_float3* finalImg, const mfsr_float
     MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
     MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
     if (int rc = mfsr_render_validate(render)) return rc;
+    MFSR_REQUIRE(!yuv_format(render->format));  // two planes: mfsr_renderImageYuv / mfsr_finishRenderedYuv
     if (out)
         if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
     const RenderArgs a = render_args(render, applyGamma);

@@ -141,11 +141,15 @@ int bytes_per_pixel(int format)
     return -1;
 }
 
+// the two-plane 4:2:0 formats: their kernels and entry points are render_yuv.hip's
+inline bool yuv_format(int format) { return format == MFSR_OUT_NV12 || format == MFSR_OUT_P010; }
+
 // How the tone table is read.  Measured at 7680 x 4320 with a 4096-interval table ("Rendered finish"):
 // the one-pixel-per-lane formats are faster reading it through the cache (235 against 272 us), RGB8 -- four pixels, 24 table
 // reads per lane -- is faster with the table staged in LDS by 1024-lane workgroups (237 against 346 us).  So RGB8 stages
 // tables that fit (up to kLdsLutMax intervals) and the other formats do not.  MFSR_RENDER_LUT=lds | cache forces one form for
-// every format (A/B); read at every call: host only, and a test can switch it.
+// every format (A/B); read at every call: host only, and a test can switch it.  The two-plane formats (eight pixels, 24 table
+// reads per lane) follow RGB8.
 bool lut_in_lds(const mfsr_render* r)
 {
     if (!r->toneLut || r->toneSize > kLdsLutMax) return false;
@@ -153,7 +157,7 @@ bool lut_in_lds(const mfsr_render* r)
         if (strcmp(e, "lds") == 0) return true;
         if (strcmp(e, "cache") == 0) return false;
     }
-    return r->format == MFSR_OUT_RGB8;
+    return r->format == MFSR_OUT_RGB8 || yuv_format(r->format);
 }
 
 RenderArgs render_args(const mfsr_render* r, int applyGamma)

@@ -277,6 +277,7 @@ extern "C" int mfsr_sharpenImage(const mfsr_float3* in, int inRowBytes, mfsr_flo
     const mfsr_render plain = plain_render();
     if (!render) render = &plain;
     if (int rc = mfsr_render_validate(render)) return rc;
+    MFSR_REQUIRE(!yuv_format(render->format));  // the tile kernel renders single rows: no two-plane 4:2:0 output
     if (out) {
         if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
         MFSR_REQUIRE(!ranges_overlap(in, (long long)inRowBytes * (h - 1) + 12LL * w, out,
@@ -309,6 +310,7 @@ extern "C" int mfsr_finishSharpened(const mfsr_float3* finalImg, const mfsr_floa
     const mfsr_render plain = plain_render();
     if (!render) render = &plain;
     if (int rc = mfsr_render_validate(render)) return rc;
+    MFSR_REQUIRE(!yuv_format(render->format));  // the tile kernel renders single rows: no two-plane 4:2:0 output
     if (out)
         if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
     {

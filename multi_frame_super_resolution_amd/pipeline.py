@@ -55,6 +55,7 @@ class _Window:
             self._rect = None
             return
         x, y, w, h = (int(v) for v in window)
+        self._asked = (x, y, w, h)
         self._base = align_window(cfg, x, y, w, h)
         self._rect = (max(x, 0), max(y, 0), min(x + w, hr_w), min(y + h, hr_h))
         self.grow(0)
@@ -83,6 +84,22 @@ class _Window:
 
     def __call__(self, img: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         return None if img is None else img[self.crop]
+
+    def check_yuv(self, fmt: int):
+        """A two-plane 4:2:0 format needs a rectangle of whole 2 x 2 blocks."""
+        if fmt in capi.YUV_FORMATS and self._rect is not None and any(v % 2 for v in self._asked):
+            raise ValueError(f"window {self._asked}: x, y, w and h must be even for a two-plane YUV 4:2:0 output")
+
+    def output(self, buf: Optional[torch.Tensor], fmt: int) -> Optional[torch.Tensor]:
+        """The integer output of the rectangle asked for: the crop of the image, or for a two-plane format the crop of both
+        planes of the aligned window's flat buffer, as one flat tensor again (a copy; the buffer itself without a window)."""
+        if buf is None or fmt not in capi.YUV_FORMATS:
+            return self(buf)
+        if self._rect is None:
+            return buf
+        ys, xs = self.crop
+        y, uv = yuv_planes(buf, fmt, self.aligned[3], self.aligned[2])
+        return torch.cat([y[ys, xs].reshape(-1), uv[ys.start // 2:ys.stop // 2, xs.start // 2:xs.stop // 2].reshape(-1)])
 
 
 Selection = namedtuple("Selection", "reference kept sums rect")
@@ -557,10 +574,34 @@ def render_row_bytes(fmt: int, width: int) -> int:
     return n
 
 
-def _render_struct(fmt: int, matrix, tone_lut, device):
-    """(capi.Render, the device tensor of the table or None): the caller keeps the tensor alive as long as the struct is used."""
+def render_image_bytes(fmt: int, w: int, h: int) -> int:
+    """Bytes of a dense rendered image (mfsr_render_image_bytes): rows of ``render_row_bytes``, h of them, or 3h/2 for the
+    two-plane formats; ValueError for an unknown format or an extent the format does not take (NV12 / P010: even w and h)."""
+    n = capi.lib().raw["mfsr_render_image_bytes"](int(fmt), int(w), int(h))
+    if n < 0:
+        raise ValueError(f"unknown output format {fmt} or extent {w} x {h}")
+    return n
+
+
+def yuv_planes(buf: torch.Tensor, fmt: int, h: int, w: int):
+    """(Y [h, w], UV [h/2, w/2, 2]) views of the flat buffer of a two-plane output (``capi.OUT_NV12``: uint8, ``capi.OUT_P010``:
+    int16 words holding code << 6), without a copy: the chroma plane follows the Y plane."""
+    if fmt not in capi.YUV_FORMATS:
+        raise ValueError(f"format {fmt} has one plane")
+    if h % 2 or w % 2 or buf.dim() != 1 or buf.numel() != h * w * 3 // 2:
+        raise ValueError("yuv_planes: a flat tensor of 3hw/2 elements, h and w even")
+    return buf[:h * w].view(h, w), buf[h * w:].view(h // 2, w // 2, 2)
+
+
+def _render_struct(fmt: int, matrix, tone_lut, device, yuv: int = 0):
+    """(capi.Render, the device tensor of the table or None): the caller keeps the tensor alive as long as the struct is used.
+    ``yuv``: the colour description of a two-plane format (``capi.YUV_BT709 | YUV_BT601 | YUV_BT2020``, ``| capi.YUV_FULL``)."""
     r = capi.Render()
     r.format = int(fmt)
+    if yuv:
+        if int(fmt) not in capi.YUV_FORMATS:
+            raise ValueError("yuv: a colour description goes with OUT_NV12 / OUT_P010 only")
+        r.reserved[0] = int(yuv)
     if matrix is not None:
         m = [float(v) for v in torch.as_tensor(matrix, dtype=torch.float64).reshape(-1).tolist()]
         if len(m) != 9:
@@ -578,7 +619,12 @@ def _render_struct(fmt: int, matrix, tone_lut, device):
 
 
 def _render_buffer(fmt: int, h: int, w: int, device) -> torch.Tensor:
-    """The tensor typed for the format: int16 [h, w, 3], uint8 [h, w, 3], uint8 [h, w, 4] or int32 [h, w]."""
+    """The tensor typed for the format: int16 [h, w, 3], uint8 [h, w, 3], uint8 [h, w, 4] or int32 [h, w]; for the two-plane
+    formats one flat tensor of 3hw/2 elements, uint8 (NV12) or int16 (P010): ``yuv_planes`` gives the planes."""
+    if fmt in capi.YUV_FORMATS:
+        if h % 2 or w % 2:
+            raise ValueError(f"a two-plane YUV 4:2:0 output needs an even width and height, not {w} x {h}")
+        return torch.empty(h * w * 3 // 2, dtype=torch.uint8 if fmt == capi.OUT_NV12 else torch.int16, device=device)
     if fmt == capi.OUT_RGB16:
         return torch.empty(h, w, 3, dtype=torch.int16, device=device)
     if fmt == capi.OUT_RGB8:
@@ -591,18 +637,25 @@ def _render_buffer(fmt: int, h: int, w: int, device) -> torch.Tensor:
 
 
 def render_image(img: torch.Tensor, format: int = capi.OUT_RGB16, matrix=None, tone_lut=None, apply_gamma: bool = False,
-                 want_float: bool = False):
-    """Matrix, tone curve and quantisation of an existing float image [h, w, 3] on the device (mfsr_renderImage): the pixel
-    body of the rendered finish on its own.  Returns the tensor typed for the format, and with ``want_float`` also the float
-    image the integers quantise."""
+                 want_float: bool = False, yuv: int = 0):
+    """Matrix, tone curve and quantisation of an existing float image [h, w, 3] on the device (mfsr_renderImage, or
+    mfsr_renderImageYuv for ``capi.OUT_NV12`` / ``OUT_P010`` with the colour description ``yuv``): the pixel body of the
+    rendered finish on its own.  Returns the tensor typed for the format (two planes: the flat tensor of ``yuv_planes``), and
+    with ``want_float`` also the float image the integers quantise."""
     if not (img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 3 and img.stride(2) == 1
             and img.stride(1) == 3):
         raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
     h, w = int(img.shape[0]), int(img.shape[1])
     with torch.cuda.device(img.device):
-        r, lut = _render_struct(format, matrix, tone_lut, img.device)
+        r, lut = _render_struct(format, matrix, tone_lut, img.device, yuv)
         out = _render_buffer(format, h, w, img.device)
         fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if want_float else None
+        if format in capi.YUV_FORMATS:
+            rb = render_row_bytes(format, w)
+            capi.lib().renderImageYuv(img.data_ptr(), img.stride(0) * 4, fl.data_ptr() if want_float else None, 12 * w, out.data_ptr(),
+                                      rb, out.data_ptr() + rb * h, rb, w, h, ctypes.byref(r), 1 if apply_gamma else 0,
+                                      torch.cuda.current_stream().cuda_stream)
+            return (out, fl) if want_float else out
         capi.lib().renderImage(img.data_ptr(), img.stride(0) * 4, fl.data_ptr() if want_float else None, 12 * w, out.data_ptr(),
                                render_row_bytes(format, w), w, h, ctypes.byref(r), 1 if apply_gamma else 0,
                                torch.cuda.current_stream().cuda_stream)
@@ -719,19 +772,25 @@ class BurstPipeline:
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
 
-    def set_render(self, format: Optional[int] = capi.OUT_RGB16, matrix=None, tone_lut=None):
+    def set_render(self, format: Optional[int] = capi.OUT_RGB16, matrix=None, tone_lut=None, yuv: int = 0):
         """Render the output inside the finish (mfsr_burst_set_render): ``matrix`` = 3 x 3 colour matrix
         (row-major, display = matrix * camera), ``tone_lut`` = N + 1 floats of a tone curve sampled at k/N (``tone_lut_srgb``;
         without one cfg.applyGamma decides), ``format`` = ``capi.OUT_*``.  ``finish`` and ``process*`` then return the integer
         image as a tensor typed for the format: int16 [h, w, 3], uint8 [h, w, 3], uint8 [h, w, 4] or int32 [h, w]; the float
-        image is the rendered one.  ``format=None`` turns rendering off.  Between bursts only."""
+        image is the rendered one.  ``format=None`` turns rendering off.  Between bursts only.
+        ``capi.OUT_NV12`` / ``OUT_P010``: two-plane YUV 4:2:0 with the colour description ``yuv``
+        (``capi.YUV_BT709 | YUV_BT601 | YUV_BT2020``, ``| capi.YUV_FULL``; 0 = BT.709 limited range); the integer image is one
+        flat tensor, uint8 or int16, of which ``yuv_planes`` gives the Y and the (Cb, Cr) plane.  A zoom window must then have
+        even x, y, w and h (ValueError), and sharpening cannot be on."""
+        if format is not None:
+            self.window.check_yuv(int(format))
         out_h, out_w = self.window.aligned[3], self.window.aligned[2]
         with torch.cuda.device(self.device):
             if format is None:
                 self.L.burst_set_render(self._h, None)
                 self._render_lut, fmt = None, capi.OUT_RGB16
             else:
-                r, lut = _render_struct(format, matrix, tone_lut, self.device)
+                r, lut = _render_struct(format, matrix, tone_lut, self.device, yuv)
                 self.L.burst_set_render(self._h, ctypes.byref(r))
                 self._render_lut, fmt = lut, int(format)   # the table is the caller's memory: alive as long as the description
             self.out16 = _render_buffer(fmt, out_h, out_w, self.device)
@@ -807,7 +866,7 @@ class BurstPipeline:
         self.L.burst_finish(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(),
                             self.out_img.data_ptr() if want_float else None,
                             self.out16.data_ptr() if want_u16 else None, self._stream())
-        return self.window(self.out_img if want_float else None), self.window(self.out16 if want_u16 else None)
+        return self.window(self.out_img if want_float else None), self.window.output(self.out16 if want_u16 else None, self._fmt)
 
     def finish_rows(self, row0: int, rows: int) -> torch.Tensor:
         """Finish only HR rows [row0, row0+rows) (reduce-scatter mode); returns the
@@ -1044,7 +1103,7 @@ class BurstPipeline:
                                         self._total_weights.data_ptr(), st)
         self.L.burst_finish_host(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), self.out16.data_ptr(),
                                  out16_host.data_ptr(), st)
-        return self.window(out16_host)
+        return self.window.output(out16_host, self._fmt)
 
     def debug_views(self):
         """(flow, mask, kernel_param, tracking) descriptors of the last add_frame."""
@@ -1086,7 +1145,7 @@ class FrameStream:
     def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
                  window: Optional[Sequence[int]] = None, render: Optional[dict] = None, sharpen: Optional[dict] = None):
         """window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
-        ``BurstPipeline.set_render`` (format, matrix, tone_lut): every output is rendered, typed for the format.  sharpen: the
+        ``BurstPipeline.set_render`` (format, matrix, tone_lut, yuv): every output is rendered, typed for the format.  sharpen: the
         keyword arguments of ``BurstPipeline.set_sharpen``: every output is sharpened inside its finish; with a window the
         library works on the aligned window grown by one 16-pixel ring, as ``BurstPipeline`` does, so the rectangle asked for
         is the crop of the whole-frame sharpened output."""
@@ -1113,11 +1172,15 @@ class FrameStream:
             self.L.stream_create(ctypes.byref(h), ctypes.byref(cfg), radius, 1 if host_frames else 0, base, nbytes)
             self._h = h
             self.window.apply(self.L.stream_set_window, self._h)
+            self._fmt = capi.OUT_RGB16
             if render is not None:
                 fmt = int(render.get("format", capi.OUT_RGB16))
-                r, self._render_lut = _render_struct(fmt, render.get("matrix"), render.get("tone_lut"), self.device)
+                self.window.check_yuv(fmt)
+                r, self._render_lut = _render_struct(fmt, render.get("matrix"), render.get("tone_lut"), self.device,
+                                                     int(render.get("yuv", 0)))
                 self.L.stream_set_render(self._h, ctypes.byref(r))
                 self.out16 = _render_buffer(fmt, self.window.aligned[3], self.window.aligned[2], self.device)
+                self._fmt = fmt
             if sharp is not None:
                 self.L.stream_set_sharpen(self._h, ctypes.byref(sharp))
 
@@ -1141,7 +1204,7 @@ class FrameStream:
         produced = ctypes.c_longlong(-1)
         self.L.stream_push(self._h, frame.data_ptr(), None, self.out16.data_ptr(), ctypes.byref(produced),
                            torch.cuda.current_stream().cuda_stream)
-        return (produced.value, self.window(self.out16)) if produced.value >= 0 else None
+        return (produced.value, self.window.output(self.out16, self._fmt)) if produced.value >= 0 else None
 
     def drain(self):
         """End of the stream: yields the outstanding (t, u16 HR image) outputs."""
@@ -1150,7 +1213,7 @@ class FrameStream:
             self.L.stream_drain(self._h, None, self.out16.data_ptr(), ctypes.byref(produced), torch.cuda.current_stream().cuda_stream)
             if produced.value < 0:
                 return
-            yield produced.value, self.window(self.out16)
+            yield produced.value, self.window.output(self.out16, self._fmt)
 
 
 def view_as_tensor(t: capi.Tex2D, channels: int, device) -> torch.Tensor:
