@@ -27,6 +27,9 @@
 //   * MFSR_NOISE=auto measures the noise model of the robustness stage (cfg.alpha, cfg.beta) on the input frames, after the
 //     steps above and before the burst is created, and prints `noise: alpha A beta B status S` to
 //     stderr (a status other than 0 keeps the defaults); MFSR_NOISE=alpha,beta sets the two values; one GPU only.
+//     MFSR_NOISE=burst measures it on the burst itself instead: the kept frames are aligned to the reference by a throw-away
+//     burst handle and the statistics are taken on the differences of frames a whole number of quads apart, where scene
+//     texture cancels; it prints `noise: alpha A beta B status S points P blocks N`.
 //   * MFSR_MASK_ERODE=1|2 erodes every moved frame's certainty mask by that radius before the merge (ghost suppression,
 //     DESIGN.md section 2.16; 2 = the 5x5 minimum); works with MFSR_GPUS > 1.
 //   * MFSR_SHARPEN="amount[,sigma[,radius[,threshold]]]" sharpens _sr_result inside the finish (an unsharp mask on the linear
@@ -269,17 +272,20 @@ int main(int argc, char** argv)
             shadingMap[i] = (int32_t)px[i] * 16;
         }
     }
-    // MFSR_NOISE=auto: calibrate cfg.alpha / cfg.beta on the input frames; MFSR_NOISE=alpha,beta: set them
-    int noiseMode = 0;  // 0 off, 1 auto, 2 given
+    // MFSR_NOISE=auto: calibrate cfg.alpha / cfg.beta on the input frames; MFSR_NOISE=burst: on the differences of the aligned
+    // frames of the burst; MFSR_NOISE=alpha,beta: set them
+    int noiseMode = 0;  // 0 off, 1 auto, 2 given, 3 burst
     if (const char* e = getenv("MFSR_NOISE")) {
         if (strcmp(e, "auto") == 0)
             noiseMode = 1;
+        else if (strcmp(e, "burst") == 0)
+            noiseMode = 3;
         else {
             char *end = nullptr, *end2 = nullptr;
             const float a = strtof(e, &end);
             const float bt = (end != e && *end == ',') ? strtof(end + 1, &end2) : 0.0f;
             if (end == e || *end != ',' || end2 == end + 1 || *end2 != '\0' || !(a > 0.0f) || !(bt >= 0.0f) || !(a < 1.0f) || !(bt < 1.0f)) {
-                fprintf(stderr, "MFSR_NOISE=%s: auto, or alpha,beta (0 < alpha < 1, 0 <= beta < 1) expected\n", e);
+                fprintf(stderr, "MFSR_NOISE=%s: auto, burst, or alpha,beta (0 < alpha < 1, 0 <= beta < 1) expected\n", e);
                 return 1;
             }
             cfg.alpha = a;
@@ -540,6 +546,41 @@ int main(int argc, char** argv)
             b = nullptr;
             MFSR_OK_OR_DIE(mfsr_burst_create(&b, &cfg, ws, wsBytes));
         }
+    }
+
+    // MFSR_NOISE=burst: the noise model measured on the burst being processed -- the kept (repaired, shaded, matched) frames
+    // aligned to the reference through a handle of its own, which is thrown away: the burst below starts on a fresh one, with
+    // the measured values when the status is 0 (mfsr_burst_calibrate_noise_temporal)
+    if (noiseMode == 3) {
+        std::vector<const uint16_t*> kept;
+        int refAt = -1;
+        for (int k : ids) {
+            if (k == reference) refAt = (int)kept.size();
+            kept.push_back(dframes[k]);
+        }
+        double a = 0.0, bt = 0.0;
+        int32_t st = 2, pts = 0;
+        long long terms = 0;
+        const size_t need = mfsr_noise_temporal_scratch_bytes(&cfg, (int)kept.size());
+        if (need != 0 && refAt >= 0) {
+            void* dscratch = nullptr;
+            HIP_OK(hipMalloc(&dscratch, need));
+            HIP_OK(hipDeviceSynchronize());  // (the raw-domain steps above are through with the first handle)
+            mfsr_burst_destroy(b);
+            b = nullptr;
+            mfsr_burst* cal = nullptr;
+            MFSR_OK_OR_DIE(mfsr_burst_create(&cal, &cfg, ws, wsBytes));
+            MFSR_OK_OR_DIE(mfsr_burst_calibrate_noise_temporal(cal, (int)kept.size(), kept.data(), refAt, 0.0f, 0, dscratch, need, &a, &bt,
+                                                               &st, &pts, &terms, nullptr));
+            mfsr_burst_destroy(cal);
+            HIP_OK(hipFree(dscratch));
+            if (st == 0) {
+                cfg.alpha = (float)a;
+                cfg.beta = (float)bt;
+            }
+            MFSR_OK_OR_DIE(mfsr_burst_create(&b, &cfg, ws, wsBytes));
+        }
+        fprintf(stderr, "noise: alpha %g beta %g status %d points %d blocks %lld\n", a, bt, st, pts, terms);
     }
 
     HIP_OK(hipMalloc((void**)&d8, (size_t)hrW * hrH * 3));

@@ -1004,6 +1004,57 @@ int mfsr_noise_defaults(const mfsr_config* cfg, int32_t black[4], float white[4]
 int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint16_t* const* frames, void* scratchDev, float* alpha,
                                float* beta, int32_t* status, mfsr_stream_t stream);
 
+/* ---- burst noise calibration: the noise model measured on the DIFFERENCES of the frames of a burst.
+ * Two frames whose displacement relative to each other is, at some place, within tol of a whole number of quads sample the
+ * scene there at the same sub-quad phase: their same-colour samples differ by noise only, texture and aliasing cancel.  No
+ * interpolation, so the device stage is exact integer arithmetic like mfsr_noiseStats; blocks, positions q, level and variance
+ * bins, rect, black, sat and the three tables are those of mfsr_noiseStats.
+ * frames: host array of nFrames DEVICE pointers (u16, w x h samples, rows rowBytes bytes apart), 2 <= nFrames <= 64, checked as
+ * mfsr_noiseStats checks its frames, pitch, width and height.  flows: host array of nFrames DEVICE pointers, flows[i] = the flow
+ * field of frame i in the burst's convention (float2 texels, flowW x flowH, rows flowRowBytes bytes apart, flowRowBytes >= 8*flowW
+ * and a multiple of 8, pointer 8-byte aligned; raw-pixel units; reference pixel p corresponds to pixel p + flow of frame i), or
+ * NULL = zero flow (the reference).  (flowW, flowH) is (w/2, h/2) or (w, h), the two sizes mfsr_burst_field_dims gives.
+ * 0 <= tol <= 0.25.
+ * PER BLOCK (bx, by) of rect:
+ *   frame i: f = the texel ((8bx+4)*flowW / w, (8by+4)*flowH / h) (integer division, a plain load); h_i = 0.5f * f;
+ *     the frame is PLACED at the block iff both components are finite and |h| <= 16384; s_i = (int)roundf(h_i) per axis;
+ *   pair j < k of placed frames: d = h_k - h_j (float), s = (int)roundf(d), r = d - (float)s; ACCEPTED iff |r.x| <= tol and
+ *     |r.y| <= tol;
+ *   block A = the 8x8 samples of frame j at (8bx + 2 s_j.x, 8by + 2 s_j.y), block B = those of frame k at A's origin + 2s; both
+ *     wholly inside the frame and all 128 samples < sat, otherwise the pair contributes nothing at this block;
+ *   per position q, p = A, t = A - B:  S = sum of p;  D = sum over r of ((t[r][0] - t[r][1])^2 + (t[r][2] - t[r][3])^2) (64-bit:
+ *     it can reach 2^38); level bin from S as mfsr_noiseStats; variance bin min(bin(D), 271): the last bin saturates.
+ * The tables are summed over all accepted (block, j, k); count[q][l] counts those terms.  Integer arithmetic: independent of
+ * the launch shape and order.  nFrames*(nFrames-1)/2 * blocks of rect < 2^31.  Every argument is checked on the host before
+ * any device call (MFSR_E_INVALID). */
+int mfsr_noiseStatsTemporal(int nFrames, const uint16_t* const* frames, int rowBytes, int w, int h,
+                            const mfsr_float2* const* flows, int flowRowBytes, int flowW, int flowH, const int32_t black[4], int sat,
+                            const int32_t rect[4], float tol, uint32_t* histDev, long long* levelSumDev, long long* countDev,
+                            mfsr_stream_t stream);
+/* mfsr_noise_fit for the tables of mfsr_noiseStatsTemporal: the same operations with var = median / 29.3764 (t[.][0] - t[.][1]
+ * has four times the variance of a sample, so D / (4 var) is chi-square with 8 degrees of freedom).  The 1/12 of the quantiser
+ * is unchanged. */
+int mfsr_noise_fit_temporal(const uint32_t* hist, const long long* levelSum, const long long* count, const int32_t black[4],
+                            const float white[4], int minBlocks, double* alpha, double* beta, int32_t* status, int32_t* points);
+/* bytes of device scratch mfsr_burst_calibrate_noise_temporal needs for nFrames frames of cfg's size (the tables, nFrames - 1
+ * flow fields, one certainty mask); 0 for an invalid cfg or nFrames outside 2 .. 64.  Host arithmetic only. */
+size_t mfsr_noise_temporal_scratch_bytes(const mfsr_config* cfg, int nFrames);
+/* The noise model of the burst `frames` (nFrames device frames, dense rows, the burst's size), measured on the burst itself.
+ * Between bursts only (MFSR_E_INVALID while frames are pending).  Starts a burst on b (as mfsr_burst_begin does, with no
+ * accumulators attached), makes frames[reference] the reference (mfsr_burst_set_reference), aligns the other frames with
+ * mfsr_burst_align_frames (flows into the scratch, one mask buffer for all: the masks are ignored, so cfg.alpha and cfg.beta
+ * have no part in the result), one mfsr_noiseStatsTemporal over all frames (the reference with a NULL flow) with black, sat and
+ * rect of mfsr_noise_defaults, one wait for the stream, mfsr_noise_fit_temporal with white of mfsr_noise_defaults.  tol <= 0 =
+ * 1/16; minBlocks <= 0 = mfsr_noise_defaults' 200.  scratchDev: scratchBytes >= mfsr_noise_temporal_scratch_bytes(cfg, nFrames)
+ * of device memory, 256-byte aligned.  Fuses nothing and changes neither the frames nor cfg: the caller writes *alpha and *beta
+ * into the mfsr_config of the burst it creates next (doubles, as mfsr_noise_fit gives them).  The handle is left as mfsr_burst_begin and mfsr_burst_set_reference leave
+ * it: the next burst starts with its own begin / set_reference as always.  *status as mfsr_noise_fit; 2 is the ordinary answer
+ * for a burst without a phase-matched pair.  *points (may be NULL): points of the fit.  *blocks (may be NULL): the accepted
+ * (block, pair) terms, the sum of count[0][.]. */
+int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, const uint16_t* const* frames, int reference, float tol,
+                                        int minBlocks, void* scratchDev, size_t scratchBytes, double* alpha, double* beta,
+                                        int32_t* status, int32_t* points, long long* blocks, mfsr_stream_t stream);
+
 /* ---- ghost suppression: erosion of the certainty mask between stage F and stage G.  Stage F decides
  * every cell on its own; at the rim of a moving object single cells pass although their neighbours fail, and the merge shows
  * a faint outline of the object there.  The erosion replaces every colour certainty by its minimum over a (2r+1) x (2r+1)

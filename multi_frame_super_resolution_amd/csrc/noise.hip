@@ -30,6 +30,7 @@ constexpr int kNoiseThreads = 1024;
 constexpr int kNoiseWaves = kNoiseThreads / 64;
 constexpr int kNoiseMaxChunk = 65535;          // blocks per workgroup: a 16-bit counter cannot overflow
 constexpr double kChi2x2 = 14.6882;            // 2 x the median of chi-square with 8 degrees of freedom
+constexpr double kChi2x2Temporal = 29.3764;    // 4 x that median: D of a difference of two frames
 
 struct NoiseGeom {
     int pitch;               // bytes
@@ -237,9 +238,12 @@ extern "C" int mfsr_noiseStats(int nFrames, const uint16_t* const* frames, int p
     return mfsr_launch_status("k_noiseStats");
 }
 
-// Host only.  The operations, one by one, are those of DESIGN.md §2.15 (the tests restate them in numpy).
-extern "C" int mfsr_noise_fit(const uint32_t* hist, const long long* levelSum, const long long* count, const int32_t black[4],
-                              const float white[4], int minBlocks, double* alpha, double* beta, int32_t* status, int32_t* points)
+// Host only.  The operations, one by one, are those of DESIGN.md §2.15 (the tests restate them in numpy).  divisor: what the
+// median of D is divided by to give the variance -- kChi2x2 for the blocks of one frame, twice that for the difference of two
+// frames (§2.22: the pair differences of a difference have four times the variance, mfsr_noise_fit_temporal).
+static int noise_fit_rule(const uint32_t* hist, const long long* levelSum, const long long* count, const int32_t black[4],
+                          const float white[4], int minBlocks, double divisor, double* alpha, double* beta, int32_t* status,
+                          int32_t* points)
 {
     MFSR_REQUIRE(hist != nullptr && levelSum != nullptr && count != nullptr && black != nullptr && white != nullptr);
     MFSR_REQUIRE(alpha != nullptr && beta != nullptr && status != nullptr);
@@ -267,7 +271,7 @@ extern "C" int mfsr_noise_fit(const uint32_t* hist, const long long* levelSum, c
                 cum += hv;
             }
             if (!found) continue;  // (a count the histogram does not back)
-            const double varDn = med / kChi2x2;
+            const double varDn = med / divisor;
             const double wq = (double)white[q];
             const double x = ((double)levelSum[q * kNL + l] / (16.0 * (double)c) - (double)black[q]) / wq;
             const double t = varDn - 1.0 / 12.0;
@@ -300,4 +304,17 @@ extern "C" int mfsr_noise_fit(const uint32_t* hist, const long long* levelSum, c
     *beta = b;
     *status = a > 0.0 ? 0 : 3;
     return MFSR_OK;
+}
+
+extern "C" int mfsr_noise_fit(const uint32_t* hist, const long long* levelSum, const long long* count, const int32_t black[4],
+                              const float white[4], int minBlocks, double* alpha, double* beta, int32_t* status, int32_t* points)
+{
+    return noise_fit_rule(hist, levelSum, count, black, white, minBlocks, kChi2x2, alpha, beta, status, points);
+}
+
+extern "C" int mfsr_noise_fit_temporal(const uint32_t* hist, const long long* levelSum, const long long* count,
+                                       const int32_t black[4], const float white[4], int minBlocks, double* alpha, double* beta,
+                                       int32_t* status, int32_t* points)
+{
+    return noise_fit_rule(hist, levelSum, count, black, white, minBlocks, kChi2x2Temporal, alpha, beta, status, points);
 }

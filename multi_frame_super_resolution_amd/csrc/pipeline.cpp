@@ -2685,6 +2685,100 @@ extern "C" int mfsr_burst_calibrate_noise(mfsr_burst* b, int nFrames, const uint
     return MFSR_OK;
 }
 
+// ---- burst noise calibration: the frames of the burst aligned to one of them, the block statistics of their
+//      differences where two frames are a whole number of quads apart (csrc/noise_temporal.hip), the fit on the host -------------
+namespace {
+struct TemporalScratch {
+    size_t flow0, flowBytes, mask, total;  // offsets after the tables; bytes of one flow field
+    int tw, th, hw, hh;
+};
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+bool temporal_scratch(const mfsr_config* cfg, int nFrames, TemporalScratch* s)
+{
+    if (cfg == nullptr || nFrames < 2 || nFrames > 64 || validate(cfg) != MFSR_OK) return false;
+    s->hw = cfg->width / 2;
+    s->hh = cfg->height / 2;
+    s->tw = cfg->mono ? cfg->width : s->hw;
+    s->th = cfg->mono ? cfg->height : s->hh;
+    s->flow0 = up256(MFSR_NOISE_SCRATCH_BYTES);
+    s->flowBytes = up256((size_t)8 * s->tw * s->th);
+    s->mask = s->flow0 + (size_t)(nFrames - 1) * s->flowBytes;
+    s->total = s->mask + up256((size_t)16 * s->hw * s->hh);
+    return true;
+}
+}  // namespace
+
+extern "C" size_t mfsr_noise_temporal_scratch_bytes(const mfsr_config* cfg, int nFrames)
+{
+    TemporalScratch s;
+    return temporal_scratch(cfg, nFrames, &s) ? s.total : 0;
+}
+
+extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, const uint16_t* const* frames, int reference, float tol,
+                                                   int minBlocks, void* scratchDev, size_t scratchBytes, double* alpha, double* beta,
+                                                   int32_t* status, int32_t* points, long long* blocks, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && frames && scratchDev && alpha && beta && status);
+    MFSR_REQUIRE(nFrames >= 2 && nFrames <= 64 && reference >= 0 && reference < nFrames);
+    MFSR_REQUIRE(!(tol > 0.25f) && tol == tol);  // (<= 0: the default)
+    for (int k = 0; k < nFrames; k++) MFSR_REQUIRE(frames[k] != nullptr && ((uintptr_t)frames[k] & 1) == 0);
+    const mfsr_config& c = b->cfg;
+    TemporalScratch s;
+    MFSR_REQUIRE(temporal_scratch(&c, nFrames, &s));
+    MFSR_REQUIRE(((uintptr_t)scratchDev & 255) == 0 && scratchBytes >= s.total);
+    if (b->pend.n > 0 || b->heldHas || b->nUnp != 0) {  // between bursts only
+        fprintf(stderr, "mfsr: mfsr_burst_calibrate_noise_temporal with frames pending (flush or finish the burst first)\n");
+        return MFSR_E_INVALID;
+    }
+    int32_t black[4], sat = 0, defBlocks = 0, r[4];
+    float white[4];
+    TRY(mfsr_noise_defaults(&c, black, white, &sat, &defBlocks, r));
+    const float useTol = tol > 0.0f ? tol : 0.0625f;
+    const int useBlocks = minBlocks > 0 ? minBlocks : defBlocks;
+
+    // a new burst on this handle (what mfsr_burst_begin resets; no accumulators: nothing is fused)
+    TRY(flush_pending(b, stream));
+    memset(b->paths, 0, sizeof(b->paths));
+    b->sharpenedFinishes = 0;
+    TRY(mfsr_burst_set_reference(b, frames[reference], stream));
+
+    char* base = (char*)scratchDev;
+    const uint16_t* moved[64];
+    const mfsr_float2* flows[64];
+    mfsr_float2* flowOut[64];
+    mfsr_float4* maskOut[64];
+    int m = 0;
+    for (int k = 0; k < nFrames; k++) {
+        if (k == reference) {
+            flows[k] = nullptr;
+            continue;
+        }
+        moved[m] = frames[k];
+        flowOut[m] = (mfsr_float2*)(base + s.flow0 + (size_t)m * s.flowBytes);
+        maskOut[m] = (mfsr_float4*)(base + s.mask);  // one buffer for every frame: the masks are not read
+        flows[k] = flowOut[m];
+        m++;
+    }
+    TRY(mfsr_burst_align_frames(b, m, moved, nullptr, flowOut, 8 * s.tw, maskOut, 16 * s.hw, stream));
+    uint32_t* histDev = (uint32_t*)base;
+    long long* sumDev = (long long*)(base + sizeof(uint32_t) * MFSR_NOISE_HIST_ENTRIES);
+    long long* countDev = sumDev + MFSR_NOISE_LEVEL_ENTRIES;
+    TRY(mfsr_noiseStatsTemporal(nFrames, frames, 2 * c.width, c.width, c.height, flows, 8 * s.tw, s.tw, s.th, black, sat, r, useTol,
+                                histDev, sumDev, countDev, stream));
+    std::vector<unsigned char> host(MFSR_NOISE_SCRATCH_BYTES);
+    TRY(download(host.data(), scratchDev, host.size(), stream));
+    const uint32_t* hist = (const uint32_t*)host.data();
+    const long long* sum = (const long long*)(host.data() + sizeof(uint32_t) * MFSR_NOISE_HIST_ENTRIES);
+    const long long* count = sum + MFSR_NOISE_LEVEL_ENTRIES;
+    TRY(mfsr_noise_fit_temporal(hist, sum, count, black, white, useBlocks, alpha, beta, status, points));
+    if (blocks) {
+        long long n = 0;
+        for (int l = 0; l < 64; l++) n += count[l];
+        *blocks = n;
+    }
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_debug_views(mfsr_burst* b, mfsr_tex2d* flow, mfsr_tex2d* mask, mfsr_tex2d* kernelParam,
                                       mfsr_tex2d* tracking)
 {

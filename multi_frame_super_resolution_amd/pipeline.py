@@ -327,10 +327,48 @@ def noise_stats(frames: Sequence[torch.Tensor], cfg: capi.Config, rect: Optional
     return NoiseStats(hist, level_sum, count)
 
 
-def noise_fit(stats, cfg: capi.Config, min_blocks: Optional[int] = None):
+NOISE_TEMPORAL_TOL = 1.0 / 16.0   # the default phase tolerance of burst noise calibration, in quads
+
+
+def noise_stats_temporal(frames: Sequence[torch.Tensor], flows: Sequence[Optional[torch.Tensor]], cfg: capi.Config,
+                         tol: float = NOISE_TEMPORAL_TOL, rect: Optional[Sequence[int]] = None,
+                         sat: Optional[int] = None) -> NoiseStats:
+    """Block statistics of the DIFFERENCES of the frames of a burst (mfsr_noiseStatsTemporal), exact:
+    wherever two frames are displaced against each other by a whole number of quads to within ``tol`` (0 .. 0.25 quads), the
+    tables of ``noise_stats`` are taken on frame j (levels) and on the difference of the two frames (variances).  ``frames``:
+    2 .. 64 frames as for ``noise_stats``.  ``flows``: per frame its flow field in the burst's convention -- a float32 device
+    tensor [fh, fw, 2] with contiguous texels and one row stride, (fh, fw) = ``BurstPipeline.field_dims()[0]`` -- or None for
+    zero flow (the reference).  rect / sat None = ``noise_defaults``.  Fit the result with ``noise_fit(..., temporal=True)``."""
+    frames, flows = list(frames), list(flows)
+    dev, pitch = _raw_frames(frames, cfg)
+    if len(flows) != len(frames):
+        raise ValueError("one flow field (or None) per frame is needed")
+    given = [f for f in flows if f is not None]
+    shape = tuple(given[0].shape) if given else (cfg.height // 2, cfg.width // 2, 2)
+    fpitch = given[0].stride(0) * 4 if given else 8 * shape[1]
+    for f in given:
+        if (f.device != dev or f.dtype != torch.float32 or f.dim() != 3 or tuple(f.shape) != shape or shape[2] != 2
+                or f.stride(2) != 1 or f.stride(1) != 2 or f.stride(0) * 4 != fpitch):
+            raise ValueError("flows must be float32 [fh, fw, 2] tensors of one shape and row stride on the frames' device")
+    d = noise_defaults(cfg)
+    r = d.rect if rect is None else tuple(int(v) for v in rect)
+    n = len(frames)
+    with torch.cuda.device(dev):
+        hist = torch.empty(4, 64, 272, dtype=torch.int32, device=dev)
+        level_sum = torch.empty(4, 64, dtype=torch.int64, device=dev)
+        count = torch.empty(4, 64, dtype=torch.int64, device=dev)
+        fptrs = (ctypes.c_void_p * n)(*[None if f is None else f.data_ptr() for f in flows])
+        capi.lib().noiseStatsTemporal(n, _ptr_table(frames), pitch, cfg.width, cfg.height, fptrs, fpitch, shape[1], shape[0],
+                                      _i4(d.black), d.sat if sat is None else int(sat), _i4(r), float(tol), hist.data_ptr(),
+                                      level_sum.data_ptr(), count.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return NoiseStats(hist, level_sum, count)
+
+
+def noise_fit(stats, cfg: capi.Config, min_blocks: Optional[int] = None, temporal: bool = False):
     """(alpha, beta, status, points) of mfsr_noise_fit on the tables of ``noise_stats`` (tensors on any device or arrays):
     the least-squares line through (level, variance) of every well-filled level bin, as Python floats (doubles).  status 0 ok,
-    2 unmeasurable (alpha = beta = 0), 3 alpha <= 0.  Host only: no device is needed."""
+    2 unmeasurable (alpha = beta = 0), 3 alpha <= 0.  Host only: no device is needed.  ``temporal=True``: the tables are those of
+    ``noise_stats_temporal`` (mfsr_noise_fit_temporal: the variances are those of a difference of two frames)."""
     import numpy as np
 
     def host(t, dtype):
@@ -343,9 +381,10 @@ def noise_fit(stats, cfg: capi.Config, min_blocks: Optional[int] = None):
     d = noise_defaults(cfg)
     a, b = ctypes.c_double(), ctypes.c_double()
     st, n = ctypes.c_int32(), ctypes.c_int32()
-    capi.lib().noise_fit(hist.ctypes.data, level_sum.ctypes.data, count.ctypes.data, _i4(d.black),
-                         (ctypes.c_float * 4)(*d.white), d.min_blocks if min_blocks is None else int(min_blocks),
-                         ctypes.byref(a), ctypes.byref(b), ctypes.byref(st), ctypes.byref(n))
+    fit = capi.lib().noise_fit_temporal if temporal else capi.lib().noise_fit
+    fit(hist.ctypes.data, level_sum.ctypes.data, count.ctypes.data, _i4(d.black),
+        (ctypes.c_float * 4)(*d.white), d.min_blocks if min_blocks is None else int(min_blocks),
+        ctypes.byref(a), ctypes.byref(b), ctypes.byref(st), ctypes.byref(n))
     return a.value, b.value, st.value, n.value
 
 
@@ -926,6 +965,32 @@ class BurstPipeline:
         q16 = [[int(gains[3 * k + c]) for c in range(3)] for k in range(n)]
         self.exposure = Exposure(r, [[g / 65536.0 for g in row] for row in q16], [int(s) for s in status],
                                  [[int(levels[5 * k + i]) for i in range(5)] for k in range(n)], q16)
+
+    def calibrate_noise(self, frames: Sequence[torch.Tensor], reference: int = 0, tol: Optional[float] = None,
+                        min_blocks: Optional[int] = None):
+        """(alpha, beta, status, points, blocks) of the noise model var = alpha * I + beta measured on the burst itself
+        (mfsr_burst_calibrate_noise_temporal): the frames are aligned to ``frames[reference]`` and the
+        statistics are taken on the differences of frames that are a whole number of quads apart, so scene texture cancels
+        where the single-frame ``calibrate_noise`` function reads it as noise.  tol None = 1/16 quad, min_blocks None =
+        ``noise_defaults``.  status 0 ok, 2 unmeasurable (no phase-matched pair of frames, too few levels: alpha = beta = 0),
+        3 alpha <= 0; points = points of the fit, blocks = accepted (block, pair) terms.  Between bursts only.  Nothing is
+        fused and neither the frames nor cfg change: alpha and beta are construction-time configuration, so write them into the
+        config of the pipeline created next."""
+        frames = self._checked(frames, clone=False)
+        n = len(frames)
+        nbytes = self.L.noise_temporal_scratch_bytes(ctypes.byref(self.cfg), n)
+        if nbytes == 0:
+            raise ValueError("burst noise calibration needs 2 .. 64 frames")
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            base = (scratch.data_ptr() + 255) // 256 * 256
+            a, b = ctypes.c_double(), ctypes.c_double()
+            st, pts, blocks = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_longlong()
+            self.L.burst_calibrate_noise_temporal(self._h, n, _ptr_table(frames), int(reference), 0.0 if tol is None else float(tol),
+                                                  0 if min_blocks is None else int(min_blocks), base, nbytes, ctypes.byref(a),
+                                                  ctypes.byref(b), ctypes.byref(st), ctypes.byref(pts), ctypes.byref(blocks),
+                                                  self._stream())
+        return a.value, b.value, st.value, pts.value, blocks.value
 
     def _run(self, work, r: int, kept: Iterable[int]):
         """The burst itself: reference products of frame ``r``, the ``kept`` frames, finish."""

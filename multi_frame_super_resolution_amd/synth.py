@@ -93,7 +93,8 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
                black: float = 256.0, white: float = 4095.0 - 256.0, shift_seed: Optional[int] = None,
                first_is_reference: bool = True,
                angles_deg: Optional[List[float]] = None,
-               keep: Optional[Sequence[int]] = None, _composite=None) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+               keep: Optional[Sequence[int]] = None, _composite=None,
+               shifts: Optional[torch.Tensor] = None) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
     """Returns (raw frames [H,W] int16 holding u16 bit patterns, shifts [N,2] in LR px, ground truth [3,sH,sW]).
 
     ``seed`` fixes the scene; ``shift_seed`` (default: same stream) fixes the per-frame shifts and
@@ -102,7 +103,8 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
     these frame numbers are rendered (the others come back as None) while the random stream advances as if all were -- a
     rank of a sharded burst gets exactly the frames the one-GPU burst has at those positions.  ``_composite(scene, k)``
     (``make_moving_burst``): the HR scene frame k is rendered from (k = None: the ground truth's); it draws nothing from the
-    random stream."""
+    random stream.  ``shifts``: an [N, 2] tensor of per-frame shifts in LR pixels that replaces the drawn ones, row 0 included
+    (the random stream advances as if they had been used, so the noise of every frame is the one of the call without it)."""
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     s = scale
@@ -112,9 +114,10 @@ def make_burst(width: int, height: int, frames: int, scale: int = 2, mono: bool 
     if shift_seed is not None:
         gen = torch.Generator(device=device)
         gen.manual_seed(shift_seed)
-    shifts = (torch.rand(frames, 2, generator=gen, device=device) * 2 - 1) * max_shift
+    drawn = (torch.rand(frames, 2, generator=gen, device=device) * 2 - 1) * max_shift
     if first_is_reference:
-        shifts[0] = 0
+        drawn[0] = 0
+    shifts = drawn if shifts is None else torch.as_tensor(shifts, dtype=drawn.dtype, device=device).reshape(frames, 2).clone()
     out = []
     yy, xx = torch.meshgrid(torch.arange(height, device=device), torch.arange(width, device=device), indexing="ij")
     cfa_idx = ((yy % 2) + (xx % 2))  # RGGB: (0,0)->R=0, (0,1)/(1,0)->G=1, (1,1)->B=2
