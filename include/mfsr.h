@@ -43,6 +43,7 @@ extern "C" {
 
 #define MFSR_VERSION 100
 #define MFSR_MAX_FUSE_GROUP 4 /* frames one warp+fuse call takes (mfsr_accumulateSuperResFullN, cfg.pairFrames) */
+#define MFSR_MAX_BURST_FUSE 16 /* frames the burst form takes: up to four such groups (mfsr_accumulateSuperResBurst) */
 
 typedef void* mfsr_stream_t; /* hipStream_t */
 
@@ -151,6 +152,19 @@ int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* const* dataIn
                                       mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale,
                                       int strideOut, int strideMask, int accumulatorsUndefined, int x0, int y0, int w, int h,
                                       mfsr_stream_t stream);
+
+/* The burst form of mfsr_accumulateSuperResFullN: nFrames = 8, 12 or 16 frames (whole groups of MFSR_MAX_FUSE_GROUP, at most
+ * MFSR_MAX_BURST_FUSE) in ONE pass over the accumulators -- both plane-sets are read (not at all with accumulatorsUndefined)
+ * and written once for the whole burst instead of once per group.  Bit for bit the result of nFrames / 4 successive FullN
+ * calls of four frames each on the same inputs, accumulatorsUndefined given to the first.  Only where the x2 Bayer tile kernel
+ * applies: scale 2, a Bayer pattern (mfsr_set_cfa_pattern), kernelParam and shifts at half the raw size, raw dimensions
+ * multiples of 4; everything else returns MFSR_E_UNSUPPORTED and touches nothing (other frame counts: MFSR_E_INVALID).
+ * The images are given as descriptors: imgOut / totalWeights float3, (scale*rawWidth) x (scale*rawHeight), 16-byte aligned rows;
+ * certaintyMasks float4 at half the raw size, all with one row pitch; dataIn dense uint16_t rows. */
+int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                 const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                 mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                 mfsr_stream_t stream);
 
 /* ---- B/E/H/I: kernel.cu --------------------------------------------------- */
 int mfsr_squaredSum(const float* inTiles, float* outValues, int maxShift, int tileSize, int tileCount,
@@ -602,7 +616,7 @@ int mfsr_burst_set_reference_rows(mfsr_burst* b, const uint16_t* rawRef, int hrR
  * accumulator traffic, and everything that depends on the reference only -- kernel parameters, tap weights -- once
  * per pixel): between groups up to group - 1 frames are still waiting -- their raw buffers must stay untouched and
  * the accumulators do not contain them -- until the next add_frame, mfsr_burst_flush, finish or finish_rows has been
- * issued on the stream.
+ * issued on the stream.  With mfsr_burst_hold_fuse(b, 1) whole groups wait as well, until flush / finish (see there).
  * With cfg.asyncFuse the warp+fuse launches go to a high-priority stream the burst owns (ordered by
  * events after the alignment on the caller's stream), so the fuse of frames k, k+1 overlaps the
  * alignment of k+2, k+3.  The caller's stream sees the accumulators complete only after
@@ -614,10 +628,31 @@ int mfsr_burst_add_frame(mfsr_burst* b, const uint16_t* raw, int isReference, mf
  * overwrites them (as if zeroed), which saves the memset and the first read of both planes.  If no frame
  * is added before flush / finish, they are zeroed then.  Without this call the caller zeroes them. */
 int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3* totalWeights, mfsr_stream_t stream);
-/* fuse a frame that is still waiting for its partner and make the caller's stream wait for every fuse issued so far */
+/* fuse the frames that are still waiting -- for the rest of their group, or, with the burst hold, for the burst launch -- and
+ * make the caller's stream wait for every fuse issued so far */
 int mfsr_burst_flush(mfsr_burst* b, mfsr_stream_t stream);
+/* Burst hold (opt-in per context, off by default).  enable != 0: a complete group is still ALIGNED when its last frame
+ * arrives, but its warp+fuse is HELD and leaves together with the burst's other complete groups as ONE launch
+ * (mfsr_accumulateSuperResBurst: the accumulators are read and written once per burst instead of once per group) at
+ * mfsr_burst_flush / finish / finish_rows / set_reference, or when the next frame needs a held frame's ring slot (the ring
+ * has max(8, min(cfg.frames, 16)) slots).  A remainder of 1 .. 3 frames follows as an ordinary launch; fewer than two held
+ * groups take the ordinary launches, so bursts of at most 7 frames behave exactly as without the hold.  Results are bit for
+ * bit those of the group-by-group launches.
+ * THE CONTRACT IT CHANGES: the raw buffers of ALL frames added since the last flush / finish must stay untouched, and the
+ * accumulators are incomplete, until flush / finish / finish_rows / set_reference has been issued (without the hold: until
+ * the next add_frame).  Every library call that reads the accumulators or takes ring slots flushes the hold itself.
+ * Only the plain resident path is held: whole-frame x2 Bayer bursts on the caller's stream.  cfg.asyncFuse, zoom windows,
+ * host bursts (add_frame_host), mfsr_burst_fuse_rows, streams and the joint mode are unchanged. */
+int mfsr_burst_hold_fuse(mfsr_burst* b, int enable);
+/* burst launches since mfsr_burst_begin and the four-frame groups they fused (host-side counters; not an mfsr_path counter:
+ * a burst launch needs eight frames) */
+int mfsr_burst_fuse_stats(const mfsr_burst* b, int* burstLaunches, int* groupsFused);
+/* process-wide switch of the burst hold for A/B (default 1; MFSR_BURST_FUSE=0 in the environment): 0 = every context fuses
+ * group by group whatever mfsr_burst_hold_fuse said */
+int mfsr_set_burst_fuse(int enable);
 /* ApplyWeighting (+fallback) + optional gamma; outImg float3 HR (may be NULL),
- * out16 dense interleaved u16 HR (may be NULL). */
+ * out16 dense interleaved u16 HR (may be NULL).  Fuses whatever is still waiting first (mfsr_burst_flush), the groups of
+ * the burst hold included. */
 int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
                       uint16_t* out16, mfsr_stream_t stream);
 /* finish restricted to HR rows [row0, row0+rows) (pointers are those of the
@@ -1245,7 +1280,9 @@ int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes);
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the
- * number of frames those launches fused (2 per launch with pairFrames). */
+ * number of frames those launches fused (2 per launch with pairFrames).  A burst launch of the
+ * burst hold (mfsr_burst_hold_fuse) counts as one launch per group it fused, so that
+ * totalMs / launches stays the time per group of mfsr_burst_group_size frames. */
 int mfsr_burst_timing(mfsr_burst* b, int enable);
 int mfsr_burst_timing_read(mfsr_burst* b, double* totalMs, int* launches, int* frames);
 /* last per-frame flow field (tracking resolution, raw-pixel units) and mask,

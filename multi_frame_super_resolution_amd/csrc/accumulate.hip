@@ -121,6 +121,12 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
                                       int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
                                       mfsr_stream_t stream);  // accumulate_fast.hip
 
+int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
+                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
+                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
+                                       mfsr_stream_t stream);  // accumulate_fast.hip
+
 static int check_superres_args(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                                const mfsr_float4* certaintyMask, const mfsr_tex2d& kernelParam, const mfsr_tex2d& shifts,
                                int dimX, int dimY, int outW, int strideOut, int strideMask)
@@ -348,4 +354,37 @@ extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* 
     return mfsr_accumulateSuperResFullRows(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel,
                                            blackLevel, dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined, 0,
                                            scale * dimY, stream);
+}
+
+// 8, 12 or 16 frames -- whole groups of four -- in one pass over the accumulators: bit for bit what nFrames / 4 successive
+// mfsr_accumulateSuperResFullN calls of four frames give (accumulatorsUndefined on the first of them), where the x2 Bayer
+// tile kernel serves the geometry; MFSR_E_UNSUPPORTED (nothing touched) where it does not.  The images are described by
+// descriptors: imgOut / totalWeights float3 (scale*dimX) x (scale*dimY), certaintyMasks float4 at half the raw size (one
+// pitch for all), the raw frames dense uint16_t rows of dimX samples.
+extern "C" int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                            const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                            mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                            mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(dataIn && certaintyMasks && shifts);
+    MFSR_REQUIRE(nFrames >= 2 * MFSR_MAX_FUSE_GROUP && nFrames <= MFSR_MAX_BURST_FUSE && (nFrames % MFSR_MAX_FUSE_GROUP) == 0);
+    MFSR_REQUIRE(scale >= 1 && scale <= 8);
+    MFSR_REQUIRE(imgOut.width > 0 && imgOut.height > 0 && (imgOut.width % scale) == 0 && (imgOut.height % scale) == 0);
+    MFSR_REQUIRE(totalWeights.width == imgOut.width && totalWeights.height == imgOut.height && totalWeights.pitch == imgOut.pitch);
+    const int dimX = imgOut.width / scale, dimY = imgOut.height / scale;
+    const mfsr_float4* masks[MFSR_MAX_BURST_FUSE];
+    for (int n = 0; n < nFrames; n++) {
+        MFSR_REQUIRE(certaintyMasks[n].width == (dimX + 1) / 2 && certaintyMasks[n].height == (dimY + 1) / 2 &&
+                     certaintyMasks[n].pitch == certaintyMasks[0].pitch);
+        masks[n] = (const mfsr_float4*)certaintyMasks[n].ptr;
+        const int rc = check_superres_args(dataIn[n], (mfsr_float3*)imgOut.ptr, (mfsr_float3*)totalWeights.ptr, masks[n], kernelParam,
+                                           shifts[n], dimX, dimY, dimX * scale, imgOut.pitch, certaintyMasks[0].pitch);
+        if (rc) return rc;
+    }
+    if (g_accumulate_fast != 2 || scale != 2) return MFSR_E_UNSUPPORTED;
+    const int r = mfsr_try_launch_accumulate2x_burst(nFrames, dataIn, (mfsr_float3*)imgOut.ptr, (mfsr_float3*)totalWeights.ptr, masks,
+                                                     kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY, imgOut.pitch,
+                                                     certaintyMasks[0].pitch, accumulatorsUndefined ? 1 : 0, stream);
+    if (r == 1) return mfsr_launch_status("accumulateSuperResBurst");
+    return r < 0 ? MFSR_E_INVALID : MFSR_E_UNSUPPORTED;
 }

@@ -1314,6 +1314,427 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     }
 }
 
+// ---- burst form of the x2 Bayer tile kernel: G groups of four frames in one launch ------------------
+// A burst of 16 frames used to be four launches of k_accumulate2xTile<CFA, 4>, each a complete pass over both accumulator
+// plane-sets.  Here a workgroup stages its two row segments ONCE (zeroes on a fresh launch, else the global_load_lds copy),
+// runs the four-frame group arithmetic of k_accumulate2xTile G times on them -- a rolled loop, each turn stages that group's flow
+// and certainty texels and adds the group's sums into the staged planes -- and writes them back ONCE: G - 1 reads and G - 1
+// write-backs of 48 B per HR pixel less, and one kernel ramp and tail instead of G.
+// Bit identity with the G launches it replaces dictates the structure: a pixel's value sums AND weight sums of a group are
+// formed from zero in registers and added to the staged planes at the end of their group (carrying the weight sums across
+// groups in registers would be another association), so both planes stay in LDS for the whole launch and the field texels
+// cannot borrow the weight plane's bytes (TILE_LDS_ALIAS): 48.6 KB of LDS, three workgroups per CU, a 168-register budget.
+// The admission rules are those of the launches it replaces (the ALIAS form: rounded flow within the 8-bit window around the
+// tile's own, 8:8 bits per pixel), so the same strips take the in-kernel straight path; a write-back followed by a read is
+// exact, so the straight path sees the same plane values either way.
+// What does not depend on the group is taken once per launch: the kernel-parameter texels, the column and row fractions and
+// the strip's mixed kernel parameters.  The frames of all groups travel in the kernel arguments, indexed by the (uniform) group.
+// Every barrier is reached by whole workgroups: the margin rows leave before the first one, and STRIP_MARGIN is a multiple
+// of the tile height, so a workgroup is live or not as a whole.  nGroups (2 .. TILE_BURST_GROUPS) is a kernel argument.
+#define TILE_BURST_GROUPS 4
+struct BurstFrames {
+    TileFrame f[4 * TILE_BURST_GROUPS];
+};
+
+template <int CFA>
+__global__ void __launch_bounds__(256, 3)
+    k_accumulate2xTileBurst(BurstFrames fr, int nGroups, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
+                            Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int tilesX,
+                            int tilesY, int tilesPerXcd, int fresh)
+{
+    constexpr int NF = 4, FC = TILE_COLS, FROWS = 3;
+    const int pid = (int)blockIdx.x;
+    const int tile = tilesPerXcd > 0 ? (pid & 7) * tilesPerXcd + (pid >> 3) : pid;  // XCD-aware order, see k_accumulate2xTile
+    if (tile >= tilesX * tilesY) return;  // whole workgroup (uniform), before any barrier
+    const int bIdY = tile / tilesX, bIdX = tile - bIdY * tilesX;
+    __shared__ __attribute__((aligned(16))) float4 sAcc[2][4][192];
+    __shared__ float4 sK[FROWS][FC];  // .w = 1 if the texel is PSD and finite, else 0
+    __shared__ float2 sF[NF][FROWS][FC];
+    __shared__ __attribute__((aligned(16))) float sMp[4][3][NF][TILE_COLS];  // [CFA position][mask row][frame][column]
+    constexpr int EP = 3 * NF * TILE_COLS * 4;
+    __shared__ uint32_t sUnsat[3][TILE_COLS];
+    __shared__ __attribute__((aligned(16))) float sColA[256];
+    __shared__ float sRowB[4];
+    const int lx = threadIdx.x, ly = threadIdx.y;
+    const int t = ly * 64 + lx;
+    const int tx = bIdX * 64 + lx;
+    const int Y = bIdY * 4 + ly;
+    const int hrW = 2 * dimX, hrH = 2 * dimY;
+    const int X0 = 4 * tx;
+    const int fw = kernelParam.width, fh = kernelParam.height;  // == hrW/4, hrH/4 (checked on the host)
+    const int mw = dimX / 2, mh = dimY / 2;
+    // flow and certainty texels of group g (and which of them are not saturated)
+    auto stage_fields = [&](int g) {
+        if (t < 3 * TILE_COLS) {
+            const int r = t / TILE_COLS, c = t - r * TILE_COLS;
+            const int gy = bIdY - 1 + r, gx = bIdX * 64 - 1 + c;
+            const int fy = clampi(gy, 0, fh - 1), fx = clampi(gx, 0, fw - 1);
+            uint32_t unsat = 0;
+#pragma unroll
+            for (int n = 0; n < NF; n++) {
+                const TileFrame& F = fr.f[4 * g + n];
+                sF[n][r][c] = row_ptr((const float2*)F.shifts.ptr, F.shifts.pitch, fy)[fx];
+                const float4 m = row_ptr(F.mask, strideMask, clampi(gy, 0, mh - 1))[clampi(gx, 0, mw - 1)];
+                const float mc[3] = {sane(m.x), sane(m.y), sane(m.z)};
+                sMp[0][r][n][c] = mc[Cfa<CFA>::col(0, 0)];
+                sMp[1][r][n][c] = mc[Cfa<CFA>::col(0, 1)];
+                sMp[2][r][n][c] = mc[Cfa<CFA>::col(1, 0)];
+                sMp[3][r][n][c] = mc[Cfa<CFA>::col(1, 1)];
+                if (!(mc[0] == 1.0f && mc[1] == 1.0f && mc[2] == 1.0f)) unsat |= 1u << n;
+            }
+            sUnsat[r][c] = unsat;
+        }
+    };
+    if (t < 3 * TILE_COLS) {
+        const int r = t / TILE_COLS, c = t - r * TILE_COLS;
+        const int fy = clampi(bIdY - 1 + r, 0, fh - 1), fx = clampi(bIdX * 64 - 1 + c, 0, fw - 1);
+        float4 k = row_ptr((const float4*)kernelParam.ptr, kernelParam.pitch, fy)[fx];
+        k.w = psd_ok(k.x, k.y, k.z) ? 1.0f : 0.0f;
+        sK[r][c] = k;
+    }
+    stage_fields(0);
+    {
+        // column t of the tile: the float path of tex_coord, texel column predicted and verified (as k_accumulate2xTile)
+        const int X = bIdX * 256 + t;
+        const float posX = ((float)X + 0.5f) / (float)hrW;
+        float xB = posX * (float)fw - 0.5f;
+        if (!finitef(xB)) xB = 0.0f;
+        const float fxf = floorf(xB);
+        const int txc = X >> 2, ci = (t & 3) < 2 ? 0 : 1;
+        const bool ok = (f2i(fxf) == txc - 1 + ci) && (txc + ci <= fw - 1);
+        sColA[t] = ok ? xB - fxf : -1.0f;
+    }
+    if (t < 4) {
+        const int Yr = bIdY * 4 + t;
+        const float posY = ((float)Yr + 0.5f) / (float)hrH;
+        float yB = posY * (float)fh - 0.5f;
+        if (!finitef(yB)) yB = 0.0f;
+        const float fyf = floorf(yB);
+        const int frr = t < 2 ? 0 : 1;
+        const bool ok = (f2i(fyf) == bIdY - 1 + frr) && f2i(fyf) >= 0 && f2i(fyf) + 1 <= fh - 1;
+        sRowB[t] = ok ? yB - fyf : -1.0f;
+    }
+    const bool rowLive = Y >= STRIP_MARGIN && Y < hrH - STRIP_MARGIN;
+    const size_t rowBytes = (size_t)hrW * 12;
+    const size_t segByte = (size_t)bIdX * 3072;
+    char* gP = (char*)imgOut + (size_t)Y * strideOut + segByte;
+    char* gW = (char*)totalWeights + (size_t)Y * strideOut + segByte;
+    auto stage_plane = [&](char* g, int pl) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if (fresh) {
+                sAcc[pl][ly][j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else {
+                const size_t off = (size_t)(j * 64 + lx) * 16;
+                if (segByte + off + 16 <= rowBytes)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + off),
+                                                     (__attribute__((address_space(3))) void*)&sAcc[pl][ly][j * 64], 16, 0, 0);
+            }
+        }
+    };
+    if (rowLive) {
+        stage_plane(gP, 0);
+        stage_plane(gW, 1);
+    }
+    __syncthreads();
+    if (!rowLive) return;
+    const bool stripLive = X0 >= STRIP_MARGIN && X0 < hrW - STRIP_MARGIN;
+
+    const int fr_ = ly < 2 ? 0 : 1;
+    auto ciOf = [](int k) { return k < 2 ? 0 : 1; };  // left texel of pixel k's pair
+    const float b0 = sRowB[ly];
+    const float4 av4 = ((const float4*)sColA)[lx];
+    const bool geomOk = stripLive && b0 >= 0.0f && fminf(fminf(av4.x, av4.y), fminf(av4.z, av4.w)) >= 0.0f;
+
+    // kernel parameters of this strip (the same for every frame of every group)
+    float kxa[4], kya[4], kza[4];
+    bool kOk;
+    {
+        const float av[4] = {av4.x, av4.y, av4.z, av4.w}, b = b0;
+        float4 Kt[2][3];
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) Kt[r][c] = sK[fr_ + r][lx + c];
+        const float kAll = ((Kt[0][0].w * Kt[0][1].w) * (Kt[0][2].w * Kt[1][0].w)) * (Kt[1][1].w * Kt[1][2].w);
+        kOk = kAll > 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int ci = ciOf(k);
+            const float w00 = (1.0f - av[k]) * (1.0f - b), w10 = av[k] * (1.0f - b), w01 = (1.0f - av[k]) * b, w11 = av[k] * b;
+            auto mix = [&](float t00, float t10, float t01, float t11) {
+                return __builtin_fmaf(w11, t11, __builtin_fmaf(w01, t01, __builtin_fmaf(w10, t10, w00 * t00)));
+            };
+            kxa[k] = mix(Kt[0][ci].x, Kt[0][ci + 1].x, Kt[1][ci].x, Kt[1][ci + 1].x);
+            kya[k] = mix(Kt[0][ci].y, Kt[0][ci + 1].y, Kt[1][ci].y, Kt[1][ci + 1].y);
+            kza[k] = mix(Kt[0][ci].z, Kt[0][ci + 1].z, Kt[1][ci].z, Kt[1][ci + 1].z);
+        }
+    }
+    const uint32_t xmax = (uint32_t)(2 * dimX - 5), ymax = (uint32_t)(2 * dimY - 5);
+    // LDS address of the certainty row each tap row reads (opaque, see k_accumulate2xTile)
+    typedef const __attribute__((address_space(3))) char* lds_cptr;
+    typedef const __attribute__((address_space(1))) char* glb_cptr;
+    uint32_t mrowA[5];
+#pragma unroll
+    for (int jt = 0; jt < 5; jt++) {
+        mrowA[jt] = (uint32_t)(uintptr_t)(lds_cptr)&sMp[0][((ly + jt - 2) >> 2) + 1][0][lx];
+        asm volatile("" : "+v"(mrowA[jt]));
+    }
+    const uint32_t rawPitch = (uint32_t)dimX * 2u;
+    float* const myP = (float*)&sAcc[0][ly][0] + lx * 12;
+    float* const myW = (float*)&sAcc[1][ly][0] + lx * 12;
+
+#pragma unroll 1
+    for (int g = 0; g < nGroups; g++) {
+        if (g > 0) {
+            __syncthreads();  // every wave is past its reads of the previous group's texels
+            stage_fields(g);
+            __syncthreads();
+        }
+        // The tap weights depend on the kernel parameters only, so the compiler would take all 4 x 13 of them (and the pair sums)
+        // out of the group loop and spill: opaque per turn, they are recomputed per group as the launches they replace did
+#pragma unroll
+        for (int k = 0; k < 4; k++) asm volatile("" : "+v"(kxa[k]), "+v"(kya[k]), "+v"(kza[k]));
+        // (likewise the bilinear weights of pass 1, which depend on the fractions only)
+        float av[4] = {av4.x, av4.y, av4.z, av4.w};
+        float b = b0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) asm volatile("" : "+v"(av[k]));
+        asm volatile("" : "+v"(b));
+        // Pass 1, per frame: whole-pixel flow of the four pixels, 8:8 bits per pixel relative to the rounded flow of the tile's
+        // centre texel, and the fast-path admission -- the rules of k_accumulate2xTile's ALIAS form, whose launches this replaces
+        uint32_t safeBits = 0;
+        uint32_t sxy[NF][2];
+        int bsx[NF], bsy[NF];
+#pragma unroll
+        for (int n = 0; n < NF; n++) {
+            sxy[n][0] = sxy[n][1] = 0u;
+            const float2 cf = sF[n][1][FC / 2];
+            bsx[n] = __builtin_amdgcn_readfirstlane(min(max(round2i(cf.x * 2.0f), -32000), 32000));
+            bsy[n] = __builtin_amdgcn_readfirstlane(min(max(round2i(cf.y * 2.0f), -32000), 32000));
+            float2 Ft[2][3];
+#pragma unroll
+            for (int r = 0; r < 2; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) Ft[r][c] = sF[n][fr_ + r][lx + c];
+            bool safe = geomOk && kOk;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int ci = ciOf(k);
+                const float ux = lerp4(Ft[0][ci].x, Ft[0][ci + 1].x, Ft[1][ci].x, Ft[1][ci + 1].x, av[k], b);
+                const float uy = lerp4(Ft[0][ci].y, Ft[0][ci + 1].y, Ft[1][ci].y, Ft[1][ci + 1].y, av[k], b);
+                const int sx = round2i(ux * 2.0f), sy = round2i(uy * 2.0f);
+                const int qx = X0 + k + sx - 2, qy = Y + sy - 2;
+                safe = safe && (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
+                const uint32_t dx = (uint32_t)sx - (uint32_t)bsx[n], dy = (uint32_t)sy - (uint32_t)bsy[n];
+                safe = safe && dx + 128u < 256u && dy + 128u < 256u;  // (implies the rounded flow fits 16 signed bits, see there)
+                sxy[n][0] |= (dx & 0xffu) << (8 * k);
+                sxy[n][1] |= (dy & 0xffu) << (8 * k);
+            }
+            if (safe) safeBits |= 1u << n;
+        }
+        // the frames' raw pointers (opaque: kept in SGPR pairs)
+        glb_cptr rawBase[NF];
+#pragma unroll
+        for (int n = 0; n < NF; n++) {
+            rawBase[n] = (glb_cptr)fr.f[4 * g + n].raw;
+            asm volatile("" : "+s"(rawBase[n]));
+        }
+        // frames whose certainty is exactly 1 on every texel this wave reads take strip_pixel_sat
+        uint32_t satW = 0;
+        {
+            const int r0 = ((ly - 2) >> 2) + 1;
+            uint32_t u = sUnsat[r0][lx] | sUnsat[r0 + 1][lx];
+            if (lx < 2) u |= sUnsat[r0][64 + lx] | sUnsat[r0 + 1][64 + lx];
+#pragma unroll
+            for (int n = 0; n < NF; n++)
+                if (__builtin_amdgcn_ballot_w64((u >> n) & 1u) == 0) satW |= 1u << n;
+            satW = (uint32_t)__builtin_amdgcn_readfirstlane((int)satW);
+        }
+        // Pass 2, per pixel: weights once, then frame after frame; the group's weight sums start from zero
+        float accW[12];
+#pragma unroll
+        for (int i = 0; i < 12; i++) accW[i] = 0.0f;
+        auto pixel = [&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if (safeBits == 0) return;
+            float aP[12];
+            aP[3 * k] = aP[3 * k + 1] = aP[3 * k + 2] = 0.0f;
+            float w[13];
+            tap_weights13(kxa[k], kya[k], kza[k], w);
+            float P[3][4];
+            if (satW) tap_pair_sums(w, P);
+#pragma unroll
+            for (int n = 0; n < NF; n++) {
+                if ((safeBits >> n) & 1u) {
+                    auto rawf = [&](int x0, int y0, float (&sv)[3][3]) {
+                        const uint32_t boff = (uint32_t)(y0 * dimX + x0) * 2u;  // admitted strips: x0, y0 >= 0, inside the frame
+#pragma unroll
+                        for (int j = 0; j < 3; j++) {
+                            uint32_t off = boff + (uint32_t)j * rawPitch;
+                            asm volatile("" : "+v"(off));
+                            glb_cptr rb = rawBase[n] + off;
+#pragma unroll
+                            for (int i = 0; i < 3; i++) sv[j][i] = (float)*(const __attribute__((address_space(1))) uint16_t*)(rb + 2 * i);
+                        }
+                    };
+                    auto mval = [&](int jt, int cell, auto... e) {
+                        return *(const __attribute__((address_space(3))) float*)(uintptr_t)((mrowA[jt] + ... + e) +
+                                                                                             (uint32_t)(n * TILE_COLS + cell) * 4u);
+                    };
+                    const int sx = bsx[n] + (int)(int8_t)(sxy[n][0] >> (8 * k));
+                    const int sy = bsy[n] + (int)(int8_t)(sxy[n][1] >> (8 * k));
+                    if ((satW >> n) & 1u)
+                        strip_pixel_sat<k, CFA>(X0 + k, Y, sx, sy, w, P, rawf, lv, aP, accW);
+                    else
+                        strip_pixel_w<k, CFA, EP>(X0 + k, Y, sx, sy, w, rawf, mval, lv, aP, accW);
+                }
+            }
+            if (k == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the staged plane-sets have landed (first group)
+            myP[3 * k] += aP[3 * k];
+            myP[3 * k + 1] += aP[3 * k + 1];
+            myP[3 * k + 2] += aP[3 * k + 2];
+        };
+        pixel(std::integral_constant<int, 0>{});
+        pixel(std::integral_constant<int, 1>{});
+        pixel(std::integral_constant<int, 2>{});
+        pixel(std::integral_constant<int, 3>{});
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (strips that took no fast path have not waited yet)
+        {
+            float4* my = (float4*)myW;
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                float4 a = my[j];
+                a.x += accW[4 * j + 0]; a.y += accW[4 * j + 1]; a.z += accW[4 * j + 2]; a.w += accW[4 * j + 3];
+                my[j] = a;
+            }
+        }
+        // border / wild-flow / non-PSD strips of a frame: the straight per-pixel arithmetic on the staged values, which hold
+        // the earlier groups and this group's fast frames -- what the group's own launch would have read
+        if (safeBits != (1u << NF) - 1u && stripLive) {
+#pragma unroll 1
+            for (int n = 0; n < NF; n++) {
+                if ((safeBits >> n) & 1u) continue;
+                const TileFrame F = fr.f[4 * g + n];
+#pragma unroll 1
+                for (int k = 0; k < 4; k++) {
+                    const int X = X0 + k;
+                    if (X >= 1 && X < hrW - 1) {
+                        pix3 px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
+                        pix3 tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
+                        accumulate_pixel_core<GEOM_FULL, true>(X, Y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, 2, strideMask,
+                                                               cfaPacked, px, tw);
+                        myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z;
+                        myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z;
+                    }
+                }
+            }
+        }
+    }
+    // both staged planes back in memory order, once (the side-margin chunks belong to the margin kernel unless fresh)
+    // (the row's address is formed again from an opaque copy of Y: kept across the loop, the two pointers were spilled)
+    int Yw = Y;
+    asm volatile("" : "+v"(Yw));
+    auto store_plane = [&](int pl, pix3* base) {
+        char* g = (char*)base + (size_t)Yw * strideOut + segByte;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const size_t off = (size_t)(j * 64 + lx) * 16;
+            const size_t gb = segByte + off;
+            const bool sideMargin = gb < (size_t)STRIP_MARGIN * 12 || gb + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
+            if (gb + 16 <= rowBytes && (fresh || !sideMargin)) *(float4*)(g + off) = sAcc[pl][ly][j * 64 + lx];
+        }
+    };
+    store_plane(0, imgOut);
+    store_plane(1, totalWeights);
+}
+
+// The margin pixels of the same G groups in one launch: k_accumulateMarginN<4>'s workgroup (64 pixels x 4 frames, one thread
+// per pixel and frame) in a rolled loop over the groups.  A frame's sums are taken from zero and meet in LDS; the pixel's first
+// thread reads the accumulators once, adds the frames one after another in call order -- the order of G consecutive launches --
+// and writes them once.  Whole workgroups reach every barrier (no thread leaves early).
+// 1 (default): this kernel; 0: k_accumulateMarginN<4 G> with one thread per (pixel, frame), up to 64 x 16 threads per
+// workgroup -- measured slower than the launches it replaces (233 against 4 x 50 us at 4K x 16).
+#ifndef MARGIN_BURST_LOOP
+#define MARGIN_BURST_LOOP 1
+#endif
+template <int SCALE>
+__global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulateMarginN<4>: the kernel is latency-bound
+    k_accumulateMarginBurst(BurstFrames fr, int nGroups, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
+                            Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked)
+{
+    constexpr int scale = SCALE, NF = 4;
+    __shared__ float sSum[NF][6][64];
+    const int hrW = scale * dimX, hrH = scale * dimY, M = STRIP_MARGIN;
+    const int rowLen = hrW - 2;
+    const int nTop = (M - 1) * rowLen, nBot = (M - 1) * rowLen;
+    const int sideLen = 2 * (M - 1);
+    const int nSide = (hrH - 2 * M) * sideLen;
+    const int lane = threadIdx.x, n = threadIdx.y;
+    const int idx = blockIdx.x * 64 + lane;
+    int x = 0, y = -1;
+    if (idx < nTop) {
+        y = 1 + idx / rowLen;
+        x = 1 + idx % rowLen;
+    } else if (idx < nTop + nBot) {
+        const int r = idx - nTop;
+        y = hrH - M + r / rowLen;
+        x = 1 + r % rowLen;
+    } else if (idx < nTop + nBot + nSide) {
+        const int r = idx - nTop - nBot;
+        y = M + r / sideLen;
+        const int c = r % sideLen;
+        x = c < M - 1 ? 1 + c : hrW - M + (c - (M - 1));
+    }
+    const bool live = y >= 0;
+    const bool first = n == 0 && live;
+    pix3 a = {0.0f, 0.0f, 0.0f}, w = {0.0f, 0.0f, 0.0f};
+    if (first) {
+        a = row_ptr(imgOut, strideOut, y)[x];
+        w = row_ptr(totalWeights, strideOut, y)[x];
+    }
+#pragma unroll 1
+    for (int g = 0; g < nGroups; g++) {
+        pix3 pixel = {0.0f, 0.0f, 0.0f}, totalWeight = {0.0f, 0.0f, 0.0f};
+        // (opaque per turn: the compiler would otherwise carry the pixel's 25 tap weights, which depend on the kernel parameters
+        // only, across the groups -- and spill 36 registers at the 128 the occupancy allows)
+        int xg = x, yg = y;
+        asm volatile("" : "+v"(xg), "+v"(yg));
+        if (live) {
+            TileFrame F = fr.f[4 * g];
+#pragma unroll
+            for (int m = 1; m < NF; m++)
+                if (n == m) F = fr.f[4 * g + m];
+            accumulate_pixel_core<GEOM_FULL, true, MARGIN_TAP_SUMS>(xg, yg, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
+                                                                    strideMask, cfaPacked, pixel, totalWeight);
+        }
+        sSum[n][0][lane] = pixel.x;
+        sSum[n][1][lane] = pixel.y;
+        sSum[n][2][lane] = pixel.z;
+        sSum[n][3][lane] = totalWeight.x;
+        sSum[n][4][lane] = totalWeight.y;
+        sSum[n][5][lane] = totalWeight.z;
+        __syncthreads();
+        if (first) {
+#pragma unroll
+            for (int m = 0; m < NF; m++) {
+                a.x += sSum[m][0][lane];
+                a.y += sSum[m][1][lane];
+                a.z += sSum[m][2][lane];
+                w.x += sSum[m][3][lane];
+                w.y += sSum[m][4][lane];
+                w.z += sSum[m][5][lane];
+            }
+        }
+        __syncthreads();  // the sums are read before the next group overwrites them
+    }
+    if (first) {
+        row_ptr(imgOut, strideOut, y)[x] = a;
+        row_ptr(totalWeights, strideOut, y)[x] = w;
+    }
+}
+
 // ---- x4 ------------------------------------------------------------------------------------------
 // The same pixel at scale 4.  The 5x5 HR taps of a pixel fall on 2x2 raw sites: tap column `it` lands
 // on site column (ph + it) >> 2 with ph = (X + sx - 2) & 3, i.e. on column 1 iff ph + it >= 4 -- a lane
@@ -2102,6 +2523,94 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
     }
 #undef STRIP_CASE
     return 0;
+}
+
+// The burst form: nFrames = 8, 12 or 16 frames (whole groups of four, Bayer, fields at HR/4, the whole frame) in ONE tile
+// launch (k_accumulate2xTileBurst) and ONE margin launch; bit for bit what nFrames / 4 calls of the function above give.
+// Returns 1 if launched, 0 if the configuration is not the burst kernel's (nothing was touched), -1 if a memset of the
+// fresh-accumulator mode failed.
+int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
+                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
+                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
+                                       mfsr_stream_t stream)
+{
+    read_env_once();
+    if (nFrames < 8 || nFrames > 4 * TILE_BURST_GROUPS || (nFrames & 3)) return 0;
+    int cfa[4];
+    mfsr_get_cfa_pattern(cfa);
+    const int packed2 = pack_cfa(cfa[0], cfa[1], cfa[2], cfa[3]);
+    if ((dimX & 1) || ((uintptr_t)imgOut & 15) || ((uintptr_t)totalWeights & 15) || (strideOut & 15)) return 0;
+    if (dimX < 2 * STRIP_MARGIN || dimY < 2 * STRIP_MARGIN) return 0;
+    for (int n = 0; n < nFrames; n++)
+        if (!tile_kernel_ok(kernelParam, shifts[n], dimX, dimY)) return 0;
+    Levels3 glv;
+    StripLevels lv;
+    const float wl[3] = {whiteLevel.x, whiteLevel.y, whiteLevel.z}, bl[3] = {blackLevel.x, blackLevel.y, blackLevel.z};
+    for (int c = 0; c < 3; c++) {
+        glv.white[c] = wl[c];
+        glv.black[c] = bl[c];
+        lv.black[c] = bl[c];
+        lv.invWhite[c] = 1.0f / wl[c];
+    }
+    const int hrW = 2 * dimX, hrH = 2 * dimY;
+    const HrWindow whole{0, 0, hrW, hrH, 0};
+    const WinLaunch wlc = win_launch(whole, hrW, 256);
+    const MarginRects mr = margin_rects(hrW, hrH, STRIP_MARGIN, whole);
+    const int tilesX = wlc.tilesX, tilesY = mfsr_cdiv(hrH, 4);
+    const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
+    const dim3 block(64, 4), g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
+    hipStream_t st = mfsr_s(stream);
+    pix3* pI = (pix3*)imgOut;
+    pix3* pT = (pix3*)totalWeights;
+    const int cp = mfsr_cfa_packed();
+    BurstFrames fr;
+    for (int n = 0; n < 4 * TILE_BURST_GROUPS; n++) {
+        const int m = n < nFrames ? n : 0;  // (unused entries: never read, nGroups bounds the loop)
+        fr.f[n].raw = dataIn[m];
+        fr.f[n].mask = (const float4*)certaintyMask[m];
+        fr.f[n].shifts = shifts[m];
+    }
+    auto launch = [&](auto cfaTag) {
+        constexpr int CFA = decltype(cfaTag)::value;
+        // fresh accumulators: the tile kernel writes every row outside the top and bottom margin bands, which are zeroed here
+        if (fresh && zero_margin_bands(imgOut, totalWeights, hrH, strideOut, 0, hrH, wlc, st) != 0) return -1;
+        hipLaunchKernelGGL((k_accumulate2xTileBurst<CFA>), g1, block, 0, st, fr, nFrames / 4, pI, pT, kernelParam, glv, lv, dimX, dimY,
+                           strideOut, strideMask, cp, tilesX, tilesY, tilesPerXcd, fresh ? 1 : 0);
+        return 1;
+    };
+    // the margin pixels of all frames in one launch (MARGIN_BURST_LOOP = 0: one thread per (pixel, frame)), the frames' sums
+    // (each from zero) added to the accumulator value one after another in call order -- the order of the launches it replaces
+    auto margin = [&](auto nfTag) {
+        constexpr int NF = decltype(nfTag)::value;
+        TileFrames<NF> mf;
+        for (int n = 0; n < NF; n++) mf.f[n] = fr.f[n];
+        launch_margin_n<NF, 2>(st, mf, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, 0, hrH, wlc, mr);
+    };
+    int rc = 0;  // monochrome and other patterns: not the burst kernel's
+#define BURST_CASE(a, b, c, d)                                                      \
+    case pack_cfa(a, b, c, d):                                                      \
+        rc = launch(std::integral_constant<int, pack_cfa(a, b, c, d)>{});           \
+        break;
+    switch (packed2) {
+        BURST_CASE(MFSR_RED, MFSR_GREEN, MFSR_GREEN, MFSR_BLUE)  // RGGB
+        BURST_CASE(MFSR_BLUE, MFSR_GREEN, MFSR_GREEN, MFSR_RED)  // BGGR
+        BURST_CASE(MFSR_GREEN, MFSR_RED, MFSR_BLUE, MFSR_GREEN)  // GRBG
+        BURST_CASE(MFSR_GREEN, MFSR_BLUE, MFSR_RED, MFSR_GREEN)  // GBRG
+        default: break;
+    }
+#undef BURST_CASE
+    if (rc != 1) return rc;
+    if (MARGIN_BURST_LOOP) {
+        const long long cnt = 2LL * (STRIP_MARGIN - 1) * (hrW - 2) + (long long)(hrH - 2 * STRIP_MARGIN) * 2 * (STRIP_MARGIN - 1);
+        hipLaunchKernelGGL((k_accumulateMarginBurst<2>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, 4), 0, st, fr, nFrames / 4, pI, pT, kernelParam,
+                           glv, dimX, dimY, strideOut, strideMask, cp);
+        return 1;
+    }
+    if (nFrames == 8) margin(std::integral_constant<int, 8>{});
+    if (nFrames == 12) margin(std::integral_constant<int, 12>{});
+    if (nFrames == 16) margin(std::integral_constant<int, 16>{});
+    return 1;
 }
 
 // x4: returns 1 if the x4 tile kernel took the nFrames (1 to 4) frames, 0 if the geometry is not its

@@ -40,6 +40,10 @@ constexpr int kMaxTimedLaunches = 4096;
 // untouched until the warp+fuse that consumes it has run, which with cfg.asyncFuse happens on the
 // burst's own stream while the caller's stream already aligns the next frames.
 constexpr int kRing = 2 * MFSR_MAX_FUSE_GROUP;  // a group waiting to be fused + the group the fuse stream is reading
+// With the burst hold (mfsr_burst_hold_fuse) the complete groups of a burst wait for ONE warp+fuse launch, so their slots must
+// outlive the alignment of the groups after them: the ring is max(kRing, min(cfg.frames, kRingMax)) slots, a run-time size.
+constexpr int kRingMax = MFSR_MAX_BURST_FUSE;
+inline int ring_size(const mfsr_config* c) { return c->frames <= kRing ? kRing : (c->frames < kRingMax ? c->frames : kRingMax); }
 constexpr int kMaxUploadRing = 32;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -83,8 +87,8 @@ struct Layout {
     Img tensor, tensorTmp, tensorSm;         // float3, tracking res
     Img fallback;                            // float3, W x H
     Img tmpA, tmpB;                          // float, tracking res
-    Img flowBuf[2 * kRing];                  // float2, tracking res: per ring slot the two buffers of the LK ping-pong
-    Img maskBuf[kRing];                      // float4, half res, one per ring slot
+    Img flowBuf[2 * kRingMax];               // float2, tracking res: per ring slot the two buffers of the LK ping-pong
+    Img maskBuf[kRingMax];                   // float4, half res, one per ring slot (ring_size(cfg) slots are allocated)
     Img maskRaw[MFSR_MAX_FUSE_GROUP];        // cfg.maskErode > 0 only: stage F writes here, the erosion writes the slot's mask
     Img pre[kMaxLevels];                     // float2, tile grids: the unfused tracker's upsampled pre-shifts
     // unfused path scratch
@@ -268,6 +272,12 @@ Layout make_layout(const mfsr_config* c, char* base)
     if (c->rawPacking != MFSR_PACK_NONE)
         for (int i = 0; i < c->uploadRing + 2; i++)
             L->stage[i] = (uint8_t*)b.take((size_t)mfsr_packed_row_bytes(c->rawPacking, L->W) * L->H);
+    // ring slots beyond the first kRing (bursts of more than kRing frames): at the END, so that everything above keeps its place
+    for (int i = kRing; i < ring_size(c); i++) {
+        L->flowBuf[2 * i] = b.image(L->tw, L->th, 8);
+        L->flowBuf[2 * i + 1] = b.image(L->tw, L->th, 8);
+        L->maskBuf[i] = b.image(L->hw, L->hh, 16);
+    }
     L->total = align_up(b.off, 256);
     return layout;
 }
@@ -316,6 +326,12 @@ struct mfsr_burst {
     Pending held;
     bool heldHas;
     int group;  // frames per warp+fuse launch (mfsr_burst_group_size)
+    // burst hold (mfsr_burst_hold_fuse): complete, aligned groups whose fuse waits for flush / finish / a full ring, where
+    // two or more of them leave as ONE launch (mfsr_accumulateSuperResBurst); in arrival order, all on the same accumulators
+    bool holdFuse;
+    int nHold;
+    Pending hold[MFSR_MAX_BURST_FUSE / MFSR_MAX_FUSE_GROUP];
+    int burstLaunches, burstGroups;  // burst launches since mfsr_burst_begin and the groups they fused (mfsr_burst_fuse_stats)
     int nFramesTimed;
     // mfsr_burst_begin: these accumulators are to be overwritten by the first fuse instead of zeroed
     struct Fresh {
@@ -325,14 +341,15 @@ struct mfsr_burst {
     // ring + asynchronous fuse (cfg.asyncFuse)
     int frameCounter;
     hipStream_t fuseStream;             // high priority, non-blocking; null without asyncFuse
-    hipEvent_t evAligned[kRing];        // recorded on the caller's stream when slot's flow/mask are complete
-    hipEvent_t evFused[kRing];          // recorded on fuseStream when the fuse that read the slot is done
+    int ring;                           // ring slots of this context (ring_size(cfg))
+    hipEvent_t evAligned[kRingMax];     // recorded on the caller's stream when slot's flow/mask are complete
+    hipEvent_t evFused[kRingMax];       // recorded on fuseStream when the fuse that read the slot is done
     // the reference products only the fuse and the finish read (kernel parameters, debayered fallback image) are made on
     // fuseStream, beside the alignment of the first group on the caller's stream: off the critical path of the burst
     hipEvent_t evRefStart, evRefDone;
     bool refOnFuse;                     // evRefDone is pending for consumers on other streams than fuseStream
-    bool fusedOutstanding[kRing];       // evFused[slot] recorded and not yet waited for by the caller's stream
-    const Img* slotFlow[kRing];         // which buffer of the slot's LK ping-pong pair holds the frame's final flow
+    bool fusedOutstanding[kRingMax];    // evFused[slot] recorded and not yet waited for by the caller's stream
+    const Img* slotFlow[kRingMax];      // which buffer of the slot's LK ping-pong pair holds the frame's final flow
     // host-frame bursts (cfg.uploadRing): copy stream, per-slot events, reference double buffer
     hipStream_t copyStream;
     hipStream_t downStream;                 // D2H of the finished image (mfsr_burst_finish_host), concurrent with the uploads
@@ -385,6 +402,7 @@ struct mfsr_burst {
     bool timing;
     int nEvents;
     hipEvent_t evStart[kMaxTimedLaunches], evStop[kMaxTimedLaunches];
+    unsigned char evLaunches[kMaxTimedLaunches];  // launches an event pair stands for: 1, or the groups of a burst launch
     // which branches the driver took since mfsr_burst_begin (mfsr_burst_debug_paths): host-side counters only
     int32_t paths[MFSR_PATH_COUNT];
 };
@@ -519,6 +537,10 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->ref = b->L.ref;
     b->pend.n = 0;
     b->group = mfsr_burst_group_size(&b->cfg);
+    b->ring = ring_size(&b->cfg);
+    b->holdFuse = false;
+    b->nHold = 0;
+    b->burstLaunches = b->burstGroups = 0;
     b->fresh.has = false;
     b->nFramesTimed = 0;
     b->timing = false;
@@ -529,7 +551,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->fuseStream = nullptr;
     b->evRefStart = b->evRefDone = nullptr;
     b->refOnFuse = false;
-    for (int i = 0; i < kRing; i++) {
+    for (int i = 0; i < kRingMax; i++) {
         b->evAligned[i] = b->evFused[i] = nullptr;
         b->fusedOutstanding[i] = false;
         b->slotFlow[i] = nullptr;
@@ -546,7 +568,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&b->fuseStream, hipStreamNonBlocking, prio);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evRefStart, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evRefDone, hipEventDisableTiming);
-        for (int i = 0; i < kRing && e == hipSuccess; i++) {
+        for (int i = 0; i < b->ring && e == hipSuccess; i++) {
             e = hipEventCreateWithFlags(&b->evAligned[i], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&b->evFused[i], hipEventDisableTiming);
         }
@@ -614,7 +636,7 @@ extern "C" void mfsr_burst_destroy(mfsr_burst* b)
         if (b->evStop[i]) (void)hipEventDestroy(b->evStop[i]);
     }
     if (b->fuseStream) (void)hipStreamSynchronize(b->fuseStream);
-    for (int i = 0; i < kRing; i++) {
+    for (int i = 0; i < kRingMax; i++) {
         if (b->evAligned[i]) (void)hipEventDestroy(b->evAligned[i]);
         if (b->evFused[i]) (void)hipEventDestroy(b->evFused[i]);
     }
@@ -655,14 +677,16 @@ extern "C" int mfsr_burst_timing_read(mfsr_burst* b, double* totalMs, int* launc
 {
     MFSR_REQUIRE(b && totalMs && launches && frames);
     double total = 0;
+    int nLaunches = 0;
     for (int i = 0; i < b->nEvents; i++) {
         MFSR_HIP_TRY(hipEventSynchronize(b->evStop[i]));
         float ms = 0;
         MFSR_HIP_TRY(hipEventElapsedTime(&ms, b->evStart[i], b->evStop[i]));
         total += ms;
+        nLaunches += b->evLaunches[i];
     }
     *totalMs = total;
-    *launches = b->nEvents;
+    *launches = nLaunches;
     *frames = b->nFramesTimed;
     b->nEvents = 0;
     b->nFramesTimed = 0;
@@ -938,7 +962,7 @@ extern "C" int mfsr_burst_set_window(mfsr_burst* b, int x0, int y0, int w, int h
     const int rc = mfsr_window_check(&b->cfg, x0, y0, w, h);
     if (rc != MFSR_OK) return rc;
     // between bursts only: a waiting frame would be fused into the other geometry
-    if (b->pend.n > 0 || b->heldHas) {
+    if (b->pend.n > 0 || b->heldHas || b->nHold > 0) {
         fprintf(stderr, "mfsr: mfsr_burst_set_window with frames pending (flush or finish the burst first)\n");
         return MFSR_E_INVALID;
     }
@@ -1049,6 +1073,130 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream);
 // G: the waiting group (b->pend, 1 .. MFSR_MAX_FUSE_GROUP aligned frames) onto its accumulators (timed with HIP events on request)
 static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream);
 
+// ---- burst hold -------------------------------------------------------------------------------------------------------------
+// Process-wide switch of the burst hold for A/B (mfsr_set_burst_fuse; MFSR_BURST_FUSE=0 in the environment): off, every
+// context fuses its groups as they complete, whatever mfsr_burst_hold_fuse said.
+static int g_burst_fuse = -1;
+static bool burst_fuse_enabled()
+{
+    if (g_burst_fuse < 0) {
+        const char* e = getenv("MFSR_BURST_FUSE");
+        g_burst_fuse = (e && e[0] == '0') ? 0 : 1;
+    }
+    return g_burst_fuse == 1;
+}
+extern "C" int mfsr_set_burst_fuse(int enable)
+{
+    g_burst_fuse = enable ? 1 : 0;
+    return MFSR_OK;
+}
+extern "C" int mfsr_burst_hold_fuse(mfsr_burst* b, int enable)
+{
+    MFSR_REQUIRE(b != nullptr);
+    b->holdFuse = enable != 0;  // (groups already held leave with the next flush / finish / add_frame that needs their slots)
+    return MFSR_OK;
+}
+extern "C" int mfsr_burst_fuse_stats(const mfsr_burst* b, int* burstLaunches, int* groupsFused)
+{
+    MFSR_REQUIRE(b && burstLaunches && groupsFused);
+    *burstLaunches = b->burstLaunches;
+    *groupsFused = b->burstGroups;
+    return MFSR_OK;
+}
+
+// may the complete, aligned group in b->pend wait for the burst launch?  Only the plain resident path of the x2 Bayer tile
+// geometry: everything else (asyncFuse, windows, host bursts, frames in upload slots, other group sizes) fuses as before.
+static bool can_hold_group(const mfsr_burst* b, bool hostBurst)
+{
+    const mfsr_config& c = b->cfg;
+    if (!b->holdFuse || !burst_fuse_enabled() || hostBurst || b->heldHas || b->fuseStream || b->win.on) return false;
+    if (!c.fused || c.mono || c.scale != 2 || b->group != MFSR_MAX_FUSE_GROUP || b->pend.n != MFSR_MAX_FUSE_GROUP) return false;
+    if (b->L.tw * 2 != b->L.W || b->L.th * 2 != b->L.H) return false;
+    if (b->nHold >= MFSR_MAX_BURST_FUSE / MFSR_MAX_FUSE_GROUP) return false;
+    if (b->nHold > 0 && (b->hold[0].imgOut != b->pend.imgOut || b->hold[0].totalWeights != b->pend.totalWeights)) return false;
+    for (int i = 0; i < b->pend.n; i++)
+        if (upload_slot_of(b, b->pend.raw[i]) >= 0) return false;
+    return true;
+}
+
+static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream);
+
+// The held groups onto their accumulators, in arrival order: two or more as ONE launch (counted as one timed launch per group,
+// so that mfsr_burst_timing_read's average stays "per four-frame group"), a single one as the ordinary launch it would have been.
+static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
+{
+    const int G = b->nHold;
+    if (G == 0) return MFSR_OK;
+    b->nHold = 0;
+    const mfsr_config& c = b->cfg;
+    const Layout& L = b->L;
+    int rc = MFSR_E_UNSUPPORTED;
+    if (G >= 2) {
+        const uint16_t* raws[MFSR_MAX_BURST_FUSE];
+        mfsr_tex2d masks[MFSR_MAX_BURST_FUSE], flows[MFSR_MAX_BURST_FUSE];
+        for (int g = 0; g < G; g++)
+            for (int i = 0; i < MFSR_MAX_FUSE_GROUP; i++) {
+                const int k = g * MFSR_MAX_FUSE_GROUP + i;
+                raws[k] = b->hold[g].raw[i];
+                masks[k] = as_tex(*b->hold[g].mask[i]);
+                flows[k] = as_tex(*b->hold[g].flow[i]);
+            }
+        mfsr_float3* imgOut = b->hold[0].imgOut;
+        mfsr_float3* totalWeights = b->hold[0].totalWeights;
+        mfsr_tex2d acc[2];
+        for (int p = 0; p < 2; p++) {
+            acc[p].ptr = p ? (void*)totalWeights : (void*)imgOut;
+            acc[p].pitch = 12 * L.hrW;
+            acc[p].width = L.hrW;
+            acc[p].height = L.hrH;
+        }
+        TRY(mfsr_set_cfa_pattern(c.cfa));
+        const int freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
+        const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
+        if (timed) {
+            const int i = b->nEvents;
+            if (!b->evStart[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStart[i]));
+            if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
+            MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
+        }
+        const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
+        const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
+        rc = mfsr_accumulateSuperResBurst(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
+                                          c.scale, freshNow, stream);
+        if (rc == MFSR_OK) {
+            if (b->fresh.has && !freshNow) {
+                // begin(A, W) followed by a fuse into other accumulators: A and W still owe their zeroes
+                const size_t bytes = acc_bytes(b);
+                MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
+                MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
+            }
+            b->fresh.has = false;
+            b->burstLaunches++;
+            b->burstGroups += G;
+            if (timed) {
+                MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
+                b->evLaunches[b->nEvents] = G;
+                b->nEvents++;
+                b->nFramesTimed += G * MFSR_MAX_FUSE_GROUP;
+            }
+            return MFSR_OK;
+        }
+        if (rc != MFSR_E_UNSUPPORTED) return rc;
+    }
+    // one group, or a geometry the burst kernel does not take (nothing was touched): the launches these groups would have been
+    const mfsr_burst::Pending later = b->pend;
+    for (int g = 0; g < G; g++) {
+        b->pend = b->hold[g];
+        const int rc1 = accumulate_pending(b, stream);
+        if (rc1 != MFSR_OK) {
+            b->pend = later;
+            return rc1;
+        }
+    }
+    b->pend = later;
+    return MFSR_OK;
+}
+
 // a group that was held back for mfsr_burst_finish_host and is fused the ordinary way after all (flush / finish / another
 // accumulator pair / its upload slot is needed): as its own launch, exactly as if it had not been held
 static int fuse_held(mfsr_burst* b, mfsr_stream_t callerStream)
@@ -1065,6 +1213,7 @@ static int fuse_held(mfsr_burst* b, mfsr_stream_t callerStream)
 
 static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
 {
+    TRY(fuse_hold(b, callerStream));       // the burst hold's groups come before everything that arrived after them
     TRY(fuse_held(b, callerStream));       // it comes before the frames that arrived after it
     TRY(align_deferred(b, callerStream));  // frames of the group that were waiting for their batch
     TRY(wait_uploads(b, callerStream));    // (a reference frame of the group is read by the fuse only)
@@ -1109,6 +1258,7 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
     }
     if (timed) {
         MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
+        b->evLaunches[b->nEvents] = 1;
         b->nEvents++;
         b->nFramesTimed += n;
     }
@@ -1140,7 +1290,7 @@ static int join_fuse(mfsr_burst* b, mfsr_stream_t stream)
 {
     if (!b->fuseStream) return MFSR_OK;
     TRY(wait_ref_products(b, stream));
-    for (int i = 0; i < kRing; i++)
+    for (int i = 0; i < b->ring; i++)
         if (b->fusedOutstanding[i]) {
             MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[i], 0));
             b->fusedOutstanding[i] = false;
@@ -1151,7 +1301,7 @@ static int join_fuse(mfsr_burst* b, mfsr_stream_t stream)
 // fuse the frames still waiting for the rest of their group, then join: afterwards the caller's stream sees every frame
 static int flush_pending(mfsr_burst* b, mfsr_stream_t stream, bool materializeFresh)
 {
-    if (materializeFresh && b->fresh.has && b->pend.n == 0 && !b->heldHas) {
+    if (materializeFresh && b->fresh.has && b->pend.n == 0 && !b->heldHas && b->nHold == 0) {
         // mfsr_burst_begin with no frame fused since: the accumulators must read as zero
         const size_t bytes = acc_bytes(b);
         MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
@@ -1590,11 +1740,15 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     b->holdLastGroup = hostBurst;
     // G: accumulate onto the HR grid -- alone, or together with the frames that were waiting for the rest of their group
     if (b->pend.n && (b->pend.imgOut != imgOut || b->pend.totalWeights != totalWeights)) TRY(flush_pending(b, stream));
+    // burst hold: held groups leave when this frame goes to other accumulators, or when its ring slot would be one of theirs
+    if (b->nHold && (b->hold[0].imgOut != imgOut || b->hold[0].totalWeights != totalWeights ||
+                     b->nHold * MFSR_MAX_FUSE_GROUP + b->pend.n >= b->ring))
+        TRY(fuse_hold(b, stream));
     // a complete group was held back for mfsr_burst_finish_host and frames keep arriving (more than cfg.frames per
     // reference, or a resident frame after a host burst): it is fused the ordinary way before this frame is registered
     if (b->pend.n >= b->group) TRY(accumulate_pending(b, stream));
     MFSR_REQUIRE(b->pend.n < MFSR_MAX_FUSE_GROUP);
-    const int slot = b->frameCounter++ % kRing;
+    const int slot = b->frameCounter++ % b->ring;
     const Img *flow = nullptr, *mask = nullptr;
     const bool defer = can_defer_alignment(b, prepared || suppliedShifts);
     b->paths[defer ? MFSR_PATH_FRAMES_DEFERRED : MFSR_PATH_FRAMES_IMMEDIATE]++;
@@ -1639,6 +1793,13 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
             return MFSR_OK;
         }
     }
+    // burst hold (mfsr_burst_hold_fuse): the group is aligned now, as always, and its fuse waits for the burst launch
+    if (can_hold_group(b, hostBurst)) {
+        TRY(align_deferred(b, stream));
+        b->hold[b->nHold++] = b->pend;
+        b->pend.n = 0;
+        return MFSR_OK;
+    }
     return accumulate_pending(b, stream);
 }
 
@@ -1678,7 +1839,8 @@ extern "C" int mfsr_burst_align_frame(mfsr_burst* b, const uint16_t* raw, int is
     MFSR_REQUIRE((long long)flowPitch >= 8LL * L.tw && (flowPitch & 7) == 0 && ((uintptr_t)flowOut & 7) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0 && ((uintptr_t)maskOut & 15) == 0);
     TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
-    const int slot = b->frameCounter++ % kRing;
+    TRY(fuse_hold(b, stream));  // (the call takes a ring slot)
+    const int slot = b->frameCounter++ % b->ring;
     const Img *flow = nullptr, *mask = nullptr;
     TRY(align_frame(b, raw, isReference, slot, nullptr, nullptr, &flow, &mask, stream));
     b->flowCur = flow;
@@ -1705,13 +1867,14 @@ extern "C" int mfsr_burst_align_frames(mfsr_burst* b, int nFrames, const uint16_
     for (int k = 0; k < nFrames; k++)
         MFSR_REQUIRE(raws[k] && flowOut[k] && maskOut[k] && ((uintptr_t)flowOut[k] & 7) == 0 && ((uintptr_t)maskOut[k] & 15) == 0);
     TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
+    TRY(fuse_hold(b, stream));  // (the call takes ring slots)
     const bool batch = can_defer_alignment(b, false);
     const int per = batch ? b->group : 1;
     for (int k0 = 0; k0 < nFrames; k0 += per) {
         const int n = nFrames - k0 < per ? nFrames - k0 : per;
         for (int j = 0; j < n; j++) {
             const int isRef = isReference ? isReference[k0 + j] : 0;
-            const int slot = b->frameCounter++ % kRing;
+            const int slot = b->frameCounter++ % b->ring;
             b->pend.slot[j] = slot;
             b->pend.raw[j] = raws[k0 + j];
             b->pend.isRef[j] = isRef;
@@ -1774,6 +1937,7 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
                                         c.scale, 12 * L.hrW, maskPitch, accumulatorsUndefined, rowBegin, rowEnd, stream));
     if (timed) {
         MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
+        b->evLaunches[b->nEvents] = 1;
         b->nEvents++;
         b->nFramesTimed += nFrames;
     }
@@ -1825,6 +1989,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
     b->sharpenedFinishes = 0;
+    b->burstLaunches = b->burstGroups = 0;
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
     b->fresh.totalWeights = totalWeights;
@@ -1913,7 +2078,7 @@ static void sharpen_reach(const mfsr_burst* b, int r0, int rows, int* above, int
 extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
     if (!sharpen) {
         b->sharpenOn = false;
         return MFSR_OK;
@@ -1936,7 +2101,7 @@ extern "C" int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes)
 extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
     if (!render) {
         b->renderOn = false;
         return MFSR_OK;
@@ -2245,6 +2410,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(b->haveRef);
     bool capturing = false;
     TRY(host_epoch(b, stream, &capturing));
+    TRY(fuse_hold(b, stream));  // (resident frames of a burst-hold context added before this call)
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
     // the previous image may still be on its way to the host out of out16Dev
@@ -2397,7 +2563,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
 extern "C" int mfsr_burst_set_host_row_bytes(mfsr_burst* b, int rowBytes)
 {
     MFSR_REQUIRE(b != nullptr && b->cfg.uploadRing > 0);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
     const bool isPacked = b->cfg.rawPacking != MFSR_PACK_NONE;
     const int dense = isPacked ? mfsr_packed_row_bytes(b->cfg.rawPacking, b->L.W) : 2 * b->L.W;
     MFSR_REQUIRE(rowBytes == 0 || rowBytes >= dense);
@@ -2726,7 +2892,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     TemporalScratch s;
     MFSR_REQUIRE(temporal_scratch(&c, nFrames, &s));
     MFSR_REQUIRE(((uintptr_t)scratchDev & 255) == 0 && scratchBytes >= s.total);
-    if (b->pend.n > 0 || b->heldHas || b->nUnp != 0) {  // between bursts only
+    if (b->pend.n > 0 || b->heldHas || b->nHold > 0 || b->nUnp != 0) {  // between bursts only
         fprintf(stderr, "mfsr: mfsr_burst_calibrate_noise_temporal with frames pending (flush or finish the burst first)\n");
         return MFSR_E_INVALID;
     }
@@ -2804,8 +2970,8 @@ extern "C" int mfsr_burst_debug_paths(const mfsr_burst* b, int32_t* counts, int 
 
 extern "C" int mfsr_burst_debug_frame_views(mfsr_burst* b, int framesBack, mfsr_tex2d* flow, mfsr_tex2d* mask)
 {
-    MFSR_REQUIRE(b != nullptr && framesBack >= 0 && framesBack < kRing && framesBack < b->frameCounter);
-    const int slot = (int)((b->frameCounter - 1 - framesBack) % kRing);
+    MFSR_REQUIRE(b != nullptr && framesBack >= 0 && framesBack < b->ring && framesBack < b->frameCounter);
+    const int slot = (int)((b->frameCounter - 1 - framesBack) % b->ring);
     MFSR_REQUIRE(b->slotFlow[slot] != nullptr);
     if (flow) *flow = as_tex(*b->slotFlow[slot]);
     if (mask) *mask = as_tex(b->L.maskBuf[slot]);

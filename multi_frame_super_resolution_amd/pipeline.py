@@ -795,6 +795,8 @@ class BurstPipeline:
             self.L.burst_create(ctypes.byref(handle), ctypes.byref(cfg), self._ws_ptr, nbytes)
             self._h = handle
             self.window.apply(self.L.burst_set_window, self._h)
+        self._hold = None        # mfsr_burst_hold_fuse is on for this context (None: not decided, begin_burst applies HOLD_FUSE)
+        self._held_frames = []   # ... and these frame tensors wait for the burst launch: referenced until flush / finish
 
     def close(self):
         if getattr(self, "_h", None):
@@ -868,6 +870,22 @@ class BurstPipeline:
     # partner is aligned (mfsr.h, mfsr_burst_add_frame): readers of the accumulators flush first.
     def flush(self):
         self.L.burst_flush(self._h, self._stream())
+        self._held_frames.clear()
+
+    # Burst hold (mfsr.h, mfsr_burst_hold_fuse): the complete groups of a burst leave as ONE warp+fuse launch at flush / finish
+    # instead of one launch per group; bit-identical results.  The library then reads the frames' raw buffers as late as that,
+    # so add_frame keeps the tensors referenced until the launch has been enqueued.
+    HOLD_FUSE = True    # what begin_burst() opts into; DESIGN.md section 5 has the measurement behind the default
+
+    def hold_fuse(self, enable: bool = True):
+        self.L.burst_hold_fuse(self._h, 1 if enable else 0)
+        self._hold = bool(enable)
+
+    def fuse_stats(self):
+        """(burst launches, four-frame groups they fused) since ``begin_burst`` (mfsr_burst_fuse_stats)."""
+        n, g = ctypes.c_int(-1), ctypes.c_int(-1)
+        self.L.burst_fuse_stats(self._h, ctypes.byref(n), ctypes.byref(g))
+        return n.value, g.value
 
     @property
     def img_out(self) -> torch.Tensor:
@@ -887,17 +905,23 @@ class BurstPipeline:
     def begin_burst(self):
         """Start a burst without zeroing: the first warp+fuse launch overwrites the accumulators
         (mfsr_burst_begin).  Equivalent to reset_accumulators() for every reader (flush zeroes them if no
-        frame was added)."""
+        frame was added).  Opts into the burst hold where ``HOLD_FUSE`` says so."""
+        if self._hold is None and self.HOLD_FUSE:
+            self.hold_fuse(True)
         self.L.burst_begin(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), self._stream())
+        self._held_frames.clear()
 
     def set_reference(self, raw: torch.Tensor):
         self._check_raw(raw)
         self.L.burst_set_reference(self._h, raw.data_ptr(), self._stream())
+        self._held_frames.clear()
 
     def add_frame(self, raw: torch.Tensor, is_reference: bool = False):
         self._check_raw(raw)
         self.L.burst_add_frame(self._h, raw.data_ptr(), 1 if is_reference else 0, self._img_out.data_ptr(),
                                self._total_weights.data_ptr(), self._stream())
+        if self._hold:
+            self._held_frames.append(raw)
 
     def finish(self, want_float: bool = True, want_u16: bool = True):
         """(float image, u16 image) of the burst: the whole HR frame, or the rectangle given as ``window``.  After
@@ -905,6 +929,7 @@ class BurstPipeline:
         self.L.burst_finish(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(),
                             self.out_img.data_ptr() if want_float else None,
                             self.out16.data_ptr() if want_u16 else None, self._stream())
+        self._held_frames.clear()
         return self.window(self.out_img if want_float else None), self.window.output(self.out16 if want_u16 else None, self._fmt)
 
     def finish_rows(self, row0: int, rows: int) -> torch.Tensor:
@@ -912,6 +937,7 @@ class BurstPipeline:
         full-size u16 buffer (after ``set_render``: the rendered image's buffer) with that stripe filled."""
         self.L.burst_finish_rows(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), None,
                                  self.out16.data_ptr(), row0, rows, self._stream())
+        self._held_frames.clear()
         return self.out16
 
     # ---- the raw-domain steps, in the order DESIGN.md sections 2.14 and 2.17 fix: repair, shade, select, match, then the burst.
