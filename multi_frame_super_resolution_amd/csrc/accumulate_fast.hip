@@ -232,10 +232,8 @@ __device__ __forceinline__ void strip_pixel_sites(const float (&C)[5][3], const 
 // ~245 VALU instructions per pixel instead of ~330; sums re-associated again (fma), same tolerance.
 // EP != 0 (the LDS tile kernel): the certainties are staged in LDS in CFA-position order, so "which channel does this site
 // see" is an LDS ADDRESS (a few integer ops per pixel) instead of three v_bitop3 selects per tap row and cell.
-//  EP == 4: one float4 texel per cell; mval(jt, cell, 4 * e) returns the certainty of the colour at CFA position e =
-//   (y parity << 1) | x parity of mask cell `cell` on tap row jt's mask row.
-//  EP > 4: one dword plane per CFA position, EP bytes apart; mval(jt, cell, ey, ex) with the byte offsets of the y parity
-//   (0 or 2 * EP) and of the x parity (0 or EP) -- a value that is 0 or c flips with `^ c` whatever c is.
+//  One dword plane per CFA position, EP bytes apart; mval(jt, cell, ey, ex) with the byte offsets of the y parity
+//  (0 or 2 * EP) and of the x parity (0 or EP) -- a value that is 0 or c flips with `^ c` whatever c is.
 // strip_pixel_w: the pixel with its 13 tap weights given (they depend on the kernel parameters only, i.e. not on the
 // frame: a kernel that takes several frames per launch computes them once per pixel).
 // RawF: void rawf(int x0, int y0, float (&s)[3][3]) -> the 3x3 raw sites whose top left one is (x0, y0).
@@ -243,7 +241,7 @@ template <int K, int CFA, int EP = 0, typename RawF, typename MaskF>
 __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, const float (&w)[13], RawF rawf, MaskF mval,
                                                const StripLevels& lv, float* accP, float* accW)
 {
-    static_assert(EP == 0 || EP >= 4, "EP: 0 (by channel), 4 (texels by CFA position) or the plane stride in bytes");
+    static_assert(EP == 0 || EP > 4, "EP: 0 (certainty by channel) or the plane stride in bytes");
     const int qx = X + sx - 2, qy = Y + sy - 2;
     const int x0 = qx >> 1, y0 = qy >> 1;
     uint32_t mbx = 0u - (uint32_t)(qx & 1), mby = 0u - (uint32_t)(qy & 1);
@@ -276,9 +274,9 @@ __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, cons
     constexpr int cellLo = (K + 0 + 2) >> 2;
     auto cidx = [](int it) { return (((K + it + 2) >> 2) == ((K + 2) >> 2)) ? 0 : 1; };
 
-    // EP > 4: plane offsets of the x parity P / ~P and of the y parities Q, ~Q, Q ^ by, ~(Q ^ by)
+    // EP != 0: plane offsets of the x parity P / ~P and of the y parities Q, ~Q, Q ^ by, ~(Q ^ by)
     uint32_t ex[2] = {0u, 0u}, ey[4] = {0u, 0u, 0u, 0u};
-    if constexpr (EP > 4) {
+    if constexpr (EP != 0) {
         ex[0] = mP & (uint32_t)EP;
         ex[1] = ex[0] ^ (uint32_t)EP;
         ey[0] = mQ & (uint32_t)(2 * EP);
@@ -295,25 +293,13 @@ __device__ __forceinline__ void strip_pixel_w(int X, int Y, int sx, int sy, cons
         if (jt == 1) mya = mY13;
         if (jt == 3) mya = ~mY13;
         float Ee[2], Eo[2];  // certainty of the colour on even / odd site columns (relative to x0), per cell
-        if constexpr (EP > 4) {
+        if constexpr (EP != 0) {
             // y parity Q (rows 0, 4), ~Q (row 2), Q ^ by (row 1), ~(Q ^ by) (row 3); even site columns x parity P, odd ~P
             const uint32_t eyj = ey[(jt == 0 || jt == 4) ? 0 : (jt == 2 ? 1 : (jt == 1 ? 2 : 3))];
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 Ee[c] = mval(jt, cellLo + c, eyj, ex[0]);
                 Eo[c] = mval(jt, cellLo + c, eyj, ex[1]);
-            }
-        } else if constexpr (EP == 4) {
-            // CFA position of an even site column on this tap row: y parity Q (rows 0, 4), ~Q (row 2), Q ^ by (row 1),
-            // ~(Q ^ by) (row 3); x parity P.  Odd site columns: x parity flipped.
-            // (as byte offsets into the texel: the address is then a plain add)
-            const int eQ = ((qy << 2) & 8) | ((qx + qx) & 4);   // ((y0 & 1) << 1 | (x0 & 1)) * 4 with x0 = qx >> 1, y0 = qy >> 1
-            const int by2 = (qy << 3) & 8;
-            const int e = (jt == 0 || jt == 4) ? eQ : (jt == 2 ? (eQ ^ 8) : (jt == 1 ? (eQ ^ by2) : (eQ ^ 8 ^ by2)));
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                Ee[c] = mval(jt, cellLo + c, e);
-                Eo[c] = mval(jt, cellLo + c, e ^ 4);
             }
         } else {
 #pragma unroll
@@ -411,12 +397,9 @@ __device__ __forceinline__ void strip_pixel(int X, int Y, int sx, int sy, float 
 // Handling them in a separate small launch keeps the fast kernels free of divergent border
 // waves (a wave with one border strip used to execute both paths: +12 % VALU instructions).
 #define STRIP_MARGIN 16
-// margin kernels: branch-free taps with per-colour sums (tap_accumulate_sums: 81 -> 55 us per 4-frame margin launch at
-// 4K); 0: colour branches (A/B).  (The tile kernels' in-kernel straight path keeps the branches: the unrolled branch-free
-// taps push those kernels over their register budget.)
-#ifndef MARGIN_TAP_SUMS
-#define MARGIN_TAP_SUMS 1
-#endif
+// The margin kernels take branch-free taps with per-colour sums (accumulate_pixel_core<.., .., true>: tap_accumulate_sums,
+// 81 -> 55 us per 4-frame margin launch at 4K).  The tile kernels' in-kernel straight path keeps the colour branches: the
+// unrolled branch-free taps push those kernels over their register budget.
 
 // SCALE is a template parameter: the straight arithmetic takes floor((x + px + sx) / scale) twenty times per pixel, and an
 // integer division by a run-time value is ~40 instructions -- half of this kernel's work when the scale was a kernel argument
@@ -431,7 +414,7 @@ __global__ void __launch_bounds__(256)
     if constexpr (WIN) {
         int x, y;
         if (!margin_rect_pixel(mr, blockIdx.x * blockDim.x + threadIdx.x, x, y)) return;
-        accumulate_pixel_generic<GEOM_FULL, true, MARGIN_TAP_SUMS>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+        accumulate_pixel_generic<GEOM_FULL, true, true>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
                                                                    glv, dimX, dimY, scale, strideOut, strideMask, cfaPacked,
                                                                    mr.accX0, mr.accY0);
         return;
@@ -460,7 +443,7 @@ __global__ void __launch_bounds__(256)
         return;
     }
     if (y < rowBegin || y >= rowEnd) return;  // HR row window of this launch (stripe-sharded bursts)
-    accumulate_pixel_generic<GEOM_FULL, true, MARGIN_TAP_SUMS>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX,
+    accumulate_pixel_generic<GEOM_FULL, true, true>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX,
                                               dimY, scale, strideOut, strideMask, cfaPacked);
 }
 
@@ -520,7 +503,7 @@ __global__ void __launch_bounds__(64 * NF)
 #pragma unroll
         for (int m = 1; m < NF; m++)
             if (n == m) F = fr.f[m];
-        accumulate_pixel_core<GEOM_FULL, true, MARGIN_TAP_SUMS>(x, y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
+        accumulate_pixel_core<GEOM_FULL, true, true>(x, y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
                                                                 strideMask, cfaPacked, pixel, totalWeight);
     }
     sSum[n][0][lane] = pixel.x;
@@ -726,64 +709,226 @@ __global__ void __launch_bounds__(256)
 //    arithmetic), are updated in LDS and written back in memory order: every accumulator access
 //    on the HBM side is a fully used 128-byte line.
 #define TILE_COLS 66
-// waves per SIMD the register budget is sized for: 4 with one frame per launch (125 VGPRs), 3 with two
-// (163 VGPRs, no spill; 128 would spill 57)
-#ifndef TILE_WAVES
-#define TILE_WAVES 4
-#endif
-#ifndef TILE_WAVES2
-#define TILE_WAVES2 4
-#endif
-// Three and four frames per launch: both plane-sets staged (43 / 48 KiB of LDS: three workgroups per CU, so the register
-// budget is 168) or one at a time (31 / 36 KiB: four workgroups, 128 registers).  Measured at 4K x 16, four frames per
-// launch: 1.004 ms with both (no spills) against 1.044 - 1.068 ms with one (10 spilled registers and the second plane-set's
-// load exposed) -- both is the default; 0 keeps the other form for A/B.
-#ifndef TILE_GROUP_BOTH_PLANES
-#define TILE_GROUP_BOTH_PLANES 1
-#endif
-#define TILE_WAVES_NF(NF) ((NF) == 1 ? TILE_WAVES : ((NF) > 2 && TILE_GROUP_BOTH_PLANES) ? (TILE_LDS_ALIAS_ON ? 4 : 3) : TILE_WAVES2)
-// several frames per launch: pixel-major order with the tap weights shared by the frames (0: frame-major, weights per
-// frame; two frames at most)
-#ifndef TILE_PIXEL_MAJOR
-#define TILE_PIXEL_MAJOR 1
-#endif
-#define TILE_LDS_ALIAS_ON (TILE_LDS_ALIAS && TILE_PIXEL_MAJOR && TILE_GROUP_BOTH_PLANES)
-// Four workgroups per CU for the group kernels (three and four frames, fields at HR/4): the weight-sum plane-set is staged
-// over the kernel-parameter and flow texels once every wave is past its last read of them (39 KiB of LDS instead of 48), and
-// the rounded flow of a strip is kept in 8:8 bits per pixel relative to the tile's own rounded flow (8 registers instead of 16;
-// strips more than 127 HR pixels away from it take the straight arithmetic), which fits the 128-register budget of four waves per SIMD.  0: three workgroups (A/B).
-#ifndef TILE_LDS_ALIAS
-#define TILE_LDS_ALIAS 1
-#endif
-// pixel-major loop: frames whose certainty is saturated over the wave's footprint take strip_pixel_sat (0: A/B)
-#ifndef TILE_SAT_PATH
-#define TILE_SAT_PATH 1
-#endif
-// Certainty staged as four dword planes, one per CFA position ([e][mask row][frame][column]), instead of one float4 texel
-// per cell ([frame][mask row][column]): a tap row's read is then at a 4-byte lane stride (every bank once per 32 lanes for
-// a wave-uniform parity, two-way at worst) where the texel layout's 16-byte stride put the lanes on 8 of the 32 banks
-// (four-way by construction), and the frame's offset (66 dwords per frame) fits the DS offset field.  Same LDS bytes.
-// 0: texels (A/B: 6.05 against 5.75 ms per burst at 4K x 16, profiles/r05_tile_layout_ab.txt).
-#ifndef TILE_CERT_PLANES
-#define TILE_CERT_PLANES 1
-#endif
-// pixel-major loop: the raw sites as one uniform frame pointer plus one 32-bit lane offset per site row (the loads take the
-// scalar-base form, no 64-bit VALU adds); 0: three uniform row pointers plus a zero-extended lane offset (A/B: 5.76 against
-// 5.75 ms per burst, inside the spread)
-#ifndef TILE_RAW_LANE32
-#define TILE_RAW_LANE32 1
-#endif
-// ALIAS pass 1 without the 16-bit range tests on the rounded flow (implied by the 8-bit window, see there); 0: A/B (6.00 ms)
-#ifndef TILE_ALIAS_IMPLIED
-#define TILE_ALIAS_IMPLIED 1
-#endif
-// pixel-major loop: black / white levels held in VGPRs (an fp32 op with an SGPR operand issues at 0.63x the rate,
-// profiles/r02_ubench_valu_ops.txt); 0: kernel-argument SGPRs.  Off: at the 128-register cap of the four-frame kernel the six
-// registers come back as spills (32 bytes of scratch against 8, 6 720 static VALU against 6 633) and the burst takes 6.13
-// instead of 5.75 ms.
-#ifndef TILE_LEVELS_VGPR
-#define TILE_LEVELS_VGPR 0
-#endif
+// How the tile kernels are laid out; each choice below won its measurement (DESIGN.md section 5 has the tables).
+//  * Several frames per launch run in pixel-major order with the tap weights shared by the frames; one frame at HR/4 keeps
+//    the frame-major form.
+//  * Both accumulator plane-sets are staged at once.  Measured at 4K x 16, four frames per launch: 1.004 ms with both (no
+//    spills) against 1.044 - 1.068 ms with one at a time (10 spilled registers and the second plane-set's load exposed).
+//  * ALIAS (three and four frames per launch, fields at HR/4): four workgroups per CU.  The weight-sum plane-set is staged
+//    over the kernel-parameter and flow texels once every wave is past its last read of them (39 KiB of LDS instead of 48),
+//    and the rounded flow of a strip is kept in 8:8 bits per pixel relative to the tile's own rounded flow (8 registers
+//    instead of 16; strips more than 127 HR pixels away from it take the straight arithmetic), which fits the 128-register
+//    budget of four waves per SIMD.  Its pass 1 has no 16-bit range test on the rounded flow: the 8-bit window implies it
+//    (see there; with the test the burst took 6.00 ms).
+//  * Frames whose certainty is saturated over the wave's footprint take strip_pixel_sat.
+//  * Certainty is staged as four dword planes, one per CFA position ([e][mask row][frame][column]), not as one float4 texel
+//    per cell: a tap row's read is then at a 4-byte lane stride (every bank once per 32 lanes for a wave-uniform parity,
+//    two-way at worst) where a texel layout's 16-byte stride put the lanes on 8 of the 32 banks (four-way by construction),
+//    and the frame's offset (66 dwords per frame) fits the DS offset field.  Same LDS bytes.  Texels: 6.05 against 5.75 ms
+//    per burst at 4K x 16 (profiles/r05_tile_layout_ab.txt).
+//  * The raw sites are one uniform frame pointer plus one 32-bit lane offset per site row (the loads take the scalar-base
+//    form, no 64-bit VALU adds).
+//  * The black / white levels stay in kernel-argument SGPRs although an fp32 op with an SGPR operand issues at 0.63x the
+//    rate (profiles/r02_ubench_valu_ops.txt): held in VGPRs, at the 128-register cap of the four-frame kernel the six
+//    registers come back as spills (32 bytes of scratch against 8, 6 720 static VALU against 6 633) and the burst takes
+//    6.13 instead of 5.75 ms.
+// Workgroups per CU (= waves per SIMD) the register budget is sized for.  x2: four with fields at HR/4 (one frame: 125
+// VGPRs; three and four: the ALIAS layout), three with fields at HR/2 (41 / 49 KB of LDS).  x4: four (one frame: 113 VGPRs;
+// three and four: the ALIAS layout), but three with two frames per launch.
+constexpr int tile_waves_x2(int /*NF*/, int FR) { return FR == 4 ? 4 : 3; }
+constexpr int tile_waves_x4(int NF) { return NF == 2 ? 3 : 4; }
+// ---- pieces the tile kernels share (k_accumulate2xTile, k_accumulate2xTileBurst, k_accumulate4xTile) ----
+// HPT = HR pixels per kernel-parameter / flow texel: 2 or 4 at x2 (FR), 8 at x4.
+// Not every kernel uses every piece: the four-frame instances of k_accumulate2xTile sit at the 128-VGPR cap with one spilled
+// register, and moving its fractions, parameter mix, passes 1 and 2, plane staging, plane add or straight loop into a function
+// costs them 4 to 76 more bytes of scratch (the burst kernel: parameter mix and passes 1 and 2, 4 to 20 bytes).  Those stay
+// inline there; a piece is shared where every instance keeps its registers, scratch and LDS.
+typedef const __attribute__((address_space(3))) char* lds_cptr;
+typedef const __attribute__((address_space(1))) char* glb_cptr;
+
+// XCD-aware tile order (tilesPerXcd > 0, the default since round 4).  Workgroups are dealt round-robin to the 8 XCDs
+// (workgroup i -> XCD i & 7), each with its own L2.  A 256 x 4 tile stages 66 x 3 field texels (kernel parameters, the
+// flows and certainties of its frames: 112 B per texel with four frames) of which it owns 64 x 1, and its raw rows
+// overlap those of the tiles above and below: in launch order vertically adjacent tiles sit on DIFFERENT XCDs, so every
+// one of those re-reads misses its L2 and goes to the fabric (served by the Infinity Cache, counted by the L2's
+// memory-side counters): 1.16 GB read per launch beyond the accumulators against 0.30 GB of inputs (PMC, request-size
+// counters, profiles/r04_pmc_fuse_xcd.txt).  With the remap XCD k walks its own contiguous band of tiles in row-major
+// order, the neighbours are L2 hits, and the launch reads 0.305 GB + the accumulators: exactly its inputs.  The launch
+// time does not move (0.86 ms either way: the kernel is not bound by bytes) -- what it buys is 0.87 GB less fabric
+// traffic per launch for the kernels running beside it, and a traffic figure that is the algorithmic one.
+__device__ __forceinline__ int xcd_tile_index(int pid, int tilesPerXcd)
+{
+    return tilesPerXcd > 0 ? (pid & 7) * tilesPerXcd + (pid >> 3) : pid;  // tilesPerXcd == 0: launch order (A/B)
+}
+
+// Interpolation fraction of HR column (or row) p on an axis of hrN HR pixels and fN field texels: the float path of
+// tex_coord, with the texel floor(xB) predicted -- p / HPT - 1 for the first half of a texel's pixels, p / HPT for the
+// second -- and verified.  -1: not on the predicted texel, or that texel's right / lower neighbour is outside the field
+// (ROW: or the texel itself is above it).
+template <int HPT, bool ROW>
+__device__ __forceinline__ float texel_fraction(int p, int hrN, int fN)
+{
+    constexpr int SH = HPT == 8 ? 3 : (HPT == 4 ? 2 : 1);
+    const float pos = ((float)p + 0.5f) / (float)hrN;
+    float xB = pos * (float)fN - 0.5f;
+    if (!finitef(xB)) xB = 0.0f;
+    const float fxf = floorf(xB);
+    const int pred = (p >> SH) - 1 + ((p & (HPT - 1)) < HPT / 2 ? 0 : 1);
+    const bool ok = (f2i(fxf) == pred) && (pred + 1 <= fN - 1) && (!ROW || f2i(fxf) >= 0);
+    return ok ? xB - fxf : -1.0f;
+}
+
+// texel columns a strip touches, and the left texel of pixel k's pair among them
+template <int HPT>
+struct StripTexels {
+    static constexpr int SC = HPT == 8 ? 2 : (HPT == 4 ? 3 : 4);
+    static constexpr int ci(int k) { return HPT == 8 ? 0 : (HPT == 4 ? (k < 2 ? 0 : 1) : (k + 1) >> 1); }
+};
+
+// Pass 1, one frame: the whole-pixel flow of the strip's four pixels (SCALE x the flow at f0 / f1, two LDS rows of 2 x SC
+// texels, rounded) and the fast-path admission -- every tap inside the frame: 0 <= q and ((q + 4) / SCALE) <= dim - 1  <=>
+// (unsigned)q <= SCALE * dim - 5.  `safe` comes in as what the strip's geometry and kernel parameters allow and is returned
+// with this frame's tests added.
+// RANGE_BITS: the rounded flow must also lie inside that many signed bits (wilder strips take the straight arithmetic): it
+// keeps saturated conversions from wrapping back into range.
+template <int SCALE, int HPT, int RANGE_BITS>
+__device__ __forceinline__ bool strip_flow(bool safe, const float2* f0, const float2* f1, const float (&av)[4], float b, int X0, int Y,
+                                           uint32_t xmax, uint32_t ymax, int (&sx)[4], int (&sy)[4])
+{
+    constexpr int SC = StripTexels<HPT>::SC;
+    float2 Ft[2][SC];
+#pragma unroll
+    for (int c = 0; c < SC; c++) {
+        Ft[0][c] = f0[c];
+        Ft[1][c] = f1[c];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int ci = StripTexels<HPT>::ci(k);
+        const float ux = lerp4(Ft[0][ci].x, Ft[0][ci + 1].x, Ft[1][ci].x, Ft[1][ci + 1].x, av[k], b);
+        const float uy = lerp4(Ft[0][ci].y, Ft[0][ci + 1].y, Ft[1][ci].y, Ft[1][ci + 1].y, av[k], b);
+        sx[k] = round2i(ux * (float)SCALE);
+        sy[k] = round2i(uy * (float)SCALE);
+        const int qx = X0 + k + sx[k] - 2, qy = Y + sy[k] - 2;
+        safe = safe && (uint32_t)(sx[k] + (1 << RANGE_BITS)) < (2u << RANGE_BITS) && (uint32_t)(sy[k] + (1 << RANGE_BITS)) < (2u << RANGE_BITS);
+        safe = safe && (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
+    }
+    return safe;
+}
+
+// A wave's accumulator row segment (3 KiB = 192 chunks of 16 bytes per plane-set) between global memory and its LDS row, in
+// memory order: contiguous 1 KiB per instruction.  g is the segment's address in the frame -- or, WIN, the WINDOW's row: the
+// chunk at frame-row byte gb then lives at g + gb - winB0 if winB0 <= gb < winB1, and chunks outside the window are neither
+// staged nor written back.
+template <bool WIN>
+struct AccSegment {
+    size_t rowBytes;      // bytes of the frame's accumulator row
+    size_t segByte;       // first byte of the segment in it
+    size_t winB0, winB1;  // WIN: the window's bytes of the row
+    int fresh;            // first launch of a burst: the accumulators are defined to be zero and are not read at all
+    __device__ __forceinline__ bool inWin(size_t gb) const { return !WIN || (gb >= winB0 && gb + 16 <= winB1); }
+    __device__ __forceinline__ char* chunk(char* g, size_t off) const { return WIN ? g + (segByte + off - winB0) : g + off; }
+    // global -> LDS: zeroes if fresh, else the asynchronous copy (no VGPRs; the caller waits with vmcnt(0))
+    __device__ __forceinline__ void stage(char* g, float4* lds, int lx) const
+    {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if (fresh) {
+                lds[j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else {
+                const size_t off = (size_t)(j * 64 + lx) * 16;
+                if (segByte + off + 16 <= rowBytes && inWin(segByte + off))
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)chunk(g, off),
+                                                     (__attribute__((address_space(3))) void*)&lds[j * 64], 16, 0, 0);
+            }
+        }
+    }
+    // LDS -> global.  The 16-pixel side margins of the row belong to the margin kernel: their (unchanged) chunks are not
+    // written back.  A fresh launch defines them (zero) instead.
+    __device__ __forceinline__ void store(const float4* lds, char* g, int lx) const
+    {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const size_t off = (size_t)(j * 64 + lx) * 16;
+            const size_t gb = segByte + off;
+            const bool sideMargin = gb < (size_t)STRIP_MARGIN * 12 || gb + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
+            if (gb + 16 <= rowBytes && (fresh || !sideMargin) && inWin(gb)) *(float4*)chunk(g, off) = lds[j * 64 + lx];
+        }
+    }
+};
+
+// my[0..11] (a lane's 4 pixels x 3 channels of a staged plane) += acc[0..11]
+__device__ __forceinline__ void lane_add12(float* my, const float* acc)
+{
+    float4* my4 = (float4*)my;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        float4 a = my4[j];
+        a.x += acc[4 * j + 0]; a.y += acc[4 * j + 1]; a.z += acc[4 * j + 2]; a.w += acc[4 * j + 3];
+        my4[j] = a;
+    }
+}
+
+// A border / wild-flow / non-PSD strip of frame F: the straight per-pixel arithmetic on the lane's staged values (after the
+// sums have left the registers: it needs most of them).  These strips are a few per frame.
+template <int SCALE>
+__device__ __forceinline__ void strip_straight(const TileFrame& F, float* myP, float* myW, int X0, int Y, int hrW, const mfsr_tex2d& kernelParam,
+                                               const Levels3& glv, int dimX, int dimY, int strideMask, int cfaPacked)
+{
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+        const int X = X0 + k;
+        if (X >= 1 && X < hrW - 1) {
+            pix3 px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
+            pix3 tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
+            accumulate_pixel_core<GEOM_FULL, true>(X, Y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, SCALE, strideMask,
+                                                   cfaPacked, px, tw);
+            myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z;
+            myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z;
+        }
+    }
+}
+
+// What the pixel-frame bodies of the x2 pass 2 share, taken once per strip (each body is its own divergent region, the
+// compiler does not hoist across them).
+// Certainty rows: the LDS address of the row each tap row reads, as opaque 32-bit addresses -- the compiler would otherwise
+// split the planes' own address off them and add it back per read as a constant too large for the DS offset field, where
+// frame and cell now fit.
+template <int NF>
+__device__ __forceinline__ void certainty_row_addrs(float (*planes)[3][NF][TILE_COLS], int lx, int ly, uint32_t (&mrowA)[5])
+{
+#pragma unroll
+    for (int jt = 0; jt < 5; jt++) {
+        mrowA[jt] = (uint32_t)(uintptr_t)(lds_cptr)&planes[0][((ly + jt - 2) >> 2) + 1][0][lx];
+        asm volatile("" : "+v"(mrowA[jt]));
+    }
+}
+// Raw sites: the frames' own pointers (opaque: kept in SGPR pairs, not fetched again by every body).
+template <int NF>
+__device__ __forceinline__ void raw_bases(const TileFrame* f, glb_cptr (&rawBase)[NF])
+{
+#pragma unroll
+    for (int n = 0; n < NF; n++) {
+        rawBase[n] = (glb_cptr)f[n].raw;
+        asm volatile("" : "+s"(rawBase[n]));
+    }
+}
+// Bit n: frame n's certainty is exactly 1 on every texel this WAVE reads (its 66 texel columns on the two mask rows its tap
+// rows touch); such a frame takes strip_pixel_sat: a wave-uniform (scalar) branch per frame, bit-identical results.
+template <int NF>
+__device__ __forceinline__ uint32_t saturated_frames(const uint32_t (*unsat)[TILE_COLS], int lx, int ly)
+{
+    const int r0 = ((ly - 2) >> 2) + 1;  // mask rows ((ly + jt - 2) >> 2) + 1, jt = 0..4: r0 and r0 + 1
+    uint32_t u = unsat[r0][lx] | unsat[r0 + 1][lx];
+    if (lx < 2) u |= unsat[r0][64 + lx] | unsat[r0 + 1][64 + lx];
+    uint32_t satW = 0;
+#pragma unroll
+    for (int n = 0; n < NF; n++)
+        if (__builtin_amdgcn_ballot_w64((u >> n) & 1u) == 0) satW |= 1u << n;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)satW);
+}
+
 // (Measured and not kept: the nine raw sites of a body loaded one body ahead -- 161 VGPRs, the address arithmetic twice:
 // 0.96 against 0.876 ms per isolated launch.  The round trip of the raw loads is already hidden.)
 // NF frames per launch (1 to 4).  Everything that does not depend on the frame is done once for
@@ -796,59 +941,41 @@ __global__ void __launch_bounds__(256)
 // the accumulators hold the window [wx0, wx1) x [wy0, ..) only, and the 16-byte accumulator chunks outside it are neither
 // staged nor written back (window edges are multiples of 16 pixels = 12 chunks: no chunk straddles one).
 template <int CFA, int NF, int FR = 4, bool WIN = false>
-__global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR = 2: 41 / 49 KB of LDS, three workgroups per CU
+__global__ void __launch_bounds__(256, tile_waves_x2(NF, FR))
     k_accumulate2xTile(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked,
                        int tilesX, int tilesY, int tilesPerXcd, int fresh, int tileY0, int tileX0, int wx0, int wx1, int wy0)
 {
-    // XCD-aware tile order (tilesPerXcd > 0, the default since round 4).  Workgroups are dealt round-robin to the 8 XCDs
-    // (workgroup i -> XCD i & 7), each with its own L2.  A 256 x 4 tile stages 66 x 3 field texels (kernel parameters, the
-    // flows and certainties of its frames: 112 B per texel with four frames) of which it owns 64 x 1, and its raw rows
-    // overlap those of the tiles above and below: in launch order vertically adjacent tiles sit on DIFFERENT XCDs, so every
-    // one of those re-reads misses its L2 and goes to the fabric (served by the Infinity Cache, counted by the L2's
-    // memory-side counters): 1.16 GB read per launch beyond the accumulators against 0.30 GB of inputs (PMC, request-size
-    // counters, profiles/r04_pmc_fuse_xcd.txt).  With the remap XCD k walks its own contiguous band of tiles in row-major
-    // order, the neighbours are L2 hits, and the launch reads 0.305 GB + the accumulators: exactly its inputs.  The launch
-    // time does not move (0.86 ms either way: the kernel is not bound by bytes) -- what it buys is 0.87 GB less fabric
-    // traffic per launch for the kernels running beside it, and a traffic figure that is the algorithmic one.
-    const int pid = (int)blockIdx.x;
-    const int tile = tilesPerXcd > 0 ? (pid & 7) * tilesPerXcd + (pid >> 3) : pid;  // tilesPerXcd == 0: launch order (A/B)
+    const int tile = xcd_tile_index((int)blockIdx.x, tilesPerXcd);
     if (tile >= tilesX * tilesY) return;  // whole workgroup (uniform), before any barrier
     const int bIdYrel = tile / tilesX, bIdX = tile - bIdYrel * tilesX + (WIN ? tileX0 : 0);
     const int bIdY = bIdYrel + tileY0;  // tileY0: first tile row of this launch's HR row window
     static_assert(FR == 4 || FR == 2, "field resolution");
     constexpr int FC = 256 / FR + 2, FROWS = 4 / FR + 2;  // field texels a tile touches: 66 x 3 (FR = 4), 130 x 4 (FR = 2)
-    constexpr int PL = (NF <= 2 || TILE_GROUP_BOTH_PLANES) ? 2 : 1;
-    // ALIAS: the field texels live in the (not yet staged) weight-sum plane-set; see TILE_LDS_ALIAS
-    constexpr bool ALIAS = TILE_LDS_ALIAS_ON && FR == 4 && NF > 2 && PL == 2;
-    __shared__ __attribute__((aligned(16))) float4 sAcc[PL][4][192];
+    // ALIAS: the field texels live in the (not yet staged) weight-sum plane-set; see above
+    constexpr bool ALIAS = FR == 4 && NF > 2;
+    __shared__ __attribute__((aligned(16))) float4 sAcc[2][4][192];  // both plane-sets staged
     __shared__ float4 sKown[ALIAS ? 1 : FROWS][ALIAS ? 1 : FC];
     __shared__ float2 sFown[ALIAS ? 1 : NF][ALIAS ? 1 : FROWS][ALIAS ? 1 : FC];
     static_assert(!ALIAS || sizeof(float4) * FROWS * FC + sizeof(float2) * NF * FROWS * FC <= sizeof(float4) * 4 * 192, "field texels fit a plane-set");
-    float4(*sK)[FC] = ALIAS ? (float4(*)[FC]) & sAcc[PL - 1][0][0] : (float4(*)[FC]) & sKown[0][0];  // .w = 1 if the texel is PSD and finite, else 0
-    float2(*sF)[FROWS][FC] = ALIAS ? (float2(*)[FROWS][FC])((char*)&sAcc[PL - 1][0][0] + sizeof(float4) * FROWS * FC)
+    float4(*sK)[FC] = ALIAS ? (float4(*)[FC]) & sAcc[1][0][0] : (float4(*)[FC]) & sKown[0][0];  // .w = 1 if the texel is PSD and finite, else 0
+    float2(*sF)[FROWS][FC] = ALIAS ? (float2(*)[FROWS][FC])((char*)&sAcc[1][0][0] + sizeof(float4) * FROWS * FC)
                                    : (float2(*)[FROWS][FC]) & sFown[0][0][0];
-    __shared__ float4 sM[NF][3][TILE_COLS];
-    // TILE_CERT_PLANES: the same bytes as four planes [CFA position][mask row][frame][column]
-    float(*sMp)[3][NF][TILE_COLS] = (float(*)[3][NF][TILE_COLS]) & sM[0][0][0];
-    constexpr int EP = TILE_CERT_PLANES ? 3 * NF * TILE_COLS * 4 : 4;  // strip_pixel_w's layout argument
+    // certainty: four dword planes [CFA position][mask row][frame][column] (allocated as 16-byte units)
+    __shared__ float4 sCert[NF][3][TILE_COLS];
+    float(*sMp)[3][NF][TILE_COLS] = (float(*)[3][NF][TILE_COLS]) & sCert[0][0][0];
+    constexpr int EP = 3 * NF * TILE_COLS * 4;  // strip_pixel_w's plane stride
     // stored by CFA position (y parity << 1 | x parity), not by channel: strip_pixel_w<EP> indexes it
     auto stage_cert = [&](int n, int r, int c, const float (&mc)[3]) {
-        if constexpr (TILE_CERT_PLANES) {
-            sMp[0][r][n][c] = mc[Cfa<CFA>::col(0, 0)];
-            sMp[1][r][n][c] = mc[Cfa<CFA>::col(0, 1)];
-            sMp[2][r][n][c] = mc[Cfa<CFA>::col(1, 0)];
-            sMp[3][r][n][c] = mc[Cfa<CFA>::col(1, 1)];
-        } else {
-            sM[n][r][c] = make_float4(mc[Cfa<CFA>::col(0, 0)], mc[Cfa<CFA>::col(0, 1)], mc[Cfa<CFA>::col(1, 0)], mc[Cfa<CFA>::col(1, 1)]);
-        }
+        sMp[0][r][n][c] = mc[Cfa<CFA>::col(0, 0)];
+        sMp[1][r][n][c] = mc[Cfa<CFA>::col(0, 1)];
+        sMp[2][r][n][c] = mc[Cfa<CFA>::col(1, 0)];
+        sMp[3][r][n][c] = mc[Cfa<CFA>::col(1, 1)];
     };
-    __shared__ uint32_t sUnsat[3][TILE_COLS];  // bit n: frame n's certainty texel is not (1, 1, 1)  (TILE_SAT_PATH)
+    __shared__ uint32_t sUnsat[3][TILE_COLS];  // bit n: frame n's certainty texel is not (1, 1, 1)
     __shared__ __attribute__((aligned(16))) float sColA[256];  // x fraction per HR column of the tile, -1 = not on the predicted texel
     __shared__ float sRowB[4];                                 // y fraction per HR row of the tile, -1 likewise
     // accumulator staging: per wave and plane-set the wave's 3 KiB row segment, in memory order
-    // (TILE_GROUP_BOTH_PLANES = 0, three and four frames per launch: one plane-set at a time through the same 3 KiB so that
-    // four workgroups per CU fit the 160 KiB -- the weight sums wait in registers, the second plane-set's load is exposed)
     const int lx = threadIdx.x, ly = threadIdx.y;
     const int tx = bIdX * 64 + lx;
     const int Y = bIdY * 4 + ly;
@@ -952,7 +1079,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     };
     if (rowLive) {
         stage_plane(gP, 0);
-        if (PL == 2 && !ALIAS) stage_plane(gW, 1);  // (ALIAS: after the last read of the field texels, below)
+        if (!ALIAS) stage_plane(gW, 1);  // (ALIAS: after the last read of the field texels, below)
     }
     __syncthreads();
     if (!rowLive) return;
@@ -998,10 +1125,8 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
     for (int i = 0; i < 12; i++) accP[i] = accW[i] = 0.0f;
     const uint32_t xmax = (uint32_t)(2 * dimX - 5), ymax = (uint32_t)(2 * dimY - 5);
     uint32_t safeBits = 0;  // bit n: frame n took the fast path
-    static_assert(NF <= 2 || TILE_PIXEL_MAJOR, "three and four frames per launch exist in pixel-major order only");
-#if TILE_PIXEL_MAJOR
     if constexpr (NF > 1 || FR != 4) {
-        // Two frames, pixel-major: the 13 tap weights of a pixel (12 v_exp_f32 and their exponents: a fifth of the
+        // Several frames, pixel-major: the 13 tap weights of a pixel (12 v_exp_f32 and their exponents: a fifth of the
         // pixel's arithmetic) depend on the kernel parameters only, so each pixel takes them ONCE and applies them to
         // both frames before the next pixel starts -- 13 live registers instead of the 4 x 13 a frame-major loop would
         // have to keep (that was 214 VGPRs; recomputing them per frame was the faster frame-major form).
@@ -1038,7 +1163,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                 // dx + 128 < 256 only if sx is congruent to bsx + d with d in [-128, 127]; |bsx| <= 32000 puts bsx + d in
                 // [-32128, 32127], far from wrapping, so the int32 sx IS that value: inside 16 signed bits.  This holds for
                 // every int32 sx, saturated conversions of wild flow included.
-                if constexpr (!(ALIAS && TILE_ALIAS_IMPLIED))
+                if constexpr (!ALIAS)
                     safe = safe && (uint32_t)(sx + (1 << 15)) < (2u << 15) && (uint32_t)(sy + (1 << 15)) < (2u << 15);
                 safe = safe && (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
                 if constexpr (ALIAS) {
@@ -1059,57 +1184,14 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
             stage_plane(gW, 1);
         }
         // Pass 2, per pixel: weights once, then frame after frame.  What the eight pixel-frame bodies share is taken
-        // here once (each body is its own divergent region, the compiler does not hoist across them): the LDS address of
-        // the certainty row each tap row reads, and the raw row bases (uniform: SGPR pairs, 32-bit lane offsets).
-        // Certainty rows.  TILE_CERT_PLANES: mrowA, opaque 32-bit LDS addresses -- the compiler would otherwise split sM's own
-        // address off them and add it back per read as a constant too large for the DS offset field, where frame and cell now
-        // fit.  Else: mrow, pointers into the texel layout.  Only one of the two is set and read.
-        typedef const __attribute__((address_space(3))) char* lds_cptr;
-        const float* mrow[5] = {};
-        uint32_t mrowA[5] = {};
-#pragma unroll
-        for (int jt = 0; jt < 5; jt++) {
-            if constexpr (TILE_CERT_PLANES) {
-                mrowA[jt] = (uint32_t)(uintptr_t)(lds_cptr)&sMp[0][((ly + jt - 2) >> 2) + 1][0][lx];
-                asm volatile("" : "+v"(mrowA[jt]));
-            } else {
-                mrow[jt] = (const float*)&sM[0][((ly + jt - 2) >> 2) + 1][lx];
-            }
-        }
-        // Raw sites.  TILE_RAW_LANE32: rawBase, the frames' own pointers (opaque: kept in SGPR pairs, not fetched again by
-        // every body) and rawPitch, the bytes per raw row.  Else: rawRow, one pointer per frame and site row.
-        typedef const __attribute__((address_space(1))) char* glb_cptr;
-        const char* rawRow[NF][3] = {};
-        glb_cptr rawBase[NF] = {};
-        const uint32_t rawPitch = (uint32_t)dimX * 2u;
-#pragma unroll
-        for (int n = 0; n < NF; n++) {
-            if constexpr (TILE_RAW_LANE32) {
-                rawBase[n] = (glb_cptr)fr.f[n].raw;
-                asm volatile("" : "+s"(rawBase[n]));
-            } else {
-#pragma unroll
-                for (int j = 0; j < 3; j++) rawRow[n][j] = (const char*)(fr.f[n].raw + (size_t)j * dimX);
-            }
-        }
-        // Levels.  TILE_LEVELS_VGPR: a copy held in VGPRs; else lvv is lv (kernel-argument SGPRs).
-        StripLevels lvv = lv;
-        if constexpr (TILE_LEVELS_VGPR) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) asm volatile("" : "+v"(lvv.black[c]), "+v"(lvv.invWhite[c]));
-        }
-        // Frames whose certainty is exactly 1 on every texel this WAVE reads (its 66 texel columns on the two mask rows
-        // its tap rows touch) take strip_pixel_sat: a wave-uniform (scalar) branch per frame, bit-identical results.
-        uint32_t satW = 0;
-        if constexpr (TILE_SAT_PATH) {
-            const int r0 = ((ly - 2) >> 2) + 1;  // mask rows ((ly + jt - 2) >> 2) + 1, jt = 0..4: r0 and r0 + 1
-            uint32_t u = sUnsat[r0][lx] | sUnsat[r0 + 1][lx];
-            if (lx < 2) u |= sUnsat[r0][64 + lx] | sUnsat[r0 + 1][64 + lx];
-#pragma unroll
-            for (int n = 0; n < NF; n++)
-                if (__builtin_amdgcn_ballot_w64((u >> n) & 1u) == 0) satW |= 1u << n;
-            satW = (uint32_t)__builtin_amdgcn_readfirstlane((int)satW);
-        }
+        // here once (each body is its own divergent region, the compiler does not hoist across them).
+        uint32_t mrowA[5];
+        certainty_row_addrs<NF>(sMp, lx, ly, mrowA);
+        glb_cptr rawBase[NF];
+        raw_bases<NF>(fr.f, rawBase);
+        const uint32_t rawPitch = (uint32_t)dimX * 2u;  // bytes per raw row
+        StripLevels lvv = lv;  // levels in kernel-argument SGPRs (a copy by value: the bodies' code depends on it)
+        const uint32_t satW = saturated_frames<NF>(sUnsat, lx, ly);
         auto pixel = [&](auto kc) {
             constexpr int k = decltype(kc)::value;
             if (safeBits == 0) return;
@@ -1120,7 +1202,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
             float w[13];
             tap_weights13(kxa[k], kya[k], kza[k], w);
             float P[3][4];
-            if (TILE_SAT_PATH && satW) tap_pair_sums(w, P);
+            if (satW) tap_pair_sums(w, P);
 #pragma unroll
             for (int n = 0; n < NF; n++) {
                 if ((safeBits >> n) & 1u) {
@@ -1128,34 +1210,24 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                         const uint32_t boff = (uint32_t)(y0 * dimX + x0) * 2u;  // admitted strips: x0, y0 >= 0, inside the frame
 #pragma unroll
                         for (int j = 0; j < 3; j++) {
-                            if constexpr (TILE_RAW_LANE32) {
-                                // The whole offset in 32 bits, the lane part of the address is one VGPR: off <= (y0 + 2) * dimX * 2
-                                // + 2 * x0 lies inside the frame, and tile_kernel_ok() admits frames below 4 GiB only.  Opaque,
-                                // so that base + offset is formed in the body that loads -- both bodies of a frame take the same
-                                // sites, and an address hoisted above their branch reaches the loads as a 64-bit VGPR pair.
-                                uint32_t off = boff + (uint32_t)j * rawPitch;
-                                asm volatile("" : "+v"(off));
-                                glb_cptr rb = rawBase[n] + off;
+                            // The whole offset in 32 bits, the lane part of the address is one VGPR: off <= (y0 + 2) * dimX * 2
+                            // + 2 * x0 lies inside the frame, and tile_kernel_ok() admits frames below 4 GiB only.  Opaque,
+                            // so that base + offset is formed in the body that loads -- both bodies of a frame take the same
+                            // sites, and an address hoisted above their branch reaches the loads as a 64-bit VGPR pair.
+                            uint32_t off = boff + (uint32_t)j * rawPitch;
+                            asm volatile("" : "+v"(off));
+                            glb_cptr rb = rawBase[n] + off;
 #pragma unroll
-                                for (int i = 0; i < 3; i++)
-                                    sv[j][i] = (float)*(const __attribute__((address_space(1))) uint16_t*)(rb + 2 * i);
-                            } else {
-                                const char* rb = rawRow[n][j] + (size_t)boff;
-#pragma unroll
-                                for (int i = 0; i < 3; i++) sv[j][i] = (float)*(const uint16_t*)(rb + 2 * i);
-                            }
+                            for (int i = 0; i < 3; i++) sv[j][i] = (float)*(const __attribute__((address_space(1))) uint16_t*)(rb + 2 * i);
                         }
                     };
                     auto mval = [&](int jt, int cell, auto... e) {
-                        if constexpr (TILE_CERT_PLANES)
-                            return *(const __attribute__((address_space(3))) float*)(uintptr_t)((mrowA[jt] + ... + e) +
-                                                                                                 (uint32_t)(n * TILE_COLS + cell) * 4u);
-                        else
-                            return *(const float*)((const char*)(mrow[jt] + n * (3 * TILE_COLS * 4) + cell * 4) + (e + ...));
+                        return *(const __attribute__((address_space(3))) float*)(uintptr_t)((mrowA[jt] + ... + e) +
+                                                                                             (uint32_t)(n * TILE_COLS + cell) * 4u);
                     };
                     const int sx = ALIAS ? bsx[n] + (int)(int8_t)(sxy[n][0] >> (8 * k)) : (int)(int16_t)(sxy[n][ALIAS ? 0 : k] & 0xffffu);
                     const int sy = ALIAS ? bsy[n] + (int)(int8_t)(sxy[n][1] >> (8 * k)) : (int)sxy[n][ALIAS ? 0 : k] >> 16;
-                    if (TILE_SAT_PATH && ((satW >> n) & 1u))
+                    if ((satW >> n) & 1u)
                         strip_pixel_sat<k, CFA>(X0 + k, Y, sx, sy, w, P, rawf, lvv, aP, accW);
                     else
                         strip_pixel_w<k, CFA, EP>(X0 + k, Y, sx, sy, w, rawf, mval, lvv, aP, accW);
@@ -1171,70 +1243,22 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
         pixel(std::integral_constant<int, 1>{});
         pixel(std::integral_constant<int, 2>{});
         pixel(std::integral_constant<int, 3>{});
-    } else
-#endif
-    {
-    // one frame after the other in a real loop (not unrolled: the two bodies would only compete for
-    // registers); the frame's pointers are picked with scalar selects so the argument struct stays
-    // in SGPRs
-#pragma unroll 1
-    for (int n = 0; n < NF; n++) {
-        const uint16_t* raw = (NF > 1 && n) ? fr.f[NF - 1].raw : fr.f[0].raw;
-        // Per-frame copies of the interpolation fractions that the compiler cannot see through: otherwise
-        // it hoists the four bilinear weights of each pixel (and more) out of the frame loop and the
-        // kernel needs 194 VGPRs; like this it fits 163 with no spill (profiles/r01_ab_pair_opaque.txt:
-        // 0.667 -> 0.626 ms per pair).
-        float avn[4] = {av[0], av[1], av[2], av[3]};
-        float bn = b;
-#pragma unroll
-        for (int k = 0; k < 4; k++) asm volatile("" : "+v"(avn[k]));
-        asm volatile("" : "+v"(bn));
-#define av avn
-#define b bn
-        float2 Ft[2][3];
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) Ft[r][c] = sF[n][fr_ + r][lx + c];
+    } else {
+        // One frame, fields at HR/4: the frame-major form
         int sx[4], sy[4];
-        bool safe = geomOk && kOk;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int ci = k < 2 ? 0 : 1;
-            const float ux = lerp4(Ft[0][ci].x, Ft[0][ci + 1].x, Ft[1][ci].x, Ft[1][ci + 1].x, av[k], b);
-            const float uy = lerp4(Ft[0][ci].y, Ft[0][ci + 1].y, Ft[1][ci].y, Ft[1][ci + 1].y, av[k], b);
-            sx[k] = round2i(ux * 2.0f);
-            sy[k] = round2i(uy * 2.0f);
-            // every tap inside the frame: 0 <= q and ((q + 4) >> 1) <= dim - 1  <=>  (unsigned)q <= 2*dim - 5;
-            // the range test on the rounded flow keeps saturated conversions from wrapping back into range
-            const int qx = X0 + k + sx[k] - 2, qy = Y + sy[k] - 2;
-            safe = safe && (uint32_t)(sx[k] + (1 << 20)) < (2u << 20) && (uint32_t)(sy[k] + (1 << 20)) < (2u << 20) &&
-                   (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
-        }
-#undef av
-#undef b
-        if (safe) {
-            safeBits |= 1u << n;
-            // The 4 x 13 tap weights depend on the kernel parameters only, so the compiler would keep
-            // them in registers for the second frame (214 VGPRs, 2 waves per SIMD).  Recomputing them per
-            // frame (+10 % instructions) fits 168 VGPRs = 3 waves per SIMD and is 9 % faster (0.724 ->
-            // 0.660 ms per pair, profiles/r01_ab_pair_nohoist.txt): occupancy beats instruction count here.
-#pragma unroll
-            for (int k = 0; k < 4; k++) asm volatile("" : "+v"(kxa[k]), "+v"(kya[k]), "+v"(kza[k]));
+        if (strip_flow<2, 4, 20>(geomOk && kOk, &sF[0][fr_][lx], &sF[0][fr_ + 1][lx], av, b, X0, Y, xmax, ymax, sx, sy)) {
+            safeBits = 1u;
+            const uint16_t* raw = fr.f[0].raw;
             // certainty: LDS row of the mask row that tap row jt reads = ((ly + jt - 2) >> 2) + 1; column lx + cell
             auto mval = [&](int jt, int cell, auto... e) {
                 const int mr = ((ly + jt - 2) >> 2) + 1;
-                if constexpr (TILE_CERT_PLANES)
-                    return *(const float*)((const char*)&sMp[0][mr][n][lx + cell] + (e + ...));
-                else
-                    return *(const float*)((const char*)&sM[n][mr][lx + cell] + (e + ...));
+                return *(const float*)((const char*)&sMp[0][mr][0][lx + cell] + (e + ...));
             };
             strip_pixel<0, CFA, EP>(X0 + 0, Y, sx[0], sy[0], kxa[0], kya[0], kza[0], raw, dimX, mval, lv, accP, accW);
             strip_pixel<1, CFA, EP>(X0 + 1, Y, sx[1], sy[1], kxa[1], kya[1], kza[1], raw, dimX, mval, lv, accP, accW);
             strip_pixel<2, CFA, EP>(X0 + 2, Y, sx[2], sy[2], kxa[2], kya[2], kza[2], raw, dimX, mval, lv, accP, accW);
             strip_pixel<3, CFA, EP>(X0 + 3, Y, sx[3], sy[3], kxa[3], kya[3], kza[3], raw, dimX, mval, lv, accP, accW);
         }
-    }
     }
     // staged plane pl += this lane's 4 pixels x 3 channels
     auto add_plane = [&](int pl, const float* acc) {
@@ -1247,12 +1271,10 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
         }
     };
     // border / wild-flow / non-PSD strips of a frame: the straight per-pixel arithmetic on the staged values (after the
-    // sums have left the registers: it needs most of them).  With one staged plane-set at a time it runs once per set
-    // and keeps that set's result only -- these strips are a few per frame.
-    auto slow_frames = [&](auto doP, auto doW, int plP, int plW) {
-        constexpr bool DO_P = decltype(doP)::value, DO_W = decltype(doW)::value;
-        float* myP = (float*)&sAcc[plP][ly][0] + lx * 12;
-        float* myW = (float*)&sAcc[plW][ly][0] + lx * 12;
+    // sums have left the registers: it needs most of them).  These strips are a few per frame.
+    auto slow_frames = [&]() {
+        float* myP = (float*)&sAcc[0][ly][0] + lx * 12;
+        float* myW = (float*)&sAcc[1][ly][0] + lx * 12;
 #pragma unroll 1
         for (int n = 0; n < NF; n++) {
             if (!((safeBits >> n) & 1u) && stripLive) {
@@ -1265,13 +1287,12 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
                 for (int k = 0; k < 4; k++) {
                     const int X = X0 + k;
                     if (X >= 1 && X < hrW - 1) {
-                        pix3 px = {0.0f, 0.0f, 0.0f}, tw = {0.0f, 0.0f, 0.0f};
-                        if (DO_P) px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
-                        if (DO_W) tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
+                        pix3 px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
+                        pix3 tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
                         accumulate_pixel_core<GEOM_FULL, true>(X, Y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, 2,
                                                                strideMask, cfaPacked, px, tw);
-                        if (DO_P) { myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z; }
-                        if (DO_W) { myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z; }
+                        myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z;
+                        myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z;
                     }
                 }
             }
@@ -1283,35 +1304,21 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
 #pragma unroll
         for (int j = 0; j < 3; j++) {
             const size_t off = (size_t)(j * 64 + lx) * 16;
-            // the 16-pixel side margins of the row belong to k_accumulateMargin, which may run concurrently on the margin
-            // stream: their (unchanged) chunks are not written back.  A fresh launch defines them (zero) instead.
+            // the 16-pixel side margins of the row belong to k_accumulateMargin: their (unchanged) chunks are not written
+            // back.  A fresh launch defines them (zero) instead.
             const size_t gb = segByte + off;
             const bool sideMargin = gb < (size_t)STRIP_MARGIN * 12 || gb + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
             if (gb + 16 <= rowBytes && (fresh || !sideMargin) && inWin(gb)) *(float4*)chunk(g, off) = sAcc[pl][ly][j * 64 + lx];
         }
     };
-    using Yes = std::true_type;
-    using No = std::false_type;
     // staged accumulators must have landed before anyone reads them
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    constexpr bool valueSumsStaged = TILE_PIXEL_MAJOR && (NF > 1 || FR != 4);  // the pixel-major loop has added them already
-    if constexpr (PL == 2) {
-        if (!valueSumsStaged) add_plane(0, accP);
-        add_plane(1, accW);
-        if (safeBits != (1u << NF) - 1u) slow_frames(Yes{}, Yes{}, 0, 1);
-        store_plane(0, gP);
-        store_plane(1, gW);
-    } else {
-        if (!valueSumsStaged) add_plane(0, accP);
-        if (safeBits != (1u << NF) - 1u) slow_frames(Yes{}, No{}, 0, 0);
-        store_plane(0, gP);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // plane 0 has been read out before the copy overwrites it
-        stage_plane(gW, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        add_plane(0, accW);
-        if (safeBits != (1u << NF) - 1u) slow_frames(No{}, Yes{}, 0, 0);
-        store_plane(0, gW);
-    }
+    constexpr bool valueSumsStaged = NF > 1 || FR != 4;  // the pixel-major loop has added them already
+    if (!valueSumsStaged) add_plane(0, accP);
+    add_plane(1, accW);
+    if (safeBits != (1u << NF) - 1u) slow_frames();
+    store_plane(0, gP);
+    store_plane(1, gW);
 }
 
 // ---- burst form of the x2 Bayer tile kernel: G groups of four frames in one launch ------------------
@@ -1323,7 +1330,7 @@ __global__ void __launch_bounds__(256, (FR != 4 ? 3 : TILE_WAVES_NF(NF)))  // FR
 // Bit identity with the G launches it replaces dictates the structure: a pixel's value sums AND weight sums of a group are
 // formed from zero in registers and added to the staged planes at the end of their group (carrying the weight sums across
 // groups in registers would be another association), so both planes stay in LDS for the whole launch and the field texels
-// cannot borrow the weight plane's bytes (TILE_LDS_ALIAS): 48.6 KB of LDS, three workgroups per CU, a 168-register budget.
+// cannot borrow the weight plane's bytes (the ALIAS layout): 48.6 KB of LDS, three workgroups per CU, a 168-register budget.
 // The admission rules are those of the launches it replaces (the ALIAS form: rounded flow within the 8-bit window around the
 // tile's own, 8:8 bits per pixel), so the same strips take the in-kernel straight path; a write-back followed by a read is
 // exact, so the straight path sees the same plane values either way.
@@ -1343,15 +1350,13 @@ __global__ void __launch_bounds__(256, 3)
                             int tilesY, int tilesPerXcd, int fresh)
 {
     constexpr int NF = 4, FC = TILE_COLS, FROWS = 3;
-    const int pid = (int)blockIdx.x;
-    const int tile = tilesPerXcd > 0 ? (pid & 7) * tilesPerXcd + (pid >> 3) : pid;  // XCD-aware order, see k_accumulate2xTile
+    const int tile = xcd_tile_index((int)blockIdx.x, tilesPerXcd);
     if (tile >= tilesX * tilesY) return;  // whole workgroup (uniform), before any barrier
     const int bIdY = tile / tilesX, bIdX = tile - bIdY * tilesX;
     __shared__ __attribute__((aligned(16))) float4 sAcc[2][4][192];
     __shared__ float4 sK[FROWS][FC];  // .w = 1 if the texel is PSD and finite, else 0
     __shared__ float2 sF[NF][FROWS][FC];
     __shared__ __attribute__((aligned(16))) float sMp[4][3][NF][TILE_COLS];  // [CFA position][mask row][frame][column]
-    constexpr int EP = 3 * NF * TILE_COLS * 4;
     __shared__ uint32_t sUnsat[3][TILE_COLS];
     __shared__ __attribute__((aligned(16))) float sColA[256];
     __shared__ float sRowB[4];
@@ -1393,55 +1398,20 @@ __global__ void __launch_bounds__(256, 3)
         sK[r][c] = k;
     }
     stage_fields(0);
-    {
-        // column t of the tile: the float path of tex_coord, texel column predicted and verified (as k_accumulate2xTile)
-        const int X = bIdX * 256 + t;
-        const float posX = ((float)X + 0.5f) / (float)hrW;
-        float xB = posX * (float)fw - 0.5f;
-        if (!finitef(xB)) xB = 0.0f;
-        const float fxf = floorf(xB);
-        const int txc = X >> 2, ci = (t & 3) < 2 ? 0 : 1;
-        const bool ok = (f2i(fxf) == txc - 1 + ci) && (txc + ci <= fw - 1);
-        sColA[t] = ok ? xB - fxf : -1.0f;
-    }
-    if (t < 4) {
-        const int Yr = bIdY * 4 + t;
-        const float posY = ((float)Yr + 0.5f) / (float)hrH;
-        float yB = posY * (float)fh - 0.5f;
-        if (!finitef(yB)) yB = 0.0f;
-        const float fyf = floorf(yB);
-        const int frr = t < 2 ? 0 : 1;
-        const bool ok = (f2i(fyf) == bIdY - 1 + frr) && f2i(fyf) >= 0 && f2i(fyf) + 1 <= fh - 1;
-        sRowB[t] = ok ? yB - fyf : -1.0f;
-    }
+    sColA[t] = texel_fraction<4, false>(bIdX * 256 + t, hrW, fw);
+    if (t < 4) sRowB[t] = texel_fraction<4, true>(bIdY * 4 + t, hrH, fh);
     const bool rowLive = Y >= STRIP_MARGIN && Y < hrH - STRIP_MARGIN;
-    const size_t rowBytes = (size_t)hrW * 12;
     const size_t segByte = (size_t)bIdX * 3072;
-    char* gP = (char*)imgOut + (size_t)Y * strideOut + segByte;
-    char* gW = (char*)totalWeights + (size_t)Y * strideOut + segByte;
-    auto stage_plane = [&](char* g, int pl) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            if (fresh) {
-                sAcc[pl][ly][j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            } else {
-                const size_t off = (size_t)(j * 64 + lx) * 16;
-                if (segByte + off + 16 <= rowBytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + off),
-                                                     (__attribute__((address_space(3))) void*)&sAcc[pl][ly][j * 64], 16, 0, 0);
-            }
-        }
-    };
+    const AccSegment<false> seg{(size_t)hrW * 12, segByte, 0, 0, fresh};
     if (rowLive) {
-        stage_plane(gP, 0);
-        stage_plane(gW, 1);
+        seg.stage((char*)imgOut + (size_t)Y * strideOut + segByte, &sAcc[0][ly][0], lx);
+        seg.stage((char*)totalWeights + (size_t)Y * strideOut + segByte, &sAcc[1][ly][0], lx);
     }
     __syncthreads();
     if (!rowLive) return;
     const bool stripLive = X0 >= STRIP_MARGIN && X0 < hrW - STRIP_MARGIN;
 
     const int fr_ = ly < 2 ? 0 : 1;
-    auto ciOf = [](int k) { return k < 2 ? 0 : 1; };  // left texel of pixel k's pair
     const float b0 = sRowB[ly];
     const float4 av4 = ((const float4*)sColA)[lx];
     const bool geomOk = stripLive && b0 >= 0.0f && fminf(fminf(av4.x, av4.y), fminf(av4.z, av4.w)) >= 0.0f;
@@ -1460,7 +1430,7 @@ __global__ void __launch_bounds__(256, 3)
         kOk = kAll > 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const int ci = ciOf(k);
+            const int ci = k < 2 ? 0 : 1;
             const float w00 = (1.0f - av[k]) * (1.0f - b), w10 = av[k] * (1.0f - b), w01 = (1.0f - av[k]) * b, w11 = av[k] * b;
             auto mix = [&](float t00, float t10, float t01, float t11) {
                 return __builtin_fmaf(w11, t11, __builtin_fmaf(w01, t01, __builtin_fmaf(w10, t10, w00 * t00)));
@@ -1471,15 +1441,9 @@ __global__ void __launch_bounds__(256, 3)
         }
     }
     const uint32_t xmax = (uint32_t)(2 * dimX - 5), ymax = (uint32_t)(2 * dimY - 5);
-    // LDS address of the certainty row each tap row reads (opaque, see k_accumulate2xTile)
-    typedef const __attribute__((address_space(3))) char* lds_cptr;
-    typedef const __attribute__((address_space(1))) char* glb_cptr;
+    constexpr int EP = 3 * NF * TILE_COLS * 4;
     uint32_t mrowA[5];
-#pragma unroll
-    for (int jt = 0; jt < 5; jt++) {
-        mrowA[jt] = (uint32_t)(uintptr_t)(lds_cptr)&sMp[0][((ly + jt - 2) >> 2) + 1][0][lx];
-        asm volatile("" : "+v"(mrowA[jt]));
-    }
+    certainty_row_addrs<NF>(sMp, lx, ly, mrowA);
     const uint32_t rawPitch = (uint32_t)dimX * 2u;
     float* const myP = (float*)&sAcc[0][ly][0] + lx * 12;
     float* const myW = (float*)&sAcc[1][ly][0] + lx * 12;
@@ -1501,8 +1465,7 @@ __global__ void __launch_bounds__(256, 3)
 #pragma unroll
         for (int k = 0; k < 4; k++) asm volatile("" : "+v"(av[k]));
         asm volatile("" : "+v"(b));
-        // Pass 1, per frame: whole-pixel flow of the four pixels, 8:8 bits per pixel relative to the rounded flow of the tile's
-        // centre texel, and the fast-path admission -- the rules of k_accumulate2xTile's ALIAS form, whose launches this replaces
+        // Pass 1, per frame: the rules of k_accumulate2xTile's ALIAS form, whose launches this replaces
         uint32_t safeBits = 0;
         uint32_t sxy[NF][2];
         int bsx[NF], bsy[NF];
@@ -1520,7 +1483,7 @@ __global__ void __launch_bounds__(256, 3)
             bool safe = geomOk && kOk;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const int ci = ciOf(k);
+                const int ci = k < 2 ? 0 : 1;  // left texel of pixel k's pair
                 const float ux = lerp4(Ft[0][ci].x, Ft[0][ci + 1].x, Ft[1][ci].x, Ft[1][ci + 1].x, av[k], b);
                 const float uy = lerp4(Ft[0][ci].y, Ft[0][ci + 1].y, Ft[1][ci].y, Ft[1][ci + 1].y, av[k], b);
                 const int sx = round2i(ux * 2.0f), sy = round2i(uy * 2.0f);
@@ -1533,25 +1496,10 @@ __global__ void __launch_bounds__(256, 3)
             }
             if (safe) safeBits |= 1u << n;
         }
-        // the frames' raw pointers (opaque: kept in SGPR pairs)
-        glb_cptr rawBase[NF];
-#pragma unroll
-        for (int n = 0; n < NF; n++) {
-            rawBase[n] = (glb_cptr)fr.f[4 * g + n].raw;
-            asm volatile("" : "+s"(rawBase[n]));
-        }
-        // frames whose certainty is exactly 1 on every texel this wave reads take strip_pixel_sat
-        uint32_t satW = 0;
-        {
-            const int r0 = ((ly - 2) >> 2) + 1;
-            uint32_t u = sUnsat[r0][lx] | sUnsat[r0 + 1][lx];
-            if (lx < 2) u |= sUnsat[r0][64 + lx] | sUnsat[r0 + 1][64 + lx];
-#pragma unroll
-            for (int n = 0; n < NF; n++)
-                if (__builtin_amdgcn_ballot_w64((u >> n) & 1u) == 0) satW |= 1u << n;
-            satW = (uint32_t)__builtin_amdgcn_readfirstlane((int)satW);
-        }
         // Pass 2, per pixel: weights once, then frame after frame; the group's weight sums start from zero
+        glb_cptr rawBase[NF];
+        raw_bases<NF>(&fr.f[4 * g], rawBase);
+        const uint32_t satW = saturated_frames<NF>(sUnsat, lx, ly);
         float accW[12];
 #pragma unroll
         for (int i = 0; i < 12; i++) accW[i] = 0.0f;
@@ -1600,65 +1548,32 @@ __global__ void __launch_bounds__(256, 3)
         pixel(std::integral_constant<int, 2>{});
         pixel(std::integral_constant<int, 3>{});
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (strips that took no fast path have not waited yet)
-        {
-            float4* my = (float4*)myW;
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                float4 a = my[j];
-                a.x += accW[4 * j + 0]; a.y += accW[4 * j + 1]; a.z += accW[4 * j + 2]; a.w += accW[4 * j + 3];
-                my[j] = a;
-            }
-        }
-        // border / wild-flow / non-PSD strips of a frame: the straight per-pixel arithmetic on the staged values, which hold
-        // the earlier groups and this group's fast frames -- what the group's own launch would have read
+        lane_add12(myW, accW);
+        // refused strips: the straight arithmetic on the staged values, which hold the earlier groups and this group's fast
+        // frames -- what the group's own launch would have read
         if (safeBits != (1u << NF) - 1u && stripLive) {
 #pragma unroll 1
             for (int n = 0; n < NF; n++) {
                 if ((safeBits >> n) & 1u) continue;
                 const TileFrame F = fr.f[4 * g + n];
-#pragma unroll 1
-                for (int k = 0; k < 4; k++) {
-                    const int X = X0 + k;
-                    if (X >= 1 && X < hrW - 1) {
-                        pix3 px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
-                        pix3 tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
-                        accumulate_pixel_core<GEOM_FULL, true>(X, Y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, 2, strideMask,
-                                                               cfaPacked, px, tw);
-                        myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z;
-                        myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z;
-                    }
-                }
+                strip_straight<2>(F, myP, myW, X0, Y, hrW, kernelParam, glv, dimX, dimY, strideMask, cfaPacked);
             }
         }
     }
-    // both staged planes back in memory order, once (the side-margin chunks belong to the margin kernel unless fresh)
+    // both staged planes back in memory order, once
     // (the row's address is formed again from an opaque copy of Y: kept across the loop, the two pointers were spilled)
     int Yw = Y;
     asm volatile("" : "+v"(Yw));
-    auto store_plane = [&](int pl, pix3* base) {
-        char* g = (char*)base + (size_t)Yw * strideOut + segByte;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const size_t off = (size_t)(j * 64 + lx) * 16;
-            const size_t gb = segByte + off;
-            const bool sideMargin = gb < (size_t)STRIP_MARGIN * 12 || gb + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
-            if (gb + 16 <= rowBytes && (fresh || !sideMargin)) *(float4*)(g + off) = sAcc[pl][ly][j * 64 + lx];
-        }
-    };
-    store_plane(0, imgOut);
-    store_plane(1, totalWeights);
+    seg.store(&sAcc[0][ly][0], (char*)imgOut + (size_t)Yw * strideOut + segByte, lx);
+    seg.store(&sAcc[1][ly][0], (char*)totalWeights + (size_t)Yw * strideOut + segByte, lx);
 }
 
 // The margin pixels of the same G groups in one launch: k_accumulateMarginN<4>'s workgroup (64 pixels x 4 frames, one thread
 // per pixel and frame) in a rolled loop over the groups.  A frame's sums are taken from zero and meet in LDS; the pixel's first
 // thread reads the accumulators once, adds the frames one after another in call order -- the order of G consecutive launches --
 // and writes them once.  Whole workgroups reach every barrier (no thread leaves early).
-// 1 (default): this kernel; 0: k_accumulateMarginN<4 G> with one thread per (pixel, frame), up to 64 x 16 threads per
-// workgroup -- measured slower than the launches it replaces (233 against 4 x 50 us at 4K x 16).
-#ifndef MARGIN_BURST_LOOP
-#define MARGIN_BURST_LOOP 1
-#endif
+// (k_accumulateMarginN<4 G> with one thread per (pixel, frame), up to 64 x 16 threads per workgroup, was measured slower
+// than the launches it replaces: 233 against 4 x 50 us at 4K x 16)
 template <int SCALE>
 __global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulateMarginN<4>: the kernel is latency-bound
     k_accumulateMarginBurst(BurstFrames fr, int nGroups, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
@@ -1706,7 +1621,7 @@ __global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulat
 #pragma unroll
             for (int m = 1; m < NF; m++)
                 if (n == m) F = fr.f[4 * g + m];
-            accumulate_pixel_core<GEOM_FULL, true, MARGIN_TAP_SUMS>(xg, yg, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
+            accumulate_pixel_core<GEOM_FULL, true, true>(xg, yg, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
                                                                     strideMask, cfaPacked, pixel, totalWeight);
         }
         sSum[n][0][lane] = pixel.x;
@@ -1851,14 +1766,10 @@ __device__ __forceinline__ void strip_pixel4(int X, int Y, int sx, int sy, float
 // constant per wave.  Staging as in the x2 kernel (64 + 2 field texels x 3 rows, column/row fractions,
 // accumulator rows through LDS-DMA); the two waves of a row share its staged segment, hence the
 // workgroup barriers around the LDS update.
-// waves per SIMD the x4 kernel's register budget is sized for with two frames per launch (one frame: 113 VGPRs = 4)
-#ifndef TILE4_WAVES2
-#define TILE4_WAVES2 3
-#endif
-// (three and four frames per launch: four workgroups per CU by the layout of TILE_LDS_ALIAS, see k_accumulate2xTile)
+// (three and four frames per launch: four workgroups per CU by the ALIAS layout, see k_accumulate2xTile)
 // WIN: as k_accumulate2xTile (window edges are multiples of 16 pixels = 12 chunks of a 512-pixel tile row)
 template <int CFA, int NF, bool WIN = false>
-__global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALIAS_ON) ? 4 : TILE4_WAVES2)
+__global__ void __launch_bounds__(256, tile_waves_x4(NF))
     k_accumulate4xTile(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                        Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked,
                        int tilesX, int fresh, int tileY0, int tileX0, int wx0, int wx1, int wy0)
@@ -1868,12 +1779,12 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
     const int hrW = 4 * dimX, hrH = 4 * dimY;
     const int Y0 = 2 * bIdY;
     if (Y0 < STRIP_MARGIN || Y0 >= hrH - STRIP_MARGIN) return;  // whole workgroup (margin rows)
-    constexpr bool ALIAS = TILE_LDS_ALIAS_ON && NF > 2;
+    constexpr bool ALIAS = NF > 2;
     __shared__ __attribute__((aligned(16))) float4 sAcc[2][2][384];  // [plane-set][row][6 KiB row segment]
     __shared__ float4 sKown[ALIAS ? 1 : 3][ALIAS ? 1 : TILE_COLS];
     __shared__ float2 sFown[ALIAS ? 1 : NF][ALIAS ? 1 : 3][ALIAS ? 1 : TILE_COLS];
     static_assert(!ALIAS || sizeof(float4) * 3 * TILE_COLS + sizeof(float2) * NF * 3 * TILE_COLS <= sizeof(float4) * 2 * 384, "field texels fit a plane-set");
-    // ALIAS: the field texels live in the weight-sum plane-set's staging area until every wave has read them (TILE_LDS_ALIAS)
+    // ALIAS: the field texels live in the weight-sum plane-set's staging area until every wave has read them
     float4(*sK)[TILE_COLS] = ALIAS ? (float4(*)[TILE_COLS]) & sAcc[1][0][0] : (float4(*)[TILE_COLS]) & sKown[0][0];  // .w = 1 if PSD and finite
     float2(*sF)[3][TILE_COLS] = ALIAS ? (float2(*)[3][TILE_COLS])((char*)&sAcc[1][0][0] + sizeof(float4) * 3 * TILE_COLS)
                                       : (float2(*)[3][TILE_COLS]) & sFown[0][0][0];
@@ -1906,51 +1817,16 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
             }
         }
 #pragma unroll
-        for (int u = 0; u < 2; u++) {
-            // column of the tile: the float path of tex_coord, texel column predicted and verified
-            const int cl = t + 256 * u, X = bIdX * 512 + cl;
-            const float posX = ((float)X + 0.5f) / (float)hrW;
-            float xB = posX * (float)fw - 0.5f;
-            if (!finitef(xB)) xB = 0.0f;
-            const float fxf = floorf(xB);
-            const int c8 = X >> 3, ci = (X & 7) < 4 ? 0 : 1;
-            const bool ok = (f2i(fxf) == c8 - 1 + ci) && (c8 + ci <= fw - 1);
-            sColA[cl] = ok ? xB - fxf : -1.0f;
-        }
-        if (t < 2) {
-            const int Yr = Y0 + t;
-            const float posY = ((float)Yr + 0.5f) / (float)hrH;
-            float yB = posY * (float)fh - 0.5f;
-            if (!finitef(yB)) yB = 0.0f;
-            const float fyf = floorf(yB);
-            const int frr = (Yr & 7) < 4 ? 0 : 1;
-            const bool ok = (f2i(fyf) == band - 1 + frr) && f2i(fyf) >= 0 && f2i(fyf) + 1 <= fh - 1;
-            sRowB[t] = ok ? yB - fyf : -1.0f;
-        }
+        for (int u = 0; u < 2; u++) sColA[t + 256 * u] = texel_fraction<8, false>(bIdX * 512 + t + 256 * u, hrW, fw);
+        if (t < 2) sRowB[t] = texel_fraction<8, true>(Y0 + t, hrH, fh);
     }
     // accumulator rows of the tile -> LDS (wave (r, h) brings half h of row r), asynchronously
-    const size_t rowBytes = (size_t)hrW * 12;
     const size_t segByte = (size_t)bIdX * 6144 + (size_t)h * 3072;
-    const size_t winB0 = WIN ? (size_t)wx0 * 12 : 0, winB1 = WIN ? (size_t)wx1 * 12 : 0;
+    const AccSegment<WIN> seg{(size_t)hrW * 12, segByte, WIN ? (size_t)wx0 * 12 : 0, WIN ? (size_t)wx1 * 12 : 0, fresh};
     char* gP = WIN ? (char*)imgOut + (size_t)(Y - wy0) * strideOut : (char*)imgOut + (size_t)Y * strideOut + segByte;
     char* gW = WIN ? (char*)totalWeights + (size_t)(Y - wy0) * strideOut : (char*)totalWeights + (size_t)Y * strideOut + segByte;
-    auto inWin = [&](size_t gb) { return !WIN || (gb >= winB0 && gb + 16 <= winB1); };
-    auto chunk = [&](char* g, size_t off) { return WIN ? g + (segByte + off - winB0) : g + off; };
-    auto stage_plane = [&](char* g, int pl) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            if (fresh) {
-                sAcc[pl][r][h * 192 + j * 64 + lx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            } else {
-                const size_t off = (size_t)(j * 64 + lx) * 16;
-                if (segByte + off + 16 <= rowBytes && inWin(segByte + off))
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)chunk(g, off),
-                                                     (__attribute__((address_space(3))) void*)&sAcc[pl][r][h * 192 + j * 64], 16, 0, 0);
-            }
-        }
-    };
-    stage_plane(gP, 0);
-    if (!ALIAS) stage_plane(gW, 1);  // (ALIAS: after the last read of the field texels, below)
+    seg.stage(gP, &sAcc[0][r][h * 192], lx);
+    if (!ALIAS) seg.stage(gW, &sAcc[1][r][h * 192], lx);  // (ALIAS: after the last read of the field texels, below)
     __syncthreads();
     const bool stripLive = X0 >= STRIP_MARGIN && X0 < hrW - STRIP_MARGIN;
 
@@ -1988,8 +1864,6 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
     const uint32_t xmax = (uint32_t)(4 * dimX - 5), ymax = (uint32_t)(4 * dimY - 5);
     const int yq = Y & 7;
     uint32_t safeBits = 0;
-    static_assert(NF <= 2 || TILE_PIXEL_MAJOR, "three and four frames per launch exist in pixel-major order only");
-#if TILE_PIXEL_MAJOR
     if constexpr (NF > 1) {
         // pixel-major, as k_accumulate2xTile: per frame the whole-pixel flow of the strip's pixels and the admission, then
         // per pixel the tap weights once and frame after frame
@@ -2004,43 +1878,33 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
                 bsx[n] = __builtin_amdgcn_readfirstlane(min(max(round2i(cf.x * 4.0f), -32000), 32000));
                 bsy[n] = __builtin_amdgcn_readfirstlane(min(max(round2i(cf.y * 4.0f), -32000), 32000));
             }
-            float2 Ft[2][2];
-#pragma unroll
-            for (int r2 = 0; r2 < 2; r2++)
-#pragma unroll
-                for (int c = 0; c < 2; c++) Ft[r2][c] = sF[n][fr_ + r2][cb + c];
-            bool safe = geomOk && kOk;
+            int sx[4], sy[4];
+            bool safe = strip_flow<4, 8, 15>(geomOk && kOk, &sF[n][fr_][cb], &sF[n][fr_ + 1][cb], av, b, X0, Y, xmax, ymax, sx, sy);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const float ux = lerp4(Ft[0][0].x, Ft[0][1].x, Ft[1][0].x, Ft[1][1].x, av[k], b);
-                const float uy = lerp4(Ft[0][0].y, Ft[0][1].y, Ft[1][0].y, Ft[1][1].y, av[k], b);
-                const int sx = round2i(ux * 4.0f), sy = round2i(uy * 4.0f);
-                const int qx = X0 + k + sx - 2, qy = Y + sy - 2;
-                safe = safe && (uint32_t)(sx + (1 << 15)) < (2u << 15) && (uint32_t)(sy + (1 << 15)) < (2u << 15) &&
-                       (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
                 if constexpr (ALIAS) {
-                    const int dx = sx - bsx[n], dy = sy - bsy[n];
+                    const int dx = sx[k] - bsx[n], dy = sy[k] - bsy[n];
                     safe = safe && (uint32_t)(dx + 128) < 256u && (uint32_t)(dy + 128) < 256u;
                     sxy[n][0] |= ((uint32_t)dx & 0xffu) << (8 * k);
                     sxy[n][1] |= ((uint32_t)dy & 0xffu) << (8 * k);
                 } else {
-                    sxy[n][k] = ((uint32_t)sx & 0xffffu) | ((uint32_t)sy << 16);
+                    sxy[n][k] = ((uint32_t)sx[k] & 0xffffu) | ((uint32_t)sy[k] << 16);
                 }
             }
             if (safe) safeBits |= 1u << n;
         }
         if constexpr (ALIAS) {
             __syncthreads();  // every wave is past its reads of sK / sF
-            stage_plane(gW, 1);
+            seg.stage(gW, &sAcc[1][r][h * 192], lx);
         }
-        const float* mrow[5];
+        const float* certRow[5];
 #pragma unroll
-        for (int jt = 0; jt < 5; jt++) mrow[jt] = (const float*)&sM[0][(yq + jt - 2 + 8) >> 3][lx];
-        const char* rawRow[NF][2];
+        for (int jt = 0; jt < 5; jt++) certRow[jt] = (const float*)&sM[0][(yq + jt - 2 + 8) >> 3][lx];
+        const char* siteRow[NF][2];
 #pragma unroll
         for (int n = 0; n < NF; n++)
 #pragma unroll
-            for (int j = 0; j < 2; j++) rawRow[n][j] = (const char*)(fr.f[n].raw + (size_t)j * dimX);
+            for (int j = 0; j < 2; j++) siteRow[n][j] = (const char*)(fr.f[n].raw + (size_t)j * dimX);
         auto pixel = [&](auto k8c) {
             constexpr int K8 = decltype(k8c)::value, k = K8 & 3;
             if (safeBits == 0) return;
@@ -2053,12 +1917,12 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
                         const uint32_t boff = (uint32_t)(y0 * dimX + x0) * 2u;  // admitted strips: inside the frame
 #pragma unroll
                         for (int j = 0; j < 2; j++) {
-                            const char* rb = rawRow[n][j] + (size_t)boff;
+                            const char* rb = siteRow[n][j] + (size_t)boff;
                             sv[j][0] = (float)*(const uint16_t*)rb;
                             sv[j][1] = (float)*(const uint16_t*)(rb + 2);
                         }
                     };
-                    auto mval = [&](int jt, int cell, int e) { return mrow[jt][n * (3 * TILE_COLS * 4) + cell * 4 + e]; };
+                    auto mval = [&](int jt, int cell, int e) { return certRow[jt][n * (3 * TILE_COLS * 4) + cell * 4 + e]; };
                     const int sx = ALIAS ? bsx[n] + (int)(int8_t)(sxy[n][0] >> (8 * k)) : (int)(int16_t)(sxy[n][ALIAS ? 0 : k] & 0xffffu);
                     const int sy = ALIAS ? bsy[n] + (int)(int8_t)(sxy[n][1] >> (8 * k)) : (int)sxy[n][ALIAS ? 0 : k] >> 16;
                     strip_pixel4_w<K8, CFA, true>(X0 + k, Y, sx, sy, w, rawf, mval, lv, accP, accW);
@@ -2076,41 +1940,16 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
             pixel(std::integral_constant<int, 6>{});
             pixel(std::integral_constant<int, 7>{});
         }
-    } else
-#endif
-#pragma unroll 1
-    for (int n = 0; n < NF; n++) {
-        const uint16_t* raw = (NF > 1 && n) ? fr.f[NF - 1].raw : fr.f[0].raw;
-        float avn[4] = {av[0], av[1], av[2], av[3]};
-        float bn = b;
-#pragma unroll
-        for (int k = 0; k < 4; k++) asm volatile("" : "+v"(avn[k]));
-        asm volatile("" : "+v"(bn));
-        float2 Ft[2][2];
-#pragma unroll
-        for (int r2 = 0; r2 < 2; r2++)
-#pragma unroll
-            for (int c = 0; c < 2; c++) Ft[r2][c] = sF[n][fr_ + r2][cb + c];
+    } else {
+        // one frame: frame-major
         int sx[4], sy[4];
-        bool safe = geomOk && kOk;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float ux = lerp4(Ft[0][0].x, Ft[0][1].x, Ft[1][0].x, Ft[1][1].x, avn[k], bn);
-            const float uy = lerp4(Ft[0][0].y, Ft[0][1].y, Ft[1][0].y, Ft[1][1].y, avn[k], bn);
-            sx[k] = round2i(ux * 4.0f);
-            sy[k] = round2i(uy * 4.0f);
-            const int qx = X0 + k + sx[k] - 2, qy = Y + sy[k] - 2;
-            safe = safe && (uint32_t)(sx[k] + (1 << 20)) < (2u << 20) && (uint32_t)(sy[k] + (1 << 20)) < (2u << 20) &&
-                   (uint32_t)qx <= xmax && (uint32_t)qy <= ymax;
-        }
-        if (safe) {
-            safeBits |= 1u << n;
-#pragma unroll
-            for (int k = 0; k < 4; k++) asm volatile("" : "+v"(kxa[k]), "+v"(kya[k]), "+v"(kza[k]));
+        if (strip_flow<4, 8, 20>(geomOk && kOk, &sF[0][fr_][cb], &sF[0][fr_ + 1][cb], av, b, X0, Y, xmax, ymax, sx, sy)) {
+            safeBits = 1u;
+            const uint16_t* raw = fr.f[0].raw;
             // certainty: LDS row of the mask row that tap row jt reads, column lx + cell
             auto mval = [&](int jt, int cell, int e) {
                 const int mr = ((yq + jt - 2 + 8) >> 3);
-                const float* p = (const float*)&sM[n][mr][lx + cell];
+                const float* p = (const float*)&sM[0][mr][lx + cell];
                 return p[e];
             };
             if (h == 0) {
@@ -2132,48 +1971,24 @@ __global__ void __launch_bounds__(256, (NF) == 1 ? 4 : ((NF) > 2 && TILE_LDS_ALI
     float* myP = (float*)&sAcc[0][r][0] + (2 * lx + h) * 12;
     float* myW = (float*)&sAcc[1][r][0] + (2 * lx + h) * 12;
     if (safeBits) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            float4 a = ((float4*)myP)[j], c = ((float4*)myW)[j];
-            a.x += accP[4 * j + 0]; a.y += accP[4 * j + 1]; a.z += accP[4 * j + 2]; a.w += accP[4 * j + 3];
-            c.x += accW[4 * j + 0]; c.y += accW[4 * j + 1]; c.z += accW[4 * j + 2]; c.w += accW[4 * j + 3];
-            ((float4*)myP)[j] = a;
-            ((float4*)myW)[j] = c;
-        }
+        lane_add12(myP, accP);
+        lane_add12(myW, accW);
     }
+    if (safeBits != (1u << NF) - 1u && stripLive) {
 #pragma unroll 1
-    for (int n = 0; n < NF; n++) {
-        TileFrame F = fr.f[0];  // picked with scalar selects: the argument struct stays in SGPRs
+        for (int n = 0; n < NF; n++) {
+            if ((safeBits >> n) & 1u) continue;
+            TileFrame F = fr.f[0];  // picked with scalar selects: the argument struct stays in SGPRs
 #pragma unroll
-        for (int m = 1; m < NF; m++)
-            if (n == m) F = fr.f[m];
-        if (!((safeBits >> n) & 1u) && stripLive) {
-#pragma unroll 1
-            for (int k = 0; k < 4; k++) {
-                const int X = X0 + k;
-                if (X >= 1 && X < hrW - 1) {
-                    pix3 px = {myP[3 * k], myP[3 * k + 1], myP[3 * k + 2]};
-                    pix3 tw = {myW[3 * k], myW[3 * k + 1], myW[3 * k + 2]};
-                    accumulate_pixel_core<GEOM_FULL, true>(X, Y, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, 4,
-                                                           strideMask, cfaPacked, px, tw);
-                    myP[3 * k] = px.x; myP[3 * k + 1] = px.y; myP[3 * k + 2] = px.z;
-                    myW[3 * k] = tw.x; myW[3 * k + 1] = tw.y; myW[3 * k + 2] = tw.z;
-                }
-            }
+            for (int m = 1; m < NF; m++)
+                if (n == m) F = fr.f[m];
+            strip_straight<4>(F, myP, myW, X0, Y, hrW, kernelParam, glv, dimX, dimY, strideMask, cfaPacked);
         }
     }
     __syncthreads();
     // write the half-row segments back in memory order
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const size_t off = (size_t)(j * 64 + lx) * 16;
-        const size_t g = segByte + off;  // side-margin chunks: see k_accumulate2xTile
-        const bool sideMargin = g < (size_t)STRIP_MARGIN * 12 || g + 16 > rowBytes - (size_t)STRIP_MARGIN * 12;
-        if (g + 16 <= rowBytes && (fresh || !sideMargin) && inWin(g)) {
-            *(float4*)chunk(gP, off) = sAcc[0][r][h * 192 + j * 64 + lx];
-            *(float4*)chunk(gW, off) = sAcc[1][r][h * 192 + j * 64 + lx];
-        }
-    }
+    seg.store(&sAcc[0][r][h * 192], gP, lx);
+    seg.store(&sAcc[1][r][h * 192], gW, lx);
 }
 
 constexpr int pack_cfa(int c00, int c01, int c10, int c11) { return c00 | (c01 << 2) | (c10 << 4) | (c11 << 6); }
@@ -2224,17 +2039,12 @@ void launch_tile(dim3 grid, dim3 block, hipStream_t st, const TileFrames<NF>& fr
     const int tilesX = (int)grid.x, tilesY = (int)grid.y;
     // (a window: the XCD-aware order is taken over the window's tiles; the order does not change any pixel's bits)
     const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
-    // occupancy probe (A/B only): unused dynamic LDS so that fewer workgroups fit a CU
-    static const int ldsPad = [] {
-        const char* e = getenv("MFSR_TILE_LDS_PAD");
-        return e ? atoi(e) : 0;
-    }();
     const dim3 g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
     if (wl.on)
-        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR, true>), g1, block, ldsPad, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR, true>), g1, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
                            strideOut, strideMask, cfaPacked, tilesX, tilesY, tilesPerXcd, fresh, tileY0, wl.tileX0, wl.x0, wl.x1, wl.y0);
     else
-        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR>), g1, block, ldsPad, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
+        hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR>), g1, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
                            strideOut, strideMask, cfaPacked, tilesX, tilesY, tilesPerXcd, fresh, tileY0, 0, 0, 0, 0);
 }
 
@@ -2298,31 +2108,31 @@ int zero_margin_bands(mfsr_float3* imgOut, mfsr_float3* totalWeights, int hrH, i
     return 0;
 }
 
-// The margin kernel (one thread per pixel of the 16-pixel frame margin, the straight per-pixel arithmetic) is small and
-// latency-bound (5.6 K waves, 25 us per 4K frame) while the tile kernel saturates the VALUs: the two touch disjoint
-// accumulator bytes (the tile kernel does not write the side-margin chunks back), so the margin launches of a call run
-// on a side stream, forked after the tile launch's predecessors and joined before the call returns -- they fill the
-// tile kernel's stalls instead of adding 2 x 25 us per pair.  The first launch of a burst ("fresh": the tile kernel
-// defines the margins' zeroes) keeps the serial order.  MFSR_MARGIN_OVERLAP=0 restores it everywhere (A/B).
-int g_margin_overlap = 0;  // measured: no gain (8.79 vs 8.88 ms per burst, profiles/r02_ab_margin_overlap.txt): off by default
-struct MarginStream {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-};
-MarginStream* margin_stream()
+// number of margin pixels of a frame: the ring of STRIP_MARGIN HR pixels less the outermost one (the kernels' index space)
+long long margin_pixel_count(int hrW, int hrH)
 {
-    static thread_local MarginStream ms[16];  // per host thread: contexts on different threads never share the fork/join events
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    MarginStream& m = ms[dev];
-    if (m.device != dev) {
-        if (hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&m.fork, hipEventDisableTiming) != hipSuccess) return nullptr;
-        if (hipEventCreateWithFlags(&m.join, hipEventDisableTiming) != hipSuccess) return nullptr;
-        m.device = dev;
-    }
-    return &m;
+    const int M = STRIP_MARGIN;
+    return 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
+}
+
+// The margin kernels (one thread per pixel of the 16-pixel frame margin, the straight per-pixel arithmetic) are small and
+// latency-bound (5.6 K waves, 25 us per 4K frame).  They touch accumulator bytes the tile kernel does not (it does not write
+// the side-margin chunks back) and are launched on the caller's stream after it.  (Measured and not kept: a side stream,
+// forked before the tile launch and joined after the last margin launch -- 8.79 against 8.88 ms per burst, no gain,
+// profiles/r02_ab_margin_overlap.txt.)
+// the margin pixels of one frame: the whole ring, or the part of it inside a window
+template <int SCALE>
+void launch_margin_1(hipStream_t st, const uint16_t* raw, const mfsr_float4* mask, mfsr_tex2d shifts, pix3* pI, pix3* pT, mfsr_tex2d kp,
+                     Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cp, int rowBegin, int rowEnd,
+                     const WinLaunch& wl, const MarginRects& mr)
+{
+    if (!wl.on)
+        hipLaunchKernelGGL(k_accumulateMargin<SCALE>, dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 256)), dim3(256), 0,
+                           st, raw, pI, pT, (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd,
+                           mr);
+    else if (mr.start[4] > 0)
+        hipLaunchKernelGGL((k_accumulateMargin<SCALE, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, st, raw, pI, pT,
+                           (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
 }
 
 // the margin pixels of NF frames in one launch: the whole ring, or the part of it inside a window
@@ -2330,15 +2140,12 @@ template <int NF, int SCALE>
 void launch_margin_n(hipStream_t st, const TileFrames<NF>& fr, pix3* pI, pix3* pT, mfsr_tex2d kp, Levels3 glv, int dimX, int dimY,
                      int strideOut, int strideMask, int cp, int rowBegin, int rowEnd, const WinLaunch& wl, const MarginRects& mr)
 {
-    const int hrW = SCALE * dimX, hrH = SCALE * dimY, M = STRIP_MARGIN;
-    if (!wl.on) {
-        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, NF), 0, st, fr, pI, pT, kp, glv, dimX,
-                           dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
-    } else if (mr.start[4] > 0) {
+    if (!wl.on)
+        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE>), dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 64)),
+                           dim3(64, NF), 0, st, fr, pI, pT, kp, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    else if (mr.start[4] > 0)
         hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE, true>), dim3(mfsr_cdiv(mr.start[4], 64)), dim3(64, NF), 0, st, fr, pI, pT, kp,
                            glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
-    }
 }
 
 void read_env_once()
@@ -2348,11 +2155,52 @@ void read_env_once()
         if (e && e[0] >= '0' && e[0] <= '1') g_strip_use_tile = e[0] - '0';
         const char* x = getenv("MFSR_XCD_REMAP");
         if (x && (x[0] == '0' || x[0] == '1')) g_strip_xcd_remap = x[0] - '0';
-        const char* mo = getenv("MFSR_MARGIN_OVERLAP");
-        if (mo && (mo[0] == '0' || mo[0] == '1')) g_margin_overlap = mo[0] - '0';
         return true;
     }();
     (void)env_read;
+}
+
+// black / white levels in the two forms the kernels take
+void make_levels(mfsr_float3 white, mfsr_float3 black, Levels3& glv, StripLevels& lv)
+{
+    const float wl[3] = {white.x, white.y, white.z}, bl[3] = {black.x, black.y, black.z};
+    for (int c = 0; c < 3; c++) {
+        glv.white[c] = wl[c];
+        glv.black[c] = bl[c];
+        lv.black[c] = bl[c];
+        lv.invWhite[c] = 1.0f / wl[c];
+    }
+}
+
+// per-frame kernel arguments of the first n frames of a call
+void fill_frames(TileFrame* fr, const uint16_t* const* dataIn, const mfsr_float4* const* certaintyMask, const mfsr_tex2d* shifts, int n)
+{
+    for (int i = 0; i < n; i++) {
+        fr[i].raw = dataIn[i];
+        fr[i].mask = (const float4*)certaintyMask[i];
+        fr[i].shifts = shifts[i];
+    }
+}
+
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
+// f(int_c<CFA>{}) for the packed CFA pattern of the call: the four Bayer patterns and, with MONO, monochrome (a compile-time
+// switch: f is not instantiated for a pattern it does not serve).  Any other pattern: 0, "not the fast kernels'".
+template <bool MONO, class F>
+int for_cfa(int packed, F f)
+{
+    constexpr int R = MFSR_RED, G = MFSR_GREEN, B = MFSR_BLUE;
+    switch (packed) {
+        case pack_cfa(R, G, G, B): return f(int_c<pack_cfa(R, G, G, B)>{});  // RGGB
+        case pack_cfa(B, G, G, R): return f(int_c<pack_cfa(B, G, G, R)>{});  // BGGR
+        case pack_cfa(G, R, B, G): return f(int_c<pack_cfa(G, R, B, G)>{});  // GRBG
+        case pack_cfa(G, B, R, G): return f(int_c<pack_cfa(G, B, R, G)>{});  // GBRG
+        case pack_cfa(G, G, G, G):
+            if constexpr (MONO) return f(int_c<pack_cfa(G, G, G, G)>{});
+            return 0;
+        default: return 0;
+    }
 }
 
 }  // namespace
@@ -2381,13 +2229,7 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
     if (dimX < 2 * STRIP_MARGIN || dimY < 2 * STRIP_MARGIN) return 0;
     Levels3 glv;
     StripLevels lv;
-    const float wl[3] = {whiteLevel.x, whiteLevel.y, whiteLevel.z}, bl[3] = {blackLevel.x, blackLevel.y, blackLevel.z};
-    for (int c = 0; c < 3; c++) {
-        glv.white[c] = wl[c];
-        glv.black[c] = bl[c];
-        lv.black[c] = bl[c];
-        lv.invWhite[c] = 1.0f / wl[c];
-    }
+    make_levels(whiteLevel, blackLevel, glv, lv);
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     // HR row window [rowBegin, rowEnd): whole 4-row tile rows (the caller aligns it to 16 rows or the frame's end); columns
     // [colBegin, colEnd): the 256-pixel tile columns that meet them
@@ -2419,110 +2261,52 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
             if (zero_rows(imgOut, totalWeights, strideOut, rowBegin, rowEnd, wlc, st) != 0) return -1;
         }
     }
-    // margin launches: on the side stream (forked here, joined after the last one) when a tile kernel leads the call
-    MarginStream* msx = (g_margin_overlap && tileFirst && !tileFresh) ? margin_stream() : nullptr;
-    if (msx && (hipEventRecord(msx->fork, st) != hipSuccess || hipStreamWaitEvent(msx->stream, msx->fork, 0) != hipSuccess)) msx = nullptr;
-    const hipStream_t mst = msx ? msx->stream : st;
     auto launch_margin = [&](int n) {
-        const int M = STRIP_MARGIN;
-        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        if (!wlc.on)
-            hipLaunchKernelGGL(k_accumulateMargin<2>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                               rowBegin, rowEnd, mr);
-        else if (mr.start[4] > 0)  // only the part of the ring inside the window
-            hipLaunchKernelGGL((k_accumulateMargin<2, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                               rowBegin, rowEnd, mr);
-        if (msx && n == nFrames - 1) {
-            (void)hipEventRecord(msx->join, msx->stream);
-            (void)hipStreamWaitEvent(st, msx->join, 0);
-        }
+        launch_margin_1<2>(st, dataIn[n], certaintyMask[n], shifts[n], pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp,
+                           rowBegin, rowEnd, wlc, mr);
     };
-    // NF frames: the tile kernel, then their margin pixels in one launch
-    auto launch_group = [&](auto cfaTag, auto nfTag) {
-        constexpr int CFA = decltype(cfaTag)::value, NF = decltype(nfTag)::value;
+    // NF frames at field resolution FR: the tile kernel, then their margin pixels in one launch (one frame: the single-frame
+    // margin kernel)
+    auto launch_group = [&](auto cfaTag, auto nfTag, auto frTag) {
+        constexpr int CFA = decltype(cfaTag)::value, NF = decltype(nfTag)::value, FR = decltype(frTag)::value;
         TileFrames<NF> fr;
-        for (int n = 0; n < NF; n++) {
-            fr.f[n].raw = dataIn[n];
-            fr.f[n].mask = (const float4*)certaintyMask[n];
-            fr.f[n].shifts = shifts[n];
-        }
-        launch_tile<CFA, NF>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, tileFresh,
-                             rowBlock0, wlc);
-        launch_margin_n<NF, 2>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
-        if (msx) {
-            (void)hipEventRecord(msx->join, msx->stream);
-            (void)hipStreamWaitEvent(st, msx->join, 0);
-        }
+        fill_frames(fr.f, dataIn, certaintyMask, shifts, NF);
+        launch_tile<CFA, NF, FR>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, tileFresh,
+                                 rowBlock0, wlc);
+        if (NF == 1)
+            launch_margin(0);
+        else
+            launch_margin_n<NF, 2>(st, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
     };
     if (mono2) {
-        auto launch_mono = [&](auto nfTag) {
-            constexpr int NF = decltype(nfTag)::value;
-            TileFrames<NF> fr;
-            for (int n = 0; n < NF; n++) {
-                fr.f[n].raw = dataIn[n];
-                fr.f[n].mask = (const float4*)certaintyMask[n];
-                fr.f[n].shifts = shifts[n];
-            }
-            launch_tile<kMono, NF, 2>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, tileFresh,
-                                      rowBlock0, wlc);
-            if (NF == 1) {
-                launch_margin(0);
-                return;
-            }
-            launch_margin_n<NF, 2>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
-            if (msx) {
-                (void)hipEventRecord(msx->join, msx->stream);
-                (void)hipStreamWaitEvent(st, msx->join, 0);
-            }
-        };
-        if (nFrames == 1) launch_mono(std::integral_constant<int, 1>{});
-        if (nFrames == 2) launch_mono(std::integral_constant<int, 2>{});
+        if (nFrames == 1) launch_group(int_c<kMono>{}, int_c<1>{}, int_c<2>{});
+        if (nFrames == 2) launch_group(int_c<kMono>{}, int_c<2>{}, int_c<2>{});
         return 1;
     }
-#define STRIP_CASE(a, b, c, d)                                                                                         \
-    case pack_cfa(a, b, c, d):                                                                                         \
-        if (pair) {                                                                                                    \
-            using CfaTag = std::integral_constant<int, pack_cfa(a, b, c, d)>;                                          \
-            if (nFrames == 2) launch_group(CfaTag{}, std::integral_constant<int, 2>{});                                \
-            if (nFrames == 3) launch_group(CfaTag{}, std::integral_constant<int, 3>{});                                \
-            if (nFrames == 4) launch_group(CfaTag{}, std::integral_constant<int, 4>{});                                \
-        } else if (nFrames == 2) {                                                                                     \
-            TileFrames<2> fr;                                                                                          \
-            for (int n = 0; n < 2; n++) {                                                                              \
-                fr.f[n].raw = dataIn[n];                                                                               \
-                fr.f[n].mask = (const float4*)certaintyMask[n];                                                        \
-                fr.f[n].shifts = shifts[n];                                                                            \
-            }                                                                                                          \
-            launch_strip_regs<pack_cfa(a, b, c, d), 2>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,  \
-                                                       strideOut, strideMask, cp, rowBlock0, wlc);                                \
-            launch_margin(0);                                                                                          \
-            launch_margin(1);                                                                                          \
-        } else {                                                                                                       \
-            TileFrames<1> fr;                                                                                          \
-            fr.f[0].raw = dataIn[0];                                                                                   \
-            fr.f[0].mask = (const float4*)certaintyMask[0];                                                            \
-            fr.f[0].shifts = shifts[0];                                                                                \
-            if (tile_kernel_ok(kernelParam, shifts[0], dimX, dimY))                                                    \
-                launch_tile<pack_cfa(a, b, c, d), 1>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,    \
-                                                     strideOut, strideMask, cp, tileFresh, rowBlock0, wlc);                       \
-            else                                                                                                       \
-                launch_strip_regs<pack_cfa(a, b, c, d), 1>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX,    \
-                                                           dimY, strideOut, strideMask, cp, rowBlock0, wlc);                       \
-            launch_margin(0);                                                                                          \
-        }                                                                                                              \
+    return for_cfa<true>(packed2, [&](auto cfaTag) {
+        constexpr int CFA = decltype(cfaTag)::value;
+        if (pair) {
+            if (nFrames == 2) launch_group(cfaTag, int_c<2>{}, int_c<4>{});
+            if (nFrames == 3) launch_group(cfaTag, int_c<3>{}, int_c<4>{});
+            if (nFrames == 4) launch_group(cfaTag, int_c<4>{}, int_c<4>{});
+        } else if (nFrames == 2) {
+            TileFrames<2> fr;
+            fill_frames(fr.f, dataIn, certaintyMask, shifts, 2);
+            launch_strip_regs<CFA, 2>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, rowBlock0,
+                                      wlc);
+            launch_margin(0);
+            launch_margin(1);
+        } else if (tile_kernel_ok(kernelParam, shifts[0], dimX, dimY)) {
+            launch_group(cfaTag, int_c<1>{}, int_c<4>{});
+        } else {
+            TileFrames<1> fr;
+            fill_frames(fr.f, dataIn, certaintyMask, shifts, 1);
+            launch_strip_regs<CFA, 1>(grid, block, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut, strideMask, cp, rowBlock0,
+                                      wlc);
+            launch_margin(0);
+        }
         return 1;
-    switch (packed2) {
-        STRIP_CASE(MFSR_RED, MFSR_GREEN, MFSR_GREEN, MFSR_BLUE)   // RGGB
-        STRIP_CASE(MFSR_BLUE, MFSR_GREEN, MFSR_GREEN, MFSR_RED)   // BGGR
-        STRIP_CASE(MFSR_GREEN, MFSR_RED, MFSR_BLUE, MFSR_GREEN)   // GRBG
-        STRIP_CASE(MFSR_GREEN, MFSR_BLUE, MFSR_RED, MFSR_GREEN)   // GBRG
-        STRIP_CASE(MFSR_GREEN, MFSR_GREEN, MFSR_GREEN, MFSR_GREEN) // monochrome
-        default: break;
-    }
-#undef STRIP_CASE
-    return 0;
+    });
 }
 
 // The burst form: nFrames = 8, 12 or 16 frames (whole groups of four, Bayer, fields at HR/4, the whole frame) in ONE tile
@@ -2546,17 +2330,9 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
         if (!tile_kernel_ok(kernelParam, shifts[n], dimX, dimY)) return 0;
     Levels3 glv;
     StripLevels lv;
-    const float wl[3] = {whiteLevel.x, whiteLevel.y, whiteLevel.z}, bl[3] = {blackLevel.x, blackLevel.y, blackLevel.z};
-    for (int c = 0; c < 3; c++) {
-        glv.white[c] = wl[c];
-        glv.black[c] = bl[c];
-        lv.black[c] = bl[c];
-        lv.invWhite[c] = 1.0f / wl[c];
-    }
+    make_levels(whiteLevel, blackLevel, glv, lv);
     const int hrW = 2 * dimX, hrH = 2 * dimY;
-    const HrWindow whole{0, 0, hrW, hrH, 0};
-    const WinLaunch wlc = win_launch(whole, hrW, 256);
-    const MarginRects mr = margin_rects(hrW, hrH, STRIP_MARGIN, whole);
+    const WinLaunch wlc = win_launch(HrWindow{0, 0, hrW, hrH, 0}, hrW, 256);
     const int tilesX = wlc.tilesX, tilesY = mfsr_cdiv(hrH, 4);
     const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
     const dim3 block(64, 4), g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
@@ -2565,51 +2341,22 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     pix3* pT = (pix3*)totalWeights;
     const int cp = mfsr_cfa_packed();
     BurstFrames fr;
-    for (int n = 0; n < 4 * TILE_BURST_GROUPS; n++) {
-        const int m = n < nFrames ? n : 0;  // (unused entries: never read, nGroups bounds the loop)
-        fr.f[n].raw = dataIn[m];
-        fr.f[n].mask = (const float4*)certaintyMask[m];
-        fr.f[n].shifts = shifts[m];
-    }
-    auto launch = [&](auto cfaTag) {
+    fill_frames(fr.f, dataIn, certaintyMask, shifts, nFrames);
+    for (int n = nFrames; n < 4 * TILE_BURST_GROUPS; n++) fr.f[n] = fr.f[0];  // (never read: nGroups bounds the loop)
+    // monochrome and other patterns are not the burst kernel's: 0
+    const int rc = for_cfa<false>(packed2, [&](auto cfaTag) {
         constexpr int CFA = decltype(cfaTag)::value;
         // fresh accumulators: the tile kernel writes every row outside the top and bottom margin bands, which are zeroed here
         if (fresh && zero_margin_bands(imgOut, totalWeights, hrH, strideOut, 0, hrH, wlc, st) != 0) return -1;
         hipLaunchKernelGGL((k_accumulate2xTileBurst<CFA>), g1, block, 0, st, fr, nFrames / 4, pI, pT, kernelParam, glv, lv, dimX, dimY,
                            strideOut, strideMask, cp, tilesX, tilesY, tilesPerXcd, fresh ? 1 : 0);
         return 1;
-    };
-    // the margin pixels of all frames in one launch (MARGIN_BURST_LOOP = 0: one thread per (pixel, frame)), the frames' sums
-    // (each from zero) added to the accumulator value one after another in call order -- the order of the launches it replaces
-    auto margin = [&](auto nfTag) {
-        constexpr int NF = decltype(nfTag)::value;
-        TileFrames<NF> mf;
-        for (int n = 0; n < NF; n++) mf.f[n] = fr.f[n];
-        launch_margin_n<NF, 2>(st, mf, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, 0, hrH, wlc, mr);
-    };
-    int rc = 0;  // monochrome and other patterns: not the burst kernel's
-#define BURST_CASE(a, b, c, d)                                                      \
-    case pack_cfa(a, b, c, d):                                                      \
-        rc = launch(std::integral_constant<int, pack_cfa(a, b, c, d)>{});           \
-        break;
-    switch (packed2) {
-        BURST_CASE(MFSR_RED, MFSR_GREEN, MFSR_GREEN, MFSR_BLUE)  // RGGB
-        BURST_CASE(MFSR_BLUE, MFSR_GREEN, MFSR_GREEN, MFSR_RED)  // BGGR
-        BURST_CASE(MFSR_GREEN, MFSR_RED, MFSR_BLUE, MFSR_GREEN)  // GRBG
-        BURST_CASE(MFSR_GREEN, MFSR_BLUE, MFSR_RED, MFSR_GREEN)  // GBRG
-        default: break;
-    }
-#undef BURST_CASE
+    });
     if (rc != 1) return rc;
-    if (MARGIN_BURST_LOOP) {
-        const long long cnt = 2LL * (STRIP_MARGIN - 1) * (hrW - 2) + (long long)(hrH - 2 * STRIP_MARGIN) * 2 * (STRIP_MARGIN - 1);
-        hipLaunchKernelGGL((k_accumulateMarginBurst<2>), dim3(mfsr_cdiv(cnt, 64)), dim3(64, 4), 0, st, fr, nFrames / 4, pI, pT, kernelParam,
-                           glv, dimX, dimY, strideOut, strideMask, cp);
-        return 1;
-    }
-    if (nFrames == 8) margin(std::integral_constant<int, 8>{});
-    if (nFrames == 12) margin(std::integral_constant<int, 12>{});
-    if (nFrames == 16) margin(std::integral_constant<int, 16>{});
+    // the margin pixels of all frames in one launch, the frames' sums (each from zero) added to the accumulator value one after
+    // another in call order -- the order of the launches it replaces
+    hipLaunchKernelGGL((k_accumulateMarginBurst<2>), dim3(mfsr_cdiv(margin_pixel_count(hrW, hrH), 64)), dim3(64, 4), 0, st, fr,
+                       nFrames / 4, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp);
     return 1;
 }
 
@@ -2638,13 +2385,7 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
             return 0;
     Levels3 glv;
     StripLevels lv;
-    const float wl[3] = {whiteLevel.x, whiteLevel.y, whiteLevel.z}, bl[3] = {blackLevel.x, blackLevel.y, blackLevel.z};
-    for (int c = 0; c < 3; c++) {
-        glv.white[c] = wl[c];
-        glv.black[c] = bl[c];
-        lv.black[c] = bl[c];
-        lv.invWhite[c] = 1.0f / wl[c];
-    }
+    make_levels(whiteLevel, blackLevel, glv, lv);
     hipStream_t st = mfsr_s(stream);
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
@@ -2658,67 +2399,28 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
     if (fresh) {  // the top and bottom margin bands are the only rows the tile kernel does not write
         if (zero_margin_bands(imgOut, totalWeights, hrH, strideOut, rowBegin, rowEnd, wlc, st) != 0) return -1;
     }
-    MarginStream* msx = (g_margin_overlap && !fresh) ? margin_stream() : nullptr;
-    if (msx && (hipEventRecord(msx->fork, st) != hipSuccess || hipStreamWaitEvent(msx->stream, msx->fork, 0) != hipSuccess)) msx = nullptr;
-    const hipStream_t mst = msx ? msx->stream : st;
-    auto launch_margin = [&](int n) {
-        const int M = STRIP_MARGIN;
-        const long long cnt = 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
-        if (!wlc.on)
-            hipLaunchKernelGGL(k_accumulateMargin<4>, dim3(mfsr_cdiv(cnt, 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                               rowBegin, rowEnd, mr);
-        else if (mr.start[4] > 0)
-            hipLaunchKernelGGL((k_accumulateMargin<4, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, mst, dataIn[n], pI, pT,
-                               (const float4*)certaintyMask[n], kernelParam, shifts[n], glv, dimX, dimY, strideOut, strideMask, cp,
-                               rowBegin, rowEnd, mr);
-        if (msx && n == nFrames - 1) {
-            (void)hipEventRecord(msx->join, msx->stream);
-            (void)hipStreamWaitEvent(st, msx->join, 0);
-        }
-    };
     // NF frames: the tile kernel, then their margin pixels in one launch (one frame: the single-frame margin kernel)
     auto launch_group = [&](auto cfaTag, auto nfTag) {
         constexpr int CFA = decltype(cfaTag)::value, NF = decltype(nfTag)::value;
         TileFrames<NF> fr;
-        for (int n = 0; n < NF; n++) {
-            fr.f[n].raw = dataIn[n];
-            fr.f[n].mask = (const float4*)certaintyMask[n];
-            fr.f[n].shifts = shifts[n];
-        }
+        fill_frames(fr.f, dataIn, certaintyMask, shifts, NF);
         if (wlc.on)
             hipLaunchKernelGGL((k_accumulate4xTile<CFA, NF, true>), grid, block, 0, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY,
                                strideOut, strideMask, cp, tilesX, fresh ? 1 : 0, tileY0, wlc.tileX0, wlc.x0, wlc.x1, wlc.y0);
         else
             hipLaunchKernelGGL((k_accumulate4xTile<CFA, NF>), grid, block, 0, st, fr, pI, pT, kernelParam, glv, lv, dimX, dimY, strideOut,
                                strideMask, cp, tilesX, fresh ? 1 : 0, tileY0, 0, 0, 0, 0);
-        if (NF == 1) {
-            launch_margin(0);
-            return;
-        }
-        launch_margin_n<NF, 4>(mst, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
-        if (msx) {
-            (void)hipEventRecord(msx->join, msx->stream);
-            (void)hipStreamWaitEvent(st, msx->join, 0);
-        }
+        if (NF == 1)
+            launch_margin_1<4>(st, dataIn[0], certaintyMask[0], shifts[0], pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, wlc, mr);
+        else
+            launch_margin_n<NF, 4>(st, fr, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, wlc, mr);
     };
-#define X4_CASE(a, b, c, d)                                                                                            \
-    case pack_cfa(a, b, c, d): {                                                                                       \
-        using CfaTag = std::integral_constant<int, pack_cfa(a, b, c, d)>;                                              \
-        if (nFrames == 1) launch_group(CfaTag{}, std::integral_constant<int, 1>{});                                    \
-        if (nFrames == 2) launch_group(CfaTag{}, std::integral_constant<int, 2>{});                                    \
-        if (nFrames == 3) launch_group(CfaTag{}, std::integral_constant<int, 3>{});                                    \
-        if (nFrames == 4) launch_group(CfaTag{}, std::integral_constant<int, 4>{});                                    \
-        return 1;                                                                                                      \
-    }
-    switch (packed2) {
-        X4_CASE(MFSR_RED, MFSR_GREEN, MFSR_GREEN, MFSR_BLUE)   // RGGB
-        X4_CASE(MFSR_BLUE, MFSR_GREEN, MFSR_GREEN, MFSR_RED)   // BGGR
-        X4_CASE(MFSR_GREEN, MFSR_RED, MFSR_BLUE, MFSR_GREEN)   // GRBG
-        X4_CASE(MFSR_GREEN, MFSR_BLUE, MFSR_RED, MFSR_GREEN)   // GBRG
-        X4_CASE(MFSR_GREEN, MFSR_GREEN, MFSR_GREEN, MFSR_GREEN) // monochrome
-        default: break;
-    }
-#undef X4_CASE
-    return 0;
+    return for_cfa<true>(packed2, [&](auto cfaTag) {
+        if (nFrames == 1) launch_group(cfaTag, int_c<1>{});
+        if (nFrames == 2) launch_group(cfaTag, int_c<2>{});
+        if (nFrames == 3) launch_group(cfaTag, int_c<3>{});
+        if (nFrames == 4) launch_group(cfaTag, int_c<4>{});
+        return 1;
+    });
 }

@@ -1,5 +1,5 @@
 """The warp+fuse tile kernel's LDS certainty layout, raw-site addressing and fast-path admission (accumulate_fast.hip:
-TILE_CERT_PLANES, TILE_RAW_LANE32, TILE_ALIAS_IMPLIED) against the oracle's frame-by-frame accumulateSuperResFull.
+certainty as one plane per CFA position, raw sites at 32-bit lane offsets, the 16-bit range test implied by the 8-bit window) against the oracle's frame-by-frame accumulateSuperResFull.
 
 Every case goes through mfsr_accumulateSuperResFullN on guarded buffers at the ragged shape of
 test_accumulate_groups_of_three_and_four (328 x 104: the last 256-pixel tile is partial, the rows are no multiple of 16), with
