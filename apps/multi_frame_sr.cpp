@@ -34,6 +34,9 @@
 //     DESIGN.md section 2.16; 2 = the 5x5 minimum); works with MFSR_GPUS > 1.
 //   * MFSR_SHARPEN="amount[,sigma[,radius[,threshold]]]" sharpens _sr_result inside the finish (an unsharp mask on the linear
 //     value), with or without MFSR_CCM; one GPU only.
+//   * MFSR_AUTO=wb|tone|wb,tone measures white-balance gains and / or a tone table on the merged image and renders _sr_result
+//     with them, with or without MFSR_CCM and MFSR_SHARPEN; it prints `auto: gains R G B ... black K
+//     white W gamma G ...` to stderr; one GPU only.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -353,7 +356,37 @@ int main(int argc, char** argv)
         sharpenOn = true;
         render.format = MFSR_OUT_RGB8;
     }
-    const bool rendered = ccm || sharpenOn;  // the 8-bit image comes out of the finish launch
+    // MFSR_AUTO=wb|tone|wb,tone: white-balance gains and / or a tone table measured on the merged image itself
+    // (mfsr_burst_auto_render) go into the render description of the finish; with MFSR_CCM the gains
+    // multiply that matrix, with MFSR_SHARPEN the measurement is taken before sharpening.  The 8-bit image then comes out of the
+    // rendered finish, as with MFSR_CCM.
+    bool autoWb = false, autoTone = false;
+    if (const char* e = getenv("MFSR_AUTO")) {
+        bool ok = *e != '\0';
+        for (const char* p = e; ok && *p;) {
+            const char* end = strchr(p, ',');
+            const size_t n = end ? (size_t)(end - p) : strlen(p);
+            if (n == 2 && strncmp(p, "wb", 2) == 0)
+                autoWb = true;
+            else if (n == 4 && strncmp(p, "tone", 4) == 0)
+                autoTone = true;
+            else
+                ok = false;
+            p += n;
+            if (*p == ',') ok = ok && *++p != '\0';
+        }
+        if (!ok) {
+            fprintf(stderr, "MFSR_AUTO=%s: wb, tone or wb,tone expected\n", e);
+            return 1;
+        }
+        render.format = MFSR_OUT_RGB8;
+    }
+    const bool autoOn = autoWb || autoTone;
+    const bool rendered = ccm || sharpenOn || autoOn;  // the 8-bit image comes out of the finish launch
+    if (autoOn && gpus > 1) {
+        fprintf(stderr, "MFSR_AUTO is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
     if (sharpenOn && gpus > 1) {
         fprintf(stderr, "MFSR_SHARPEN is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
@@ -587,6 +620,19 @@ int main(int argc, char** argv)
     HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
     if (rendered) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
     if (sharpenOn) MFSR_OK_OR_DIE(mfsr_burst_set_sharpen(b, &sharpen));
+    // MFSR_AUTO: the table of the statistics and the tone table the measurement writes (device memory of the caller's)
+    uint64_t* dstats = nullptr;
+    float* dlut = nullptr;
+    mfsr_auto_params autoParams;
+    mfsr_auto_result autoResult;
+    memset(&autoResult, 0, sizeof(autoResult));
+    if (autoOn) {
+        MFSR_OK_OR_DIE(mfsr_auto_defaults((long long)hrW * hrH, &autoParams));
+        autoParams.awb = autoWb;
+        autoParams.tone = autoTone;
+        HIP_OK(hipMalloc((void**)&dstats, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS));
+        HIP_OK(hipMalloc((void**)&dlut, sizeof(float) * ((size_t)autoParams.toneSize + 1)));
+    }
     for (int rep = 0; rep < num_times; rep++) {
         if (rep == start_i) {
             HIP_OK(hipDeviceSynchronize());
@@ -598,6 +644,11 @@ int main(int argc, char** argv)
         for (int k : ids)
             MFSR_OK_OR_DIE(mfsr_burst_add_frame(b, dframes[k], k == reference, (mfsr_float3*)imgOut,
                                                 (mfsr_float3*)weights, nullptr));
+        if (autoOn) {  // measured on this burst's accumulators; the description it installs is the one the finish below uses
+            mfsr_render measured = render;
+            MFSR_OK_OR_DIE(mfsr_burst_auto_render(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, &autoParams, dstats, dlut,
+                                                  &measured, &autoResult, nullptr));
+        }
         if (rendered)  // (sharpening +) matrix + gamma + 8-bit store in the finish launch: the float image is neither written nor
                        // read again
             MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights,
@@ -610,6 +661,10 @@ int main(int argc, char** argv)
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%g sec\n", sec);                                               // :205
     printf("%g FPS\n", (double)(num_images * real_times) / sec);           // :206
+    if (autoOn)
+        fprintf(stderr, "auto: gains %g %g %g (status %d, neutral share %g) black %g white %g gamma %g (status %d)\n",
+                autoResult.gains[0], autoResult.gains[1], autoResult.gains[2], autoResult.awbStatus, autoResult.neutralShare,
+                autoResult.black, autoResult.white, autoResult.gamma, autoResult.toneStatus);
 
     // result -> 8-bit RGB (D2H), then sharpenImg2 on the device
     if (!rendered) MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));

@@ -1277,6 +1277,106 @@ int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharpen);
  * not an mfsr_path: those count branches that a configuration (mfsr_config) chooses, this one follows a setter. */
 int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes);
 
+/* ---- image statistics, auto white balance, auto tone.  The measurement the render description
+ * lacks: an exact-integer statistics stage on the device, two small fits on the host, and a burst driver that fills and
+ * installs the mfsr_render of the finish.  Nothing here runs unless it is called.
+ * THE STATISTIC.  For an HR pixel, p is the value of the rendered output's rule (after ApplyWeighting, with the fallback, before
+ * gamma) and q is p after its step 1: the matrix (useMatrix != 0; same clamp, same order of operations), else q = p.
+ *   codes    c_k = (int)(clamp(q_k, 0, 1) * 4095.0f + 0.5f), NaN -> 0                         (k = 0, 1, 2; 0 .. 4095)
+ *   luma key y = (54 c_0 + 183 c_1 + 19 c_2 + 128) >> 8;   peak key m = max(c_0, c_1, c_2)     (both 0 .. 4095)
+ *   neutral  lo <= min(c) and max(c) <= hi and, if chromaTol > 0, 256 |c_0 - c_1| <= chromaTol c_1 and
+ *            256 |c_2 - c_1| <= chromaTol c_1
+ * One table of MFSR_IMAGE_STATS_WORDS uint64_t: [0] pixels measured, [1] neutral pixels, [2..4] sums of c_0, c_1, c_2 over the
+ * neutral set, [5..7] the same sums over all pixels, [8 .. 8+4096) the histogram of y, [8+4096 .. 8+8192) the histogram of m.
+ * A launch ADDS to the table (device memory, 8-byte aligned; the caller zeroes it first), so stripes, windows and bands of an
+ * image add up to the whole image's table exactly; integers, so nothing depends on the order of arrival or the launch shape.
+ * mfsr_imageStats measures an existing float image (q from p = the image's value); mfsr_finishStats measures the accumulators
+ * of a burst: its arguments are those of mfsr_finishRendered without the outputs and the render description, and it evaluates
+ * the same float expressions (one definition), so what is measured is what the finish renders.  0 <= lo <= hi <= 4095,
+ * 0 <= chromaTol <= 65536, a matrix in use finite with |m| <= 256, reserved zero-filled, w, h > 0 with w * h < 2^31, row bytes
+ * >= 12 w and a multiple of 4: every argument is checked on the host before any device call (MFSR_E_INVALID).  Asynchronous on
+ * `stream`, nothing is allocated: capturable. */
+#define MFSR_IMAGE_STATS_BINS 4096
+#define MFSR_IMAGE_STATS_WORDS (8 + 2 * MFSR_IMAGE_STATS_BINS)
+typedef struct {
+    int32_t useMatrix;   /* 0: matrix[] is ignored */
+    float matrix[9];     /* row-major 3x3, as mfsr_render.matrix */
+    int32_t lo, hi;      /* the neutral set: codes */
+    int32_t chromaTol;   /* ... and its chroma bound in 1/256 of the green code; 0 = none */
+    int32_t reserved[3]; /* zeros */
+} mfsr_image_stats_params;
+int mfsr_imageStats(const mfsr_float3* in, int inRowBytes, int w, int h, const mfsr_image_stats_params* params,
+                    uint64_t* statsDev, mfsr_stream_t stream);
+int mfsr_finishStats(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                     int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, int w, int h, float threshold,
+                     int colOffset, int rowOffset, int fullWidth, int fullHeight, const mfsr_image_stats_params* params,
+                     uint64_t* statsDev, mfsr_stream_t stream);
+/* THE FITS (host only, no device call, double precision; the table as a HOST array).
+ * mfsr_awb_gains: grey-world gains over the neutral set, S_k = stats[2 + k]: g_0 = S_1 / S_0, g_1 = 1, g_2 = S_1 / S_2, each
+ * rounded to float.  *status: 0 ok; 1 unmeasurable (stats[1] < minCount, or a sum is 0: the gains are 1, 1, 1); 2 a gain was
+ * clamped to [1/8, 8].
+ * mfsr_tone_fit: black point, white point and a mid-tone gamma from the two histograms, and the tone table of them.  N =
+ * stats[0] > 0; tLo = (uint64)(pLo N); tHi = (uint64)((1 - pHi) N); cumY / cumM = the running sums of the two histograms;
+ *   kLo = the smallest k with cumY(k) > tLo;  kHi = the smallest k with cumM(k) >= N - tHi;  kMed = the smallest k with
+ *   cumY(k) >= (N + 1) / 2 (integer division); each 4095 when the table never gets there;
+ *   b = kLo / 4095;  span = max(kHi / 4095 - b, 1 / maxGain) (*status 1 when the floor was taken, else 0);
+ *   u(v) = clamp((v - b) / span, 0, 1);  um = u(kMed / 4095);
+ *   gamma = 1 if mid <= 0 or um is not inside (0, 1), else clamp(log(mid) / log(um), 0.5, 2);
+ *   lut[k] = (float)sRGB(u(k / toneSize)^gamma), k = 0 .. toneSize, with sRGB(v) = v <= 0.0031308 ? 12.92 v :
+ *   1.055 v^(1/2.4) - 0.055: toneSize + 1 floats for mfsr_render.toneLut once copied to the device.
+ * *black = b, *white = b + span, *gamma; lutHost and the three may be NULL.  0 <= pLo, pHi <= 1, 1 <= maxGain <= 65536,
+ * mid < 1, 1 <= toneSize <= 65536 (MFSR_E_INVALID otherwise).
+ * mfsr_auto_defaults: awb = tone = 1, lo = 64, hi = 3967, chromaTol = 64, iterations = 2, minCount = pixels / 64, pLo = 0.001,
+ * pHi = 0.999, maxGain = 8, mid = 0.18, toneSize = 4096. */
+typedef struct {
+    double pLo, pHi;  /* the shares of the pixels below the black point and up to the white point */
+    double maxGain;   /* the span is at least 1 / maxGain */
+    double mid;       /* where the median luma should land after the stretch; <= 0: no gamma */
+} mfsr_tone_params;
+typedef struct {
+    int32_t awb, tone;          /* which of the two measurements run */
+    int32_t lo, hi, chromaTol;  /* the neutral set (chromaTol: from the second pass on) */
+    int32_t iterations;         /* white-balance passes, 1 .. 4 */
+    long long minCount;         /* neutral pixels a pass needs; <= 0: 1/64 of the pixels measured */
+    mfsr_tone_params toneParams;
+    int32_t toneSize;           /* intervals of the table mfsr_burst_auto_render writes, 1 .. 65536 */
+    int32_t reserved[3];        /* zeros */
+} mfsr_auto_params;
+typedef struct {
+    float gains[3];          /* the white-balance gains in the installed matrix (1, 1, 1 without awb or when unmeasurable) */
+    int32_t awbStatus;       /* 0 ok (or off); 1 the first pass was unmeasurable; 2 a gain was clamped to [1/8, 8] */
+    int32_t awbPasses;       /* passes that changed the gains */
+    int32_t toneStatus;      /* as mfsr_tone_fit (0 when off) */
+    int32_t reserved;
+    double black, white, gamma; /* as mfsr_tone_fit (0, 1, 1 when off) */
+    double neutralShare;     /* stats[1] / stats[0] of the last white-balance pass (0 when off) */
+} mfsr_auto_result;
+int mfsr_awb_gains(const uint64_t* statsHost, long long minCount, float gains[3], int32_t* status);
+int mfsr_tone_fit(const uint64_t* statsHost, const mfsr_tone_params* tone, int toneSize, float* lutHost, double* black,
+                  double* white, double* gamma, int32_t* status);
+int mfsr_auto_defaults(long long pixels, mfsr_auto_params* ap);
+/* THE BURST DRIVER.  After the last mfsr_burst_add_frame and before mfsr_burst_finish: measures the burst's accumulators (the
+ * output, or the zoom window when one is set; whatever cfg.fused is) with mfsr_finishStats and the arguments the finish itself
+ * uses, and fills and installs the render description the finish then consumes.
+ *   1. the frames still waiting are fused (as mfsr_burst_flush);
+ *   2. ap->awb: pass 1 measures without a matrix and with chromaTol = 0 and takes g = mfsr_awb_gains; every further pass, up
+ *      to ap->iterations in all, measures with the matrix diag(g) and ap->chromaTol and multiplies g by its gains,
+ *      g_k = (float)((double)g_k * c_k), clamped to [1/8, 8]; a pass of status 1 leaves g as it is.  Else g = 1, 1, 1;
+ *   3. M = render->matrix * diag(g) (render->useMatrix != 0), entry (float)((double)matrix[3i+j] * g_j), or diag(g) (awb
+ *      without a matrix); |m| > 256 is refused (MFSR_E_INVALID).  Without awb the caller's matrix (or none) stays as given;
+ *   4. ap->tone: one measurement with M, mfsr_tone_fit, and the table is copied to lutDev (ap->toneSize + 1 floats of device
+ *      memory, 4-byte aligned, the caller's: it must stay valid as mfsr_render.toneLut must).  Else render->toneLut / toneSize
+ *      stay as given;
+ *   5. *render (in: format, the optional matrix and table, reserved; out: as installed) is installed exactly as
+ *      mfsr_burst_set_render would install it (same checks), and *res reports the outcome.
+ * statsDev: MFSR_IMAGE_STATS_WORDS uint64_t of device memory, 8-byte aligned.  ap NULL = mfsr_auto_defaults.  The driver waits
+ * for the stream after every measurement (the fits run on the host): it is not capturable, like mfsr_burst_calibrate_noise; the
+ * host staging is the burst's own.  The description stays installed for the following bursts until mfsr_burst_set_render
+ * replaces it or turns it off.  Not for host-memory bursts (mfsr_burst_finish_host, mfsr_burst_process_source: their bands
+ * finish before the accumulators are complete), frame streams, the joint mode or the multi-GPU layer. */
+int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_auto_params* ap,
+                           uint64_t* statsDev, float* lutDev, mfsr_render* render, mfsr_auto_result* res, mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

@@ -138,10 +138,44 @@ class Sharpen(ctypes.Structure):
                 ("threshold", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
 
 
+# image statistics, auto white balance and auto tone (include/mfsr.h)
+IMAGE_STATS_BINS = 4096
+IMAGE_STATS_WORDS = 8 + 2 * IMAGE_STATS_BINS
+
+
+class ImageStatsParams(ctypes.Structure):
+    """mfsr_image_stats_params: what mfsr_imageStats / mfsr_finishStats measure."""
+
+    _fields_ = [("useMatrix", ctypes.c_int32), ("matrix", ctypes.c_float * 9), ("lo", ctypes.c_int32), ("hi", ctypes.c_int32),
+                ("chromaTol", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class ToneParams(ctypes.Structure):
+    """mfsr_tone_params: the percentiles, the gain bound and the mid-tone target of mfsr_tone_fit."""
+
+    _fields_ = [("pLo", ctypes.c_double), ("pHi", ctypes.c_double), ("maxGain", ctypes.c_double), ("mid", ctypes.c_double)]
+
+
+class AutoParams(ctypes.Structure):
+    """mfsr_auto_params: what mfsr_burst_auto_render measures and fits (mfsr_auto_defaults fills one)."""
+
+    _fields_ = [("awb", ctypes.c_int32), ("tone", ctypes.c_int32), ("lo", ctypes.c_int32), ("hi", ctypes.c_int32),
+                ("chromaTol", ctypes.c_int32), ("iterations", ctypes.c_int32), ("minCount", ctypes.c_longlong),
+                ("toneParams", ToneParams), ("toneSize", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class AutoResult(ctypes.Structure):
+    """mfsr_auto_result: the outcome of mfsr_burst_auto_render."""
+
+    _fields_ = [("gains", ctypes.c_float * 3), ("awbStatus", ctypes.c_int32), ("awbPasses", ctypes.c_int32),
+                ("toneStatus", ctypes.c_int32), ("reserved", ctypes.c_int32), ("black", ctypes.c_double),
+                ("white", ctypes.c_double), ("gamma", ctypes.c_double), ("neutralShare", ctypes.c_double)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
-    "mfsr_stream_t": ctypes.c_void_p, "long long": ctypes.c_longlong,
+    "mfsr_stream_t": ctypes.c_void_p, "long long": ctypes.c_longlong, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double,
 }
 _RET = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p, "long long": ctypes.c_longlong,
         "mfsr_burst*": ctypes.c_void_p, "mfsr_dist*": ctypes.c_void_p}

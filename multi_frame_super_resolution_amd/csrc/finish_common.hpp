@@ -1,6 +1,7 @@
 // finish_common.hpp -- the pixel arithmetic of the burst's finish (stage H), shared by glue.hip (k_finishFused, k_quantize,
-// k_resampleFloat3) and render.hip (k_finishRendered, k_renderImage): one definition, so that the rendered finish holds the
-// same value as the plain one before its gamma, and quantises by the same rule.
+// k_resampleFloat3), render.hip (k_finishRendered, k_renderImage) and image_stats.hip (k_imageStats): one definition, so that
+// the rendered finish holds the same value as the plain one before its gamma, quantises by the same rule, and is measured as
+// it is rendered.
 #pragma once
 
 #include "common.hpp"
@@ -35,6 +36,33 @@ __device__ __forceinline__ float apply_weight_f(float inout, float val, float w,
     }
     inout = 0;
     if (w != 0) inout = val / w;
+    return inout;
+}
+
+// Where the fallback of a finish launch lies and which pixel of the whole image the launch's pixel (0, 0) is: the arguments of
+// mfsr_finishRendered that its pixel value depends on.
+struct FinishSrc {
+    const pix3* fallback;  // or null
+    int fbPitch, fbW, fbH;
+    float u0, u1, v0, v1;
+    float threshold;
+    int rowOffset, fullHeight, colOffset, fullWidth;
+};
+
+// The value section 2.19 calls p at pixel (x, y) of the launch: the body of k_finishFused up to its gamma, expression for
+// expression (a stripe or window is the crop of the whole).  val / w: the accumulator and the weight of the pixel.  One
+// definition for k_finishRendered (render.hip) and k_imageStats (image_stats.hip): what is measured is what is rendered.
+__device__ __forceinline__ pix3 finish_value(pix3 val, pix3 w, int x, int y, const FinishSrc& f)
+{
+    pix3 inout = {0.0f, 0.0f, 0.0f};
+    if (f.fallback && (w.x < f.threshold || w.y < f.threshold || w.z < f.threshold)) {
+        const float u = f.u0 + (f.u1 - f.u0) * (((float)(x + f.colOffset) + 0.5f) / (float)f.fullWidth);
+        const float v = f.v0 + (f.v1 - f.v0) * (((float)(y + f.rowOffset) + 0.5f) / (float)f.fullHeight);
+        inout = sample_pix3(f.fallback, f.fbPitch, f.fbW, f.fbH, u, v);
+    }
+    inout.x = apply_weight_f(inout.x, val.x, w.x, f.threshold);
+    inout.y = apply_weight_f(inout.y, val.y, w.y, f.threshold);
+    inout.z = apply_weight_f(inout.z, val.z, w.z, f.threshold);
     return inout;
 }
 

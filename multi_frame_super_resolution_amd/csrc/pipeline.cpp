@@ -370,6 +370,9 @@ struct mfsr_burst {
     bool sharpenOn;
     mfsr_sharpen sharpen;
     int sharpenedFinishes;  // launches of mfsr_finishSharpened since mfsr_burst_begin (mfsr_burst_debug_sharpened)
+    // host staging of mfsr_burst_auto_render: the downloaded table and the tone table on its way to the device
+    std::vector<uint64_t> autoStats;
+    std::vector<float> autoLut;
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -2110,6 +2113,112 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
     MFSR_REQUIRE(!(b->sharpenOn && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen: whichever comes second)
     b->render = *render;
     b->renderOn = true;
+    return MFSR_OK;
+}
+
+// ---- auto white balance and auto tone: the accumulators measured with the finish's own arguments
+//      (csrc/image_stats.hip), the fits on the host, the result installed as the burst's render description ---------------------
+// one measurement of the burst's output (or window) into the zeroed table, downloaded into b->autoStats; waits for the stream
+static int auto_measure(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_image_stats_params* p,
+                        uint64_t* statsDev, mfsr_stream_t stream)
+{
+    const Layout& L = b->L;
+    const int oW = out_w(b), pitch = 12 * oW;
+    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    MFSR_HIP_TRY(hipMemsetAsync(statsDev, 0, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS, mfsr_s(stream)));
+    TRY(mfsr_finishStats(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f,
+                         0.0f, 1.0f, oW, out_h(b), b->cfg.weightThreshold, x0, y0, L.hrW, L.hrH, p, statsDev, stream));
+    b->autoStats.resize(MFSR_IMAGE_STATS_WORDS);
+    MFSR_HIP_TRY(hipMemcpyAsync(b->autoStats.data(), statsDev, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS, hipMemcpyDeviceToHost,
+                                mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights,
+                                      const mfsr_auto_params* apIn, uint64_t* statsDev, float* lutDev, mfsr_render* render,
+                                      mfsr_auto_result* res, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && imgOut && totalWeights && statsDev && render && res);
+    MFSR_REQUIRE(b->haveRef && ((uintptr_t)statsDev & 7) == 0);
+    MFSR_REQUIRE(!b->cfg.uploadRing);  // a host burst finishes band by band, before its accumulators are complete
+    const long long pixels = (long long)out_w(b) * out_h(b);
+    mfsr_auto_params ap;
+    if (apIn)
+        ap = *apIn;
+    else
+        TRY(mfsr_auto_defaults(pixels, &ap));
+    MFSR_REQUIRE(ap.iterations >= 1 && ap.iterations <= 4 && ap.toneSize >= 1 && ap.toneSize <= 65536);
+    MFSR_REQUIRE(0 <= ap.lo && ap.lo <= ap.hi && ap.hi <= MFSR_IMAGE_STATS_BINS - 1 && 0 <= ap.chromaTol && ap.chromaTol <= 65536);
+    MFSR_REQUIRE(ap.reserved[0] == 0 && ap.reserved[1] == 0 && ap.reserved[2] == 0);
+    if (ap.tone) MFSR_REQUIRE(lutDev != nullptr && ((uintptr_t)lutDev & 3) == 0);
+    TRY(mfsr_render_validate(render));  // (before any work: the format, the caller's matrix and table)
+    TRY(flush_pending(b, stream));
+    const long long minCount = ap.minCount > 0 ? ap.minCount : pixels / 64;
+
+    mfsr_auto_result out;
+    memset(&out, 0, sizeof(out));
+    out.gains[0] = out.gains[1] = out.gains[2] = 1.0f;
+    out.white = out.gamma = 1.0;
+    mfsr_image_stats_params sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.lo = ap.lo;
+    sp.hi = ap.hi;
+    if (ap.awb) {
+        float g[3] = {1.0f, 1.0f, 1.0f};
+        for (int pass = 0; pass < ap.iterations; pass++) {
+            sp.useMatrix = pass > 0;
+            sp.chromaTol = pass > 0 ? ap.chromaTol : 0;
+            for (int k = 0; k < 3; k++) sp.matrix[4 * k] = g[k];
+            TRY(auto_measure(b, imgOut, totalWeights, &sp, statsDev, stream));
+            const uint64_t* t = b->autoStats.data();
+            out.neutralShare = t[0] ? (double)t[1] / (double)t[0] : 0.0;
+            float c[3];
+            int32_t st = 0;
+            TRY(mfsr_awb_gains(t, minCount, c, &st));
+            if (st == 1) {
+                if (pass == 0) out.awbStatus = 1;
+                continue;  // (this pass leaves g as it is)
+            }
+            if (st == 2 && out.awbStatus == 0) out.awbStatus = 2;
+            for (int k = 0; k < 3; k++) {
+                double v = (double)g[k] * (double)c[k];
+                if (v < 0.125 || v > 8.0) {
+                    v = v < 0.125 ? 0.125 : 8.0;
+                    if (out.awbStatus == 0) out.awbStatus = 2;
+                }
+                g[k] = (float)v;
+            }
+            out.awbPasses++;
+        }
+        for (int k = 0; k < 3; k++) out.gains[k] = g[k];
+        float m[9];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const double ccm = render->useMatrix ? (double)render->matrix[3 * i + j] : (i == j ? 1.0 : 0.0);
+                m[3 * i + j] = (float)(ccm * (double)g[j]);
+                MFSR_REQUIRE(fabsf(m[3 * i + j]) <= 256.0f);
+            }
+        memcpy(render->matrix, m, sizeof(m));
+        render->useMatrix = 1;
+    }
+    if (ap.tone) {
+        memset(&sp, 0, sizeof(sp));
+        sp.lo = ap.lo;
+        sp.hi = ap.hi;
+        sp.useMatrix = render->useMatrix != 0;
+        memcpy(sp.matrix, render->matrix, sizeof(sp.matrix));
+        TRY(auto_measure(b, imgOut, totalWeights, &sp, statsDev, stream));
+        b->autoLut.resize((size_t)ap.toneSize + 1);
+        TRY(mfsr_tone_fit(b->autoStats.data(), &ap.toneParams, ap.toneSize, b->autoLut.data(), &out.black, &out.white, &out.gamma,
+                          &out.toneStatus));
+        MFSR_HIP_TRY(hipMemcpyAsync(lutDev, b->autoLut.data(), sizeof(float) * b->autoLut.size(), hipMemcpyHostToDevice, mfsr_s(stream)));
+        MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));  // (the staging may be written again by the next call)
+        render->toneLut = lutDev;
+        render->toneSize = ap.toneSize;
+    }
+    TRY(mfsr_burst_set_render(b, render));  // (after the flush its own guard holds)
+    *res = out;
     return MFSR_OK;
 }
 

@@ -37,21 +37,9 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
     if (x0 >= width || y >= height) return;
     const pix3* valRow = row_ptr(finalImg, imgPitch, y);
     const pix3* wRow = row_ptr(weight, imgPitch, y);
-    // the body of k_finishFused up to its gamma, expression for expression (a stripe or window is the crop of the whole)
-    auto src = [&](int x) {
-        const pix3 val = valRow[x];
-        const pix3 w = wRow[x];
-        pix3 inout = {0.0f, 0.0f, 0.0f};
-        if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
-            const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
-            const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
-            inout = sample_pix3(fallback, fbPitch, fbW, fbH, u, v);
-        }
-        inout.x = apply_weight_f(inout.x, val.x, w.x, threshold);
-        inout.y = apply_weight_f(inout.y, val.y, w.y, threshold);
-        inout.z = apply_weight_f(inout.z, val.z, w.z, threshold);
-        return inout;
-    };
+    // the body of k_finishFused up to its gamma (finish_value, finish_common.hpp: shared with the statistics of section 2.23)
+    const FinishSrc f = {fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset, fullWidth};
+    auto src = [&](int x) { return finish_value(valRow[x], wRow[x], x, y, f); };
     render_span<FORMAT>(src, outImg ? row_ptr(outImg, outPitch, y) : nullptr, out ? out + (size_t)outRowBytes * (size_t)y : nullptr,
                         x0, width, r, lut);
 }

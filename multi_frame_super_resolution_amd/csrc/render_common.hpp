@@ -38,16 +38,22 @@ __device__ __forceinline__ float tone1(float q, const RenderArgs& r, const float
 
 __device__ __forceinline__ float matrix_in(float p) { return isnan(p) ? 0.0f : fminf(fmaxf(p, 0.0f), 65536.0f); }
 
+// step 1 of section 2.19 with a matrix (also what the statistics of section 2.23 measure: image_stats.hip)
+__device__ __forceinline__ pix3 matrix_pixel(pix3 p, const float* m)
+{
+    const float c0 = matrix_in(p.x), c1 = matrix_in(p.y), c2 = matrix_in(p.z);
+    pix3 q;
+    q.x = (m[0] * c0 + m[1] * c1) + m[2] * c2;
+    q.y = (m[3] * c0 + m[4] * c1) + m[5] * c2;
+    q.z = (m[6] * c0 + m[7] * c1) + m[8] * c2;
+    return q;
+}
+
 // steps 1 and 2 of section 2.19: the float value the image holds and the integer output quantises
 __device__ __forceinline__ pix3 render_pixel(pix3 p, const RenderArgs& r, const float* lut)
 {
     pix3 q = p;
-    if (r.useMatrix) {  // uniform
-        const float c0 = matrix_in(p.x), c1 = matrix_in(p.y), c2 = matrix_in(p.z);
-        q.x = (r.m[0] * c0 + r.m[1] * c1) + r.m[2] * c2;
-        q.y = (r.m[3] * c0 + r.m[4] * c1) + r.m[5] * c2;
-        q.z = (r.m[6] * c0 + r.m[7] * c1) + r.m[8] * c2;
-    }
+    if (r.useMatrix) q = matrix_pixel(p, r.m);  // uniform
     pix3 o;
     o.x = tone1(q.x, r, lut);
     o.y = tone1(q.y, r, lut);

@@ -760,6 +760,81 @@ def sharpen_image(img: torch.Tensor, amount: float = 1.0, sigma: float = 1.0, ra
     return (out, fl) if want_float else out
 
 
+# ---- image statistics, auto white balance, auto tone (include/mfsr.h, mfsr_imageStats) ---------------
+ToneFit = namedtuple("ToneFit", "lut black white gamma status")
+
+
+def auto_defaults(pixels: int = 0) -> capi.AutoParams:
+    """The defaults of auto white balance and auto tone (mfsr_auto_defaults; host only): neutral set lo 64, hi 3967, chromaTol
+    64, 2 passes, minCount = pixels / 64 (0: decided from the pixels measured), pLo 0.001, pHi 0.999, maxGain 8, mid 0.18, a
+    table of 4096 intervals."""
+    ap = capi.AutoParams()
+    capi.lib().auto_defaults(int(pixels), ctypes.byref(ap))
+    return ap
+
+
+def _stats_params(matrix, lo, hi, chroma_tol) -> capi.ImageStatsParams:
+    p = capi.ImageStatsParams()
+    p.lo, p.hi, p.chromaTol = int(lo), int(hi), int(chroma_tol)
+    if matrix is not None:
+        m = [float(v) for v in torch.as_tensor(matrix, dtype=torch.float64).reshape(-1).tolist()]
+        if len(m) != 9:
+            raise ValueError("matrix: 3 x 3 coefficients, row-major")
+        p.useMatrix = 1
+        p.matrix = (ctypes.c_float * 9)(*m)
+    return p
+
+
+def image_stats(img: torch.Tensor, matrix=None, lo: int = 64, hi: int = 3967, chroma_tol: int = 0) -> torch.Tensor:
+    """The statistics table of a float image [h, w, 3] on the device (mfsr_imageStats), exact: a CPU int64 tensor of
+    ``capi.IMAGE_STATS_WORDS`` words -- pixels, neutral pixels, the three code sums over the neutral set and over all pixels, the
+    histogram of the luma key and the histogram of the channel maximum, of the 12-bit codes of the pixel after ``matrix`` (None:
+    the pixel itself).  Rows may be pitched; the image is only read."""
+    if not (img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 3 and img.stride(2) == 1
+            and img.stride(1) == 3):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    p = _stats_params(matrix, lo, hi, chroma_tol)
+    with torch.cuda.device(img.device):
+        table = torch.zeros(capi.IMAGE_STATS_WORDS, dtype=torch.int64, device=img.device)
+        capi.lib().imageStats(img.data_ptr(), img.stride(0) * 4, w, h, ctypes.byref(p), table.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream)
+        return table.cpu()
+
+
+def _stats_host(stats):
+    import numpy as np
+    a = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    a = np.ascontiguousarray(a.astype(np.uint64, copy=False) if a.dtype != np.int64 else a.view(np.uint64))
+    if a.shape != (capi.IMAGE_STATS_WORDS,):
+        raise ValueError(f"stats: the table of image_stats, {capi.IMAGE_STATS_WORDS} words")
+    return a
+
+
+def awb_gains(stats, min_count: Optional[int] = None):
+    """((g_r, 1, g_b), status) of mfsr_awb_gains on a table of ``image_stats``: grey-world gains over the neutral set.  status 0
+    ok, 1 unmeasurable (gains 1, 1, 1), 2 clamped to [1/8, 8].  min_count None = 1/64 of the pixels measured.  Host only."""
+    a = _stats_host(stats)
+    g, st = (ctypes.c_float * 3)(), ctypes.c_int32()
+    capi.lib().awb_gains(a.ctypes.data, int(a[0]) // 64 if min_count is None else int(min_count), g, ctypes.byref(st))
+    return tuple(g), st.value
+
+
+def tone_fit(stats, p_lo: float = 0.001, p_hi: float = 0.999, max_gain: float = 8.0, mid: float = 0.18,
+             tone_size: int = 4096) -> ToneFit:
+    """Black point, white point, mid-tone gamma and the tone table of them (mfsr_tone_fit) from a table of ``image_stats``:
+    ``ToneFit(lut, black, white, gamma, status)`` with ``lut`` a CPU float32 tensor of tone_size + 1 floats for
+    ``set_render(tone_lut=...)``.  status 1: the span was floored at 1 / max_gain.  Host only."""
+    import numpy as np
+    a = _stats_host(stats)
+    tp = capi.ToneParams(float(p_lo), float(p_hi), float(max_gain), float(mid))
+    lut = np.empty(int(tone_size) + 1, np.float32)
+    b, w, g, st = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int32()
+    capi.lib().tone_fit(a.ctypes.data, ctypes.byref(tp), int(tone_size), lut.ctypes.data, ctypes.byref(b), ctypes.byref(w),
+                        ctypes.byref(g), ctypes.byref(st))
+    return ToneFit(torch.from_numpy(lut), b.value, w.value, g.value, st.value)
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -837,6 +912,64 @@ class BurstPipeline:
             self.out16 = _render_buffer(fmt, out_h, out_w, self.device)
             self._out16_host = None
             self._fmt = fmt
+
+    _AUTO_KEYS = {"lo": "lo", "hi": "hi", "chroma_tol": "chromaTol", "iterations": "iterations", "min_count": "minCount",
+                  "tone_size": "toneSize"}
+    _TONE_KEYS = {"p_lo": "pLo", "p_hi": "pHi", "max_gain": "maxGain", "mid": "mid"}
+
+    def auto_render(self, format: int = capi.OUT_RGB8, matrix=None, awb: bool = True, tone: bool = True, yuv: int = 0,
+                    tone_lut=None, **params) -> capi.AutoResult:
+        """Measure the burst and render by the measurement (mfsr_burst_auto_render): after the last
+        ``add_frame`` and before ``finish``.  ``awb``: white-balance gains from the near-grey pixels of the merged image go into
+        the colour matrix (``matrix`` times diag(gains), or diag(gains)).  ``tone``: black point, white point and a mid-tone
+        gamma from the image's histograms become the tone table.  With both off this is ``set_render(format, matrix, tone_lut,
+        yuv)``; ``tone_lut`` is used only when ``tone`` is off.  ``params``: lo, hi, chroma_tol, iterations, min_count, p_lo,
+        p_hi, max_gain, mid, tone_size (``auto_defaults``).  The statistics are those of the output, or of the aligned zoom window.
+        ``finish`` then returns the integer image typed for ``format`` as after ``set_render``; the description stays installed
+        until ``set_render`` changes it.  Returns the ``capi.AutoResult``; the installed description is ``self.auto_description``
+        (a ``capi.Render``) and the table behind it ``self.auto_lut`` (a device tensor or None)."""
+        self.window.check_yuv(int(format))
+        out_h, out_w = self.window.aligned[3], self.window.aligned[2]
+        ap = auto_defaults(out_h * out_w)
+        ap.awb, ap.tone = int(bool(awb)), int(bool(tone))
+        for k, v in params.items():
+            if k in self._AUTO_KEYS:
+                setattr(ap, self._AUTO_KEYS[k], int(v))
+            elif k in self._TONE_KEYS:
+                setattr(ap.toneParams, self._TONE_KEYS[k], float(v))
+            else:
+                raise TypeError(f"auto_render: unknown parameter {k!r}")
+        if not 1 <= ap.toneSize <= 65536:
+            raise ValueError("tone_size: 1 .. 65536")
+        res = capi.AutoResult()
+        with torch.cuda.device(self.device):
+            r, lut = _render_struct(format, matrix, None if tone else tone_lut, self.device, yuv)
+            table = torch.empty(capi.IMAGE_STATS_WORDS, dtype=torch.int64, device=self.device)
+            if tone:
+                lut = torch.empty(ap.toneSize + 1, dtype=torch.float32, device=self.device)
+            self.L.burst_auto_render(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), ctypes.byref(ap),
+                                     table.data_ptr(), lut.data_ptr() if tone else None, ctypes.byref(r), ctypes.byref(res),
+                                     self._stream())
+            self._held_frames.clear()
+            # the table is the caller's memory: alive as long as the description; the statistics table with it
+            self._render_lut, self._auto_table = lut, table
+            self.auto_description, self.auto_lut = r, lut
+            self.out16 = _render_buffer(int(format), out_h, out_w, self.device)
+            self._out16_host = None
+            self._fmt = int(format)
+        return res
+
+    def process_auto(self, frames: Sequence[torch.Tensor], frame_ids: Optional[Iterable[int]] = None, **auto):
+        """Whole burst on this device, rendered by its own measurement: reference products, every frame, ``auto_render(**auto)``,
+        finish.  Returns (float image, integer image) like ``process`` after ``set_render``; the outcome of the measurement is
+        left in ``self.auto_result`` (a ``capi.AutoResult``)."""
+        r = self.cfg.reference
+        self.begin_burst()
+        self.set_reference(frames[r])
+        for k in (range(len(frames)) if frame_ids is None else frame_ids):
+            self.add_frame(frames[k], k == r)
+        self.auto_result = self.auto_render(**auto)
+        return self.finish()
 
     def set_sharpen(self, amount: Optional[float] = None, sigma: float = 1.0, radius: int = 0, threshold: float = 0.0, taps=None):
         """Sharpen inside the finish (mfsr_burst_set_sharpen): an unsharp mask of strength ``amount`` on
