@@ -650,6 +650,10 @@ int mfsr_burst_fuse_stats(const mfsr_burst* b, int* burstLaunches, int* groupsFu
 /* process-wide switch of the burst hold for A/B (default 1; MFSR_BURST_FUSE=0 in the environment): 0 = every context fuses
  * group by group whatever mfsr_burst_hold_fuse said */
 int mfsr_set_burst_fuse(int enable);
+/* process-wide switch of the x2 margin kernels' body for A/B (default 1; MFSR_MARGIN_SITES=0 in the environment): 1 = raw
+ * samples and certainty texels once per site (3 x 3 sites, 2 x 2 texels), tap weights once per pixel and workgroup; 0 = the
+ * per-tap body (25 loads of each).  Both give the same accumulators bit for bit. */
+int mfsr_set_margin_sites(int enable);
 /* ApplyWeighting (+fallback) + optional gamma; outImg float3 HR (may be NULL),
  * out16 dense interleaved u16 HR (may be NULL).  Fuses whatever is still waiting first (mfsr_burst_flush), the groups of
  * the burst hold included. */

@@ -404,7 +404,32 @@ __device__ __forceinline__ void strip_pixel(int X, int Y, int sx, int sy, float 
 // SCALE is a template parameter: the straight arithmetic takes floor((x + px + sx) / scale) twenty times per pixel, and an
 // integer division by a run-time value is ~40 instructions -- half of this kernel's work when the scale was a kernel argument
 // WIN: the part of the ring inside a window (MarginRects), accumulators relative to the window's origin
-template <int SCALE, bool WIN = false>
+// SITES: the site-wise body (accumulate_pixel_sites; mfsr_set_margin_sites), else accumulate_pixel_core's 25 taps
+template <int SCALE, bool SITES>
+__device__ __forceinline__ void margin_pixel_1(int x, int y, const uint16_t* __restrict__ raw, pix3* __restrict__ imgOut,
+                                               pix3* __restrict__ totalWeights, const float4* __restrict__ certaintyMask,
+                                               const mfsr_tex2d& kernelParam, const mfsr_tex2d& shifts, const Levels3& glv, int dimX,
+                                               int dimY, int strideOut, int strideMask, int cfaPacked, int accX0 = 0, int accY0 = 0)
+{
+    if constexpr (SITES) {
+        const float2 pos = margin_pixel_pos<SCALE>(x, y, dimX, dimY);
+        const float4 kernel = tex4<ADDR_CLAMP>(kernelParam, pos.x, pos.y);
+        float wSym[13];
+#pragma unroll
+        for (int n = 0; n < 13; n++) wSym[n] = tap_weight<true>(n % 5 - 2, n / 5 - 2, kernel.x, kernel.y, kernel.z);
+        pix3 pixel = row_ptr(imgOut, strideOut, y - accY0)[x - accX0];
+        pix3 totalWeight = row_ptr(totalWeights, strideOut, y - accY0)[x - accX0];
+        accumulate_pixel_sites<SCALE>(x, y, raw, certaintyMask, shifts, glv, dimX, dimY, strideMask, cfaPacked, pos.x, pos.y,
+                                      margin_pixel_sums(kernel), [&](int n) { return wSym[n]; }, pixel, totalWeight);
+        row_ptr(imgOut, strideOut, y - accY0)[x - accX0] = pixel;
+        row_ptr(totalWeights, strideOut, y - accY0)[x - accX0] = totalWeight;
+    } else {
+        accumulate_pixel_generic<GEOM_FULL, true, true>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX,
+                                                        dimY, SCALE, strideOut, strideMask, cfaPacked, accX0, accY0);
+    }
+}
+
+template <int SCALE, bool WIN = false, bool SITES = false>
 __global__ void __launch_bounds__(256)
     k_accumulateMargin(const uint16_t* __restrict__ raw, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights,
                        const float4* __restrict__ certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts, Levels3 glv,
@@ -414,9 +439,8 @@ __global__ void __launch_bounds__(256)
     if constexpr (WIN) {
         int x, y;
         if (!margin_rect_pixel(mr, blockIdx.x * blockDim.x + threadIdx.x, x, y)) return;
-        accumulate_pixel_generic<GEOM_FULL, true, true>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
-                                                                   glv, dimX, dimY, scale, strideOut, strideMask, cfaPacked,
-                                                                   mr.accX0, mr.accY0);
+        margin_pixel_1<SCALE, SITES>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX, dimY, strideOut,
+                                     strideMask, cfaPacked, mr.accX0, mr.accY0);
         return;
     }
     const int hrW = scale * dimX, hrH = scale * dimY, M = STRIP_MARGIN;
@@ -443,8 +467,8 @@ __global__ void __launch_bounds__(256)
         return;
     }
     if (y < rowBegin || y >= rowEnd) return;  // HR row window of this launch (stripe-sharded bursts)
-    accumulate_pixel_generic<GEOM_FULL, true, true>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX,
-                                              dimY, scale, strideOut, strideMask, cfaPacked);
+    margin_pixel_1<SCALE, SITES>(x, y, raw, imgOut, totalWeights, certaintyMask, kernelParam, shifts, glv, dimX, dimY, strideOut,
+                                 strideMask, cfaPacked);
 }
 
 // FR = HR pixels per field texel along each axis (4: fields at LR/2, the Bayer
@@ -464,7 +488,33 @@ struct TileFrames {
 // parameters, then raw and certainty per tap) on 7.6 K wavefronts at 4K: one thread per (pixel, frame) -- 64 pixels x NF
 // frames per workgroup -- keeps the chain one frame long; the frames' sums (each taken from zero) meet in LDS and are
 // added to the accumulators in call order by the pixel's first thread, which reads and writes them once.
-template <int NF, int SCALE, bool WIN = false>
+// The pixel's header once per workgroup (SITES): the tap weights and the `sums` predicate depend on the kernel parameters of
+// the reference only -- the same for every frame of the pixel.  The pixel's frame-threads split the 13 weights between them
+// (thread n takes weights n, n + NF, ...), put them into LDS and every thread reads them after one barrier: the same values
+// as each thread's own, computed once.  Whole workgroups reach the barrier (threads of pixels past the end take part).
+struct MarginHeader {
+    float w[13][64];
+    float pos[2][64];  // margin_pixel_pos: two IEEE divisions
+    int sums[64];
+};
+template <int NF, int SCALE>
+__device__ __forceinline__ void margin_header(MarginHeader& h, bool live, int x, int y, int lane, int n, const mfsr_tex2d& kernelParam,
+                                              int dimX, int dimY)
+{
+    if (live) {
+        const float2 pos = margin_pixel_pos<SCALE>(x, y, dimX, dimY);
+        const float4 kernel = tex4<ADDR_CLAMP>(kernelParam, pos.x, pos.y);
+        if (n == 0) {
+            h.pos[0][lane] = pos.x;
+            h.pos[1][lane] = pos.y;
+        }
+        for (int k = n; k < 13; k += NF) h.w[k][lane] = tap_weight<true>(k % 5 - 2, k / 5 - 2, kernel.x, kernel.y, kernel.z);
+        if (n == 0) h.sums[lane] = margin_pixel_sums(kernel) ? 1 : 0;
+    }
+    __syncthreads();
+}
+
+template <int NF, int SCALE, bool WIN = false, bool SITES = false>
 __global__ void __launch_bounds__(64 * NF)
     k_accumulateMarginN(TileFrames<NF> fr, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                         Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int rowBegin, int rowEnd,
@@ -477,7 +527,8 @@ __global__ void __launch_bounds__(64 * NF)
     const int nTop = (M - 1) * rowLen, nBot = (M - 1) * rowLen;
     const int sideLen = 2 * (M - 1);
     const int nSide = (hrH - 2 * M) * sideLen;
-    const int lane = threadIdx.x, n = threadIdx.y;
+    // (SITES: the frame index as the wave-uniform value it is -- the frame's pointers then sit in scalar registers)
+    const int lane = threadIdx.x, n = SITES ? __builtin_amdgcn_readfirstlane(threadIdx.y) : threadIdx.y;
     const int idx = blockIdx.x * 64 + lane;
     int x = 0, y = -1;
     if constexpr (WIN) {
@@ -498,7 +549,15 @@ __global__ void __launch_bounds__(64 * NF)
     const bool live = y >= rowBegin && y < rowEnd && y >= 0;
     const int ax = WIN ? mr.accX0 : 0, ay = WIN ? mr.accY0 : 0;  // accumulator origin
     pix3 pixel = {0.0f, 0.0f, 0.0f}, totalWeight = {0.0f, 0.0f, 0.0f};
-    if (live) {
+    if constexpr (SITES) {
+        __shared__ MarginHeader sHdr;
+        margin_header<NF, SCALE>(sHdr, live, x, y, lane, n, kernelParam, dimX, dimY);
+        if (live) {
+            const TileFrame F = fr.f[n];
+            accumulate_pixel_sites<SCALE>(x, y, F.raw, F.mask, F.shifts, glv, dimX, dimY, strideMask, cfaPacked, sHdr.pos[0][lane], sHdr.pos[1][lane],
+                                          sHdr.sums[lane] != 0, [&](int k) { return sHdr.w[k][lane]; }, pixel, totalWeight);
+        }
+    } else if (live) {
         TileFrame F = fr.f[0];
 #pragma unroll
         for (int m = 1; m < NF; m++)
@@ -1574,8 +1633,12 @@ __global__ void __launch_bounds__(256, 3)
 // and writes them once.  Whole workgroups reach every barrier (no thread leaves early).
 // (k_accumulateMarginN<4 G> with one thread per (pixel, frame), up to 64 x 16 threads per workgroup, was measured slower
 // than the launches it replaces: 233 against 4 x 50 us at 4K x 16)
-template <int SCALE>
-__global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulateMarginN<4>: the kernel is latency-bound
+// Occupancy bound of the SITES form, by measurement (4K x 16): four waves per SIMD with the pixel
+// opaque per turn 108 us; three waves (168 registers: the compiler then carries the pixel's cell offsets, phases and texture
+// coordinates across the groups, 87 VALU instructions fewer per group) 119 us, three waves and opaque 119 us; five waves
+// spill 29 registers (not run).
+template <int SCALE, bool SITES = false>
+__global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulateMarginN<4>
     k_accumulateMarginBurst(BurstFrames fr, int nGroups, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                             Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked)
 {
@@ -1586,7 +1649,7 @@ __global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulat
     const int nTop = (M - 1) * rowLen, nBot = (M - 1) * rowLen;
     const int sideLen = 2 * (M - 1);
     const int nSide = (hrH - 2 * M) * sideLen;
-    const int lane = threadIdx.x, n = threadIdx.y;
+    const int lane = threadIdx.x, n = SITES ? __builtin_amdgcn_readfirstlane(threadIdx.y) : threadIdx.y;
     const int idx = blockIdx.x * 64 + lane;
     int x = 0, y = -1;
     if (idx < nTop) {
@@ -1609,20 +1672,36 @@ __global__ void __launch_bounds__(256, 4)  // four waves per SIMD as k_accumulat
         a = row_ptr(imgOut, strideOut, y)[x];
         w = row_ptr(totalWeights, strideOut, y)[x];
     }
+    __shared__ MarginHeader sHdr;  // (SITES only; an unused __shared__ object takes no LDS)
+    if constexpr (SITES) margin_header<NF, SCALE>(sHdr, live, x, y, lane, n, kernelParam, dimX, dimY);
 #pragma unroll 1
     for (int g = 0; g < nGroups; g++) {
         pix3 pixel = {0.0f, 0.0f, 0.0f}, totalWeight = {0.0f, 0.0f, 0.0f};
-        // (opaque per turn: the compiler would otherwise carry the pixel's 25 tap weights, which depend on the kernel parameters
-        // only, across the groups -- and spill 36 registers at the 128 the occupancy allows)
-        int xg = x, yg = y;
-        asm volatile("" : "+v"(xg), "+v"(yg));
-        if (live) {
-            TileFrame F = fr.f[4 * g];
+        if constexpr (SITES) {
+            // the weights and the predicate come from LDS in every group: nothing of the header is carried across the loop
+            // (the pixel opaque per turn, as below: what the compiler would carry across the groups spills 28 registers at
+            // the 128 of four waves per SIMD)
+            int xg = x, yg = y;
+            asm volatile("" : "+v"(xg), "+v"(yg));
+            if (live) {
+                const TileFrame F = fr.f[4 * g + n];
+                accumulate_pixel_sites<SCALE>(xg, yg, F.raw, F.mask, F.shifts, glv, dimX, dimY, strideMask, cfaPacked,
+                                              sHdr.pos[0][lane], sHdr.pos[1][lane], sHdr.sums[lane] != 0,
+                                              [&](int k) { return sHdr.w[k][lane]; }, pixel, totalWeight);
+            }
+        } else {
+            // (opaque per turn: the compiler would otherwise carry the pixel's 25 tap weights, which depend on the kernel
+            // parameters only, across the groups -- and spill 36 registers at the 128 the occupancy allows)
+            int xg = x, yg = y;
+            asm volatile("" : "+v"(xg), "+v"(yg));
+            if (live) {
+                TileFrame F = fr.f[4 * g];
 #pragma unroll
-            for (int m = 1; m < NF; m++)
-                if (n == m) F = fr.f[4 * g + m];
-            accumulate_pixel_core<GEOM_FULL, true, true>(xg, yg, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
-                                                                    strideMask, cfaPacked, pixel, totalWeight);
+                for (int m = 1; m < NF; m++)
+                    if (n == m) F = fr.f[4 * g + m];
+                accumulate_pixel_core<GEOM_FULL, true, true>(xg, yg, F.raw, F.mask, kernelParam, F.shifts, glv, dimX, dimY, scale,
+                                                             strideMask, cfaPacked, pixel, totalWeight);
+            }
         }
         sSum[n][0][lane] = pixel.x;
         sSum[n][1][lane] = pixel.y;
@@ -1994,6 +2073,7 @@ __global__ void __launch_bounds__(256, tile_waves_x4(NF))
 constexpr int pack_cfa(int c00, int c01, int c10, int c11) { return c00 | (c01 << 2) | (c10 << 4) | (c11 << 6); }
 
 int g_strip_xcd_remap = 1;  // MFSR_XCD_REMAP=0: launch order (A/B); see k_accumulate2xTile
+int g_margin_sites = 1;  // mfsr_set_margin_sites / MFSR_MARGIN_SITES=0: the x2 margin kernels' per-tap body (A/B)
 int g_strip_use_tile = 1;  // MFSR_STRIP_TILE: 0 register-only strip kernel, 1 LDS tile kernel (fields at HR/4)
 
 // true when the LDS tile kernel serves this geometry (fields at HR/4, whole tiles)
@@ -2115,24 +2195,42 @@ long long margin_pixel_count(int hrW, int hrH)
     return 2LL * (M - 1) * (hrW - 2) + (long long)(hrH - 2 * M) * 2 * (M - 1);
 }
 
-// The margin kernels (one thread per pixel of the 16-pixel frame margin, the straight per-pixel arithmetic) are small and
-// latency-bound (5.6 K waves, 25 us per 4K frame).  They touch accumulator bytes the tile kernel does not (it does not write
-// the side-margin chunks back) and are launched on the caller's stream after it.  (Measured and not kept: a side stream,
-// forked before the tile launch and joined after the last margin launch -- 8.79 against 8.88 ms per burst, no gain,
-// profiles/r02_ab_margin_overlap.txt.)
-// the margin pixels of one frame: the whole ring, or the part of it inside a window
+// The margin kernels (one thread per pixel of the 16-pixel frame margin, the straight per-pixel arithmetic) are small (5.6 K
+// waves per 4K frame).  Counters on the per-tap body's 16-frame launch (profiles/r08_pmc_margin.txt): it issues VALU
+// instructions in as many wave-cycles as it waits (SQ_ACTIVE_INST_VALU 124 M, SQ_WAIT_INST_ANY 136 M) -- instruction-bound
+// as much as latency-bound; the site-wise body issues a third fewer instructions and waits a third as long.  They touch
+// accumulator bytes the tile kernel does not (it does not write the side-margin chunks back) and are launched on the
+// caller's stream after it.  (Measured and not kept: a side stream, forked before the tile launch and joined after the last
+// margin launch -- 8.79 against 8.88 ms per burst, no gain, profiles/r02_ab_margin_overlap.txt.)
+// The site-wise body (k_accumulateMargin*<.., SITES = true>) serves x2 with the switch on; it addresses a frame's raw and
+// certainty planes with 32-bit offsets, so planes of 2 GiB and more keep the per-tap body.  (x4 keeps the per-tap body: its
+// instances of the site-wise body have not been measured.)
+template <int SCALE>
+bool margin_sites_ok(int dimX, int dimY, int strideMask)
+{
+    return SCALE == 2 && g_margin_sites == 1 && (long long)dimX * dimY * 2 < (1LL << 31) &&
+           (long long)strideMask * ((dimY + 1) / 2) < (1LL << 31);
+}
+
 template <int SCALE>
 void launch_margin_1(hipStream_t st, const uint16_t* raw, const mfsr_float4* mask, mfsr_tex2d shifts, pix3* pI, pix3* pT, mfsr_tex2d kp,
                      Levels3 glv, int dimX, int dimY, int strideOut, int strideMask, int cp, int rowBegin, int rowEnd,
                      const WinLaunch& wl, const MarginRects& mr)
 {
-    if (!wl.on)
-        hipLaunchKernelGGL(k_accumulateMargin<SCALE>, dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 256)), dim3(256), 0,
-                           st, raw, pI, pT, (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd,
-                           mr);
-    else if (mr.start[4] > 0)
-        hipLaunchKernelGGL((k_accumulateMargin<SCALE, true>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, st, raw, pI, pT,
-                           (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    auto launch = [&](auto sites) {
+        constexpr bool SITES = decltype(sites)::value;
+        if (!wl.on)
+            hipLaunchKernelGGL((k_accumulateMargin<SCALE, false, SITES>), dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 256)),
+                               dim3(256), 0, st, raw, pI, pT, (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp,
+                               rowBegin, rowEnd, mr);
+        else if (mr.start[4] > 0)
+            hipLaunchKernelGGL((k_accumulateMargin<SCALE, true, SITES>), dim3(mfsr_cdiv(mr.start[4], 256)), dim3(256), 0, st, raw, pI, pT,
+                               (const float4*)mask, kp, shifts, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    };
+    if constexpr (SCALE == 2) {
+        if (margin_sites_ok<SCALE>(dimX, dimY, strideMask)) return launch(std::true_type{});
+    }
+    launch(std::false_type{});
 }
 
 // the margin pixels of NF frames in one launch: the whole ring, or the part of it inside a window
@@ -2140,12 +2238,19 @@ template <int NF, int SCALE>
 void launch_margin_n(hipStream_t st, const TileFrames<NF>& fr, pix3* pI, pix3* pT, mfsr_tex2d kp, Levels3 glv, int dimX, int dimY,
                      int strideOut, int strideMask, int cp, int rowBegin, int rowEnd, const WinLaunch& wl, const MarginRects& mr)
 {
-    if (!wl.on)
-        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE>), dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 64)),
-                           dim3(64, NF), 0, st, fr, pI, pT, kp, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
-    else if (mr.start[4] > 0)
-        hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE, true>), dim3(mfsr_cdiv(mr.start[4], 64)), dim3(64, NF), 0, st, fr, pI, pT, kp,
-                           glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    auto launch = [&](auto sites) {
+        constexpr bool SITES = decltype(sites)::value;
+        if (!wl.on)
+            hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE, false, SITES>), dim3(mfsr_cdiv(margin_pixel_count(SCALE * dimX, SCALE * dimY), 64)),
+                               dim3(64, NF), 0, st, fr, pI, pT, kp, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+        else if (mr.start[4] > 0)
+            hipLaunchKernelGGL((k_accumulateMarginN<NF, SCALE, true, SITES>), dim3(mfsr_cdiv(mr.start[4], 64)), dim3(64, NF), 0, st, fr, pI,
+                               pT, kp, glv, dimX, dimY, strideOut, strideMask, cp, rowBegin, rowEnd, mr);
+    };
+    if constexpr (SCALE == 2) {
+        if (margin_sites_ok<SCALE>(dimX, dimY, strideMask)) return launch(std::true_type{});
+    }
+    launch(std::false_type{});
 }
 
 void read_env_once()
@@ -2155,6 +2260,8 @@ void read_env_once()
         if (e && e[0] >= '0' && e[0] <= '1') g_strip_use_tile = e[0] - '0';
         const char* x = getenv("MFSR_XCD_REMAP");
         if (x && (x[0] == '0' || x[0] == '1')) g_strip_xcd_remap = x[0] - '0';
+        const char* m = getenv("MFSR_MARGIN_SITES");
+        if (m && m[0] == '0') g_margin_sites = 0;
         return true;
     }();
     (void)env_read;
@@ -2355,9 +2462,20 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     if (rc != 1) return rc;
     // the margin pixels of all frames in one launch, the frames' sums (each from zero) added to the accumulator value one after
     // another in call order -- the order of the launches it replaces
-    hipLaunchKernelGGL((k_accumulateMarginBurst<2>), dim3(mfsr_cdiv(margin_pixel_count(hrW, hrH), 64)), dim3(64, 4), 0, st, fr,
-                       nFrames / 4, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp);
+    if (margin_sites_ok<2>(dimX, dimY, strideMask))
+        hipLaunchKernelGGL((k_accumulateMarginBurst<2, true>), dim3(mfsr_cdiv(margin_pixel_count(hrW, hrH), 64)), dim3(64, 4), 0, st, fr,
+                           nFrames / 4, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp);
+    else
+        hipLaunchKernelGGL((k_accumulateMarginBurst<2, false>), dim3(mfsr_cdiv(margin_pixel_count(hrW, hrH), 64)), dim3(64, 4), 0, st, fr,
+                           nFrames / 4, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp);
     return 1;
+}
+
+extern "C" int mfsr_set_margin_sites(int enable)
+{
+    read_env_once();  // (a later first launch must not put the environment's value over this one)
+    g_margin_sites = enable ? 1 : 0;
+    return MFSR_OK;
 }
 
 // x4: returns 1 if the x4 tile kernel took the nFrames (1 to 4) frames, 0 if the geometry is not its

@@ -65,9 +65,23 @@ for wl in wls:
     n_main = sum(len(per[m]["SQ_INSTS_VALU"]) for m in main)   # every tile / strip dispatch (an odd burst ends with a 1-frame one)
     n_margin = sum(len(per[m]["SQ_INSTS_VALU"]) for m in margin)
 
+    # frames per launch and launches per burst of the profiled run (bench.py's own line in the pass log).  A burst-hold dispatch
+    # (k_accumulate2xTileBurst) fuses several four-frame groups and bench.py counts it as that many launches
+    # (roofline.avg_launch_ms is per group): the counters are divided by the launches bench.py counted, not by the dispatches.
+    fpl, n_launch = None, n_main
+    try:
+        for ln in open(f"{root}/{wl}/p1.log"):
+            if ln.startswith("{") and '"roofline"' in ln:
+                line = json.loads(ln)
+                fpl = line["roofline"].get("frames_per_launch")
+                if line["roofline"].get("launches_timed") and line.get("steps"):
+                    n_launch = max(n_main, int(round(line["roofline"]["launches_timed"] / line["steps"])))
+    except Exception:
+        fpl, n_launch = None, n_main
+
     def per_launch(counter):
         tot = sum(sum(per[m].get(counter, [])) for m in main) + sum(sum(per[m].get(counter, [])) for m in margin)
-        return tot / max(n_main, 1)
+        return tot / max(n_launch, 1)
 
     fetch, write, valu = per_launch("FETCH_SIZE"), per_launch("WRITE_SIZE"), per_launch("SQ_INSTS_VALU")
     hbm = 2 * fetch * 1024 + write * 1024
@@ -90,19 +104,11 @@ for wl in wls:
         first_later = None
     mk = re.search(r"k_\w+", k)
     kname = mk.group(0) if mk else k
-    # frames per launch of the profiled run (bench.py's own line in the pass log): bench.py applies the entry only to runs
-    # with the same grouping
-    fpl = None
-    try:
-        for ln in open(f"{root}/{wl}/p1.log"):
-            if ln.startswith("{") and '"roofline"' in ln:
-                fpl = json.loads(ln)["roofline"].get("frames_per_launch")
-    except Exception:
-        fpl = None
+    # (fpl: bench.py applies the entry only to runs with the same grouping)
     res[wl] = {"hbm_bytes_per_launch": int(hbm), "valu_wave_insts_per_launch": int(valu), "frames_per_launch": fpl,
                "kernel_source_sha16": fuse_source_sha16(),
                "source": f"rocprofv3 --pmc passes of tools/gpu_pmc_workloads.sh ({kname}: {n_main} dispatches + "
-                         f"{n_margin} margin dispatches per burst)"}
+                         f"{n_margin} margin dispatches per burst, counted as {n_launch} launches)"}
     if read_exact:
         res[wl]["hbm_bytes_per_launch_2xfetch"] = res[wl]["hbm_bytes_per_launch"]
         res[wl]["read_bytes_by_request_size"] = int(read_exact)
@@ -117,7 +123,7 @@ for wl in wls:
     if first_later:
         lines.append(f"  tile kernel, 128-B read requests (or FETCH_SIZE KB) per dispatch: first launch of a burst {first_later[0]:.4g} (n={first_later[1]}), "
                      f"later launches {first_later[2]:.4g} (n={first_later[3]})")
-    lines.append(f"  dispatches per burst: {n_main} (+{n_margin} margin); per launch: FETCH_SIZE {fetch:.0f} KB, WRITE_SIZE {write:.0f} KB, "
+    lines.append(f"  dispatches per burst: {n_main} (+{n_margin} margin) = {n_launch} launches; per launch: FETCH_SIZE {fetch:.0f} KB, WRITE_SIZE {write:.0f} KB, "
                  f"HBM bytes (2*F+W) {hbm / 1e9:.3f} GB, SQ_INSTS_VALU {valu:.4g}, waves {per_launch('SQ_WAVES'):.0f}")
 mix = static_mix([MIX_KERNEL[w] for w in res if w in MIX_KERNEL])
 for wl in res:
