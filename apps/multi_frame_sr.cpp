@@ -34,6 +34,8 @@
 //     DESIGN.md section 2.16; 2 = the 5x5 minimum); works with MFSR_GPUS > 1.
 //   * MFSR_SHARPEN="amount[,sigma[,radius[,threshold]]]" sharpens _sr_result inside the finish (an unsharp mask on the linear
 //     value), with or without MFSR_CCM; one GPU only.
+//   * MFSR_DENOISE="strength[,radius[,gain]]" denoises _sr_result inside the finish (a range filter whose tolerance follows the
+//     accumulated weight), with or without MFSR_CCM; not with MFSR_SHARPEN; one GPU only.
 //   * MFSR_AUTO=wb|tone|wb,tone measures white-balance gains and / or a tone table on the merged image and renders _sr_result
 //     with them, with or without MFSR_CCM and MFSR_SHARPEN; it prints `auto: gains R G B ... black K
 //     white W gamma G ...` to stderr; one GPU only.
@@ -356,6 +358,44 @@ int main(int argc, char** argv)
         sharpenOn = true;
         render.format = MFSR_OUT_RGB8;
     }
+    // MFSR_DENOISE="strength[,radius[,gain]]": the merge-aware range filter inside the finish, on the linear value before the
+    // matrix and the tone curve (mfsr_burst_set_denoise; radius 2, gain 2 by default; alpha and beta are cfg's at the time of the
+    // finish, so MFSR_NOISE's measurement goes in).  The 8-bit image then comes out of the denoised finish.
+    bool denoiseOn = false;
+    mfsr_denoise denoise;
+    memset(&denoise, 0, sizeof(denoise));
+    if (const char* e = getenv("MFSR_DENOISE")) {
+        float v[3] = {0.0f, 2.0f, 2.0f};  // strength, radius, gain
+        const char* p = e;
+        bool ok = true;
+        for (int n = 0; ok; n++) {
+            char* end = nullptr;
+            v[n] = strtof(p, &end);
+            ok = end != p && std::isfinite(v[n]);
+            p = end;
+            if (!ok || *p == '\0') break;
+            ok = *p == ',' && n < 2;
+            p++;
+        }
+        ok = ok && *p == '\0' && v[1] >= 1.0f && v[1] <= 3.0f && v[1] == (float)(int)v[1] && v[0] != 0.0f &&
+             mfsr_denoise_defaults(0.0f, 0.0f, &denoise) == MFSR_OK;
+        if (ok) {
+            denoise.strength = v[0];
+            denoise.radius = (int)v[1];
+            denoise.gain = v[2];
+            ok = mfsr_denoise_validate(&denoise) == MFSR_OK;
+        }
+        if (!ok) {
+            fprintf(stderr, "MFSR_DENOISE=%s: strength[,radius[,gain]] expected: 1/16 <= strength <= 16, radius 1..3, 0 < gain <= 1024\n", e);
+            return 1;
+        }
+        denoiseOn = true;
+        render.format = MFSR_OUT_RGB8;
+    }
+    if (denoiseOn && sharpenOn) {
+        fprintf(stderr, "MFSR_DENOISE is not supported with MFSR_SHARPEN (one stencil per finish: DESIGN.md section 2.24)\n");
+        return 1;
+    }
     // MFSR_AUTO=wb|tone|wb,tone: white-balance gains and / or a tone table measured on the merged image itself
     // (mfsr_burst_auto_render) go into the render description of the finish; with MFSR_CCM the gains
     // multiply that matrix, with MFSR_SHARPEN the measurement is taken before sharpening.  The 8-bit image then comes out of the
@@ -382,7 +422,11 @@ int main(int argc, char** argv)
         render.format = MFSR_OUT_RGB8;
     }
     const bool autoOn = autoWb || autoTone;
-    const bool rendered = ccm || sharpenOn || autoOn;  // the 8-bit image comes out of the finish launch
+    const bool rendered = ccm || sharpenOn || denoiseOn || autoOn;  // the 8-bit image comes out of the finish launch
+    if (denoiseOn && gpus > 1) {
+        fprintf(stderr, "MFSR_DENOISE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
     if (autoOn && gpus > 1) {
         fprintf(stderr, "MFSR_AUTO is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
@@ -620,6 +664,11 @@ int main(int argc, char** argv)
     HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
     if (rendered) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
     if (sharpenOn) MFSR_OK_OR_DIE(mfsr_burst_set_sharpen(b, &sharpen));
+    if (denoiseOn) {
+        denoise.alpha = cfg.alpha;  // (as calibrated, when MFSR_NOISE asked for it)
+        denoise.beta = cfg.beta;
+        MFSR_OK_OR_DIE(mfsr_burst_set_denoise(b, &denoise));
+    }
     // MFSR_AUTO: the table of the statistics and the tone table the measurement writes (device memory of the caller's)
     uint64_t* dstats = nullptr;
     float* dlut = nullptr;

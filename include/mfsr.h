@@ -1281,6 +1281,85 @@ int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharpen);
  * not an mfsr_path: those count branches that a configuration (mfsr_config) chooses, this one follows a setter. */
 int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes);
 
+/* ---- merge-aware denoise inside the finish: a range filter on the linear float value whose tolerance is the variance the
+ * merge left at the pixel.  Off unless asked for; without a denoise description every entry point
+ * produces the bits and the launches it always did.  All arithmetic is float32, no contraction, in the order written.  For an
+ * HR pixel i, p is the value section 2.19 calls p (after ApplyWeighting with the fallback, before gamma), three channels k;
+ * w is its accumulated weight (the totalWeights accumulator), threshold is cfg.weightThreshold:
+ *   1. s_k = isnan(p_k) ? 0 : fminf(fmaxf(p_k, -65536), 65536)
+ *   2. effective count, by the finish's own rule: n_k = (w_k < threshold) ? w_k + 1 : w_k;  n_k = isnan(n_k) ? 0 : n_k
+ *   3. fade: wHi <= wLo (the default, both 0): lambda_k = 1; otherwise lambda_k = fminf(fmaxf((wHi - n_k) * rSpan, 0), 1) with
+ *      rSpan = 1.0f / (wHi - wLo), formed once on the host in float
+ *   4. tolerance: v_k = fmaxf((gain * (alpha * fmaxf(s_k, 0) + beta)) / fmaxf(n_k, 1e-6f), 1e-20f);  r_k = 1.0f / (hh * v_k)
+ *      with hh = strength * strength, formed once on the host in float
+ *   5. for dy = -R .. R and inside it dx = -R .. R, the neighbour j at the coordinate clamped to the valid extent (borders
+ *      replicate; the extent is stated per entry point):
+ *        d_k = s_jk - s_ik;  t = ((d_0*d_0)*r_0 + (d_1*d_1)*r_1) + (d_2*d_2)*r_2;  u = fmaxf(1.0f - t, 0);  g = u*u
+ *      row sums start at 0 and add in dx order: G_dy = G_dy + g, S_dy,k = S_dy,k + g * s_jk; G and S_k start at 0 and the rows
+ *      are added in dy order from row -R: G = G + G_dy, S_k = S_k + S_dy,k.  The centre contributes g = 1, so G >= 1.
+ *   6. f_k = S_k / G;  o_k = (lambda_k == 0) ? s_k : s_k + lambda_k * (f_k - s_k)
+ *   7. o takes the place of p in steps 1-3 of the rendered output (matrix, tone, quantise); with no render description the
+ *      steps are those of {MFSR_OUT_RGB16, no matrix, no table}.
+ * The tolerance is the expected variance (alpha p + beta) / n of a pixel that averaged n samples, times gain (a merge's
+ * measured variance was about twice the prediction: the weights are not equal and the samples are interpolated) and times
+ * strength^2: the filter is wide where few samples were merged and narrows by itself where many were.  The range kernel is a
+ * polynomial, max(1 - t, 0)^2, so that no exp is evaluated and a float32 restatement is exact.
+ * A description: radius 1..3 (0 = off), strength in [1/16, 16] (0 = off), gain in (0, 1024], alpha and beta in [0, 1], wLo and
+ * wHi finite with 0 <= wLo and either wHi <= wLo or wHi - wLo >= 2^-10, reserved zero-filled; anything else is MFSR_E_INVALID.
+ * With these bounds no inf or NaN arises in steps 3-6: |s| <= 2^16 and n is not NaN, so lambda is fmaxf / fminf of a product
+ * with rSpan in (0, 1024] (fmaxf returns its other argument for a NaN: lambda lies in [0, 1] whatever n is); the numerator of
+ * v is at most 1024 * (2^16 + 1) < 2^27 and its denominator at least 1e-6 (an infinite n gives 0, then 1e-20), so
+ * 1e-20 <= v < 2^47; hh lies in [2^-8, 2^8], so 2^-55 < r < 2.6e22; |d| <= 2^17, so (d*d)*r < 2^34 * 2.6e22 < 5e32 and
+ * t < 1.5e33 is finite; u and g lie in [0, 1]; G lies in [1, 49] (the centre has d = 0, t = 0, g = 1) and |S_k| <= 49 * 2^16;
+ * f_k = S_k / G is a weighted mean of values of s, and |lambda (f - s)| <= 2^17.
+ * mfsr_denoise_defaults (host only): radius 2, strength 3, gain 2, wLo = wHi = 0 and the caller's alpha, beta (the noise
+ * model of one raw sample, cfg.alpha / cfg.beta, which mfsr_burst_calibrate_noise* can measure).
+ * mfsr_denoise_tile: the output tile one workgroup owns (the sizes at which the kernels take another path). */
+typedef struct {
+    int32_t radius;      /* R, 1..3; 0 = off */
+    float strength;      /* 1/16 .. 16; 0 = off */
+    float gain;          /* measured / predicted variance of the merge, (0, 1024] */
+    float alpha, beta;   /* variance of one raw sample = alpha * p + beta; each in [0, 1] */
+    float wLo, wHi;      /* fade: full strength at n <= wLo, none at n >= wHi; wHi <= wLo = no fade */
+    int32_t reserved[5]; /* zeros */
+} mfsr_denoise;
+int mfsr_denoise_defaults(float alpha, float beta, mfsr_denoise* out);
+int mfsr_denoise_validate(const mfsr_denoise* denoise);
+int mfsr_denoise_tile(int* tileW, int* tileH);
+/* Steps 1 and 3-7 on an existing float image; the valid extent is the image.  count: a float3 image of n (rows countRowBytes
+ * apart), or NULL for n = 1 everywhere, the single-frame case.  A count image IS n: the threshold rule of step 2 is skipped and
+ * only its NaN cleaning applies.  Neither outImg nor out may overlap `in` or `count` (MFSR_E_INVALID: a stencil cannot run in
+ * place); outImg or out may be NULL, not both.  render may be NULL ({MFSR_OUT_RGB16, no matrix, no table}); the two-plane
+ * formats are refused.  A description that is off (radius or strength 0) is refused: call mfsr_renderImage.
+ * mfsr_finishDenoised: mfsr_finishRendered with steps 1-6 in the same launch.  Columns are valid in [0, w) of the launch, rows
+ * in [-rowsAbove, h + rowsBelow) relative to the launch's first row, exactly as for mfsr_finishSharpened: the accumulator and
+ * weight rows in that range must be complete, and neither outImg nor out may overlap them.  A stripe with rowsAbove =
+ * rowsBelow = R is the crop of the whole in its rows; a window clamps at its own left and right edges.  A wave whose pixels
+ * all have lambda_k == 0 skips the stencil (step 6 makes that value-preserving).  Both check every argument on the host before
+ * any device call, are asynchronous on `stream` and allocate nothing. */
+int mfsr_denoiseImage(const mfsr_float3* in, int inRowBytes, const mfsr_float3* count, int countRowBytes, mfsr_float3* outImg,
+                      int outImgRowBytes, void* out, int outRowBytes, int w, int h, const mfsr_denoise* denoise,
+                      const mfsr_render* render, int applyGamma, mfsr_stream_t stream);
+int mfsr_finishDenoised(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                        int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                        int outImgRowBytes, void* out, int outRowBytes, const mfsr_render* render, int w, int h, float threshold,
+                        int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight, const mfsr_denoise* denoise,
+                        int rowsAbove, int rowsBelow, mfsr_stream_t stream);
+/* The burst's denoise description (copied; NULL, radius == 0 or strength == 0 = off, the default).  Between bursts only, as
+ * mfsr_burst_set_render.  With one set, every finish of the burst goes through mfsr_finishDenoised, by the plumbing of the
+ * sharpened finish: mfsr_burst_finish (cfg.fused = 0 too), _finish_rows (rowsAbove = min(R, row0), rowsBelow = min(R, H -
+ * row0 - rows)), _finish_host (band i - 1 after band i has been fused), mfsr_burst_process_source, mfsr_burst_process_joint and
+ * the outputs of a stream.  A window clamps at its own edges (the Python layer grows it by one 16-pixel ring and crops).
+ * alpha and beta are the description's, not cfg's: the caller decides (the Python and CLI layers default them to cfg's).
+ * Refused (MFSR_E_INVALID, by whichever setter comes second): a denoise description that is on together with a two-plane format,
+ * and together with a sharpen description that is on (one launch would need a halo of both radii and a third LDS stage;
+ * finish denoised to the linear float image, then mfsr_sharpenImage with the render description).  The multi-GPU layer
+ * (mfsr_dist.h) never sets one. */
+int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise);
+int mfsr_stream_set_denoise(mfsr_stream* s, const mfsr_denoise* denoise);
+/* *finishes = the launches of mfsr_finishDenoised this burst has made since mfsr_burst_begin (as mfsr_burst_debug_sharpened) */
+int mfsr_burst_debug_denoised(const mfsr_burst* b, int* finishes);
+
 /* ---- image statistics, auto white balance, auto tone.  The measurement the render description
  * lacks: an exact-integer statistics stage on the device, two small fits on the host, and a burst driver that fills and
  * installs the mfsr_render of the finish.  Nothing here runs unless it is called.

@@ -138,6 +138,13 @@ class Sharpen(ctypes.Structure):
                 ("threshold", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
 
 
+class Denoise(ctypes.Structure):
+    """mfsr_denoise (include/mfsr.h): the merge-aware range filter of a denoised finish."""
+
+    _fields_ = [("radius", ctypes.c_int32), ("strength", ctypes.c_float), ("gain", ctypes.c_float), ("alpha", ctypes.c_float),
+                ("beta", ctypes.c_float), ("wLo", ctypes.c_float), ("wHi", ctypes.c_float), ("reserved", ctypes.c_int32 * 5)]
+
+
 # image statistics, auto white balance and auto tone (include/mfsr.h; DESIGN.md section 2.23)
 IMAGE_STATS_BINS = 4096
 IMAGE_STATS_WORDS = 8 + 2 * IMAGE_STATS_BINS

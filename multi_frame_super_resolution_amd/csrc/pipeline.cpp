@@ -370,6 +370,10 @@ struct mfsr_burst {
     bool sharpenOn;
     mfsr_sharpen sharpen;
     int sharpenedFinishes;  // launches of mfsr_finishSharpened since mfsr_burst_begin (mfsr_burst_debug_sharpened)
+    // merge-aware denoise inside the finish (mfsr_burst_set_denoise); never on together with sharpenOn
+    bool denoiseOn;
+    mfsr_denoise denoise;
+    int denoisedFinishes;   // launches of mfsr_finishDenoised since mfsr_burst_begin (mfsr_burst_debug_denoised)
     // host staging of mfsr_burst_auto_render: the downloaded table and the tone table on its way to the device
     std::vector<uint64_t> autoStats;
     std::vector<float> autoLut;
@@ -605,6 +609,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->renderOn = false;
     b->sharpenOn = false;
     b->sharpenedFinishes = 0;
+    b->denoiseOn = false;
+    b->denoisedFinishes = 0;
     b->nUnp = 0;
     b->hostEpoch = 0;
     b->evEpoch = nullptr;
@@ -1991,7 +1997,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     MFSR_REQUIRE(b && imgOut && totalWeights);
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = 0;
     b->burstLaunches = b->burstGroups = 0;
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
@@ -2050,10 +2056,14 @@ static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const 
                                c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
 }
 
-// the sharpened finish of output rows [r0, r0 + rows), as finish_rendered_rows; the rows [r0 - rowsAbove, r0 + rows + rowsBelow)
+// A finish with a reach: a stencil on the value the finish holds -- the sharpened (§2.20) or the denoised (§2.24) finish, never
+// both -- reads R rows beyond the rows it writes.
+static bool stencil_on(const mfsr_burst* b) { return b->sharpenOn || b->denoiseOn; }
+
+// the stencil finish of output rows [r0, r0 + rows), as finish_rendered_rows; the rows [r0 - rowsAbove, r0 + rows + rowsBelow)
 // of the accumulators are complete.  Without a render description the integer output is uint16_t RGB.
-static int finish_sharpened_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
-                                 void* out, int r0, int rows, int rowsAbove, int rowsBelow, mfsr_stream_t stream)
+static int finish_stencil_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
+                               void* out, int r0, int rows, int rowsAbove, int rowsBelow, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
@@ -2061,6 +2071,15 @@ static int finish_sharpened_rows(mfsr_burst* b, const mfsr_float3* imgOut, const
     const int rowBytes = (int)out_row_bytes(b);
     const size_t off = (size_t)r0 * pitch;
     const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    if (b->denoiseOn) {
+        b->denoisedFinishes++;
+        return mfsr_finishDenoised((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                                   pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                   outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
+                                   out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : nullptr, oW,
+                                   rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, &b->denoise, rowsAbove, rowsBelow,
+                                   stream);
+    }
     b->sharpenedFinishes++;
     return mfsr_finishSharpened((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
                                 pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
@@ -2070,10 +2089,10 @@ static int finish_sharpened_rows(mfsr_burst* b, const mfsr_float3* imgOut, const
                                 stream);
 }
 
-// rows of the output above / below [r0, r0 + rows) that a sharpened finish of those rows reads
-static void sharpen_reach(const mfsr_burst* b, int r0, int rows, int* above, int* below)
+// rows of the output above / below [r0, r0 + rows) that a stencil finish of those rows reads
+static void stencil_reach(const mfsr_burst* b, int r0, int rows, int* above, int* below)
 {
-    const int R = b->sharpen.radius, rest = out_h(b) - r0 - rows;
+    const int R = b->denoiseOn ? b->denoise.radius : b->sharpen.radius, rest = out_h(b) - r0 - rows;
     *above = R < r0 ? R : r0;
     *below = R < rest ? R : rest;
 }
@@ -2089,8 +2108,33 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
     TRY(mfsr_sharpen_validate(sharpen));
     const bool on = sharpen->radius != 0 && sharpen->amount != 0.0f;
     MFSR_REQUIRE(!(on && yuv_on(b)));  // the sharpen tile kernel renders single rows: no two-plane output
+    MFSR_REQUIRE(!(on && b->denoiseOn));  // one stencil per finish: whichever setter comes second is refused
     b->sharpen = *sharpen;
     b->sharpenOn = on;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise)
+{
+    MFSR_REQUIRE(b != nullptr);
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    if (!denoise) {
+        b->denoiseOn = false;
+        return MFSR_OK;
+    }
+    TRY(mfsr_denoise_validate(denoise));
+    const bool on = denoise->radius != 0 && denoise->strength != 0.0f;
+    MFSR_REQUIRE(!(on && yuv_on(b)));     // the denoise tile kernel renders single rows, as the sharpen one
+    MFSR_REQUIRE(!(on && b->sharpenOn));  // one stencil per finish
+    b->denoise = *denoise;
+    b->denoiseOn = on;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_debug_denoised(const mfsr_burst* b, int* finishes)
+{
+    MFSR_REQUIRE(b && finishes);
+    *finishes = b->denoisedFinishes;
     return MFSR_OK;
 }
 
@@ -2110,7 +2154,7 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
         return MFSR_OK;
     }
     TRY(mfsr_render_validate(render));
-    MFSR_REQUIRE(!(b->sharpenOn && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen: whichever comes second)
+    MFSR_REQUIRE(!(stencil_on(b) && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen / _denoise: whichever comes second)
     b->render = *render;
     b->renderOn = true;
     return MFSR_OK;
@@ -2234,7 +2278,7 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     // cfg.fused = 0 too: the stencil cannot run in place on the chain's in/out image, and the value the fused finish holds
     // before its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting (tests/test_parity_kernels.py::
     // test_finishFused_equals_chain), so the unfused burst's sharpened finish is this launch as well: no second HR float image
-    if (b->sharpenOn) return finish_sharpened_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
+    if (stencil_on(b)) return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
     if (b->renderOn && c.fused) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
     if (b->renderOn) {
         // the unfused chain up to ApplyWeighting, then the pixel body on the float image in place of GammasRGB + quantize
@@ -2284,10 +2328,10 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     if (yuv_on(b)) MFSR_REQUIRE((row0 & 1) == 0 && (rows & 1) == 0);  // whole 2 x 2 chroma blocks
     TRY(flush_pending(b, stream));
-    if (b->sharpenOn) {
+    if (stencil_on(b)) {
         int above, below;
-        sharpen_reach(b, row0, rows, &above, &below);
-        return finish_sharpened_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
+        stencil_reach(b, row0, rows, &above, &below);
+        return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
     }
     if (b->renderOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
     const int pitch = 12 * L.hrW;
@@ -2587,13 +2631,14 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // bands of output rows (window rows when a window is set: y0 is a multiple of 16, so are the bands' HR rows)
     const int tileRows = (oH + 15) / 16;
     if (nBands > tileRows) nBands = tileRows;
-    // A sharpened band reads R <= 4 rows of its neighbours: band i - 1 is finished and downloaded after band i has been fused
-    // (every band but the last is a multiple of 16 rows), the last one after the loop.  lagR0 < 0: no band waits.
+    // A band of a stencil finish reads R rows of its neighbours (sharpened: R <= 4, denoised: R <= 3): band i - 1 is finished and
+    // downloaded after band i has been fused (every band but the last is a multiple of 16 rows), the last one after the loop.
+    // lagR0 < 0: no band waits.
     int lagI = -1, lagR0 = -1, lagR1 = -1;
     auto finish_lagged = [&]() -> int {
         int above, below;
-        sharpen_reach(b, lagR0, lagR1 - lagR0, &above, &below);
-        TRY(finish_sharpened_rows(b, imgOut, totalWeights, nullptr, out16Dev, lagR0, lagR1 - lagR0, above, below, stream));
+        stencil_reach(b, lagR0, lagR1 - lagR0, &above, &below);
+        TRY(finish_stencil_rows(b, imgOut, totalWeights, nullptr, out16Dev, lagR0, lagR1 - lagR0, above, below, stream));
         if (!b->evBand[lagI]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[lagI], hipEventDisableTiming));
         MFSR_HIP_TRY(hipEventRecord(b->evBand[lagI], mfsr_s(stream)));
         MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[lagI], 0));
@@ -2623,7 +2668,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
                 fresh = 0;
             }
         }
-        if (b->sharpenOn) {
+        if (stencil_on(b)) {
             if (lagR0 >= 0) TRY(finish_lagged());
             lagI = i;
             lagR0 = r0;
@@ -3014,7 +3059,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     // a new burst on this handle (what mfsr_burst_begin resets; no accumulators: nothing is fused)
     TRY(flush_pending(b, stream));
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = 0;
     TRY(mfsr_burst_set_reference(b, frames[reference], stream));
 
     char* base = (char*)scratchDev;
@@ -3314,6 +3359,12 @@ extern "C" int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharp
 {
     MFSR_REQUIRE(s != nullptr);
     return mfsr_burst_set_sharpen(s->b, sharpen);  // every output's finish sharpens
+}
+
+extern "C" int mfsr_stream_set_denoise(mfsr_stream* s, const mfsr_denoise* denoise)
+{
+    MFSR_REQUIRE(s != nullptr);
+    return mfsr_burst_set_denoise(s->b, denoise);  // every output's finish denoises
 }
 
 extern "C" int mfsr_stream_reset(mfsr_stream* s)

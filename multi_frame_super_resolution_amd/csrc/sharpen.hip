@@ -15,7 +15,7 @@
 // owns four consecutive columns: it reads them as one float4 per row, channel and tap (ds_read_b128; four dword reads would
 // put the 32 lanes of a half on 8 banks, a 4-way conflict), computes its four pixels, and then hands them to render_span.
 // R is a runtime argument: one set of kernels.
-#include "render_common.hpp"
+#include "stencil_host.hpp"
 
 namespace {
 
@@ -161,16 +161,6 @@ __global__ void __launch_bounds__(kLanes)
     sharpen_tile<FORMAT>(fetch, s_s, s_h, outImg, outPitch, out, outRowBytes, width, height, a, r, lut);
 }
 
-// How the tone table is read here.  Measured at 7680 x 4320 with a 4096-interval table ("Sharpened
-// finish"): with the tile's 39 KB of LDS a staged table (32 KB more) halves the workgroups per CU, and RGB8 -- the one format
-// render.hip stages it for -- takes 621 / 904 us (R = 1 / 4) staged against 412 / 538 us through the cache.  So every format
-// reads the table through the cache; MFSR_RENDER_LUT=lds still forces the staged form (A/B, and the tests run both).
-bool sharpen_lut_in_lds(const mfsr_render* r)
-{
-    const char* e = getenv("MFSR_RENDER_LUT");
-    return e && strcmp(e, "lds") == 0 && lut_in_lds(r);
-}
-
 bool sharpen_on(const mfsr_sharpen* s) { return s->radius != 0 && s->amount != 0.0f; }
 
 SharpenArgs sharpen_args(const mfsr_sharpen* s, int yLo, int yHi)
@@ -185,38 +175,9 @@ SharpenArgs sharpen_args(const mfsr_sharpen* s, int yLo, int yHi)
     return a;
 }
 
-// without a render description: the plain finish's steps
-mfsr_render plain_render()
-{
-    mfsr_render r;
-    memset(&r, 0, sizeof(r));
-    r.format = MFSR_OUT_RGB16;
-    return r;
-}
-
-bool ranges_overlap(const void* a, long long aBytes, const void* b, long long bBytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + (uintptr_t)bBytes && b0 < a0 + (uintptr_t)aBytes;
-}
-
 }  // namespace
 
-#define SHARPEN_DISPATCH(KERNEL, format, lds, ...)                                                                          \
-    do {                                                                                                                    \
-        const dim3 block(kLanes);                                                                                           \
-        const dim3 grid(mfsr_cdiv(w, kTW), mfsr_cdiv(h, kTH));                                                              \
-        switch (((format) << 1) | ((lds) ? 1 : 0)) {                                                                        \
-            case 0: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 1: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 2: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
-            case 3: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
-            case 4: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 5: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 6: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;  \
-            default: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break; \
-        }                                                                                                                   \
-    } while (0)
+#define SHARPEN_DISPATCH(KERNEL, format, lds, ...) STENCIL_DISPATCH(KERNEL, kTW, kTH, kLanes, format, lds, __VA_ARGS__)
 
 extern "C" int mfsr_sharpen_tile(int* tileW, int* tileH)
 {
@@ -266,26 +227,16 @@ extern "C" int mfsr_sharpenImage(const mfsr_float3* in, int inRowBytes, mfsr_flo
                                  int outRowBytes, int w, int h, const mfsr_sharpen* sharpen, const mfsr_render* render,
                                  int applyGamma, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(in && (outImg || out) && w > 0 && h > 0);
-    MFSR_REQUIRE((long long)inRowBytes >= 12LL * w && (inRowBytes & 3) == 0 && ((uintptr_t)in & 3) == 0);
-    if (outImg) {
-        MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0 && ((uintptr_t)outImg & 3) == 0);
-        MFSR_REQUIRE(!ranges_overlap(in, (long long)inRowBytes * (h - 1) + 12LL * w, outImg, (long long)outImgRowBytes * (h - 1) + 12LL * w));
-    }
+    if (int rc = stencil_image_args(in, inRowBytes, outImg, outImgRowBytes, out, w, h)) return rc;
     if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
     MFSR_REQUIRE(sharpen_on(sharpen));
     const mfsr_render plain = plain_render();
-    if (!render) render = &plain;
-    if (int rc = mfsr_render_validate(render)) return rc;
-    MFSR_REQUIRE(!yuv_format(render->format));  // the tile kernel renders single rows: no two-plane 4:2:0 output
-    if (out) {
-        if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
-        MFSR_REQUIRE(!ranges_overlap(in, (long long)inRowBytes * (h - 1) + 12LL * w, out,
-                                     (long long)outRowBytes * (h - 1) + (long long)bytes_per_pixel(render->format) * w));
-    }
+    if (int rc = stencil_render(render, &plain, &render)) return rc;
+    if (int rc = stencil_outputs_apart(in, image_span(inRowBytes, h, 12, w), outImg, outImgRowBytes, out, outRowBytes, render->format, w, h))
+        return rc;
     const RenderArgs ra = render_args(render, applyGamma);
     const SharpenArgs sa = sharpen_args(sharpen, 0, h - 1);
-    const bool lds = sharpen_lut_in_lds(render);
+    const bool lds = stencil_lut_in_lds(render);
     SHARPEN_DISPATCH(k_sharpenImage, render->format, lds, (const pix3*)in, inRowBytes, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
                      outRowBytes, w, h, sa, ra);
     return mfsr_launch_status("sharpenImage");
@@ -298,38 +249,19 @@ extern "C" int mfsr_finishSharpened(const mfsr_float3* finalImg, const mfsr_floa
                                     int rowOffset, int fullWidth, int fullHeight, const mfsr_sharpen* sharpen, int rowsAbove,
                                     int rowsBelow, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out) && w > 0 && h > 0);
-    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
-    MFSR_REQUIRE(rowsAbove >= 0 && rowsAbove <= rowOffset && rowsBelow >= 0 && rowsBelow <= fullHeight - rowOffset - h);
+    if (int rc = stencil_finish_args(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, outImg, outImgRowBytes, out, w, h,
+                                     colOffset, rowOffset, fullWidth, fullHeight, rowsAbove, rowsBelow))
+        return rc;
     if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
     MFSR_REQUIRE(sharpen_on(sharpen));
     const mfsr_render plain = plain_render();
-    if (!render) render = &plain;
-    if (int rc = mfsr_render_validate(render)) return rc;
-    MFSR_REQUIRE(!yuv_format(render->format));  // the tile kernel renders single rows: no two-plane 4:2:0 output
-    if (out)
-        if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
-    {
-        // a stencil: no output may overlap the accumulator or weight rows the launch reads (its own and the reach's)
-        const long long readBytes = (long long)imgRowBytes * (h - 1 + rowsAbove + rowsBelow) + 12LL * w;
-        const char* fin0 = (const char*)finalImg - (long long)imgRowBytes * rowsAbove;
-        const char* wt0 = (const char*)weight - (long long)imgRowBytes * rowsAbove;
-        if (outImg) {
-            const long long n = (long long)outImgRowBytes * (h - 1) + 12LL * w;
-            MFSR_REQUIRE(!ranges_overlap(fin0, readBytes, outImg, n) && !ranges_overlap(wt0, readBytes, outImg, n));
-        }
-        if (out) {
-            const long long n = (long long)outRowBytes * (h - 1) + (long long)bytes_per_pixel(render->format) * w;
-            MFSR_REQUIRE(!ranges_overlap(fin0, readBytes, out, n) && !ranges_overlap(wt0, readBytes, out, n));
-        }
-    }
+    if (int rc = stencil_render(render, &plain, &render)) return rc;
+    if (int rc = stencil_finish_apart(finalImg, weight, imgRowBytes, rowsAbove, rowsBelow, outImg, outImgRowBytes, out, outRowBytes,
+                                      render->format, w, h))
+        return rc;
     const RenderArgs ra = render_args(render, applyGamma);
     const SharpenArgs sa = sharpen_args(sharpen, -rowsAbove, h - 1 + rowsBelow);
-    const bool lds = sharpen_lut_in_lds(render);
+    const bool lds = stencil_lut_in_lds(render);
     SHARPEN_DISPATCH(k_finishSharpened, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes,
                      (const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
                      outRowBytes, w, h, threshold, rowOffset, fullHeight, colOffset, fullWidth, sa, ra);

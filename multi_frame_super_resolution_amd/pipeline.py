@@ -760,6 +760,65 @@ def sharpen_image(img: torch.Tensor, amount: float = 1.0, sigma: float = 1.0, ra
     return (out, fl) if want_float else out
 
 
+# ---- merge-aware denoise inside the finish (include/mfsr.h, mfsr_denoise) -----------------------------
+def denoise_defaults(alpha: float = 0.0, beta: float = 0.0) -> capi.Denoise:
+    """The default denoise description (mfsr_denoise_defaults; host arithmetic, no device): radius 2, strength 3, gain 2, no
+    fade, and the noise model alpha, beta of one raw sample (``cfg.alpha`` / ``cfg.beta``)."""
+    d = capi.Denoise()
+    if capi.lib().raw["mfsr_denoise_defaults"](float(alpha), float(beta), ctypes.byref(d)) != 0:
+        raise ValueError("denoise: alpha and beta in [0, 1], finite")
+    return d
+
+
+def _denoise_struct(strength, radius=2, gain=2.0, alpha=0.0, beta=0.0, fade=None) -> Optional[capi.Denoise]:
+    """The description of ``BurstPipeline.set_denoise``'s arguments; None = off.  fade = (w_lo, w_hi) or None."""
+    if strength is None:
+        return None
+    d = capi.Denoise()
+    d.radius, d.strength, d.gain, d.alpha, d.beta = int(radius), float(strength), float(gain), float(alpha), float(beta)
+    if fade is not None:
+        d.wLo, d.wHi = float(fade[0]), float(fade[1])
+    if capi.lib().raw["mfsr_denoise_validate"](ctypes.byref(d)) != 0:
+        raise ValueError("denoise: radius 0..3, strength 0 or 1/16..16, 0 < gain <= 1024, alpha and beta in [0, 1], "
+                         "fade = (w_lo >= 0, w_hi) with w_hi <= w_lo or w_hi - w_lo >= 2^-10, all finite")
+    return d
+
+
+def denoise_image(img: torch.Tensor, count: Optional[torch.Tensor] = None, strength: float = 3.0, radius: int = 2, gain: float = 2.0,
+                  alpha: float = 0.0, beta: float = 0.0, fade=None, format: Optional[int] = None, matrix=None, tone_lut=None,
+                  apply_gamma: bool = False, want_float: bool = True):
+    """The range filter of a denoised finish on an existing linear float image [h, w, 3] on the device (mfsr_denoiseImage),
+    followed by the steps of ``render_image`` when ``format`` is given.  ``count``: a float image [h, w, 3] of how many samples
+    each value averaged (the tolerance is gain * (alpha * p + beta) / count), or None for one everywhere, the single-frame
+    case.  Returns the float image, or with ``format`` the tensor typed for it (and with ``want_float`` the pair (integers,
+    float image))."""
+    def dense(t):
+        return t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3
+    if not dense(img):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    if count is not None and not (dense(count) and count.shape == img.shape and count.device == img.device):
+        raise ValueError("count: a float32 device tensor of img's shape with dense pixels")
+    d = _denoise_struct(strength, radius, gain, alpha, beta, fade)
+    if d is None or d.radius == 0 or d.strength == 0:
+        raise ValueError("denoise_image: strength and radius must not be 0")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    with torch.cuda.device(img.device):
+        r, lut, out = None, None, None
+        if format is not None:
+            r, lut = _render_struct(format, matrix, tone_lut, img.device)
+            out = _render_buffer(format, h, w, img.device)
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if (want_float or out is None) else None
+        capi.lib().denoiseImage(img.data_ptr(), img.stride(0) * 4, None if count is None else count.data_ptr(),
+                                0 if count is None else count.stride(0) * 4, None if fl is None else fl.data_ptr(), 12 * w,
+                                None if out is None else out.data_ptr(), 0 if out is None else render_row_bytes(format, w), w, h,
+                                ctypes.byref(d), None if r is None else ctypes.byref(r), 1 if apply_gamma else 0,
+                                torch.cuda.current_stream().cuda_stream)
+        del lut
+    if out is None:
+        return fl
+    return (out, fl) if want_float else out
+
+
 # ---- image statistics, auto white balance, auto tone (DESIGN.md section 2.23; include/mfsr.h, mfsr_imageStats) ---------------
 ToneFit = namedtuple("ToneFit", "lut black white gamma status")
 
@@ -849,6 +908,7 @@ class BurstPipeline:
         self.L = capi.lib()
         self.cfg = cfg
         self.window = _Window(cfg, window)
+        self._sharpen_on = self._denoise_on = False   # a stencil in the finish (set_sharpen, set_denoise) grows the window
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.burst_workspace_bytes(ctypes.byref(cfg))
         if nbytes == 0:
@@ -983,14 +1043,43 @@ class BurstPipeline:
         on = s is not None and s.radius != 0 and s.amount != 0
         with torch.cuda.device(self.device):
             self.L.burst_set_sharpen(self._h, None if s is None else ctypes.byref(s))
-            if self.window.grow(WINDOW_GRID if on else 0):
-                self.L.burst_set_window(self._h, *self.window.aligned)
-                out_h, out_w = self.window.aligned[3], self.window.aligned[2]
-                self._img_out = torch.zeros(out_h, out_w, 3, dtype=torch.float32, device=self.device)
-                self._total_weights = torch.zeros_like(self._img_out)
-                self.out_img = torch.empty_like(self._img_out)
-                self.out16 = _render_buffer(self._fmt, out_h, out_w, self.device)
-                self._out16_host = None
+            self._sharpen_on = on
+            self._grow_window()
+
+    def _grow_window(self):
+        """A stencil in the finish (sharpen, denoise): the aligned window grows by one 16-pixel ring, or shrinks back."""
+        if self.window.grow(WINDOW_GRID if (self._sharpen_on or self._denoise_on) else 0):
+            self.L.burst_set_window(self._h, *self.window.aligned)
+            out_h, out_w = self.window.aligned[3], self.window.aligned[2]
+            self._img_out = torch.zeros(out_h, out_w, 3, dtype=torch.float32, device=self.device)
+            self._total_weights = torch.zeros_like(self._img_out)
+            self.out_img = torch.empty_like(self._img_out)
+            self.out16 = _render_buffer(self._fmt, out_h, out_w, self.device)
+            self._out16_host = None
+
+    def set_denoise(self, strength: Optional[float] = None, radius: int = 2, gain: float = 2.0, alpha: Optional[float] = None,
+                    beta: Optional[float] = None, fade=None):
+        """Denoise inside the finish (mfsr_burst_set_denoise): a range filter of ``radius`` 1..3 on the
+        linear float value, before the colour matrix and the tone curve, in the finish's own launch.  Its tolerance is
+        ``strength``^2 * ``gain`` * (alpha * p + beta) / n with n the pixel's accumulated weight, so it is wide where the merge
+        averaged few samples and narrows by itself where it averaged many.  ``alpha`` / ``beta``: the noise model of one raw
+        sample, None = ``cfg.alpha`` / ``cfg.beta``.  ``fade`` = (w_lo, w_hi): full strength at n <= w_lo, none at n >= w_hi.
+        ``strength=None`` turns it off.  Between bursts only; not together with ``set_sharpen`` or a two-plane format.  With a
+        zoom window the aligned window grows by one 16-pixel ring, as for ``set_sharpen``."""
+        d = _denoise_struct(strength, radius, gain, self.cfg.alpha if alpha is None else alpha,
+                            self.cfg.beta if beta is None else beta, fade)
+        on = d is not None and d.radius != 0 and d.strength != 0
+        with torch.cuda.device(self.device):
+            self.L.burst_set_denoise(self._h, None if d is None else ctypes.byref(d))
+            self._denoise_on = on
+            self._grow_window()
+
+    def denoised_finishes(self) -> int:
+        """Launches of mfsr_finishDenoised since ``begin_burst`` (mfsr_burst_debug_denoised): 1 for a resident burst, one per
+        band for a host burst, 0 when denoising is off."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_denoised(self._h, ctypes.byref(n))
+        return n.value
 
     def sharpened_finishes(self) -> int:
         """Launches of mfsr_finishSharpened since ``begin_burst`` (mfsr_burst_debug_sharpened): 1 for a resident burst, one per
@@ -1367,12 +1456,14 @@ class FrameStream:
     copy stream."""
 
     def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
-                 window: Optional[Sequence[int]] = None, render: Optional[dict] = None, sharpen: Optional[dict] = None):
+                 window: Optional[Sequence[int]] = None, render: Optional[dict] = None, sharpen: Optional[dict] = None,
+                 denoise: Optional[dict] = None):
         """window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
         ``BurstPipeline.set_render`` (format, matrix, tone_lut, yuv): every output is rendered, typed for the format.  sharpen: the
         keyword arguments of ``BurstPipeline.set_sharpen``: every output is sharpened inside its finish; with a window the
         library works on the aligned window grown by one 16-pixel ring, as ``BurstPipeline`` does, so the rectangle asked for
-        is the crop of the whole-frame sharpened output."""
+        is the crop of the whole-frame sharpened output.  denoise: the keyword arguments of ``BurstPipeline.set_denoise``
+        (alpha / beta default to cfg's): every output is denoised inside its finish; a window grows in the same way."""
         if not torch.cuda.is_available():
             raise RuntimeError("multi_frame_super_resolution_amd needs a HIP device (MI355X); there is no CPU fallback")
         self.L = capi.lib()
@@ -1381,7 +1472,14 @@ class FrameStream:
         self.host_frames = host_frames
         self.window = _Window(cfg, window)
         sharp = None if sharpen is None else _sharpen_struct(**sharpen)
-        if sharp is not None and sharp.radius != 0 and sharp.amount != 0:
+        den = None
+        if denoise is not None:
+            kw = dict(denoise)
+            kw["alpha"] = cfg.alpha if kw.get("alpha") is None else kw["alpha"]
+            kw["beta"] = cfg.beta if kw.get("beta") is None else kw["beta"]
+            den = _denoise_struct(**kw)
+        if (sharp is not None and sharp.radius != 0 and sharp.amount != 0) or (
+                den is not None and den.radius != 0 and den.strength != 0):
             self.window.grow(WINDOW_GRID)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.stream_workspace_bytes(ctypes.byref(cfg), radius)
@@ -1407,6 +1505,8 @@ class FrameStream:
                 self._fmt = fmt
             if sharp is not None:
                 self.L.stream_set_sharpen(self._h, ctypes.byref(sharp))
+            if den is not None:
+                self.L.stream_set_denoise(self._h, ctypes.byref(den))
 
     def close(self):
         if getattr(self, "_h", None):
