@@ -486,6 +486,31 @@ typedef struct {
 int mfsr_robustnessMaskFusedBatch(int nFrames, const mfsr_robustness_frame* frames, const mfsr_float3* rawImgRef, int flowPitch,
                                   int flowWidth, int flowHeight, int imgWidth, int imgHeight, int imgPitch, int maskPitch, float alpha,
                                   float beta, float thresholdM, mfsr_stream_t stream);
+/* ---- the robustness masks of a group in one pass over the reference (csrc/robustness.hip, k_robustnessGroup) ----
+ * mfsr_prepareFrameFusedBatch whose halfOut receives, instead of the half-resolution pixel, that pixel's 3 x 3 patch mean as
+ * the robustness mask forms it: per channel div9(sum of half(clamp(x + dx), clamp(y + dy))), summed from 0.0f row-major, the
+ * division exact.  Both pyramid outputs are bit-identical to mfsr_prepareFrameFusedBatch.  meansRowBytes >= 12 * w.
+ * MFSR_E_UNSUPPORTED (nothing launched) for ntaps < 3 (the tile has no halo) and for ntaps / 2 > 8. */
+int mfsr_prepareFrameMeansBatch(int nFrames, const mfsr_prepare_frame* frames, int meansRowBytes, float maxVal, int w, int h,
+                                int pyr0RowBytes, int pyr1RowBytes, const float* taps, int ntaps, mfsr_stream_t stream);
+/* The masks of 1 .. 4 moved frames against one reference, bit-identical to mfsr_robustnessMaskFusedBatch: what depends on the
+ * reference alone is computed once per pixel and kept across the frames, and a frame's moved side is one gather from its
+ * patch-mean image (movedMeans: mfsr_prepareFrameMeansBatch).  Where the displaced position leaves the image the nine
+ * individually clamped pixels are rebuilt from the frame's dense raw samples (movedRaw: 2 * w samples per row, 2 * h rows;
+ * maxVal and the CFA pattern as given to the prepare call).  Every flow field has the image's resolution (w x h texels of
+ * flowRowBytes rows).  MFSR_E_UNSUPPORTED (nothing launched) after mfsr_set_robustness_fast(0). */
+typedef struct {
+    const mfsr_float3* movedMeans;
+    const uint16_t* movedRaw;
+    mfsr_float4* mask;
+    const mfsr_float2* flow;
+} mfsr_robustness_group_frame;
+int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf, int refRowBytes,
+                             int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal, float alpha,
+                             float beta, float thresholdM, mfsr_stream_t stream);
+/* process-wide switch for A/B (default 1; MFSR_ROBUST_GROUP=0 in the environment): 1 = the burst driver makes the masks of an
+ * aligned group with the two calls above, 0 = with mfsr_prepareFrameFusedBatch + mfsr_robustnessMaskFusedBatch.  Same bits. */
+int mfsr_set_robustness_group(int enable);
 /* The iteration of mfsr_lucasKanadeIterationWarped for 1 .. 4 frames against one reference in ONE launch (csrc/lk_fused.hip,
  * k_lkSweep: one wavefront per 64 columns sweeping down a band of rows, vertical state in registers, horizontal window sums
  * through whole-wave DPP shifts, no LDS).  Agrees with mfsr_lucasKanadeIterationWarped to fp32 rounding (another
@@ -1359,6 +1384,9 @@ int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise);
 int mfsr_stream_set_denoise(mfsr_stream* s, const mfsr_denoise* denoise);
 /* *finishes = the launches of mfsr_finishDenoised this burst has made since mfsr_burst_begin (as mfsr_burst_debug_sharpened) */
 int mfsr_burst_debug_denoised(const mfsr_burst* b, int* finishes);
+/* *launches = the launches of mfsr_robustnessMaskGroup this burst has made since mfsr_burst_begin: one per aligned group that
+ * took the patch-mean path (mfsr_set_robustness_group), 0 with the switch off */
+int mfsr_burst_debug_robust_group(const mfsr_burst* b, int* launches);
 
 /* ---- image statistics, auto white balance, auto tone.  The measurement the render description
  * lacks: an exact-integer statistics stage on the device, two small fits on the host, and a burst driver that fills and

@@ -78,6 +78,12 @@ class RobustnessFrame(ctypes.Structure):
     _fields_ = [("movedHalf", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("flow", ctypes.c_void_p)]
 
 
+class RobustnessGroupFrame(ctypes.Structure):
+    """mfsr_robustness_group_frame: one moved frame of mfsr_robustnessMaskGroup (its patch-mean image from
+    mfsr_prepareFrameMeansBatch, its raw samples, its mask and its flow field)."""
+    _fields_ = [("movedMeans", ctypes.c_void_p), ("movedRaw", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("flow", ctypes.c_void_p)]
+
+
 class Config(ctypes.Structure):
     """mfsr_config (include/mfsr.h)."""
 

@@ -69,6 +69,8 @@ struct MfsrBatch {
 };
 int mfsr_cfa_packed();  // defined in debayer.hip (process-wide state)
 int mfsr_reference_fused();  // the switch of mfsr_set_reference_fused, kernel_field.hip (process-wide state)
+int mfsr_robustness_group();  // mfsr_set_robustness_group and the fast robustness kernel both on, robustness.hip (process-wide state)
+int mfsr_robustness_group_fits(int h, int flowRowBytes, int meansRowBytes, int maskRowBytes);  // images below 2 GiB (k_robustnessGroup's offsets)
 // x / d for a divisor that is the same for a whole launch (an image dimension): q = x r, q' = fma(fma(-d, q, x), r, q) with
 // r = RN(1 / d) -- two multiply-adds after the product instead of the ~10 instructions of the IEEE division expansion.  For a
 // given d the sequence either is the correctly rounded quotient for EVERY x or it is not (scaling x by a power of two

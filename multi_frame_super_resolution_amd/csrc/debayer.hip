@@ -4,6 +4,7 @@
 // bit-identical to the CPU oracle.
 #include <cstring>
 #include "common.hpp"
+#include "half_pixel.hpp"
 
 // ---- A0: c_cfaPattern (DeBayerKernels.cu:40-41) -------------------------------
 // Process-wide like the reference's module constant, but passed to every kernel
@@ -89,30 +90,13 @@ struct PrepTaps {
     int n;
 };
 
-__device__ __forceinline__ pix3 a1_pixel(const uint16_t* __restrict__ dataIn, int dimX, int x, int y, float factor, int cfa)
-{
-    const size_t rowElems = (size_t)dimX * 2;
-    const uint32_t top = *(const uint32_t*)(dataIn + (size_t)(2 * y) * rowElems + 2 * x);
-    const uint32_t bot = *(const uint32_t*)(dataIn + (size_t)(2 * y + 1) * rowElems + 2 * x);
-    const float raw[2][2] = {{(float)(top & 0xffffu), (float)(top >> 16)}, {(float)(bot & 0xffffu), (float)(bot >> 16)}};
-    pix3 pixel = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int ix = 0; ix < 2; ix++) {
-#pragma unroll
-        for (int iy = 0; iy < 2; iy++) {
-            const int c = cfa_at(cfa, iy, ix);
-            const float v = raw[iy][ix] * factor;
-            if (c == MFSR_GREEN)
-                pixel.y += v * 0.5f;
-            else if (c == MFSR_RED)
-                pixel.x = v;
-            else if (c == MFSR_BLUE)
-                pixel.z = v;
-        }
-    }
-    return pixel;
-}
-
+// MEANS (mfsr_prepareFrameMeansBatch): halfOut receives, instead of the half-resolution pixel, that pixel's 3 x 3 patch mean
+// as the robustness mask forms it (robustness.hip: sum from 0.0f over the individually clamped coordinates, row-major, then
+// div9).  The three channels of the tile + a one-pixel halo are kept in LDS planes (needs a halo: taps.n >= 3); the halo
+// samples are the samples at the clamped coordinates, which is what that sum reads.  The pyramid outputs are not affected.
+#define PREP_MW (PREP_TX + 2)
+#define PREP_MH (PREP_TY + 2)
+template <bool MEANS>
 __global__ void __launch_bounds__(256)
     k_prepareFrameFused(const uint16_t* __restrict__ dataIn, pix3* __restrict__ halfOut, int halfPitch, float maxVal,
                         int dimX, int dimY, float* __restrict__ pyr0, int pyr0Pitch, float* __restrict__ pyr1,
@@ -130,6 +114,11 @@ __global__ void __launch_bounds__(256)
     float* sG = s_prep;              // GH x GW luma of tile + halo
     float* sH = sG + GW * GH;        // GH x PREP_TX after the row pass
     float* sO = sH + PREP_TX * GH;   // PREP_TY x PREP_TX filtered tile
+    // MEANS: 3 planes of PREP_MH x PREP_MW, the half-resolution tile + 1.  They are read right after the first barrier and
+    // then dead, so (one more barrier) the row pass writes sH over them, and the filtered tile goes where the luma was once the
+    // row pass has read it: the workgroup's LDS stays at what eight workgroups per CU can share.
+    float* sM = sH;
+    if (MEANS) sO = sG;
     const int tid = threadIdx.y * 64 + threadIdx.x;
     const int x0 = blockIdx.x * PREP_TX, y0 = blockIdx.y * PREP_TY;
     const float factor = 1.0f / maxVal;
@@ -139,10 +128,53 @@ __global__ void __launch_bounds__(256)
         const int gx = x0 + lx - c0, gy = y0 + ly - c0;
         const int cx = clampi(gx, 0, dimX - 1), cy = clampi(gy, 0, dimY - 1);
         const pix3 p = a1_pixel(dataIn, dimX, cx, cy, factor, cfa);
-        if (gx == cx && gy == cy && lx >= c0 && lx < c0 + PREP_TX && ly >= c0 && ly < c0 + PREP_TY) row_ptr(halfOut, halfPitch, gy)[gx] = p;
+        if (MEANS) {
+            const int mx = lx - (c0 - 1), my = ly - (c0 - 1);
+            if (mx >= 0 && mx < PREP_MW && my >= 0 && my < PREP_MH) {
+                sM[(0 * PREP_MH + my) * PREP_MW + mx] = p.x;
+                sM[(1 * PREP_MH + my) * PREP_MW + mx] = p.y;
+                sM[(2 * PREP_MH + my) * PREP_MW + mx] = p.z;
+            }
+        } else {
+            if (gx == cx && gy == cy && lx >= c0 && lx < c0 + PREP_TX && ly >= c0 && ly < c0 + PREP_TY) row_ptr(halfOut, halfPitch, gy)[gx] = p;
+        }
         sG[i] = 0.299f * p.x + 0.587f * p.y + 0.114f * p.z;  // k_rgbToGray
     }
     __syncthreads();
+    if (MEANS) {
+        // four pixels of one column per thread: the six patch rows they share are read once (18 LDS reads per channel for
+        // four means instead of 36); every mean is still its own sum from 0.0f in row-major order
+        static_assert(PREP_TY == 16, "four rows for each of the block's four thread rows");
+        const int lx = threadIdx.x, r0 = 4 * threadIdx.y;
+        float mean[4][3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float v[6][3];
+#pragma unroll
+            for (int y = 0; y < 6; y++)
+#pragma unroll
+                for (int x = 0; x < 3; x++) v[y][x] = sM[(c * PREP_MH + r0 + y) * PREP_MW + lx + x];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float m = 0.0f;
+#pragma unroll
+                for (int y = 0; y < 3; y++)
+#pragma unroll
+                    for (int x = 0; x < 3; x++) m += v[r + y][x];
+                mean[r][c] = div9(m);
+            }
+        }
+        const int gx = x0 + lx;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int gy = y0 + r0 + r;
+            if (gx < dimX && gy < dimY) {
+                const pix3 o = {mean[r][0], mean[r][1], mean[r][2]};
+                row_ptr(halfOut, halfPitch, gy)[gx] = o;
+            }
+        }
+        __syncthreads();  // (sH takes the planes' place)
+    }
     for (int i = tid; i < PREP_TX * GH; i += 256) {
         const int ly = i / PREP_TX, lx = i - ly * PREP_TX;
         // k_filter1d<true> at column x0+lx of (clamped) row: taps read clamp(x + t - c0); the halo already
@@ -180,13 +212,14 @@ __global__ void __launch_bounds__(256)
 }
 
 static int prepare_frames_impl(int n, const mfsr_prepare_frame* f, int halfPitch, float maxVal, int dimX, int dimY, int pyr0Pitch,
-                               int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream)
+                               int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream, bool means = false)
 {
     MFSR_REQUIRE(f && n >= 1 && n <= MFSR_BATCH_MAX && taps && dimX > 0 && dimY > 0);
     MFSR_REQUIRE((long long)halfPitch >= 12LL * dimX && (halfPitch & 3) == 0);
     MFSR_REQUIRE((long long)pyr0Pitch >= 4LL * dimX && (pyr0Pitch & 3) == 0);
     MFSR_REQUIRE(ntaps > 0 && (ntaps & 1) == 1);
     if (ntaps / 2 > PREP_MAXC0) return MFSR_E_UNSUPPORTED;
+    if (means && ntaps < 3) return MFSR_E_UNSUPPORTED;  // (no halo to take the patch from)
     MfsrBatch bt;
     memset(&bt, 0, sizeof(bt));
     for (int i = 0; i < n; i++) {
@@ -204,7 +237,15 @@ static int prepare_frames_impl(int n, const mfsr_prepare_frame* f, int halfPitch
     const int c0 = ntaps / 2, GW = PREP_TX + 2 * c0, GH = PREP_TY + 2 * c0;
     const size_t lds = sizeof(float) * ((size_t)GW * GH + (size_t)PREP_TX * GH + (size_t)PREP_TX * PREP_TY);
     dim3 block(64, 4), grid(mfsr_cdiv(dimX, PREP_TX), mfsr_cdiv(dimY, PREP_TY), n);
-    hipLaunchKernelGGL(k_prepareFrameFused, grid, block, lds, mfsr_s(stream), f[0].dataIn, (pix3*)f[0].halfOut, halfPitch, maxVal, dimX,
+    if (means) {
+        const size_t planes = 3 * PREP_MW * PREP_MH, rows = (size_t)PREP_TX * GH;  // (sM and sH share one region, sO lies in sG)
+        const size_t ldsMeans = sizeof(float) * ((size_t)GW * GH + (planes > rows ? planes : rows));
+        hipLaunchKernelGGL(k_prepareFrameFused<true>, grid, block, ldsMeans, mfsr_s(stream), f[0].dataIn,
+                           (pix3*)f[0].halfOut, halfPitch, maxVal, dimX, dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp,
+                           mfsr_cfa_packed(), bt);
+        return mfsr_launch_status("prepareFrameMeans");
+    }
+    hipLaunchKernelGGL(k_prepareFrameFused<false>, grid, block, lds, mfsr_s(stream), f[0].dataIn, (pix3*)f[0].halfOut, halfPitch, maxVal, dimX,
                        dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp, mfsr_cfa_packed(), bt);
     return mfsr_launch_status("prepareFrameFused");
 }
@@ -221,6 +262,13 @@ extern "C" int mfsr_prepareFrameFusedBatch(int nFrames, const mfsr_prepare_frame
                                            int pyr0Pitch, int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream)
 {
     return prepare_frames_impl(nFrames, frames, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch, taps, ntaps, stream);
+}
+
+// mfsr_prepareFrameFusedBatch whose halfOut receives the 3 x 3 patch means of the half-resolution image (k_prepareFrameFused<true>)
+extern "C" int mfsr_prepareFrameMeansBatch(int nFrames, const mfsr_prepare_frame* frames, int meansRowBytes, float maxVal, int w, int h,
+                                           int pyr0RowBytes, int pyr1RowBytes, const float* taps, int ntaps, mfsr_stream_t stream)
+{
+    return prepare_frames_impl(nFrames, frames, meansRowBytes, maxVal, w, h, pyr0RowBytes, pyr1RowBytes, taps, ntaps, stream, true);
 }
 
 // ---- A2: deBayerGreenKernel (DeBayerKernels.cu:55-149) ------------------------

@@ -374,6 +374,7 @@ struct mfsr_burst {
     bool denoiseOn;
     mfsr_denoise denoise;
     int denoisedFinishes;   // launches of mfsr_finishDenoised since mfsr_burst_begin (mfsr_burst_debug_denoised)
+    int robustGroupLaunches;  // launches of mfsr_robustnessMaskGroup since mfsr_burst_begin (mfsr_burst_debug_robust_group)
     // host staging of mfsr_burst_auto_render: the downloaded table and the tone table on its way to the device
     std::vector<uint64_t> autoStats;
     std::vector<float> autoLut;
@@ -611,6 +612,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->sharpenedFinishes = 0;
     b->denoiseOn = false;
     b->denoisedFinishes = 0;
+    b->robustGroupLaunches = 0;
     b->nUnp = 0;
     b->hostEpoch = 0;
     b->evEpoch = nullptr;
@@ -1583,6 +1585,10 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     int mq[MFSR_MAX_FUSE_GROUP], m = 0;  // batch positions of the moved (non-reference) frames
     for (int q = 0; q < n; q++)
         if (!b->pend.isRef[idx[q]]) mq[m++] = q;
+    // The masks of the group in one pass (mfsr_robustnessMaskGroup): the prepare launch then leaves the 3 x 3 patch MEANS of the
+    // half-resolution image in L.mov[q].half, which on this path only the mask kernel reads.  Decided once, here, for both launches.
+    const bool maskGroup = stageBatch && m > 0 && b->ntaps >= 3 && mfsr_robustness_group() != 0 &&
+                           mfsr_robustness_group_fits(L.hh, L.flowBuf[0].pitch, L.mov[0].half.pitch, L.maskBuf[0].pitch) != 0;
     if (stageBatch) {
         b->paths[MFSR_PATH_STAGE_BATCHES]++;
         for (int q = 0; q < n; q++) {
@@ -1606,8 +1612,9 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
                 pf[k].pyr0 = (float*)pyr[0].ptr;
                 pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
             }
-            TRY(mfsr_prepareFrameFusedBatch(m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
-                                            nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream));
+            TRY((maskGroup ? mfsr_prepareFrameMeansBatch : mfsr_prepareFrameFusedBatch)(
+                m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch, nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps,
+                b->ntaps, stream));
             b->paths[MFSR_PATH_PREPARE_BATCH]++;
             for (int k = 0; k < m; k++) {
                 const Img* pyr = L.mov[mq[k]].pyr;
@@ -1693,7 +1700,33 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     }
     // robustness masks (and, without the batch kernel, the iterations frame by frame)
     bool maskBatch = stageBatch && batched && m > 0;
-    if (maskBatch) {
+    if (maskGroup && !batched) {
+        // (cannot happen, as above: the frame-by-frame masks read the half-resolution images, so put them back)
+        mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
+        for (int k = 0; k < m; k++) {
+            const Img* pyr = L.mov[mq[k]].pyr;
+            pf[k].dataIn = b->pend.raw[idx[mq[k]]];
+            pf[k].halfOut = (mfsr_float3*)L.mov[mq[k]].half.ptr;
+            pf[k].pyr0 = (float*)pyr[0].ptr;
+            pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
+        }
+        TRY(mfsr_prepareFrameFusedBatch(m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
+                                        nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream));
+    }
+    if (maskBatch && maskGroup) {
+        mfsr_robustness_group_frame gf[MFSR_MAX_FUSE_GROUP];
+        for (int k = 0; k < m; k++) {
+            const int slot = b->pend.slot[idx[mq[k]]];
+            gf[k].movedMeans = (const mfsr_float3*)L.mov[mq[k]].half.ptr;
+            gf[k].movedRaw = b->pend.raw[idx[mq[k]]];
+            gf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
+            gf[k].flow = (const mfsr_float2*)final_flow(b, slot, 0)->ptr;
+        }
+        TRY(mfsr_robustnessMaskGroup(m, gf, (const mfsr_float3*)ref.half.ptr, ref.half.pitch, L.flowBuf[0].pitch, L.mov[0].half.pitch,
+                                     L.maskBuf[0].pitch, L.hw, L.hh, c.maxVal, c.alpha, c.beta, c.thresholdM, stream));
+        b->robustGroupLaunches++;
+        b->paths[MFSR_PATH_ROBUST_BATCH]++;
+    } else if (maskBatch) {
         mfsr_robustness_frame rf[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
             const int slot = b->pend.slot[idx[mq[k]]];
@@ -1709,15 +1742,15 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             return rc;
         else
             b->paths[MFSR_PATH_ROBUST_BATCH]++;
-        if (maskBatch && c.maskErode > 0) {  // one erosion launch for the whole group
-            const mfsr_float4* ein[MFSR_MAX_FUSE_GROUP];
-            mfsr_float4* eout[MFSR_MAX_FUSE_GROUP];
-            for (int k = 0; k < m; k++) {
-                ein[k] = (const mfsr_float4*)L.maskRaw[k].ptr;
-                eout[k] = (mfsr_float4*)L.maskBuf[b->pend.slot[idx[mq[k]]]].ptr;
-            }
-            TRY(mfsr_erodeMaskBatch(m, ein, eout, L.hw, L.hh, L.maskRaw[0].pitch, L.maskBuf[0].pitch, c.maskErode, stream));
+    }
+    if (maskBatch && c.maskErode > 0) {  // one erosion launch for the whole group
+        const mfsr_float4* ein[MFSR_MAX_FUSE_GROUP];
+        mfsr_float4* eout[MFSR_MAX_FUSE_GROUP];
+        for (int k = 0; k < m; k++) {
+            ein[k] = (const mfsr_float4*)L.maskRaw[k].ptr;
+            eout[k] = (mfsr_float4*)L.maskBuf[b->pend.slot[idx[mq[k]]]].ptr;
         }
+        TRY(mfsr_erodeMaskBatch(m, ein, eout, L.hw, L.hh, L.maskRaw[0].pitch, L.maskBuf[0].pitch, c.maskErode, stream));
     }
     for (int q = 0; q < n; q++) {
         const int i = idx[q], slot = b->pend.slot[i];
@@ -1998,6 +2031,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
     b->sharpenedFinishes = b->denoisedFinishes = 0;
+    b->robustGroupLaunches = 0;
     b->burstLaunches = b->burstGroups = 0;
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
@@ -2135,6 +2169,13 @@ extern "C" int mfsr_burst_debug_denoised(const mfsr_burst* b, int* finishes)
 {
     MFSR_REQUIRE(b && finishes);
     *finishes = b->denoisedFinishes;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_debug_robust_group(const mfsr_burst* b, int* launches)
+{
+    MFSR_REQUIRE(b && launches);
+    *launches = b->robustGroupLaunches;
     return MFSR_OK;
 }
 
@@ -3060,6 +3101,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     TRY(flush_pending(b, stream));
     memset(b->paths, 0, sizeof(b->paths));
     b->sharpenedFinishes = b->denoisedFinishes = 0;
+    b->robustGroupLaunches = 0;
     TRY(mfsr_burst_set_reference(b, frames[reference], stream));
 
     char* base = (char*)scratchDev;

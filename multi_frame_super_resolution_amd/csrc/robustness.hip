@@ -6,23 +6,10 @@
 // stay in VGPRs.  Quirk kept: of the 25 flow fetches only the last one
 // (x=2,y=2) can influence min/max (:62-72), so only that one is issued -- the
 // other 24 are dead in the reference too.
+#include <cstdlib>
 #include <cstring>
 #include "common.hpp"
-
-// x / 9 and x / 3 as reciprocal multiply + one fma correction (3 instructions instead of the ~11 of the
-// IEEE division expansion): q = x*r, q' = fma(fma(-d, q, x), r, q) with r = RN(1/d).  For d = 9 and
-// d = 3 this equals the correctly rounded quotient for EVERY finite float x, checked exhaustively over
-// all bit patterns on the host (it does not for 12 or sqrt(2), which keep the division).
-__device__ __forceinline__ float div9(float x)
-{
-    const float q = x * 0.111111112f;
-    return __builtin_fmaf(__builtin_fmaf(-9.0f, q, x), 0.111111112f, q);
-}
-__device__ __forceinline__ float div3(float x)
-{
-    const float q = x * 0.333333343f;
-    return __builtin_fmaf(__builtin_fmaf(-3.0f, q, x), 0.333333343f, q);
-}
+#include "half_pixel.hpp"
 
 __global__ void __launch_bounds__(256)
     k_ComputeRobustnessMask(const pix3* __restrict__ rawImgRef, const pix3* __restrict__ rawImgMoved,
@@ -269,6 +256,170 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
     *out = make_float4(m3[0], m3[1], m3[2], M);
 }
 
+// ---- the masks of a whole group in one pass --------------------------------------------------------------------------
+// k_robustnessFused<true> for the 1 .. 4 moved frames of a group in ONE pass over the reference (gridDim.z = 1), same bits:
+//  * everything that depends on the reference alone -- the patch means mr, the Wiener factor A = sd2 * rcp(sd2 + smd2) and
+//    Rg = rcp(max(smd2, sd2)) -- is computed once per pixel from the LDS tile and kept in nine registers across the frames
+//    (the fused kernel recomputes it per frame; 403 -> 166 VALU instructions per pixel and frame at four frames);
+//  * the moved side is ONE gather: the frame's image holds the 3 x 3 patch MEANS (k_prepareFrameFused<true>, debayer.hip:
+//    the very sum and division of k_robustnessFused), and mm at pixel p is the mean at q = p + round(0.5 * flow).  That holds
+//    for q inside the image.  For q outside, the fused kernel clamps each of the nine coordinates on its own (q = -1 reads
+//    column 0 three times), which is not the mean at clamp(q): under a wave-uniform ballot those lanes rebuild the nine
+//    pixels from the frame's raw samples (a1_pixel, half_pixel.hpp) and sum them as the fused kernel does;
+//  * the flow fetches of all frames are issued first, the gathers of all frames before the barrier: the two dependent
+//    round trips per frame overlap across the frames and with the staging of the reference.
+// Coordinates are formed modulo 2^32 (an infinite flow saturates round2i), as the fused kernel's adds behave on the hardware.
+struct RobustGroupFrame {
+    const pix3* means;
+    const uint16_t* raw;
+    float4* mask;
+    const float2* flow;
+};
+struct RobustGroupArgs {
+    RobustGroupFrame f[MFSR_BATCH_MAX];
+};
+__device__ __forceinline__ int rb_wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+
+#ifndef RB_GROUP_WAVES
+#define RB_GROUP_WAVES 8
+#endif
+template <int NF>
+__global__ void __launch_bounds__(RB_TX* RB_TY) __attribute__((amdgpu_waves_per_eu(RB_GROUP_WAVES, RB_GROUP_WAVES)))
+    k_robustnessGroup(const pix3* __restrict__ rawImgRef, RobustGroupArgs ga, int imgWidth, int imgHeight, int imgPitch, int flowPitch,
+                      int meansPitch, int maskPitch, float maxVal, int cfa, float alpha, float beta, float thresholdM, MfsrExactDiv dW,
+                      MfsrExactDiv dH)
+{
+    __shared__ float sR[3][RB_TY + 2][RB_TX + 2];
+    const int lx = threadIdx.x, ly = threadIdx.y;
+    const int x0 = blockIdx.x * RB_TX, y0 = blockIdx.y * RB_TY;
+    const int pxXe = min(x0 + lx, imgWidth - 1), pxYe = min(y0 + ly, imgHeight - 1);
+    // a frame's flow at this pixel (the bit-exact bilinear fetch) and the one live sample of the 5 x 5 loop; its patch mean
+    // under the rounded flow.  Two frames are in flight at a time (ten flow registers each while their loads are): the first
+    // two are fetched before the reference tile is staged and gathered before the barrier, the others are fetched before
+    // the barrier and gathered after it, ahead of the reference side.
+    // Every address is a frame's base pointer (uniform) plus a 32-bit byte offset that all frames share (the host checks
+    // that the images are below 2 GiB): no 64-bit address arithmetic per frame and texel.
+    float2 shiftf[NF], s[NF];
+    pix3 mm[NF];
+    const TexCoord tc = tex_coord<ADDR_CLAMP>(imgWidth, imgHeight, mfsr_div((float)pxXe + 0.5f, dW), mfsr_div((float)pxYe + 0.5f, dH));
+    const unsigned fr0 = (unsigned)tc.j0 * (unsigned)flowPitch, fr1 = (unsigned)tc.j1 * (unsigned)flowPitch;
+    const unsigned o00 = fr0 + 8u * (unsigned)tc.i0, o10 = fr0 + 8u * (unsigned)tc.i1, o01 = fr1 + 8u * (unsigned)tc.i0,
+                   o11 = fr1 + 8u * (unsigned)tc.i1;
+    const unsigned oS = (unsigned)min(pxYe + 2, imgHeight - 1) * (unsigned)flowPitch + 8u * (unsigned)min(pxXe + 2, imgWidth - 1);
+    auto fetch_flow = [&](int f) {
+        const char* base = (const char*)ga.f[f].flow;
+        const float2 t00 = *(const float2*)(base + o00), t10 = *(const float2*)(base + o10), t01 = *(const float2*)(base + o01),
+                     t11 = *(const float2*)(base + o11);
+        shiftf[f] = make_float2(lerp4(t00.x, t10.x, t01.x, t11.x, tc.a, tc.b), lerp4(t00.y, t10.y, t01.y, t11.y, tc.a, tc.b));  // tex2
+        s[f] = *(const float2*)(base + oS);
+    };
+    auto gather_mean = [&](int f) {
+        const int qx = rb_wrap_add(pxXe, round2i(shiftf[f].x * 0.5f)), qy = rb_wrap_add(pxYe, round2i(shiftf[f].y * 0.5f));
+        const unsigned o = (unsigned)clampi(qy, 0, imgHeight - 1) * (unsigned)meansPitch + 12u * (unsigned)clampi(qx, 0, imgWidth - 1);
+        mm[f] = *(const pix3*)((const char*)ga.f[f].means + o);
+    };
+#pragma unroll
+    for (int f = 0; f < NF && f < 2; f++) fetch_flow(f);
+    for (int t = ly * RB_TX + lx; t < (RB_TY + 2) * (RB_TX + 2); t += RB_TX * RB_TY) {
+        const int r = t / (RB_TX + 2), c = t - r * (RB_TX + 2);
+        const int gy = clampi(y0 - 1 + r, 0, imgHeight - 1), gx = clampi(x0 - 1 + c, 0, imgWidth - 1);
+        const pix3 p = row_ptr(rawImgRef, imgPitch, gy)[gx];
+        sR[0][r][c] = p.x;
+        sR[1][r][c] = p.y;
+        sR[2][r][c] = p.z;
+    }
+#pragma unroll
+    for (int f = 0; f < NF && f < 2; f++) gather_mean(f);
+#pragma unroll
+    for (int f = 2; f < NF; f++) fetch_flow(f);
+    __syncthreads();
+    const int pxX = x0 + lx, pxY = y0 + ly;
+    if (pxX >= imgWidth || pxY >= imgHeight) return;
+    const unsigned oM = (unsigned)pxY * (unsigned)maskPitch + 16u * (unsigned)pxX;
+    if (pxX < 1 || pxY < 1 || pxX >= imgWidth - 1 || pxY >= imgHeight - 1) {
+#pragma unroll
+        for (int f = 0; f < NF; f++) *(float4*)((char*)ga.f[f].mask + oM) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+#pragma unroll
+    for (int f = 2; f < NF; f++) gather_mean(f);
+    // the reference side, once: means in the reference's summation order (row-major from 0), exact division by 9
+    float mr[3], A[3], Rg[3];
+    int patch = ly * (RB_TX + 2) + lx;  // the patch's first element in a plane of sR
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float pr[9];
+        float m = 0.0f;
+#pragma unroll
+        for (int p = 0; p < 9; p++) {
+            pr[p] = (&sR[c][0][0])[patch + (p / 3) * (RB_TX + 2) + p % 3];
+            m += pr[p];
+        }
+        m = div9(m);
+        float sd2 = 0.0f;
+#pragma unroll
+        for (int p = 0; p < 9; p++) {
+            const float d = pr[p] - m;
+            sd2 = __builtin_fmaf(d, d, sd2);
+        }
+        sd2 = div9(sd2);                                  // variance of the reference patch
+        float smd2 = __builtin_fmaf(alpha, m, beta);      // noise model variance (green: / 2, :131)
+        if (c == 1) smd2 *= 0.5f;
+        mr[c] = m;
+        A[c] = sd2 * __builtin_amdgcn_rcpf(sd2 + smd2);   // Wiener shrink (:142-144)
+        Rg[c] = __builtin_amdgcn_rcpf(fmaxf(smd2, sd2));  // 1 / max(sigma_md, std)^2
+        // channel after channel -- nine patch registers live, not 27: the next channel's reads wait for this one's results
+        asm volatile("" : "+v"(patch) : "v"(mr[c]), "v"(A[c]), "v"(Rg[c]));
+    }
+#pragma unroll
+    for (int f = 0; f < NF; f++) {
+        const int shx = round2i(shiftf[f].x * 0.5f), shy = round2i(shiftf[f].y * 0.5f);
+        const int qx = rb_wrap_add(pxX, shx), qy = rb_wrap_add(pxY, shy);
+        const bool outside = (unsigned)qx >= (unsigned)imgWidth || (unsigned)qy >= (unsigned)imgHeight;
+        if (__ballot(outside) != 0) {
+            if (outside) {
+                // the nine individually clamped pixels, summed and divided as k_robustnessFused does
+                const float factor = 1.0f / maxVal;
+                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+                // (a rare path: rolled, so that its eighteen loads do not set the kernel's register count)
+#pragma unroll 1
+                for (int k = 0; k < 9; k++) {
+                    const int y = k / 3, x = k - 3 * y;
+                    const pix3 p = a1_pixel(ga.f[f].raw, imgWidth, clampi(rb_wrap_add(qx, x - 1), 0, imgWidth - 1),
+                                            clampi(rb_wrap_add(qy, y - 1), 0, imgHeight - 1), factor, cfa);
+                    a0 += p.x;
+                    a1 += p.y;
+                    a2 += p.z;
+                }
+                mm[f].x = div9(a0);
+                mm[f].y = div9(a1);
+                mm[f].z = div9(a2);
+            }
+        }
+        float2 maxShift, minShift;
+        maxShift.x = fmaxf(s[f].x, shiftf[f].x);
+        maxShift.y = fmaxf(s[f].y, shiftf[f].y);
+        minShift.x = fminf(s[f].x, shiftf[f].x);
+        minShift.y = fminf(s[f].y, shiftf[f].y);
+        const float mmc[3] = {mm[f].x, mm[f].y, mm[f].z};
+        float meandist = fabsf(mr[0] - mmc[0]) + fabsf(mr[1] - mmc[1]) + fabsf(mr[2] - mmc[2]);
+        meandist = div3(meandist);
+        const float hm = 0.5f * meandist;
+        const float ddx = maxShift.x * hm - minShift.x * hm, ddy = maxShift.y * hm - minShift.y * hm;
+        const float M = __builtin_amdgcn_sqrtf(ddx * ddx + ddy * ddy);
+        const float sc = (M > thresholdM) ? 0.0f : 1.5f;
+        float m3[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float d = fabsf(mr[c] - mmc[c]);
+            d = d * A[c];                                 // (0 * inf = NaN as in the reference)
+            const float e = __builtin_amdgcn_exp2f(-(d * d) * Rg[c] * 1.44269504088896340736f);
+            m3[c] = fmaxf(fminf(__builtin_fmaf(sc, e, -0.12f), 1.0f), 0.0f);
+        }
+        *(float4*)((char*)ga.f[f].mask + oM) = make_float4(m3[0], m3[1], m3[2], M);
+    }
+}
+
 // 0: the straight kernel (IEEE sqrt / division, ocml expf: tight parity tests); 1 (default): k_robustnessFused
 static int g_robustness_fast = 1;
 extern "C" int mfsr_set_robustness_fast(int enable)
@@ -339,6 +490,84 @@ extern "C" int mfsr_robustnessMaskFusedBatch(int nFrames, const mfsr_robustness_
         hipLaunchKernelGGL(k_robustnessFused<false>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, (const pix3*)frames[0].movedHalf,
                            (float4*)frames[0].mask, texUV, imgWidth, imgHeight, imgPitch, maskPitch, alpha, beta, thresholdM, bt, dW, dH);
     return mfsr_launch_status("robustnessMaskFusedBatch");
+}
+
+// 1 (default): the burst driver makes the masks of an aligned group with mfsr_prepareFrameMeansBatch + mfsr_robustnessMaskGroup;
+// 0 (mfsr_set_robustness_group / MFSR_ROBUST_GROUP=0): with mfsr_prepareFrameFusedBatch + mfsr_robustnessMaskFusedBatch (A/B)
+static int g_robustness_group = 1;
+static void robust_group_env_once()
+{
+    static const bool env_read = [] {
+        const char* e = getenv("MFSR_ROBUST_GROUP");
+        if (e && e[0] == '0') g_robustness_group = 0;
+        return true;
+    }();
+    (void)env_read;
+}
+extern "C" int mfsr_set_robustness_group(int enable)
+{
+    robust_group_env_once();  // (a later first query must not put the environment's value over this one)
+    g_robustness_group = enable ? 1 : 0;
+    return MFSR_OK;
+}
+int mfsr_robustness_group()
+{
+    robust_group_env_once();
+    return g_robustness_group && g_robustness_fast;
+}
+
+// the kernel addresses a frame's flow, patch-mean and mask images with 32-bit byte offsets
+int mfsr_robustness_group_fits(int h, int flowRowBytes, int meansRowBytes, int maskRowBytes)
+{
+    const long long lim = 1LL << 31;
+    return (long long)flowRowBytes * h < lim && (long long)meansRowBytes * h < lim && (long long)maskRowBytes * h < lim;
+}
+
+template <int NF>
+static void launch_robustness_group(dim3 grid, dim3 block, hipStream_t st, const pix3* ref, const RobustGroupArgs& ga, int w, int h,
+                                    int refRowBytes, int flowRowBytes, int meansRowBytes, int maskRowBytes, float maxVal, float alpha,
+                                    float beta, float thresholdM)
+{
+    hipLaunchKernelGGL(k_robustnessGroup<NF>, grid, block, 0, st, ref, ga, w, h, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes,
+                       maxVal, mfsr_cfa_packed(), alpha, beta, thresholdM, mfsr_exact_div((float)w), mfsr_exact_div((float)h));
+}
+
+// The masks of 1 .. 4 moved frames against one reference in one pass (k_robustnessGroup): bit-identical to
+// mfsr_robustnessMaskFusedBatch with a flow field of the image's resolution
+extern "C" int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf, int refRowBytes,
+                                        int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal, float alpha,
+                                        float beta, float thresholdM, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(frames && nFrames >= 1 && nFrames <= MFSR_BATCH_MAX && refHalf && w > 2 && h > 2);
+    MFSR_REQUIRE((long long)refRowBytes >= 12LL * w && (refRowBytes & 3) == 0);
+    MFSR_REQUIRE((long long)meansRowBytes >= 12LL * w && (meansRowBytes & 3) == 0);
+    MFSR_REQUIRE((long long)maskRowBytes >= 16LL * w && (maskRowBytes & 15) == 0);
+    MFSR_REQUIRE((long long)flowRowBytes >= 8LL * w && (flowRowBytes & 7) == 0);
+    MFSR_REQUIRE(((uintptr_t)refHalf & 3) == 0);
+    RobustGroupArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    for (int i = 0; i < nFrames; i++) {
+        MFSR_REQUIRE(frames[i].movedMeans && frames[i].movedRaw && frames[i].mask && frames[i].flow);
+        MFSR_REQUIRE(((uintptr_t)frames[i].mask & 15) == 0 && ((uintptr_t)frames[i].flow & 7) == 0);
+        MFSR_REQUIRE(((uintptr_t)frames[i].movedMeans & 3) == 0 && ((uintptr_t)frames[i].movedRaw & 3) == 0);
+        ga.f[i].means = (const pix3*)frames[i].movedMeans;
+        ga.f[i].raw = frames[i].movedRaw;
+        ga.f[i].mask = (float4*)frames[i].mask;
+        ga.f[i].flow = (const float2*)frames[i].flow;
+    }
+    if (!g_robustness_fast || !mfsr_robustness_group_fits(h, flowRowBytes, meansRowBytes, maskRowBytes)) return MFSR_E_UNSUPPORTED;
+    dim3 block(RB_TX, RB_TY), grid(mfsr_cdiv(w, RB_TX), mfsr_cdiv(h, RB_TY));
+    const pix3* ref = (const pix3*)refHalf;
+    hipStream_t st = mfsr_s(stream);
+#define RB_GROUP_ARGS grid, block, st, ref, ga, w, h, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes, maxVal, alpha, beta, thresholdM
+    switch (nFrames) {
+        case 1: launch_robustness_group<1>(RB_GROUP_ARGS); break;
+        case 2: launch_robustness_group<2>(RB_GROUP_ARGS); break;
+        case 3: launch_robustness_group<3>(RB_GROUP_ARGS); break;
+        default: launch_robustness_group<4>(RB_GROUP_ARGS); break;
+    }
+#undef RB_GROUP_ARGS
+    return mfsr_launch_status("robustnessMaskGroup");
 }
 
 extern "C" int mfsr_ComputeRobustnessMask(const mfsr_float3* rawImgRef, const mfsr_float3* rawImgMoved,

@@ -1081,6 +1081,13 @@ class BurstPipeline:
         self.L.burst_debug_denoised(self._h, ctypes.byref(n))
         return n.value
 
+    def robust_group_launches(self) -> int:
+        """Launches of mfsr_robustnessMaskGroup since ``begin_burst`` (mfsr_burst_debug_robust_group): one per aligned group
+        whose masks came from the patch-mean path, 0 after ``capi.lib().set_robustness_group(0)`` / MFSR_ROBUST_GROUP=0."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_robust_group(self._h, ctypes.byref(n))
+        return n.value
+
     def sharpened_finishes(self) -> int:
         """Launches of mfsr_finishSharpened since ``begin_burst`` (mfsr_burst_debug_sharpened): 1 for a resident burst, one per
         band for a host burst, 0 when sharpening is off."""
