@@ -166,6 +166,22 @@ int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfs
                                  mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
                                  mfsr_stream_t stream);
 
+/* mfsr_accumulateSuperResBurst followed by the plain uint16_t finish of the whole frame, without the finish pass: the tile
+ * launch finishes its pixels from the sums it still holds on chip and a small launch finishes the 16-pixel ring after the
+ * margin launch.  Both accumulators are written as by mfsr_accumulateSuperResBurst, and out16 (dense RGB, out16Width x
+ * out16Height = the accumulators' size, 8-byte aligned) is bit for bit what mfsr_finishFusedWindow with the same finish
+ * arguments writes from them.  The finish arguments are mfsr_finishFusedWindow's, the fallback image (float3) as a descriptor
+ * like the others (fallback.ptr may be NULL: no fallback).  The refusals of mfsr_accumulateSuperResBurst apply; in addition
+ * everything but the plain finish of the whole frame -- applyGamma != 0, maxOut != 65535, a window (colOffset, rowOffset != 0
+ * or out16Width, out16Height != fullWidth, fullHeight != the accumulators' size) -- returns MFSR_E_UNSUPPORTED.  A refusal
+ * touches nothing. */
+int mfsr_accumulateSuperResBurstFinish(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                       const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                       mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                       mfsr_tex2d fallback, float u0, float u1, float v0, float v1, float threshold,
+                                       uint16_t* out16, int out16Width, int out16Height, int applyGamma, float maxOut,
+                                       int colOffset, int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream);
+
 /* ---- B/E/H/I: kernel.cu --------------------------------------------------- */
 int mfsr_squaredSum(const float* inTiles, float* outValues, int maxShift, int tileSize, int tileCount,
                     mfsr_stream_t stream); /* :119 */
@@ -679,9 +695,18 @@ int mfsr_set_burst_fuse(int enable);
  * samples and certainty texels once per site (3 x 3 sites, 2 x 2 texels), tap weights once per pixel and workgroup; 0 = the
  * per-tap body (25 loads of each).  Both give the same accumulators bit for bit. */
 int mfsr_set_margin_sites(int enable);
+/* process-wide switch of the finish inside the burst launch for A/B (default 1; MFSR_FINISH_FUSE=0 in the environment):
+ * 0 = mfsr_burst_finish always runs its finish pass.  Both give the same image bit for bit. */
+int mfsr_set_finish_fuse(int enable);
+/* *finishes = the finishes this burst has taken inside its burst launch (mfsr_accumulateSuperResBurstFinish) since
+ * mfsr_burst_begin: host-side counter */
+int mfsr_burst_debug_finish_fused(const mfsr_burst* b, int* finishes);
 /* ApplyWeighting (+fallback) + optional gamma; outImg float3 HR (may be NULL),
  * out16 dense interleaved u16 HR (may be NULL).  Fuses whatever is still waiting first (mfsr_burst_flush), the groups of
- * the burst hold included. */
+ * the burst hold included.  Where the burst hold's launch is the burst's last fuse (8, 12 or 16 held frames and nothing
+ * after them) and the call asks for the plain whole-frame uint16_t image only (out16 without outImg, no gamma, render,
+ * sharpen, denoise or window), that launch writes out16 itself and no finish pass runs; the accumulators are written as
+ * ever.  With timing on, the events around that launch then include the finish. */
 int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
                       uint16_t* out16, mfsr_stream_t stream);
 /* finish restricted to HR rows [row0, row0+rows) (pointers are those of the
@@ -1493,7 +1518,8 @@ int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_
  * the events and returns the summed kernel milliseconds, the launch count and the
  * number of frames those launches fused (2 per launch with pairFrames).  A burst launch of the
  * burst hold (mfsr_burst_hold_fuse) counts as one launch per group it fused, so that
- * totalMs / launches stays the time per group of mfsr_burst_group_size frames. */
+ * totalMs / launches stays the time per group of mfsr_burst_group_size frames.  Where mfsr_burst_finish takes the finish
+ * inside that launch (see there), the events around it include the finish: the tile launch's epilogue and the ring launch. */
 int mfsr_burst_timing(mfsr_burst* b, int enable);
 int mfsr_burst_timing_read(mfsr_burst* b, double* totalMs, int* launches, int* frames);
 /* last per-frame flow field (tracking resolution, raw-pixel units) and mask,

@@ -125,7 +125,8 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
-                                       mfsr_stream_t stream);  // accumulate_fast.hip
+                                       const mfsr_float3* fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0,
+                                       float v1, float threshold, uint16_t* out16, mfsr_stream_t stream);  // accumulate_fast.hip
 
 static int check_superres_args(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                                const mfsr_float4* certaintyMask, const mfsr_tex2d& kernelParam, const mfsr_tex2d& shifts,
@@ -361,10 +362,12 @@ extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* 
 // tile kernel serves the geometry; MFSR_E_UNSUPPORTED (nothing touched) where it does not.  The images are described by
 // descriptors: imgOut / totalWeights float3 (scale*dimX) x (scale*dimY), certaintyMasks float4 at half the raw size (one
 // pitch for all), the raw frames dense uint16_t rows of dimX samples.
-extern "C" int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
-                                            const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
-                                            mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
-                                            mfsr_stream_t stream)
+// (out16 != null: the finishing form, mfsr_accumulateSuperResBurstFinish below, whose finish arguments have been checked)
+static int accumulate_burst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                            const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
+                            mfsr_float3 blackLevel, int scale, int accumulatorsUndefined, const mfsr_float3* fallback, int fbPitch,
+                            int fbW, int fbH, float u0, float u1, float v0, float v1, float threshold, uint16_t* out16,
+                            mfsr_stream_t stream)
 {
     MFSR_REQUIRE(dataIn && certaintyMasks && shifts);
     MFSR_REQUIRE(nFrames >= 2 * MFSR_MAX_FUSE_GROUP && nFrames <= MFSR_MAX_BURST_FUSE && (nFrames % MFSR_MAX_FUSE_GROUP) == 0);
@@ -384,7 +387,45 @@ extern "C" int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* 
     if (g_accumulate_fast != 2 || scale != 2) return MFSR_E_UNSUPPORTED;
     const int r = mfsr_try_launch_accumulate2x_burst(nFrames, dataIn, (mfsr_float3*)imgOut.ptr, (mfsr_float3*)totalWeights.ptr, masks,
                                                      kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY, imgOut.pitch,
-                                                     certaintyMasks[0].pitch, accumulatorsUndefined ? 1 : 0, stream);
-    if (r == 1) return mfsr_launch_status("accumulateSuperResBurst");
+                                                     certaintyMasks[0].pitch, accumulatorsUndefined ? 1 : 0, fallback, fbPitch, fbW,
+                                                     fbH, u0, u1, v0, v1, threshold, out16, stream);
+    if (r == 1) return mfsr_launch_status(out16 ? "accumulateSuperResBurstFinish" : "accumulateSuperResBurst");
     return r < 0 ? MFSR_E_INVALID : MFSR_E_UNSUPPORTED;
+}
+
+extern "C" int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                            const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                            mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                            mfsr_stream_t stream)
+{
+    return accumulate_burst(nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
+                            accumulatorsUndefined, nullptr, 0, 0, 0, 0.0f, 1.0f, 0.0f, 1.0f, 0.0f, nullptr, stream);
+}
+
+// The burst form with the plain uint16_t finish of the whole frame inside the launch (the finishing tile kernel and the ring
+// launch of accumulate_fast.hip): the accumulators as above, out16 bit for bit what mfsr_finishFusedWindow gives from them.
+// The finish arguments are validated as mfsr_finishFusedWindow validates them; what is not the plain whole-frame finish is
+// MFSR_E_UNSUPPORTED, and a refusal of either kind touches nothing.
+extern "C" int mfsr_accumulateSuperResBurstFinish(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut,
+                                                  mfsr_tex2d totalWeights, const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam,
+                                                  const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale,
+                                                  int accumulatorsUndefined, mfsr_tex2d fallback, float u0, float u1, float v0,
+                                                  float v1, float threshold, uint16_t* out16, int out16Width, int out16Height,
+                                                  int applyGamma, float maxOut, int colOffset, int rowOffset, int fullWidth,
+                                                  int fullHeight, mfsr_stream_t stream)
+{
+    const int width = out16Width, height = out16Height;
+    MFSR_REQUIRE(out16 && width > 0 && height > 0);
+    if (fallback.ptr)
+        MFSR_REQUIRE(fallback.width > 0 && fallback.height > 0 && (long long)fallback.pitch >= 12LL * fallback.width &&
+                     (fallback.pitch & 3) == 0);
+    MFSR_REQUIRE(maxOut > 0 && maxOut <= 65535.0f);
+    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + height);
+    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + width);
+    if (applyGamma || maxOut != 65535.0f || colOffset != 0 || rowOffset != 0 || width != fullWidth || height != fullHeight ||
+        width != imgOut.width || height != imgOut.height || ((uintptr_t)out16 & 7) != 0)
+        return MFSR_E_UNSUPPORTED;
+    return accumulate_burst(nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
+                            accumulatorsUndefined, (const mfsr_float3*)fallback.ptr, fallback.pitch, fallback.width, fallback.height, u0,
+                            u1, v0, v1, threshold, out16, stream);
 }

@@ -31,6 +31,8 @@
 #include <cstdlib>
 
 #include "accumulate_common.hpp"
+#include "finish_common.hpp"
+#include "finish_ring.hpp"
 #include <type_traits>
 
 namespace {
@@ -1402,11 +1404,25 @@ struct BurstFrames {
     TileFrame f[4 * TILE_BURST_GROUPS];
 };
 
-template <int CFA>
+// The finishing form (FIN): the launch is the burst's last fuse and the output is the plain uint16_t image, so each live lane
+// also finishes its own four pixels from the staged planes -- the arithmetic of k_finishFused without gamma, finish_common.hpp --
+// and the wave's 1 536 bytes of RGB leave through its own LDS row in memory order.  The finish pass over both plane-sets
+// (24 B read per pixel) is then not run; the ring is k_finishRing's.  A second instance, so that the form without it is the
+// kernel it was, instruction for instruction.
+template <bool FIN>
+struct TileFinish {
+};
+template <>
+struct TileFinish<true> {
+    FinishSrc src;    // the fallback image, its window, the threshold; the launch is the whole frame (offsets 0)
+    uint16_t* out16;  // dense RGB, hrW x hrH
+};
+
+template <int CFA, bool FIN = false>
 __global__ void __launch_bounds__(256, 3)
     k_accumulate2xTileBurst(BurstFrames fr, int nGroups, pix3* __restrict__ imgOut, pix3* __restrict__ totalWeights, mfsr_tex2d kernelParam,
                             Levels3 glv, StripLevels lv, int dimX, int dimY, int strideOut, int strideMask, int cfaPacked, int tilesX,
-                            int tilesY, int tilesPerXcd, int fresh)
+                            int tilesY, int tilesPerXcd, int fresh, TileFinish<FIN> fin)
 {
     constexpr int NF = 4, FC = TILE_COLS, FROWS = 3;
     const int tile = xcd_tile_index((int)blockIdx.x, tilesPerXcd);
@@ -1625,6 +1641,82 @@ __global__ void __launch_bounds__(256, 3)
     asm volatile("" : "+v"(Yw));
     seg.store(&sAcc[0][ly][0], (char*)imgOut + (size_t)Yw * strideOut + segByte, lx);
     seg.store(&sAcc[1][ly][0], (char*)totalWeights + (size_t)Yw * strideOut + segByte, lx);
+    if constexpr (FIN) {
+        // The lane's own 12 value and 12 weight floats (written by this lane or staged by this wave: no barrier), twelve
+        // independent divisions, then 24 bytes of RGB into the wave's own value row -- whose plane store has been issued and
+        // whose last reads are waited for -- so that the row leaves as whole chunks in memory order.
+        uint2* const row16 = (uint2*)&sAcc[0][ly][0];
+        if (stripLive) {
+            float v[12], w[12];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const float4 a = ((const float4*)myP)[j], c = ((const float4*)myW)[j];
+                v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+                w[4 * j] = c.x; w[4 * j + 1] = c.y; w[4 * j + 2] = c.z; w[4 * j + 3] = c.w;
+            }
+            uint32_t need = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (finish_needs_fallback(pix3{w[3 * k], w[3 * k + 1], w[3 * k + 2]}, fin.src)) need |= 1u << k;
+            pix3 fb[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) fb[k] = pix3{0.0f, 0.0f, 0.0f};
+            if (__builtin_amdgcn_ballot_w64(need != 0) != 0) {  // (wave-uniform: most waves resample nothing)
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if ((need >> k) & 1u) fb[k] = finish_fallback(X0 + k, Yw, fin.src);
+            }
+            uint16_t q[12];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const pix3 p = finish_weighted(fb[k], pix3{v[3 * k], v[3 * k + 1], v[3 * k + 2]}, pix3{w[3 * k], w[3 * k + 1], w[3 * k + 2]},
+                                               fin.src);
+                finish_quantize3(p, 65535.0f, &q[3 * k]);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane has its floats before the row is written over
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                row16[3 * lx + j] = make_uint2((uint32_t)q[4 * j] | ((uint32_t)q[4 * j + 1] << 16),
+                                               (uint32_t)q[4 * j + 2] | ((uint32_t)q[4 * j + 3] << 16));
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // the live bytes of the row: everything but the 16 ring pixels (96 bytes) at either end, a whole number of strips
+        const size_t rowB = (size_t)hrW * 6, segB = (size_t)bIdX * 1536;
+        char* const orow = (char*)fin.out16 + (size_t)Yw * rowB + segB;
+        if ((((uintptr_t)fin.out16 | rowB) & 15) == 0) {  // 16-byte chunks where every row starts on one (uniform)
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int c = j * 64 + lx;
+                const size_t gb = segB + (size_t)c * 16;
+                if (c < 96 && gb >= (size_t)STRIP_MARGIN * 6 && gb + 16 <= rowB - (size_t)STRIP_MARGIN * 6)
+                    *(uint4*)(orow + (size_t)c * 16) = ((const uint4*)row16)[c];
+            }
+        } else {  // rows that start on an odd multiple of 8 bytes (hrW = 4 (2 m + 1)): 8-byte chunks
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const int c = j * 64 + lx;
+                const size_t gb = segB + (size_t)c * 8;
+                if (gb >= (size_t)STRIP_MARGIN * 6 && gb + 8 <= rowB - (size_t)STRIP_MARGIN * 6) *(uint2*)(orow + (size_t)c * 8) = row16[c];
+            }
+        }
+    }
+}
+
+// The ring of the finishing burst launch: the STRIP_MARGIN pixels along every edge (the margin kernel's pixels and the outermost
+// line that nobody accumulates), finished from the accumulators after k_accumulateMarginBurst by the arithmetic of
+// k_finishFused (finish_common.hpp).  One thread per ring pixel in the order of finish_ring.hpp; with the tile kernel's
+// epilogue every HR pixel is written exactly once.
+__global__ void __launch_bounds__(256)
+    k_finishRing(const pix3* __restrict__ imgOut, const pix3* __restrict__ totalWeights, int strideOut, FinishSrc src,
+                 uint16_t* __restrict__ out16, int hrW, int hrH)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= finish_ring_count(hrW, hrH, STRIP_MARGIN)) return;
+    int x, y;
+    finish_ring_pixel(i, hrW, hrH, STRIP_MARGIN, x, y);
+    const pix3 val = row_ptr(imgOut, strideOut, y)[x];
+    const pix3 w = row_ptr(totalWeights, strideOut, y)[x];
+    finish_quantize3(finish_value(val, w, x, y, src), 65535.0f, out16 + ((size_t)y * hrW + x) * 3);
 }
 
 // The margin pixels of the same G groups in one launch: k_accumulateMarginN<4>'s workgroup (64 pixels x 4 frames, one thread
@@ -2424,7 +2516,8 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
-                                       mfsr_stream_t stream)
+                                       const mfsr_float3* fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0,
+                                       float v1, float threshold, uint16_t* out16, mfsr_stream_t stream)
 {
     read_env_once();
     if (nFrames < 8 || nFrames > 4 * TILE_BURST_GROUPS || (nFrames & 3)) return 0;
@@ -2450,13 +2543,19 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     BurstFrames fr;
     fill_frames(fr.f, dataIn, certaintyMask, shifts, nFrames);
     for (int n = nFrames; n < 4 * TILE_BURST_GROUPS; n++) fr.f[n] = fr.f[0];  // (never read: nGroups bounds the loop)
+    // the finishing form (out16): the whole frame's plain finish, the launch's pixel (0, 0) is the image's
+    const FinishSrc src{(const pix3*)fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, 0, hrH, 0, hrW};
     // monochrome and other patterns are not the burst kernel's: 0
     const int rc = for_cfa<false>(packed2, [&](auto cfaTag) {
         constexpr int CFA = decltype(cfaTag)::value;
         // fresh accumulators: the tile kernel writes every row outside the top and bottom margin bands, which are zeroed here
         if (fresh && zero_margin_bands(imgOut, totalWeights, hrH, strideOut, 0, hrH, wlc, st) != 0) return -1;
-        hipLaunchKernelGGL((k_accumulate2xTileBurst<CFA>), g1, block, 0, st, fr, nFrames / 4, pI, pT, kernelParam, glv, lv, dimX, dimY,
-                           strideOut, strideMask, cp, tilesX, tilesY, tilesPerXcd, fresh ? 1 : 0);
+        if (out16)
+            hipLaunchKernelGGL((k_accumulate2xTileBurst<CFA, true>), g1, block, 0, st, fr, nFrames / 4, pI, pT, kernelParam, glv, lv, dimX,
+                               dimY, strideOut, strideMask, cp, tilesX, tilesY, tilesPerXcd, fresh ? 1 : 0, TileFinish<true>{src, out16});
+        else
+            hipLaunchKernelGGL((k_accumulate2xTileBurst<CFA>), g1, block, 0, st, fr, nFrames / 4, pI, pT, kernelParam, glv, lv, dimX, dimY,
+                               strideOut, strideMask, cp, tilesX, tilesY, tilesPerXcd, fresh ? 1 : 0, TileFinish<false>{});
         return 1;
     });
     if (rc != 1) return rc;
@@ -2468,6 +2567,10 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     else
         hipLaunchKernelGGL((k_accumulateMarginBurst<2, false>), dim3(mfsr_cdiv(margin_pixel_count(hrW, hrH), 64)), dim3(64, 4), 0, st, fr,
                            nFrames / 4, pI, pT, kernelParam, glv, dimX, dimY, strideOut, strideMask, cp);
+    // the ring's finish, from the accumulators the margin launch has just completed
+    if (out16)
+        hipLaunchKernelGGL(k_finishRing, dim3((unsigned)mfsr_cdiv(finish_ring_count(hrW, hrH, STRIP_MARGIN), 256)), dim3(256), 0, st, pI, pT,
+                           strideOut, src, out16, hrW, hrH);
     return 1;
 }
 

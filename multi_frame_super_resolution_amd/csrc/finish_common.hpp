@@ -1,5 +1,6 @@
 // finish_common.hpp -- the pixel arithmetic of the burst's finish (stage H), shared by glue.hip (k_finishFused, k_quantize,
-// k_resampleFloat3), render.hip (k_finishRendered, k_renderImage) and image_stats.hip (k_imageStats): one definition, so that
+// k_resampleFloat3), render.hip (k_finishRendered, k_renderImage), image_stats.hip (k_imageStats) and accumulate_fast.hip (the
+// finishing burst tile kernel and k_finishRing, which write what k_finishFused writes): one definition, so that
 // the rendered finish holds the same value as the plain one before its gamma, quantises by the same rule, and is measured as
 // it is rendered.
 #pragma once
@@ -49,21 +50,50 @@ struct FinishSrc {
     int rowOffset, fullHeight, colOffset, fullWidth;
 };
 
-// The value section 2.19 calls p at pixel (x, y) of the launch: the body of k_finishFused up to its gamma, expression for
-// expression (a stripe or window is the crop of the whole).  val / w: the accumulator and the weight of the pixel.  One
-// definition for k_finishRendered (render.hip) and k_imageStats (image_stats.hip): what is measured is what is rendered.
-__device__ __forceinline__ pix3 finish_value(pix3 val, pix3 w, int x, int y, const FinishSrc& f)
+// The three pieces of finish_value (below), for the launches that take them apart (the finishing burst tile kernel,
+// accumulate_fast.hip, asks a whole wave whether any pixel needs the fallback before it resamples):
+// ApplyWeighting reads the fallback only where a weight is under the threshold (kernel.cu:444-462): the resample (12 loads, two
+// divisions, the bilinear mix: 40 % of the plain finish's instructions) is skipped by the waves that need none
+__device__ __forceinline__ bool finish_needs_fallback(pix3 w, const FinishSrc& f)
 {
-    pix3 inout = {0.0f, 0.0f, 0.0f};
-    if (f.fallback && (w.x < f.threshold || w.y < f.threshold || w.z < f.threshold)) {
-        const float u = f.u0 + (f.u1 - f.u0) * (((float)(x + f.colOffset) + 0.5f) / (float)f.fullWidth);
-        const float v = f.v0 + (f.v1 - f.v0) * (((float)(y + f.rowOffset) + 0.5f) / (float)f.fullHeight);
-        inout = sample_pix3(f.fallback, f.fbPitch, f.fbW, f.fbH, u, v);
-    }
+    return f.fallback && (w.x < f.threshold || w.y < f.threshold || w.z < f.threshold);
+}
+
+// Row y of a launch is row y + rowOffset of a fullHeight-row image (column x + colOffset of a fullWidth-column image likewise:
+// a window's finish): the same float expression as the whole-image launch evaluates for that pixel, so a stripe-wise or
+// window-wise finish is bit-identical to the whole one
+__device__ __forceinline__ pix3 finish_fallback(int x, int y, const FinishSrc& f)
+{
+    const float u = f.u0 + (f.u1 - f.u0) * (((float)(x + f.colOffset) + 0.5f) / (float)f.fullWidth);
+    const float v = f.v0 + (f.v1 - f.v0) * (((float)(y + f.rowOffset) + 0.5f) / (float)f.fullHeight);
+    return sample_pix3(f.fallback, f.fbPitch, f.fbW, f.fbH, u, v);
+}
+
+__device__ __forceinline__ pix3 finish_weighted(pix3 inout, pix3 val, pix3 w, const FinishSrc& f)
+{
     inout.x = apply_weight_f(inout.x, val.x, w.x, f.threshold);
     inout.y = apply_weight_f(inout.y, val.y, w.y, f.threshold);
     inout.z = apply_weight_f(inout.z, val.z, w.z, f.threshold);
     return inout;
+}
+
+// The value section 2.19 calls p at pixel (x, y) of the launch: the body of k_finishFused up to its gamma (a stripe or window is
+// the crop of the whole).  val / w: the accumulator and the weight of the pixel.  One definition for k_finishFused (glue.hip),
+// k_finishRendered (render.hip), k_imageStats (image_stats.hip) and k_finishRing (accumulate_fast.hip): what is measured is what
+// is rendered.  (The test is finish_needs_fallback's, spelled out: through the call k_finishFused came out as other code.)
+__device__ __forceinline__ pix3 finish_value(pix3 val, pix3 w, int x, int y, const FinishSrc& f)
+{
+    pix3 inout = {0.0f, 0.0f, 0.0f};
+    if (f.fallback && (w.x < f.threshold || w.y < f.threshold || w.z < f.threshold)) inout = finish_fallback(x, y, f);
+    return finish_weighted(inout, val, w, f);
+}
+
+// the plain uint16_t RGB of p: three samples of maxOut levels
+__device__ __forceinline__ void finish_quantize3(pix3 p, float maxOut, uint16_t* __restrict__ o)
+{
+    o[0] = (uint16_t)quantize1(p.x, maxOut);
+    o[1] = (uint16_t)quantize1(p.y, maxOut);
+    o[2] = (uint16_t)quantize1(p.z, maxOut);
 }
 
 __device__ __forceinline__ float gamma_f(float v)

@@ -551,20 +551,10 @@ __global__ void __launch_bounds__(256)
     if (x >= width || y >= height) return;
     const pix3 val = row_ptr(finalImg, imgPitch, y)[x];
     const pix3 w = row_ptr(weight, imgPitch, y)[x];
-    pix3 inout = {0.0f, 0.0f, 0.0f};
-    // ApplyWeighting reads the fallback only where a weight is under the threshold (kernel.cu:444-462): the resample (12
-    // loads, two divisions, the bilinear mix: 40 % of this kernel's instructions) is skipped by the waves that need none
-    if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
-        // (column x + colOffset of a fullWidth-column image likewise: a window's finish)
-        const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
-        // row y of this launch is row y + rowOffset of a fullHeight-row image: the same float expression as the whole-image
-        // launch evaluates for that row, so a stripe-wise finish is bit-identical to the whole one
-        const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
-        inout = sample_pix3(fallback, fbPitch, fbW, fbH, u, v);
-    }
-    inout.x = apply_weight_f(inout.x, val.x, w.x, threshold);
-    inout.y = apply_weight_f(inout.y, val.y, w.y, threshold);
-    inout.z = apply_weight_f(inout.z, val.z, w.z, threshold);
+    // the pixel arithmetic is finish_common.hpp's (one definition with the rendered finish, the statistics, the finishing burst
+    // tile kernel and the ring finish)
+    const FinishSrc src{fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset, fullWidth};
+    pix3 inout = finish_value(val, w, x, y, src);
     if (applyGamma) {
         inout.x = gamma_f(inout.x);
         inout.y = gamma_f(inout.y);

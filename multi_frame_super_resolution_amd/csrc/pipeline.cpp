@@ -375,6 +375,12 @@ struct mfsr_burst {
     mfsr_denoise denoise;
     int denoisedFinishes;   // launches of mfsr_finishDenoised since mfsr_burst_begin (mfsr_burst_debug_denoised)
     int robustGroupLaunches;  // launches of mfsr_robustnessMaskGroup since mfsr_burst_begin (mfsr_burst_debug_robust_group)
+    // The finish inside the burst launch (mfsr_accumulateSuperResBurstFinish): mfsr_burst_finish sets finishOut16 before it
+    // flushes when the hold's launch is the burst's last fuse and the plain whole-frame uint16_t image is all it was asked for;
+    // fuse_hold then issues the finishing launch and sets finishTaken, or launches as ever where the entry refuses.
+    uint16_t* finishOut16;
+    bool finishTaken;
+    int fusedFinishes;  // finishes taken that way since mfsr_burst_begin (mfsr_burst_debug_finish_fused)
     // host staging of mfsr_burst_auto_render: the downloaded table and the tone table on its way to the device
     std::vector<uint64_t> autoStats;
     std::vector<float> autoLut;
@@ -613,6 +619,9 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->denoiseOn = false;
     b->denoisedFinishes = 0;
     b->robustGroupLaunches = 0;
+    b->finishOut16 = nullptr;
+    b->finishTaken = false;
+    b->fusedFinishes = 0;
     b->nUnp = 0;
     b->hostEpoch = 0;
     b->evEpoch = nullptr;
@@ -1101,6 +1110,28 @@ extern "C" int mfsr_set_burst_fuse(int enable)
     g_burst_fuse = enable ? 1 : 0;
     return MFSR_OK;
 }
+// Process-wide switch of the finish inside the burst launch for A/B (mfsr_set_finish_fuse; MFSR_FINISH_FUSE=0 in the
+// environment): off, mfsr_burst_finish always runs its finish pass.
+static int g_finish_fuse = -1;
+static bool finish_fuse_enabled()
+{
+    if (g_finish_fuse < 0) {
+        const char* e = getenv("MFSR_FINISH_FUSE");
+        g_finish_fuse = (e && e[0] == '0') ? 0 : 1;
+    }
+    return g_finish_fuse == 1;
+}
+extern "C" int mfsr_set_finish_fuse(int enable)
+{
+    g_finish_fuse = enable ? 1 : 0;
+    return MFSR_OK;
+}
+extern "C" int mfsr_burst_debug_finish_fused(const mfsr_burst* b, int* finishes)
+{
+    MFSR_REQUIRE(b && finishes);
+    *finishes = b->fusedFinishes;
+    return MFSR_OK;
+}
 extern "C" int mfsr_burst_hold_fuse(mfsr_burst* b, int enable)
 {
     MFSR_REQUIRE(b != nullptr);
@@ -1172,8 +1203,27 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
         }
         const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
         const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
-        rc = mfsr_accumulateSuperResBurst(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
-                                          c.scale, freshNow, stream);
+        // the burst's last fuse and a plain uint16_t finish waiting behind it (mfsr_burst_finish): the launch finishes as well
+        uint16_t* const out16 = b->finishOut16;
+        b->finishOut16 = nullptr;
+        rc = MFSR_E_UNSUPPORTED;
+        if (out16) {
+            mfsr_tex2d fb;  // as mfsr_burst_finish hands it to mfsr_finishFused: the LR image at its pitch
+            fb.ptr = L.fallback.ptr;
+            fb.pitch = L.fallback.pitch;
+            fb.width = L.W;
+            fb.height = L.H;
+            rc = mfsr_accumulateSuperResBurstFinish(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white,
+                                                    black, c.scale, freshNow, fb, 0.0f, 1.0f, 0.0f, 1.0f, c.weightThreshold, out16,
+                                                    L.hrW, L.hrH, 0, 65535.0f, 0, 0, L.hrW, L.hrH, stream);
+            if (rc == MFSR_OK) {
+                b->finishTaken = true;
+                b->fusedFinishes++;
+            }
+        }
+        if (rc == MFSR_E_UNSUPPORTED)
+            rc = mfsr_accumulateSuperResBurst(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
+                                              c.scale, freshNow, stream);
         if (rc == MFSR_OK) {
             if (b->fresh.has && !freshNow) {
                 // begin(A, W) followed by a fuse into other accumulators: A and W still owe their zeroes
@@ -2032,6 +2082,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     memset(b->paths, 0, sizeof(b->paths));
     b->sharpenedFinishes = b->denoisedFinishes = 0;
     b->robustGroupLaunches = 0;
+    b->fusedFinishes = 0;
     b->burstLaunches = b->burstGroups = 0;
     b->fresh.has = true;
     b->fresh.imgOut = imgOut;
@@ -2312,9 +2363,23 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
 {
     MFSR_REQUIRE(b && imgOut && totalWeights && (outImg || out16));
     MFSR_REQUIRE(b->haveRef);
-    TRY(flush_pending(b, stream));
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
+    // The finish inside the burst launch: only the plain whole-frame uint16_t image, and only where the hold's launch (two or
+    // more groups on these accumulators) is the burst's last fuse -- nothing waits behind it (with 9 frames the ninth is fused
+    // after the burst launch, which then must not finish).  fuse_hold decides the rest (the entry's own refusals).
+    b->finishTaken = false;
+    b->finishOut16 = nullptr;
+    if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->win.on && out16 && !outImg && !c.applyGamma &&
+        b->nHold >= 2 && b->pend.n == 0 && !b->heldHas && b->hold[0].imgOut == imgOut && b->hold[0].totalWeights == totalWeights)
+        b->finishOut16 = out16;
+    const int rcFlush = flush_pending(b, stream);
+    b->finishOut16 = nullptr;
+    if (rcFlush != MFSR_OK) return rcFlush;
+    if (b->finishTaken) {
+        b->finishTaken = false;
+        return MFSR_OK;
+    }
     const int pitch = 12 * out_w(b);
     // cfg.fused = 0 too: the stencil cannot run in place on the chain's in/out image, and the value the fused finish holds
     // before its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting (tests/test_parity_kernels.py::
@@ -3102,6 +3167,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     memset(b->paths, 0, sizeof(b->paths));
     b->sharpenedFinishes = b->denoisedFinishes = 0;
     b->robustGroupLaunches = 0;
+    b->fusedFinishes = 0;
     TRY(mfsr_burst_set_reference(b, frames[reference], stream));
 
     char* base = (char*)scratchDev;

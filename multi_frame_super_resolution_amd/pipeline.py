@@ -1088,6 +1088,14 @@ class BurstPipeline:
         self.L.burst_debug_robust_group(self._h, ctypes.byref(n))
         return n.value
 
+    def fused_finishes(self) -> int:
+        """Finishes taken inside the burst launch since ``begin_burst`` (mfsr_burst_debug_finish_fused): 1 where ``finish``
+        asked for the plain whole-frame uint16 image only and the hold's 8, 12 or 16 frames were the burst's last fuse, else 0
+        (also after ``capi.lib().set_finish_fuse(0)`` / MFSR_FINISH_FUSE=0)."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_finish_fused(self._h, ctypes.byref(n))
+        return n.value
+
     def sharpened_finishes(self) -> int:
         """Launches of mfsr_finishSharpened since ``begin_burst`` (mfsr_burst_debug_sharpened): 1 for a resident burst, one per
         band for a host burst, 0 when sharpening is off."""
