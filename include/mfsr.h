@@ -544,6 +544,11 @@ typedef struct {
 int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* frames, const float* refImg, int pitchShift, int pitchImg,
                                int pitchSD, int width, int height, int halfWindowSize, float minDet, float outScale,
                                mfsr_stream_t stream);
+/* The band height, in rows, that mfsr_lucasKanadeSweepBatch gives each wavefront at this geometry (the launcher calls this very
+ * function; MFSR_LK_BAND=rows in the environment, >= 8, overrides the rule), or 0 where that entry point refuses the geometry
+ * (half window outside 1..7, width < 64, height < 2 (halfWindowSize + 2), nFrames outside 1..4).  Host arithmetic, no GPU call.
+ * A pixel's flow and warped planes do not depend on the band it falls in: bit-identical at every band height. */
+int mfsr_lucasKanadeSweepBand(int width, int height, int halfWindowSize, int nFrames);
 /* D1 (mfsr_CreateFlowFieldFromTiles; base != NULL: mfsr_CreateFlowFieldFromTilesBase) + the warp of every pixel under the flow
  * it writes: outImg and the first iteration's sumIn / diffIn in one launch (opticalFlow.cu:48 + :28) */
 int mfsr_CreateFlowFieldWarped(mfsr_float2* outImg, mfsr_tex2d texObjShiftXY, int imgWidth, int imgHeight, int imgPitch,

@@ -295,7 +295,7 @@ class _Lib:
         ret = self.protos[full][0]
         if ret != "int" or full in ("mfsr_version", "mfsr_device_count", "mfsr_gaussin_filter_1D", "mfsr_burst_group_size",
                                      "mfsr_trackTilesFastSupported", "mfsr_packed_row_bytes", "mfsr_render_row_bytes",
-                                     "mfsr_get_accumulate_fast_exp"):
+                                     "mfsr_get_accumulate_fast_exp", "mfsr_exactDivisionOk", "mfsr_lucasKanadeSweepBand"):
             return raw
 
         def checked(*a):

@@ -662,14 +662,18 @@ extern "C" int mfsr_checkFlowBound(const mfsr_float2* flow, int pitch, int width
 
 // ---- mfsr_exact_div (common.hpp) -----------------------------------------------------------------------------------------
 #include <mutex>
+#include <unordered_map>
 MfsrExactDiv mfsr_exact_div(float d)
 {
     static std::mutex mu;
-    static MfsrExactDiv cache[32];
-    static int nCache = 0;
+    // every divisor asked for so far, by its bit pattern: a process meets as many as it has image widths and heights, and a
+    // miss costs the 2^23-step proof below
+    static std::unordered_map<uint32_t, MfsrExactDiv> cache;
+    uint32_t key;
+    memcpy(&key, &d, 4);
     std::lock_guard<std::mutex> lk(mu);
-    for (int i = 0; i < nCache; i++)
-        if (cache[i].d == d) return cache[i];
+    const auto hit = cache.find(key);
+    if (hit != cache.end()) return hit->second;
     MfsrExactDiv e{d, 1.0f / d, 0};
     static const bool off = [] {
         const char* v = getenv("MFSR_EXACT_DIV");
@@ -687,7 +691,7 @@ MfsrExactDiv mfsr_exact_div(float d)
         }
         e.ok = ok ? 1 : 0;
     }
-    if (nCache < 32) cache[nCache++] = e;
+    cache.emplace(key, e);
     return e;
 }
 

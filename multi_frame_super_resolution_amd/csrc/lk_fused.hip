@@ -749,27 +749,12 @@ __global__ void __launch_bounds__(64)
     if (F.sumOut) finish_pending();
 }
 
-extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* frames, const float* refImg, int pitchShift, int pitchImg,
-                                          int pitchSD, int width, int height, int halfWindowSize, float minDet, float outScale,
-                                          mfsr_stream_t stream)
+// The band height of a sweep launch, in rows: the launcher's only source of it (include/mfsr.h: mfsr_lucasKanadeSweepBand).
+// 0 where mfsr_lucasKanadeSweepBatch refuses the geometry.  Host arithmetic only.
+extern "C" int mfsr_lucasKanadeSweepBand(int width, int height, int halfWindowSize, int nFrames)
 {
-    MFSR_REQUIRE(frames && refImg && nFrames >= 1 && nFrames <= MFSR_LK_SWEEP_MAX_BATCH);
-    if (halfWindowSize < 1 || halfWindowSize > 7 || width < 64 || height < 2 * (halfWindowSize + 2)) return MFSR_E_UNSUPPORTED;
-    MFSR_REQUIRE((long long)pitchShift >= 8LL * width && (pitchShift & 7) == 0);
-    MFSR_REQUIRE((long long)pitchImg >= 4LL * width && (pitchImg & 3) == 0 && (long long)pitchSD >= 4LL * width && (pitchSD & 3) == 0);
-    // (32-bit byte offsets inside every image, lk_at)
-    if ((long long)pitchShift * height >= (1LL << 32) || (long long)pitchImg * height >= (1LL << 32) || (long long)pitchSD * height >= (1LL << 32))
-        return MFSR_E_UNSUPPORTED;
-    LkSweepBatch b;
-    memset(&b, 0, sizeof(b));
-    for (int i = 0; i < nFrames; i++) {
-        const mfsr_lk_frame& f = frames[i];
-        MFSR_REQUIRE(f.shiftsIn && f.shiftsOut && f.shiftsIn != f.shiftsOut && f.movedImg && f.sumIn && f.diffIn);
-        MFSR_REQUIRE(((uintptr_t)f.shiftsIn & 7) == 0 && ((uintptr_t)f.shiftsOut & 7) == 0);
-        MFSR_REQUIRE((f.sumOut != nullptr) == (f.diffOut != nullptr) && f.sumOut != f.sumIn && f.diffOut != f.diffIn);
-        MFSR_REQUIRE(!f.sumOut || outScale == 1.0f);  // the flow a next iteration reads is in tracking pixels
-        b.f[i] = LkSweepFrame{(const float2*)f.shiftsIn, (float2*)f.shiftsOut, f.movedImg, f.sumIn, f.diffIn, f.sumOut, f.diffOut};
-    }
+    if (nFrames < 1 || nFrames > MFSR_LK_SWEEP_MAX_BATCH) return 0;
+    if (halfWindowSize < 1 || halfWindowSize > 7 || width < 64 || height < 2 * (halfWindowSize + 2)) return 0;
     const int h = halfWindowSize, VW = 64 - 2 * (h + 2);
     const int strips = mfsr_cdiv(width, VW);
     // band height: enough wavefronts to fill 1024 SIMDs a few times over without paying too many halo rows
@@ -798,6 +783,33 @@ extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* fram
         }
     }
     if (forceBand >= 8) band = forceBand;
+    return band;
+}
+
+extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* frames, const float* refImg, int pitchShift, int pitchImg,
+                                          int pitchSD, int width, int height, int halfWindowSize, float minDet, float outScale,
+                                          mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(frames && refImg && nFrames >= 1 && nFrames <= MFSR_LK_SWEEP_MAX_BATCH);
+    if (halfWindowSize < 1 || halfWindowSize > 7 || width < 64 || height < 2 * (halfWindowSize + 2)) return MFSR_E_UNSUPPORTED;
+    MFSR_REQUIRE((long long)pitchShift >= 8LL * width && (pitchShift & 7) == 0);
+    MFSR_REQUIRE((long long)pitchImg >= 4LL * width && (pitchImg & 3) == 0 && (long long)pitchSD >= 4LL * width && (pitchSD & 3) == 0);
+    // (32-bit byte offsets inside every image, lk_at)
+    if ((long long)pitchShift * height >= (1LL << 32) || (long long)pitchImg * height >= (1LL << 32) || (long long)pitchSD * height >= (1LL << 32))
+        return MFSR_E_UNSUPPORTED;
+    LkSweepBatch b;
+    memset(&b, 0, sizeof(b));
+    for (int i = 0; i < nFrames; i++) {
+        const mfsr_lk_frame& f = frames[i];
+        MFSR_REQUIRE(f.shiftsIn && f.shiftsOut && f.shiftsIn != f.shiftsOut && f.movedImg && f.sumIn && f.diffIn);
+        MFSR_REQUIRE(((uintptr_t)f.shiftsIn & 7) == 0 && ((uintptr_t)f.shiftsOut & 7) == 0);
+        MFSR_REQUIRE((f.sumOut != nullptr) == (f.diffOut != nullptr) && f.sumOut != f.sumIn && f.diffOut != f.diffIn);
+        MFSR_REQUIRE(!f.sumOut || outScale == 1.0f);  // the flow a next iteration reads is in tracking pixels
+        b.f[i] = LkSweepFrame{(const float2*)f.shiftsIn, (float2*)f.shiftsOut, f.movedImg, f.sumIn, f.diffIn, f.sumOut, f.diffOut};
+    }
+    const int h = halfWindowSize, VW = 64 - 2 * (h + 2);
+    const int strips = mfsr_cdiv(width, VW);
+    const int band = mfsr_lucasKanadeSweepBand(width, height, h, nFrames);
     static const int xcdRemap = [] {
         const char* e = getenv("MFSR_LK_XCD");
         return e ? atoi(e) : 1;
@@ -805,7 +817,8 @@ extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* fram
     const int bands = mfsr_cdiv(height, band);
     const int total = strips * bands * nFrames;
     const int perXcd = xcdRemap ? mfsr_cdiv(total, 8) : 0;
-    // (remapped: a 1-D grid of 8 * perXcd workgroups whose .z still carries the frame count for the kernel's bound check)
+    // (remapped: a 1-D grid of 8 * perXcd workgroups; the frame count reaches the kernel as nFramesLaunch, and the up to seven
+    // surplus workgroups return at its `t >= strips * bands * nFramesLaunch` check)
     dim3 grid = perXcd ? dim3(8 * perXcd, 1, 1) : dim3(strips, bands, nFrames), block(64);
     const MfsrExactDiv dW = mfsr_exact_div((float)width), dH = mfsr_exact_div((float)height);
 #define LKS_CASE(HT)                                                                                                          \

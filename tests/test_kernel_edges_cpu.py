@@ -41,7 +41,6 @@ EXCLUDED = {
     "mfsr_CreateFlowFieldFromTilesBase": "device-prealign form, bit-compared in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",
     "mfsr_CreateFlowFieldWarped": "bit-compared with the swept chain in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",
     "mfsr_lucasKanadeIterationWarped": "bit-compared with mfsr_lucasKanadeIterationFused in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",
-    "mfsr_lucasKanadeSweepBatch": "ragged strips and bands against the oracle chain in test_parity_kernels.py::test_lucasKanadeSweepBatch_vs_oracle_chain",
     "mfsr_prepareFrameFusedBatch": BATCH,
     "mfsr_CreateFlowFieldWarpedBatch": BATCH,
     "mfsr_robustnessMaskFusedBatch": BATCH,
@@ -57,6 +56,7 @@ EXCLUDED = {
     # drivers and host functions
     "mfsr_config_default": "host function: fills a configuration",
     "mfsr_window_check": "host function: argument check",
+    "mfsr_lucasKanadeSweepBand": "host function: the sweep's band rule, values pinned in tests/test_lk_band_cpu.py",
     "mfsr_burst_set_window": PIPELINE,
     "mfsr_burst_get_window": PIPELINE,
     "mfsr_burst_align_frame": PIPELINE,

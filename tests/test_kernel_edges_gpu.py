@@ -435,6 +435,20 @@ def c_lkFused(orc, hip, w, h, first):
     assert_bitexact(got[:hw], flow0[:hw], "ring rows")
 
 
+# h = 3: strips of VW = 54 columns, bands of 8 rows.  The minimum (width 64, height 2 (h + 2)), then VW - 1 / VW / VW + 1 columns of a
+# second strip crossed with band - 1 / band / band + 1 rows of a second band, and two odd sizes
+LKS = [(64, 10), (64, 11), (107, 15), (108, 16), (109, 17), (131, 11), (163, 35)]
+
+
+@case("lucasKanadeSweepBatch", shp=LKS)
+def c_lkSweep(orc, hip, w, h, first):
+    # the guarded harness of the sweep's own module (three different padded pitches, every buffer between guards), one frame and
+    # three: one iteration against the oracle at c_lkFused's tolerance, ring rows and columns and both warped planes bit for bit
+    from tests.test_lk_sweep_gpu import conditioned_case, one_iteration_against_the_oracle
+    for nf in (1, 3) if first else (1 + (w + h) % 4,):
+        one_iteration_against_the_oracle(orc, hip, conditioned_case(orc, 3, w, h, nf, 90 + w), f"lucasKanadeSweepBatch h=3 {w}x{h} x{nf}")
+
+
 # ---------------------------------------------------------------- structure tensor / kernel parameters
 @case("ComputeStructureTensor", "ComputeKernelParam")
 def c_tensor(orc, hip, w, h, first):
@@ -702,11 +716,14 @@ class DevBufs:
                 buf.reshape(-1).view(np.uint8)[...] = t.cpu().numpy().reshape(-1).view(np.uint8)
 
 
-def _pad2d(a, fill, align=None, rows_around=0):
-    """-> (byte buffer [rows_around + H + rows_around, pitch], pitch, row bytes): ``a`` with padded rows, ``fill`` elsewhere."""
+def _pad2d(a, fill, align=None, rows_around=0, pitch=None):
+    """-> (byte buffer [rows_around + H + rows_around, pitch], pitch, row bytes): ``a`` with padded rows, ``fill`` elsewhere.
+    ``pitch``: a caller's own padded pitch (tests/test_lk_sweep_gpu.py: three different ones) instead of ``padded_pitch``'s."""
     a = np.ascontiguousarray(a)
     rowb = a.strides[0]
-    pitch = padded_pitch(rowb, align or texel_align(a))
+    if pitch is None:
+        pitch = padded_pitch(rowb, align or texel_align(a))
+    assert pitch > rowb
     buf = np.full((a.shape[0] + 2 * rows_around, pitch), fill, np.uint8)
     buf[rows_around:rows_around + a.shape[0], :rowb] = a.view(np.uint8).reshape(a.shape[0], rowb)
     return buf, pitch, rowb
