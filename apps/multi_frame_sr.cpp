@@ -36,6 +36,9 @@
 //     value), with or without MFSR_CCM; one GPU only.
 //   * MFSR_DENOISE="strength[,radius[,gain]]" denoises _sr_result inside the finish (a range filter whose tolerance follows the
 //     accumulated weight), with or without MFSR_CCM; not with MFSR_SHARPEN; one GPU only.
+//   * MFSR_LOCAL_TONE="shadows[,highlights[,cell[,bins]]]" lifts the shadows of _sr_result locally inside the finish (a bilateral
+//     grid of gains measured on the merged image), with or without MFSR_CCM and MFSR_AUTO; it prints
+//     `local tone: cell C bins N pivot P gains LO .. HI` on stderr; not with MFSR_SHARPEN or MFSR_DENOISE; one GPU only.
 //   * MFSR_AUTO=wb|tone|wb,tone measures white-balance gains and / or a tone table on the merged image and renders _sr_result
 //     with them, with or without MFSR_CCM and MFSR_SHARPEN; it prints `auto: gains R G B ... black K
 //     white W gamma G ...` to stderr; one GPU only.
@@ -422,7 +425,52 @@ int main(int argc, char** argv)
         render.format = MFSR_OUT_RGB8;
     }
     const bool autoOn = autoWb || autoTone;
-    const bool rendered = ccm || sharpenOn || denoiseOn || autoOn;  // the 8-bit image comes out of the finish launch
+    // MFSR_LOCAL_TONE="shadows[,highlights[,cell[,bins]]]": local tone mapping inside the finish (mfsr_burst_local_tone, DESIGN.md
+    // section 2.25): a bilateral grid of gains measured on the merged image, after MFSR_AUTO's measurement and with its matrix,
+    // lifts shadows locally (highlights 0.25, the cell chosen from the frame, 16 bins by default).  The 8-bit image then comes
+    // out of the rendered finish, as with MFSR_CCM.
+    bool localToneOn = false;
+    float localToneV[4] = {0.0f, 0.25f, 0.0f, 16.0f};  // shadows, highlights, cell (0 = default), bins
+    if (const char* e = getenv("MFSR_LOCAL_TONE")) {
+        const char* p = e;
+        bool ok = true;
+        for (int n = 0; ok; n++) {
+            char* end = nullptr;
+            localToneV[n] = strtof(p, &end);
+            ok = end != p && std::isfinite(localToneV[n]);
+            p = end;
+            if (!ok || *p == '\0') break;
+            ok = *p == ',' && n < 3;
+            p++;
+        }
+        mfsr_local_tone probe;
+        ok = ok && *p == '\0' && localToneV[2] == (float)(int)localToneV[2] && localToneV[3] == (float)(int)localToneV[3] &&
+             mfsr_local_tone_defaults(16, 16, &probe) == MFSR_OK;
+        if (ok) {
+            probe.shadows = localToneV[0];
+            probe.highlights = localToneV[1];
+            if (localToneV[2] != 0.0f) probe.cell = (int)localToneV[2];
+            probe.bins = (int)localToneV[3];
+            ok = mfsr_local_tone_validate(&probe) == MFSR_OK;
+        }
+        if (!ok) {
+            fprintf(stderr, "MFSR_LOCAL_TONE=%s: shadows[,highlights[,cell[,bins]]] expected: shadows and highlights in [0, 1], cell a "
+                            "power of two 16..512 (0 = chosen from the frame), bins 4, 8, 16 or 32\n", e);
+            return 1;
+        }
+        localToneOn = true;
+        render.format = MFSR_OUT_RGB8;
+    }
+    if (localToneOn && (sharpenOn || denoiseOn)) {
+        fprintf(stderr, "MFSR_LOCAL_TONE is not supported with %s (the local-tone finish is pointwise: DESIGN.md section 2.25)\n",
+                sharpenOn ? "MFSR_SHARPEN" : "MFSR_DENOISE");
+        return 1;
+    }
+    if (localToneOn && gpus > 1) {
+        fprintf(stderr, "MFSR_LOCAL_TONE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
+    const bool rendered = ccm || sharpenOn || denoiseOn || autoOn || localToneOn;  // the 8-bit image comes out of the finish launch
     if (denoiseOn && gpus > 1) {
         fprintf(stderr, "MFSR_DENOISE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
@@ -682,6 +730,23 @@ int main(int argc, char** argv)
         HIP_OK(hipMalloc((void**)&dstats, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS));
         HIP_OK(hipMalloc((void**)&dlut, sizeof(float) * ((size_t)autoParams.toneSize + 1)));
     }
+    // MFSR_LOCAL_TONE: the description for this frame, the statistics table and the grid (device memory of the caller's)
+    mfsr_local_tone localTone;
+    mfsr_local_tone_result localToneResult;
+    memset(&localToneResult, 0, sizeof(localToneResult));
+    uint64_t* dtoneStats = nullptr;
+    float* dtoneGrid = nullptr;
+    if (localToneOn) {
+        MFSR_OK_OR_DIE(mfsr_local_tone_defaults(hrW, hrH, &localTone));
+        localTone.shadows = localToneV[0];
+        localTone.highlights = localToneV[1];
+        if (localToneV[2] != 0.0f) localTone.cell = (int)localToneV[2];
+        localTone.bins = (int)localToneV[3];
+        int gx = 0, gy = 0, gz = 0;
+        MFSR_OK_OR_DIE(mfsr_local_tone_grid(hrW, hrH, &localTone, &gx, &gy, &gz));
+        HIP_OK(hipMalloc((void**)&dtoneStats, sizeof(uint64_t) * 2 * (size_t)gx * gy * gz));
+        HIP_OK(hipMalloc((void**)&dtoneGrid, sizeof(float) * (size_t)gx * gy * gz));
+    }
     for (int rep = 0; rep < num_times; rep++) {
         if (rep == start_i) {
             HIP_OK(hipDeviceSynchronize());
@@ -698,6 +763,9 @@ int main(int argc, char** argv)
             MFSR_OK_OR_DIE(mfsr_burst_auto_render(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, &autoParams, dstats, dlut,
                                                   &measured, &autoResult, nullptr));
         }
+        if (localToneOn)  // after the auto render: measured with the matrix the finish below uses
+            MFSR_OK_OR_DIE(mfsr_burst_local_tone(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, &localTone, dtoneStats,
+                                                 dtoneGrid, &localToneResult, nullptr));
         if (rendered)  // (sharpening +) matrix + gamma + 8-bit store in the finish launch: the float image is neither written nor
                        // read again
             MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights,
@@ -714,6 +782,9 @@ int main(int argc, char** argv)
         fprintf(stderr, "auto: gains %g %g %g (status %d, neutral share %g) black %g white %g gamma %g (status %d)\n",
                 autoResult.gains[0], autoResult.gains[1], autoResult.gains[2], autoResult.awbStatus, autoResult.neutralShare,
                 autoResult.black, autoResult.white, autoResult.gamma, autoResult.toneStatus);
+    if (localToneOn)
+        fprintf(stderr, "local tone: cell %d bins %d pivot %g gains %g .. %g (status %d)\n", localTone.cell, localTone.bins,
+                localToneResult.pivot, localToneResult.minGain, localToneResult.maxGain, localToneResult.status);
 
     // result -> 8-bit RGB (D2H), then sharpenImg2 on the device
     if (!rendered) MFSR_OK_OR_DIE(mfsr_quantize((const mfsr_float3*)outF, 12 * hrW, nullptr, d8, hrW, hrH, 255.0f, nullptr));

@@ -1518,6 +1518,102 @@ int mfsr_auto_defaults(long long pixels, mfsr_auto_params* ap);
 int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_auto_params* ap,
                            uint64_t* statsDev, float* lutDev, mfsr_render* render, mfsr_auto_result* res, mfsr_stream_t stream);
 
+/* ---- local tone mapping in the finish: a bilateral grid of gains over (x, y, luma).  One global tone
+ * curve can only spend the dynamic range of a merged burst by flattening the whole image; a gain that depends on where the pixel
+ * is and how bright its surroundings are lifts shadows locally and keeps local contrast.  Three stages: exact integer statistics
+ * per grid entry on the device, the gains fitted on the host, and a trilinear lookup of the gain per pixel inside the rendered
+ * finish.  Nothing here runs unless it is called; without a description every entry point produces the bits it produced before.
+ * THE GRID belongs to the FULL frame, fullWidth x fullHeight: GX = cdiv(fullWidth, C), GY = cdiv(fullHeight, C), GZ = NZ
+ * (mfsr_local_tone_grid).  Every launch carries colOffset / rowOffset of its pixel (0, 0) in the full frame, as every finish
+ * does, so that stripes and windows add up to (statistics) or are the crop of (slice) the whole-frame launch.
+ * mfsr_local_tone_validate: anything out of the ranges below, or not finite, is MFSR_E_INVALID.  mfsr_local_tone_defaults: cell =
+ * the smallest power of two >= 16 with cdiv(max(w, h), cell) <= 128, bins 16, smooth 1, shadows 0.5, highlights 0.25, pivot 0
+ * (measured), maxGain 4. */
+typedef struct {
+    int32_t cell;        /* C: HR pixels per grid cell, a power of two, 16..512 */
+    int32_t bins;        /* NZ: luma bins, 4, 8, 16 or 32 */
+    int32_t smooth;      /* passes of the [1 2 1]/4 blur along x, y and luma, 0..4 */
+    float shadows;       /* 0..1: exponent below the pivot; 0 = leave shadows */
+    float highlights;    /* 0..1: exponent above the pivot; 0 = leave highlights */
+    float pivot;         /* linear luma in (0, 1]; 0 = measured (log-average) */
+    float maxGain;       /* 1..64: gains are clamped to [1/maxGain, maxGain] */
+    int32_t reserved[4]; /* zeros */
+} mfsr_local_tone;
+int mfsr_local_tone_validate(const mfsr_local_tone* lt);
+int mfsr_local_tone_defaults(int w, int h, mfsr_local_tone* lt);
+int mfsr_local_tone_grid(int fullWidth, int fullHeight, const mfsr_local_tone* lt, int* gx, int* gy, int* gz);
+/* 1. THE STATISTICS (device, exact).  For a pixel at full-frame position (X, Y), p and q as for mfsr_imageStats (q = the matrix
+ * applied to p when `matrix` is not NULL: nine host floats, row-major, finite, |m| <= 256), the codes c_k and the luma key
+ *   key = (54 c_0 + 183 c_1 + 19 c_2 + 128) >> 8                                                  (0 .. 4095)
+ * of mfsr_imageStats: the pixel adds 1 to count[Y / C][X / C][(key NZ) >> 12] and key to sum[...] of the same entry.  The table
+ * has 2 GX GY NZ uint64_t words of device memory (8-byte aligned): entries in the order y, x, luma (luma fastest), the two words
+ * of an entry adjacent, count first.  A launch ADDS to the table and the caller zeroes it, so stripes and windows add up to the
+ * whole image's table exactly, for any launch shape.  mfsr_toneGridStats measures a float image, mfsr_finishToneGridStats the
+ * accumulators of a burst with the arguments of mfsr_finishStats.  w h < 2^31; every argument is checked on the host before any
+ * device call.  Asynchronous on `stream`, nothing is allocated: capturable. */
+int mfsr_toneGridStats(const mfsr_float3* in, int inRowBytes, int w, int h, int colOffset, int rowOffset, int fullWidth,
+                       int fullHeight, const float* matrix, const mfsr_local_tone* lt, uint64_t* statsDev, mfsr_stream_t stream);
+int mfsr_finishToneGridStats(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                             int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, int w, int h, float threshold,
+                             int colOffset, int rowOffset, int fullWidth, int fullHeight, const float* matrix,
+                             const mfsr_local_tone* lt, uint64_t* statsDev, mfsr_stream_t stream);
+/* 2. THE FIT (host only, no device call, doubles; the table as a HOST array, the grid as GX GY NZ host floats, luma fastest, then
+ * x, then y).  N = counts, S = sums as doubles.
+ *   a. `smooth` passes, each [1 2 1] / 4 with replicated borders, ((lo + 2 c) + hi) * 0.25, along x, then y, then luma, on N
+ *      and on S;
+ *   b. base B = N > 0 ? S / (4095 N) : (k + 0.5) / NZ, floored at 1 / 4095;
+ *   c. pivot = lt->pivot if > 0, else exp(sum n ln(max(s / (4095 n), 1 / 4095)) / sum n) over the UNSMOOTHED entries with
+ *      n > 0, in the table's order; an empty table: *status = 1 and pivot 0.18 (else *status = 0);
+ *   d. r = B / pivot; g = r < 1 ? pow(r, -shadows) : pow(r, -highlights), clamped to [1 / maxGain, maxGain], rounded to float.
+ * shadows = highlights = 0 gives exactly 1.0f everywhere.  *pivotUsed (may be NULL) = the pivot. */
+int mfsr_local_tone_fit(const uint64_t* statsHost, int fullWidth, int fullHeight, const mfsr_local_tone* lt, float* gridHost,
+                        double* pivotUsed, int32_t* status);
+/* 3. THE SLICE (device).  mfsr_localToneImage / mfsr_finishLocalTone: mfsr_renderImage / mfsr_finishRendered with the gain of
+ * the grid applied to the pixel before step 1 of the rendered output.  For a pixel of value p at full-frame (X, Y), all in
+ * float32, one rounding per operation, in the order written:
+ *   a. q = matrix applied to p (render->useMatrix), else p; v_k = isnan(q_k) ? 0 : min(max(q_k, 0), 1);
+ *      l = ((54 v_0 + 183 v_1) + 19 v_2) * (1 / 256);
+ *   b. fx = (X + 0.5f) * (1 / C) - 0.5f clamped to [0, GX - 1]; i0 = (int)fx, i1 = min(i0 + 1, GX - 1), ax = fx - i0; fy, j0,
+ *      j1, ay likewise with Y and GY; fz = l NZ - 0.5f clamped to [0, NZ - 1], k0, k1, az;
+ *   c. at each of the four (y, x) corners a + (b - a) az with a, b the gains at k0, k1; the same expression along x for the
+ *      rows j0 and j1; then along y: the gain g;
+ *   d. o_k = p_k g, the same g for the three channels (hue is kept), and o takes the place of p in steps 1-3 of the rendered
+ *      output.  A NaN stays a NaN and is quantised to 0 as before.
+ * gridDev: GX GY NZ floats of device memory, 4-byte aligned, read only.  The four single-plane formats; the two-plane formats
+ * are refused.  The image form may run in place (outImg == in).  The tone table is staged as mfsr_renderImage stages it; the
+ * corner columns of the grid a workgroup's tile touches are staged in LDS or read through the cache (MFSR_LOCAL_TONE_GRID = lds |
+ * cache forces one; both give the same bits).  Asynchronous on `stream`, nothing is allocated: capturable. */
+int mfsr_localToneImage(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes,
+                        int w, int h, const mfsr_render* render, int applyGamma, const float* gridDev, const mfsr_local_tone* lt,
+                        int colOffset, int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream);
+int mfsr_finishLocalTone(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                         int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                         int outImgRowBytes, void* out, int outRowBytes, const mfsr_render* render, int w, int h, float threshold,
+                         int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight, const float* gridDev,
+                         const mfsr_local_tone* lt, mfsr_stream_t stream);
+/* 4. BURSTS.  mfsr_burst_set_local_tone installs a grid (device memory of the caller's, GX GY NZ floats of the FULL HR frame,
+ * valid while installed); NULL switches it off.  Between bursts only, as mfsr_burst_set_render.  With one installed every finish
+ * of the burst (mfsr_burst_finish, mfsr_burst_finish_rows; a stripe is the crop) goes through mfsr_finishLocalTone, whatever
+ * cfg.fused is; without a render description it renders {MFSR_OUT_RGB16, no matrix, no table}.  Refused (MFSR_E_INVALID): a handle
+ * with cfg.uploadRing (its bands finish before the accumulators are complete), together with a sharpen or a denoise description
+ * that is on, or with a two-plane format -- whichever setter comes second is refused.  Frame streams and the multi-GPU layer never
+ * set one.
+ * mfsr_burst_local_tone: after the last mfsr_burst_add_frame and before mfsr_burst_finish.  It fuses the frames still waiting,
+ * zeroes statsDev (2 GX GY NZ uint64_t, 8-byte aligned), measures the accumulators with mfsr_finishToneGridStats, the finish's
+ * own arguments and the burst's current matrix (so after mfsr_burst_auto_render: the matrix it installed), downloads, runs
+ * mfsr_local_tone_fit, uploads the grid to gridDev and installs it.  lt NULL = mfsr_local_tone_defaults of the HR frame.  With a
+ * zoom window the grid is still the full frame's, filled from the window's pixels only: entries the window does not reach hold
+ * the gain of their bin's centre.  Waits for the stream (the fit runs on the host): not capturable. */
+typedef struct {
+    double pivot;        /* the pivot the fit used */
+    int32_t status;      /* as mfsr_local_tone_fit */
+    int32_t reserved;
+    float minGain, maxGain; /* the smallest and the largest gain of the grid */
+} mfsr_local_tone_result;
+int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* lt, const float* gridDev);
+int mfsr_burst_local_tone(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_local_tone* lt,
+                          uint64_t* statsDev, float* gridDev, mfsr_local_tone_result* res, mfsr_stream_t stream);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

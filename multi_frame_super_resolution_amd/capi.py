@@ -185,6 +185,21 @@ class AutoResult(ctypes.Structure):
                 ("white", ctypes.c_double), ("gamma", ctypes.c_double), ("neutralShare", ctypes.c_double)]
 
 
+class LocalTone(ctypes.Structure):
+    """mfsr_local_tone (include/mfsr.h): the bilateral grid of gains of a local-tone finish."""
+
+    _fields_ = [("cell", ctypes.c_int32), ("bins", ctypes.c_int32), ("smooth", ctypes.c_int32), ("shadows", ctypes.c_float),
+                ("highlights", ctypes.c_float), ("pivot", ctypes.c_float), ("maxGain", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+class LocalToneResult(ctypes.Structure):
+    """mfsr_local_tone_result: the outcome of mfsr_burst_local_tone."""
+
+    _fields_ = [("pivot", ctypes.c_double), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("minGain", ctypes.c_float), ("maxGain", ctypes.c_float)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,

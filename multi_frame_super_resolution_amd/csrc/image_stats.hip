@@ -14,14 +14,11 @@
 // address would serialise) one lane adds the lane count.  The seven sums and the neutral count are kept per lane in 64 bits,
 // reduced over the wave with shuffles and over the workgroup in LDS.  At the end of its chunk the workgroup sweeps the table
 // once: contiguous lanes add the non-zero counters and the eight leading words to memory with 64-bit vector atomic adds.
-#include "render_common.hpp"
+#include "stats_common.hpp"
 
 namespace {
 
 constexpr int kBins = 4096;                    // codes 0 .. 4095
-constexpr int kStatsThreads = 1024;
-constexpr int kStatsPpl = 4;                   // consecutive pixels of a row one lane owns
-constexpr float kMaxCode = 4095.0f;
 
 static_assert(MFSR_IMAGE_STATS_WORDS == 8 + 2 * kBins, "the table of include/mfsr.h");
 
@@ -32,35 +29,6 @@ struct StatsArgs {
     int width, height, pitch;                  // of the launch; pitch of `in`, or of the accumulator and the weight image
     int rowsPerGroup;
 };
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// pixels [x0, x0 + 4) of a row, clipped to `width` (pixels beyond it: zeros, never loaded)
-__device__ __forceinline__ void load_quad(const pix3* row, int x0, int width, pix3 (&p)[kStatsPpl])
-{
-    const pix3* a = row + x0;
-    if (x0 + kStatsPpl <= width && ((uintptr_t)a & 15) == 0) {
-        const float4* v = (const float4*)a;
-        const float4 A = v[0], B = v[1], C = v[2];
-        p[0] = {A.x, A.y, A.z};
-        p[1] = {A.w, B.x, B.y};
-        p[2] = {B.z, B.w, C.x};
-        p[3] = {C.y, C.z, C.w};
-    } else {
-#pragma unroll
-        for (int k = 0; k < kStatsPpl; k++) {
-            p[k] = {0.0f, 0.0f, 0.0f};
-            if (x0 + k < width) p[k] = a[k];
-        }
-    }
-}
 
 // one LDS add per live lane, or one for the whole wave where every live lane holds the same key.  Called by all lanes of the
 // wave (the ballots and the shuffle stay outside divergent code).
@@ -157,16 +125,6 @@ __global__ void __launch_bounds__(kStatsThreads)
         const uint32_t c = sHist[k];
         if (c) atomicAdd(&stats[8 + k], (u64)c);
     }
-}
-
-int stats_cus()
-{
-    static int cached = 0;
-    if (cached > 0) return cached;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return 256;
-    return cached = cus;
 }
 
 int stats_validate(const mfsr_image_stats_params* p, int w, int h, int rowBytes, const uint64_t* statsDev)

@@ -384,6 +384,13 @@ struct mfsr_burst {
     // host staging of mfsr_burst_auto_render: the downloaded table and the tone table on its way to the device
     std::vector<uint64_t> autoStats;
     std::vector<float> autoLut;
+    // local tone mapping in the finish (mfsr_burst_set_local_tone): the installed grid (the caller's device
+    // memory) and the host staging of mfsr_burst_local_tone; never on together with a stencil or a two-plane format
+    bool localToneOn;
+    mfsr_local_tone localTone;
+    const float* localToneGrid;
+    std::vector<uint64_t> toneStats;
+    std::vector<float> toneGrid;
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -618,6 +625,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->sharpenedFinishes = 0;
     b->denoiseOn = false;
     b->denoisedFinishes = 0;
+    b->localToneOn = false;
+    b->localToneGrid = nullptr;
     b->robustGroupLaunches = 0;
     b->finishOut16 = nullptr;
     b->finishTaken = false;
@@ -2134,6 +2143,17 @@ static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const 
                                       outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch, y, rowBytes, uv, rowBytes,
                                       &b->render, oW, rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
     }
+    if (b->localToneOn) {  // (§2.25; without a render description: uint16_t RGB of the gained linear image)
+        mfsr_render plain;
+        memset(&plain, 0, sizeof(plain));
+        plain.format = MFSR_OUT_RGB16;
+        return mfsr_finishLocalTone((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
+                                    pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
+                                    outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
+                                    out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : &plain, oW,
+                                    rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, b->localToneGrid, &b->localTone,
+                                    stream);
+    }
     return mfsr_finishRendered((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
                                pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
                                outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
@@ -2194,6 +2214,7 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
     const bool on = sharpen->radius != 0 && sharpen->amount != 0.0f;
     MFSR_REQUIRE(!(on && yuv_on(b)));  // the sharpen tile kernel renders single rows: no two-plane output
     MFSR_REQUIRE(!(on && b->denoiseOn));  // one stencil per finish: whichever setter comes second is refused
+    MFSR_REQUIRE(!(on && b->localToneOn));  // the local-tone finish is pointwise: no stencil
     b->sharpen = *sharpen;
     b->sharpenOn = on;
     return MFSR_OK;
@@ -2211,6 +2232,7 @@ extern "C" int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise
     const bool on = denoise->radius != 0 && denoise->strength != 0.0f;
     MFSR_REQUIRE(!(on && yuv_on(b)));     // the denoise tile kernel renders single rows, as the sharpen one
     MFSR_REQUIRE(!(on && b->sharpenOn));  // one stencil per finish
+    MFSR_REQUIRE(!(on && b->localToneOn));  // (as mfsr_burst_set_sharpen)
     b->denoise = *denoise;
     b->denoiseOn = on;
     return MFSR_OK;
@@ -2247,6 +2269,7 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
     }
     TRY(mfsr_render_validate(render));
     MFSR_REQUIRE(!(stencil_on(b) && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen / _denoise: whichever comes second)
+    MFSR_REQUIRE(!(b->localToneOn && yuv_format(render->format)));  // (mfsr_burst_set_local_tone likewise)
     b->render = *render;
     b->renderOn = true;
     return MFSR_OK;
@@ -2358,6 +2381,70 @@ extern "C" int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, 
     return MFSR_OK;
 }
 
+// ---- local tone mapping in the finish: the grid of the full HR frame, measured on the accumulators with the
+//      finish's own arguments (csrc/local_tone.hip), fitted on the host, installed for finish_rendered_rows ---------------------
+extern "C" int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* lt, const float* gridDev)
+{
+    MFSR_REQUIRE(b != nullptr);
+    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    if (!lt) {
+        b->localToneOn = false;
+        b->localToneGrid = nullptr;
+        return MFSR_OK;
+    }
+    TRY(mfsr_local_tone_validate(lt));
+    MFSR_REQUIRE(gridDev != nullptr && ((uintptr_t)gridDev & 3) == 0);
+    MFSR_REQUIRE(!b->cfg.uploadRing);  // a host burst finishes band by band, before its accumulators are complete
+    MFSR_REQUIRE(!stencil_on(b));      // whichever setter comes second is refused
+    MFSR_REQUIRE(!yuv_on(b));          // single-plane formats only
+    b->localTone = *lt;
+    b->localToneGrid = gridDev;
+    b->localToneOn = true;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_local_tone(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights,
+                                     const mfsr_local_tone* ltIn, uint64_t* statsDev, float* gridDev, mfsr_local_tone_result* res,
+                                     mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && imgOut && totalWeights && statsDev && gridDev && res);
+    MFSR_REQUIRE(b->haveRef && ((uintptr_t)statsDev & 7) == 0 && ((uintptr_t)gridDev & 3) == 0);
+    MFSR_REQUIRE(!b->cfg.uploadRing && !stencil_on(b) && !yuv_on(b));  // (before any work: what mfsr_burst_set_local_tone refuses)
+    const Layout& L = b->L;
+    mfsr_local_tone lt;
+    if (ltIn)
+        lt = *ltIn;
+    else
+        TRY(mfsr_local_tone_defaults(L.hrW, L.hrH, &lt));
+    int gx = 0, gy = 0, gz = 0;
+    TRY(mfsr_local_tone_grid(L.hrW, L.hrH, &lt, &gx, &gy, &gz));
+    TRY(flush_pending(b, stream));
+    const size_t entries = (size_t)gx * gy * gz;
+    const int oW = out_w(b), pitch = 12 * oW;
+    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    MFSR_HIP_TRY(hipMemsetAsync(statsDev, 0, sizeof(uint64_t) * 2 * entries, mfsr_s(stream)));
+    TRY(mfsr_finishToneGridStats(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f,
+                                 0.0f, 1.0f, oW, out_h(b), b->cfg.weightThreshold, x0, y0, L.hrW, L.hrH,
+                                 b->renderOn && b->render.useMatrix ? b->render.matrix : nullptr, &lt, statsDev, stream));
+    b->toneStats.resize(2 * entries);
+    MFSR_HIP_TRY(hipMemcpyAsync(b->toneStats.data(), statsDev, sizeof(uint64_t) * 2 * entries, hipMemcpyDeviceToHost, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
+    b->toneGrid.resize(entries);
+    mfsr_local_tone_result out;
+    memset(&out, 0, sizeof(out));
+    TRY(mfsr_local_tone_fit(b->toneStats.data(), L.hrW, L.hrH, &lt, b->toneGrid.data(), &out.pivot, &out.status));
+    out.minGain = out.maxGain = b->toneGrid[0];
+    for (size_t i = 1; i < entries; i++) {
+        out.minGain = b->toneGrid[i] < out.minGain ? b->toneGrid[i] : out.minGain;
+        out.maxGain = b->toneGrid[i] > out.maxGain ? b->toneGrid[i] : out.maxGain;
+    }
+    MFSR_HIP_TRY(hipMemcpyAsync(gridDev, b->toneGrid.data(), sizeof(float) * entries, hipMemcpyHostToDevice, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));  // (the staging may be written again by the next call)
+    TRY(mfsr_burst_set_local_tone(b, &lt, gridDev));  // (after the flush its own guard holds)
+    *res = out;
+    return MFSR_OK;
+}
+
 extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights,
                                  mfsr_float3* outImg, uint16_t* out16, mfsr_stream_t stream)
 {
@@ -2370,7 +2457,8 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     // after the burst launch, which then must not finish).  fuse_hold decides the rest (the entry's own refusals).
     b->finishTaken = false;
     b->finishOut16 = nullptr;
-    if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->win.on && out16 && !outImg && !c.applyGamma &&
+    if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->localToneOn && !b->win.on && out16 && !outImg &&
+        !c.applyGamma &&
         b->nHold >= 2 && b->pend.n == 0 && !b->heldHas && b->hold[0].imgOut == imgOut && b->hold[0].totalWeights == totalWeights)
         b->finishOut16 = out16;
     const int rcFlush = flush_pending(b, stream);
@@ -2385,6 +2473,8 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     // before its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting (tests/test_parity_kernels.py::
     // test_finishFused_equals_chain), so the unfused burst's sharpened finish is this launch as well: no second HR float image
     if (stencil_on(b)) return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
+    // the local-tone finish (§2.25) likewise: one launch on the accumulators whatever cfg.fused is
+    if (b->localToneOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
     if (b->renderOn && c.fused) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
     if (b->renderOn) {
         // the unfused chain up to ApplyWeighting, then the pixel body on the float image in place of GammasRGB + quantize
@@ -2439,7 +2529,7 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
         stencil_reach(b, row0, rows, &above, &below);
         return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
     }
-    if (b->renderOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
+    if (b->renderOn || b->localToneOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
     const int pitch = 12 * L.hrW;
     const size_t off = (size_t)row0 * pitch;
     return mfsr_finishFusedRows((const mfsr_float3*)((const char*)imgOut + off),

@@ -894,6 +894,119 @@ def tone_fit(stats, p_lo: float = 0.001, p_hi: float = 0.999, max_gain: float = 
     return ToneFit(torch.from_numpy(lut), b.value, w.value, g.value, st.value)
 
 
+# ---- local tone mapping in the finish (include/mfsr.h, mfsr_local_tone) ------------------------------
+LocalToneFit = namedtuple("LocalToneFit", "grid pivot status")
+
+
+def local_tone_defaults(w: int, h: int) -> capi.LocalTone:
+    """The default description for a w x h frame (mfsr_local_tone_defaults; host only): cell = the smallest power of two >= 16
+    with at most 128 cells along the longer side, 16 bins, one smoothing pass, shadows 0.5, highlights 0.25, a measured pivot,
+    gains within [1/4, 4]."""
+    lt = capi.LocalTone()
+    if capi.lib().raw["mfsr_local_tone_defaults"](int(w), int(h), ctypes.byref(lt)) != 0:
+        raise ValueError("local_tone_defaults: 1 <= w, h <= 65536")
+    return lt
+
+
+def _local_tone_struct(w, h, shadows, highlights, cell=None, bins=16, smooth=1, pivot=0.0, max_gain=4.0) -> capi.LocalTone:
+    lt = local_tone_defaults(w, h)
+    lt.shadows, lt.highlights, lt.pivot, lt.maxGain = float(shadows), float(highlights), float(pivot), float(max_gain)
+    lt.bins, lt.smooth = int(bins), int(smooth)
+    if cell is not None:
+        lt.cell = int(cell)
+    if capi.lib().raw["mfsr_local_tone_validate"](ctypes.byref(lt)) != 0:
+        raise ValueError("local tone: cell a power of two 16..512, bins 4, 8, 16 or 32, smooth 0..4, shadows and highlights "
+                         "in [0, 1], pivot in [0, 1], max_gain in [1, 64], all finite")
+    return lt
+
+
+def local_tone_grid(full_w: int, full_h: int, lt: capi.LocalTone) -> Tuple[int, int, int]:
+    """(GX, GY, GZ) of the grid of a full_w x full_h frame (mfsr_local_tone_grid): the statistics table has 2 GX GY GZ words and
+    the gain grid GX GY GZ floats, luma fastest, then x, then y."""
+    gx, gy, gz = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if capi.lib().raw["mfsr_local_tone_grid"](int(full_w), int(full_h), ctypes.byref(lt), ctypes.byref(gx), ctypes.byref(gy),
+                                              ctypes.byref(gz)) != 0:
+        raise ValueError("local_tone_grid: a positive extent and a valid description")
+    return gx.value, gy.value, gz.value
+
+
+def _dense_f3(img: torch.Tensor) -> bool:
+    return (img.is_cuda and img.dtype == torch.float32 and img.dim() == 3 and img.shape[2] == 3 and img.stride(2) == 1
+            and img.stride(1) == 3)
+
+
+def _matrix9(matrix):
+    if matrix is None:
+        return None
+    m = [float(v) for v in torch.as_tensor(matrix, dtype=torch.float64).reshape(-1).tolist()]
+    if len(m) != 9:
+        raise ValueError("matrix: 3 x 3 coefficients, row-major")
+    return (ctypes.c_float * 9)(*m)
+
+
+def tone_grid_stats(img: torch.Tensor, lt: capi.LocalTone, matrix=None, offset=(0, 0), full=None,
+                    table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The statistics of the bilateral grid of a float image [h, w, 3] on the device (mfsr_toneGridStats), exact: a device int64
+    tensor [GY, GX, GZ, 2] of (count, sum of the luma key) per grid entry.  ``offset`` = (x, y) of the image's first pixel in
+    the ``full`` = (w, h) frame the grid belongs to (default: the image is the frame).  ``table``: add to this table instead of
+    a zeroed one (stripes and windows add up to the whole)."""
+    if not _dense_f3(img):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    fw, fh = (w, h) if full is None else (int(full[0]), int(full[1]))
+    gx, gy, gz = local_tone_grid(fw, fh, lt)
+    with torch.cuda.device(img.device):
+        if table is None:
+            table = torch.zeros(gy, gx, gz, 2, dtype=torch.int64, device=img.device)
+        elif table.shape != (gy, gx, gz, 2) or table.dtype != torch.int64 or not table.is_contiguous():
+            raise ValueError(f"table: a contiguous int64 tensor [{gy}, {gx}, {gz}, 2]")
+        capi.lib().toneGridStats(img.data_ptr(), img.stride(0) * 4, w, h, int(offset[0]), int(offset[1]), fw, fh, _matrix9(matrix),
+                                 ctypes.byref(lt), table.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return table
+
+
+def local_tone_fit(stats, full_w: int, full_h: int, lt: capi.LocalTone) -> LocalToneFit:
+    """The gains of a table of ``tone_grid_stats`` (mfsr_local_tone_fit; host only): ``LocalToneFit(grid, pivot, status)`` with
+    ``grid`` a CPU float32 tensor [GY, GX, GZ].  status 1: the table was empty (pivot 0.18)."""
+    import numpy as np
+    gx, gy, gz = local_tone_grid(full_w, full_h, lt)
+    a = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    a = np.ascontiguousarray(a.view(np.uint64) if a.dtype == np.int64 else a.astype(np.uint64, copy=False)).reshape(-1)
+    if a.size != 2 * gx * gy * gz:
+        raise ValueError(f"stats: the table of tone_grid_stats, {2 * gx * gy * gz} words")
+    grid = np.empty((gy, gx, gz), np.float32)
+    pivot, st = ctypes.c_double(), ctypes.c_int32()
+    capi.lib().local_tone_fit(a.ctypes.data, int(full_w), int(full_h), ctypes.byref(lt), grid.ctypes.data, ctypes.byref(pivot),
+                              ctypes.byref(st))
+    return LocalToneFit(torch.from_numpy(grid), pivot.value, st.value)
+
+
+def local_tone_image(img: torch.Tensor, grid: torch.Tensor, lt: capi.LocalTone, format: int = capi.OUT_RGB16, matrix=None,
+                     tone_lut=None, apply_gamma: bool = False, want_float: bool = False, offset=(0, 0), full=None):
+    """``render_image`` with the gain of the bilateral ``grid`` ([GY, GX, GZ] floats, device or host) applied to every pixel
+    before the matrix (mfsr_localToneImage).  ``offset`` / ``full`` as for ``tone_grid_stats``.  Returns the tensor typed for
+    the format, and with ``want_float`` also the float image the integers quantise."""
+    if not _dense_f3(img):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    if format in capi.YUV_FORMATS:
+        raise ValueError("local_tone_image: single-plane formats only")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    fw, fh = (w, h) if full is None else (int(full[0]), int(full[1]))
+    gx, gy, gz = local_tone_grid(fw, fh, lt)
+    with torch.cuda.device(img.device):
+        g = torch.as_tensor(grid).to(device=img.device, dtype=torch.float32).contiguous()
+        if g.numel() != gx * gy * gz:
+            raise ValueError(f"grid: {gy} x {gx} x {gz} floats")
+        r, lut = _render_struct(format, matrix, tone_lut, img.device)
+        out = _render_buffer(format, h, w, img.device)
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if want_float else None
+        capi.lib().localToneImage(img.data_ptr(), img.stride(0) * 4, fl.data_ptr() if want_float else None, 12 * w, out.data_ptr(),
+                                  render_row_bytes(format, w), w, h, ctypes.byref(r), 1 if apply_gamma else 0, g.data_ptr(),
+                                  ctypes.byref(lt), int(offset[0]), int(offset[1]), fw, fh, torch.cuda.current_stream().cuda_stream)
+        del lut, g
+    return (out, fl) if want_float else out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -909,6 +1022,8 @@ class BurstPipeline:
         self.cfg = cfg
         self.window = _Window(cfg, window)
         self._sharpen_on = self._denoise_on = False   # a stencil in the finish (set_sharpen, set_denoise) grows the window
+        self._local_tone = None         # the description of set_local_tone; its grid and table live as long as it is installed
+        self.local_tone_result = None   # capi.LocalToneResult of the last measurement
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         nbytes = self.L.burst_workspace_bytes(ctypes.byref(cfg))
         if nbytes == 0:
@@ -1029,7 +1144,55 @@ class BurstPipeline:
         for k in (range(len(frames)) if frame_ids is None else frame_ids):
             self.add_frame(frames[k], k == r)
         self.auto_result = self.auto_render(**auto)
+        if self._local_tone is not None:     # measured with the matrix auto_render has just installed
+            self.local_tone()
         return self.finish()
+
+    def set_local_tone(self, shadows: Optional[float] = 0.5, highlights: float = 0.25, cell: Optional[int] = None, bins: int = 16,
+                       smooth: int = 1, pivot: float = 0.0, max_gain: float = 4.0):
+        """Local tone mapping inside the finish (mfsr_burst_set_local_tone): a gain per pixel from a
+        bilateral grid over (x, y, luma) of the merged image, applied before the colour matrix, the same for the three
+        channels.  Regions darker than the ``pivot`` (0 = the image's log-average luma) are lifted by (B / pivot)^-shadows,
+        brighter ones lowered by (B / pivot)^-highlights, B the mean luma of the grid cell and luma bin around the pixel;
+        gains stay within [1 / max_gain, max_gain].  ``cell`` = HR pixels per grid cell (None: chosen from the frame),
+        ``bins`` luma bins, ``smooth`` blur passes over the grid.  ``shadows=None`` turns it off.  Between bursts only; not
+        together with ``set_sharpen`` / ``set_denoise`` or a two-plane format.  ``process`` and ``process_auto`` then measure the
+        burst before they finish it (``local_tone``; the outcome is ``self.local_tone_result``); until a burst has been measured
+        the installed grid holds ones."""
+        with torch.cuda.device(self.device):
+            if shadows is None:
+                self.L.burst_set_local_tone(self._h, None, None)
+                self._local_tone = self._tone_grid = self._tone_table = None
+                return
+            lt = _local_tone_struct(self.hr_w, self.hr_h, shadows, highlights, cell, bins, smooth, pivot, max_gain)
+            gx, gy, gz = local_tone_grid(self.hr_w, self.hr_h, lt)
+            grid = torch.ones(gy, gx, gz, dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream().synchronize()   # (the library may read the grid on another stream than the fill's)
+            self.L.burst_set_local_tone(self._h, ctypes.byref(lt), grid.data_ptr())
+            self._local_tone, self._tone_grid = lt, grid
+            self._tone_table = torch.zeros(gy, gx, gz, 2, dtype=torch.int64, device=self.device)
+
+    def local_tone(self) -> capi.LocalToneResult:
+        """Measure the burst's accumulators and install the fitted grid (mfsr_burst_local_tone): after the last ``add_frame``
+        (and after ``auto_render``, whose matrix the measurement then uses) and before ``finish``.  Needs ``set_local_tone``.
+        The table is left in ``self.tone_table`` (int64 [GY, GX, GZ, 2]), the grid in ``self.tone_grid``."""
+        if self._local_tone is None:
+            raise RuntimeError("local_tone: call set_local_tone first")
+        res = capi.LocalToneResult()
+        with torch.cuda.device(self.device):
+            self.L.burst_local_tone(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), ctypes.byref(self._local_tone),
+                                    self._tone_table.data_ptr(), self._tone_grid.data_ptr(), ctypes.byref(res), self._stream())
+            self._held_frames.clear()
+        self.local_tone_result = res
+        return res
+
+    @property
+    def tone_grid(self) -> Optional[torch.Tensor]:
+        return self._tone_grid if self._local_tone is not None else None
+
+    @property
+    def tone_table(self) -> Optional[torch.Tensor]:
+        return self._tone_table if self._local_tone is not None else None
 
     def set_sharpen(self, amount: Optional[float] = None, sigma: float = 1.0, radius: int = 0, threshold: float = 0.0, taps=None):
         """Sharpen inside the finish (mfsr_burst_set_sharpen): an unsharp mask of strength ``amount`` on
@@ -1261,6 +1424,8 @@ class BurstPipeline:
         self.set_reference(work[r])
         for k in kept:
             self.add_frame(work[k], k == r)
+        if self._local_tone is not None:
+            self.local_tone()
         return self.finish()
 
     def process(self, frames: Sequence[torch.Tensor], frame_ids: Optional[Iterable[int]] = None):
