@@ -2544,7 +2544,7 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     fill_frames(fr.f, dataIn, certaintyMask, shifts, nFrames);
     for (int n = nFrames; n < 4 * TILE_BURST_GROUPS; n++) fr.f[n] = fr.f[0];  // (never read: nGroups bounds the loop)
     // the finishing form (out16): the whole frame's plain finish, the launch's pixel (0, 0) is the image's
-    const FinishSrc src{(const pix3*)fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, 0, hrH, 0, hrW};
+    const FinishSrc src = finish_src(fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, 0, 0, hrW, hrH);
     // monochrome and other patterns are not the burst kernel's: 0
     const int rc = for_cfa<false>(packed2, [&](auto cfaTag) {
         constexpr int CFA = decltype(cfaTag)::value;

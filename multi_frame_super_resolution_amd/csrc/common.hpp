@@ -59,6 +59,13 @@ static inline bool mfsr_window_ok(int hrW, int hrH, int x0, int y0, int w, int h
 static inline unsigned mfsr_cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 // the host checks of a render description (format, matrix coefficients, tone table size): MFSR_OK or MFSR_E_INVALID; render.hip
 int mfsr_render_validate(const mfsr_render* r);
+// without a render description: the plain finish's steps (no matrix, no table, uint16_t RGB)
+static inline mfsr_render mfsr_plain_render()
+{
+    mfsr_render r = {};
+    r.format = MFSR_OUT_RGB16;
+    return r;
+}
 
 // ---- CFA pattern: packed 4 x 8 bit, [y%2][x%2] -> bits ((y&1)*2+(x&1))*8 -----
 // Frame batches: the per-frame pointer arguments of a kernel for up to MFSR_BATCH_MAX frames, appended to its argument list; a

@@ -219,12 +219,8 @@ __global__ void __launch_bounds__(kLanes)
     __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
     __shared__ __attribute__((aligned(16))) float s_s[3][kSH][kSW];
     const float* lut = stage_lut<LDS>(r, s_lut);
-    // k_finishRendered's value (finish_value: one definition); y may be negative (rowsAbove): the pointers are 64-bit
-    auto fetch = [&](int x, int y) {
-        const pix3 val = *(const pix3*)((const char*)finalImg + (long long)imgPitch * y + 12LL * x);
-        const pix3 w = *(const pix3*)((const char*)weight + (long long)imgPitch * y + 12LL * x);
-        return finish_value(val, w, x, y, f);
-    };
+    // k_finishRendered's value (finish_value_at: one definition); y may be negative (rowsAbove)
+    auto fetch = [&](int x, int y) { return finish_value_at(finalImg, weight, imgPitch, x, y, f); };
     // step 2: the count apply_weight_f divided by
     auto count = [&](int x, int y) {
         pix3 n = row_ptr(weight, imgPitch, y)[x];
@@ -304,7 +300,7 @@ extern "C" int mfsr_denoiseImage(const mfsr_float3* in, int inRowBytes, const mf
     if (count) MFSR_REQUIRE((long long)countRowBytes >= 12LL * w && (countRowBytes & 3) == 0 && ((uintptr_t)count & 3) == 0);
     if (int rc = mfsr_denoise_validate(denoise)) return rc;
     MFSR_REQUIRE(denoise_on(denoise));
-    const mfsr_render plain = plain_render();
+    const mfsr_render plain = mfsr_plain_render();
     if (int rc = stencil_render(render, &plain, &render)) return rc;
     if (int rc = stencil_outputs_apart(in, image_span(inRowBytes, h, 12, w), outImg, outImgRowBytes, out, outRowBytes, render->format, w, h))
         return rc;
@@ -332,7 +328,7 @@ extern "C" int mfsr_finishDenoised(const mfsr_float3* finalImg, const mfsr_float
         return rc;
     if (int rc = mfsr_denoise_validate(denoise)) return rc;
     MFSR_REQUIRE(denoise_on(denoise));
-    const mfsr_render plain = plain_render();
+    const mfsr_render plain = mfsr_plain_render();
     if (int rc = stencil_render(render, &plain, &render)) return rc;
     if (int rc = stencil_finish_apart(finalImg, weight, imgRowBytes, rowsAbove, rowsBelow, outImg, outImgRowBytes, out, outRowBytes,
                                       render->format, w, h))
@@ -340,20 +336,7 @@ extern "C" int mfsr_finishDenoised(const mfsr_float3* finalImg, const mfsr_float
     const RenderArgs ra = render_args(render, applyGamma);
     const DenoiseArgs da = denoise_args(denoise, -rowsAbove, h - 1 + rowsBelow);
     const bool lds = stencil_lut_in_lds(render);
-    FinishSrc f;
-    f.fallback = (const pix3*)fallback;
-    f.fbPitch = fbRowBytes;
-    f.fbW = fbW;
-    f.fbH = fbH;
-    f.u0 = u0;
-    f.u1 = u1;
-    f.v0 = v0;
-    f.v1 = v1;
-    f.threshold = threshold;
-    f.rowOffset = rowOffset;
-    f.fullHeight = fullHeight;
-    f.colOffset = colOffset;
-    f.fullWidth = fullWidth;
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     DENOISE_DISPATCH(k_finishDenoised, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes, f, (pix3*)outImg,
                      outImgRowBytes, (uint8_t*)out, outRowBytes, w, h, da, ra);
     return mfsr_launch_status("finishDenoised");

@@ -1,8 +1,10 @@
 // finish_common.hpp -- the pixel arithmetic of the burst's finish (stage H), shared by glue.hip (k_finishFused, k_quantize,
-// k_resampleFloat3), render.hip (k_finishRendered, k_renderImage), image_stats.hip (k_imageStats) and accumulate_fast.hip (the
-// finishing burst tile kernel and k_finishRing, which write what k_finishFused writes): one definition, so that
-// the rendered finish holds the same value as the plain one before its gamma, quantises by the same rule, and is measured as
-// it is rendered.
+// k_resampleFloat3), render.hip (k_finishRendered, k_renderImage), render_yuv.hip (k_finishRenderedYuv), sharpen.hip
+// (k_finishSharpened), denoise.hip (k_finishDenoised), local_tone.hip (k_finishLocalTone, k_toneGridStats), image_stats.hip
+// (k_imageStats) and accumulate_fast.hip (the finishing burst tile kernel and k_finishRing, which write what k_finishFused
+// writes): one definition, so that every finish holds the same value as the plain one before its own step, quantises by the
+// same rule, and is measured as it is rendered.  The host side of those launches is here as well: one check of the arguments
+// they share and one fill of FinishSrc.
 #pragma once
 
 #include "common.hpp"
@@ -78,14 +80,58 @@ __device__ __forceinline__ pix3 finish_weighted(pix3 inout, pix3 val, pix3 w, co
 }
 
 // The value section 2.19 calls p at pixel (x, y) of the launch: the body of k_finishFused up to its gamma (a stripe or window is
-// the crop of the whole).  val / w: the accumulator and the weight of the pixel.  One definition for k_finishFused (glue.hip),
-// k_finishRendered (render.hip), k_imageStats (image_stats.hip) and k_finishRing (accumulate_fast.hip): what is measured is what
-// is rendered.  (The test is finish_needs_fallback's, spelled out: through the call k_finishFused came out as other code.)
+// the crop of the whole).  val / w: the accumulator and the weight of the pixel.  One definition for every finish kernel and
+// both statistics passes (the list at the head of this file): what is measured is what is rendered.  (The test is
+// finish_needs_fallback's, spelled out: through the call k_finishFused came out as other code.)
 __device__ __forceinline__ pix3 finish_value(pix3 val, pix3 w, int x, int y, const FinishSrc& f)
 {
     pix3 inout = {0.0f, 0.0f, 0.0f};
     if (f.fallback && (w.x < f.threshold || w.y < f.threshold || w.z < f.threshold)) inout = finish_fallback(x, y, f);
     return finish_weighted(inout, val, w, f);
+}
+
+// finish_value at pixel (x, y) of a launch whose accumulator and weight rows are imgPitch bytes apart.  The stencil finishes
+// (sharpen.hip, denoise.hip) fetch through this: their reach puts y below 0 (rowsAbove), so the address is signed 64-bit.
+__device__ __forceinline__ pix3 finish_value_at(const pix3* finalImg, const pix3* weight, int imgPitch, int x, int y,
+                                                const FinishSrc& f)
+{
+    const pix3 val = *(const pix3*)((const char*)finalImg + (long long)imgPitch * y + 12LL * x);
+    const pix3 w = *(const pix3*)((const char*)weight + (long long)imgPitch * y + 12LL * x);
+    return finish_value(val, w, x, y, f);
+}
+
+// ---- host: what every finish entry point checks and fills before its own arguments --------------------------------------
+// the FinishSrc of an entry point's arguments
+static inline FinishSrc finish_src(const void* fallback, int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1,
+                                   float threshold, int colOffset, int rowOffset, int fullWidth, int fullHeight)
+{
+    return FinishSrc{(const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset, fullWidth};
+}
+
+// what a finish launch of w x h pixels reads: the accumulator pair, the fallback's extent and pitch, the launch's place in the
+// full frame.  (The statistics passes stop here: they have no image output.)
+static inline int finish_check_src(const void* finalImg, const void* weight, int imgRowBytes, const void* fallback, int fbRowBytes,
+                                   int fbW, int fbH, int w, int h, int colOffset, int rowOffset, int fullWidth, int fullHeight)
+{
+    MFSR_REQUIRE(finalImg && weight && w > 0 && h > 0);
+    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
+    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
+    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
+    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
+    return MFSR_OK;
+}
+
+// ... and writes: the float image and / or an integer output (`out`: any plane of it), one of them at least
+static inline int finish_check(const void* finalImg, const void* weight, int imgRowBytes, const void* fallback, int fbRowBytes, int fbW,
+                               int fbH, const void* outImg, int outImgRowBytes, const void* out, int w, int h, int colOffset,
+                               int rowOffset, int fullWidth, int fullHeight)
+{
+    MFSR_REQUIRE(outImg || out);
+    if (int rc = finish_check_src(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, w, h, colOffset, rowOffset, fullWidth,
+                                  fullHeight))
+        return rc;
+    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
+    return MFSR_OK;
 }
 
 // the plain uint16_t RGB of p: three samples of maxOut levels

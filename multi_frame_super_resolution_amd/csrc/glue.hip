@@ -541,19 +541,16 @@ extern "C" int mfsr_structureTensorFused(const float* img, int imgPitch, mfsr_fl
 
 // ---- H1 (+fallback resample) + H2 + quantise in one launch ---------------------------
 __global__ void __launch_bounds__(256)
-    k_finishFused(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
-                  const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
-                  pix3* __restrict__ outImg, int outPitch, uint16_t* __restrict__ out16, int width, int height,
-                  float threshold, int applyGamma, float maxOut, int rowOffset, int fullHeight, int colOffset, int fullWidth)
+    k_finishFused(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch, FinishSrc src,
+                  pix3* __restrict__ outImg, int outPitch, uint16_t* __restrict__ out16, int width, int height, int applyGamma,
+                  float maxOut)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= width || y >= height) return;
     const pix3 val = row_ptr(finalImg, imgPitch, y)[x];
     const pix3 w = row_ptr(weight, imgPitch, y)[x];
-    // the pixel arithmetic is finish_common.hpp's (one definition with the rendered finish, the statistics, the finishing burst
-    // tile kernel and the ring finish)
-    const FinishSrc src{fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset, fullWidth};
+    // the pixel arithmetic is finish_common.hpp's (one definition with every other finish and the statistics)
     pix3 inout = finish_value(val, w, x, y, src);
     if (applyGamma) {
         inout.x = gamma_f(inout.x);
@@ -577,17 +574,14 @@ extern "C" int mfsr_finishFusedWindow(const mfsr_float3* finalImg, const mfsr_fl
                                       float threshold, int applyGamma, float maxOut, int colOffset, int rowOffset, int fullWidth,
                                       int fullHeight, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out16) && width > 0 && height > 0);
-    MFSR_REQUIRE((long long)imgPitch >= 12LL * width && (imgPitch & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outPitch >= 12LL * width && (outPitch & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbPitch >= 12LL * fbW && (fbPitch & 3) == 0);
+    if (int rc = finish_check(finalImg, weight, imgPitch, fallback, fbPitch, fbW, fbH, outImg, outPitch, out16, width, height,
+                              colOffset, rowOffset, fullWidth, fullHeight))
+        return rc;
     MFSR_REQUIRE(maxOut > 0 && maxOut <= 65535.0f);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + height);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + width);
+    const FinishSrc src = finish_src(fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     dim3 block(64, 4), grid(mfsr_cdiv(width, 64), mfsr_cdiv(height, 4));
-    hipLaunchKernelGGL(k_finishFused, grid, block, 0, mfsr_s(stream), (const pix3*)finalImg, (const pix3*)weight, imgPitch,
-                       (const pix3*)fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outPitch, out16, width,
-                       height, threshold, applyGamma, maxOut, rowOffset, fullHeight, colOffset, fullWidth);
+    hipLaunchKernelGGL(k_finishFused, grid, block, 0, mfsr_s(stream), (const pix3*)finalImg, (const pix3*)weight, imgPitch, src,
+                       (pix3*)outImg, outPitch, out16, width, height, applyGamma, maxOut);
     return mfsr_launch_status("finishFused");
 }
 

@@ -171,7 +171,7 @@ extern "C" int mfsr_imageStats(const mfsr_float3* in, int inRowBytes, int w, int
     if (int rc = stats_validate(params, w, h, inRowBytes, statsDev)) return rc;
     unsigned blocks = 0;
     const StatsArgs s = stats_args(params, w, h, inRowBytes, &blocks);
-    const FinishSrc none = {};
+    const FinishSrc none = FinishSrc();
     hipLaunchKernelGGL(k_imageStats<0>, dim3(blocks), dim3(kStatsThreads), 0, mfsr_s(stream), (const pix3*)in, (const pix3*)nullptr,
                        none, s, (u64*)statsDev);
     return mfsr_launch_status("k_imageStats");
@@ -182,16 +182,15 @@ extern "C" int mfsr_finishStats(const mfsr_float3* finalImg, const mfsr_float3* 
                                 float threshold, int colOffset, int rowOffset, int fullWidth, int fullHeight,
                                 const mfsr_image_stats_params* params, uint64_t* statsDev, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg != nullptr && weight != nullptr && ((uintptr_t)finalImg & 3) == 0 && ((uintptr_t)weight & 3) == 0);
+    if (int rc = finish_check_src(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, w, h, colOffset, rowOffset, fullWidth,
+                                  fullHeight))
+        return rc;
+    // (its own: the quad loads want the three images dword-aligned)
+    MFSR_REQUIRE(((uintptr_t)finalImg & 3) == 0 && ((uintptr_t)weight & 3) == 0 && ((uintptr_t)fallback & 3) == 0);
     if (int rc = stats_validate(params, w, h, imgRowBytes, statsDev)) return rc;
-    if (fallback)
-        MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0 && ((uintptr_t)fallback & 3) == 0);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
     unsigned blocks = 0;
     const StatsArgs s = stats_args(params, w, h, imgRowBytes, &blocks);
-    const FinishSrc f = {(const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset,
-                         fullWidth};
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     hipLaunchKernelGGL(k_imageStats<1>, dim3(blocks), dim3(kStatsThreads), 0, mfsr_s(stream), (const pix3*)finalImg,
                        (const pix3*)weight, f, s, (u64*)statsDev);
     return mfsr_launch_status("k_imageStats");

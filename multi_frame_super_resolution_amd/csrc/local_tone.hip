@@ -509,7 +509,7 @@ extern "C" int mfsr_toneGridStats(const mfsr_float3* in, int inRowBytes, int w, 
     if (int rc = tone_stats_validate(matrix, lt, w, h, inRowBytes, colOffset, rowOffset, fullWidth, fullHeight, statsDev)) return rc;
     unsigned groups = 0;
     const ToneStatsArgs s = tone_stats_args(matrix, lt, w, h, inRowBytes, colOffset, rowOffset, fullWidth, fullHeight, &groups);
-    const FinishSrc none = {nullptr, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, rowOffset, fullHeight, colOffset, fullWidth};
+    const FinishSrc none = finish_src(nullptr, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, colOffset, rowOffset, fullWidth, fullHeight);
     hipLaunchKernelGGL(k_toneGridStats<0>, dim3(groups), dim3(kStatsThreads), 0, mfsr_s(stream), (const pix3*)in, (const pix3*)nullptr,
                        none, s, (u64*)statsDev);
     return mfsr_launch_status("k_toneGridStats");
@@ -521,14 +521,15 @@ extern "C" int mfsr_finishToneGridStats(const mfsr_float3* finalImg, const mfsr_
                                         int fullHeight, const float* matrix, const mfsr_local_tone* lt, uint64_t* statsDev,
                                         mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg != nullptr && weight != nullptr && ((uintptr_t)finalImg & 3) == 0 && ((uintptr_t)weight & 3) == 0);
+    if (int rc = finish_check_src(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, w, h, colOffset, rowOffset, fullWidth,
+                                  fullHeight))
+        return rc;
+    // (its own: the quad loads want the three images dword-aligned)
+    MFSR_REQUIRE(((uintptr_t)finalImg & 3) == 0 && ((uintptr_t)weight & 3) == 0 && ((uintptr_t)fallback & 3) == 0);
     if (int rc = tone_stats_validate(matrix, lt, w, h, imgRowBytes, colOffset, rowOffset, fullWidth, fullHeight, statsDev)) return rc;
-    if (fallback)
-        MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0 && ((uintptr_t)fallback & 3) == 0);
     unsigned groups = 0;
     const ToneStatsArgs s = tone_stats_args(matrix, lt, w, h, imgRowBytes, colOffset, rowOffset, fullWidth, fullHeight, &groups);
-    const FinishSrc f = {(const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset,
-                         fullWidth};
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     hipLaunchKernelGGL(k_toneGridStats<1>, dim3(groups), dim3(kStatsThreads), 0, mfsr_s(stream), (const pix3*)finalImg,
                        (const pix3*)weight, f, s, (u64*)statsDev);
     return mfsr_launch_status("k_toneGridStats");
@@ -673,10 +674,9 @@ extern "C" int mfsr_finishLocalTone(const mfsr_float3* finalImg, const mfsr_floa
                                     float threshold, int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight,
                                     const float* gridDev, const mfsr_local_tone* lt, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out) && w > 0 && h > 0);
-    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
+    if (int rc = finish_check(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, outImg, outImgRowBytes, out, w, h, colOffset,
+                              rowOffset, fullWidth, fullHeight))
+        return rc;
     if (int rc = mfsr_render_validate(render)) return rc;
     MFSR_REQUIRE(!yuv_format(render->format));
     if (out)
@@ -684,8 +684,7 @@ extern "C" int mfsr_finishLocalTone(const mfsr_float3* finalImg, const mfsr_floa
     if (int rc = slice_validate(gridDev, lt, w, h, colOffset, rowOffset, fullWidth, fullHeight)) return rc;
     const RenderArgs a = render_args(render, applyGamma);
     const SliceArgs t = slice_args(gridDev, lt, colOffset, rowOffset, fullWidth, fullHeight);
-    const FinishSrc f = {(const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset,
-                         fullWidth};
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     const bool lds = lut_in_lds(render), gl = grid_in_lds(render->format);
     LOCAL_TONE_DISPATCH(k_finishLocalTone, render->format, lds, gl, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes, f,
                         (pix3*)outImg, outImgRowBytes, (uint8_t*)out, outRowBytes, w, h, a, t);

@@ -2122,76 +2122,82 @@ static size_t out_image_bytes(const mfsr_burst* b)
     return b->renderOn ? (size_t)mfsr_render_image_bytes(b->render.format, out_w(b), out_h(b)) : (size_t)out_w(b) * 6 * out_h(b);
 }
 
-// the rendered finish of output rows [r0, r0 + rows) (rows of the window when one is set); pointers are those of the whole
-// images, `out` holds dense rendered rows (two-plane formats: both planes, so r0 and rows are even)
-static int finish_rendered_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
-                                void* out, int r0, int rows, mfsr_stream_t stream)
-{
-    const mfsr_config& c = b->cfg;
-    const Layout& L = b->L;
-    const int oW = out_w(b), pitch = 12 * oW;
-    const int rowBytes = (int)out_row_bytes(b);
-    const size_t off = (size_t)r0 * pitch;
-    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
-    if (yuv_on(b)) {
-        MFSR_REQUIRE((oW & 1) == 0 && (out_h(b) & 1) == 0 && (r0 & 1) == 0 && (rows & 1) == 0);
-        char* y = out ? (char*)out + (size_t)r0 * rowBytes : nullptr;
-        char* uv = out ? (char*)out + ((size_t)out_h(b) + (size_t)(r0 / 2)) * rowBytes : nullptr;
-        return mfsr_finishRenderedYuv((const mfsr_float3*)((const char*)imgOut + off),
-                                      (const mfsr_float3*)((const char*)totalWeights + off), pitch, (const mfsr_float3*)L.fallback.ptr,
-                                      L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                      outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch, y, rowBytes, uv, rowBytes,
-                                      &b->render, oW, rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
-    }
-    if (b->localToneOn) {  // (§2.25; without a render description: uint16_t RGB of the gained linear image)
-        mfsr_render plain;
-        memset(&plain, 0, sizeof(plain));
-        plain.format = MFSR_OUT_RGB16;
-        return mfsr_finishLocalTone((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                    pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                    outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
-                                    out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : &plain, oW,
-                                    rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, b->localToneGrid, &b->localTone,
-                                    stream);
-    }
-    return mfsr_finishRendered((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                               pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                               outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
-                               out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, &b->render, oW, rows,
-                               c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, stream);
-}
-
 // A finish with a reach: a stencil on the value the finish holds -- the sharpened (§2.20) or the denoised (§2.24) finish, never
 // both -- reads R rows beyond the rows it writes.
 static bool stencil_on(const mfsr_burst* b) { return b->sharpenOn || b->denoiseOn; }
 
-// the stencil finish of output rows [r0, r0 + rows), as finish_rendered_rows; the rows [r0 - rowsAbove, r0 + rows + rowsBelow)
-// of the accumulators are complete.  Without a render description the integer output is uint16_t RGB.
-static int finish_stencil_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg,
-                               void* out, int r0, int rows, int rowsAbove, int rowsBelow, mfsr_stream_t stream)
+// Rows [r0, r0 + rows) of the burst's accumulators (of its window's, when one is set) as a finish launch or a statistics pass
+// takes them; imgOut and totalWeights are the whole images.
+struct FinishView {
+    const mfsr_float3 *acc, *wt;  // the first pixel of row r0
+    size_t off;                   // its bytes into the accumulators, and into a float output image
+    int pitch, w, rows;
+    int x0, y0;                   // the pixel of the full HR frame that the view's pixel (0, 0) is
+};
+
+static FinishView finish_view(const mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, int r0, int rows)
+{
+    FinishView v;
+    v.w = out_w(b);
+    v.rows = rows;
+    v.pitch = 12 * v.w;
+    v.off = (size_t)r0 * v.pitch;
+    v.acc = (const mfsr_float3*)((const char*)imgOut + v.off);
+    v.wt = (const mfsr_float3*)((const char*)totalWeights + v.off);
+    v.x0 = b->win.on ? b->win.x0 : 0;
+    v.y0 = (b->win.on ? b->win.y0 : 0) + r0;
+    return v;
+}
+
+// the arguments every finish entry point begins with (the accumulator pair, the fallback: the whole LR image) and the four that
+// place the view in the full frame
+#define FINISH_SOURCE(b, v) \
+    (v).acc, (v).wt, (v).pitch, (const mfsr_float3*)(b)->L.fallback.ptr, (b)->L.fallback.pitch, (b)->L.W, (b)->L.H, 0.0f, 1.0f, 0.0f, 1.0f
+#define FINISH_PLACE(b, v) (v).x0, (v).y0, (b)->L.hrW, (b)->L.hrH
+
+// The finish of output rows [r0, r0 + rows) (rows of the window when one is set) in one launch on the accumulators, whatever the
+// burst is set to.  Pointers are those of the whole images; `out` holds dense rows of the integer output: uint16_t RGB, or the
+// render description's format (two-plane formats: both planes, so r0 and rows are even).  A stencil finish reads rowsAbove /
+// rowsBelow rows beyond its own (stencil_reach), which are complete; the pointwise finishes take 0, 0.
+static int finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_float3* outImg, void* out,
+                       int r0, int rows, int rowsAbove, int rowsBelow, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
-    const Layout& L = b->L;
-    const int oW = out_w(b), pitch = 12 * oW;
+    const FinishView v = finish_view(b, imgOut, totalWeights, r0, rows);
     const int rowBytes = (int)out_row_bytes(b);
-    const size_t off = (size_t)r0 * pitch;
-    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    mfsr_float3* outF = outImg ? (mfsr_float3*)((char*)outImg + v.off) : nullptr;
+    char* outQ = out ? (char*)out + (size_t)r0 * rowBytes : nullptr;
+    const mfsr_render* render = b->renderOn ? &b->render : nullptr;  // (none: the stencil entries render plainly themselves)
+    // Which launch: denoised, sharpened, two-plane, local tone, rendered, plain.  The setters (mfsr_burst_set_sharpen, _denoise,
+    // _render, _local_tone: whichever comes second is refused) leave at most one of the first four on: never two stencils, no
+    // stencil with a two-plane format or with local tone, no local tone with a two-plane format -- and none with a host burst
+    // (cfg.uploadRing), whose bands therefore never meet it.  So the order of the first four decides nothing.
     if (b->denoiseOn) {
         b->denoisedFinishes++;
-        return mfsr_finishDenoised((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                   pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                   outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
-                                   out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : nullptr, oW,
-                                   rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, &b->denoise, rowsAbove, rowsBelow,
-                                   stream);
+        return mfsr_finishDenoised(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, render, v.w, rows, c.weightThreshold, c.applyGamma,
+                                   FINISH_PLACE(b, v), &b->denoise, rowsAbove, rowsBelow, stream);
     }
-    b->sharpenedFinishes++;
-    return mfsr_finishSharpened((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
-                                out ? (char*)out + (size_t)r0 * rowBytes : nullptr, rowBytes, b->renderOn ? &b->render : nullptr, oW,
-                                rows, c.weightThreshold, c.applyGamma, x0, y0 + r0, L.hrW, L.hrH, &b->sharpen, rowsAbove, rowsBelow,
-                                stream);
+    if (b->sharpenOn) {
+        b->sharpenedFinishes++;
+        return mfsr_finishSharpened(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, render, v.w, rows, c.weightThreshold, c.applyGamma,
+                                    FINISH_PLACE(b, v), &b->sharpen, rowsAbove, rowsBelow, stream);
+    }
+    if (yuv_on(b)) {
+        MFSR_REQUIRE((v.w & 1) == 0 && (out_h(b) & 1) == 0 && (r0 & 1) == 0 && (rows & 1) == 0);
+        char* uv = out ? (char*)out + ((size_t)out_h(b) + (size_t)(r0 / 2)) * rowBytes : nullptr;
+        return mfsr_finishRenderedYuv(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, uv, rowBytes, render, v.w, rows,
+                                      c.weightThreshold, c.applyGamma, FINISH_PLACE(b, v), stream);
+    }
+    if (b->localToneOn) {  // (§2.25; without a render description: uint16_t RGB of the gained linear image)
+        const mfsr_render plain = mfsr_plain_render();
+        return mfsr_finishLocalTone(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, render ? render : &plain, v.w, rows,
+                                    c.weightThreshold, c.applyGamma, FINISH_PLACE(b, v), b->localToneGrid, &b->localTone, stream);
+    }
+    if (render)
+        return mfsr_finishRendered(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, render, v.w, rows, c.weightThreshold, c.applyGamma,
+                                   FINISH_PLACE(b, v), stream);
+    return mfsr_finishFusedWindow(FINISH_SOURCE(b, v), outF, v.pitch, (uint16_t*)outQ, v.w, rows, c.weightThreshold, c.applyGamma,
+                                  65535.0f, FINISH_PLACE(b, v), stream);
 }
 
 // rows of the output above / below [r0, r0 + rows) that a stencil finish of those rows reads
@@ -2281,12 +2287,9 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
 static int auto_measure(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_image_stats_params* p,
                         uint64_t* statsDev, mfsr_stream_t stream)
 {
-    const Layout& L = b->L;
-    const int oW = out_w(b), pitch = 12 * oW;
-    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    const FinishView v = finish_view(b, imgOut, totalWeights, 0, out_h(b));
     MFSR_HIP_TRY(hipMemsetAsync(statsDev, 0, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS, mfsr_s(stream)));
-    TRY(mfsr_finishStats(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f,
-                         0.0f, 1.0f, oW, out_h(b), b->cfg.weightThreshold, x0, y0, L.hrW, L.hrH, p, statsDev, stream));
+    TRY(mfsr_finishStats(FINISH_SOURCE(b, v), v.w, v.rows, b->cfg.weightThreshold, FINISH_PLACE(b, v), p, statsDev, stream));
     b->autoStats.resize(MFSR_IMAGE_STATS_WORDS);
     MFSR_HIP_TRY(hipMemcpyAsync(b->autoStats.data(), statsDev, sizeof(uint64_t) * MFSR_IMAGE_STATS_WORDS, hipMemcpyDeviceToHost,
                                 mfsr_s(stream)));
@@ -2382,7 +2385,7 @@ extern "C" int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, 
 }
 
 // ---- local tone mapping in the finish: the grid of the full HR frame, measured on the accumulators with the
-//      finish's own arguments (csrc/local_tone.hip), fitted on the host, installed for finish_rendered_rows ---------------------
+//      finish's own arguments (csrc/local_tone.hip), fitted on the host, installed for finish_rows ------------------------------
 extern "C" int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* lt, const float* gridDev)
 {
     MFSR_REQUIRE(b != nullptr);
@@ -2420,11 +2423,9 @@ extern "C" int mfsr_burst_local_tone(mfsr_burst* b, const mfsr_float3* imgOut, c
     TRY(mfsr_local_tone_grid(L.hrW, L.hrH, &lt, &gx, &gy, &gz));
     TRY(flush_pending(b, stream));
     const size_t entries = (size_t)gx * gy * gz;
-    const int oW = out_w(b), pitch = 12 * oW;
-    const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
+    const FinishView v = finish_view(b, imgOut, totalWeights, 0, out_h(b));
     MFSR_HIP_TRY(hipMemsetAsync(statsDev, 0, sizeof(uint64_t) * 2 * entries, mfsr_s(stream)));
-    TRY(mfsr_finishToneGridStats(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f,
-                                 0.0f, 1.0f, oW, out_h(b), b->cfg.weightThreshold, x0, y0, L.hrW, L.hrH,
+    TRY(mfsr_finishToneGridStats(FINISH_SOURCE(b, v), v.w, v.rows, b->cfg.weightThreshold, FINISH_PLACE(b, v),
                                  b->renderOn && b->render.useMatrix ? b->render.matrix : nullptr, &lt, statsDev, stream));
     b->toneStats.resize(2 * entries);
     MFSR_HIP_TRY(hipMemcpyAsync(b->toneStats.data(), statsDev, sizeof(uint64_t) * 2 * entries, hipMemcpyDeviceToHost, mfsr_s(stream)));
@@ -2468,43 +2469,25 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
         b->finishTaken = false;
         return MFSR_OK;
     }
+    // One launch on the accumulators (finish_rows).  A stencil takes it with cfg.fused = 0 too: it cannot run in place on the
+    // chain's in/out image, and the value the fused finish holds before its gamma is bit for bit the chain's resampleFloat3 +
+    // ApplyWeighting (tests/test_parity_kernels.py::test_finishFused_equals_chain), so the unfused burst's sharpened finish is
+    // this launch as well: no second HR float image.  The local-tone finish (§2.25) likewise.
+    if (c.fused || stencil_on(b) || b->localToneOn) return finish_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
+    // the unfused chain: the reference's own sequence, with the float image as its in/out buffer
     const int pitch = 12 * out_w(b);
-    // cfg.fused = 0 too: the stencil cannot run in place on the chain's in/out image, and the value the fused finish holds
-    // before its gamma is bit for bit the chain's resampleFloat3 + ApplyWeighting (tests/test_parity_kernels.py::
-    // test_finishFused_equals_chain), so the unfused burst's sharpened finish is this launch as well: no second HR float image
-    if (stencil_on(b)) return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
-    // the local-tone finish (§2.25) likewise: one launch on the accumulators whatever cfg.fused is
-    if (b->localToneOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
-    if (b->renderOn && c.fused) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), stream);
-    if (b->renderOn) {
-        // the unfused chain up to ApplyWeighting, then the pixel body on the float image in place of GammasRGB + quantize
-        MFSR_REQUIRE(outImg != nullptr);
-        TRY(mfsr_resampleFloat3((const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, outImg, pitch, L.hrW, L.hrH,
-                                0.0f, 1.0f, 0.0f, 1.0f, stream));
-        TRY(mfsr_ApplyWeighting(outImg, imgOut, totalWeights, L.hrW, L.hrH, pitch, c.weightThreshold, stream));
-        if (yuv_on(b)) {
-            const int rowBytes = (int)out_row_bytes(b);
-            return mfsr_renderImageYuv(outImg, pitch, outImg, pitch, out16, rowBytes,
-                                       out16 ? (char*)out16 + (size_t)L.hrH * rowBytes : nullptr, rowBytes, L.hrW, L.hrH, &b->render,
-                                       c.applyGamma, stream);
-        }
-        return mfsr_renderImage(outImg, pitch, outImg, pitch, out16, (int)out_row_bytes(b), L.hrW, L.hrH, &b->render, c.applyGamma,
-                                stream);
-    }
-    if (c.fused && b->win.on) {
-        return mfsr_finishFusedWindow(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
-                                      0.0f, 1.0f, 0.0f, 1.0f, outImg, pitch, out16, b->win.w, b->win.h, c.weightThreshold,
-                                      c.applyGamma, 65535.0f, b->win.x0, b->win.y0, L.hrW, L.hrH, stream);
-    }
-    if (c.fused) {
-        return mfsr_finishFused(imgOut, totalWeights, pitch, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H,
-                                0.0f, 1.0f, 0.0f, 1.0f, outImg, pitch, out16, L.hrW, L.hrH, c.weightThreshold,
-                                c.applyGamma, 65535.0f, stream);
-    }
-    MFSR_REQUIRE(outImg != nullptr);  // the unfused chain needs the float image as its in/out buffer
+    MFSR_REQUIRE(outImg != nullptr);
     TRY(mfsr_resampleFloat3((const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, outImg, pitch, L.hrW, L.hrH,
                             0.0f, 1.0f, 0.0f, 1.0f, stream));
     TRY(mfsr_ApplyWeighting(outImg, imgOut, totalWeights, L.hrW, L.hrH, pitch, c.weightThreshold, stream));
+    if (b->renderOn) {  // the pixel body on the float image in place of GammasRGB + quantize
+        const int rowBytes = (int)out_row_bytes(b);
+        if (yuv_on(b))
+            return mfsr_renderImageYuv(outImg, pitch, outImg, pitch, out16, rowBytes,
+                                       out16 ? (char*)out16 + (size_t)L.hrH * rowBytes : nullptr, rowBytes, L.hrW, L.hrH, &b->render,
+                                       c.applyGamma, stream);
+        return mfsr_renderImage(outImg, pitch, outImg, pitch, out16, rowBytes, L.hrW, L.hrH, &b->render, c.applyGamma, stream);
+    }
     if (c.applyGamma) TRY(mfsr_GammasRGB(outImg, L.hrW, L.hrH, pitch, stream));
     if (out16) TRY(mfsr_quantize(outImg, pitch, out16, nullptr, L.hrW, L.hrH, 65535.0f, stream));
     return MFSR_OK;
@@ -2518,26 +2501,13 @@ extern "C" int mfsr_burst_finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, 
 {
     MFSR_REQUIRE(b && imgOut && totalWeights && (outImg || out16));
     MFSR_REQUIRE(b->haveRef);
-    const mfsr_config& c = b->cfg;
-    const Layout& L = b->L;
-    MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= L.hrH);
+    MFSR_REQUIRE(row0 >= 0 && rows > 0 && row0 + rows <= b->L.hrH);
     MFSR_REQUIRE(!b->win.on);  // (stripes of whole-frame images)
     if (yuv_on(b)) MFSR_REQUIRE((row0 & 1) == 0 && (rows & 1) == 0);  // whole 2 x 2 chroma blocks
     TRY(flush_pending(b, stream));
-    if (stencil_on(b)) {
-        int above, below;
-        stencil_reach(b, row0, rows, &above, &below);
-        return finish_stencil_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
-    }
-    if (b->renderOn || b->localToneOn) return finish_rendered_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, stream);
-    const int pitch = 12 * L.hrW;
-    const size_t off = (size_t)row0 * pitch;
-    return mfsr_finishFusedRows((const mfsr_float3*)((const char*)imgOut + off),
-                                (const mfsr_float3*)((const char*)totalWeights + off), pitch,
-                                (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                outImg ? (mfsr_float3*)((char*)outImg + off) : nullptr, pitch,
-                                out16 ? out16 + (size_t)row0 * L.hrW * 3 : nullptr, L.hrW, rows, c.weightThreshold,
-                                c.applyGamma, 65535.0f, row0, L.hrH, stream);
+    int above = 0, below = 0;
+    if (stencil_on(b)) stencil_reach(b, row0, rows, &above, &below);
+    return finish_rows(b, imgOut, totalWeights, outImg, out16, row0, rows, above, below, stream);
 }
 
 // ---- host-frame bursts (cfg.uploadRing) --------------------------------------------------------------------------
@@ -2780,7 +2750,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // (only where the image is small against the burst -- x2: 199 MB down for 265 MB up.  At x4 the download, 796 MB, is as
     // long as the burst's compute: it has to start with the first band, or the NEXT burst's finish waits for it to leave
     // out16Dev: 18.1 instead of 17.0 ms per burst with two bands)
-    const int oW = out_w(b), oH = out_h(b);  // the window's extent when one is set
+    const int oH = out_h(b);  // the window's height when one is set
     const size_t rowBytes = out_row_bytes(b);  // rendered bytes when a render is set
     const double outBytes = (double)out_image_bytes(b), inBytes = (double)L.W * L.H * 2.0 * c.frames;
     if (b->hostBusy && nBandsBusy >= 1 && nBandsBusy < nBands && outBytes <= 1.5 * inBytes) nBands = nBandsBusy;
@@ -2831,15 +2801,21 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // downloaded after band i has been fused (every band but the last is a multiple of 16 rows), the last one after the loop.
     // lagR0 < 0: no band waits.
     int lagI = -1, lagR0 = -1, lagR1 = -1;
-    auto finish_lagged = [&]() -> int {
-        int above, below;
-        stencil_reach(b, lagR0, lagR1 - lagR0, &above, &below);
-        TRY(finish_stencil_rows(b, imgOut, totalWeights, nullptr, out16Dev, lagR0, lagR1 - lagR0, above, below, stream));
-        if (!b->evBand[lagI]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[lagI], hipEventDisableTiming));
-        MFSR_HIP_TRY(hipEventRecord(b->evBand[lagI], mfsr_s(stream)));
-        MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[lagI], 0));
-        MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)lagR0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)lagR0 * rowBytes,
-                                      rowBytes, rowBytes, (size_t)(lagR1 - lagR0), hipMemcpyDeviceToHost, b->downStream));
+    // band i = rows [r0, r1): its finish, the event that lets the download stream follow it, and its rows on their way to the host
+    auto finish_band = [&](int i, int r0, int r1) -> int {
+        int above = 0, below = 0;
+        if (stencil_on(b)) stencil_reach(b, r0, r1 - r0, &above, &below);
+        TRY(finish_rows(b, imgOut, totalWeights, nullptr, out16Dev, r0, r1 - r0, above, below, stream));
+        if (!b->evBand[i]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[i], hipEventDisableTiming));
+        MFSR_HIP_TRY(hipEventRecord(b->evBand[i], mfsr_s(stream)));
+        MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[i], 0));
+        MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)r0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)r0 * rowBytes,
+                                      rowBytes, rowBytes, (size_t)(r1 - r0), hipMemcpyDeviceToHost, b->downStream));
+        if (yuv_on(b)) {  // the band's chroma rows (r0 is a multiple of 16, r1 one or the even height)
+            const size_t c0 = ((size_t)oH + (size_t)(r0 / 2)) * rowBytes;
+            MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + c0, rowBytes, (const char*)out16Dev + c0, rowBytes, rowBytes,
+                                          (size_t)((r1 - r0) / 2), hipMemcpyDeviceToHost, b->downStream));
+        }
         return MFSR_OK;
     };
     for (int i = 0; i < nBands; i++) {
@@ -2865,34 +2841,15 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
             }
         }
         if (stencil_on(b)) {
-            if (lagR0 >= 0) TRY(finish_lagged());
+            if (lagR0 >= 0) TRY(finish_band(lagI, lagR0, lagR1));
             lagI = i;
             lagR0 = r0;
             lagR1 = r1;
             continue;
         }
-        const size_t off = (size_t)r0 * 12 * oW;
-        const int x0 = b->win.on ? b->win.x0 : 0, y0 = b->win.on ? b->win.y0 : 0;
-        if (b->renderOn) {
-            TRY(finish_rendered_rows(b, imgOut, totalWeights, nullptr, out16Dev, r0, r1 - r0, stream));
-        } else {
-            TRY(mfsr_finishFusedWindow((const mfsr_float3*)((const char*)imgOut + off), (const mfsr_float3*)((const char*)totalWeights + off),
-                                       12 * oW, (const mfsr_float3*)L.fallback.ptr, L.fallback.pitch, L.W, L.H, 0.0f, 1.0f, 0.0f, 1.0f,
-                                       nullptr, 12 * oW, out16Dev + (size_t)r0 * oW * 3, oW, r1 - r0, c.weightThreshold,
-                                       c.applyGamma, 65535.0f, x0, y0 + r0, L.hrW, L.hrH, stream));
-        }
-        if (!b->evBand[i]) MFSR_HIP_TRY(hipEventCreateWithFlags(&b->evBand[i], hipEventDisableTiming));
-        MFSR_HIP_TRY(hipEventRecord(b->evBand[i], mfsr_s(stream)));
-        MFSR_HIP_TRY(hipStreamWaitEvent(b->downStream, b->evBand[i], 0));
-        MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + (size_t)r0 * rowBytes, rowBytes, (const char*)out16Dev + (size_t)r0 * rowBytes,
-                                      rowBytes, rowBytes, (size_t)(r1 - r0), hipMemcpyDeviceToHost, b->downStream));
-        if (yuv_on(b)) {  // the band's chroma rows (r0 is a multiple of 16, r1 one or the even height)
-            const size_t c0 = ((size_t)oH + (size_t)(r0 / 2)) * rowBytes;
-            MFSR_HIP_TRY(hipMemcpy2DAsync((char*)out16Host + c0, rowBytes, (const char*)out16Dev + c0, rowBytes, rowBytes,
-                                          (size_t)((r1 - r0) / 2), hipMemcpyDeviceToHost, b->downStream));
-        }
+        TRY(finish_band(i, r0, r1));
     }
-    if (lagR0 >= 0) TRY(finish_lagged());
+    if (lagR0 >= 0) TRY(finish_band(lagI, lagR0, lagR1));
     if (heldGroup && b->copyStream) {
         // upload slots whose raw frame these launches were the last to read
         for (int gi = 0; gi < 2; gi++) {

@@ -25,10 +25,9 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
 
 template <int FORMAT, int LDS>
 __global__ void __launch_bounds__(LDS ? 1024 : 256)
-    k_finishRendered(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
-                     const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
+    k_finishRendered(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch, FinishSrc f,
                      pix3* __restrict__ outImg, int outPitch, uint8_t* __restrict__ out, int outRowBytes, int width, int height,
-                     float threshold, int rowOffset, int fullHeight, int colOffset, int fullWidth, RenderArgs r)
+                     RenderArgs r)
 {
     __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
     const float* lut = stage_lut<LDS>(r, s_lut);
@@ -38,7 +37,6 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
     const pix3* valRow = row_ptr(finalImg, imgPitch, y);
     const pix3* wRow = row_ptr(weight, imgPitch, y);
     // the body of k_finishFused up to its gamma (finish_value, finish_common.hpp: shared with the statistics of section 2.23)
-    const FinishSrc f = {fallback, fbPitch, fbW, fbH, u0, u1, v0, v1, threshold, rowOffset, fullHeight, colOffset, fullWidth};
     auto src = [&](int x) { return finish_value(valRow[x], wRow[x], x, y, f); };
     render_span<FORMAT>(src, outImg ? row_ptr(outImg, outPitch, y) : nullptr, out ? out + (size_t)outRowBytes * (size_t)y : nullptr,
                         x0, width, r, lut);
@@ -81,21 +79,10 @@ int mfsr_render_validate(const mfsr_render* r)
     return MFSR_OK;
 }
 
-#define RENDER_DISPATCH(KERNEL, format, lds, ...)                                                                   \
-    do {                                                                                                            \
-        const dim3 block(64, (lds) ? 16 : 4);                                                                       \
-        const dim3 grid(mfsr_cdiv(mfsr_cdiv(w, (format) == MFSR_OUT_RGB8 ? 4 : 1), 64), mfsr_cdiv(h, block.y));     \
-        switch (((format) << 1) | ((lds) ? 1 : 0)) {                                                                \
-            case 0: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;   \
-            case 1: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;   \
-            case 2: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 3: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 4: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;   \
-            case 5: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;   \
-            case 6: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break; \
-        }                                                                                                           \
-    } while (0)
+// 64 x 4 lanes (64 x 16 where the workgroup stages the table), one or (RGB8) four pixels of a row per lane; w, h, stream: the caller's
+#define RENDER_DISPATCH(KERNEL, format, lds, ...)                                                                                    \
+    FORMAT_LUT_DISPATCH(KERNEL, dim3(mfsr_cdiv(mfsr_cdiv(w, (format) == MFSR_OUT_RGB8 ? 4 : 1), 64), mfsr_cdiv(h, (lds) ? 16 : 4)), \
+                        dim3(64, (lds) ? 16 : 4), format, lds, __VA_ARGS__)
 
 extern "C" int mfsr_renderImage(const mfsr_float3* in, int inRowBytes, mfsr_float3* outImg, int outImgRowBytes, void* out,
                                 int outRowBytes, int w, int h, const mfsr_render* render, int applyGamma, mfsr_stream_t stream)
@@ -120,20 +107,17 @@ extern "C" int mfsr_finishRendered(const mfsr_float3* finalImg, const mfsr_float
                                    const mfsr_render* render, int w, int h, float threshold, int applyGamma, int colOffset,
                                    int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out) && w > 0 && h > 0);
-    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
+    if (int rc = finish_check(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, outImg, outImgRowBytes, out, w, h, colOffset,
+                              rowOffset, fullWidth, fullHeight))
+        return rc;
     if (int rc = mfsr_render_validate(render)) return rc;
     MFSR_REQUIRE(!yuv_format(render->format));  // two planes: mfsr_renderImageYuv / mfsr_finishRenderedYuv
     if (out)
         if (int rc = check_out(render->format, out, outRowBytes, w)) return rc;
     const RenderArgs a = render_args(render, applyGamma);
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     const bool lds = lut_in_lds(render);
-    RENDER_DISPATCH(k_finishRendered, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes,
-                    (const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
-                    outRowBytes, w, h, threshold, rowOffset, fullHeight, colOffset, fullWidth, a);
+    RENDER_DISPATCH(k_finishRendered, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes, f, (pix3*)outImg,
+                    outImgRowBytes, (uint8_t*)out, outRowBytes, w, h, a);
     return mfsr_launch_status("finishRendered");
 }

@@ -1,6 +1,7 @@
 // render_common.hpp -- the pixel body of the rendered finish and the host checks of its output, shared
-// by render.hip (k_renderImage, k_finishRendered) and sharpen.hip (k_sharpenImage, k_finishSharpened): one definition, so
-// that a sharpened finish renders and stores exactly as the rendered one does.  Both files compile with -ffp-contract=off.
+// by render.hip (k_renderImage, k_finishRendered), sharpen.hip, denoise.hip and local_tone.hip (their image and finish kernels):
+// one definition, so that a sharpened finish renders and stores exactly as the rendered one does, and one (format, table form)
+// launch switch (FORMAT_LUT_DISPATCH, at the end).  All of them compile with -ffp-contract=off.
 #pragma once
 
 #include <cmath>
@@ -189,3 +190,19 @@ int check_out(int format, const void* out, int outRowBytes, int width)
 }
 
 }  // namespace
+
+// one launch of KERNEL<format, lds> over `grid` workgroups of `block` lanes on the caller's `stream`: the (format, table form)
+// switch of every single-plane rendering kernel (render.hip, sharpen.hip, denoise.hip)
+#define FORMAT_LUT_DISPATCH(KERNEL, grid, block, format, lds, ...)                                                              \
+    do {                                                                                                                        \
+        switch (((format) << 1) | ((lds) ? 1 : 0)) {                                                                            \
+            case 0: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 0>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 1: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 1>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 2: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 0>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;     \
+            case 3: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 1>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;     \
+            case 4: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 0>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 5: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 1>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;    \
+            case 6: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 0>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break;  \
+            default: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 1>), (grid), (block), 0, mfsr_s(stream), __VA_ARGS__); break; \
+        }                                                                                                                       \
+    } while (0)

@@ -124,32 +124,17 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
 
 template <int BITS, int LDS>
 __global__ void __launch_bounds__(LDS ? 1024 : 256)
-    k_finishRenderedYuv(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
-                        const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
+    k_finishRenderedYuv(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch, FinishSrc f,
                         pix3* __restrict__ outImg, int outPitch, uint8_t* __restrict__ outY, int yRowBytes,
-                        uint8_t* __restrict__ outUV, int uvRowBytes, int width, int height, float threshold, int rowOffset,
-                        int fullHeight, int colOffset, int fullWidth, RenderArgs r, YuvArgs ya)
+                        uint8_t* __restrict__ outUV, int uvRowBytes, int width, int height, RenderArgs r, YuvArgs ya)
 {
     __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
     const float* lut = stage_lut<LDS>(r, s_lut);
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int yPair = blockIdx.y * blockDim.y + threadIdx.y;
     if (x0 >= width || 2 * yPair >= height) return;
-    // the body of k_finishRendered up to its tone curve, expression for expression (a stripe or window is the crop of the whole)
-    auto src = [&](int x, int y) {
-        const pix3 val = row_ptr(finalImg, imgPitch, y)[x];
-        const pix3 w = row_ptr(weight, imgPitch, y)[x];
-        pix3 inout = {0.0f, 0.0f, 0.0f};
-        if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
-            const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
-            const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
-            inout = sample_pix3(fallback, fbPitch, fbW, fbH, u, v);
-        }
-        inout.x = apply_weight_f(inout.x, val.x, w.x, threshold);
-        inout.y = apply_weight_f(inout.y, val.y, w.y, threshold);
-        inout.z = apply_weight_f(inout.z, val.z, w.z, threshold);
-        return inout;
-    };
+    // k_finishRendered's value up to its tone curve (finish_value: one definition; a stripe or window is the crop of the whole)
+    auto src = [&](int x, int y) { return finish_value(row_ptr(finalImg, imgPitch, y)[x], row_ptr(weight, imgPitch, y)[x], x, y, f); };
     yuv_block<BITS>(src, outImg, outPitch, outY, yRowBytes, outUV, uvRowBytes, x0, yPair, width, r, ya, lut);
 }
 
@@ -230,20 +215,18 @@ extern "C" int mfsr_finishRenderedYuv(const mfsr_float3* finalImg, const mfsr_fl
                                       int uvRowBytes, const mfsr_render* render, int w, int h, float threshold, int applyGamma,
                                       int colOffset, int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || outY || outUV) && w > 0 && h > 0 && (w & 1) == 0 && (h & 1) == 0);
-    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
+    if (int rc = finish_check(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, outImg, outImgRowBytes, outY ? outY : outUV,
+                              w, h, colOffset, rowOffset, fullWidth, fullHeight))
+        return rc;
+    MFSR_REQUIRE((w & 1) == 0 && (h & 1) == 0);
     if (int rc = mfsr_render_validate(render)) return rc;
     MFSR_REQUIRE(yuv_format(render->format));
     if (int rc = check_planes(render->format, outY, yRowBytes, outUV, uvRowBytes, w)) return rc;
     const RenderArgs a = render_args(render, applyGamma);
     const YuvArgs ya = yuv_args(render);
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     const bool lds = lut_in_lds(render);
-    YUV_DISPATCH(k_finishRenderedYuv, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes,
-                 (const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outImgRowBytes, (uint8_t*)outY, yRowBytes,
-                 (uint8_t*)outUV, uvRowBytes, w, h, threshold, rowOffset, fullHeight, colOffset, fullWidth, a, ya);
+    YUV_DISPATCH(k_finishRenderedYuv, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes, f, (pix3*)outImg,
+                 outImgRowBytes, (uint8_t*)outY, yRowBytes, (uint8_t*)outUV, uvRowBytes, w, h, a, ya);
     return mfsr_launch_status("finishRenderedYuv");
 }

@@ -134,30 +134,16 @@ __global__ void __launch_bounds__(kLanes)
 
 template <int FORMAT, int LDS>
 __global__ void __launch_bounds__(kLanes)
-    k_finishSharpened(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch,
-                      const pix3* __restrict__ fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0, float v1,
+    k_finishSharpened(const pix3* __restrict__ finalImg, const pix3* __restrict__ weight, int imgPitch, FinishSrc f,
                       pix3* __restrict__ outImg, int outPitch, uint8_t* __restrict__ out, int outRowBytes, int width, int height,
-                      float threshold, int rowOffset, int fullHeight, int colOffset, int fullWidth, SharpenArgs a, RenderArgs r)
+                      SharpenArgs a, RenderArgs r)
 {
     __shared__ float s_lut[LDS ? kLdsLutMax + 1 : 1];
     __shared__ __attribute__((aligned(16))) float s_s[3][kSH][kSW];
     __shared__ __attribute__((aligned(16))) float s_h[3][kSH][kTW];
     const float* lut = stage_lut<LDS>(r, s_lut);
-    // the body of k_finishRendered's src, expression for expression; y may be negative (rowsAbove): the pointers are 64-bit
-    auto fetch = [&](int x, int y) {
-        const pix3 val = *(const pix3*)((const char*)finalImg + (long long)imgPitch * y + 12LL * x);
-        const pix3 w = *(const pix3*)((const char*)weight + (long long)imgPitch * y + 12LL * x);
-        pix3 inout = {0.0f, 0.0f, 0.0f};
-        if (fallback && (w.x < threshold || w.y < threshold || w.z < threshold)) {
-            const float u = u0 + (u1 - u0) * (((float)(x + colOffset) + 0.5f) / (float)fullWidth);
-            const float v = v0 + (v1 - v0) * (((float)(y + rowOffset) + 0.5f) / (float)fullHeight);
-            inout = sample_pix3(fallback, fbPitch, fbW, fbH, u, v);
-        }
-        inout.x = apply_weight_f(inout.x, val.x, w.x, threshold);
-        inout.y = apply_weight_f(inout.y, val.y, w.y, threshold);
-        inout.z = apply_weight_f(inout.z, val.z, w.z, threshold);
-        return inout;
-    };
+    // k_finishRendered's value (finish_value_at: one definition); y may be negative (rowsAbove)
+    auto fetch = [&](int x, int y) { return finish_value_at(finalImg, weight, imgPitch, x, y, f); };
     sharpen_tile<FORMAT>(fetch, s_s, s_h, outImg, outPitch, out, outRowBytes, width, height, a, r, lut);
 }
 
@@ -230,7 +216,7 @@ extern "C" int mfsr_sharpenImage(const mfsr_float3* in, int inRowBytes, mfsr_flo
     if (int rc = stencil_image_args(in, inRowBytes, outImg, outImgRowBytes, out, w, h)) return rc;
     if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
     MFSR_REQUIRE(sharpen_on(sharpen));
-    const mfsr_render plain = plain_render();
+    const mfsr_render plain = mfsr_plain_render();
     if (int rc = stencil_render(render, &plain, &render)) return rc;
     if (int rc = stencil_outputs_apart(in, image_span(inRowBytes, h, 12, w), outImg, outImgRowBytes, out, outRowBytes, render->format, w, h))
         return rc;
@@ -254,16 +240,16 @@ extern "C" int mfsr_finishSharpened(const mfsr_float3* finalImg, const mfsr_floa
         return rc;
     if (int rc = mfsr_sharpen_validate(sharpen)) return rc;
     MFSR_REQUIRE(sharpen_on(sharpen));
-    const mfsr_render plain = plain_render();
+    const mfsr_render plain = mfsr_plain_render();
     if (int rc = stencil_render(render, &plain, &render)) return rc;
     if (int rc = stencil_finish_apart(finalImg, weight, imgRowBytes, rowsAbove, rowsBelow, outImg, outImgRowBytes, out, outRowBytes,
                                       render->format, w, h))
         return rc;
     const RenderArgs ra = render_args(render, applyGamma);
     const SharpenArgs sa = sharpen_args(sharpen, -rowsAbove, h - 1 + rowsBelow);
+    const FinishSrc f = finish_src(fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, threshold, colOffset, rowOffset, fullWidth, fullHeight);
     const bool lds = stencil_lut_in_lds(render);
-    SHARPEN_DISPATCH(k_finishSharpened, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes,
-                     (const pix3*)fallback, fbRowBytes, fbW, fbH, u0, u1, v0, v1, (pix3*)outImg, outImgRowBytes, (uint8_t*)out,
-                     outRowBytes, w, h, threshold, rowOffset, fullHeight, colOffset, fullWidth, sa, ra);
+    SHARPEN_DISPATCH(k_finishSharpened, render->format, lds, (const pix3*)finalImg, (const pix3*)weight, imgRowBytes, f, (pix3*)outImg,
+                     outImgRowBytes, (uint8_t*)out, outRowBytes, w, h, sa, ra);
     return mfsr_launch_status("finishSharpened");
 }

@@ -9,15 +9,6 @@
 
 namespace {
 
-// without a render description: the plain finish's steps
-mfsr_render plain_render()
-{
-    mfsr_render r;
-    memset(&r, 0, sizeof(r));
-    r.format = MFSR_OUT_RGB16;
-    return r;
-}
-
 bool ranges_overlap(const void* a, long long aBytes, const void* b, long long bBytes)
 {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -70,17 +61,15 @@ int stencil_image_args(const void* in, int inRowBytes, const void* outImg, int o
     return MFSR_OK;
 }
 
-// the arguments of mfsr_finishSharpened / mfsr_finishDenoised before their descriptions
+// the arguments of mfsr_finishSharpened / mfsr_finishDenoised before their descriptions: every finish's (finish_check), and
+// the reach lies inside the full frame
 int stencil_finish_args(const void* finalImg, const void* weight, int imgRowBytes, const void* fallback, int fbRowBytes, int fbW,
                         int fbH, const void* outImg, int outImgRowBytes, const void* out, int w, int h, int colOffset,
                         int rowOffset, int fullWidth, int fullHeight, int rowsAbove, int rowsBelow)
 {
-    MFSR_REQUIRE(finalImg && weight && (outImg || out) && w > 0 && h > 0);
-    MFSR_REQUIRE((long long)imgRowBytes >= 12LL * w && (imgRowBytes & 3) == 0);
-    if (outImg) MFSR_REQUIRE((long long)outImgRowBytes >= 12LL * w && (outImgRowBytes & 3) == 0);
-    if (fallback) MFSR_REQUIRE(fbW > 0 && fbH > 0 && (long long)fbRowBytes >= 12LL * fbW && (fbRowBytes & 3) == 0);
-    MFSR_REQUIRE(rowOffset >= 0 && fullHeight >= rowOffset + h);
-    MFSR_REQUIRE(colOffset >= 0 && fullWidth >= colOffset + w);
+    if (int rc = finish_check(finalImg, weight, imgRowBytes, fallback, fbRowBytes, fbW, fbH, outImg, outImgRowBytes, out, w, h, colOffset,
+                              rowOffset, fullWidth, fullHeight))
+        return rc;
     MFSR_REQUIRE(rowsAbove >= 0 && rowsAbove <= rowOffset && rowsBelow >= 0 && rowsBelow <= fullHeight - rowOffset - h);
     return MFSR_OK;
 }
@@ -100,18 +89,5 @@ int stencil_finish_apart(const void* finalImg, const void* weight, int imgRowByt
 
 // one launch of KERNEL<format, lds> over tiles of tileW x tileH output pixels, `lanes` lanes per workgroup; w, h and stream
 // are the caller's
-#define STENCIL_DISPATCH(KERNEL, tileW, tileH, lanes, format, lds, ...)                                                     \
-    do {                                                                                                                    \
-        const dim3 block(lanes);                                                                                            \
-        const dim3 grid(mfsr_cdiv(w, tileW), mfsr_cdiv(h, tileH));                                                          \
-        switch (((format) << 1) | ((lds) ? 1 : 0)) {                                                                        \
-            case 0: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 1: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB16, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 2: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
-            case 3: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;     \
-            case 4: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 5: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGBA8, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;    \
-            case 6: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 0>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break;  \
-            default: hipLaunchKernelGGL((KERNEL<MFSR_OUT_RGB10A2, 1>), grid, block, 0, mfsr_s(stream), __VA_ARGS__); break; \
-        }                                                                                                                   \
-    } while (0)
+#define STENCIL_DISPATCH(KERNEL, tileW, tileH, lanes, format, lds, ...) \
+    FORMAT_LUT_DISPATCH(KERNEL, dim3(mfsr_cdiv(w, tileW), mfsr_cdiv(h, tileH)), dim3(lanes), format, lds, __VA_ARGS__)

@@ -37,7 +37,6 @@ EXCLUDED = {
     "mfsr_accumulateSuperResFull2": "two-frame form of mfsr_accumulateSuperResFullN, which the row-stripe test runs whole-frame",
     "mfsr_accumulateSuperResFullN": "the whole-frame side of test_kernel_edges_gpu.py::test_accumulateSuperResFullRows",
     "mfsr_accumulateSuperResFullWindow": WINDOW,
-    "mfsr_finishFusedWindow": "column-window form behind mfsr_finishFusedRows (swept: the same kernel with colOffset 0); windows in tests/test_window_gpu.py",
     "mfsr_CreateFlowFieldFromTilesBase": "device-prealign form, bit-compared in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",
     "mfsr_CreateFlowFieldWarped": "bit-compared with the swept chain in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",
     "mfsr_lucasKanadeIterationWarped": "bit-compared with mfsr_lucasKanadeIterationFused in test_parity_kernels.py::test_lucasKanadeIterationWarped_is_bit_identical",

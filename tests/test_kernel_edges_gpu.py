@@ -1047,6 +1047,47 @@ def test_finishFusedRows(hip):
         assert np.array_equal(gq, want_q), f"out16 rows [{r0}, {r1})"
 
 
+def test_finishFusedWindow(hip):
+    """outImg and out16 of a 70 x 22 launch at (colOffset, rowOffset) = (6, 10) of a 96 x 48 frame equal that rectangle of
+    mfsr_finishFused on the whole frame bit for bit, with and without the gamma: a 48 x 24 fallback, a third of the pixels with
+    weights under the threshold (they take the resample at the full frame's coordinate), one weight of exactly zero inside the
+    window.  The launch is neither a multiple of the 64 x 4 block nor aligned to it; bytes around its outputs keep the canary."""
+    W, H, x0, y0, w, h = 96, 48, 6, 10, 70, 22
+    g = rng(92)
+    fin = g.random((H, W, 3), dtype=np.float32) * 4
+    wt = 0.5 + g.random((H, W, 3), dtype=np.float32) * 4
+    low = (np.add.outer(np.arange(H), np.arange(W)) % 3) == 0
+    wt[low] = np.array([5e-4, 2e-4, 0.7], np.float32)
+    wt[y0 + 5, x0 + 9] = 0
+    inside = low[y0:y0 + h, x0:x0 + w]
+    assert 0.3 < inside.mean() < 0.37 and (wt[y0:y0 + h, x0:x0 + w] == 0).any()
+    fb = g.random((24, 48, 3), dtype=np.float32)
+    bf, pf, _ = _pad2d(fin, POISON)
+    bw, _, _ = _pad2d(wt, POISON)
+    bb, pb, _ = _pad2d(fb, POISON)
+    for gamma in (0, 1):
+        D = DevBufs(hip)
+        wo, po, _ = _pad2d(np.full((H, W, 3), CANARY, np.float32), SENTINEL)
+        wq = np.full((H, W, 3), 0xC3C3, np.uint16)
+        hip.L.finishFused(D.up(bf, True), D.up(bw, True), pf, D.up(bb, True), pb, 48, 24, 0.0, 1.0, 0.0, 1.0, D.up(wo), po, D.up(wq), W, H,
+                          1e-3, gamma, 65535.0, None)
+        D.finish("mfsr_finishFused")
+        D = DevBufs(hip)
+        go, gpo, rowb = _pad2d(np.full((h, w, 3), CANARY, np.float32), SENTINEL, rows_around=1)
+        want_o = go.copy()
+        gq = np.full((h + 2, w, 3), 0xC3C3, np.uint16)
+        off = y0 * pf + 12 * x0
+        hip.L.finishFusedWindow(D.up(bf, True) + off, D.up(bw, True) + off, pf, D.up(bb, True), pb, 48, 24, 0.0, 1.0, 0.0, 1.0,
+                                D.up(go) + gpo, gpo, D.up(gq) + w * 6, w, h, 1e-3, gamma, 65535.0, x0, y0, W, H, None)
+        D.finish("mfsr_finishFusedWindow")
+        want_o[1:-1, :rowb] = wo[y0:y0 + h, 12 * x0:12 * (x0 + w)]
+        want_q = np.full((h + 2, w, 3), 0xC3C3, np.uint16)
+        want_q[1:-1] = wq[y0:y0 + h, x0:x0 + w]
+        assert not np.array_equal(wq, np.full_like(wq, 0xC3C3))
+        assert np.array_equal(go, want_o), f"outImg, gamma {gamma}"
+        assert np.array_equal(gq, want_q), f"out16, gamma {gamma}"
+
+
 def test_ComputeDerivatives2Rows(hip):
     """Rows [row0, row0 + rows) equal those rows of mfsr_ComputeDerivatives2Kernel bit for bit (MIRROR addressing at both
     ends: row0 = 0 and the last rows); all other rows keep the canary."""
@@ -1132,6 +1173,7 @@ def test_checkFlowBound_and_maxAbsFlowY(hip, width, rows):
 ROW_STRIPE_TESTS = {
     "mfsr_accumulateSuperResFullRows": "test_accumulateSuperResFullRows",
     "mfsr_finishFusedRows": "test_finishFusedRows",
+    "mfsr_finishFusedWindow": "test_finishFusedWindow",
     "mfsr_ComputeDerivatives2Rows": "test_ComputeDerivatives2Rows",
     "mfsr_checkFlowBound": "test_checkFlowBound_and_maxAbsFlowY",
     "mfsr_maxAbsFlowY": "test_checkFlowBound_and_maxAbsFlowY",
