@@ -14,7 +14,8 @@
  *   - cudaTextureObject_t  ->  mfsr_tex2d {ptr, pitch, width, height} by value
  *     (linear filtering, normalised coordinates; MIRROR addressing for images,
  *     CLAMP for flow / parameter fields -- stated per function),
- *   - the module constant c_cfaPattern -> mfsr_set_cfa_pattern(),
+ *   - the module constant c_cfaPattern -> mfsr_set_cfa_pattern(), read by these
+ *     reference-shaped entry points only (bursts and frame streams take cfg.cfa),
  *   - grid/block shapes chosen by the library,
  *   - one trailing mfsr_stream_t (a hipStream_t; NULL = default stream).
  *
@@ -76,8 +77,10 @@ int mfsr_version(void);
 int mfsr_device_count(void);
 
 /* ---- A0: c_cfaPattern[2][2], DeBayerKernels.cu:40-41 ---------------------- */
-/* pattern[0..3] = {[0][0],[0][1],[1][0],[1][1]}; RGGB = {0,1,1,2}.  Process-
- * wide state like the reference's module constant; read at launch time. */
+/* pattern[0..3] = {[0][0],[0][1],[1][0],[1][1]}; RGGB = {0,1,1,2}; entries 0 .. MFSR_WHITE, else MFSR_E_INVALID.
+ * Process-wide state like the reference's module constant, read at launch time by the reference-shaped entry points
+ * (mfsr_deBayer*, mfsr_prepareFrame*, mfsr_accumulate*, mfsr_robustnessMaskGroup).  A burst (mfsr_burst_*) or frame stream
+ * (mfsr_stream_*) takes cfg.cfa instead, checked the same way by its create call, and neither reads nor writes this one. */
 int mfsr_set_cfa_pattern(const int32_t pattern[4]);
 int mfsr_get_cfa_pattern(int32_t pattern[4]);
 

@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256)
 // 0: straight kernel with the ocml expf (tight parity tests); 1: straight kernel with
 // v_exp_f32; 2 (default): additionally the x2 strip kernel of accumulate_fast.hip where
 // it applies.
-static int g_accumulate_fast = 2;
+static std::atomic<int> g_accumulate_fast{2};
 extern "C" int mfsr_set_accumulate_fast_exp(int enable)
 {
     g_accumulate_fast = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
@@ -107,21 +107,21 @@ extern "C" int mfsr_set_accumulate_fast_exp(int enable)
 }
 extern "C" int mfsr_get_accumulate_fast_exp(void) { return g_accumulate_fast; }
 
-int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate2x_strip(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
                                        int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
                                        mfsr_stream_t stream);  // accumulate_fast.hip
 
-int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate4x_tile(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
                                       int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
                                       mfsr_stream_t stream);  // accumulate_fast.hip
 
-int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate2x_burst(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
@@ -164,7 +164,7 @@ extern "C" int mfsr_accumulateImagesSuperRes(const uint16_t* dataIn, mfsr_float3
 }
 
 // one frame, HR window w (whole frame: 0, 0, scale*dimX, scale*dimY)
-static int accumulate_full_win(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+static int accumulate_full_win(int cfa, const uint16_t* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                                const mfsr_float4* certaintyMask, mfsr_tex2d kernelParam, mfsr_tex2d shifts,
                                mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
                                int strideMask, const HrWindow& w, mfsr_stream_t stream)
@@ -174,12 +174,12 @@ static int accumulate_full_win(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr
                                  w.rel ? w.x1 - w.x0 : dimX * scale, strideOut, strideMask);
     if (rc) return rc;
     if (g_accumulate_fast == 2 && scale == 2 &&
-        mfsr_try_launch_accumulate2x_strip(1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
+        mfsr_try_launch_accumulate2x_strip(cfa, 1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
                                            blackLevel, dimX, dimY, strideOut, strideMask, 0, w.y0, w.y1, w.x0, w.x1, w.rel,
                                            stream) == 1)
         return mfsr_launch_status("accumulateSuperResFull(strip)");
     if (g_accumulate_fast == 2 && scale == 4 &&
-        mfsr_try_launch_accumulate4x_tile(1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
+        mfsr_try_launch_accumulate4x_tile(cfa, 1, &dataIn, imgOut, totalWeights, &certaintyMask, kernelParam, &shifts, whiteLevel,
                                           blackLevel, dimX, dimY, strideOut, strideMask, 0, w.y0, w.y1, w.x0, w.x1, w.rel,
                                           stream) == 1)
         return mfsr_launch_status("accumulateSuperResFull(x4 tile)");
@@ -190,19 +190,19 @@ static int accumulate_full_win(const uint16_t* dataIn, mfsr_float3* imgOut, mfsr
     if (win && g_accumulate_fast)
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, true, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
                            (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
-                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, w.x0, w.x1);
+                           strideOut, strideMask, cfa, rowBegin, rowEnd, w.x0, w.x1);
     else if (win)
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, false, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
                            (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
-                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, w.x0, w.x1);
+                           strideOut, strideMask, cfa, rowBegin, rowEnd, w.x0, w.x1);
     else if (g_accumulate_fast)
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, true>), grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut,
                            (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX, dimY, scale,
-                           strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, 0, 0);
+                           strideOut, strideMask, cfa, rowBegin, rowEnd, 0, 0);
     else
         hipLaunchKernelGGL((k_accumulateSuperRes<GEOM_FULL, false>), grid, block, 0, mfsr_s(stream), dataIn,
                            (pix3*)imgOut, (pix3*)totalWeights, (const float4*)certaintyMask, kernelParam, shifts, lv, dimX,
-                           dimY, scale, strideOut, strideMask, mfsr_cfa_packed(), rowBegin, rowEnd, 0, 0);
+                           dimY, scale, strideOut, strideMask, cfa, rowBegin, rowEnd, 0, 0);
     return mfsr_launch_status("accumulateSuperResFull");
 }
 
@@ -211,7 +211,7 @@ extern "C" int mfsr_accumulateSuperResFull(const uint16_t* dataIn, mfsr_float3* 
                                            mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale,
                                            int strideOut, int strideMask, mfsr_stream_t stream)
 {
-    return accumulate_full_win(dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY,
+    return accumulate_full_win(mfsr_cfa_packed(), dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY,
                                scale, strideOut, strideMask, HrWindow{0, 0, scale * dimX, scale * dimY, 0}, stream);
 }
 
@@ -252,7 +252,7 @@ extern "C" int mfsr_accumulateSuperResFull2(const uint16_t* dataIn0, const uint1
 // Only the HR window w is touched: rows [y0, y1) (stripe-sharded bursts, whole-frame accumulators) or a rectangle with
 // window-relative accumulators (zoom windows); every pixel of it gets exactly what the whole-frame call gives it.  The
 // kernels are chosen from the frame's geometry, never from the window's.
-static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
+static int accumulate_group_win(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut, mfsr_float3* totalWeights,
                                 const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
                                 mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
                                 int strideMask, int accumulatorsUndefined, const HrWindow& w, mfsr_stream_t stream)
@@ -264,14 +264,14 @@ static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr
     }
     const int fresh = accumulatorsUndefined ? 1 : 0;
     if (g_accumulate_fast == 2 && scale == 2) {
-        const int r = mfsr_try_launch_accumulate2x_strip(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+        const int r = mfsr_try_launch_accumulate2x_strip(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
                                                          whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, w.y0, w.y1,
                                                          w.x0, w.x1, w.rel, stream);
         if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(strip)");
         if (r < 0) return MFSR_E_INVALID;
     }
     if (g_accumulate_fast == 2 && scale == 4) {
-        const int r = mfsr_try_launch_accumulate4x_tile(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+        const int r = mfsr_try_launch_accumulate4x_tile(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
                                                         whiteLevel, blackLevel, dimX, dimY, strideOut, strideMask, fresh, w.y0, w.y1,
                                                         w.x0, w.x1, w.rel, stream);
         if (r == 1) return mfsr_launch_status("accumulateSuperResFullN(x4 tile)");
@@ -279,10 +279,10 @@ static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr
     }
     if (nFrames > 2) {
         // no kernel of this geometry takes the whole group: two frames, then the rest
-        const int rc = accumulate_group_win(2, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel,
+        const int rc = accumulate_group_win(cfa, 2, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel,
                                             dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined, w, stream);
         if (rc) return rc;
-        return accumulate_group_win(nFrames - 2, dataIn + 2, imgOut, totalWeights, certaintyMask + 2, kernelParam, shifts + 2,
+        return accumulate_group_win(cfa, nFrames - 2, dataIn + 2, imgOut, totalWeights, certaintyMask + 2, kernelParam, shifts + 2,
                                     whiteLevel, blackLevel, dimX, dimY, scale, strideOut, strideMask, 0, w, stream);
     }
     if (fresh) {
@@ -298,7 +298,7 @@ static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr
         }
     }
     for (int n = 0; n < nFrames; n++) {
-        const int rc = accumulate_full_win(dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], whiteLevel,
+        const int rc = accumulate_full_win(cfa, dataIn[n], imgOut, totalWeights, certaintyMask[n], kernelParam, shifts[n], whiteLevel,
                                            blackLevel, dimX, dimY, scale, strideOut, strideMask, w, stream);
         if (rc) return rc;
     }
@@ -307,6 +307,20 @@ static int accumulate_group_win(int nFrames, const uint16_t* const* dataIn, mfsr
 
 // Only HR rows [rowBegin, rowEnd) are touched (stripe-sharded bursts): rowBegin a multiple of 16, rowEnd a multiple
 // of 16 or the frame's last row + 1; every pixel of the window gets exactly what the whole-frame call gives it.
+int mfsr_cfa::accumulateSuperResFullRows(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                         mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam,
+                                         const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY,
+                                         int scale, int strideOut, int strideMask, int accumulatorsUndefined, int rowBegin, int rowEnd,
+                                         mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= MFSR_MAX_FUSE_GROUP && dataIn && certaintyMask && shifts);
+    MFSR_REQUIRE(scale >= 1 && scale <= 8);
+    const int hrH = scale * dimY;
+    MFSR_REQUIRE(rowBegin >= 0 && rowBegin < rowEnd && rowEnd <= hrH && (rowBegin % 16) == 0 && ((rowEnd % 16) == 0 || rowEnd == hrH));
+    return accumulate_group_win(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
+                                dimY, scale, strideOut, strideMask, accumulatorsUndefined,
+                                HrWindow{0, rowBegin, scale * dimX, rowEnd, 0}, stream);
+}
 extern "C" int mfsr_accumulateSuperResFullRows(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                                mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                                mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
@@ -314,23 +328,18 @@ extern "C" int mfsr_accumulateSuperResFullRows(int nFrames, const uint16_t* cons
                                                int strideMask, int accumulatorsUndefined, int rowBegin, int rowEnd,
                                                mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(nFrames >= 1 && nFrames <= MFSR_MAX_FUSE_GROUP && dataIn && certaintyMask && shifts);
-    MFSR_REQUIRE(scale >= 1 && scale <= 8);
-    const int hrH = scale * dimY;
-    MFSR_REQUIRE(rowBegin >= 0 && rowBegin < rowEnd && rowEnd <= hrH && (rowBegin % 16) == 0 && ((rowEnd % 16) == 0 || rowEnd == hrH));
-    return accumulate_group_win(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
-                                dimY, scale, strideOut, strideMask, accumulatorsUndefined,
-                                HrWindow{0, rowBegin, scale * dimX, rowEnd, 0}, stream);
+    return mfsr_cfa::accumulateSuperResFullRows(mfsr_cfa_packed(), nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+                                                whiteLevel, blackLevel, dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined,
+                                                rowBegin, rowEnd, stream);
 }
 
 // the HR window [x0, x0+w) x [y0, y0+h) with window-relative accumulators (pitch strideOut >= 12 w, 16-byte aligned):
 // bit for bit that rectangle of the whole-frame call (mfsr_window_check states the constraints)
-extern "C" int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
-                                                 mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
-                                                 mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
-                                                 mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
-                                                 int strideMask, int accumulatorsUndefined, int x0, int y0, int w, int h,
-                                                 mfsr_stream_t stream)
+int mfsr_cfa::accumulateSuperResFullWindow(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                           mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam,
+                                           const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY,
+                                           int scale, int strideOut, int strideMask, int accumulatorsUndefined, int x0, int y0, int w,
+                                           int h, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(nFrames >= 1 && nFrames <= MFSR_MAX_FUSE_GROUP && dataIn && certaintyMask && shifts);
     MFSR_REQUIRE(scale >= 1 && scale <= 8 && dimX > 0 && dimY > 0);
@@ -341,8 +350,19 @@ extern "C" int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* co
     }
     MFSR_REQUIRE(mfsr_window_ok(hrW, hrH, x0, y0, w, h));
     MFSR_REQUIRE((strideOut & 15) == 0 && ((uintptr_t)imgOut & 15) == 0 && ((uintptr_t)totalWeights & 15) == 0);
-    return accumulate_group_win(nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
+    return accumulate_group_win(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts, whiteLevel, blackLevel, dimX,
                                 dimY, scale, strideOut, strideMask, accumulatorsUndefined, HrWindow{x0, y0, x0 + w, y0 + h, 1}, stream);
+}
+extern "C" int mfsr_accumulateSuperResFullWindow(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                                 mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
+                                                 mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
+                                                 mfsr_float3 blackLevel, int dimX, int dimY, int scale, int strideOut,
+                                                 int strideMask, int accumulatorsUndefined, int x0, int y0, int w, int h,
+                                                 mfsr_stream_t stream)
+{
+    return mfsr_cfa::accumulateSuperResFullWindow(mfsr_cfa_packed(), nFrames, dataIn, imgOut, totalWeights, certaintyMask, kernelParam, shifts,
+                                                  whiteLevel, blackLevel, dimX, dimY, scale, strideOut, strideMask, accumulatorsUndefined, x0,
+                                                  y0, w, h, stream);
 }
 
 extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
@@ -363,7 +383,7 @@ extern "C" int mfsr_accumulateSuperResFullN(int nFrames, const uint16_t* const* 
 // descriptors: imgOut / totalWeights float3 (scale*dimX) x (scale*dimY), certaintyMasks float4 at half the raw size (one
 // pitch for all), the raw frames dense uint16_t rows of dimX samples.
 // (out16 != null: the finishing form, mfsr_accumulateSuperResBurstFinish below, whose finish arguments have been checked)
-static int accumulate_burst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+static int accumulate_burst(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
                             const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                             mfsr_float3 blackLevel, int scale, int accumulatorsUndefined, const mfsr_float3* fallback, int fbPitch,
                             int fbW, int fbH, float u0, float u1, float v0, float v1, float threshold, uint16_t* out16,
@@ -385,7 +405,7 @@ static int accumulate_burst(int nFrames, const uint16_t* const* dataIn, mfsr_tex
         if (rc) return rc;
     }
     if (g_accumulate_fast != 2 || scale != 2) return MFSR_E_UNSUPPORTED;
-    const int r = mfsr_try_launch_accumulate2x_burst(nFrames, dataIn, (mfsr_float3*)imgOut.ptr, (mfsr_float3*)totalWeights.ptr, masks,
+    const int r = mfsr_try_launch_accumulate2x_burst(cfa, nFrames, dataIn, (mfsr_float3*)imgOut.ptr, (mfsr_float3*)totalWeights.ptr, masks,
                                                      kernelParam, shifts, whiteLevel, blackLevel, dimX, dimY, imgOut.pitch,
                                                      certaintyMasks[0].pitch, accumulatorsUndefined ? 1 : 0, fallback, fbPitch, fbW,
                                                      fbH, u0, u1, v0, v1, threshold, out16, stream);
@@ -393,26 +413,34 @@ static int accumulate_burst(int nFrames, const uint16_t* const* dataIn, mfsr_tex
     return r < 0 ? MFSR_E_INVALID : MFSR_E_UNSUPPORTED;
 }
 
+int mfsr_cfa::accumulateSuperResBurst(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                      const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                      mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                      mfsr_stream_t stream)
+{
+    return accumulate_burst(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
+                            accumulatorsUndefined, nullptr, 0, 0, 0, 0.0f, 1.0f, 0.0f, 1.0f, 0.0f, nullptr, stream);
+}
 extern "C" int mfsr_accumulateSuperResBurst(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
                                             const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
                                             mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
                                             mfsr_stream_t stream)
 {
-    return accumulate_burst(nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
-                            accumulatorsUndefined, nullptr, 0, 0, 0, 0.0f, 1.0f, 0.0f, 1.0f, 0.0f, nullptr, stream);
+    return mfsr_cfa::accumulateSuperResBurst(mfsr_cfa_packed(), nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts,
+                                             whiteLevel, blackLevel, scale, accumulatorsUndefined, stream);
 }
 
 // The burst form with the plain uint16_t finish of the whole frame inside the launch (the finishing tile kernel and the ring
 // launch of accumulate_fast.hip): the accumulators as above, out16 bit for bit what mfsr_finishFusedWindow gives from them.
 // The finish arguments are validated as mfsr_finishFusedWindow validates them; what is not the plain whole-frame finish is
 // MFSR_E_UNSUPPORTED, and a refusal of either kind touches nothing.
-extern "C" int mfsr_accumulateSuperResBurstFinish(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut,
-                                                  mfsr_tex2d totalWeights, const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam,
-                                                  const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale,
-                                                  int accumulatorsUndefined, mfsr_tex2d fallback, float u0, float u1, float v0,
-                                                  float v1, float threshold, uint16_t* out16, int out16Width, int out16Height,
-                                                  int applyGamma, float maxOut, int colOffset, int rowOffset, int fullWidth,
-                                                  int fullHeight, mfsr_stream_t stream)
+int mfsr_cfa::accumulateSuperResBurstFinish(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut,
+                                            mfsr_tex2d totalWeights, const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam,
+                                            const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale,
+                                            int accumulatorsUndefined, mfsr_tex2d fallback, float u0, float u1, float v0, float v1,
+                                            float threshold, uint16_t* out16, int out16Width, int out16Height, int applyGamma,
+                                            float maxOut, int colOffset, int rowOffset, int fullWidth, int fullHeight,
+                                            mfsr_stream_t stream)
 {
     const int width = out16Width, height = out16Height;
     MFSR_REQUIRE(out16 && width > 0 && height > 0);
@@ -425,7 +453,20 @@ extern "C" int mfsr_accumulateSuperResBurstFinish(int nFrames, const uint16_t* c
     if (applyGamma || maxOut != 65535.0f || colOffset != 0 || rowOffset != 0 || width != fullWidth || height != fullHeight ||
         width != imgOut.width || height != imgOut.height || ((uintptr_t)out16 & 7) != 0)
         return MFSR_E_UNSUPPORTED;
-    return accumulate_burst(nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
+    return accumulate_burst(cfa, nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam, shifts, whiteLevel, blackLevel, scale,
                             accumulatorsUndefined, (const mfsr_float3*)fallback.ptr, fallback.pitch, fallback.width, fallback.height, u0,
                             u1, v0, v1, threshold, out16, stream);
+}
+extern "C" int mfsr_accumulateSuperResBurstFinish(int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut,
+                                                  mfsr_tex2d totalWeights, const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam,
+                                                  const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale,
+                                                  int accumulatorsUndefined, mfsr_tex2d fallback, float u0, float u1, float v0,
+                                                  float v1, float threshold, uint16_t* out16, int out16Width, int out16Height,
+                                                  int applyGamma, float maxOut, int colOffset, int rowOffset, int fullWidth,
+                                                  int fullHeight, mfsr_stream_t stream)
+{
+    return mfsr_cfa::accumulateSuperResBurstFinish(mfsr_cfa_packed(), nFrames, dataIn, imgOut, totalWeights, certaintyMasks, kernelParam,
+                                                   shifts, whiteLevel, blackLevel, scale, accumulatorsUndefined, fallback, u0, u1, v0, v1,
+                                                   threshold, out16, out16Width, out16Height, applyGamma, maxOut, colOffset, rowOffset,
+                                                   fullWidth, fullHeight, stream);
 }

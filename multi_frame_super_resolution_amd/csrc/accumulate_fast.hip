@@ -2164,9 +2164,30 @@ __global__ void __launch_bounds__(256, tile_waves_x4(NF))
 
 constexpr int pack_cfa(int c00, int c01, int c10, int c11) { return c00 | (c01 << 2) | (c10 << 4) | (c11 << 6); }
 
-int g_strip_xcd_remap = 1;  // MFSR_XCD_REMAP=0: launch order (A/B); see k_accumulate2xTile
-int g_margin_sites = 1;  // mfsr_set_margin_sites / MFSR_MARGIN_SITES=0: the x2 margin kernels' per-tap body (A/B)
-int g_strip_use_tile = 1;  // MFSR_STRIP_TILE: 0 register-only strip kernel, 1 LDS tile kernel (fields at HR/4)
+// the 2-bit form of a packed launch word (colours 0..3: the callers refuse the others first)
+constexpr int pack_cfa(int cp) { return pack_cfa(cp & 0xff, (cp >> 8) & 0xff, (cp >> 16) & 0xff, (cp >> 24) & 0xff); }
+bool cfa_rgb(int cp)  // every colour of the launch word is red, green or blue
+{
+    for (int i = 0; i < 4; i++)
+        if (((cp >> (8 * i)) & 0xff) > MFSR_BLUE) return false;
+    return true;
+}
+
+bool strip_xcd_remap()  // MFSR_XCD_REMAP=0: launch order (A/B); see k_accumulate2xTile
+{
+    static const bool on = !mfsr_env_is0("MFSR_XCD_REMAP");
+    return on;
+}
+bool strip_use_tile()  // MFSR_STRIP_TILE=0: the register-only strip kernel instead of the LDS tile kernel (fields at HR/4)
+{
+    static const bool on = !mfsr_env_is0("MFSR_STRIP_TILE");
+    return on;
+}
+MfsrKnob g_margin_sites;  // mfsr_set_margin_sites / MFSR_MARGIN_SITES=0: the x2 margin kernels' per-tap body (A/B)
+bool margin_sites()
+{
+    return g_margin_sites.get([] { return mfsr_env_is0("MFSR_MARGIN_SITES") ? 0 : 1; }) == 1;
+}
 
 // true when the LDS tile kernel serves this geometry (fields at HR/4, whole tiles)
 bool tile_kernel_ok(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
@@ -2174,7 +2195,7 @@ bool tile_kernel_ok(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     // (the tile kernels address the raw sites with 32-bit byte offsets: frames below 4 GiB)
     return kp.width == sh.width && kp.height == sh.height && kp.width * 4 == hrW && kp.height * 4 == hrH && kp.width >= 4 &&
-           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && g_strip_use_tile == 1;
+           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && strip_use_tile();
 }
 
 // the same for fields at HR/2 (the monochrome pipeline: tracking at the raw resolution)
@@ -2182,7 +2203,7 @@ bool tile_kernel_ok_fr2(mfsr_tex2d kp, mfsr_tex2d sh, int dimX, int dimY)
 {
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     return kp.width == sh.width && kp.height == sh.height && kp.width * 2 == hrW && kp.height * 2 == hrH && kp.width >= 4 &&
-           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && g_strip_use_tile == 1;
+           (dimX % 4) == 0 && (dimY % 4) == 0 && (uint64_t)dimX * (uint64_t)dimY * 2u < (1ull << 32) && strip_use_tile();
 }
 
 // the tile launch of a window: its first tile column (x0 / tileW) and how many it covers (whole frame: 0, all)
@@ -2210,7 +2231,7 @@ void launch_tile(dim3 grid, dim3 block, hipStream_t st, const TileFrames<NF>& fr
 {
     const int tilesX = (int)grid.x, tilesY = (int)grid.y;
     // (a window: the XCD-aware order is taken over the window's tiles; the order does not change any pixel's bits)
-    const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
+    const int tilesPerXcd = strip_xcd_remap() ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
     const dim3 g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
     if (wl.on)
         hipLaunchKernelGGL((k_accumulate2xTile<CFA, NF, FR, true>), g1, block, 0, st, fr, imgOut, tw, kp, glv, lv, dimX, dimY,
@@ -2300,7 +2321,7 @@ long long margin_pixel_count(int hrW, int hrH)
 template <int SCALE>
 bool margin_sites_ok(int dimX, int dimY, int strideMask)
 {
-    return SCALE == 2 && g_margin_sites == 1 && (long long)dimX * dimY * 2 < (1LL << 31) &&
+    return SCALE == 2 && margin_sites() && (long long)dimX * dimY * 2 < (1LL << 31) &&
            (long long)strideMask * ((dimY + 1) / 2) < (1LL << 31);
 }
 
@@ -2343,20 +2364,6 @@ void launch_margin_n(hipStream_t st, const TileFrames<NF>& fr, pix3* pI, pix3* p
         if (margin_sites_ok<SCALE>(dimX, dimY, strideMask)) return launch(std::true_type{});
     }
     launch(std::false_type{});
-}
-
-void read_env_once()
-{
-    static const bool env_read = [] {
-        const char* e = getenv("MFSR_STRIP_TILE");
-        if (e && e[0] >= '0' && e[0] <= '1') g_strip_use_tile = e[0] - '0';
-        const char* x = getenv("MFSR_XCD_REMAP");
-        if (x && (x[0] == '0' || x[0] == '1')) g_strip_xcd_remap = x[0] - '0';
-        const char* m = getenv("MFSR_MARGIN_SITES");
-        if (m && m[0] == '0') g_margin_sites = 0;
-        return true;
-    }();
-    (void)env_read;
 }
 
 // black / white levels in the two forms the kernels take
@@ -2409,20 +2416,16 @@ int for_cfa(int packed, F f)
 // three or four), -1 if a memset of the fresh-accumulator mode failed.
 // With two to four frames the LDS tile kernel fuses all of them in one pass over the accumulators; the other
 // geometries take at most two, frame after frame.
-int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate2x_strip(int cp, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
                                        int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
                                        mfsr_stream_t stream)
 {
-    read_env_once();
     if (nFrames < 1 || nFrames > 4) return 0;
-    int cfa[4];
-    mfsr_get_cfa_pattern(cfa);
-    for (int i = 0; i < 4; i++)
-        if (cfa[i] > MFSR_BLUE) return 0;
-    const int packed2 = pack_cfa(cfa[0], cfa[1], cfa[2], cfa[3]);
+    if (!cfa_rgb(cp)) return 0;
+    const int packed2 = pack_cfa(cp);
     // layout requirements of the vectorised accumulator access
     if ((dimX & 1) || ((uintptr_t)imgOut & 15) || ((uintptr_t)totalWeights & 15) || (strideOut & 15)) return 0;
     if (dimX < 2 * STRIP_MARGIN || dimY < 2 * STRIP_MARGIN) return 0;
@@ -2439,7 +2442,6 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
     hipStream_t st = mfsr_s(stream);
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
-    const int cp = mfsr_cfa_packed();
     // two to four frames in one pass over the accumulators: the LDS tile kernel's geometry only
     bool pair = nFrames >= 2;
     for (int n = 0; n < nFrames; n++) pair = pair && tile_kernel_ok(kernelParam, shifts[n], dimX, dimY);
@@ -2512,18 +2514,15 @@ int mfsr_try_launch_accumulate2x_strip(int nFrames, const uint16_t* const* dataI
 // launch (k_accumulate2xTileBurst) and ONE margin launch; bit for bit what nFrames / 4 calls of the function above give.
 // Returns 1 if launched, 0 if the configuration is not the burst kernel's (nothing was touched), -1 if a memset of the
 // fresh-accumulator mode failed.
-int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate2x_burst(int cp, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                        mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                        mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                        mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask, int fresh,
                                        const mfsr_float3* fallback, int fbPitch, int fbW, int fbH, float u0, float u1, float v0,
                                        float v1, float threshold, uint16_t* out16, mfsr_stream_t stream)
 {
-    read_env_once();
     if (nFrames < 8 || nFrames > 4 * TILE_BURST_GROUPS || (nFrames & 3)) return 0;
-    int cfa[4];
-    mfsr_get_cfa_pattern(cfa);
-    const int packed2 = pack_cfa(cfa[0], cfa[1], cfa[2], cfa[3]);
+    const int packed2 = pack_cfa(cp);
     if ((dimX & 1) || ((uintptr_t)imgOut & 15) || ((uintptr_t)totalWeights & 15) || (strideOut & 15)) return 0;
     if (dimX < 2 * STRIP_MARGIN || dimY < 2 * STRIP_MARGIN) return 0;
     for (int n = 0; n < nFrames; n++)
@@ -2534,12 +2533,11 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
     const int hrW = 2 * dimX, hrH = 2 * dimY;
     const WinLaunch wlc = win_launch(HrWindow{0, 0, hrW, hrH, 0}, hrW, 256);
     const int tilesX = wlc.tilesX, tilesY = mfsr_cdiv(hrH, 4);
-    const int tilesPerXcd = g_strip_xcd_remap ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
+    const int tilesPerXcd = strip_xcd_remap() ? mfsr_cdiv(tilesX * tilesY, 8) : 0;
     const dim3 block(64, 4), g1(tilesPerXcd ? 8 * tilesPerXcd : tilesX * tilesY);
     hipStream_t st = mfsr_s(stream);
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
-    const int cp = mfsr_cfa_packed();
     BurstFrames fr;
     fill_frames(fr.f, dataIn, certaintyMask, shifts, nFrames);
     for (int n = nFrames; n < 4 * TILE_BURST_GROUPS; n++) fr.f[n] = fr.f[0];  // (never read: nGroups bounds the loop)
@@ -2576,27 +2574,22 @@ int mfsr_try_launch_accumulate2x_burst(int nFrames, const uint16_t* const* dataI
 
 extern "C" int mfsr_set_margin_sites(int enable)
 {
-    read_env_once();  // (a later first launch must not put the environment's value over this one)
-    g_margin_sites = enable ? 1 : 0;
+    g_margin_sites.set(enable ? 1 : 0);
     return MFSR_OK;
 }
 
 // x4: returns 1 if the x4 tile kernel took the nFrames (1 to 4) frames, 0 if the geometry is not its
 // (fields at HR/8, even dimensions); the caller then uses the straight kernel.
-int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+int mfsr_try_launch_accumulate4x_tile(int cp, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
                                       mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask,
                                       mfsr_tex2d kernelParam, const mfsr_tex2d* shifts, mfsr_float3 whiteLevel,
                                       mfsr_float3 blackLevel, int dimX, int dimY, int strideOut, int strideMask,
                                       int fresh, int rowBegin, int rowEnd, int colBegin, int colEnd, int relative,
                                       mfsr_stream_t stream)
 {
-    read_env_once();
-    if (nFrames < 1 || nFrames > 4 || !g_strip_use_tile) return 0;
-    int cfa[4];
-    mfsr_get_cfa_pattern(cfa);
-    for (int i = 0; i < 4; i++)
-        if (cfa[i] > MFSR_BLUE) return 0;
-    const int packed2 = pack_cfa(cfa[0], cfa[1], cfa[2], cfa[3]);
+    if (nFrames < 1 || nFrames > 4 || !strip_use_tile()) return 0;
+    if (!cfa_rgb(cp)) return 0;
+    const int packed2 = pack_cfa(cp);
     const int hrW = 4 * dimX, hrH = 4 * dimY;
     if ((dimX & 1) || (dimY & 1) || ((uintptr_t)imgOut & 15) || ((uintptr_t)totalWeights & 15) || (strideOut & 15)) return 0;
     if (hrW < 4 * STRIP_MARGIN || hrH < 4 * STRIP_MARGIN) return 0;
@@ -2610,7 +2603,6 @@ int mfsr_try_launch_accumulate4x_tile(int nFrames, const uint16_t* const* dataIn
     hipStream_t st = mfsr_s(stream);
     pix3* pI = (pix3*)imgOut;
     pix3* pT = (pix3*)totalWeights;
-    const int cp = mfsr_cfa_packed();
     // HR row window [rowBegin, rowEnd): whole 2-row tile rows; columns [colBegin, colEnd): the 512-pixel tile columns that meet them
     const int tileY0 = rowBegin / 2;
     const WinLaunch wlc = win_launch(HrWindow{colBegin, rowBegin, colEnd, rowEnd, relative}, hrW, 512);

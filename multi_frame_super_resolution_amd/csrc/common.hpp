@@ -7,8 +7,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 
 #include "../../include/mfsr.h"
 
@@ -67,14 +69,119 @@ static inline mfsr_render mfsr_plain_render()
     return r;
 }
 
-// ---- CFA pattern: packed 4 x 8 bit, [y%2][x%2] -> bits ((y&1)*2+(x&1))*8 -----
 // Frame batches: the per-frame pointer arguments of a kernel for up to MFSR_BATCH_MAX frames, appended to its argument list; a
 // launch with gridDim.z > 1 takes frame blockIdx.z's pointers from the table (a scalar load), a plain launch ignores it.
 #define MFSR_BATCH_MAX 4
 struct MfsrBatch {
     const void* p[MFSR_BATCH_MAX][6];
 };
-int mfsr_cfa_packed();  // defined in debayer.hip (process-wide state)
+
+// internal C++ functions shared between the library's translation units: not part of its exported symbols
+#define MFSR_INTERNAL __attribute__((visibility("hidden")))
+
+// ---- environment knobs (A/B switches) --------------------
+// The three parses the knobs use.  A knob without a setter keeps its value in a function-local `static const`.
+static inline bool mfsr_env_is0(const char* name)  // set and begins with '0'
+{
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+}
+static inline bool mfsr_env_is1(const char* name)  // set and begins with '1'
+{
+    const char* e = getenv(name);
+    return e && e[0] == '1';
+}
+static inline int mfsr_env_int(const char* name, int dflt)  // atoi of the value, dflt when unset
+{
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// A knob that also has a setter (mfsr_set_*): the first get() takes the environment's value (fromEnv), unless set() came first;
+// set() overrides it for good.  Values are >= 0.  Rank threads read and set it concurrently, hence the atomic.
+class MfsrKnob {
+public:
+    template <class FromEnv>
+    int get(FromEnv fromEnv)
+    {
+        int v = v_.load(std::memory_order_relaxed);
+        if (v < 0) {
+            const int e = fromEnv();
+            if (v_.compare_exchange_strong(v, e, std::memory_order_relaxed)) v = e;  // (lost to a set(): v holds its value)
+        }
+        return v;
+    }
+    void set(int v) { v_.store(v, std::memory_order_relaxed); }
+
+private:
+    std::atomic<int> v_{-1};
+};
+
+// compute units of the current device, cached per device (256 where the query fails)
+static inline int mfsr_device_cus()
+{
+    constexpr int kDevs = 64;
+    static std::atomic<int> cache[kDevs];
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) return 256;
+    if ((cus = cache[dev].load(std::memory_order_relaxed)) > 0) return cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 256;
+    cache[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+}
+
+// ---- CFA pattern: packed 4 x 8 bit, [y%2][x%2] -> bits ((y&1)*2+(x&1))*8 -----
+// Every kernel takes the pattern as a packed launch argument.  A burst or frame stream packs cfg.cfa once at create and
+// passes it down (the mfsr_cfa:: forms below); the process-wide pattern of mfsr_set_cfa_pattern, the port of the reference's
+// module constant, serves the reference-shaped extern "C" entry points only, which forward mfsr_cfa_packed().
+// *packed = the launch word of `pattern`; MFSR_E_INVALID (mfsr_set_cfa_pattern's refusal) for an entry outside 0..MFSR_WHITE
+static inline int mfsr_pack_cfa(const int32_t pattern[4], int* packed)
+{
+    MFSR_REQUIRE(pattern != nullptr);
+    for (int i = 0; i < 4; i++) MFSR_REQUIRE(pattern[i] >= 0 && pattern[i] <= MFSR_WHITE);
+    *packed = pattern[0] | (pattern[1] << 8) | (pattern[2] << 16) | (pattern[3] << 24);
+    return MFSR_OK;
+}
+MFSR_INTERNAL int mfsr_cfa_packed();  // the process-wide pattern, packed; debayer.hip
+// The launchers with the packed pattern as their first argument; everything else as the extern "C" entry point of the same name
+// (include/mfsr.h), which forwards here.  prepareFrames serves mfsr_prepareFrameFused / FusedBatch / MeansBatch (means).
+namespace mfsr_cfa {
+MFSR_INTERNAL int deBayersSubSample3(int cfa, const uint16_t* dataIn, mfsr_float3* imgOut, float maxVal, int dimX, int dimY, int strideOut,
+                                     mfsr_stream_t stream);
+MFSR_INTERNAL int prepareFrames(int cfa, int n, const mfsr_prepare_frame* f, int halfPitch, float maxVal, int dimX, int dimY, int pyr0Pitch,
+                                int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream, bool means);
+MFSR_INTERNAL int deBayerGreenKernel(int cfa, int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage, int strideOut,
+                                     mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream);
+MFSR_INTERNAL int deBayerRedBlueKernel(int cfa, int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage,
+                                       int strideOut, mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream);
+MFSR_INTERNAL int deBayerFused(int cfa, const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
+                               mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream);
+MFSR_INTERNAL int deBayerFusedRing(int cfa, const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
+                                   mfsr_stream_t stream);
+MFSR_INTERNAL int accumulateSuperResFullRows(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                             mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam,
+                                             const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY,
+                                             int scale, int strideOut, int strideMask, int accumulatorsUndefined, int rowBegin, int rowEnd,
+                                             mfsr_stream_t stream);
+MFSR_INTERNAL int accumulateSuperResFullWindow(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_float3* imgOut,
+                                               mfsr_float3* totalWeights, const mfsr_float4* const* certaintyMask, mfsr_tex2d kernelParam,
+                                               const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int dimX, int dimY,
+                                               int scale, int strideOut, int strideMask, int accumulatorsUndefined, int x0, int y0, int w,
+                                               int h, mfsr_stream_t stream);
+MFSR_INTERNAL int accumulateSuperResBurst(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut, mfsr_tex2d totalWeights,
+                                          const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam, const mfsr_tex2d* shifts,
+                                          mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale, int accumulatorsUndefined,
+                                          mfsr_stream_t stream);
+MFSR_INTERNAL int accumulateSuperResBurstFinish(int cfa, int nFrames, const uint16_t* const* dataIn, mfsr_tex2d imgOut,
+                                                mfsr_tex2d totalWeights, const mfsr_tex2d* certaintyMasks, mfsr_tex2d kernelParam,
+                                                const mfsr_tex2d* shifts, mfsr_float3 whiteLevel, mfsr_float3 blackLevel, int scale,
+                                                int accumulatorsUndefined, mfsr_tex2d fallback, float u0, float u1, float v0, float v1,
+                                                float threshold, uint16_t* out16, int out16Width, int out16Height, int applyGamma,
+                                                float maxOut, int colOffset, int rowOffset, int fullWidth, int fullHeight,
+                                                mfsr_stream_t stream);
+MFSR_INTERNAL int robustnessMaskGroup(int cfa, int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf,
+                                      int refRowBytes, int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal,
+                                      float alpha, float beta, float thresholdM, mfsr_stream_t stream);
+}  // namespace mfsr_cfa
 int mfsr_reference_fused();  // the switch of mfsr_set_reference_fused, kernel_field.hip (process-wide state)
 int mfsr_robustness_group();  // mfsr_set_robustness_group and the fast robustness kernel both on, robustness.hip (process-wide state)
 int mfsr_robustness_group_fits(int h, int flowRowBytes, int meansRowBytes, int maskRowBytes);  // images below 2 GiB (k_robustnessGroup's offsets)

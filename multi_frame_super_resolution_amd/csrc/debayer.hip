@@ -7,25 +7,27 @@
 #include "half_pixel.hpp"
 
 // ---- A0: c_cfaPattern (DeBayerKernels.cu:40-41) -------------------------------
-// Process-wide like the reference's module constant, but passed to every kernel
-// as a packed launch argument so that concurrent streams never race on a
-// __constant__ symbol.
-static int g_cfa[4] = {MFSR_RED, MFSR_GREEN, MFSR_GREEN, MFSR_BLUE};
+// Process-wide like the reference's module constant, for the reference-shaped entry points (include/mfsr.h), each of which
+// forwards it to the mfsr_cfa:: launcher of its name.  Bursts and frame streams pass their own cfg.cfa to those launchers and
+// neither read nor write it.  One packed word (the kernels' launch argument), so that a set and a get on two threads never see
+// half a pattern.
+static std::atomic<int> g_cfa{MFSR_RED | (MFSR_GREEN << 8) | (MFSR_GREEN << 16) | (MFSR_BLUE << 24)};
 
-int mfsr_cfa_packed() { return (g_cfa[0] & 0xff) | ((g_cfa[1] & 0xff) << 8) | ((g_cfa[2] & 0xff) << 16) | ((g_cfa[3] & 0xff) << 24); }
+int mfsr_cfa_packed() { return g_cfa.load(std::memory_order_relaxed); }
 
 extern "C" int mfsr_set_cfa_pattern(const int32_t pattern[4])
 {
-    MFSR_REQUIRE(pattern != nullptr);
-    for (int i = 0; i < 4; i++) MFSR_REQUIRE(pattern[i] >= 0 && pattern[i] <= MFSR_WHITE);
-    for (int i = 0; i < 4; i++) g_cfa[i] = pattern[i];
-    return MFSR_OK;
+    int packed = 0;
+    const int rc = mfsr_pack_cfa(pattern, &packed);
+    if (rc == MFSR_OK) g_cfa.store(packed, std::memory_order_relaxed);
+    return rc;
 }
 
 extern "C" int mfsr_get_cfa_pattern(int32_t pattern[4])
 {
     MFSR_REQUIRE(pattern != nullptr);
-    for (int i = 0; i < 4; i++) pattern[i] = g_cfa[i];
+    const int packed = mfsr_cfa_packed();
+    for (int i = 0; i < 4; i++) pattern[i] = (packed >> (8 * i)) & 0xff;
     return MFSR_OK;
 }
 
@@ -62,16 +64,21 @@ __global__ void __launch_bounds__(256) k_deBayersSubSample3(const uint16_t* __re
     row_ptr(imgOut, strideOut, y)[x] = pixel;
 }
 
-extern "C" int mfsr_deBayersSubSample3(const uint16_t* dataIn, mfsr_float3* imgOut, float maxVal, int dimX, int dimY,
-                                       int strideOut, mfsr_stream_t stream)
+int mfsr_cfa::deBayersSubSample3(int cfa, const uint16_t* dataIn, mfsr_float3* imgOut, float maxVal, int dimX, int dimY, int strideOut,
+                                 mfsr_stream_t stream)
 {
     MFSR_REQUIRE(dataIn && imgOut && dimX > 0 && dimY > 0);
     MFSR_REQUIRE((long long)strideOut >= 12LL * dimX && (strideOut & 3) == 0);
     MFSR_REQUIRE(((uintptr_t)dataIn & 3) == 0);
     dim3 block(64, 4), grid(mfsr_cdiv(dimX, 64), mfsr_cdiv(dimY, 4));
     hipLaunchKernelGGL(k_deBayersSubSample3, grid, block, 0, mfsr_s(stream), dataIn, (pix3*)imgOut, maxVal, dimX, dimY,
-                       strideOut, mfsr_cfa_packed());
+                       strideOut, cfa);
     return mfsr_launch_status("deBayersSubSample3");
+}
+extern "C" int mfsr_deBayersSubSample3(const uint16_t* dataIn, mfsr_float3* imgOut, float maxVal, int dimX, int dimY,
+                                       int strideOut, mfsr_stream_t stream)
+{
+    return mfsr_cfa::deBayersSubSample3(mfsr_cfa_packed(), dataIn, imgOut, maxVal, dimX, dimY, strideOut, stream);
 }
 
 // ---- A1 + gray + separable prefilter + first pyramid level in one launch ------------------
@@ -211,8 +218,8 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-static int prepare_frames_impl(int n, const mfsr_prepare_frame* f, int halfPitch, float maxVal, int dimX, int dimY, int pyr0Pitch,
-                               int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream, bool means = false)
+int mfsr_cfa::prepareFrames(int cfa, int n, const mfsr_prepare_frame* f, int halfPitch, float maxVal, int dimX, int dimY, int pyr0Pitch,
+                            int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream, bool means)
 {
     MFSR_REQUIRE(f && n >= 1 && n <= MFSR_BATCH_MAX && taps && dimX > 0 && dimY > 0);
     MFSR_REQUIRE((long long)halfPitch >= 12LL * dimX && (halfPitch & 3) == 0);
@@ -242,11 +249,11 @@ static int prepare_frames_impl(int n, const mfsr_prepare_frame* f, int halfPitch
         const size_t ldsMeans = sizeof(float) * ((size_t)GW * GH + (planes > rows ? planes : rows));
         hipLaunchKernelGGL(k_prepareFrameFused<true>, grid, block, ldsMeans, mfsr_s(stream), f[0].dataIn,
                            (pix3*)f[0].halfOut, halfPitch, maxVal, dimX, dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp,
-                           mfsr_cfa_packed(), bt);
+                           cfa, bt);
         return mfsr_launch_status("prepareFrameMeans");
     }
     hipLaunchKernelGGL(k_prepareFrameFused<false>, grid, block, lds, mfsr_s(stream), f[0].dataIn, (pix3*)f[0].halfOut, halfPitch, maxVal, dimX,
-                       dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp, mfsr_cfa_packed(), bt);
+                       dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp, cfa, bt);
     return mfsr_launch_status("prepareFrameFused");
 }
 
@@ -255,20 +262,22 @@ extern "C" int mfsr_prepareFrameFused(const uint16_t* dataIn, mfsr_float3* halfO
                                       int ntaps, mfsr_stream_t stream)
 {
     const mfsr_prepare_frame f = {dataIn, halfOut, pyr0, pyr1};
-    return prepare_frames_impl(1, &f, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch, taps, ntaps, stream);
+    return mfsr_cfa::prepareFrames(mfsr_cfa_packed(), 1, &f, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch, taps, ntaps, stream, false);
 }
 
 extern "C" int mfsr_prepareFrameFusedBatch(int nFrames, const mfsr_prepare_frame* frames, int halfPitch, float maxVal, int dimX, int dimY,
                                            int pyr0Pitch, int pyr1Pitch, const float* taps, int ntaps, mfsr_stream_t stream)
 {
-    return prepare_frames_impl(nFrames, frames, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch, taps, ntaps, stream);
+    return mfsr_cfa::prepareFrames(mfsr_cfa_packed(), nFrames, frames, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch, taps, ntaps, stream,
+                                   false);
 }
 
 // mfsr_prepareFrameFusedBatch whose halfOut receives the 3 x 3 patch means of the half-resolution image (k_prepareFrameFused<true>)
 extern "C" int mfsr_prepareFrameMeansBatch(int nFrames, const mfsr_prepare_frame* frames, int meansRowBytes, float maxVal, int w, int h,
                                            int pyr0RowBytes, int pyr1RowBytes, const float* taps, int ntaps, mfsr_stream_t stream)
 {
-    return prepare_frames_impl(nFrames, frames, meansRowBytes, maxVal, w, h, pyr0RowBytes, pyr1RowBytes, taps, ntaps, stream, true);
+    return mfsr_cfa::prepareFrames(mfsr_cfa_packed(), nFrames, frames, meansRowBytes, maxVal, w, h, pyr0RowBytes, pyr1RowBytes, taps, ntaps,
+                                   stream, true);
 }
 
 // ---- A2: deBayerGreenKernel (DeBayerKernels.cu:55-149) ------------------------
@@ -321,16 +330,21 @@ static inline Lvl make_lvl(mfsr_float3 bp, mfsr_float3 sc)
     return L;
 }
 
-extern "C" int mfsr_deBayerGreenKernel(int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage,
-                                       int strideOut, mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+int mfsr_cfa::deBayerGreenKernel(int cfa, int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage, int strideOut,
+                                 mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(imgIn && outImage && width > 0 && height > 0);
     MFSR_REQUIRE((long long)strideIn >= 4LL * width && (long long)strideOut >= 12LL * width);
     MFSR_REQUIRE((strideIn & 3) == 0 && (strideOut & 3) == 0);
     dim3 block(64, 4), grid(mfsr_cdiv(width, 64), mfsr_cdiv(height, 4));
     hipLaunchKernelGGL(k_deBayerGreen, grid, block, 0, mfsr_s(stream), width, height, imgIn, strideIn, (pix3*)outImage,
-                       strideOut, make_lvl(blackPoint, scale), mfsr_cfa_packed());
+                       strideOut, make_lvl(blackPoint, scale), cfa);
     return mfsr_launch_status("deBayerGreenKernel");
+}
+extern "C" int mfsr_deBayerGreenKernel(int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage,
+                                       int strideOut, mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+{
+    return mfsr_cfa::deBayerGreenKernel(mfsr_cfa_packed(), width, height, imgIn, strideIn, outImage, strideOut, blackPoint, scale, stream);
 }
 
 // ---- A3: deBayerRedBlueKernel (DeBayerKernels.cu:153-231) ---------------------
@@ -382,16 +396,21 @@ __global__ void __launch_bounds__(256) k_deBayerRedBlue(int width, int height, c
     rowc[x].z = b;
 }
 
-extern "C" int mfsr_deBayerRedBlueKernel(int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage,
-                                         int strideOut, mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+int mfsr_cfa::deBayerRedBlueKernel(int cfa, int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage, int strideOut,
+                                   mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(imgIn && outImage && width > 0 && height > 0);
     MFSR_REQUIRE((long long)strideIn >= 4LL * width && (long long)strideOut >= 12LL * width);
     MFSR_REQUIRE((strideIn & 3) == 0 && (strideOut & 3) == 0);
     dim3 block(64, 4), grid(mfsr_cdiv(width, 64), mfsr_cdiv(height, 4));
     hipLaunchKernelGGL(k_deBayerRedBlue, grid, block, 0, mfsr_s(stream), width, height, imgIn, strideIn, (pix3*)outImage,
-                       strideOut, make_lvl(blackPoint, scale), mfsr_cfa_packed());
+                       strideOut, make_lvl(blackPoint, scale), cfa);
     return mfsr_launch_status("deBayerRedBlueKernel");
+}
+extern "C" int mfsr_deBayerRedBlueKernel(int width, int height, const float* imgIn, int strideIn, mfsr_float3* outImage,
+                                         int strideOut, mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+{
+    return mfsr_cfa::deBayerRedBlueKernel(mfsr_cfa_packed(), width, height, imgIn, strideIn, outImage, strideOut, blackPoint, scale, stream);
 }
 
 // ---- A2+A3 fused (u16 in, one launch) -----------------------------------------
@@ -509,24 +528,34 @@ __global__ void __launch_bounds__(DBF_TX* DBF_TY) k_deBayerFusedRing(const uint1
     debayer_fused_tile<true>(raw, outImage, strideOut, width, height, L, cfa);
 }
 
-extern "C" int mfsr_deBayerFused(const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
-                                 mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+int mfsr_cfa::deBayerFused(int cfa, const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
+                           mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(raw && outImage && width > 4 && height > 4);
     MFSR_REQUIRE((long long)strideOut >= 12LL * width && (strideOut & 3) == 0);
     dim3 block(DBF_TX, DBF_TY), grid(mfsr_cdiv(width, DBF_TX), mfsr_cdiv(height, DBF_TY));
     hipLaunchKernelGGL(k_deBayerFused, grid, block, 0, mfsr_s(stream), raw, (pix3*)outImage, strideOut, width, height,
-                       make_lvl(blackPoint, scale), mfsr_cfa_packed());
+                       make_lvl(blackPoint, scale), cfa);
     return mfsr_launch_status("deBayerFused");
+}
+extern "C" int mfsr_deBayerFused(const uint16_t* raw, mfsr_float3* outImage, int strideOut, int width, int height,
+                                 mfsr_float3 blackPoint, mfsr_float3 scale, mfsr_stream_t stream)
+{
+    return mfsr_cfa::deBayerFused(mfsr_cfa_packed(), raw, outImage, strideOut, width, height, blackPoint, scale, stream);
 }
 
 // the same with the 2-pixel ring of the image written as zero: every pixel of outImage is stored, so the image needs no clear
-extern "C" int mfsr_deBayerFusedRing(const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
-                                     mfsr_stream_t stream)
+int mfsr_cfa::deBayerFusedRing(int cfa, const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
+                               mfsr_stream_t stream)
 {
     MFSR_REQUIRE(raw && mfsr_tex_ok(outImage, 12) && outImage.width > 4 && outImage.height > 4 && (outImage.pitch & 3) == 0);
     dim3 block(DBF_TX, DBF_TY), grid(mfsr_cdiv(outImage.width, DBF_TX), mfsr_cdiv(outImage.height, DBF_TY));
     hipLaunchKernelGGL(k_deBayerFusedRing, grid, block, 0, mfsr_s(stream), raw, (pix3*)outImage.ptr, outImage.pitch, outImage.width,
-                       outImage.height, make_lvl(blackPoint, scale), mfsr_cfa_packed());
+                       outImage.height, make_lvl(blackPoint, scale), cfa);
     return mfsr_launch_status("deBayerFusedRing");
+}
+extern "C" int mfsr_deBayerFusedRing(const uint16_t* raw, mfsr_tex2d outImage, mfsr_float3 blackPoint, mfsr_float3 scale,
+                                     mfsr_stream_t stream)
+{
+    return mfsr_cfa::deBayerFusedRing(mfsr_cfa_packed(), raw, outImage, blackPoint, scale, stream);
 }

@@ -669,10 +669,7 @@ MfsrExactDiv mfsr_exact_div(float d)
     const auto hit = cache.find(key);
     if (hit != cache.end()) return hit->second;
     MfsrExactDiv e{d, 1.0f / d, 0};
-    static const bool off = [] {
-        const char* v = getenv("MFSR_EXACT_DIV");
-        return v && v[0] == '0';
-    }();
+    static const bool off = mfsr_env_is0("MFSR_EXACT_DIV");
     if (!off && d > 0.0f && d < 16777216.0f) {
         bool ok = true;
         for (uint32_t m = 0; m < (1u << 23) && ok; m++) {

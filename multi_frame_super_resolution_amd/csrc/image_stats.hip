@@ -154,7 +154,7 @@ StatsArgs stats_args(const mfsr_image_stats_params* p, int w, int h, int rowByte
     s.pitch = rowBytes;
     const int upr = (w + kStatsPpl - 1) / kStatsPpl;
     const int minRows = (kStatsThreads + upr - 1) / upr;
-    int rows = (int)mfsr_cdiv(h, stats_cus());
+    int rows = (int)mfsr_cdiv(h, mfsr_device_cus());
     rows = rows < minRows ? minRows : rows;
     s.rowsPerGroup = rows < h ? rows : h;
     *blocks = mfsr_cdiv(h, s.rowsPerGroup);  // every chunk non-empty

@@ -178,7 +178,7 @@ static size_t kf_lds_bytes(int h)
 
 // 1 (default): set_reference takes the fused reference setup (this file, mfsr_tileSquaredSumsLevels, mfsr_deBayerFusedRing);
 // 0: the kernel chain
-static int g_reference_fused = 1;
+static std::atomic<int> g_reference_fused{1};
 extern "C" int mfsr_set_reference_fused(int enable)
 {
     g_reference_fused = enable ? 1 : 0;

@@ -308,10 +308,7 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
     // TX is a template parameter of the kernel: 48 only for the half-window sizes that have a <h,48>
     // instantiation below (1..7); every other size runs the generic <0,32> kernel
     const bool hasWide = h >= 1 && h <= 7;
-    static const int forceTx = [] {
-        const char* e = getenv("MFSR_LK_TX");
-        return e ? atoi(e) : 0;
-    }();
+    static const int forceTx = mfsr_env_int("MFSR_LK_TX", 0);
     // tile width: 48 when the kernel warps its tile + halo itself (fewest warps per pixel); 32 when the warped image is
     // handed in (PRE): the halo is then only loads, and the smaller workgroup (40 KB of LDS, four per CU instead of two)
     // hides the two global round trips of a tile better -- 6.55 against 6.69 ms per 4K burst; 64 wide: no better.
@@ -328,14 +325,9 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
     dim3 block(TX, LK_TY), grid(mfsr_cdiv(width, TX), mfsr_cdiv(height, LK_TY));
 #define LK_LAUNCH(HT, TXV)                                                                                             \
     do {                                                                                                               \
-        if (lds > 64 * 1024) {                                                                                         \
-            static bool attr_set = false;                                                                              \
-            if (!attr_set) {                                                                                           \
-                MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_lkIterationFused<HT, TXV, PRE>,                        \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));             \
-                attr_set = true;                                                                                       \
-            }                                                                                                          \
-        }                                                                                                              \
+        if (lds > 64 * 1024) /* the attribute is the function's on the current device: set for every such launch */    \
+            MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_lkIterationFused<HT, TXV, PRE>,                            \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                 \
         hipLaunchKernelGGL((k_lkIterationFused<HT, TXV, PRE>), grid, block, lds, mfsr_s(stream), (const float2*)shiftsIn, \
                            (float2*)shiftsOut, pitchShift, refImg, movedImg, pitchImg, width, height, h, minDet,       \
                            outScale, sumIn, diffIn, sumOut, diffOut, pitchSD);                                         \
@@ -758,10 +750,7 @@ extern "C" int mfsr_lucasKanadeSweepBand(int width, int height, int halfWindowSi
     const int h = halfWindowSize, VW = 64 - 2 * (h + 2);
     const int strips = mfsr_cdiv(width, VW);
     // band height: enough wavefronts to fill 1024 SIMDs a few times over without paying too many halo rows
-    static const int forceBand = [] {
-        const char* e = getenv("MFSR_LK_BAND");
-        return e ? atoi(e) : 0;
-    }();
+    static const int forceBand = mfsr_env_int("MFSR_LK_BAND", 0);
     // (measured at 1920 x 1080, h = 3: one frame 27.0 / 32.5 / 48.8 us with bands of 8 / 16 / 32 rows, four frames 27.1 / 26.5 /
     // 27.6 us per frame: the wave count decides, the halo rows cost less than idle SIMDs)
     int band = (int)((long long)height * strips * nFrames / 8192);
@@ -810,10 +799,7 @@ extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* fram
     const int h = halfWindowSize, VW = 64 - 2 * (h + 2);
     const int strips = mfsr_cdiv(width, VW);
     const int band = mfsr_lucasKanadeSweepBand(width, height, h, nFrames);
-    static const int xcdRemap = [] {
-        const char* e = getenv("MFSR_LK_XCD");
-        return e ? atoi(e) : 1;
-    }();
+    static const int xcdRemap = mfsr_env_int("MFSR_LK_XCD", 1);
     const int bands = mfsr_cdiv(height, band);
     const int total = strips * bands * nFrames;
     const int perXcd = xcdRemap ? mfsr_cdiv(total, 8) : 0;

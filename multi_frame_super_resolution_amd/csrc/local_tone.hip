@@ -441,7 +441,7 @@ ToneStatsArgs tone_stats_args(const float* matrix, const mfsr_local_tone* lt, in
     s.chunks = ((colOffset + w - 1) / lt->cell) / s.chunkCells - s.chunk0 + 1;
     const long long chunkPx = (long long)s.chunkCells * lt->cell;
     const long long itemW = chunkPx < w ? chunkPx : w;
-    const int want = 2 * stats_cus();
+    const int want = 2 * mfsr_device_cus();
     int shift = s.cellShift;
     for (;;) {
         const int R = 1 << shift;

@@ -162,14 +162,6 @@ __global__ __launch_bounds__(kNoiseThreads) void k_noiseStats(RawFrames frames, 
     }
 }
 
-int noise_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    return cus;
-}
-
 // [lo, hi) of the D values of variance bin v
 void noise_bin_bounds(int v, double& lo, double& hi)
 {
@@ -217,7 +209,7 @@ extern "C" int mfsr_noiseStats(int nFrames, const uint16_t* const* frames, int p
     }
     g.sat = sat;
     // one chunk per CU, no chunk longer than a 16-bit counter holds, no workgroup without a full round of blocks
-    long long groups = noise_cus();
+    long long groups = mfsr_device_cus();
     const long long rounds = (total + kNoiseThreads - 1) / kNoiseThreads;
     groups = groups < rounds ? groups : rounds;
     const long long need = (total + kNoiseMaxChunk - 1) / kNoiseMaxChunk;

@@ -323,14 +323,6 @@ __global__ __launch_bounds__(kTempThreads) void k_noiseStatsTemporal(RawFrames f
     temporal_flush(sHist, sSum, hist, levelSum, count, false);
 }
 
-int temporal_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    return cus;
-}
-
 }  // namespace
 
 extern "C" int mfsr_noiseStatsTemporal(int nFrames, const uint16_t* const* frames, int rowBytes, int w, int h,
@@ -383,7 +375,7 @@ extern "C" int mfsr_noiseStatsTemporal(int nFrames, const uint16_t* const* frame
     }
     g.sat = sat;
     // one chunk per CU, no workgroup without a full round of blocks
-    long long groups = temporal_cus();
+    long long groups = mfsr_device_cus();
     const long long rounds = (total + kTempThreads - 1) / kTempThreads;
     groups = groups < rounds ? groups : rounds;
     g.chunk = (unsigned)((total + groups - 1) / groups);

@@ -297,6 +297,7 @@ mfsr_tex2d as_tex(const Img& im)
 struct mfsr_burst {
     mfsr_burst(const mfsr_config& c, char* workspace) : cfg(c), L(make_layout(&c, workspace)) {}
     mfsr_config cfg;
+    int cfa;            // cfg.cfa as the kernels' launch word (mfsr_pack_cfa), checked at create
     const Layout L;     // written by make_layout only
     FrameProducts ref;  // the current reference's products: L.ref, or what the caller of set_reference_impl supplied
     float taps[99];
@@ -452,11 +453,11 @@ static int fuse_group(mfsr_burst* b, int n, const uint16_t* const* raws, mfsr_fl
     const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
     const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
     if (!b->win.on)
-        return mfsr_accumulateSuperResFullRows(n, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), flows, white, black, L.W, L.H,
+        return mfsr_cfa::accumulateSuperResFullRows(b->cfa, n, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), flows, white, black, L.W, L.H,
                                                c.scale, 12 * L.hrW, maskPitch, fresh, r0, r1, stream);
     const int pitch = 12 * b->win.w;
     const size_t off = (size_t)r0 * pitch;
-    return mfsr_accumulateSuperResFullWindow(n, raws, (mfsr_float3*)((char*)imgOut + off), (mfsr_float3*)((char*)totalWeights + off),
+    return mfsr_cfa::accumulateSuperResFullWindow(b->cfa, n, raws, (mfsr_float3*)((char*)imgOut + off), (mfsr_float3*)((char*)totalWeights + off),
                                              masks, as_tex(L.kparam4), flows, white, black, L.W, L.H, c.scale, pitch, maskPitch, fresh,
                                              b->win.x0, b->win.y0 + r0, b->win.w, r1 - r0, stream);
 }
@@ -538,6 +539,8 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
 {
     MFSR_REQUIRE(out != nullptr && workspace != nullptr);
     TRY(validate(cfg));
+    int cfa = 0;
+    TRY(mfsr_pack_cfa(cfg->cfa, &cfa));
     if (mfsr_device_count() <= 0) {
         fprintf(stderr, "mfsr: no HIP device available (there is no CPU fallback)\n");
         return MFSR_E_NODEVICE;
@@ -550,6 +553,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
         delete b;
         return MFSR_E_WORKSPACE;
     }
+    b->cfa = cfa;
     b->ntaps = mfsr_gaussin_filter_1D(cfg->sigmaTracking, b->taps);
     b->ntensorTaps = mfsr_gaussin_filter_1D(cfg->sigmaTensor, b->tensorTaps);
     b->flowCur = &b->L.flowBuf[0];
@@ -783,14 +787,13 @@ static int prepare_frame(mfsr_burst* b, const uint16_t* raw, const FrameProducts
     const Layout& L = b->L;
     const Img& half = f.half;
     const Img* pyr = f.pyr;
-    TRY(mfsr_set_cfa_pattern(c.cfa));
     const float maxValEff = c.mono ? 2.0f * c.maxVal : c.maxVal;  // mono: 4 "greens" x 0.5 -> mean of the quad
     const int nlev = ilog2(L.maxFactor) + 1;
     if (c.fused && !c.mono && b->ntaps / 2 <= 8 && L.tw == L.hw && L.th == L.hh) {
         // A1 + luma + prefilter + first pyramid level in one launch (bit-identical to the chain below)
-        TRY(mfsr_prepareFrameFused(raw, (mfsr_float3*)half.ptr, half.pitch, maxValEff, L.hw, L.hh, (float*)pyr[0].ptr,
-                                   pyr[0].pitch, nlev > 1 ? (float*)pyr[1].ptr : nullptr, nlev > 1 ? pyr[1].pitch : 0,
-                                   b->taps, b->ntaps, stream));
+        const mfsr_prepare_frame pf = {raw, (mfsr_float3*)half.ptr, (float*)pyr[0].ptr, nlev > 1 ? (float*)pyr[1].ptr : nullptr};
+        TRY(mfsr_cfa::prepareFrames(b->cfa, 1, &pf, half.pitch, maxValEff, L.hw, L.hh, pyr[0].pitch, nlev > 1 ? pyr[1].pitch : 0, b->taps,
+                                    b->ntaps, stream, false));
         b->paths[MFSR_PATH_PREPARE_FUSED]++;
         for (int i = 2; i < nlev; i++)
             TRY(mfsr_downsample2x((const float*)pyr[i - 1].ptr, pyr[i - 1].pitch, (float*)pyr[i].ptr, pyr[i].pitch, pyr[i].w,
@@ -798,7 +801,7 @@ static int prepare_frame(mfsr_burst* b, const uint16_t* raw, const FrameProducts
         return MFSR_OK;
     }
     b->paths[MFSR_PATH_PREPARE_CHAIN]++;
-    TRY(mfsr_deBayersSubSample3(raw, (mfsr_float3*)half.ptr, maxValEff, L.hw, L.hh, half.pitch, stream));
+    TRY(mfsr_cfa::deBayersSubSample3(b->cfa, raw, (mfsr_float3*)half.ptr, maxValEff, L.hw, L.hh, half.pitch, stream));
     if (c.mono)
         TRY(mfsr_u16ToFloat(raw, (float*)L.tmpA.ptr, L.tmpA.pitch, L.W, L.H, 1.0f / c.maxVal, stream));
     else
@@ -839,10 +842,7 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     if (!prepared) TRY(prepare_frame(b, rawRef, R, stream));
     const bool refFused = c.fused && mfsr_reference_fused();  // (mfsr_set_reference_fused(0): the launches this replaced, A/B)
     // MFSR_REF_FUSED_PARTS: which parts of the fused setup run, for A/B of one part (1 kernel field, 2 tile sums, 4 ring debayer)
-    static const int refParts = [] {
-        const char* e = getenv("MFSR_REF_FUSED_PARTS");
-        return e ? atoi(e) : 7;
-    }();
+    static const int refParts = mfsr_env_int("MFSR_REF_FUSED_PARTS", 7);
     const bool fusedField = refFused && (refParts & 1), fusedSums = refFused && (refParts & 2), fusedRing = refFused && (refParts & 4);
     if (fusedSums) {
         mfsr_tex2d lv[kMaxLevels];
@@ -864,10 +864,7 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     // stream (after everything the caller's stream has enqueued so far: the previous burst's finish reads the same images),
     // beside the alignment of the first group -- 0.2 ms off the burst's critical path, on which the GPU is otherwise
     // half empty.  MFSR_REF_OVERLAP=0: on the caller's stream (A/B).
-    static const bool refOverlap = [] {
-        const char* e = getenv("MFSR_REF_OVERLAP");
-        return !(e && e[0] == '0');
-    }();
+    static const bool refOverlap = !mfsr_env_is0("MFSR_REF_OVERLAP");
     mfsr_stream_t es = stream;
     b->refOnFuse = false;
     if (refOverlap && b->fuseStream && c.fused) {
@@ -940,18 +937,18 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     if (c.fused) {
         if (fusedRing) {
             const mfsr_tex2d fbt = {fb, L.fallback.pitch, L.W, r1 - r0};
-            TRY(mfsr_deBayerFusedRing(rawRef + (size_t)r0 * L.W, fbt, bp, sc, es));
+            TRY(mfsr_cfa::deBayerFusedRing(b->cfa, rawRef + (size_t)r0 * L.W, fbt, bp, sc, es));
         } else
-            TRY(mfsr_deBayerFused(rawRef + (size_t)r0 * L.W, (mfsr_float3*)fb, L.fallback.pitch, L.W, r1 - r0, bp, sc, es));
+            TRY(mfsr_cfa::deBayerFused(b->cfa, rawRef + (size_t)r0 * L.W, (mfsr_float3*)fb, L.fallback.pitch, L.W, r1 - r0, bp, sc, es));
         if (es != stream) {
             MFSR_HIP_TRY(hipEventRecord(b->evRefDone, b->fuseStream));
             b->refOnFuse = true;
         }
     } else {
         TRY(mfsr_u16ToFloat(rawRef, (float*)L.rawf.ptr, L.rawf.pitch, L.W, L.H, 1.0f, stream));
-        TRY(mfsr_deBayerGreenKernel(L.W, L.H, (const float*)L.rawf.ptr, L.rawf.pitch, (mfsr_float3*)L.fallback.ptr,
+        TRY(mfsr_cfa::deBayerGreenKernel(b->cfa, L.W, L.H, (const float*)L.rawf.ptr, L.rawf.pitch, (mfsr_float3*)L.fallback.ptr,
                                     L.fallback.pitch, bp, sc, stream));
-        TRY(mfsr_deBayerRedBlueKernel(L.W, L.H, (const float*)L.rawf.ptr, L.rawf.pitch, (mfsr_float3*)L.fallback.ptr,
+        TRY(mfsr_cfa::deBayerRedBlueKernel(b->cfa, L.W, L.H, (const float*)L.rawf.ptr, L.rawf.pitch, (mfsr_float3*)L.fallback.ptr,
                                       L.fallback.pitch, bp, sc, stream));
     }
     b->haveRef = true;
@@ -1105,34 +1102,26 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream);
 // ---- burst hold -------------------------------------------------------------------------------------------------------------
 // Process-wide switch of the burst hold for A/B (mfsr_set_burst_fuse; MFSR_BURST_FUSE=0 in the environment): off, every
 // context fuses its groups as they complete, whatever mfsr_burst_hold_fuse said.
-static int g_burst_fuse = -1;
+static MfsrKnob g_burst_fuse;
 static bool burst_fuse_enabled()
 {
-    if (g_burst_fuse < 0) {
-        const char* e = getenv("MFSR_BURST_FUSE");
-        g_burst_fuse = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_burst_fuse == 1;
+    return g_burst_fuse.get([] { return mfsr_env_is0("MFSR_BURST_FUSE") ? 0 : 1; }) == 1;
 }
 extern "C" int mfsr_set_burst_fuse(int enable)
 {
-    g_burst_fuse = enable ? 1 : 0;
+    g_burst_fuse.set(enable ? 1 : 0);
     return MFSR_OK;
 }
 // Process-wide switch of the finish inside the burst launch for A/B (mfsr_set_finish_fuse; MFSR_FINISH_FUSE=0 in the
 // environment): off, mfsr_burst_finish always runs its finish pass.
-static int g_finish_fuse = -1;
+static MfsrKnob g_finish_fuse;
 static bool finish_fuse_enabled()
 {
-    if (g_finish_fuse < 0) {
-        const char* e = getenv("MFSR_FINISH_FUSE");
-        g_finish_fuse = (e && e[0] == '0') ? 0 : 1;
-    }
-    return g_finish_fuse == 1;
+    return g_finish_fuse.get([] { return mfsr_env_is0("MFSR_FINISH_FUSE") ? 0 : 1; }) == 1;
 }
 extern "C" int mfsr_set_finish_fuse(int enable)
 {
-    g_finish_fuse = enable ? 1 : 0;
+    g_finish_fuse.set(enable ? 1 : 0);
     return MFSR_OK;
 }
 extern "C" int mfsr_burst_debug_finish_fused(const mfsr_burst* b, int* finishes)
@@ -1201,7 +1190,6 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
             acc[p].width = L.hrW;
             acc[p].height = L.hrH;
         }
-        TRY(mfsr_set_cfa_pattern(c.cfa));
         const int freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
         const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
         if (timed) {
@@ -1222,7 +1210,7 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
             fb.pitch = L.fallback.pitch;
             fb.width = L.W;
             fb.height = L.H;
-            rc = mfsr_accumulateSuperResBurstFinish(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white,
+            rc = mfsr_cfa::accumulateSuperResBurstFinish(b->cfa, G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white,
                                                     black, c.scale, freshNow, fb, 0.0f, 1.0f, 0.0f, 1.0f, c.weightThreshold, out16,
                                                     L.hrW, L.hrH, 0, 65535.0f, 0, 0, L.hrW, L.hrH, stream);
             if (rc == MFSR_OK) {
@@ -1231,7 +1219,7 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
             }
         }
         if (rc == MFSR_E_UNSUPPORTED)
-            rc = mfsr_accumulateSuperResBurst(G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
+            rc = mfsr_cfa::accumulateSuperResBurst(b->cfa, G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
                                               c.scale, freshNow, stream);
         if (rc == MFSR_OK) {
             if (b->fresh.has && !freshNow) {
@@ -1287,7 +1275,6 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
     TRY(fuse_held(b, callerStream));       // it comes before the frames that arrived after it
     TRY(align_deferred(b, callerStream));  // frames of the group that were waiting for their batch
     TRY(wait_uploads(b, callerStream));    // (a reference frame of the group is read by the fuse only)
-    const mfsr_config& c = b->cfg;
     const mfsr_burst::Pending p = b->pend;
     b->pend.n = 0;
     const int n = p.n;
@@ -1300,7 +1287,6 @@ static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
         stream = (mfsr_stream_t)b->fuseStream;
         for (int i = 0; i < n; i++) MFSR_HIP_TRY(hipStreamWaitEvent(b->fuseStream, b->evAligned[p.slot[i]], 0));
     }
-    TRY(mfsr_set_cfa_pattern(c.cfa));
     const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
     if (timed) {
         const int i = b->nEvents;
@@ -1386,10 +1372,7 @@ static bool lk_warped_path(const mfsr_burst* b)
 {
     // fused LK: the warped moved image travels from launch to launch (every pixel warped once per iteration, by the
     // thread that has just updated its flow) instead of being re-gathered for every tile halo; MFSR_LK_WARPED=0: A/B
-    static const bool lkWarped = [] {
-        const char* e = getenv("MFSR_LK_WARPED");
-        return !(e && e[0] == '0');
-    }();
+    static const bool lkWarped = !mfsr_env_is0("MFSR_LK_WARPED");
     const mfsr_config& c = b->cfg;
     return c.fused && lkWarped && c.lkIterations > 0 && b->L.tw >= 64 && b->L.th >= 32;
 }
@@ -1610,10 +1593,7 @@ static bool can_defer_alignment(const mfsr_burst* b, bool supplied)
     // (host bursts: frames are aligned one by one as they come off the PCIe link -- waiting for a whole group would leave
     // the GPU idle during the first uploads and would put the whole last group's alignment between the last upload and
     // the first byte of the download; MFSR_HOST_DEFER=1 batches the groups after the first anyway)
-    static const bool hostDefer = [] {
-        const char* e = getenv("MFSR_HOST_DEFER");
-        return e && e[0] == '1';
-    }();
+    static const bool hostDefer = mfsr_env_is1("MFSR_HOST_DEFER");
     // ... and a host burst that was enqueued while the previous one was still being fused and downloaded (bursts back to
     // back: b->hostBusy) batches every group: the GPU has work queued, so frame-by-frame launches buy no latency and cost
     // a tenth of the alignment's throughput
@@ -1661,7 +1641,6 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             }
         }
         if (m > 0) {
-            TRY(mfsr_set_cfa_pattern(c.cfa));
             // A1 + luma + prefilter + first pyramid level
             mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
             for (int k = 0; k < m; k++) {
@@ -1671,9 +1650,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
                 pf[k].pyr0 = (float*)pyr[0].ptr;
                 pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
             }
-            TRY((maskGroup ? mfsr_prepareFrameMeansBatch : mfsr_prepareFrameFusedBatch)(
-                m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch, nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps,
-                b->ntaps, stream));
+            TRY(mfsr_cfa::prepareFrames(b->cfa, m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
+                                        nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream, maskGroup));
             b->paths[MFSR_PATH_PREPARE_BATCH]++;
             for (int k = 0; k < m; k++) {
                 const Img* pyr = L.mov[mq[k]].pyr;
@@ -1769,8 +1747,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             pf[k].pyr0 = (float*)pyr[0].ptr;
             pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
         }
-        TRY(mfsr_prepareFrameFusedBatch(m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
-                                        nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream));
+        TRY(mfsr_cfa::prepareFrames(b->cfa, m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
+                                    nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream, false));
     }
     if (maskBatch && maskGroup) {
         mfsr_robustness_group_frame gf[MFSR_MAX_FUSE_GROUP];
@@ -1781,7 +1759,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             gf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
             gf[k].flow = (const mfsr_float2*)final_flow(b, slot, 0)->ptr;
         }
-        TRY(mfsr_robustnessMaskGroup(m, gf, (const mfsr_float3*)ref.half.ptr, ref.half.pitch, L.flowBuf[0].pitch, L.mov[0].half.pitch,
+        TRY(mfsr_cfa::robustnessMaskGroup(b->cfa, m, gf, (const mfsr_float3*)ref.half.ptr, ref.half.pitch, L.flowBuf[0].pitch, L.mov[0].half.pitch,
                                      L.maskBuf[0].pitch, L.hw, L.hh, c.maxVal, c.alpha, c.beta, c.thresholdM, stream));
         b->robustGroupLaunches++;
         b->paths[MFSR_PATH_ROBUST_BATCH]++;
@@ -1837,7 +1815,6 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     MFSR_REQUIRE(b->haveRef);
     MFSR_REQUIRE(!b->refStale);  // after mfsr_burst_process_joint: call mfsr_burst_set_reference first
     const mfsr_config& c = b->cfg;
-    TRY(mfsr_set_cfa_pattern(c.cfa));
     b->holdLastGroup = hostBurst;
     // G: accumulate onto the HR grid -- alone, or together with the frames that were waiting for the rest of their group
     if (b->pend.n && (b->pend.imgOut != imgOut || b->pend.totalWeights != totalWeights)) TRY(flush_pending(b, stream));
@@ -1879,10 +1856,7 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     // ... and so does the group before it (MFSR_HOST_HOLD=2, the default): the first band of the image is then complete after
     // 1/8 of two groups' fuse instead of after a whole group's, and the download -- the tail of the burst -- starts that much
     // earlier; the earlier groups are fused as they arrive, under the uploads
-    static const int holdGroups = [] {
-        const char* e = getenv("MFSR_HOST_HOLD");
-        return e ? atoi(e) : 2;
-    }();
+    static const int holdGroups = mfsr_env_int("MFSR_HOST_HOLD", 2);
     if (b->holdLastGroup && holdGroups >= 2 && !b->heldHas && c.frames - b->framesSinceRef <= b->group &&
         c.frames - b->framesSinceRef > 0 && !b->pend.deferred[0]) {
         bool aligned = true;
@@ -1939,7 +1913,6 @@ extern "C" int mfsr_burst_align_frame(mfsr_burst* b, const uint16_t* raw, int is
     const Layout& L = b->L;
     MFSR_REQUIRE((long long)flowPitch >= 8LL * L.tw && (flowPitch & 7) == 0 && ((uintptr_t)flowOut & 7) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0 && ((uintptr_t)maskOut & 15) == 0);
-    TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
     TRY(fuse_hold(b, stream));  // (the call takes a ring slot)
     const int slot = b->frameCounter++ % b->ring;
     const Img *flow = nullptr, *mask = nullptr;
@@ -1967,7 +1940,6 @@ extern "C" int mfsr_burst_align_frames(mfsr_burst* b, int nFrames, const uint16_
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0);
     for (int k = 0; k < nFrames; k++)
         MFSR_REQUIRE(raws[k] && flowOut[k] && maskOut[k] && ((uintptr_t)flowOut[k] & 7) == 0 && ((uintptr_t)maskOut[k] & 15) == 0);
-    TRY(mfsr_set_cfa_pattern(b->cfg.cfa));
     TRY(fuse_hold(b, stream));  // (the call takes ring slots)
     const bool batch = can_defer_alignment(b, false);
     const int per = batch ? b->group : 1;
@@ -2019,7 +1991,6 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
     const Layout& L = b->L;
     const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
     const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
-    TRY(mfsr_set_cfa_pattern(c.cfa));
     mfsr_tex2d sh[MFSR_MAX_FUSE_GROUP];
     for (int n = 0; n < nFrames; n++) {
         sh[n].ptr = flows[n];
@@ -2034,7 +2005,7 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
         if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
         MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
     }
-    TRY(mfsr_accumulateSuperResFullRows(nFrames, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), sh, white, black, L.W, L.H,
+    TRY(mfsr_cfa::accumulateSuperResFullRows(b->cfa, nFrames, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), sh, white, black, L.W, L.H,
                                         c.scale, 12 * L.hrW, maskPitch, accumulatorsUndefined, rowBegin, rowEnd, stream));
     if (timed) {
         MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
@@ -2556,12 +2527,24 @@ static int join_captured(mfsr_burst* b, mfsr_stream_t stream)
 }
 
 // MFSR_UPLOAD_1D=1: the round-3 form of the uploads (A/B, see upload_into)
+// MFSR_HOST_BANDS: a value that begins with '0' switches the banded tail of a host burst off (mfsr_burst_add_frame_host);
+// otherwise it is the number of bands, 1 .. 16 (default 8; mfsr_burst_finish_host)
+struct HostBands {
+    bool on;
+    int count;
+};
+static HostBands host_bands()
+{
+    static const HostBands hb = [] {
+        const int n = mfsr_env_int("MFSR_HOST_BANDS", 8);
+        return HostBands{!mfsr_env_is0("MFSR_HOST_BANDS"), n < 1 ? 1 : (n > 16 ? 16 : n)};
+    }();
+    return hb;
+}
+
 static bool upload_1d()
 {
-    static const bool up1d = [] {
-        const char* e = getenv("MFSR_UPLOAD_1D");
-        return e && e[0] == '1';
-    }();
+    static const bool up1d = mfsr_env_is1("MFSR_UPLOAD_1D");
     return up1d;
 }
 
@@ -2619,10 +2602,7 @@ extern "C" int mfsr_burst_set_reference_host(mfsr_burst* b, const uint16_t* host
     TRY(host_epoch(b, stream));
     TRY(flush_pending(b, stream, false));    // a frame still waiting reads the previous reference's slots
     b->nUnp = 0;                             // (packed frames the last burst announced and did not consume: never unpacked)
-    static const bool adaptive = [] {
-        const char* e = getenv("MFSR_HOST_ADAPTIVE");
-        return !(e && e[0] == '0');
-    }();
+    static const bool adaptive = !mfsr_env_is0("MFSR_HOST_ADAPTIVE");
     b->hostBusy = false;
     if (adaptive && b->downRecorded) {
         // (an event query is not allowed while the caller's stream is being captured into a graph)
@@ -2651,10 +2631,7 @@ extern "C" int mfsr_burst_add_frame_host(mfsr_burst* b, const uint16_t* hostRaw,
     MFSR_REQUIRE(b && hostRaw && imgOut && totalWeights);
     MFSR_REQUIRE(b->copyStream != nullptr);
     TRY(host_epoch(b, stream));
-    static const bool banded = [] {
-        const char* e = getenv("MFSR_HOST_BANDS");
-        return !(e && e[0] == '0');
-    }();
+    const bool banded = host_bands().on;
     if (isReference && hostRaw == b->refHost && b->refDev)
         return add_frame_impl(b, b->refDev, 1, imgOut, totalWeights, banded, stream);
     if (b->prefetchHead < b->nPrefetched) {
@@ -2734,19 +2711,12 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     const Layout& L = b->L;
     // the previous image may still be on its way to the host out of out16Dev
     if (b->downRecorded) MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evDown, 0));
-    static const int nBandsEnv = [] {
-        const char* e = getenv("MFSR_HOST_BANDS");
-        return e ? atoi(e) : 8;
-    }();
-    int nBands = nBandsEnv < 1 ? 1 : (nBandsEnv > 16 ? 16 : nBandsEnv);
+    int nBands = host_bands().count;
     // The bands exist for the LATENCY of one burst (its download starts after 1/8 of the tail).  A burst that was enqueued
     // while the previous one's download was still in flight (b->hostBusy: bursts back to back) gains nothing from them -- its
     // download runs under the next burst's compute anyway -- and pays 16 band-sized fuse launches + 8 finish launches for it:
     // such a burst takes MFSR_HOST_BANDS_BUSY bands (default 2).
-    static const int nBandsBusy = [] {
-        const char* e = getenv("MFSR_HOST_BANDS_BUSY");
-        return e ? atoi(e) : 2;
-    }();
+    static const int nBandsBusy = mfsr_env_int("MFSR_HOST_BANDS_BUSY", 2);
     // (only where the image is small against the burst -- x2: 199 MB down for 265 MB up.  At x4 the download, 796 MB, is as
     // long as the burst's compute: it has to start with the first band, or the NEXT burst's finish waits for it to leave
     // out16Dev: 18.1 instead of 17.0 ms per burst with two bands)
@@ -3471,7 +3441,6 @@ extern "C" int mfsr_stream_push(mfsr_stream* s, const uint16_t* frame, mfsr_floa
         MFSR_HIP_TRY(hipMemcpyAsync(f.raw, frame, rawBytes, hipMemcpyDeviceToDevice, mfsr_s(stream)));
     }
     // per-frame products, once per frame
-    TRY(mfsr_set_cfa_pattern(s->cfg.cfa));
     TRY(prepare_frame(b, f.raw, f, stream));
     if (s->cfg.preAlign)
         TRY(mfsr_preAlignPyramid((const float*)f.pyr[0].ptr, L.tw, L.th, f.pyr[0].pitch, f.prePyr, stream));
@@ -3642,7 +3611,6 @@ extern "C" int mfsr_burst_process_joint(mfsr_burst* b, const uint16_t* const* fr
     char* base = (char*)jointWorkspace;
     const int N = c.frames, last = c.levels - 1;
     std::vector<FrameProducts> fp(N);
-    TRY(mfsr_set_cfa_pattern(c.cfa));
     TRY(flush_pending(b, stream, false));
     // per-frame products of every frame (each serves as reference and as moved frame of some pair)
     for (int k = 0; k < N; k++) {

@@ -74,14 +74,12 @@ template <auto Kernel>
 static int resident_blocks(int threads)
 {
     constexpr int kDevs = 64;
-    static int cache[kDevs];
-    int dev = 0;
+    static std::atomic<int> cache[kDevs];
+    int dev = 0, perCU = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) dev = -1;
     if (dev >= 0 && cache[dev] > 0) return cache[dev];
-    int cus = 0, perCU = 0;
-    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, Kernel, threads, 0) != hipSuccess || perCU <= 0) perCU = 4;
-    const int r = cus * perCU;
+    const int r = mfsr_device_cus() * perCU;
     if (dev >= 0) cache[dev] = r;
     return r;
 }

@@ -157,13 +157,17 @@ inline bool yuv_format(int format) { return format == MFSR_OUT_NV12 || format ==
 // tables that fit (up to kLdsLutMax intervals) and the other formats do not.  MFSR_RENDER_LUT=lds | cache forces one form for
 // every format (A/B); read at every call: host only, and a test can switch it.  The two-plane formats (eight pixels, 24 table
 // reads per lane) follow RGB8.
+enum { LUT_BY_FORMAT = 0, LUT_LDS = 1, LUT_CACHE = 2 };
+int render_lut_forced()
+{
+    const char* e = getenv("MFSR_RENDER_LUT");
+    return !e ? LUT_BY_FORMAT : (strcmp(e, "lds") == 0 ? LUT_LDS : (strcmp(e, "cache") == 0 ? LUT_CACHE : LUT_BY_FORMAT));
+}
 bool lut_in_lds(const mfsr_render* r)
 {
     if (!r->toneLut || r->toneSize > kLdsLutMax) return false;
-    if (const char* e = getenv("MFSR_RENDER_LUT")) {
-        if (strcmp(e, "lds") == 0) return true;
-        if (strcmp(e, "cache") == 0) return false;
-    }
+    const int forced = render_lut_forced();
+    if (forced != LUT_BY_FORMAT) return forced == LUT_LDS;
     return r->format == MFSR_OUT_RGB8 || yuv_format(r->format);
 }
 

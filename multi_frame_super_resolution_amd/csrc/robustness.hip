@@ -421,7 +421,7 @@ __global__ void __launch_bounds__(RB_TX* RB_TY) __attribute__((amdgpu_waves_per_
 }
 
 // 0: the straight kernel (IEEE sqrt / division, ocml expf: tight parity tests); 1 (default): k_robustnessFused
-static int g_robustness_fast = 1;
+static std::atomic<int> g_robustness_fast{1};
 extern "C" int mfsr_set_robustness_fast(int enable)
 {
     g_robustness_fast = enable ? 1 : 0;
@@ -494,26 +494,15 @@ extern "C" int mfsr_robustnessMaskFusedBatch(int nFrames, const mfsr_robustness_
 
 // 1 (default): the burst driver makes the masks of an aligned group with mfsr_prepareFrameMeansBatch + mfsr_robustnessMaskGroup;
 // 0 (mfsr_set_robustness_group / MFSR_ROBUST_GROUP=0): with mfsr_prepareFrameFusedBatch + mfsr_robustnessMaskFusedBatch (A/B)
-static int g_robustness_group = 1;
-static void robust_group_env_once()
-{
-    static const bool env_read = [] {
-        const char* e = getenv("MFSR_ROBUST_GROUP");
-        if (e && e[0] == '0') g_robustness_group = 0;
-        return true;
-    }();
-    (void)env_read;
-}
+static MfsrKnob g_robustness_group;
 extern "C" int mfsr_set_robustness_group(int enable)
 {
-    robust_group_env_once();  // (a later first query must not put the environment's value over this one)
-    g_robustness_group = enable ? 1 : 0;
+    g_robustness_group.set(enable ? 1 : 0);
     return MFSR_OK;
 }
 int mfsr_robustness_group()
 {
-    robust_group_env_once();
-    return g_robustness_group && g_robustness_fast;
+    return g_robustness_group.get([] { return mfsr_env_is0("MFSR_ROBUST_GROUP") ? 0 : 1; }) && g_robustness_fast;
 }
 
 // the kernel addresses a frame's flow, patch-mean and mask images with 32-bit byte offsets
@@ -524,19 +513,19 @@ int mfsr_robustness_group_fits(int h, int flowRowBytes, int meansRowBytes, int m
 }
 
 template <int NF>
-static void launch_robustness_group(dim3 grid, dim3 block, hipStream_t st, const pix3* ref, const RobustGroupArgs& ga, int w, int h,
+static void launch_robustness_group(int cfa, dim3 grid, dim3 block, hipStream_t st, const pix3* ref, const RobustGroupArgs& ga, int w, int h,
                                     int refRowBytes, int flowRowBytes, int meansRowBytes, int maskRowBytes, float maxVal, float alpha,
                                     float beta, float thresholdM)
 {
     hipLaunchKernelGGL(k_robustnessGroup<NF>, grid, block, 0, st, ref, ga, w, h, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes,
-                       maxVal, mfsr_cfa_packed(), alpha, beta, thresholdM, mfsr_exact_div((float)w), mfsr_exact_div((float)h));
+                       maxVal, cfa, alpha, beta, thresholdM, mfsr_exact_div((float)w), mfsr_exact_div((float)h));
 }
 
 // The masks of 1 .. 4 moved frames against one reference in one pass (k_robustnessGroup): bit-identical to
 // mfsr_robustnessMaskFusedBatch with a flow field of the image's resolution
-extern "C" int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf, int refRowBytes,
-                                        int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal, float alpha,
-                                        float beta, float thresholdM, mfsr_stream_t stream)
+int mfsr_cfa::robustnessMaskGroup(int cfa, int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf,
+                                  int refRowBytes, int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal,
+                                  float alpha, float beta, float thresholdM, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(frames && nFrames >= 1 && nFrames <= MFSR_BATCH_MAX && refHalf && w > 2 && h > 2);
     MFSR_REQUIRE((long long)refRowBytes >= 12LL * w && (refRowBytes & 3) == 0);
@@ -559,7 +548,7 @@ extern "C" int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group
     dim3 block(RB_TX, RB_TY), grid(mfsr_cdiv(w, RB_TX), mfsr_cdiv(h, RB_TY));
     const pix3* ref = (const pix3*)refHalf;
     hipStream_t st = mfsr_s(stream);
-#define RB_GROUP_ARGS grid, block, st, ref, ga, w, h, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes, maxVal, alpha, beta, thresholdM
+#define RB_GROUP_ARGS cfa, grid, block, st, ref, ga, w, h, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes, maxVal, alpha, beta, thresholdM
     switch (nFrames) {
         case 1: launch_robustness_group<1>(RB_GROUP_ARGS); break;
         case 2: launch_robustness_group<2>(RB_GROUP_ARGS); break;
@@ -568,6 +557,13 @@ extern "C" int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group
     }
 #undef RB_GROUP_ARGS
     return mfsr_launch_status("robustnessMaskGroup");
+}
+extern "C" int mfsr_robustnessMaskGroup(int nFrames, const mfsr_robustness_group_frame* frames, const mfsr_float3* refHalf, int refRowBytes,
+                                        int flowRowBytes, int meansRowBytes, int maskRowBytes, int w, int h, float maxVal, float alpha,
+                                        float beta, float thresholdM, mfsr_stream_t stream)
+{
+    return mfsr_cfa::robustnessMaskGroup(mfsr_cfa_packed(), nFrames, frames, refHalf, refRowBytes, flowRowBytes, meansRowBytes, maskRowBytes, w,
+                                         h, maxVal, alpha, beta, thresholdM, stream);
 }
 
 extern "C" int mfsr_ComputeRobustnessMask(const mfsr_float3* rawImgRef, const mfsr_float3* rawImgMoved,

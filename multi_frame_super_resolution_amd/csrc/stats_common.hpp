@@ -47,14 +47,4 @@ __device__ __forceinline__ int luma_key(pix3 q)
     return (54 * c0 + 183 * c1 + 19 * c2 + 128) >> 8;
 }
 
-int stats_cus()
-{
-    static int cached = 0;
-    if (cached > 0) return cached;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return 256;
-    return cached = cus;
-}
-
 }  // namespace

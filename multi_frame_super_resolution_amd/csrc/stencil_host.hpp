@@ -22,8 +22,7 @@ bool ranges_overlap(const void* a, long long aBytes, const void* b, long long bB
 // both).
 bool stencil_lut_in_lds(const mfsr_render* r)
 {
-    const char* e = getenv("MFSR_RENDER_LUT");
-    return e && strcmp(e, "lds") == 0 && lut_in_lds(r);
+    return render_lut_forced() == LUT_LDS && lut_in_lds(r);
 }
 
 // bytes from the first byte of row 0 to the last byte of row h - 1 of an image of w pixels of bpp bytes

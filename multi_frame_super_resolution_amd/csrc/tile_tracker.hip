@@ -1186,10 +1186,7 @@ static int track_tiles_fused_impl(const float* refImg, const float* movedImg, co
     if (preShift)
         MFSR_REQUIRE((long long)preShiftPitch >= 8LL * tileCountX && (preShiftPitch & 7) == 0 && ((uintptr_t)preShift & 7) == 0);
     // the pipeline's tile sizes run the compile-time kernel (sum(ref^2) given, as the pipeline does); MFSR_TRK_FAST=0: A/B
-    static const bool fast = [] {
-        const char* e = getenv("MFSR_TRK_FAST");
-        return !(e && e[0] == '0');
-    }();
+    static const bool fast = !mfsr_env_is0("MFSR_TRK_FAST");
 #define TRK_FAST_CASE(TT, SS, TPW)                                                                                       \
     if (fast && refSquaredSums && tileSize == TT && maxShift == SS) {                                                    \
         using G = TrkFast<TT, SS, TPW>;                                                                                  \
@@ -1221,14 +1218,9 @@ static int track_tiles_fused_impl(const float* refImg, const float* movedImg, co
     const int tiles = tileCountX * tileCountY;
     // (one tile of more than 64 KB, e.g. 64 + 2 * 15: the workgroup may take up to the CU's 160 KB once the kernel allows it)
 #define TRK_LAUNCH(N)                                                                                                  \
-    if (lds > 64 * 1024) {                                                                                             \
-        static bool attr_set = false;                                                                                  \
-        if (!attr_set) {                                                                                               \
-            MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_trackTilesFused<N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                             160 * 1024));                                                             \
-            attr_set = true;                                                                                           \
-        }                                                                                                              \
-    }                                                                                                                  \
+    if (lds > 64 * 1024) /* the attribute is the function's on the current device: set for every such launch */        \
+        MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_trackTilesFused<N>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                         160 * 1024));                                                                 \
     hipLaunchKernelGGL(k_trackTilesFused<N>, dim3(mfsr_cdiv(tiles, tilesPerWg)), dim3(TRK_THREADS), lds, mfsr_s(stream),  \
                        refImg, movedImg, (const float2*)preShift, preShiftPitch, (float2*)coordinates, coordinatesPitch, \
                        imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX, tileCountY, threshold,           \

@@ -129,6 +129,60 @@ def test_no_cpu_fallback_without_device():
         BurstPipeline(cfg)
 
 
+def _create_burst_and_stream(cfg):
+    """(rc of mfsr_burst_create, rc of mfsr_stream_create) on a host buffer: neither gets as far as using it without a device"""
+    raw = capi.lib().raw
+    buf = ctypes.create_string_buffer(4096)
+    addr = (ctypes.addressof(buf) + 255) // 256 * 256
+    hb, hs = ctypes.c_void_p(), ctypes.c_void_p()
+    rcs = (raw["mfsr_burst_create"](ctypes.byref(hb), ctypes.byref(cfg), addr, 1 << 40),
+           raw["mfsr_stream_create"](ctypes.byref(hs), ctypes.byref(cfg), 1, 0, addr, 1 << 40))
+    if rcs[0] == 0:
+        raw["mfsr_burst_destroy"](hb)
+    if rcs[1] == 0:
+        raw["mfsr_stream_destroy"](hs)
+    return rcs
+
+
+def test_create_checks_cfg_cfa_on_the_host_and_leaves_the_process_wide_pattern():
+    """cfg.cfa is the burst's own: mfsr_burst_create / mfsr_stream_create refuse an entry outside 0 .. MFSR_WHITE (6) with
+    mfsr_set_cfa_pattern's code before anything touches the device, accept the four Bayer patterns and all-green (without a
+    device the next check, MFSR_E_NODEVICE, answers), and neither changes what mfsr_get_cfa_pattern returns."""
+    import torch
+    raw = capi.lib().raw
+    assert raw["mfsr_set_cfa_pattern"]((ctypes.c_int32 * 4)(1, 0, 2, 1)) == 0   # GRBG: none of the patterns below
+
+    def process_wide():
+        got = (ctypes.c_int32 * 4)()
+        assert raw["mfsr_get_cfa_pattern"](got) == 0
+        return list(got)
+
+    try:
+        cfg = capi.Config()
+        assert raw["mfsr_config_default"](ctypes.byref(cfg), 256, 128, 3, 2, 0) == 0
+        for bad in (7, -1):
+            cfg.cfa[2] = bad
+            assert _create_burst_and_stream(cfg) == (-1, -1), bad   # MFSR_E_INVALID
+            assert process_wide() == [1, 0, 2, 1]
+        # (with a device a create that passes its checks would go on with the host buffer as its workspace: refusals only there)
+        for pat in () if torch.cuda.is_available() else ([0, 1, 1, 2], [2, 1, 1, 0], [1, 0, 2, 1], [1, 2, 0, 1], [1, 1, 1, 1]):
+            for i in range(4):
+                cfg.cfa[i] = pat[i]
+            assert _create_burst_and_stream(cfg) == (-3, -3), pat   # MFSR_E_NODEVICE: past the argument checks
+            assert process_wide() == [1, 0, 2, 1]
+    finally:
+        assert raw["mfsr_set_cfa_pattern"]((ctypes.c_int32 * 4)(0, 1, 1, 2)) == 0
+
+
+@pytest.mark.parametrize("setter", ["mfsr_set_burst_fuse", "mfsr_set_robustness_group", "mfsr_set_margin_sites"])
+def test_knob_setters_take_any_int(setter):
+    """The A/B setters treat their argument as a boolean (non-zero, negative included: on) and return MFSR_OK for every int,
+    as recorded from the library before the knobs moved to one type.  Each ends switched on, its default."""
+    f = capi.lib().raw[setter]
+    for v in (-2147483648, -1, 0, 1, 2, 7, 2147483647, 0, 1):
+        assert f(v) == 0, v
+
+
 def test_product_path_never_imports_the_oracle():
     """oracle/ is test infrastructure: nothing in the package or apps/ may reference it."""
     pkg = os.path.join(ROOT, "multi_frame_super_resolution_amd")
