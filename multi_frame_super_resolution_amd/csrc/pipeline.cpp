@@ -294,6 +294,19 @@ mfsr_tex2d as_tex(const Img& im)
 
 }  // namespace
 
+// The frames of one warp+fuse launch.  A group waits in one of three places of the burst: the filling group (pend), the host
+// burst's second-to-last group (held), the burst hold (hold[]); every function that acts on a group takes it as an argument.
+struct FuseGroup {
+    int n;  // frames (the filling group: 0 .. group - 1 waiting)
+    int slot[MFSR_MAX_FUSE_GROUP];
+    const uint16_t* raw[MFSR_MAX_FUSE_GROUP];
+    const Img* flow[MFSR_MAX_FUSE_GROUP];
+    const Img* mask[MFSR_MAX_FUSE_GROUP];
+    bool deferred[MFSR_MAX_FUSE_GROUP];  // not aligned yet: align_deferred aligns the group's waiting frames as one batch
+    int isRef[MFSR_MAX_FUSE_GROUP];
+    mfsr_float3 *imgOut, *totalWeights;
+};
+
 struct mfsr_burst {
     mfsr_burst(const mfsr_config& c, char* workspace) : cfg(c), L(make_layout(&c, workspace)) {}
     mfsr_config cfg;
@@ -312,26 +325,17 @@ struct mfsr_burst {
                                         // still valid, aligning another frame needs a new set_reference
     // frame grouping (cfg.pairFrames): aligned frames wait here until their group is complete, then the
     // group is fused in one pass over the accumulators; flush/finish fuses what is left of a group
-    struct Pending {
-        int n;  // frames waiting (0 .. group - 1)
-        int slot[MFSR_MAX_FUSE_GROUP];
-        const uint16_t* raw[MFSR_MAX_FUSE_GROUP];
-        const Img* flow[MFSR_MAX_FUSE_GROUP];
-        const Img* mask[MFSR_MAX_FUSE_GROUP];
-        bool deferred[MFSR_MAX_FUSE_GROUP];  // not aligned yet: align_deferred aligns the waiting frames as one batch
-        int isRef[MFSR_MAX_FUSE_GROUP];
-        mfsr_float3 *imgOut, *totalWeights;
-    } pend;
+    FuseGroup pend;
     // host bursts: the burst's second-to-last group, aligned and waiting with the last one (pend) for mfsr_burst_finish_host,
     // which fuses both band by band (heldHas: the entries of `held` are valid)
-    Pending held;
+    FuseGroup held;
     bool heldHas;
     int group;  // frames per warp+fuse launch (mfsr_burst_group_size)
     // burst hold (mfsr_burst_hold_fuse): complete, aligned groups whose fuse waits for flush / finish / a full ring, where
     // two or more of them leave as ONE launch (mfsr_accumulateSuperResBurst); in arrival order, all on the same accumulators
     bool holdFuse;
     int nHold;
-    Pending hold[MFSR_MAX_BURST_FUSE / MFSR_MAX_FUSE_GROUP];
+    FuseGroup hold[MFSR_MAX_BURST_FUSE / MFSR_MAX_FUSE_GROUP];
     int burstLaunches, burstGroups;  // burst launches since mfsr_burst_begin and the groups they fused (mfsr_burst_fuse_stats)
     int nFramesTimed;
     // mfsr_burst_begin: these accumulators are to be overwritten by the first fuse instead of zeroed
@@ -378,7 +382,7 @@ struct mfsr_burst {
     int robustGroupLaunches;  // launches of mfsr_robustnessMaskGroup since mfsr_burst_begin (mfsr_burst_debug_robust_group)
     // The finish inside the burst launch (mfsr_accumulateSuperResBurstFinish): mfsr_burst_finish sets finishOut16 before it
     // flushes when the hold's launch is the burst's last fuse and the plain whole-frame uint16_t image is all it was asked for;
-    // fuse_hold then issues the finishing launch and sets finishTaken, or launches as ever where the entry refuses.
+    // drain_waiting then issues the finishing launch and sets finishTaken, or launches as ever where the entry refuses.
     uint16_t* finishOut16;
     bool finishTaken;
     int fusedFinishes;  // finishes taken that way since mfsr_burst_begin (mfsr_burst_debug_finish_fused)
@@ -442,26 +446,40 @@ static int out_w(const mfsr_burst* b) { return b->win.on ? b->win.w : b->L.hrW; 
 static int out_h(const mfsr_burst* b) { return b->win.on ? b->win.h : b->L.hrH; }
 static size_t acc_bytes(const mfsr_burst* b) { return (size_t)12 * out_w(b) * out_h(b); }
 
-// stage G of n frames onto the burst's accumulators, output rows [r0, r1) of the burst's output (the window's rows when one is
-// set; the pointers are the accumulators' first pixel either way)
-static int fuse_group(mfsr_burst* b, int n, const uint16_t* const* raws, mfsr_float3* imgOut, mfsr_float3* totalWeights,
-                      const mfsr_float4* const* masks, const mfsr_tex2d* flows, int maskPitch, int fresh, int r0, int r1,
-                      mfsr_stream_t stream)
+// the config's levels as the kernels take them
+static mfsr_float3 cfg_white(const mfsr_config& c) { return {c.white[0], c.white[1], c.white[2]}; }
+static mfsr_float3 cfg_black(const mfsr_config& c) { return {c.black[0], c.black[1], c.black[2]}; }
+
+// the certainty masks and the flows of an aligned group, frame i at masks[i] / flows[i]
+static void group_tables(const FuseGroup& g, mfsr_tex2d* masks, mfsr_tex2d* flows)
+{
+    for (int i = 0; i < g.n; i++) {
+        masks[i] = as_tex(*g.mask[i]);
+        flows[i] = as_tex(*g.flow[i]);
+    }
+}
+
+// stage G of an aligned group onto its accumulators, output rows [r0, r1) of the burst's output (the window's rows when one is
+// set; the group's pointers are the accumulators' first pixel either way)
+static int fuse_group(mfsr_burst* b, const FuseGroup& g, int fresh, int r0, int r1, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
-    const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
-    const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
+    const mfsr_float3 white = cfg_white(c), black = cfg_black(c);
+    mfsr_tex2d maskTex[MFSR_MAX_FUSE_GROUP], flows[MFSR_MAX_FUSE_GROUP];
+    group_tables(g, maskTex, flows);
+    const mfsr_float4* masks[MFSR_MAX_FUSE_GROUP];
+    for (int i = 0; i < g.n; i++) masks[i] = (const mfsr_float4*)maskTex[i].ptr;
+    const int maskPitch = maskTex[0].pitch;
     if (!b->win.on)
-        return mfsr_cfa::accumulateSuperResFullRows(b->cfa, n, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), flows, white, black, L.W, L.H,
-                                               c.scale, 12 * L.hrW, maskPitch, fresh, r0, r1, stream);
+        return mfsr_cfa::accumulateSuperResFullRows(b->cfa, g.n, g.raw, g.imgOut, g.totalWeights, masks, as_tex(L.kparam4), flows, white, black,
+                                               L.W, L.H, c.scale, 12 * L.hrW, maskPitch, fresh, r0, r1, stream);
     const int pitch = 12 * b->win.w;
     const size_t off = (size_t)r0 * pitch;
-    return mfsr_cfa::accumulateSuperResFullWindow(b->cfa, n, raws, (mfsr_float3*)((char*)imgOut + off), (mfsr_float3*)((char*)totalWeights + off),
-                                             masks, as_tex(L.kparam4), flows, white, black, L.W, L.H, c.scale, pitch, maskPitch, fresh,
-                                             b->win.x0, b->win.y0 + r0, b->win.w, r1 - r0, stream);
+    return mfsr_cfa::accumulateSuperResFullWindow(b->cfa, g.n, g.raw, (mfsr_float3*)((char*)g.imgOut + off),
+                                             (mfsr_float3*)((char*)g.totalWeights + off), masks, as_tex(L.kparam4), flows, white, black, L.W,
+                                             L.H, c.scale, pitch, maskPitch, fresh, b->win.x0, b->win.y0 + r0, b->win.w, r1 - r0, stream);
 }
-
 
 extern "C" int mfsr_config_default(mfsr_config* cfg, int width, int height, int frames, int scale, int mono)
 {
@@ -920,7 +938,7 @@ static int set_reference_impl(mfsr_burst* b, const uint16_t* rawRef, int hrRow0,
     // A2 + A3: debayered reference = fallback image of ApplyWeighting (finish resamples it bilinearly: raw rows Y / s +- 1;
     // the row window starts on an even row -- the CFA phase -- and carries the 3-row stencil halo plus the 2-row ring the
     // kernels leave untouched at a window edge)
-    const mfsr_float3 bp = {c.black[0], c.black[1], c.black[2]};
+    const mfsr_float3 bp = cfg_black(c);
     const mfsr_float3 sc = {1.0f / c.white[0], 1.0f / c.white[1], 1.0f / c.white[2]};
     int r0 = 0, r1 = L.H;
     if (!whole) {
@@ -1094,10 +1112,80 @@ static int upload_slot_of(const mfsr_burst* b, const uint16_t* raw)
     return -1;
 }
 
-static int align_deferred(mfsr_burst* b, mfsr_stream_t stream);
+static int align_deferred(mfsr_burst* b, FuseGroup& g, mfsr_stream_t stream);
 
-// G: the waiting group (b->pend, 1 .. MFSR_MAX_FUSE_GROUP aligned frames) onto its accumulators (timed with HIP events on request)
-static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream);
+// ---- bookkeeping every fuse launch shares ---------------------------------------------------------------------------------
+// Per-launch timing on request (mfsr_burst_timing): the event pair round a launch on `stream`.  *timed is handed on to timed_end,
+// with the launches the pair stands for (1, or the groups of a burst launch) and the frames they fused.
+static int timed_begin(mfsr_burst* b, mfsr_stream_t stream, bool* timed)
+{
+    *timed = b->timing && b->nEvents < kMaxTimedLaunches;
+    if (*timed) {
+        const int i = b->nEvents;
+        if (!b->evStart[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStart[i]));
+        if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
+        MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
+    }
+    return MFSR_OK;
+}
+static int timed_end(mfsr_burst* b, bool timed, int launches, int frames, mfsr_stream_t stream)
+{
+    if (timed) {
+        MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
+        b->evLaunches[b->nEvents] = launches;
+        b->nEvents++;
+        b->nFramesTimed += frames;
+    }
+    return MFSR_OK;
+}
+
+// mfsr_burst_begin(A, W): the first fuse onto A and W overwrites them (they are not zeroed or read)
+static bool fresh_for(const mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights)
+{
+    return b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
+}
+// ... and the zeroes A and W are owed when nothing overwrites them
+static int zero_fresh(mfsr_burst* b, mfsr_stream_t stream)
+{
+    const size_t bytes = acc_bytes(b);
+    MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
+    MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
+    b->fresh.has = false;
+    return MFSR_OK;
+}
+// The fresh decision of a fuse onto imgOut / totalWeights on `stream`: *freshNow = this fuse is the overwriting one.  A fuse into
+// other accumulators than those of mfsr_burst_begin: A and W get their zeroes here.  Either way the burst is fresh no longer.
+static int take_fresh(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, mfsr_stream_t stream, int* freshNow)
+{
+    *freshNow = fresh_for(b, imgOut, totalWeights);
+    if (b->fresh.has && !*freshNow) TRY(zero_fresh(b, stream));
+    b->fresh.has = false;
+    return MFSR_OK;
+}
+
+// upload slots whose raw frame the group's launch on `stream` was the last to read may be overwritten once it has run
+static int release_group_slots(mfsr_burst* b, const FuseGroup& g, mfsr_stream_t stream)
+{
+    if (!b->copyStream) return MFSR_OK;
+    for (int j = 0; j < g.n; j++) {
+        const int us = upload_slot_of(b, g.raw[j]);
+        if (us >= 0) TRY(record_free(b, us, stream));
+    }
+    return MFSR_OK;
+}
+
+// a ring slot's buffers are free once the fuse that read them last has run: `stream` is about to rewrite them
+static int wait_slot_fused(mfsr_burst* b, int slot, mfsr_stream_t stream)
+{
+    if (b->fuseStream && b->fusedOutstanding[slot]) {
+        MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[slot], 0));
+        b->fusedOutstanding[slot] = false;
+    }
+    return MFSR_OK;
+}
+
+// between bursts: no group waits anywhere and no packed upload waits for its unpack
+static bool burst_idle(const mfsr_burst* b) { return b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0; }
 
 // ---- burst hold -------------------------------------------------------------------------------------------------------------
 // Process-wide switch of the burst hold for A/B (mfsr_set_burst_fuse; MFSR_BURST_FUSE=0 in the environment): off, every
@@ -1159,14 +1247,43 @@ static bool can_hold_group(const mfsr_burst* b, bool hostBurst)
     return true;
 }
 
-static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream);
+// G: one aligned group (1 .. MFSR_MAX_FUSE_GROUP frames) onto its accumulators as the ordinary launch, with all of its
+// bookkeeping (timed with HIP events on request)
+static int launch_group(mfsr_burst* b, const FuseGroup& g, mfsr_stream_t callerStream)
+{
+    const int n = g.n;
+    if (n == 0) return MFSR_OK;
+    // with asyncFuse the launch goes to the burst's own stream, ordered after the alignment of its frames
+    mfsr_stream_t stream = callerStream;
+    if (b->fuseStream) {
+        stream = (mfsr_stream_t)b->fuseStream;
+        for (int i = 0; i < n; i++) MFSR_HIP_TRY(hipStreamWaitEvent(b->fuseStream, b->evAligned[g.slot[i]], 0));
+    }
+    bool timed;
+    TRY(timed_begin(b, stream, &timed));
+    int freshNow;
+    TRY(take_fresh(b, g.imgOut, g.totalWeights, stream, &freshNow));
+    TRY(fuse_group(b, g, freshNow, 0, out_h(b), stream));
+    TRY(timed_end(b, timed, 1, n, stream));
+    TRY(release_group_slots(b, g, stream));
+    if (b->fuseStream) {
+        for (int i = 0; i < n; i++) {
+            MFSR_HIP_TRY(hipEventRecord(b->evFused[g.slot[i]], b->fuseStream));
+            b->fusedOutstanding[g.slot[i]] = true;
+        }
+    }
+    return MFSR_OK;
+}
 
-// The held groups onto their accumulators, in arrival order: two or more as ONE launch (counted as one timed launch per group,
-// so that mfsr_burst_timing_read's average stays "per four-frame group"), a single one as the ordinary launch it would have been.
-static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
+// The groups that wait outside the filling group onto their accumulators, in arrival order: the burst hold's first (a held
+// group can only have arrived after every one of them: can_hold_group refuses while one is held), then -- heldToo -- the host
+// burst's held group.  Two or more hold groups leave as ONE launch (counted as one timed launch per group, so that
+// mfsr_burst_timing_read's average stays "per four-frame group"); a single one, or a geometry the burst kernel does not take,
+// as the ordinary launches they would have been, and so does the held group: exactly as if it had not been held.
+// (heldToo = false: callers that only need the hold's ring slots, and mfsr_burst_finish_host, which fuses `held` band by band)
+static int drain_waiting(mfsr_burst* b, mfsr_stream_t stream, bool heldToo = true)
 {
     const int G = b->nHold;
-    if (G == 0) return MFSR_OK;
     b->nHold = 0;
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
@@ -1174,13 +1291,11 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
     if (G >= 2) {
         const uint16_t* raws[MFSR_MAX_BURST_FUSE];
         mfsr_tex2d masks[MFSR_MAX_BURST_FUSE], flows[MFSR_MAX_BURST_FUSE];
-        for (int g = 0; g < G; g++)
-            for (int i = 0; i < MFSR_MAX_FUSE_GROUP; i++) {
-                const int k = g * MFSR_MAX_FUSE_GROUP + i;
-                raws[k] = b->hold[g].raw[i];
-                masks[k] = as_tex(*b->hold[g].mask[i]);
-                flows[k] = as_tex(*b->hold[g].flow[i]);
-            }
+        for (int g = 0; g < G; g++) {
+            const int k = g * MFSR_MAX_FUSE_GROUP;
+            for (int i = 0; i < MFSR_MAX_FUSE_GROUP; i++) raws[k + i] = b->hold[g].raw[i];
+            group_tables(b->hold[g], masks + k, flows + k);
+        }
         mfsr_float3* imgOut = b->hold[0].imgOut;
         mfsr_float3* totalWeights = b->hold[0].totalWeights;
         mfsr_tex2d acc[2];
@@ -1190,20 +1305,13 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
             acc[p].width = L.hrW;
             acc[p].height = L.hrH;
         }
-        const int freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
-        const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
-        if (timed) {
-            const int i = b->nEvents;
-            if (!b->evStart[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStart[i]));
-            if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
-            MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
-        }
-        const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
-        const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
+        int freshNow = fresh_for(b, imgOut, totalWeights);  // (taken after the launch: an entry that refuses leaves the burst fresh)
+        bool timed;
+        TRY(timed_begin(b, stream, &timed));
+        const mfsr_float3 white = cfg_white(c), black = cfg_black(c);
         // the burst's last fuse and a plain uint16_t finish waiting behind it (mfsr_burst_finish): the launch finishes as well
         uint16_t* const out16 = b->finishOut16;
         b->finishOut16 = nullptr;
-        rc = MFSR_E_UNSUPPORTED;
         if (out16) {
             mfsr_tex2d fb;  // as mfsr_burst_finish hands it to mfsr_finishFused: the LR image at its pitch
             fb.ptr = L.fallback.ptr;
@@ -1222,116 +1330,35 @@ static int fuse_hold(mfsr_burst* b, mfsr_stream_t stream)
             rc = mfsr_cfa::accumulateSuperResBurst(b->cfa, G * MFSR_MAX_FUSE_GROUP, raws, acc[0], acc[1], masks, as_tex(L.kparam4), flows, white, black,
                                               c.scale, freshNow, stream);
         if (rc == MFSR_OK) {
-            if (b->fresh.has && !freshNow) {
-                // begin(A, W) followed by a fuse into other accumulators: A and W still owe their zeroes
-                const size_t bytes = acc_bytes(b);
-                MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
-                MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
-            }
-            b->fresh.has = false;
+            TRY(take_fresh(b, imgOut, totalWeights, stream, &freshNow));
             b->burstLaunches++;
             b->burstGroups += G;
-            if (timed) {
-                MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
-                b->evLaunches[b->nEvents] = G;
-                b->nEvents++;
-                b->nFramesTimed += G * MFSR_MAX_FUSE_GROUP;
-            }
-            return MFSR_OK;
-        }
-        if (rc != MFSR_E_UNSUPPORTED) return rc;
+            TRY(timed_end(b, timed, G, G * MFSR_MAX_FUSE_GROUP, stream));
+        } else if (rc != MFSR_E_UNSUPPORTED)
+            return rc;
     }
-    // one group, or a geometry the burst kernel does not take (nothing was touched): the launches these groups would have been
-    const mfsr_burst::Pending later = b->pend;
-    for (int g = 0; g < G; g++) {
-        b->pend = b->hold[g];
-        const int rc1 = accumulate_pending(b, stream);
-        if (rc1 != MFSR_OK) {
-            b->pend = later;
-            return rc1;
-        }
+    // (a refusal touched nothing)
+    for (int g = 0; g < G && rc == MFSR_E_UNSUPPORTED; g++) {
+        TRY(wait_uploads(b, stream));
+        TRY(launch_group(b, b->hold[g], stream));
     }
-    b->pend = later;
-    return MFSR_OK;
-}
-
-// a group that was held back for mfsr_burst_finish_host and is fused the ordinary way after all (flush / finish / another
-// accumulator pair / its upload slot is needed): as its own launch, exactly as if it had not been held
-static int fuse_held(mfsr_burst* b, mfsr_stream_t callerStream)
-{
-    if (!b->heldHas) return MFSR_OK;
-    const mfsr_burst::Pending later = b->pend;
-    b->pend = b->held;
+    if (!heldToo || !b->heldHas) return MFSR_OK;
+    const FuseGroup held = b->held;
     b->heldHas = false;
     b->held.n = 0;
-    const int rc = accumulate_pending(b, callerStream);
-    b->pend = later;
-    return rc;
+    TRY(wait_uploads(b, stream));
+    return launch_group(b, held, stream);
 }
 
-static int accumulate_pending(mfsr_burst* b, mfsr_stream_t callerStream)
+// the filling group onto its accumulators, behind everything that arrived before it
+static int accumulate_pending(mfsr_burst* b, mfsr_stream_t stream)
 {
-    TRY(fuse_hold(b, callerStream));       // the burst hold's groups come before everything that arrived after them
-    TRY(fuse_held(b, callerStream));       // it comes before the frames that arrived after it
-    TRY(align_deferred(b, callerStream));  // frames of the group that were waiting for their batch
-    TRY(wait_uploads(b, callerStream));    // (a reference frame of the group is read by the fuse only)
-    const mfsr_burst::Pending p = b->pend;
+    TRY(drain_waiting(b, stream));
+    TRY(align_deferred(b, b->pend, stream));  // frames of the group that were waiting for their batch
+    TRY(wait_uploads(b, stream));             // (a reference frame of the group is read by the fuse only)
+    const FuseGroup g = b->pend;
     b->pend.n = 0;
-    const int n = p.n;
-    if (n == 0) return MFSR_OK;
-    mfsr_float3* imgOut = p.imgOut;
-    mfsr_float3* totalWeights = p.totalWeights;
-    // with asyncFuse the launch goes to the burst's own stream, ordered after the alignment of its frames
-    mfsr_stream_t stream = callerStream;
-    if (b->fuseStream) {
-        stream = (mfsr_stream_t)b->fuseStream;
-        for (int i = 0; i < n; i++) MFSR_HIP_TRY(hipStreamWaitEvent(b->fuseStream, b->evAligned[p.slot[i]], 0));
-    }
-    const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
-    if (timed) {
-        const int i = b->nEvents;
-        if (!b->evStart[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStart[i]));
-        if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
-        MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
-    }
-    {
-        const mfsr_float4* masks[MFSR_MAX_FUSE_GROUP];
-        mfsr_tex2d flows[MFSR_MAX_FUSE_GROUP];
-        for (int i = 0; i < n; i++) {
-            masks[i] = (const mfsr_float4*)p.mask[i]->ptr;
-            flows[i] = as_tex(*p.flow[i]);
-        }
-        // the first fuse after mfsr_burst_begin overwrites the accumulators (they are not zeroed or read)
-        const int freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
-        if (b->fresh.has && !freshNow) {
-            // begin(A, W) followed by a fuse into other accumulators: A and W still owe their zeroes
-            const size_t bytes = acc_bytes(b);
-            MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
-            MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
-        }
-        b->fresh.has = false;
-        TRY(fuse_group(b, n, p.raw, imgOut, totalWeights, masks, flows, p.mask[0]->pitch, freshNow, 0, out_h(b), stream));
-    }
-    if (timed) {
-        MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
-        b->evLaunches[b->nEvents] = 1;
-        b->nEvents++;
-        b->nFramesTimed += n;
-    }
-    if (b->copyStream) {
-        // upload slots whose raw frame this launch was the last to read may be overwritten once it has run
-        for (int j = 0; j < n; j++) {
-            const int us = upload_slot_of(b, p.raw[j]);
-            if (us >= 0) TRY(record_free(b, us, stream));
-        }
-    }
-    if (b->fuseStream) {
-        for (int i = 0; i < n; i++) {
-            MFSR_HIP_TRY(hipEventRecord(b->evFused[p.slot[i]], b->fuseStream));
-            b->fusedOutstanding[p.slot[i]] = true;
-        }
-    }
-    return MFSR_OK;
+    return launch_group(b, g, stream);
 }
 
 // `stream` is about to read the kernel parameters / the fallback image: wait for the launches that make them
@@ -1357,13 +1384,8 @@ static int join_fuse(mfsr_burst* b, mfsr_stream_t stream)
 // fuse the frames still waiting for the rest of their group, then join: afterwards the caller's stream sees every frame
 static int flush_pending(mfsr_burst* b, mfsr_stream_t stream, bool materializeFresh)
 {
-    if (materializeFresh && b->fresh.has && b->pend.n == 0 && !b->heldHas && b->nHold == 0) {
-        // mfsr_burst_begin with no frame fused since: the accumulators must read as zero
-        const size_t bytes = acc_bytes(b);
-        MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
-        MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
-        b->fresh.has = false;
-    }
+    // mfsr_burst_begin with no frame fused since: the accumulators must read as zero
+    if (materializeFresh && b->fresh.has && b->pend.n == 0 && !b->heldHas && b->nHold == 0) TRY(zero_fresh(b, stream));
     TRY(accumulate_pending(b, stream));
     return join_fuse(b, stream);
 }
@@ -1398,11 +1420,7 @@ static int align_pre(mfsr_burst* b, const uint16_t* raw, int isReference, int sl
     const Layout& L = b->L;
     const FrameProducts& ref = b->ref;
     TRY(wait_uploads(b, stream));
-    // the slot's buffers are free once the fuse that read them last has run
-    if (b->fuseStream && b->fusedOutstanding[slot]) {
-        MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[slot], 0));
-        b->fusedOutstanding[slot] = false;
-    }
+    TRY(wait_slot_fused(b, slot, stream));
     const Img* flow = &L.flowBuf[2 * slot];
     if (isReference) {
         const Img* mask = &L.maskBuf[slot];
@@ -1453,6 +1471,34 @@ static int align_pre(mfsr_burst* b, const uint16_t* raw, int isReference, int sl
     return MFSR_OK;
 }
 
+// one frame of a sweep launch, iteration `it` of the fused Lucas-Kanade: the slot's flow pair and the frame's running sums ping-pong
+static mfsr_lk_frame lk_frame_desc(const Layout& L, int slot, int it, bool lastIt, const FrameProducts& mov, const AlignScratch& work)
+{
+    const int in = it & 1, out = in ^ 1;
+    mfsr_lk_frame f;
+    f.shiftsIn = (const mfsr_float2*)L.flowBuf[2 * slot + in].ptr;
+    f.shiftsOut = (mfsr_float2*)L.flowBuf[2 * slot + out].ptr;
+    f.movedImg = (const float*)mov.pyr[0].ptr;
+    f.sumIn = (const float*)work.lkSum[in].ptr;
+    f.diffIn = (const float*)work.lkDiff[in].ptr;
+    f.sumOut = lastIt ? nullptr : (float*)work.lkSum[out].ptr;
+    f.diffOut = lastIt ? nullptr : (float*)work.lkDiff[out].ptr;
+    return f;
+}
+
+// the fused prepare launch's table for the moved frames of a batch: the frame at batch position mq[k] is g's frame idx[mq[k]]
+static void prepare_table(const Layout& L, const FuseGroup& g, const int* idx, const int* mq, int m, mfsr_prepare_frame* pf)
+{
+    const int nlev = ilog2(L.maxFactor) + 1;
+    for (int k = 0; k < m; k++) {
+        const Img* pyr = L.mov[mq[k]].pyr;
+        pf[k].dataIn = g.raw[idx[mq[k]]];
+        pf[k].halfOut = (mfsr_float3*)L.mov[mq[k]].half.ptr;
+        pf[k].pyr0 = (float*)pyr[0].ptr;
+        pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
+    }
+}
+
 // align_lk: K, the Lucas-Kanade iterations of one moved frame, launch by launch; the flow ends in final_flow(b, slot, 0)
 static int align_lk(mfsr_burst* b, int slot, const FrameProducts& mov, const AlignScratch& work, mfsr_stream_t stream)
 {
@@ -1470,14 +1516,7 @@ static int align_lk(mfsr_burst* b, int slot, const FrameProducts& mov, const Ali
             // the sweep kernel wherever it applies, also for a single frame: the frame-by-frame paths (frame streams,
             // joint mode, mfsr_burst_align_frame of the multi-GPU layer, groups of one) then give the very bits of the
             // frame-batched burst -- its result does not depend on how many frames share a launch
-            mfsr_lk_frame one;
-            one.shiftsIn = (const mfsr_float2*)flow->ptr;
-            one.shiftsOut = (mfsr_float2*)other->ptr;
-            one.movedImg = (const float*)mov.pyr[0].ptr;
-            one.sumIn = (const float*)work.lkSum[in].ptr;
-            one.diffIn = (const float*)work.lkDiff[in].ptr;
-            one.sumOut = lastIt ? nullptr : (float*)work.lkSum[out].ptr;
-            one.diffOut = lastIt ? nullptr : (float*)work.lkDiff[out].ptr;
+            const mfsr_lk_frame one = lk_frame_desc(L, slot, it, lastIt, mov, work);
             const int rcs = mfsr_lucasKanadeSweepBatch(1, &one, (const float*)ref.pyr[0].ptr, flow->pitch, ref.pyr[0].pitch,
                                                        work.lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet, scale, stream);
             if (rcs != MFSR_E_UNSUPPORTED) {
@@ -1602,14 +1641,14 @@ static bool can_defer_alignment(const mfsr_burst* b, bool supplied)
            c.lkHalfWindow >= 1 && c.lkHalfWindow <= 7 && !supplied && !hostImmediate;
 }
 
-static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
+static int align_deferred(mfsr_burst* b, FuseGroup& g, mfsr_stream_t stream)
 {
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
     const FrameProducts& ref = b->ref;
     int idx[MFSR_MAX_FUSE_GROUP], n = 0;
-    for (int i = 0; i < b->pend.n; i++)
-        if (b->pend.deferred[i]) idx[n++] = i;
+    for (int i = 0; i < g.n; i++)
+        if (g.deferred[i]) idx[n++] = i;
     if (n == 0) return MFSR_OK;
     TRY(wait_uploads(b, stream));
     b->paths[MFSR_PATH_ALIGN_BATCHES]++;
@@ -1623,7 +1662,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     for (int l = 0; l < c.levels && stageBatch; l++) stageBatch = mfsr_trackTilesFastSupported(c.tileSize[l], c.maxShift[l]) != 0;
     int mq[MFSR_MAX_FUSE_GROUP], m = 0;  // batch positions of the moved (non-reference) frames
     for (int q = 0; q < n; q++)
-        if (!b->pend.isRef[idx[q]]) mq[m++] = q;
+        if (!g.isRef[idx[q]]) mq[m++] = q;
     // The masks of the group in one pass (mfsr_robustnessMaskGroup): the prepare launch then leaves the 3 x 3 patch MEANS of the
     // half-resolution image in L.mov[q].half, which on this path only the mask kernel reads.  Decided once, here, for both launches.
     const bool maskGroup = stageBatch && m > 0 && b->ntaps >= 3 && mfsr_robustness_group() != 0 &&
@@ -1631,25 +1670,16 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     if (stageBatch) {
         b->paths[MFSR_PATH_STAGE_BATCHES]++;
         for (int q = 0; q < n; q++) {
-            const int i = idx[q], slot = b->pend.slot[i];
-            if (b->pend.isRef[i]) {  // identity flow, certainty 1 (and the slot wait) through the frame path
-                TRY(align_pre(b, b->pend.raw[i], 1, slot, L.mov[q], false, L.work[q], nullptr, stream));
-            } else if (b->fuseStream && b->fusedOutstanding[slot]) {
-                // the slot's buffers are free once the fuse that read them last has run
-                MFSR_HIP_TRY(hipStreamWaitEvent(mfsr_s(stream), b->evFused[slot], 0));
-                b->fusedOutstanding[slot] = false;
-            }
+            const int i = idx[q], slot = g.slot[i];
+            if (g.isRef[i]) {  // identity flow, certainty 1 (and the slot wait) through the frame path
+                TRY(align_pre(b, g.raw[i], 1, slot, L.mov[q], false, L.work[q], nullptr, stream));
+            } else
+                TRY(wait_slot_fused(b, slot, stream));
         }
         if (m > 0) {
             // A1 + luma + prefilter + first pyramid level
             mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
-            for (int k = 0; k < m; k++) {
-                const Img* pyr = L.mov[mq[k]].pyr;
-                pf[k].dataIn = b->pend.raw[idx[mq[k]]];
-                pf[k].halfOut = (mfsr_float3*)L.mov[mq[k]].half.ptr;
-                pf[k].pyr0 = (float*)pyr[0].ptr;
-                pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
-            }
+            prepare_table(L, g, idx, mq, m, pf);
             TRY(mfsr_cfa::prepareFrames(b->cfa, m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
                                         nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream, maskGroup));
             b->paths[MFSR_PATH_PREPARE_BATCH]++;
@@ -1683,7 +1713,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
             const int last = c.levels - 1;
             mfsr_flowfield_frame ff[MFSR_MAX_FUSE_GROUP];
             for (int k = 0; k < m; k++) {
-                const int slot = b->pend.slot[idx[mq[k]]];
+                const int slot = g.slot[idx[mq[k]]];
                 ff[k].outImg = (mfsr_float2*)L.flowBuf[2 * slot].ptr;
                 ff[k].tileShifts = (const mfsr_float2*)L.work[mq[k]].shifts[last].ptr;
                 ff[k].base = nullptr;
@@ -1700,7 +1730,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         // per-frame stages up to the flow field + first warp
         for (int q = 0; q < n; q++) {
             const int i = idx[q];
-            TRY(align_pre(b, b->pend.raw[i], b->pend.isRef[i], b->pend.slot[i], L.mov[q], false, L.work[q], nullptr, stream));
+            TRY(align_pre(b, g.raw[i], g.isRef[i], g.slot[i], L.mov[q], false, L.work[q], nullptr, stream));
         }
     }
     // every Lucas-Kanade iteration of the batch in one launch
@@ -1709,21 +1739,8 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         mfsr_lk_frame fr[MFSR_MAX_FUSE_GROUP];
         int m = 0;
         const bool lastIt = it == c.lkIterations - 1;
-        const int in = it & 1, out = in ^ 1;
-        for (int q = 0; q < n; q++) {
-            const int i = idx[q];
-            if (b->pend.isRef[i]) continue;
-            const int slot = b->pend.slot[i];
-            const Img *sum = L.work[q].lkSum, *diff = L.work[q].lkDiff;
-            fr[m].shiftsIn = (const mfsr_float2*)L.flowBuf[2 * slot + in].ptr;
-            fr[m].shiftsOut = (mfsr_float2*)L.flowBuf[2 * slot + out].ptr;
-            fr[m].movedImg = (const float*)L.mov[q].pyr[0].ptr;
-            fr[m].sumIn = (const float*)sum[in].ptr;
-            fr[m].diffIn = (const float*)diff[in].ptr;
-            fr[m].sumOut = lastIt ? nullptr : (float*)sum[out].ptr;
-            fr[m].diffOut = lastIt ? nullptr : (float*)diff[out].ptr;
-            m++;
-        }
+        for (int q = 0; q < n; q++)
+            if (!g.isRef[idx[q]]) fr[m++] = lk_frame_desc(L, g.slot[idx[q]], it, lastIt, L.mov[q], L.work[q]);
         if (m == 0) break;
         const int rc = mfsr_lucasKanadeSweepBatch(m, fr, (const float*)ref.pyr[0].ptr, L.flowBuf[0].pitch, ref.pyr[0].pitch,
                                                   L.work[0].lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
@@ -1740,22 +1757,16 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     if (maskGroup && !batched) {
         // (cannot happen, as above: the frame-by-frame masks read the half-resolution images, so put them back)
         mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
-        for (int k = 0; k < m; k++) {
-            const Img* pyr = L.mov[mq[k]].pyr;
-            pf[k].dataIn = b->pend.raw[idx[mq[k]]];
-            pf[k].halfOut = (mfsr_float3*)L.mov[mq[k]].half.ptr;
-            pf[k].pyr0 = (float*)pyr[0].ptr;
-            pf[k].pyr1 = nlev > 1 ? (float*)pyr[1].ptr : nullptr;
-        }
+        prepare_table(L, g, idx, mq, m, pf);
         TRY(mfsr_cfa::prepareFrames(b->cfa, m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
                                     nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream, false));
     }
     if (maskBatch && maskGroup) {
         mfsr_robustness_group_frame gf[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
-            const int slot = b->pend.slot[idx[mq[k]]];
+            const int slot = g.slot[idx[mq[k]]];
             gf[k].movedMeans = (const mfsr_float3*)L.mov[mq[k]].half.ptr;
-            gf[k].movedRaw = b->pend.raw[idx[mq[k]]];
+            gf[k].movedRaw = g.raw[idx[mq[k]]];
             gf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
             gf[k].flow = (const mfsr_float2*)final_flow(b, slot, 0)->ptr;
         }
@@ -1766,7 +1777,7 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
     } else if (maskBatch) {
         mfsr_robustness_frame rf[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
-            const int slot = b->pend.slot[idx[mq[k]]];
+            const int slot = g.slot[idx[mq[k]]];
             rf[k].movedHalf = (const mfsr_float3*)L.mov[mq[k]].half.ptr;
             rf[k].mask = (mfsr_float4*)(c.maskErode > 0 ? L.maskRaw[k].ptr : L.maskBuf[slot].ptr);
             rf[k].flow = (const mfsr_float2*)final_flow(b, slot, 0)->ptr;
@@ -1785,21 +1796,21 @@ static int align_deferred(mfsr_burst* b, mfsr_stream_t stream)
         mfsr_float4* eout[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
             ein[k] = (const mfsr_float4*)L.maskRaw[k].ptr;
-            eout[k] = (mfsr_float4*)L.maskBuf[b->pend.slot[idx[mq[k]]]].ptr;
+            eout[k] = (mfsr_float4*)L.maskBuf[g.slot[idx[mq[k]]]].ptr;
         }
         TRY(mfsr_erodeMaskBatch(m, ein, eout, L.hw, L.hh, L.maskRaw[0].pitch, L.maskBuf[0].pitch, c.maskErode, stream));
     }
     for (int q = 0; q < n; q++) {
-        const int i = idx[q], slot = b->pend.slot[i];
-        if (!b->pend.isRef[i]) {
+        const int i = idx[q], slot = g.slot[i];
+        if (!g.isRef[i]) {
             if (!batched) TRY(align_lk(b, slot, L.mov[q], L.work[q], stream));
             if (!maskBatch) TRY(align_post(b, slot, L.mov[q], stream));
         }
-        aligned_outputs(b, slot, b->pend.isRef[i], &b->pend.flow[i], &b->pend.mask[i]);
-        b->pend.deferred[i] = false;
-        b->flowCur = b->pend.flow[i];
-        b->maskCur = b->pend.mask[i];
-        if (b->fuseStream) MFSR_HIP_TRY(hipEventRecord(b->evAligned[b->pend.slot[i]], mfsr_s(stream)));
+        aligned_outputs(b, slot, g.isRef[i], &g.flow[i], &g.mask[i]);
+        g.deferred[i] = false;
+        b->flowCur = g.flow[i];
+        b->maskCur = g.mask[i];
+        if (b->fuseStream) MFSR_HIP_TRY(hipEventRecord(b->evAligned[g.slot[i]], mfsr_s(stream)));
     }
     return MFSR_OK;
 }
@@ -1821,7 +1832,7 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     // burst hold: held groups leave when this frame goes to other accumulators, or when its ring slot would be one of theirs
     if (b->nHold && (b->hold[0].imgOut != imgOut || b->hold[0].totalWeights != totalWeights ||
                      b->nHold * MFSR_MAX_FUSE_GROUP + b->pend.n >= b->ring))
-        TRY(fuse_hold(b, stream));
+        TRY(drain_waiting(b, stream, false));
     // a complete group was held back for mfsr_burst_finish_host and frames keep arriving (more than cfg.frames per
     // reference, or a resident frame after a host burst): it is fused the ordinary way before this frame is registered
     if (b->pend.n >= b->group) TRY(accumulate_pending(b, stream));
@@ -1831,7 +1842,7 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     const bool defer = can_defer_alignment(b, prepared || suppliedShifts);
     b->paths[defer ? MFSR_PATH_FRAMES_DEFERRED : MFSR_PATH_FRAMES_IMMEDIATE]++;
     if (!defer) {
-        TRY(align_deferred(b, stream));  // keep the alignment in frame order on the stream
+        TRY(align_deferred(b, b->pend, stream));  // keep the alignment in frame order on the stream
         TRY(align_frame(b, raw, isReference, slot, prepared, suppliedShifts, &flow, &mask, stream));
         b->flowCur = flow;
         b->maskCur = mask;
@@ -1870,7 +1881,7 @@ static int add_frame_impl(mfsr_burst* b, const uint16_t* raw, int isReference, m
     }
     // burst hold (mfsr_burst_hold_fuse): the group is aligned now, as always, and its fuse waits for the burst launch
     if (can_hold_group(b, hostBurst)) {
-        TRY(align_deferred(b, stream));
+        TRY(align_deferred(b, b->pend, stream));
         b->hold[b->nHold++] = b->pend;
         b->pend.n = 0;
         return MFSR_OK;
@@ -1913,7 +1924,7 @@ extern "C" int mfsr_burst_align_frame(mfsr_burst* b, const uint16_t* raw, int is
     const Layout& L = b->L;
     MFSR_REQUIRE((long long)flowPitch >= 8LL * L.tw && (flowPitch & 7) == 0 && ((uintptr_t)flowOut & 7) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0 && ((uintptr_t)maskOut & 15) == 0);
-    TRY(fuse_hold(b, stream));  // (the call takes a ring slot)
+    TRY(drain_waiting(b, stream, false));  // (the call takes a ring slot)
     const int slot = b->frameCounter++ % b->ring;
     const Img *flow = nullptr, *mask = nullptr;
     TRY(align_frame(b, raw, isReference, slot, nullptr, nullptr, &flow, &mask, stream));
@@ -1940,33 +1951,21 @@ extern "C" int mfsr_burst_align_frames(mfsr_burst* b, int nFrames, const uint16_
     MFSR_REQUIRE((long long)maskPitch >= 16LL * L.hw && (maskPitch & 15) == 0);
     for (int k = 0; k < nFrames; k++)
         MFSR_REQUIRE(raws[k] && flowOut[k] && maskOut[k] && ((uintptr_t)flowOut[k] & 7) == 0 && ((uintptr_t)maskOut[k] & 15) == 0);
-    TRY(fuse_hold(b, stream));  // (the call takes ring slots)
+    TRY(drain_waiting(b, stream, false));  // (the call takes ring slots)
     const bool batch = can_defer_alignment(b, false);
     const int per = batch ? b->group : 1;
     for (int k0 = 0; k0 < nFrames; k0 += per) {
         const int n = nFrames - k0 < per ? nFrames - k0 : per;
+        FuseGroup p = {};  // (these frames are not waiting for a fuse: the group lives for this batch only)
+        p.n = n;
         for (int j = 0; j < n; j++) {
-            const int isRef = isReference ? isReference[k0 + j] : 0;
-            const int slot = b->frameCounter++ % b->ring;
-            b->pend.slot[j] = slot;
-            b->pend.raw[j] = raws[k0 + j];
-            b->pend.isRef[j] = isRef;
-            b->pend.deferred[j] = batch;
-            b->pend.flow[j] = nullptr;
-            b->pend.mask[j] = nullptr;
-            if (!batch) {
-                const int rc = align_frame(b, raws[k0 + j], isRef, slot, nullptr, nullptr, &b->pend.flow[j], &b->pend.mask[j], stream);
-                if (rc) {
-                    b->pend.n = 0;
-                    return rc;
-                }
-            }
+            p.slot[j] = b->frameCounter++ % b->ring;
+            p.raw[j] = raws[k0 + j];
+            p.isRef[j] = isReference ? isReference[k0 + j] : 0;
+            p.deferred[j] = batch;
+            if (!batch) TRY(align_frame(b, p.raw[j], p.isRef[j], p.slot[j], nullptr, nullptr, &p.flow[j], &p.mask[j], stream));
         }
-        b->pend.n = n;
-        const int rc = align_deferred(b, stream);
-        const mfsr_burst::Pending p = b->pend;
-        b->pend.n = 0;  // these frames are not waiting for a fuse
-        if (rc) return rc;
+        TRY(align_deferred(b, p, stream));
         for (int j = 0; j < n; j++) {
             b->flowCur = p.flow[j];
             b->maskCur = p.mask[j];
@@ -1989,8 +1988,7 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
     TRY(wait_ref_products(b, stream));
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
-    const mfsr_float3 white = {c.white[0], c.white[1], c.white[2]};
-    const mfsr_float3 black = {c.black[0], c.black[1], c.black[2]};
+    const mfsr_float3 white = cfg_white(c), black = cfg_black(c);
     mfsr_tex2d sh[MFSR_MAX_FUSE_GROUP];
     for (int n = 0; n < nFrames; n++) {
         sh[n].ptr = flows[n];
@@ -1998,22 +1996,11 @@ extern "C" int mfsr_burst_fuse_rows(mfsr_burst* b, int nFrames, const uint16_t* 
         sh[n].width = L.tw;
         sh[n].height = L.th;
     }
-    const bool timed = b->timing && b->nEvents < kMaxTimedLaunches;
-    if (timed) {
-        const int i = b->nEvents;
-        if (!b->evStart[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStart[i]));
-        if (!b->evStop[i]) MFSR_HIP_TRY(hipEventCreate(&b->evStop[i]));
-        MFSR_HIP_TRY(hipEventRecord(b->evStart[i], mfsr_s(stream)));
-    }
+    bool timed;
+    TRY(timed_begin(b, stream, &timed));
     TRY(mfsr_cfa::accumulateSuperResFullRows(b->cfa, nFrames, raws, imgOut, totalWeights, masks, as_tex(L.kparam4), sh, white, black, L.W, L.H,
                                         c.scale, 12 * L.hrW, maskPitch, accumulatorsUndefined, rowBegin, rowEnd, stream));
-    if (timed) {
-        MFSR_HIP_TRY(hipEventRecord(b->evStop[b->nEvents], mfsr_s(stream)));
-        b->evLaunches[b->nEvents] = 1;
-        b->nEvents++;
-        b->nFramesTimed += nFrames;
-    }
-    return MFSR_OK;
+    return timed_end(b, timed, 1, nFrames, stream);
 }
 
 // Stripe plan of rank `rank` of `worldSize`: its HR rows and the rows of every per-frame product its fuse reads.
@@ -2182,7 +2169,7 @@ static void stencil_reach(const mfsr_burst* b, int r0, int rows, int* above, int
 extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
     if (!sharpen) {
         b->sharpenOn = false;
         return MFSR_OK;
@@ -2200,7 +2187,7 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
 extern "C" int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
     if (!denoise) {
         b->denoiseOn = false;
         return MFSR_OK;
@@ -2239,7 +2226,7 @@ extern "C" int mfsr_burst_debug_sharpened(const mfsr_burst* b, int* finishes)
 extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
     if (!render) {
         b->renderOn = false;
         return MFSR_OK;
@@ -2360,7 +2347,7 @@ extern "C" int mfsr_burst_auto_render(mfsr_burst* b, const mfsr_float3* imgOut, 
 extern "C" int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* lt, const float* gridDev)
 {
     MFSR_REQUIRE(b != nullptr);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
     if (!lt) {
         b->localToneOn = false;
         b->localToneGrid = nullptr;
@@ -2426,7 +2413,7 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     const Layout& L = b->L;
     // The finish inside the burst launch: only the plain whole-frame uint16_t image, and only where the hold's launch (two or
     // more groups on these accumulators) is the burst's last fuse -- nothing waits behind it (with 9 frames the ninth is fused
-    // after the burst launch, which then must not finish).  fuse_hold decides the rest (the entry's own refusals).
+    // after the burst launch, which then must not finish).  drain_waiting decides the rest (the entry's own refusals).
     b->finishTaken = false;
     b->finishOut16 = nullptr;
     if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->localToneOn && !b->win.on && out16 && !outImg &&
@@ -2652,7 +2639,7 @@ extern "C" int mfsr_burst_add_frame_host(mfsr_burst* b, const uint16_t* hostRaw,
     if (waiting)
         TRY(accumulate_pending(b, stream));
     else if (waitingHeld)
-        TRY(fuse_held(b, stream));  // only the held group: the frames waiting after it keep their group
+        TRY(drain_waiting(b, stream));  // only the groups before the filling one: the frames waiting in it keep their group
     TRY(upload_into(b, us, b->L.rawRing[us], hostRaw, stream));
     return add_frame_impl(b, b->L.rawRing[us], isReference, imgOut, totalWeights, banded, stream);
 }
@@ -2706,7 +2693,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     MFSR_REQUIRE(b->haveRef);
     bool capturing = false;
     TRY(host_epoch(b, stream, &capturing));
-    TRY(fuse_hold(b, stream));  // (resident frames of a burst-hold context added before this call)
+    TRY(drain_waiting(b, stream, false));  // (resident frames of a burst-hold context added before this call: before `held`)
     const mfsr_config& c = b->cfg;
     const Layout& L = b->L;
     // the previous image may still be on its way to the host out of out16Dev
@@ -2743,26 +2730,21 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         if (capturing) TRY(join_captured(b, stream));
         return release_ref_slot(b, stream);
     }
-    mfsr_burst::Pending p = b->pend, p0;
-    p0.n = 0;
+    // the groups fused band by band, in frame order: the second-to-last group where one was held, then the last
+    FuseGroup gs[2];
+    gs[0].n = gs[1].n = 0;
     int freshNow = 0;
     if (heldGroup) {
-        TRY(align_deferred(b, stream));
-        p = b->pend;
+        TRY(align_deferred(b, b->pend, stream));
+        gs[1] = b->pend;
         b->pend.n = 0;
         if (b->heldHas) {
-            p0 = b->held;  // the second-to-last group: fused first on every band (frame order)
+            gs[0] = b->held;
             b->heldHas = false;
             b->held.n = 0;
         }
         TRY(join_fuse(b, stream));  // the earlier groups' launches ran on the burst's own stream
-        freshNow = b->fresh.has && b->fresh.imgOut == imgOut && b->fresh.totalWeights == totalWeights;
-        if (b->fresh.has && !freshNow) {
-            const size_t bytes = acc_bytes(b);
-            MFSR_HIP_TRY(hipMemsetAsync(b->fresh.imgOut, 0, bytes, mfsr_s(stream)));
-            MFSR_HIP_TRY(hipMemsetAsync(b->fresh.totalWeights, 0, bytes, mfsr_s(stream)));
-        }
-        b->fresh.has = false;
+        TRY(take_fresh(b, imgOut, totalWeights, stream, &freshNow));
     }
     // bands of output rows (window rows when a window is set: y0 is a multiple of 16, so are the bands' HR rows)
     const int tileRows = (oH + 15) / 16;
@@ -2793,22 +2775,11 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         int r1 = (int)((long long)tileRows * (i + 1) / nBands) * 16;
         if (r1 > oH || i == nBands - 1) r1 = oH;
         if (r1 <= r0) continue;
-        if (heldGroup) {
-            const mfsr_burst::Pending* gs[2] = {&p0, &p};
-            int fresh = freshNow;
-            for (int gi = 0; gi < 2; gi++) {
-                const mfsr_burst::Pending& q = *gs[gi];
-                if (q.n == 0) continue;
-                const mfsr_float4* masks[MFSR_MAX_FUSE_GROUP];
-                mfsr_tex2d flows[MFSR_MAX_FUSE_GROUP];
-                for (int k = 0; k < q.n; k++) {
-                    masks[k] = (const mfsr_float4*)q.mask[k]->ptr;
-                    flows[k] = as_tex(*q.flow[k]);
-                }
-                TRY(fuse_group(b, q.n, q.raw, const_cast<mfsr_float3*>(imgOut), const_cast<mfsr_float3*>(totalWeights), masks, flows,
-                               q.mask[0]->pitch, fresh, r0, r1, stream));
-                fresh = 0;
-            }
+        int fresh = freshNow;
+        for (int gi = 0; gi < 2; gi++) {
+            if (gs[gi].n == 0) continue;
+            TRY(fuse_group(b, gs[gi], fresh, r0, r1, stream));
+            fresh = 0;
         }
         if (stencil_on(b)) {
             if (lagR0 >= 0) TRY(finish_band(lagI, lagR0, lagR1));
@@ -2820,16 +2791,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
         TRY(finish_band(i, r0, r1));
     }
     if (lagR0 >= 0) TRY(finish_band(lagI, lagR0, lagR1));
-    if (heldGroup && b->copyStream) {
-        // upload slots whose raw frame these launches were the last to read
-        for (int gi = 0; gi < 2; gi++) {
-            const mfsr_burst::Pending& q = gi ? p : p0;
-            for (int j = 0; j < q.n; j++) {
-                const int us = upload_slot_of(b, q.raw[j]);
-                if (us >= 0) TRY(record_free(b, us, stream));
-            }
-        }
-    }
+    for (int gi = 0; gi < 2; gi++) TRY(release_group_slots(b, gs[gi], stream));
     MFSR_HIP_TRY(hipEventRecord(b->evDown, b->downStream));
     b->downRecorded = true;
     b->nUnp = 0;  // (packed frames that were announced and not consumed are never unpacked)
@@ -2840,7 +2802,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
 extern "C" int mfsr_burst_set_host_row_bytes(mfsr_burst* b, int rowBytes)
 {
     MFSR_REQUIRE(b != nullptr && b->cfg.uploadRing > 0);
-    MFSR_REQUIRE(b->pend.n == 0 && !b->heldHas && b->nHold == 0 && b->nUnp == 0);  // between bursts only
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
     const bool isPacked = b->cfg.rawPacking != MFSR_PACK_NONE;
     const int dense = isPacked ? mfsr_packed_row_bytes(b->cfg.rawPacking, b->L.W) : 2 * b->L.W;
     MFSR_REQUIRE(rowBytes == 0 || rowBytes >= dense);
@@ -3169,7 +3131,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     TemporalScratch s;
     MFSR_REQUIRE(temporal_scratch(&c, nFrames, &s));
     MFSR_REQUIRE(((uintptr_t)scratchDev & 255) == 0 && scratchBytes >= s.total);
-    if (b->pend.n > 0 || b->heldHas || b->nHold > 0 || b->nUnp != 0) {  // between bursts only
+    if (!burst_idle(b)) {  // between bursts only
         fprintf(stderr, "mfsr: mfsr_burst_calibrate_noise_temporal with frames pending (flush or finish the burst first)\n");
         return MFSR_E_INVALID;
     }
@@ -3261,7 +3223,7 @@ extern "C" int mfsr_burst_prealign_result(mfsr_burst* b, mfsr_prealign* hostOut,
 {
     MFSR_REQUIRE(b && hostOut);
     MFSR_REQUIRE(b->cfg.preAlign && b->preCur);
-    TRY(align_deferred(b, stream));  // the last frame may still be waiting for its group: its estimate does not exist yet
+    TRY(align_deferred(b, b->pend, stream));  // the last frame may still be waiting for its group: its estimate does not exist yet
     MFSR_HIP_TRY(hipMemcpyAsync(hostOut, b->preCur, sizeof(*hostOut), hipMemcpyDeviceToHost, mfsr_s(stream)));
     MFSR_HIP_TRY(hipStreamSynchronize(mfsr_s(stream)));
     return MFSR_OK;

@@ -124,6 +124,65 @@ def test_process_wide_switch(hip, frames, plain):
     assert off[4] == (0, 0)
 
 
+def _mixed_burst(hip, dev_frames, host_frames, upload_ring):
+    """20 frames on one handle with the hold on and cfg.uploadRing set: frames 0-7 resident, a flush, frames 8-11 resident, frames
+    12-19 from the host.  Frames 0-7 are then in the accumulators, frames 8-11 wait in the burst hold, frames 12-15 become the
+    host burst's held group and frames 16-19 the filling group.  -> (imgOut, totalWeights, downloaded u16 image, fuse_stats)"""
+    cfg = default_config(W, H, 20, 2, False)
+    cfg.uploadRing = upload_ring
+    pipe = BurstPipeline(cfg, hip.dev)
+    try:
+        L, h, st = pipe.L, pipe._h, pipe._stream()
+        acc = (pipe._img_out.data_ptr(), pipe._total_weights.data_ptr())
+        out16_host = torch.empty_like(pipe.out16, device="cpu").pin_memory()
+        pipe.hold_fuse(True)
+        pipe.begin_burst()
+        L.burst_set_reference_host(h, host_frames[0].data_ptr(), st)
+        for k in range(8):
+            pipe.add_frame(dev_frames[k], k == 0)
+        pipe.flush()
+        for k in range(8, 12):
+            pipe.add_frame(dev_frames[k])
+        for k in range(12, 20):
+            L.burst_add_frame_host(h, host_frames[k].data_ptr(), 0, *acc, st)
+        L.burst_finish_host(h, *acc, pipe.out16.data_ptr(), out16_host.data_ptr(), st)
+        pipe.host_sync()
+        torch.cuda.synchronize()
+        return (pipe._img_out.cpu().numpy(), pipe._total_weights.cpu().numpy(), out16_host.numpy().copy(), pipe.fuse_stats())
+    finally:
+        pipe.close()
+
+
+@pytest.fixture(scope="module")
+def frames20(hip):
+    fr, _, _ = make_burst(W, H, 20, scale=2, mono=False, seed=778, max_shift=3.0)
+    return [f.to(hip.dev) for f in fr], [f.cpu().pin_memory() for f in fr]
+
+
+@pytest.mark.parametrize("upload_ring", [4, 8])
+def test_groups_fuse_in_arrival_order_on_a_mixed_handle(hip, frames20, upload_ring):
+    """Resident and host frames on one handle with the hold on: a group of the burst hold (frames 8-11) and the host burst's held
+    group (12-15) wait at the same time.  The hold's group arrived first, so it is fused first: the accumulators and the
+    downloaded image are, bit for bit, those of the same calls under mfsr_set_burst_fuse(0), where every resident group is
+    fused the moment it is complete -- arrival order by construction.  (The driver used to fuse the held group before a single
+    hold group there: (x + held) + g where arrival order is (x + g) + held.)  The flush sends frames 0-7 off as one burst
+    launch of two groups; the third held group leaves alone.
+    uploadRing = 4: frame 16 needs the upload slot of frame 12, so both waiting groups leave there, inside
+    mfsr_burst_add_frame_host (the old driver kept the order on that path).  uploadRing = 8: both are still waiting when
+    mfsr_burst_finish_host is called, which sends the hold's group off and fuses the held and the filling group band by band
+    (where the old driver did not)."""
+    dev, host = frames20
+    on = _mixed_burst(hip, dev, host, upload_ring)
+    hip.L.set_burst_fuse(0)
+    try:
+        off = _mixed_burst(hip, dev, host, upload_ring)
+    finally:
+        hip.L.set_burst_fuse(1)
+    assert off[3] == (0, 0)
+    assert on[3] == (1, 2)
+    _same(on, off)
+
+
 def _async(cfg):
     cfg.asyncFuse = 1
 
