@@ -465,8 +465,8 @@ int mfsr_lucasKanadeIterationWarped(const mfsr_float2* shiftsIn, mfsr_float2* sh
                                     float* diffOut, int pitchSD, int width, int height, int halfWindowSize, float minDet,
                                     float outScale, mfsr_stream_t stream);
 /* ---- frame batches: the per-frame stages of the alignment for 1 .. 4 moved frames against one reference in ONE launch each
- * (gridDim.z = frame; the kernels are the single-frame entry points' own, so a frame's result does not depend on the batch it
- * is in).  mfsr_burst_add_frame aligns the frames of a fuse group this way. */
+ * (gridDim.z = frame; the single-frame entry points launch the same kernels with a table of one frame, so a frame's result
+ * does not depend on the batch it is in).  mfsr_burst_add_frame aligns the frames of a fuse group this way. */
 typedef struct {
     const uint16_t* dataIn;
     mfsr_float3* halfOut;

@@ -69,12 +69,9 @@ static inline mfsr_render mfsr_plain_render()
     return r;
 }
 
-// Frame batches: the per-frame pointer arguments of a kernel for up to MFSR_BATCH_MAX frames, appended to its argument list; a
-// launch with gridDim.z > 1 takes frame blockIdx.z's pointers from the table (a scalar load), a plain launch ignores it.
+// Frame batches: a batched kernel takes a table of up to MFSR_BATCH_MAX entries of its own typed per-frame pointers by value and
+// reads entry blockIdx.z (a scalar load); a single-frame entry point launches it with a table of one.
 #define MFSR_BATCH_MAX 4
-struct MfsrBatch {
-    const void* p[MFSR_BATCH_MAX][6];
-};
 
 // internal C++ functions shared between the library's translation units: not part of its exported symbols
 #define MFSR_INTERNAL __attribute__((visibility("hidden")))
@@ -185,6 +182,8 @@ MFSR_INTERNAL int robustnessMaskGroup(int cfa, int nFrames, const mfsr_robustnes
 int mfsr_reference_fused();  // the switch of mfsr_set_reference_fused, kernel_field.hip (process-wide state)
 int mfsr_robustness_group();  // mfsr_set_robustness_group and the fast robustness kernel both on, robustness.hip (process-wide state)
 int mfsr_robustness_group_fits(int h, int flowRowBytes, int meansRowBytes, int maskRowBytes);  // images below 2 GiB (k_robustnessGroup's offsets)
+// what mfsr_lucasKanadeSweepBatch takes: MFSR_OK, or the status it returns (lk_fused.hip)
+MFSR_INTERNAL int mfsr_lk_sweep_accepts(int nFrames, int width, int height, int halfWindowSize, int pitchShift, int pitchImg, int pitchSD);
 // x / d for a divisor that is the same for a whole launch (an image dimension): q = x r, q' = fma(fma(-d, q, x), r, q) with
 // r = RN(1 / d) -- two multiply-adds after the product instead of the ~10 instructions of the IEEE division expansion.  For a
 // given d the sequence either is the correctly rounded quotient for EVERY x or it is not (scaling x by a power of two

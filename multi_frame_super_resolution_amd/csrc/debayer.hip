@@ -103,18 +103,25 @@ struct PrepTaps {
 // samples are the samples at the clamped coordinates, which is what that sum reads.  The pyramid outputs are not affected.
 #define PREP_MW (PREP_TX + 2)
 #define PREP_MH (PREP_TY + 2)
+// the frames of a launch: frame blockIdx.z reads its own entry
+struct PrepFrame {
+    const uint16_t* dataIn;
+    pix3* halfOut;
+    float* pyr0;
+    float* pyr1;  // nullptr (for all frames): no second pyramid level
+};
+struct PrepFrames {
+    PrepFrame f[MFSR_BATCH_MAX];
+};
 template <bool MEANS>
 __global__ void __launch_bounds__(256)
-    k_prepareFrameFused(const uint16_t* __restrict__ dataIn, pix3* __restrict__ halfOut, int halfPitch, float maxVal,
-                        int dimX, int dimY, float* __restrict__ pyr0, int pyr0Pitch, float* __restrict__ pyr1,
-                        int pyr1Pitch, PrepTaps taps, int cfa, MfsrBatch bt)
+    k_prepareFrameFused(PrepFrames frames, int halfPitch, float maxVal, int dimX, int dimY, int pyr0Pitch, int pyr1Pitch, PrepTaps taps,
+                        int cfa)
 {
-    if (gridDim.z > 1) {
-        dataIn = (const uint16_t*)bt.p[blockIdx.z][0];
-        halfOut = (pix3*)bt.p[blockIdx.z][1];
-        pyr0 = (float*)bt.p[blockIdx.z][2];
-        pyr1 = (float*)bt.p[blockIdx.z][3];
-    }
+    const uint16_t* __restrict__ dataIn = frames.f[blockIdx.z].dataIn;
+    pix3* __restrict__ halfOut = frames.f[blockIdx.z].halfOut;
+    float* __restrict__ pyr0 = frames.f[blockIdx.z].pyr0;
+    float* __restrict__ pyr1 = frames.f[blockIdx.z].pyr1;
     extern __shared__ __attribute__((aligned(16))) float s_prep[];
     const int c0 = taps.n / 2;
     const int GW = PREP_TX + 2 * c0, GH = PREP_TY + 2 * c0;
@@ -227,15 +234,12 @@ int mfsr_cfa::prepareFrames(int cfa, int n, const mfsr_prepare_frame* f, int hal
     MFSR_REQUIRE(ntaps > 0 && (ntaps & 1) == 1);
     if (ntaps / 2 > PREP_MAXC0) return MFSR_E_UNSUPPORTED;
     if (means && ntaps < 3) return MFSR_E_UNSUPPORTED;  // (no halo to take the patch from)
-    MfsrBatch bt;
-    memset(&bt, 0, sizeof(bt));
+    PrepFrames fr;
+    memset(&fr, 0, sizeof(fr));
     for (int i = 0; i < n; i++) {
         MFSR_REQUIRE(f[i].dataIn && f[i].halfOut && f[i].pyr0 && ((uintptr_t)f[i].dataIn & 3) == 0);
         MFSR_REQUIRE((f[i].pyr1 != nullptr) == (f[0].pyr1 != nullptr));
-        bt.p[i][0] = f[i].dataIn;
-        bt.p[i][1] = f[i].halfOut;
-        bt.p[i][2] = f[i].pyr0;
-        bt.p[i][3] = f[i].pyr1;
+        fr.f[i] = PrepFrame{f[i].dataIn, (pix3*)f[i].halfOut, f[i].pyr0, f[i].pyr1};
     }
     if (f[0].pyr1) MFSR_REQUIRE((long long)pyr1Pitch >= 4LL * (dimX / 2) && (pyr1Pitch & 3) == 0 && dimX >= 2 && dimY >= 2);
     PrepTaps tp;
@@ -247,13 +251,12 @@ int mfsr_cfa::prepareFrames(int cfa, int n, const mfsr_prepare_frame* f, int hal
     if (means) {
         const size_t planes = 3 * PREP_MW * PREP_MH, rows = (size_t)PREP_TX * GH;  // (sM and sH share one region, sO lies in sG)
         const size_t ldsMeans = sizeof(float) * ((size_t)GW * GH + (planes > rows ? planes : rows));
-        hipLaunchKernelGGL(k_prepareFrameFused<true>, grid, block, ldsMeans, mfsr_s(stream), f[0].dataIn,
-                           (pix3*)f[0].halfOut, halfPitch, maxVal, dimX, dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp,
-                           cfa, bt);
+        hipLaunchKernelGGL(k_prepareFrameFused<true>, grid, block, ldsMeans, mfsr_s(stream), fr, halfPitch, maxVal, dimX, dimY, pyr0Pitch,
+                           pyr1Pitch, tp, cfa);
         return mfsr_launch_status("prepareFrameMeans");
     }
-    hipLaunchKernelGGL(k_prepareFrameFused<false>, grid, block, lds, mfsr_s(stream), f[0].dataIn, (pix3*)f[0].halfOut, halfPitch, maxVal, dimX,
-                       dimY, f[0].pyr0, pyr0Pitch, f[0].pyr1, pyr1Pitch, tp, cfa, bt);
+    hipLaunchKernelGGL(k_prepareFrameFused<false>, grid, block, lds, mfsr_s(stream), fr, halfPitch, maxVal, dimX, dimY, pyr0Pitch, pyr1Pitch,
+                       tp, cfa);
     return mfsr_launch_status("prepareFrameFused");
 }
 

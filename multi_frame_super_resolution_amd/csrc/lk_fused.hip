@@ -28,18 +28,22 @@
 //
 // Flow is double-buffered (shiftsIn -> shiftsOut): the halo of a tile reads
 // flow values owned by other workgroups, so an in-place update would race.
+//
+// Kernels of this file: k_lkIterationFused (tiles: 48 or 32 wide where it warps its own tile + halo, 32 wide where the warped
+// image is handed in), k_flowFieldWarped (flow field + first warp, a table of frames) and k_lkSweep (the same iteration as a
+// register / DPP column sweep for up to four frames: the burst's kernel).  One warp of a pixel (lk_warp_issue + lk_warp_finish)
+// serves all three.  The solve and flow update is written out in both Lucas-Kanade kernels: as a shared function it moved
+// k_lkSweep's instructions and cost it a register (profiles/isa_alignment_forks.txt).
 #include <cstdlib>
 #include <cstring>
 #include "common.hpp"
 #include "lk_math.hpp"
 
-// Tile: LK_TY rows x TX columns (template), one thread per pixel.  TX = 48 is the default: with the
+// Tile: LK_TY rows x TX columns (template), one thread per pixel.  TX = 48 where the kernel warps its own tile: with the
 // 7x7 window the warped region (58 x 26 = 1508 samples) is 1.96 rounds of the 768 threads, where a
 // 32-wide tile needs 3 rounds of 512 for 2.13 (the warp is half of the kernel's instructions); TX = 32
-// serves images narrower than 48 + 2h + 4.
-#ifndef LK_TY
-#define LK_TY 16
-#endif
+// serves images narrower than 48 + 2h + 4 and the form that is handed the warped image (PRE).
+constexpr int LK_TY = 16;
 
 // reflection about the image edges for -n <= i < 2n (the tile halo never reaches further):
 // ... 1 0 | 0 1 ... n-1 | n-1 n-2 ...   (no integer division)
@@ -68,17 +72,27 @@ __device__ __forceinline__ T* lk_at(T* base, int pitch, int y, int x)
     return (T*)((char*)base + (uint32_t)((uint32_t)y * (uint32_t)pitch + (uint32_t)x * (uint32_t)sizeof(T)));
 }
 
-// warped moved image and reference at pixel (gx, gy) (inside the image) under flow f: opticalFlow.cu:28-44.
+// ---- the warp of the moved image at pixel (gx, gy) (inside the image) under flow f: opticalFlow.cu:28-44 ---------------------
+// In two phases, so that k_lkSweep can consume the gather a pixel issues after its flow update one row later (the wave works
+// on the next row meanwhile); lk_warp_sample below is the two in a row: one address arithmetic, one blend.
 // Interior samples (0 <= u,v < 1, both texel pairs inside the image): mirror_coord is the identity and no index is
-// clamped, so the fetch is four plain loads with the very same arithmetic as tex1<ADDR_MIRROR>; the few other samples
-// are redone with the full addressing (wave-uniform branch: only waves that touch the image border pay for it).
-__device__ __forceinline__ void lk_warp_sample(const float* __restrict__ refImg, const float* __restrict__ movedImg, int pitchImg,
-                                               int width, int height, int gx, int gy, float2 f, float& wv, float& rv,
-                                               const MfsrExactDiv* dW = nullptr, const MfsrExactDiv* dH = nullptr)
+// clamped, so the fetch is four plain loads with the very same arithmetic as tex1<ADDR_MIRROR>.
+// What a pending warp keeps across a row step: the four texels on their way, the blend weights and the reference pixel -- seven
+// registers (LkGather).  A sample the plain fetch does not cover (outside the unit square or on the last texel row / column: waves at the
+// image border only) is fetched with the full MIRROR addressing right here, under a wave-uniform branch, and parked as four
+// equal texels with zero weights: lerp4 of those returns it bit for bit ((t + 0) + 0 + 0; an infinite texel, which no tracking
+// image holds, would become NaN), so the finish needs neither the coordinates nor an "interior" flag.
+struct LkGather {
+    float t00, t10, t01, t11, a, b;
+    float rv;
+};
+// dW, dH: / width, / height as mfsr_div takes them -- mfsr_exact_div's sequence, or lk_plain_div: the division itself
+__device__ __forceinline__ MfsrExactDiv lk_plain_div(int n) { return MfsrExactDiv{(float)n, 0.0f, 0}; }
+__device__ __forceinline__ void lk_warp_issue(const float* __restrict__ movedImg, int pitchImg, int width, int height, int gx, int gy,
+                                              float2 f, bool wanted, LkGather& g, const MfsrExactDiv& dW, const MfsrExactDiv& dH)
 {
-    rv = *lk_at(refImg, pitchImg, gy, gx);
-    const float u = dW ? mfsr_div((float)gx + 0.5f + f.x, *dW) : ((float)gx + 0.5f + f.x) / (float)width;   // opticalFlow.cu:38-39
-    const float v = dH ? mfsr_div((float)gy + 0.5f + f.y, *dH) : ((float)gy + 0.5f + f.y) / (float)height;
+    const float u = mfsr_div((float)gx + 0.5f + f.x, dW);   // opticalFlow.cu:38-39: / (float)width
+    const float v = mfsr_div((float)gy + 0.5f + f.y, dH);   //                        / (float)height
     const float xB = u * (float)width - 0.5f, yB = v * (float)height - 0.5f;
     const float fx = floorf(xB), fy = floorf(yB);
     const int ix = f2i(fx), iy = f2i(fy);
@@ -87,16 +101,32 @@ __device__ __forceinline__ void lk_warp_sample(const float* __restrict__ refImg,
     const int ixc = clampi(ix, 0, width - 2), iyc = clampi(iy, 0, height - 2);
     const float* r0 = lk_at(movedImg, pitchImg, iyc, ixc);
     const float* r1 = lk_at(movedImg, pitchImg, iyc + 1, ixc);
-    wv = lerp4(r0[0], r0[1], r1[0], r1[1], xB - fx, yB - fy);
-    if (__ballot(!interior) != 0) {
+    g.t00 = r0[0], g.t10 = r0[1], g.t01 = r1[0], g.t11 = r1[1];
+    g.a = xB - fx, g.b = yB - fy;
+    if (__ballot(!interior && wanted) != 0) {   // (lanes whose result is not stored do not send the wave here)
         mfsr_tex2d texMoved;
         texMoved.ptr = movedImg;
         texMoved.pitch = pitchImg;
         texMoved.width = width;
         texMoved.height = height;
         const float full = tex1<ADDR_MIRROR>(texMoved, u, v);
-        wv = interior ? wv : full;
+        if (!interior) {
+            g.t00 = g.t10 = g.t01 = g.t11 = full;
+            g.a = g.b = 0.0f;
+        }
     }
+}
+__device__ __forceinline__ float lk_warp_finish(const LkGather& g) { return lerp4(g.t00, g.t10, g.t01, g.t11, g.a, g.b); }
+
+// warped moved image (wv) and reference (rv) at the pixel
+__device__ __forceinline__ void lk_warp_sample(const float* __restrict__ refImg, const float* __restrict__ movedImg, int pitchImg,
+                                               int width, int height, int gx, int gy, float2 f, float& wv, float& rv,
+                                               const MfsrExactDiv& dW, const MfsrExactDiv& dH)
+{
+    rv = *lk_at(refImg, pitchImg, gy, gx);
+    LkGather g;
+    lk_warp_issue(movedImg, pitchImg, width, height, gx, gy, f, true, g, dW, dH);
+    wv = lk_warp_finish(g);
 }
 
 // HT > 0: half window size known at compile time (tile geometry becomes constant, so the
@@ -145,7 +175,7 @@ __global__ void __launch_bounds__(LK_TX * LK_TY)
         }
         const float2 f = row_ptr(shiftsIn, pitchShift, gy)[gx];
         float wv, rv;
-        lk_warp_sample(refImg, movedImg, pitchImg, width, height, gx, gy, f, wv, rv);
+        lk_warp_sample(refImg, movedImg, pitchImg, width, height, gx, gy, f, wv, rv, lk_plain_div(width), lk_plain_div(height));
         if (active) {
             // the derivative stencil is linear: keep (warped + ref) for Ix, Iy and (warped - ref) = It
             s_ref[i] = wv + rv;
@@ -264,7 +294,7 @@ __global__ void __launch_bounds__(LK_TX * LK_TY)
         if (PRE && sumOut) {
             // the next iteration's input: this pixel warped under its new flow (outScale is 1 on every iteration but the last)
             float wv, rv;
-            lk_warp_sample(refImg, movedImg, pitchImg, width, height, pxX, pxY, shift, wv, rv);
+            lk_warp_sample(refImg, movedImg, pitchImg, width, height, pxX, pxY, shift, wv, rv, lk_plain_div(width), lk_plain_div(height));
             row_ptr(sumOut, pitchSD, pxY)[pxX] = wv + rv;
             row_ptr(diffOut, pitchSD, pxY)[pxX] = wv - rv;
         }
@@ -308,15 +338,10 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
     // TX is a template parameter of the kernel: 48 only for the half-window sizes that have a <h,48>
     // instantiation below (1..7); every other size runs the generic <0,32> kernel
     const bool hasWide = h >= 1 && h <= 7;
-    static const int forceTx = mfsr_env_int("MFSR_LK_TX", 0);
     // tile width: 48 when the kernel warps its tile + halo itself (fewest warps per pixel); 32 when the warped image is
     // handed in (PRE): the halo is then only loads, and the smaller workgroup (40 KB of LDS, four per CU instead of two)
-    // hides the two global round trips of a tile better -- 6.55 against 6.69 ms per 4K burst; 64 wide: no better.
-    // MFSR_LK_TX=32|48|64 overrides (A/B).
-    int TX = (hasWide && !PRE && width >= 48 + 2 * h + 4) ? 48 : 32;
-    if (forceTx == 32) TX = 32;
-    if (forceTx == 48 && hasWide && width >= 48 + 2 * h + 4) TX = 48;
-    if (PRE && forceTx == 64 && hasWide && width >= 64 + 2 * h + 4) TX = 64;
+    // hides the two global round trips of a tile better -- 6.55 against 6.69 ms per 4K burst; 64 wide measured no better.
+    const int TX = (hasWide && !PRE && width >= 48 + 2 * h + 4) ? 48 : 32;
     const int BW = TX + 2 * h + 4, BH = LK_TY + 2 * h + 4, AW = TX + 2 * h, AH = LK_TY + 2 * h;
     const int AWp = hasWide ? ((AW + 3) & ~3) : AW;  // as in the kernel: padded when h is a template parameter
     const size_t lds = sizeof(float) * ((size_t)2 * BW * BH + (size_t)5 * AWp * AH + (size_t)5 * TX * AH);
@@ -332,14 +357,16 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
                            (float2*)shiftsOut, pitchShift, refImg, movedImg, pitchImg, width, height, h, minDet,       \
                            outScale, sumIn, diffIn, sumOut, diffOut, pitchSD);                                         \
     } while (0)
+    /* (PRE never runs 48 wide: no such kernel is emitted) */
 #define LK_CASE(HT)                                                                                                    \
     case HT:                                                                                                           \
-        if (PRE && TX == 64)                                                                                           \
-            LK_LAUNCH(HT, 64);                                                                                         \
-        else if (TX == 48)                                                                                             \
-            LK_LAUNCH(HT, 48);                                                                                         \
-        else                                                                                                           \
-            LK_LAUNCH(HT, 32);                                                                                         \
+        if constexpr (!PRE) {                                                                                          \
+            if (TX == 48) {                                                                                            \
+                LK_LAUNCH(HT, 48);                                                                                     \
+                break;                                                                                                 \
+            }                                                                                                          \
+        }                                                                                                              \
+        LK_LAUNCH(HT, 32);                                                                                             \
         break;
     switch (h) {
         LK_CASE(1)
@@ -349,8 +376,7 @@ static int lk_iteration_impl(const mfsr_float2* shiftsIn, mfsr_float2* shiftsOut
         LK_CASE(5)
         LK_CASE(6)
         LK_CASE(7)
-        default:
-            if (TX != 32) return MFSR_E_UNSUPPORTED;  // unreachable: hasWide covers exactly the cases above
+        default:  // (TX == 32: hasWide covers exactly the cases above)
             LK_LAUNCH(0, 32);
             break;
     }
@@ -382,21 +408,29 @@ extern "C" int mfsr_lucasKanadeIterationWarped(const mfsr_float2* shiftsIn, mfsr
 // D1 (CreateFlowFieldFromTiles, opticalFlow.cu:48) + the warp of every pixel under that flow: the input of the first
 // mfsr_lucasKanadeIterationWarped.  Base shift / rotation by value (cosf / sinf on the device, as mfsr_CreateFlowFieldFromTiles)
 // or from a device mfsr_prealign (its cos / sin table, as mfsr_CreateFlowFieldFromTilesBase): the same flow bits either way.
+struct FlowFieldFrame {
+    float2* outImg;
+    const float2* tileShifts;
+    const mfsr_prealign* base;  // BASE_PTR only
+    const float* movedImg;
+    float* sumOut;
+    float* diffOut;
+};
+struct FlowFieldFrames {
+    FlowFieldFrame f[MFSR_BATCH_MAX];
+};
+// texShift: the tile grid's pitch and size; its pointer is the frame's tileShifts
 template <bool BASE_PTR>
 __global__ void __launch_bounds__(256)
-    k_flowFieldWarped(float2* __restrict__ outImg, mfsr_tex2d texShift, int imgWidth, int imgHeight, int imgPitch, float2 baseShift,
-                      float baseRotation, const mfsr_prealign* __restrict__ base, const float* __restrict__ refImg,
-                      const float* __restrict__ movedImg, int pitchImg, float* __restrict__ sumOut, float* __restrict__ diffOut,
-                      int pitchSD, MfsrBatch bt, MfsrExactDiv dW, MfsrExactDiv dH)
+    k_flowFieldWarped(FlowFieldFrames frames, mfsr_tex2d texShift, int imgWidth, int imgHeight, int imgPitch, float2 baseShift,
+                      float baseRotation, const float* __restrict__ refImg, int pitchImg, int pitchSD, MfsrExactDiv dW, MfsrExactDiv dH)
 {
-    if (gridDim.z > 1) {
-        outImg = (float2*)bt.p[blockIdx.z][0];
-        texShift.ptr = bt.p[blockIdx.z][1];
-        base = (const mfsr_prealign*)bt.p[blockIdx.z][2];
-        movedImg = (const float*)bt.p[blockIdx.z][3];
-        sumOut = (float*)bt.p[blockIdx.z][4];
-        diffOut = (float*)bt.p[blockIdx.z][5];
-    }
+    float2* __restrict__ outImg = frames.f[blockIdx.z].outImg;
+    texShift.ptr = frames.f[blockIdx.z].tileShifts;
+    const mfsr_prealign* __restrict__ base = frames.f[blockIdx.z].base;
+    const float* __restrict__ movedImg = frames.f[blockIdx.z].movedImg;
+    float* __restrict__ sumOut = frames.f[blockIdx.z].sumOut;
+    float* __restrict__ diffOut = frames.f[blockIdx.z].diffOut;
     const int pxX = blockIdx.x * blockDim.x + threadIdx.x;
     const int pxY = blockIdx.y * blockDim.y + threadIdx.y;
     if (pxX >= imgWidth || pxY >= imgHeight) return;
@@ -428,7 +462,7 @@ __global__ void __launch_bounds__(256)
     shift.y += shiftPatch.y;
     *lk_at(outImg, imgPitch, pxY, pxX) = shift;
     float wv, rv;
-    lk_warp_sample(refImg, movedImg, pitchImg, imgWidth, imgHeight, pxX, pxY, shift, wv, rv, &dW, &dH);
+    lk_warp_sample(refImg, movedImg, pitchImg, imgWidth, imgHeight, pxX, pxY, shift, wv, rv, dW, dH);
     *lk_at(sumOut, pitchSD, pxY, pxX) = wv + rv;
     *lk_at(diffOut, pitchSD, pxY, pxX) = wv - rv;
 }
@@ -450,28 +484,22 @@ static int flow_field_warped_impl(int n, const mfsr_flowfield_frame* f, int tile
     tex.width = tileW;
     tex.height = tileH;
     MFSR_REQUIRE(mfsr_tex_ok(tex, 8) && (tilePitch & 7) == 0);
-    MfsrBatch bt;
-    memset(&bt, 0, sizeof(bt));
+    FlowFieldFrames fr;
+    memset(&fr, 0, sizeof(fr));
     for (int i = 0; i < n; i++) {
         MFSR_REQUIRE(f[i].outImg && f[i].tileShifts && f[i].movedImg && f[i].sumOut && f[i].diffOut);
         MFSR_REQUIRE(((uintptr_t)f[i].outImg & 7) == 0 && ((uintptr_t)f[i].tileShifts & 7) == 0);
         MFSR_REQUIRE((f[i].base != nullptr) == (f[0].base != nullptr));
-        bt.p[i][0] = f[i].outImg;
-        bt.p[i][1] = f[i].tileShifts;
-        bt.p[i][2] = f[i].base;
-        bt.p[i][3] = f[i].movedImg;
-        bt.p[i][4] = f[i].sumOut;
-        bt.p[i][5] = f[i].diffOut;
+        fr.f[i] = FlowFieldFrame{(float2*)f[i].outImg, (const float2*)f[i].tileShifts, f[i].base, f[i].movedImg, f[i].sumOut, f[i].diffOut};
     }
     dim3 block(64, 4), grid(mfsr_cdiv(imgWidth, 64), mfsr_cdiv(imgHeight, 4), n);
     const MfsrExactDiv dW = mfsr_exact_div((float)imgWidth), dH = mfsr_exact_div((float)imgHeight);
     if (f[0].base)
-        hipLaunchKernelGGL(k_flowFieldWarped<true>, grid, block, 0, mfsr_s(stream), (float2*)f[0].outImg, tex, imgWidth, imgHeight, imgPitch,
-                           make_float2(0.0f, 0.0f), 0.0f, f[0].base, refImg, f[0].movedImg, pitchImg, f[0].sumOut, f[0].diffOut, pitchSD, bt, dW, dH);
+        hipLaunchKernelGGL(k_flowFieldWarped<true>, grid, block, 0, mfsr_s(stream), fr, tex, imgWidth, imgHeight, imgPitch,
+                           make_float2(0.0f, 0.0f), 0.0f, refImg, pitchImg, pitchSD, dW, dH);
     else
-        hipLaunchKernelGGL(k_flowFieldWarped<false>, grid, block, 0, mfsr_s(stream), (float2*)f[0].outImg, tex, imgWidth, imgHeight, imgPitch,
-                           make_float2(baseShift.x, baseShift.y), baseRotation, f[0].base, refImg, f[0].movedImg, pitchImg, f[0].sumOut,
-                           f[0].diffOut, pitchSD, bt, dW, dH);
+        hipLaunchKernelGGL(k_flowFieldWarped<false>, grid, block, 0, mfsr_s(stream), fr, tex, imgWidth, imgHeight, imgPitch,
+                           make_float2(baseShift.x, baseShift.y), baseRotation, refImg, pitchImg, pitchSD, dW, dH);
     return mfsr_launch_status("CreateFlowFieldWarped");
 }
 
@@ -494,7 +522,7 @@ extern "C" int mfsr_CreateFlowFieldWarpedBatch(int nFrames, const mfsr_flowfield
                                   pitchImg, pitchSD, stream);
 }
 
-// ---- the same iteration as a register / DPP column sweep, for up to MFSR_LK_MAX_BATCH frames per launch -----------------------
+// ---- the same iteration as a register / DPP column sweep, for up to MFSR_LK_SWEEP_MAX_BATCH frames per launch -----------------------
 // k_lkIterationFused spends most of its ~430 VALU instructions per pixel around the arithmetic: a 32 x 16 tile stages
 // (32+10) x (16+10) samples (2.1x), forms the products on (32+6) x (16+6) (1.6x), moves everything through LDS with
 // index arithmetic for every element and crosses three barriers.  Here ONE WAVEFRONT owns 64 image columns and sweeps
@@ -534,60 +562,12 @@ __device__ __forceinline__ float lk_wshl1(float v)  // lane l <- lane l+1 (lane 
     return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x130, 0xf, 0xf, true));
 }
 
-// the warp of lk_warp_sample in two phases, so that the gather a pixel issues after its flow update is consumed one row
-// later (the wave works on the next row meanwhile): same address arithmetic, same blend, same bits
+// (the warp of a pixel after its flow update: lk_warp_issue above, consumed one row later by lk_warp_finish)
 // Register diet of k_lkSweep (round 4; all bit-identical, profiles/r04_lk_regs_ab.txt; h = 3): 32-bit offsets (lk_at) 95 -> 85
 // VGPRs and -3.6 % instructions: 110.3 -> 107 us per 4-frame launch; the border fetch at issue time (no coordinates / flag in
-// the pending gather) and the difference image loaded two steps before its use instead of four (LK_DIFF_LATE): 79 VGPRs = six
-// waves per SIMD: 106 us.  LK_RV_REREAD=1 (the reference pixel re-read at the finish instead of held in a register: 76 VGPRs)
-// puts a load in front of the two stores of every row: 120 us -- off.
-#ifndef LK_RV_REREAD
-#define LK_RV_REREAD 0
-#endif
-#ifndef LK_DIFF_LATE
-#define LK_DIFF_LATE 1
-#endif
-// What a pending warp keeps across a row step: the four texels on their way, the blend weights and the reference pixel -- seven
-// registers (LkGather + rv).  A sample the plain fetch does not cover (outside the unit square or on the last texel row / column: waves at the
-// image border only) is fetched with the full MIRROR addressing right here, under a wave-uniform branch, and parked as four
-// equal texels with zero weights: lerp4 of those returns it bit for bit ((t + 0) + 0 + 0), so the finish needs neither the
-// coordinates nor an "interior" flag.
-struct LkGather {
-    float t00, t10, t01, t11, a, b;
-#if !LK_RV_REREAD
-    float rv;
-#endif
-};
-__device__ __forceinline__ void lk_warp_issue(const float* __restrict__ movedImg, int pitchImg, int width, int height, int gx, int gy,
-                                              float2 f, bool wanted, LkGather& g, const MfsrExactDiv& dW, const MfsrExactDiv& dH)
-{
-    const float u = mfsr_div((float)gx + 0.5f + f.x, dW);   // opticalFlow.cu:38-39: / (float)width
-    const float v = mfsr_div((float)gy + 0.5f + f.y, dH);   //                        / (float)height
-    const float xB = u * (float)width - 0.5f, yB = v * (float)height - 0.5f;
-    const float fx = floorf(xB), fy = floorf(yB);
-    const int ix = f2i(fx), iy = f2i(fy);
-    const bool interior = u >= 0.0f && u < 1.0f && v >= 0.0f && v < 1.0f && (uint32_t)ix <= (uint32_t)(width - 2) &&
-                          (uint32_t)iy <= (uint32_t)(height - 2);
-    const int ixc = clampi(ix, 0, width - 2), iyc = clampi(iy, 0, height - 2);
-    const float* r0 = lk_at(movedImg, pitchImg, iyc, ixc);
-    const float* r1 = lk_at(movedImg, pitchImg, iyc + 1, ixc);
-    g.t00 = r0[0], g.t10 = r0[1], g.t01 = r1[0], g.t11 = r1[1];
-    g.a = xB - fx, g.b = yB - fy;
-    if (__ballot(!interior && wanted) != 0) {   // (lanes whose result is not stored do not send the wave here)
-        mfsr_tex2d texMoved;
-        texMoved.ptr = movedImg;
-        texMoved.pitch = pitchImg;
-        texMoved.width = width;
-        texMoved.height = height;
-        const float full = tex1<ADDR_MIRROR>(texMoved, u, v);
-        if (!interior) {
-            g.t00 = g.t10 = g.t01 = g.t11 = full;
-            g.a = g.b = 0.0f;
-        }
-    }
-}
-__device__ __forceinline__ float lk_warp_finish(const LkGather& g) { return lerp4(g.t00, g.t10, g.t01, g.t11, g.a, g.b); }
-
+// the pending gather) and the difference image loaded two steps before its use instead of four: 79 VGPRs = six
+// waves per SIMD: 106 us.  Re-reading the reference pixel at the finish instead of holding it in a register (76 VGPRs) put a
+// load in front of the two stores of every row: 120 us -- not kept.
 template <int HT>
 __global__ void __launch_bounds__(64)
     k_lkSweep(LkSweepBatch batch, const float* __restrict__ refImg, int pitchShift, int pitchImg, int pitchSD, int width, int height,
@@ -635,21 +615,12 @@ __global__ void __launch_bounds__(64)
     float sA, sB, dA = 0, dB = 0;
     load_sum(0, sA);
     load_sum(min(1, T - 1), sB);
-#if !LK_DIFF_LATE
-    float d1 = 0, d2 = 0;
-    load_diff(0, dA);
-    load_diff(min(1, T - 1), dB);
-#endif
     LkGather pend;            // the previous output row's warp, issued and not yet consumed
     int pendY = -1;
     auto finish_pending = [&]() {
         if (pendY < 0) return;   // wave-uniform
         const float wv = lk_warp_finish(pend);
-#if LK_RV_REREAD
-        const float rv = *lk_at(refImg, pitchImg, pendY, colOutC);   // (A/B: a load in front of the row's stores -- slower)
-#else
         const float rv = pend.rv;
-#endif
         if (outLane) {
             *lk_at(F.sumOut, pitchSD, pendY, colOutC) = wv + rv;
             *lk_at(F.diffOut, pitchSD, pendY, colOutC) = wv - rv;
@@ -663,25 +634,16 @@ __global__ void __launch_bounds__(64)
             if (t >= T) break;
             // rotate the raw-row rings; fetch row t + 2
             s0 = s1, s1 = s2, s2 = s3, s3 = s4, s4 = sA;
-#if LK_DIFF_LATE
             d0 = dA, dA = dB;
             sA = sB;
             load_sum(min(t + 2, T - 1), sB);
             load_diff(t, dB);
-#else
-            d0 = d1, d1 = d2, d2 = dA, dA = dB;
-            sA = sB;
-            load_sum(min(t + 2, T - 1), sB);
-            load_diff(min(t + 2, T - 1), dB);
-#endif
             if (t < 4) continue;   // the derivative of row r - 2 needs rows r - 4 .. r
             // this row's own flow and reference pixel: on their way while the sums are formed (every lane loads: clamped column)
             const int y = ry0 + t - 2 * HALO;                  // the row whose window this step completes (if t >= 2 HALO)
             const int yc = min(max(y, 0), height - 1);
             float2 shift = *lk_at(F.flowIn, pitchShift, yc, colOutC);
-#if !LK_RV_REREAD
             const float rvOwn = *lk_at(refImg, pitchImg, yc, colOutC);
-#endif
             // products of image row r - 2 (opticalFlow.cu:116-131 on the sum image, as k_lkIterationFused step 2)
             const float xp1 = lk_wshl1(s2), xp2 = lk_wshl1(xp1), xm1 = lk_wshr1(s2), xm2 = lk_wshr1(xm1);
             float tx = xp2;
@@ -728,9 +690,7 @@ __global__ void __launch_bounds__(64)
             if (F.sumOut) {   // wave-uniform
                 finish_pending();   // the previous row's gather: issued one row ago
                 lk_warp_issue(F.moved, pitchImg, width, height, colOutC, y, shift, outLane, pend, dW, dH);
-#if !LK_RV_REREAD
                 pend.rv = rvOwn;
-#endif
                 pendY = y;
             }
             shift.x *= outScale;
@@ -741,12 +701,30 @@ __global__ void __launch_bounds__(64)
     if (F.sumOut) finish_pending();
 }
 
+// What the sweep takes: the one rule of mfsr_lucasKanadeSweepBatch, of mfsr_lucasKanadeSweepBand (the geometry: it knows no
+// pitches) and of the burst driver's choice of the frame-batched route.  MFSR_OK, MFSR_E_UNSUPPORTED (another kernel's case) or
+// MFSR_E_INVALID.
+static bool lk_sweep_geometry(int nFrames, int width, int height, int h)
+{
+    return nFrames >= 1 && nFrames <= MFSR_LK_SWEEP_MAX_BATCH && h >= 1 && h <= 7 && width >= 64 && height >= 2 * (h + 2);
+}
+int mfsr_lk_sweep_accepts(int nFrames, int width, int height, int halfWindowSize, int pitchShift, int pitchImg, int pitchSD)
+{
+    MFSR_REQUIRE(nFrames >= 1 && nFrames <= MFSR_LK_SWEEP_MAX_BATCH);
+    if (!lk_sweep_geometry(nFrames, width, height, halfWindowSize)) return MFSR_E_UNSUPPORTED;
+    MFSR_REQUIRE((long long)pitchShift >= 8LL * width && (pitchShift & 7) == 0);
+    MFSR_REQUIRE((long long)pitchImg >= 4LL * width && (pitchImg & 3) == 0 && (long long)pitchSD >= 4LL * width && (pitchSD & 3) == 0);
+    // (32-bit byte offsets inside every image, lk_at)
+    if ((long long)pitchShift * height >= (1LL << 32) || (long long)pitchImg * height >= (1LL << 32) || (long long)pitchSD * height >= (1LL << 32))
+        return MFSR_E_UNSUPPORTED;
+    return MFSR_OK;
+}
+
 // The band height of a sweep launch, in rows: the launcher's only source of it (include/mfsr.h: mfsr_lucasKanadeSweepBand).
 // 0 where mfsr_lucasKanadeSweepBatch refuses the geometry.  Host arithmetic only.
 extern "C" int mfsr_lucasKanadeSweepBand(int width, int height, int halfWindowSize, int nFrames)
 {
-    if (nFrames < 1 || nFrames > MFSR_LK_SWEEP_MAX_BATCH) return 0;
-    if (halfWindowSize < 1 || halfWindowSize > 7 || width < 64 || height < 2 * (halfWindowSize + 2)) return 0;
+    if (!lk_sweep_geometry(nFrames, width, height, halfWindowSize)) return 0;
     const int h = halfWindowSize, VW = 64 - 2 * (h + 2);
     const int strips = mfsr_cdiv(width, VW);
     // band height: enough wavefronts to fill 1024 SIMDs a few times over without paying too many halo rows
@@ -779,13 +757,9 @@ extern "C" int mfsr_lucasKanadeSweepBatch(int nFrames, const mfsr_lk_frame* fram
                                           int pitchSD, int width, int height, int halfWindowSize, float minDet, float outScale,
                                           mfsr_stream_t stream)
 {
-    MFSR_REQUIRE(frames && refImg && nFrames >= 1 && nFrames <= MFSR_LK_SWEEP_MAX_BATCH);
-    if (halfWindowSize < 1 || halfWindowSize > 7 || width < 64 || height < 2 * (halfWindowSize + 2)) return MFSR_E_UNSUPPORTED;
-    MFSR_REQUIRE((long long)pitchShift >= 8LL * width && (pitchShift & 7) == 0);
-    MFSR_REQUIRE((long long)pitchImg >= 4LL * width && (pitchImg & 3) == 0 && (long long)pitchSD >= 4LL * width && (pitchSD & 3) == 0);
-    // (32-bit byte offsets inside every image, lk_at)
-    if ((long long)pitchShift * height >= (1LL << 32) || (long long)pitchImg * height >= (1LL << 32) || (long long)pitchSD * height >= (1LL << 32))
-        return MFSR_E_UNSUPPORTED;
+    MFSR_REQUIRE(frames && refImg);
+    const int rc = mfsr_lk_sweep_accepts(nFrames, width, height, halfWindowSize, pitchShift, pitchImg, pitchSD);
+    if (rc) return rc;
     LkSweepBatch b;
     memset(&b, 0, sizeof(b));
     for (int i = 0; i < nFrames; i++) {

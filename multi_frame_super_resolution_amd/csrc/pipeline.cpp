@@ -1637,8 +1637,12 @@ static bool can_defer_alignment(const mfsr_burst* b, bool supplied)
     // back: b->hostBusy) batches every group: the GPU has work queued, so frame-by-frame launches buy no latency and cost
     // a tenth of the alignment's throughput
     const bool hostImmediate = b->holdLastGroup && !b->hostBusy && (b->framesSinceRef < b->group || !hostDefer);
-    return align_batch_mode() != ALIGN_BATCH_OFF && b->group > 1 && b->L.nAlign >= b->group && lk_warped_path(b) &&
-           c.lkHalfWindow >= 1 && c.lkHalfWindow <= 7 && !supplied && !hostImmediate;
+    // (the sweep's own rule for the layout's images: what it admits here it takes in align_deferred)
+    const Layout& L = b->L;
+    return align_batch_mode() != ALIGN_BATCH_OFF && b->group > 1 && L.nAlign >= b->group && lk_warped_path(b) && !supplied &&
+           !hostImmediate &&
+           mfsr_lk_sweep_accepts(b->group, L.tw, L.th, c.lkHalfWindow, L.flowBuf[0].pitch, b->ref.pyr[0].pitch, L.work[0].lkSum[0].pitch) ==
+               MFSR_OK;
 }
 
 static int align_deferred(mfsr_burst* b, FuseGroup& g, mfsr_stream_t stream)
@@ -1734,33 +1738,19 @@ static int align_deferred(mfsr_burst* b, FuseGroup& g, mfsr_stream_t stream)
         }
     }
     // every Lucas-Kanade iteration of the batch in one launch
-    bool batched = true;
-    for (int it = 0; it < c.lkIterations && batched; it++) {
+    for (int it = 0; it < c.lkIterations; it++) {
         mfsr_lk_frame fr[MFSR_MAX_FUSE_GROUP];
         int m = 0;
         const bool lastIt = it == c.lkIterations - 1;
         for (int q = 0; q < n; q++)
             if (!g.isRef[idx[q]]) fr[m++] = lk_frame_desc(L, g.slot[idx[q]], it, lastIt, L.mov[q], L.work[q]);
         if (m == 0) break;
-        const int rc = mfsr_lucasKanadeSweepBatch(m, fr, (const float*)ref.pyr[0].ptr, L.flowBuf[0].pitch, ref.pyr[0].pitch,
-                                                  L.work[0].lkSum[0].pitch, L.tw, L.th, c.lkHalfWindow, c.lkMinDet,
-                                                  lastIt ? (float)L.flowScale : 1.0f, stream);
-        if (rc == MFSR_E_UNSUPPORTED && it == 0)
-            batched = false;  // (cannot happen after can_defer_alignment; kept as a safe fallback)
-        else if (rc)
-            return rc;
-        else
-            b->paths[MFSR_PATH_LK_SWEEP_BATCH]++;
+        TRY(mfsr_lucasKanadeSweepBatch(m, fr, (const float*)ref.pyr[0].ptr, L.flowBuf[0].pitch, ref.pyr[0].pitch, L.work[0].lkSum[0].pitch,
+                                       L.tw, L.th, c.lkHalfWindow, c.lkMinDet, lastIt ? (float)L.flowScale : 1.0f, stream));
+        b->paths[MFSR_PATH_LK_SWEEP_BATCH]++;
     }
-    // robustness masks (and, without the batch kernel, the iterations frame by frame)
-    bool maskBatch = stageBatch && batched && m > 0;
-    if (maskGroup && !batched) {
-        // (cannot happen, as above: the frame-by-frame masks read the half-resolution images, so put them back)
-        mfsr_prepare_frame pf[MFSR_MAX_FUSE_GROUP];
-        prepare_table(L, g, idx, mq, m, pf);
-        TRY(mfsr_cfa::prepareFrames(b->cfa, m, pf, L.mov[0].half.pitch, c.maxVal, L.hw, L.hh, L.mov[0].pyr[0].pitch,
-                                    nlev > 1 ? L.mov[0].pyr[1].pitch : 0, b->taps, b->ntaps, stream, false));
-    }
+    // robustness masks
+    bool maskBatch = stageBatch && m > 0;
     if (maskBatch && maskGroup) {
         mfsr_robustness_group_frame gf[MFSR_MAX_FUSE_GROUP];
         for (int k = 0; k < m; k++) {
@@ -1802,10 +1792,7 @@ static int align_deferred(mfsr_burst* b, FuseGroup& g, mfsr_stream_t stream)
     }
     for (int q = 0; q < n; q++) {
         const int i = idx[q], slot = g.slot[i];
-        if (!g.isRef[i]) {
-            if (!batched) TRY(align_lk(b, slot, L.mov[q], L.work[q], stream));
-            if (!maskBatch) TRY(align_post(b, slot, L.mov[q], stream));
-        }
+        if (!g.isRef[i] && !maskBatch) TRY(align_post(b, slot, L.mov[q], stream));
         aligned_outputs(b, slot, g.isRef[i], &g.flow[i], &g.mask[i]);
         g.deferred[i] = false;
         b->flowCur = g.flow[i];

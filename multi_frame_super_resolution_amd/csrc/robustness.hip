@@ -6,6 +6,12 @@
 // stay in VGPRs.  Quirk kept: of the 25 flow fetches only the last one
 // (x=2,y=2) can influence min/max (:62-72), so only that one is issued -- the
 // other 24 are dead in the reference too.
+//
+// Kernels of this file: k_ComputeRobustnessMask (the straight port), k_robustnessFused (one frame per grid layer: a table of
+// frames, the flow fetched before the reference patch is staged) and k_robustnessGroup (all frames of a group in one pass over
+// the reference: the burst's kernel).  The last two end in the same per-frame tail (maxShift / minShift to the four stored
+// floats), written out in both: as a shared function it moved k_robustnessGroup's instructions
+// (profiles/isa_alignment_forks.txt).
 #include <cstdlib>
 #include <cstring>
 #include "common.hpp"
@@ -117,29 +123,33 @@ __global__ void __launch_bounds__(256)
 //  * reads the one live sample of the 5 x 5 flow loop (x = y = 2, :66) as a plain texel when the flow field has the
 //    image's resolution (the Bayer pipeline): the bilinear fetch lands on a texel centre up to 1 ulp of the coordinate;
 //  * writes the zero ring the reference leaves to its caller (:48-49): no separate ring launch;
-//  * (round 3, RB_FLOW_FIRST) fetches the pixel's flow BEFORE the reference patch is staged and gathers the moved patch
+//  * (round 3) fetches the pixel's flow BEFORE the reference patch is staged and gathers the moved patch
 //    before the barrier: of the three dependent round trips (stage, flow, gather) two overlap -- the kernel waits twice as
-//    long as it issues (SQ_WAIT_INST_ANY 1.05e8 vs SQ_ACTIVE_INST_VALU 5.2e7 per 4-frame launch); 115.5 -> 106 us.
+//    long as it issues (SQ_WAIT_INST_ANY 1.05e8 vs SQ_ACTIVE_INST_VALU 5.2e7 per 4-frame launch); 115.5 -> 106 us against
+//    fetching the flow after the barrier.
 #define RB_TX 64
 #define RB_TY 8
-#ifndef RB_FLOW_FIRST
-#define RB_FLOW_FIRST 1
-#endif
+
+struct RobustFusedFrame {
+    const pix3* moved;
+    float4* mask;
+    const float2* flow;
+};
+struct RobustFusedFrames {
+    RobustFusedFrame f[MFSR_BATCH_MAX];
+};
+// texUV: the flow fields' pitch and size; its pointer is the frame's flow
 template <bool ALIGNED>
 __global__ void __launch_bounds__(RB_TX* RB_TY)
-    k_robustnessFused(const pix3* __restrict__ rawImgRef, const pix3* __restrict__ rawImgMoved, float4* __restrict__ robustnessMask,
-                      mfsr_tex2d texUV, int imgWidth, int imgHeight, int imgPitch, int maskPitch, float alpha, float beta,
-                      float thresholdM, MfsrBatch bt, MfsrExactDiv dW, MfsrExactDiv dH)
+    k_robustnessFused(const pix3* __restrict__ rawImgRef, RobustFusedFrames frames, mfsr_tex2d texUV, int imgWidth, int imgHeight,
+                      int imgPitch, int maskPitch, float alpha, float beta, float thresholdM, MfsrExactDiv dW, MfsrExactDiv dH)
 {
-    if (gridDim.z > 1) {
-        rawImgMoved = (const pix3*)bt.p[blockIdx.z][0];
-        robustnessMask = (float4*)bt.p[blockIdx.z][1];
-        texUV.ptr = bt.p[blockIdx.z][2];
-    }
+    const pix3* __restrict__ rawImgMoved = frames.f[blockIdx.z].moved;
+    float4* __restrict__ robustnessMask = frames.f[blockIdx.z].mask;
+    texUV.ptr = frames.f[blockIdx.z].flow;
     __shared__ float sR[3][RB_TY + 2][RB_TX + 2];
     const int lx = threadIdx.x, ly = threadIdx.y;
     const int x0 = blockIdx.x * RB_TX, y0 = blockIdx.y * RB_TY;
-#if RB_FLOW_FIRST
     // this pixel's flow first: its fetch and the moved-image gather that depends on it are then in flight while the
     // reference patch is staged (three dependent round trips become two)
     const int pxXe = min(x0 + lx, imgWidth - 1), pxYe = min(y0 + ly, imgHeight - 1);
@@ -151,7 +161,6 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
     } else {
         sE = tex2<ADDR_CLAMP>(texUV, mfsr_div((float)pxXe + (float)2 + 0.5f, dW), mfsr_div((float)pxYe + (float)2 + 0.5f, dH));
     }
-#endif
     for (int t = ly * RB_TX + lx; t < (RB_TY + 2) * (RB_TX + 2); t += RB_TX * RB_TY) {
         const int r = t / (RB_TX + 2), c = t - r * (RB_TX + 2);
         const int gy = clampi(y0 - 1 + r, 0, imgHeight - 1), gx = clampi(x0 - 1 + c, 0, imgWidth - 1);
@@ -160,7 +169,6 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
         sR[1][r][c] = p.y;
         sR[2][r][c] = p.z;
     }
-#if RB_FLOW_FIRST
     // the moved patch under the rounded flow: gathered before the barrier, summed after it
     const int shxE = round2i(shiftfE.x * 0.5f), shyE = round2i(shiftfE.y * 0.5f);
     pix3 pmv[9];
@@ -170,7 +178,6 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
 #pragma unroll
         for (int x = 0; x < 3; x++) pmv[y * 3 + x] = rm[clampi(pxXe + shxE + x - 1, 0, imgWidth - 1)];
     }
-#endif
     __syncthreads();
     const int pxX = x0 + lx, pxY = y0 + ly;
     if (pxX >= imgWidth || pxY >= imgHeight) return;
@@ -179,33 +186,18 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
         *out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
-#if RB_FLOW_FIRST
     const float2 shiftf = shiftfE, s = sE;   // (pxX == pxXe, pxY == pxYe for every pixel that gets here)
-#else
-    const float2 shiftf =
-        tex2<ADDR_CLAMP>(texUV, ((float)pxX + 0.5f) / (float)imgWidth, ((float)pxY + 0.5f) / (float)imgHeight);
-    float2 s;
-    if (ALIGNED) {
-        s = row_ptr((const float2*)texUV.ptr, texUV.pitch, min(pxY + 2, imgHeight - 1))[min(pxX + 2, imgWidth - 1)];
-    } else {
-        s = tex2<ADDR_CLAMP>(texUV, ((float)pxX + (float)2 + 0.5f) / (float)imgWidth, ((float)pxY + (float)2 + 0.5f) / (float)imgHeight);
-    }
-#endif
     float2 maxShift, minShift;
     maxShift.x = fmaxf(s.x, shiftf.x);
     maxShift.y = fmaxf(s.y, shiftf.y);
     minShift.x = fminf(s.x, shiftf.x);
     minShift.y = fminf(s.y, shiftf.y);
-    const int shx = round2i(shiftf.x * 0.5f);
-    const int shy = round2i(shiftf.y * 0.5f);
-    (void)shx;
 
     // means in the reference's summation order (row-major from 0), exact division by 9
     float pr[3][9];
     float mr[3] = {0.0f, 0.0f, 0.0f}, mm[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int y = 0; y < 3; y++) {
-        const pix3* rm = row_ptr(rawImgMoved, imgPitch, clampi(pxY + shy + y - 1, 0, imgHeight - 1));
 #pragma unroll
         for (int x = 0; x < 3; x++) {
 #pragma unroll
@@ -213,12 +205,7 @@ __global__ void __launch_bounds__(RB_TX* RB_TY)
                 pr[c][y * 3 + x] = sR[c][ly + y][lx + x];
                 mr[c] += pr[c][y * 3 + x];
             }
-#if RB_FLOW_FIRST
             const pix3 p = pmv[y * 3 + x];
-            (void)rm;
-#else
-            const pix3 p = rm[clampi(pxX + shx + x - 1, 0, imgWidth - 1)];
-#endif
             mm[0] += p.x;
             mm[1] += p.y;
             mm[2] += p.z;
@@ -280,9 +267,7 @@ struct RobustGroupArgs {
 };
 __device__ __forceinline__ int rb_wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
 
-#ifndef RB_GROUP_WAVES
-#define RB_GROUP_WAVES 8
-#endif
+constexpr int RB_GROUP_WAVES = 8;  // waves per SIMD the group kernel is compiled for
 template <int NF>
 __global__ void __launch_bounds__(RB_TX* RB_TY) __attribute__((amdgpu_waves_per_eu(RB_GROUP_WAVES, RB_GROUP_WAVES)))
     k_robustnessGroup(const pix3* __restrict__ rawImgRef, RobustGroupArgs ga, int imgWidth, int imgHeight, int imgPitch, int flowPitch,
@@ -428,6 +413,35 @@ extern "C" int mfsr_set_robustness_fast(int enable)
     return MFSR_OK;
 }
 
+// k_robustnessFused for 1 .. 4 moved frames against one reference in one launch: the frame table's checks and the launch
+static int robustness_fused_launch(int nFrames, const mfsr_robustness_frame* frames, const mfsr_float3* rawImgRef, int flowPitch,
+                                   int flowWidth, int flowHeight, int imgWidth, int imgHeight, int imgPitch, int maskPitch, float alpha,
+                                   float beta, float thresholdM, mfsr_stream_t stream, const char* what)
+{
+    mfsr_tex2d texUV;
+    texUV.ptr = frames[0].flow;
+    texUV.pitch = flowPitch;
+    texUV.width = flowWidth;
+    texUV.height = flowHeight;
+    MFSR_REQUIRE(mfsr_tex_ok(texUV, 8) && (flowPitch & 7) == 0);
+    RobustFusedFrames fr;
+    memset(&fr, 0, sizeof(fr));
+    for (int i = 0; i < nFrames; i++) {
+        MFSR_REQUIRE(frames[i].movedHalf && frames[i].mask && frames[i].flow);
+        MFSR_REQUIRE(((uintptr_t)frames[i].mask & 15) == 0 && ((uintptr_t)frames[i].flow & 7) == 0);
+        fr.f[i] = RobustFusedFrame{(const pix3*)frames[i].movedHalf, (float4*)frames[i].mask, (const float2*)frames[i].flow};
+    }
+    dim3 block(RB_TX, RB_TY), grid(mfsr_cdiv(imgWidth, RB_TX), mfsr_cdiv(imgHeight, RB_TY), nFrames);
+    const MfsrExactDiv dW = mfsr_exact_div((float)imgWidth), dH = mfsr_exact_div((float)imgHeight);
+    if (flowWidth == imgWidth && flowHeight == imgHeight)
+        hipLaunchKernelGGL(k_robustnessFused<true>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, fr, texUV, imgWidth, imgHeight,
+                           imgPitch, maskPitch, alpha, beta, thresholdM, dW, dH);
+    else
+        hipLaunchKernelGGL(k_robustnessFused<false>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, fr, texUV, imgWidth, imgHeight,
+                           imgPitch, maskPitch, alpha, beta, thresholdM, dW, dH);
+    return mfsr_launch_status(what);
+}
+
 // F1 + the zero ring in one launch (what the burst pipeline calls); falls back to ring + straight kernel when the fast
 // kernel is switched off
 extern "C" int mfsr_robustnessMaskFused(const mfsr_float3* rawImgRef, const mfsr_float3* rawImgMoved, mfsr_float4* robustnessMask,
@@ -444,17 +458,9 @@ extern "C" int mfsr_robustnessMaskFused(const mfsr_float3* rawImgRef, const mfsr
         return mfsr_ComputeRobustnessMask(rawImgRef, rawImgMoved, robustnessMask, texUV, imgWidth, imgHeight, imgPitch, maskPitch,
                                           alpha, beta, thresholdM, stream);
     }
-    MfsrBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    dim3 block(RB_TX, RB_TY), grid(mfsr_cdiv(imgWidth, RB_TX), mfsr_cdiv(imgHeight, RB_TY));
-    const MfsrExactDiv dW = mfsr_exact_div((float)imgWidth), dH = mfsr_exact_div((float)imgHeight);
-    if (texUV.width == imgWidth && texUV.height == imgHeight)
-        hipLaunchKernelGGL(k_robustnessFused<true>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, (const pix3*)rawImgMoved,
-                           (float4*)robustnessMask, texUV, imgWidth, imgHeight, imgPitch, maskPitch, alpha, beta, thresholdM, bt, dW, dH);
-    else
-        hipLaunchKernelGGL(k_robustnessFused<false>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, (const pix3*)rawImgMoved,
-                           (float4*)robustnessMask, texUV, imgWidth, imgHeight, imgPitch, maskPitch, alpha, beta, thresholdM, bt, dW, dH);
-    return mfsr_launch_status("robustnessMaskFused");
+    const mfsr_robustness_frame one = {rawImgMoved, robustnessMask, (const mfsr_float2*)texUV.ptr};
+    return robustness_fused_launch(1, &one, rawImgRef, texUV.pitch, texUV.width, texUV.height, imgWidth, imgHeight, imgPitch, maskPitch,
+                                   alpha, beta, thresholdM, stream, "robustnessMaskFused");
 }
 
 // mfsr_robustnessMaskFused for 1 .. 4 moved frames against one reference in one launch (the fused kernel only)
@@ -466,30 +472,8 @@ extern "C" int mfsr_robustnessMaskFusedBatch(int nFrames, const mfsr_robustness_
     MFSR_REQUIRE((long long)imgPitch >= 12LL * imgWidth && (imgPitch & 3) == 0);
     MFSR_REQUIRE((long long)maskPitch >= 16LL * imgWidth && (maskPitch & 15) == 0);
     if (!g_robustness_fast) return MFSR_E_UNSUPPORTED;
-    mfsr_tex2d texUV;
-    texUV.ptr = frames[0].flow;
-    texUV.pitch = flowPitch;
-    texUV.width = flowWidth;
-    texUV.height = flowHeight;
-    MFSR_REQUIRE(mfsr_tex_ok(texUV, 8) && (flowPitch & 7) == 0);
-    MfsrBatch bt;
-    memset(&bt, 0, sizeof(bt));
-    for (int i = 0; i < nFrames; i++) {
-        MFSR_REQUIRE(frames[i].movedHalf && frames[i].mask && frames[i].flow);
-        MFSR_REQUIRE(((uintptr_t)frames[i].mask & 15) == 0 && ((uintptr_t)frames[i].flow & 7) == 0);
-        bt.p[i][0] = frames[i].movedHalf;
-        bt.p[i][1] = frames[i].mask;
-        bt.p[i][2] = frames[i].flow;
-    }
-    dim3 block(RB_TX, RB_TY), grid(mfsr_cdiv(imgWidth, RB_TX), mfsr_cdiv(imgHeight, RB_TY), nFrames);
-    const MfsrExactDiv dW = mfsr_exact_div((float)imgWidth), dH = mfsr_exact_div((float)imgHeight);
-    if (flowWidth == imgWidth && flowHeight == imgHeight)
-        hipLaunchKernelGGL(k_robustnessFused<true>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, (const pix3*)frames[0].movedHalf,
-                           (float4*)frames[0].mask, texUV, imgWidth, imgHeight, imgPitch, maskPitch, alpha, beta, thresholdM, bt, dW, dH);
-    else
-        hipLaunchKernelGGL(k_robustnessFused<false>, grid, block, 0, mfsr_s(stream), (const pix3*)rawImgRef, (const pix3*)frames[0].movedHalf,
-                           (float4*)frames[0].mask, texUV, imgWidth, imgHeight, imgPitch, maskPitch, alpha, beta, thresholdM, bt, dW, dH);
-    return mfsr_launch_status("robustnessMaskFusedBatch");
+    return robustness_fused_launch(nFrames, frames, rawImgRef, flowPitch, flowWidth, flowHeight, imgWidth, imgHeight, imgPitch, maskPitch,
+                                   alpha, beta, thresholdM, stream, "robustnessMaskFusedBatch");
 }
 
 // 1 (default): the burst driver makes the masks of an aligned group with mfsr_prepareFrameMeansBatch + mfsr_robustnessMaskGroup;

@@ -9,7 +9,10 @@
 //    the serial semantics (first strict minimum) by reducing (value, index)
 //    pairs with index as tie-break, so its result is bit-identical.
 //  * trackTilesFused evaluates the whole B1..B7 chain for one tile inside one
-//    workgroup from LDS (no FFT, no tile stacks in HBM).
+//    workgroup from LDS (no FFT, no tile stacks in HBM): k_trackTilesFused for any
+//    tile size and search range, one frame and one candidate shift per thread;
+//    k_trackTilesFast for the pipeline's (tile size, search range) pairs at compile
+//    time, with a table of 1 .. 4 frames (TrkFrames, frame = blockIdx.z).
 #include <cfloat>
 
 #include <cstdlib>
@@ -686,16 +689,15 @@ extern "C" int mfsr_fftshift(mfsr_float2* fft, int width, int height, mfsr_strea
 //    reference (mfsr_tileSquaredSums) and passed in; without it one lane per tile takes it here.
 //  * the box term shares its row sums: rowsq[patch row][sx] is used by all 2S+1 candidates of a
 //    column, so it is tabulated first (L*(2S+1) sums of T) instead of (2S+1)^2 * T per tile.
-//  * a thread owns NSX neighbouring sx of one sy and (2S+1)*ceil((2S+1)/NSX) threads serve a tile; a
-//    workgroup packs as many tiles as fit into its 128 threads.  NSX > 1 re-uses each LDS load for
-//    NSX multiply-adds but leaves about one wavefront per SIMD at 4K (every candidate is one serial
+//  * a thread owns one candidate (sx, sy) and (2S+1)^2 threads serve a tile; a workgroup packs as many
+//    tiles as fit into its 128 threads.  Two or three neighbouring sx per thread re-used each LDS load
+//    for as many multiply-adds but left about one wavefront per SIMD at 4K (every candidate is one serial
 //    chain of T*T multiply-adds, so tiles x candidates is all the parallelism there is): measured
-//    36.6 us (NSX = 1), 59 us (2), 60 us (3) per launch, so NSX = 1 is the default (MFSR_TRK_NSX).
+//    36.6 us (one sx per thread), 59 us (two), 60 us (three) per launch, so one it is.
 //    (Reading the template through the scalar cache instead of LDS -- its address is wave-uniform with
 //    one tile per workgroup -- was also tried: 41 us, the SMEM and LDS waits share one counter.)
 // One wavefront per tile then reduces D with shuffles and lane 0 runs the quadratic fit.
 #define TRK_THREADS 128
-template <int TRK_NSX>
 __global__ void __launch_bounds__(TRK_THREADS)
     k_trackTilesFused(const float* __restrict__ refImg, const float* __restrict__ movedImg,
                       const float2* __restrict__ preShift, int preShiftPitch, float2* __restrict__ coordinates,
@@ -706,9 +708,8 @@ __global__ void __launch_bounds__(TRK_THREADS)
 {
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
     const int T = tileSize, S = maxShift, L = T + 2 * S, R = 2 * S + 1;
-    const int Lp = L + TRK_NSX;                 // patch row stride: the last sx group may read past the row
-    const int G = (R + TRK_NSX - 1) / TRK_NSX;  // sx groups per sy
-    const int nRef = T * T, nMov = L * Lp + TRK_NSX, nRow = L * R, nDist = R * R;
+    const int Lp = L + 1;                       // patch row stride (one pad column)
+    const int nRef = T * T, nMov = L * Lp + 1, nRow = L * R, nDist = R * R;
     const int slotFloats = ((nRef + nMov + nRow + nDist + 1) + 3) & ~3;
     const int tid = threadIdx.x;
     const int tileCount = tileCountX * tileCountY;
@@ -796,54 +797,37 @@ __global__ void __launch_bounds__(TRK_THREADS)
     }
     __syncthreads();
 
-    // correlation: thread = (tile slot, sy, group of three sx)
-    const int perTile = R * G;
+    // correlation: thread = (tile slot, sy, sx)
+    const int perTile = R * R;
     for (int item = tid; item < tilesPerWg * perTile; item += TRK_THREADS) {
         const int sl = item / perTile, q = item - sl * perTile;
-        const int sy = q / G, sx0 = (q - sy * G) * TRK_NSX;
+        const int sy = q / R, sx = q - sy * R;
         if (tile0 + sl < tileCount) {
             const float* ref = slot_ref(sl);
-            const float* mov = slot_mov(sl) + sy * Lp + sx0;
-            float cc[TRK_NSX];
-#pragma unroll
-            for (int j = 0; j < TRK_NSX; j++) cc[j] = 0;
+            const float* mov = slot_mov(sl) + sy * Lp + sx;
+            float cc = 0;
             for (int y = 0; y < T; y++) {
                 const float* rrow = ref + y * T;
                 const float* mrow = mov + y * Lp;
-                float rs[TRK_NSX];  // row sum, left to right; the rows add top to bottom
-#pragma unroll
-                for (int j = 0; j < TRK_NSX; j++) rs[j] = 0;
+                float rs = 0;  // row sum, left to right; the rows add top to bottom
                 int x = 0;
                 for (; x + 8 <= T; x += 8) {
-                    float r[8], m[8 + TRK_NSX - 1];
+                    float r[8], m[8];
 #pragma unroll
                     for (int d = 0; d < 8; d++) r[d] = rrow[x + d];
 #pragma unroll
-                    for (int d = 0; d < 8 + TRK_NSX - 1; d++) m[d] = mrow[x + d];
+                    for (int d = 0; d < 8; d++) m[d] = mrow[x + d];
 #pragma unroll
-                    for (int d = 0; d < 8; d++)
-#pragma unroll
-                        for (int j = 0; j < TRK_NSX; j++) rs[j] += r[d] * m[d + j];
+                    for (int d = 0; d < 8; d++) rs += r[d] * m[d];
                 }
-                for (; x < T; x++) {
-                    const float r = rrow[x];
-#pragma unroll
-                    for (int j = 0; j < TRK_NSX; j++) rs[j] += r * mrow[x + j];
-                }
-#pragma unroll
-                for (int j = 0; j < TRK_NSX; j++) cc[j] += rs[j];
+                for (; x < T; x++) rs += rrow[x] * mrow[x];
+                cc += rs;
             }
             const float sq = *slot_sq(sl);
             const float* rows = slot_row(sl);
-#pragma unroll
-            for (int j = 0; j < TRK_NSX; j++) {
-                const int sx = sx0 + j;
-                if (sx < R) {
-                    float box = 0;
-                    for (int y = 0; y < TB; y++) box += rows[(sy + y) * R + sx];
-                    slot_dist(sl)[sy * R + sx] = sq + box - 2 * cc[j];
-                }
-            }
+            float box = 0;
+            for (int y = 0; y < TB; y++) box += rows[(sy + y) * R + sx];
+            slot_dist(sl)[sy * R + sx] = sq + box - 2 * cc;
         }
     }
     __syncthreads();
@@ -903,20 +887,29 @@ struct TrkFast {
     static_assert(threads <= 1024 && ldsBytes <= 64 * 1024 && TPW * R * R <= corrThreads && T % 4 == 0, "tile geometry");
 };
 
+// the frames of a launch: frame blockIdx.z reads its own entry
+struct TrkFrame {
+    const float* movedImg;
+    const float2* preShift;  // given pre-shifts (B8's output), or
+    const float2* coarse;    // the coarser level's shifts to take them from, or neither
+    float2* coordinates;
+    const mfsr_prealign* base;  // or nullptr
+};
+struct TrkFrames {
+    TrkFrame f[MFSR_BATCH_MAX];
+};
+
 template <int T, int S, int TPW>
 __global__ void __launch_bounds__((TrkFast<T, S, TPW>::threads))
-    k_trackTilesFast(const float* __restrict__ refImg, const float* __restrict__ movedImg, const float2* __restrict__ preShift,
-                     int preShiftPitch, float2* __restrict__ coordinates, int coordinatesPitch, int imgWidth, int imgHeight,
-                     int imgPitch, int tileCountX, int tileCountY, float threshold, const float* __restrict__ refSq,
-                     const mfsr_prealign* __restrict__ base, float baseInvScale, const float2* __restrict__ coarse, int coarsePitch,
-                     int4 up, int upOldTile, MfsrBatch bt)
+    k_trackTilesFast(const float* __restrict__ refImg, TrkFrames frames, int preShiftPitch, int coordinatesPitch, int imgWidth,
+                     int imgHeight, int imgPitch, int tileCountX, int tileCountY, float threshold, const float* __restrict__ refSq,
+                     float baseInvScale, int coarsePitch, int4 up, int upOldTile)
 {
-    if (gridDim.z > 1) {
-        movedImg = (const float*)bt.p[blockIdx.z][0];
-        coarse = (const float2*)bt.p[blockIdx.z][1];
-        coordinates = (float2*)bt.p[blockIdx.z][2];
-        base = (const mfsr_prealign*)bt.p[blockIdx.z][3];
-    }
+    const float* __restrict__ movedImg = frames.f[blockIdx.z].movedImg;
+    const float2* __restrict__ preShift = frames.f[blockIdx.z].preShift;
+    const float2* __restrict__ coarse = frames.f[blockIdx.z].coarse;
+    float2* __restrict__ coordinates = frames.f[blockIdx.z].coordinates;
+    const mfsr_prealign* __restrict__ base = frames.f[blockIdx.z].base;
     using G = TrkFast<T, S, TPW>;
     constexpr int L = G::L, R = G::R, Tp = G::Tp, Lp = G::Lp;
     extern __shared__ __attribute__((aligned(16))) float s_mem[];
@@ -1166,18 +1159,17 @@ extern "C" int mfsr_tileSquaredSumsLevels(int levels, const mfsr_tex2d* refImgs,
     return mfsr_launch_status("tileSquaredSumsLevels");
 }
 
-static int track_tiles_fused_impl(const float* refImg, const float* movedImg, const mfsr_float2* preShift, int preShiftPitch,
-                                  mfsr_float2* coordinates, int coordinatesPitch, int imgWidth, int imgHeight, int imgPitch,
-                                  int maxShift, int tileSize, int tileCountX, int tileCountY, float threshold,
-                                  const float* refSquaredSums, const mfsr_prealign* base, float baseInvScale,
-                                  const mfsr_float2* coarse, int coarsePitch, int4 up, int upOldTile, mfsr_stream_t stream,
-                                  int nFrames = 1, const MfsrBatch* batch = nullptr)
+// nFrames frames (fr.f[0 .. nFrames - 1]) against one reference: the compile-time kernel where it applies, for a single frame
+// the generic one otherwise.  The checks of the per-frame pointers beyond the first frame's are the batch entry point's.
+static int track_tiles_fused_impl(int nFrames, const TrkFrames& fr, const float* refImg, int preShiftPitch, int coordinatesPitch,
+                                  int imgWidth, int imgHeight, int imgPitch, int maxShift, int tileSize, int tileCountX, int tileCountY,
+                                  float threshold, const float* refSquaredSums, float baseInvScale, int coarsePitch, int4 up, int upOldTile,
+                                  mfsr_stream_t stream)
 {
-    MfsrBatch bt;
-    if (batch)
-        bt = *batch;
-    else
-        memset(&bt, 0, sizeof(bt));
+    const float* movedImg = fr.f[0].movedImg;
+    const float2 *preShift = fr.f[0].preShift, *coarse = fr.f[0].coarse;
+    float2* coordinates = fr.f[0].coordinates;
+    const mfsr_prealign* base = fr.f[0].base;
     MFSR_REQUIRE(refImg && movedImg && coordinates && imgWidth > 0 && imgHeight > 0);
     MFSR_REQUIRE((long long)imgPitch >= 4LL * imgWidth && (imgPitch & 3) == 0);
     MFSR_REQUIRE(maxShift >= 1 && maxShift <= 15 && tileSize >= 4 && tileSize <= 128 && tileCountX > 0 && tileCountY > 0);
@@ -1191,10 +1183,9 @@ static int track_tiles_fused_impl(const float* refImg, const float* movedImg, co
     if (fast && refSquaredSums && tileSize == TT && maxShift == SS) {                                                    \
         using G = TrkFast<TT, SS, TPW>;                                                                                  \
         hipLaunchKernelGGL((k_trackTilesFast<TT, SS, TPW>), dim3(mfsr_cdiv(tileCountX * tileCountY, TPW), 1, nFrames),    \
-                           dim3(G::threads), G::ldsBytes, mfsr_s(stream), refImg, movedImg, (const float2*)preShift,      \
-                           preShiftPitch, (float2*)coordinates, coordinatesPitch, imgWidth, imgHeight, imgPitch, tileCountX, \
-                           tileCountY, threshold, refSquaredSums, base, baseInvScale, (const float2*)coarse, coarsePitch, \
-                           up, upOldTile, bt);                                                                            \
+                           dim3(G::threads), G::ldsBytes, mfsr_s(stream), refImg, fr, preShiftPitch, coordinatesPitch,    \
+                           imgWidth, imgHeight, imgPitch, tileCountX, tileCountY, threshold, refSquaredSums, baseInvScale, \
+                           coarsePitch, up, upOldTile);                                                                   \
         return mfsr_launch_status("trackTilesFast");                                                                     \
     }
     TRK_FAST_CASE(32, 4, 2)
@@ -1203,36 +1194,20 @@ static int track_tiles_fused_impl(const float* refImg, const float* movedImg, co
     TRK_FAST_CASE(32, 8, 1)
 #undef TRK_FAST_CASE
     if (nFrames > 1) return MFSR_E_UNSUPPORTED;  // frame batches run the compile-time kernel only
-    static const int nsx = [] {
-        const char* e = getenv("MFSR_TRK_NSX");
-        return (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 1;
-    }();
-    const int TRK_NSX = nsx;
-    const int T = tileSize, L = T + 2 * maxShift, R = 2 * maxShift + 1, Lp = L + TRK_NSX;
-    const int G = (R + TRK_NSX - 1) / TRK_NSX;
-    const int slotFloats = ((T * T + L * Lp + TRK_NSX + L * R + R * R + 1) + 3) & ~3;
-    int tilesPerWg = TRK_THREADS / (R * G) > 0 ? TRK_THREADS / (R * G) : 1;  // large search ranges: several rounds per tile
+    const int T = tileSize, L = T + 2 * maxShift, R = 2 * maxShift + 1, Lp = L + 1;   // (as in the kernel)
+    const int slotFloats = ((T * T + L * Lp + 1 + L * R + R * R + 1) + 3) & ~3;
+    int tilesPerWg = TRK_THREADS / (R * R) > 0 ? TRK_THREADS / (R * R) : 1;  // large search ranges: several rounds per tile
     while (tilesPerWg > 1 && sizeof(float) * (size_t)slotFloats * tilesPerWg > 56 * 1024) tilesPerWg--;
     const size_t lds = sizeof(float) * (size_t)slotFloats * tilesPerWg;
     if (lds > 160 * 1024) return MFSR_E_UNSUPPORTED;
     const int tiles = tileCountX * tileCountY;
     // (one tile of more than 64 KB, e.g. 64 + 2 * 15: the workgroup may take up to the CU's 160 KB once the kernel allows it)
-#define TRK_LAUNCH(N)                                                                                                  \
-    if (lds > 64 * 1024) /* the attribute is the function's on the current device: set for every such launch */        \
-        MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_trackTilesFused<N>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
-                                         160 * 1024));                                                                 \
-    hipLaunchKernelGGL(k_trackTilesFused<N>, dim3(mfsr_cdiv(tiles, tilesPerWg)), dim3(TRK_THREADS), lds, mfsr_s(stream),  \
-                       refImg, movedImg, (const float2*)preShift, preShiftPitch, (float2*)coordinates, coordinatesPitch, \
-                       imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX, tileCountY, threshold,           \
-                       refSquaredSums, tilesPerWg, base, baseInvScale, (const float2*)coarse, coarsePitch, up, upOldTile)
-    if (nsx == 1) {
-        TRK_LAUNCH(1);
-    } else if (nsx == 2) {
-        TRK_LAUNCH(2);
-    } else {
-        TRK_LAUNCH(3);
-    }
-#undef TRK_LAUNCH
+    if (lds > 64 * 1024)  // the attribute is the function's on the current device: set for every such launch
+        MFSR_HIP_TRY(hipFuncSetAttribute((const void*)k_trackTilesFused, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(k_trackTilesFused, dim3(mfsr_cdiv(tiles, tilesPerWg)), dim3(TRK_THREADS), lds, mfsr_s(stream), refImg, movedImg,
+                       preShift, preShiftPitch, coordinates, coordinatesPitch, imgWidth, imgHeight, imgPitch, maxShift, tileSize,
+                       tileCountX, tileCountY, threshold, refSquaredSums, tilesPerWg, base, baseInvScale, coarse, coarsePitch, up,
+                       upOldTile);
     return mfsr_launch_status("trackTilesFused");
 }
 
@@ -1242,9 +1217,10 @@ extern "C" int mfsr_trackTilesFusedBase(const float* refImg, const float* movedI
                                         int tileCountY, float threshold, const float* refSquaredSums,
                                         const mfsr_prealign* base, float baseInvScale, mfsr_stream_t stream)
 {
-    return track_tiles_fused_impl(refImg, movedImg, preShift, preShiftPitch, coordinates, coordinatesPitch, imgWidth, imgHeight,
-                                  imgPitch, maxShift, tileSize, tileCountX, tileCountY, threshold, refSquaredSums, base, baseInvScale,
-                                  nullptr, 0, make_int4(0, 0, 0, 0), 0, stream);
+    TrkFrames one = {};
+    one.f[0] = TrkFrame{movedImg, (const float2*)preShift, nullptr, (float2*)coordinates, base};
+    return track_tiles_fused_impl(1, one, refImg, preShiftPitch, coordinatesPitch, imgWidth, imgHeight, imgPitch, maxShift, tileSize,
+                                  tileCountX, tileCountY, threshold, refSquaredSums, baseInvScale, 0, make_int4(0, 0, 0, 0), 0, stream);
 }
 
 // the same with UpSampleShifts (B8, kernel.cu:642) folded in: the pre-shift of every tile is the bilinear up-sampling of the
@@ -1259,9 +1235,11 @@ extern "C" int mfsr_trackTilesFusedUp(const float* refImg, const float* movedImg
 {
     MFSR_REQUIRE(coarseShifts && oldLevel > 0 && newLevel > 0 && oldCountX > 0 && oldCountY > 0 && oldTileSize > 0);
     MFSR_REQUIRE((long long)coarsePitch >= 8LL * oldCountX && (coarsePitch & 7) == 0 && ((uintptr_t)coarseShifts & 7) == 0);
-    return track_tiles_fused_impl(refImg, movedImg, nullptr, 0, coordinates, coordinatesPitch, imgWidth, imgHeight, imgPitch, maxShift,
-                                  tileSize, tileCountX, tileCountY, threshold, refSquaredSums, base, baseInvScale, coarseShifts,
-                                  coarsePitch, make_int4(oldLevel, newLevel, oldCountX, oldCountY), oldTileSize, stream);
+    TrkFrames one = {};
+    one.f[0] = TrkFrame{movedImg, nullptr, (const float2*)coarseShifts, (float2*)coordinates, base};
+    return track_tiles_fused_impl(1, one, refImg, 0, coordinatesPitch, imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX,
+                                  tileCountY, threshold, refSquaredSums, baseInvScale, coarsePitch,
+                                  make_int4(oldLevel, newLevel, oldCountX, oldCountY), oldTileSize, stream);
 }
 
 // 1 if (tileSize, maxShift) runs the compile-time tracker kernel (the only one that takes frame batches)
@@ -1280,26 +1258,21 @@ extern "C" int mfsr_trackTilesFusedBatch(int nFrames, const mfsr_track_frame* fr
                                          float threshold, const float* refSquaredSums, float baseInvScale, mfsr_stream_t stream)
 {
     MFSR_REQUIRE(frames && nFrames >= 1 && nFrames <= MFSR_BATCH_MAX && refSquaredSums);
-    MfsrBatch bt;
-    memset(&bt, 0, sizeof(bt));
+    TrkFrames fr = {};
     const bool up = frames[0].coarseShifts != nullptr;
     for (int i = 0; i < nFrames; i++) {
         MFSR_REQUIRE(frames[i].movedImg && frames[i].coordinates && ((uintptr_t)frames[i].coordinates & 7) == 0);
         MFSR_REQUIRE((frames[i].coarseShifts != nullptr) == up && ((uintptr_t)frames[i].coarseShifts & 7) == 0);
-        bt.p[i][0] = frames[i].movedImg;
-        bt.p[i][1] = frames[i].coarseShifts;
-        bt.p[i][2] = frames[i].coordinates;
-        bt.p[i][3] = frames[i].base;
+        fr.f[i] = TrkFrame{frames[i].movedImg, nullptr, (const float2*)frames[i].coarseShifts, (float2*)frames[i].coordinates, frames[i].base};
     }
     if (up) {
         MFSR_REQUIRE(oldLevel > 0 && newLevel > 0 && oldCountX > 0 && oldCountY > 0 && oldTileSize > 0);
         MFSR_REQUIRE((long long)coarsePitch >= 8LL * oldCountX && (coarsePitch & 7) == 0);
     }
-    return track_tiles_fused_impl(refImg, frames[0].movedImg, nullptr, 0, frames[0].coordinates, coordinatesPitch, imgWidth, imgHeight,
-                                  imgPitch, maxShift, tileSize, tileCountX, tileCountY, threshold, refSquaredSums, frames[0].base,
-                                  baseInvScale, frames[0].coarseShifts, coarsePitch,
+    return track_tiles_fused_impl(nFrames, fr, refImg, 0, coordinatesPitch, imgWidth, imgHeight, imgPitch, maxShift, tileSize, tileCountX,
+                                  tileCountY, threshold, refSquaredSums, baseInvScale, coarsePitch,
                                   up ? make_int4(oldLevel, newLevel, oldCountX, oldCountY) : make_int4(0, 0, 0, 0), up ? oldTileSize : 0,
-                                  stream, nFrames, &bt);
+                                  stream);
 }
 
 extern "C" int mfsr_trackTilesFused(const float* refImg, const float* movedImg, const mfsr_float2* preShift,
