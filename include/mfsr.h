@@ -1617,6 +1617,72 @@ int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* lt, const fl
 int mfsr_burst_local_tone(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_local_tone* lt,
                           uint64_t* statsDev, float* gridDev, mfsr_local_tone_result* res, mfsr_stream_t stream);
 
+/* ---- the finish chain: denoise, then sharpen, then the local-tone gain, then matrix, tone and the store of ANY output format,
+ * the two-plane ones included, in one launch.  Off unless asked for: a separate description; the
+ * setters above keep their refusals and every other entry point produces the bits and the launches it always did.  At each
+ * pixel of the launch, in this order, each stage only if it is on:
+ *   1. p = the value section 2.19 calls p (a stripe or window is the crop of the whole frame)
+ *   2. d = steps 1-6 of the denoise above on p (the count is the weight with the + 1 under the threshold); off: d = p
+ *   3. s = steps 1-4 of the unsharp mask above on d (NaN cleaning, clamped coordinates, coring); off: s = d
+ *   4. t = s * g, g the trilinear gain of section 2.25 looked up with the luma key of s (through the matrix when the render
+ *      description has one) at the pixel's place in the full frame; off: t = s
+ *   5. t takes the place of p in the rendered output: matrix, tone and store of the four single-plane formats, or the Y'CbCr and
+ *      the 2 x 2 chroma mean of MFSR_OUT_NV12 / MFSR_OUT_P010
+ * A stage's stencil at a position outside the valid pixels takes that stage's value at the clamped position: the sharpen reads
+ * the DENOISED value of the clamped pixel.  So the result equals, bit for bit, mfsr_finishDenoised to a float image ({no
+ * matrix, no table}, applyGamma 0), then mfsr_sharpenImage to a float image likewise, then mfsr_localToneImage,
+ * mfsr_renderImage or mfsr_renderImageYuv with the real render description.  The cleaning is that of the first stage that is
+ * on.  A stage is off with radius 0 or strength / amount 0 (local tone: useLocalTone 0); its description must still be a valid
+ * one (mfsr_denoise_defaults, mfsr_local_tone_defaults; a zero-filled mfsr_sharpen is valid).
+ * mfsr_finish_chain_validate: the three descriptions' own validators, useLocalTone 0 or 1, reserved zero-filled.
+ * mfsr_finish_chain_reach: *rows = R_d + R_s, a stage that is off counting 0 (at most 7): the rows beyond its own that a launch
+ * reads.  mfsr_chain_tile: the output tile one workgroup owns. */
+typedef struct {
+    mfsr_denoise denoise;
+    mfsr_sharpen sharpen;
+    mfsr_local_tone localTone;
+    int32_t useLocalTone;  /* 1: stage 4 is on and a grid is given */
+    int32_t reserved[7];   /* zeros */
+} mfsr_finish_chain;
+int mfsr_finish_chain_validate(const mfsr_finish_chain* chain);
+int mfsr_finish_chain_reach(const mfsr_finish_chain* chain, int* rows);
+int mfsr_chain_tile(int* tileW, int* tileH);
+/* mfsr_chainImage: steps 2-5 on an existing float image (p = in); the valid extent is the image.  count as for
+ * mfsr_denoiseImage (NULL: n = 1 everywhere; read only when the denoise stage is on).  The image is the rectangle at (colOffset,
+ * rowOffset) of the fullWidth x fullHeight frame the grid belongs to (used by stage 4 only, always checked).
+ * mfsr_finishChain: mfsr_finishRendered with steps 2-4 in the same launch.  Columns are valid in [0, w), rows in [-rowsAbove,
+ * h + rowsBelow) relative to the launch's first row, as for the two stencil finishes: the accumulator and weight rows in that
+ * range must be complete.  The result equals the composition run on exactly those rows, cropped; with rowsAbove / rowsBelow >=
+ * min(reach, rows available) it is the crop of the whole frame's.
+ * Outputs: outImg (the float image the integers quantise) and / or the integer output.  Single-plane formats: out / outRowBytes,
+ * outUV NULL.  Two-plane formats: out is the Y plane, outUV the chroma plane (h / 2 rows uvRowBytes apart), both or neither, w
+ * and h even.  render NULL = {MFSR_OUT_RGB16, no matrix, no table}.  gridDev: the grid of gains (GX GY NZ floats of the full
+ * frame, 4-byte aligned), non-NULL if and only if useLocalTone.  Refused (MFSR_E_INVALID), on the host and before any device
+ * call: a description with every stage off; an output -- the chroma plane included -- that overlaps the rows read (a stencil
+ * cannot run in place); rowsAbove / rowsBelow outside the full frame.  A wave whose positions all have lambda == 0 skips the
+ * denoise stencil.  Asynchronous on `stream`; nothing is allocated. */
+int mfsr_chainImage(const mfsr_float3* in, int inRowBytes, const mfsr_float3* count, int countRowBytes, mfsr_float3* outImg,
+                    int outImgRowBytes, void* out, int outRowBytes, void* outUV, int uvRowBytes, int w, int h,
+                    const mfsr_render* render, int applyGamma, const mfsr_finish_chain* chain, const float* gridDev, int colOffset,
+                    int rowOffset, int fullWidth, int fullHeight, mfsr_stream_t stream);
+int mfsr_finishChain(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                     int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, mfsr_float3* outImg,
+                     int outImgRowBytes, void* out, int outRowBytes, void* outUV, int uvRowBytes, const mfsr_render* render, int w,
+                     int h, float threshold, int applyGamma, int colOffset, int rowOffset, int fullWidth, int fullHeight,
+                     const mfsr_finish_chain* chain, const float* gridDev, int rowsAbove, int rowsBelow, mfsr_stream_t stream);
+/* The burst's chain (copied; gridDev: the caller's device memory, valid while installed).  NULL, or a chain with every stage
+ * off, removes it.  Between bursts only, as mfsr_burst_set_render.  With one installed every finish of the burst goes through
+ * mfsr_finishChain; a chain with a stencil stage is a stencil finish of reach R_d + R_s (mfsr_burst_finish_rows, the lagged host
+ * bands, streams), and mfsr_burst_set_render accepts the two-plane formats (even extents as ever).  Refused (MFSR_E_INVALID; a
+ * refused call changes nothing): while mfsr_burst_set_sharpen, _denoise or _local_tone has a description on, and those three
+ * with a description that is on while a chain is installed; useLocalTone on a handle with cfg.uploadRing (its bands finish
+ * before the grid can be measured).  The grid is measured as ever (mfsr_finishToneGridStats on p, mfsr_local_tone_fit): before
+ * the denoise and the sharpen. */
+int mfsr_burst_set_finish_chain(mfsr_burst* b, const mfsr_finish_chain* chain, const float* gridDev);
+int mfsr_stream_set_finish_chain(mfsr_stream* s, const mfsr_finish_chain* chain, const float* gridDev);
+/* *finishes = the launches of mfsr_finishChain this burst has made since mfsr_burst_begin (as mfsr_burst_debug_denoised) */
+int mfsr_burst_debug_chained(const mfsr_burst* b, int* finishes);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

@@ -200,6 +200,13 @@ class LocalToneResult(ctypes.Structure):
                 ("minGain", ctypes.c_float), ("maxGain", ctypes.c_float)]
 
 
+class FinishChain(ctypes.Structure):
+    """mfsr_finish_chain (include/mfsr.h): denoise, sharpen and local tone of a chained finish."""
+
+    _fields_ = [("denoise", Denoise), ("sharpen", Sharpen), ("localTone", LocalTone), ("useLocalTone", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 7)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,

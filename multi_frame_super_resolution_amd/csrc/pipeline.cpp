@@ -396,6 +396,13 @@ struct mfsr_burst {
     const float* localToneGrid;
     std::vector<uint64_t> toneStats;
     std::vector<float> toneGrid;
+    // the finish chain (mfsr_burst_set_finish_chain): denoise, sharpen and local tone in one launch, to any
+    // format; never installed together with sharpenOn, denoiseOn or localToneOn
+    bool chainOn;
+    mfsr_finish_chain chain;
+    const float* chainGrid;  // the caller's device memory, or null without the chain's local tone
+    int chainReach;          // R_d + R_s of the installed chain
+    int chainedFinishes;     // launches of mfsr_finishChain since mfsr_burst_begin (mfsr_burst_debug_chained)
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -649,6 +656,10 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->denoisedFinishes = 0;
     b->localToneOn = false;
     b->localToneGrid = nullptr;
+    b->chainOn = false;
+    b->chainGrid = nullptr;
+    b->chainReach = 0;
+    b->chainedFinishes = 0;
     b->robustGroupLaunches = 0;
     b->finishOut16 = nullptr;
     b->finishTaken = false;
@@ -2034,7 +2045,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     MFSR_REQUIRE(b && imgOut && totalWeights);
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = b->denoisedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = 0;
     b->robustGroupLaunches = 0;
     b->fusedFinishes = 0;
     b->burstLaunches = b->burstGroups = 0;
@@ -2068,8 +2079,8 @@ static size_t out_image_bytes(const mfsr_burst* b)
 }
 
 // A finish with a reach: a stencil on the value the finish holds -- the sharpened (§2.20) or the denoised (§2.24) finish, never
-// both -- reads R rows beyond the rows it writes.
-static bool stencil_on(const mfsr_burst* b) { return b->sharpenOn || b->denoiseOn; }
+// both, or a chain (§2.26) with one of those stages or both -- reads R rows beyond the rows it writes.
+static bool stencil_on(const mfsr_burst* b) { return b->sharpenOn || b->denoiseOn || (b->chainOn && b->chainReach > 0); }
 
 // Rows [r0, r0 + rows) of the burst's accumulators (of its window's, when one is set) as a finish launch or a statistics pass
 // takes them; imgOut and totalWeights are the whole images.
@@ -2113,6 +2124,15 @@ static int finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_floa
     mfsr_float3* outF = outImg ? (mfsr_float3*)((char*)outImg + v.off) : nullptr;
     char* outQ = out ? (char*)out + (size_t)r0 * rowBytes : nullptr;
     const mfsr_render* render = b->renderOn ? &b->render : nullptr;  // (none: the stencil entries render plainly themselves)
+    // A chain (§2.26) takes every finish of the burst, whatever the format: the setters keep it apart from the three below.
+    if (b->chainOn) {
+        const bool yuv = yuv_on(b);
+        if (yuv) MFSR_REQUIRE((v.w & 1) == 0 && (out_h(b) & 1) == 0 && (r0 & 1) == 0 && (rows & 1) == 0);
+        char* uv = yuv && out ? (char*)out + ((size_t)out_h(b) + (size_t)(r0 / 2)) * rowBytes : nullptr;
+        b->chainedFinishes++;
+        return mfsr_finishChain(FINISH_SOURCE(b, v), outF, v.pitch, outQ, rowBytes, uv, rowBytes, render, v.w, rows, c.weightThreshold,
+                                c.applyGamma, FINISH_PLACE(b, v), &b->chain, b->chainGrid, rowsAbove, rowsBelow, stream);
+    }
     // Which launch: denoised, sharpened, two-plane, local tone, rendered, plain.  The setters (mfsr_burst_set_sharpen, _denoise,
     // _render, _local_tone: whichever comes second is refused) leave at most one of the first four on: never two stencils, no
     // stencil with a two-plane format or with local tone, no local tone with a two-plane format -- and none with a host burst
@@ -2148,7 +2168,7 @@ static int finish_rows(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_floa
 // rows of the output above / below [r0, r0 + rows) that a stencil finish of those rows reads
 static void stencil_reach(const mfsr_burst* b, int r0, int rows, int* above, int* below)
 {
-    const int R = b->denoiseOn ? b->denoise.radius : b->sharpen.radius, rest = out_h(b) - r0 - rows;
+    const int R = b->chainOn ? b->chainReach : (b->denoiseOn ? b->denoise.radius : b->sharpen.radius), rest = out_h(b) - r0 - rows;
     *above = R < r0 ? R : r0;
     *below = R < rest ? R : rest;
 }
@@ -2166,6 +2186,7 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
     MFSR_REQUIRE(!(on && yuv_on(b)));  // the sharpen tile kernel renders single rows: no two-plane output
     MFSR_REQUIRE(!(on && b->denoiseOn));  // one stencil per finish: whichever setter comes second is refused
     MFSR_REQUIRE(!(on && b->localToneOn));  // the local-tone finish is pointwise: no stencil
+    MFSR_REQUIRE(!(on && b->chainOn));      // a chain is installed: its own sharpen stage is the way
     b->sharpen = *sharpen;
     b->sharpenOn = on;
     return MFSR_OK;
@@ -2184,6 +2205,7 @@ extern "C" int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise
     MFSR_REQUIRE(!(on && yuv_on(b)));     // the denoise tile kernel renders single rows, as the sharpen one
     MFSR_REQUIRE(!(on && b->sharpenOn));  // one stencil per finish
     MFSR_REQUIRE(!(on && b->localToneOn));  // (as mfsr_burst_set_sharpen)
+    MFSR_REQUIRE(!(on && b->chainOn));      // (likewise)
     b->denoise = *denoise;
     b->denoiseOn = on;
     return MFSR_OK;
@@ -2193,6 +2215,36 @@ extern "C" int mfsr_burst_debug_denoised(const mfsr_burst* b, int* finishes)
 {
     MFSR_REQUIRE(b && finishes);
     *finishes = b->denoisedFinishes;
+    return MFSR_OK;
+}
+
+// ---- the finish chain -------------------------------------------------------------------------------
+extern "C" int mfsr_burst_set_finish_chain(mfsr_burst* b, const mfsr_finish_chain* chain, const float* gridDev)
+{
+    MFSR_REQUIRE(b != nullptr);
+    MFSR_REQUIRE(burst_idle(b));  // between bursts only
+    int reach = 0;
+    if (chain) TRY(mfsr_finish_chain_reach(chain, &reach));  // (validates)
+    if (!chain || (reach == 0 && !chain->useLocalTone)) {    // every stage off: no chain
+        b->chainOn = false;
+        b->chainGrid = nullptr;
+        b->chainReach = 0;
+        return MFSR_OK;
+    }
+    MFSR_REQUIRE(!b->sharpenOn && !b->denoiseOn && !b->localToneOn);  // one way to each stage: the chain's, or the setter's
+    MFSR_REQUIRE((gridDev != nullptr) == (chain->useLocalTone != 0) && ((uintptr_t)gridDev & 3) == 0);
+    MFSR_REQUIRE(!(chain->useLocalTone && b->cfg.uploadRing));  // a host burst finishes band by band: no grid can be measured first
+    b->chain = *chain;
+    b->chainGrid = gridDev;
+    b->chainReach = reach;
+    b->chainOn = true;
+    return MFSR_OK;
+}
+
+extern "C" int mfsr_burst_debug_chained(const mfsr_burst* b, int* finishes)
+{
+    MFSR_REQUIRE(b && finishes);
+    *finishes = b->chainedFinishes;
     return MFSR_OK;
 }
 
@@ -2219,7 +2271,8 @@ extern "C" int mfsr_burst_set_render(mfsr_burst* b, const mfsr_render* render)
         return MFSR_OK;
     }
     TRY(mfsr_render_validate(render));
-    MFSR_REQUIRE(!(stencil_on(b) && yuv_format(render->format)));  // (as mfsr_burst_set_sharpen / _denoise: whichever comes second)
+    // (as mfsr_burst_set_sharpen / _denoise: whichever comes second; a chain, §2.26, stores the two-plane formats itself)
+    MFSR_REQUIRE(!((b->sharpenOn || b->denoiseOn) && yuv_format(render->format)));
     MFSR_REQUIRE(!(b->localToneOn && yuv_format(render->format)));  // (mfsr_burst_set_local_tone likewise)
     b->render = *render;
     b->renderOn = true;
@@ -2344,6 +2397,7 @@ extern "C" int mfsr_burst_set_local_tone(mfsr_burst* b, const mfsr_local_tone* l
     MFSR_REQUIRE(gridDev != nullptr && ((uintptr_t)gridDev & 3) == 0);
     MFSR_REQUIRE(!b->cfg.uploadRing);  // a host burst finishes band by band, before its accumulators are complete
     MFSR_REQUIRE(!stencil_on(b));      // whichever setter comes second is refused
+    MFSR_REQUIRE(!b->chainOn);         // (a chain, §2.26, takes its grid with its own setter)
     MFSR_REQUIRE(!yuv_on(b));          // single-plane formats only
     b->localTone = *lt;
     b->localToneGrid = gridDev;
@@ -2357,7 +2411,7 @@ extern "C" int mfsr_burst_local_tone(mfsr_burst* b, const mfsr_float3* imgOut, c
 {
     MFSR_REQUIRE(b && imgOut && totalWeights && statsDev && gridDev && res);
     MFSR_REQUIRE(b->haveRef && ((uintptr_t)statsDev & 7) == 0 && ((uintptr_t)gridDev & 3) == 0);
-    MFSR_REQUIRE(!b->cfg.uploadRing && !stencil_on(b) && !yuv_on(b));  // (before any work: what mfsr_burst_set_local_tone refuses)
+    MFSR_REQUIRE(!b->cfg.uploadRing && !stencil_on(b) && !yuv_on(b) && !b->chainOn);  // (before any work: what mfsr_burst_set_local_tone refuses)
     const Layout& L = b->L;
     mfsr_local_tone lt;
     if (ltIn)
@@ -2403,7 +2457,7 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     // after the burst launch, which then must not finish).  drain_waiting decides the rest (the entry's own refusals).
     b->finishTaken = false;
     b->finishOut16 = nullptr;
-    if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->localToneOn && !b->win.on && out16 && !outImg &&
+    if (finish_fuse_enabled() && c.fused && !stencil_on(b) && !b->renderOn && !b->localToneOn && !b->chainOn && !b->win.on && out16 && !outImg &&
         !c.applyGamma &&
         b->nHold >= 2 && b->pend.n == 0 && !b->heldHas && b->hold[0].imgOut == imgOut && b->hold[0].totalWeights == totalWeights)
         b->finishOut16 = out16;
@@ -2418,7 +2472,7 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     // chain's in/out image, and the value the fused finish holds before its gamma is bit for bit the chain's resampleFloat3 +
     // ApplyWeighting (tests/test_parity_kernels.py::test_finishFused_equals_chain), so the unfused burst's sharpened finish is
     // this launch as well: no second HR float image.  The local-tone finish (§2.25) likewise.
-    if (c.fused || stencil_on(b) || b->localToneOn) return finish_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
+    if (c.fused || stencil_on(b) || b->localToneOn || b->chainOn) return finish_rows(b, imgOut, totalWeights, outImg, out16, 0, out_h(b), 0, 0, stream);
     // the unfused chain: the reference's own sequence, with the float image as its in/out buffer
     const int pitch = 12 * out_w(b);
     MFSR_REQUIRE(outImg != nullptr);
@@ -2736,7 +2790,7 @@ extern "C" int mfsr_burst_finish_host(mfsr_burst* b, const mfsr_float3* imgOut, 
     // bands of output rows (window rows when a window is set: y0 is a multiple of 16, so are the bands' HR rows)
     const int tileRows = (oH + 15) / 16;
     if (nBands > tileRows) nBands = tileRows;
-    // A band of a stencil finish reads R rows of its neighbours (sharpened: R <= 4, denoised: R <= 3): band i - 1 is finished and
+    // A band of a stencil finish reads R rows of its neighbours (sharpened: R <= 4, denoised: R <= 3, a chain: R <= 7): band i - 1 is finished and
     // downloaded after band i has been fused (every band but the last is a multiple of 16 rows), the last one after the loop.
     // lagR0 < 0: no band waits.
     int lagI = -1, lagR0 = -1, lagR1 = -1;
@@ -3131,7 +3185,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     // a new burst on this handle (what mfsr_burst_begin resets; no accumulators: nothing is fused)
     TRY(flush_pending(b, stream));
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = b->denoisedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = 0;
     b->robustGroupLaunches = 0;
     b->fusedFinishes = 0;
     TRY(mfsr_burst_set_reference(b, frames[reference], stream));
@@ -3432,6 +3486,12 @@ extern "C" int mfsr_stream_set_sharpen(mfsr_stream* s, const mfsr_sharpen* sharp
 {
     MFSR_REQUIRE(s != nullptr);
     return mfsr_burst_set_sharpen(s->b, sharpen);  // every output's finish sharpens
+}
+
+extern "C" int mfsr_stream_set_finish_chain(mfsr_stream* s, const mfsr_finish_chain* chain, const float* gridDev)
+{
+    MFSR_REQUIRE(s != nullptr);
+    return mfsr_burst_set_finish_chain(s->b, chain, gridDev);  // every output's finish runs the chain
 }
 
 extern "C" int mfsr_stream_set_denoise(mfsr_stream* s, const mfsr_denoise* denoise)

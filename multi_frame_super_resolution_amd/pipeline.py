@@ -1007,6 +1007,82 @@ def local_tone_image(img: torch.Tensor, grid: torch.Tensor, lt: capi.LocalTone, 
     return (out, fl) if want_float else out
 
 
+# ---- the finish chain (include/mfsr.h, mfsr_finish_chain) --------------------------------------------
+def _chain_struct(full_w: int, full_h: int, denoise: Optional[dict], sharpen: Optional[dict], local_tone, device,
+                  alpha: float = 0.0, beta: float = 0.0):
+    """(capi.FinishChain or None when every stage is off, the device tensor of the grid or None, reach) of the arguments of
+    ``BurstPipeline.set_finish_chain``.  The stages that are off hold valid descriptions that are off (a zero radius)."""
+    c = capi.FinishChain()
+    den = None
+    if denoise is not None:
+        kw = dict(denoise)
+        kw["alpha"] = alpha if kw.get("alpha") is None else kw["alpha"]
+        kw["beta"] = beta if kw.get("beta") is None else kw["beta"]
+        den = _denoise_struct(**kw)
+    if den is None:
+        den = denoise_defaults(0.0, 0.0)
+        den.radius = 0
+    c.denoise = den
+    sh = None if sharpen is None else _sharpen_struct(**sharpen)
+    if sh is not None:
+        c.sharpen = sh
+    grid = None
+    if local_tone is not None:
+        lt, g = local_tone
+        gx, gy, gz = local_tone_grid(full_w, full_h, lt)
+        grid = torch.as_tensor(g).to(device=device, dtype=torch.float32).contiguous()
+        if grid.numel() != gx * gy * gz:
+            raise ValueError(f"local_tone: a grid of {gy} x {gx} x {gz} floats")
+        c.localTone, c.useLocalTone = lt, 1
+    else:
+        c.localTone = local_tone_defaults(full_w, full_h)
+    reach = ctypes.c_int(-1)
+    if capi.lib().raw["mfsr_finish_chain_reach"](ctypes.byref(c), ctypes.byref(reach)) != 0:
+        raise ValueError("finish chain: an invalid denoise, sharpen or local-tone description")
+    if reach.value == 0 and grid is None:
+        return None, None, 0
+    return c, grid, reach.value
+
+
+def finish_chain_image(img: torch.Tensor, count: Optional[torch.Tensor] = None, denoise: Optional[dict] = None,
+                       sharpen: Optional[dict] = None, local_tone=None, format: Optional[int] = None, matrix=None, tone_lut=None,
+                       apply_gamma: bool = False, want_float: bool = True, yuv: int = 0, offset=(0, 0), full=None):
+    """The finish chain on an existing linear float image [h, w, 3] on the device (mfsr_chainImage): denoise, then sharpen, then
+    the local-tone gain, then the steps of ``render_image`` when ``format`` is given (any format, ``capi.OUT_NV12`` /
+    ``OUT_P010`` with the colour description ``yuv`` included), in one launch.  ``denoise`` / ``sharpen``: dicts of the keyword
+    arguments of ``denoise_image`` / ``sharpen_image``'s descriptions (strength, radius, gain, alpha, beta, fade; amount, sigma,
+    radius, threshold, taps); ``local_tone``: a ``(capi.LocalTone, grid)`` pair; None = that stage is off, and one stage at
+    least must be on.  ``count`` as for ``denoise_image``.  ``offset`` / ``full`` as for ``local_tone_image``.  Returns the float
+    image, or with ``format`` the tensor typed for it (and with ``want_float`` the pair (integers, float image))."""
+    if not _dense_f3(img):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    if count is not None and not (_dense_f3(count) and count.shape == img.shape and count.device == img.device):
+        raise ValueError("count: a float32 device tensor of img's shape with dense pixels")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    fw, fh = (w, h) if full is None else (int(full[0]), int(full[1]))
+    with torch.cuda.device(img.device):
+        c, grid, _ = _chain_struct(fw, fh, denoise, sharpen, local_tone, img.device)
+        if c is None:
+            raise ValueError("finish_chain_image: one stage at least must be on")
+        r, lut, out = None, None, None
+        if format is not None:
+            r, lut = _render_struct(format, matrix, tone_lut, img.device, yuv)
+            out = _render_buffer(format, h, w, img.device)
+        two = format in capi.YUV_FORMATS
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if (want_float or out is None) else None
+        rb = 0 if out is None else render_row_bytes(format, w)
+        capi.lib().chainImage(img.data_ptr(), img.stride(0) * 4, None if count is None else count.data_ptr(),
+                              0 if count is None else count.stride(0) * 4, None if fl is None else fl.data_ptr(), 12 * w,
+                              None if out is None else out.data_ptr(), rb, out.data_ptr() + rb * h if two else None, rb if two else 0,
+                              w, h, None if r is None else ctypes.byref(r), 1 if apply_gamma else 0, ctypes.byref(c),
+                              None if grid is None else grid.data_ptr(), int(offset[0]), int(offset[1]), fw, fh,
+                              torch.cuda.current_stream().cuda_stream)
+        del lut, grid
+    if out is None:
+        return fl
+    return (out, fl) if want_float else out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -1022,6 +1098,8 @@ class BurstPipeline:
         self.cfg = cfg
         self.window = _Window(cfg, window)
         self._sharpen_on = self._denoise_on = False   # a stencil in the finish (set_sharpen, set_denoise) grows the window
+        self._chain_reach = 0           # ... and so does a chain with a stencil stage (set_finish_chain)
+        self._chain = self._chain_grid = None
         self._local_tone = None         # the description of set_local_tone; its grid and table live as long as it is installed
         self.local_tone_result = None   # capi.LocalToneResult of the last measurement
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -1211,7 +1289,7 @@ class BurstPipeline:
 
     def _grow_window(self):
         """A stencil in the finish (sharpen, denoise): the aligned window grows by one 16-pixel ring, or shrinks back."""
-        if self.window.grow(WINDOW_GRID if (self._sharpen_on or self._denoise_on) else 0):
+        if self.window.grow(WINDOW_GRID if (self._sharpen_on or self._denoise_on or self._chain_reach > 0) else 0):
             self.L.burst_set_window(self._h, *self.window.aligned)
             out_h, out_w = self.window.aligned[3], self.window.aligned[2]
             self._img_out = torch.zeros(out_h, out_w, 3, dtype=torch.float32, device=self.device)
@@ -1236,6 +1314,31 @@ class BurstPipeline:
             self.L.burst_set_denoise(self._h, None if d is None else ctypes.byref(d))
             self._denoise_on = on
             self._grow_window()
+
+    def set_finish_chain(self, denoise: Optional[dict] = None, sharpen: Optional[dict] = None, local_tone=None):
+        """The finish chain (mfsr_burst_set_finish_chain): denoise, then sharpen, then the local-tone
+        gain, then matrix, tone and the store of ``set_render``'s format -- ``capi.OUT_NV12`` / ``OUT_P010`` included -- in the
+        finish's one launch.  ``denoise`` / ``sharpen``: dicts of the keyword arguments of ``set_denoise`` / ``set_sharpen``
+        (alpha / beta default to cfg's); ``local_tone``: a ``(capi.LocalTone, grid)`` pair, the grid [GY, GX, GZ] of the full HR
+        frame as ``local_tone_fit`` returns it (measured on the plain value, before denoise and sharpen).  All three None turns
+        the chain off.  Between bursts only; not while ``set_sharpen``, ``set_denoise`` or ``set_local_tone`` is on, which are
+        refused in turn while a chain is installed.  With a zoom window and a stencil stage the aligned window grows by one
+        16-pixel ring (the reach is at most 7), as for ``set_sharpen``."""
+        with torch.cuda.device(self.device):
+            c, grid, reach = _chain_struct(self.hr_w, self.hr_h, denoise, sharpen, local_tone, self.device, self.cfg.alpha,
+                                           self.cfg.beta)
+            if grid is not None:
+                torch.cuda.current_stream().synchronize()   # (the library may read the grid on another stream than the copy's)
+            self.L.burst_set_finish_chain(self._h, None if c is None else ctypes.byref(c), None if grid is None else grid.data_ptr())
+            self._chain, self._chain_grid, self._chain_reach = c, grid, reach   # the grid is alive as long as it is installed
+            self._grow_window()
+
+    def chained_finishes(self) -> int:
+        """Launches of mfsr_finishChain since ``begin_burst`` (mfsr_burst_debug_chained): 1 for a resident burst, one per band
+        for a host burst, 0 without a chain."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_chained(self._h, ctypes.byref(n))
+        return n.value
 
     def denoised_finishes(self) -> int:
         """Launches of mfsr_finishDenoised since ``begin_burst`` (mfsr_burst_debug_denoised): 1 for a resident burst, one per
@@ -1637,8 +1740,10 @@ class FrameStream:
 
     def __init__(self, cfg: capi.Config, radius: int = 1, device: Optional[torch.device] = None, host_frames: bool = False,
                  window: Optional[Sequence[int]] = None, render: Optional[dict] = None, sharpen: Optional[dict] = None,
-                 denoise: Optional[dict] = None):
-        """window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
+                 denoise: Optional[dict] = None, chain: Optional[dict] = None):
+        """chain: the keyword arguments of ``BurstPipeline.set_finish_chain`` (denoise, sharpen, local_tone): every output's
+        finish runs the chain; a window grows as for sharpen when the chain has a stencil stage.
+        window: every output is that HR rectangle (see BurstPipeline).  render: the keyword arguments of
         ``BurstPipeline.set_render`` (format, matrix, tone_lut, yuv): every output is rendered, typed for the format.  sharpen: the
         keyword arguments of ``BurstPipeline.set_sharpen``: every output is sharpened inside its finish; with a window the
         library works on the aligned window grown by one 16-pixel ring, as ``BurstPipeline`` does, so the rectangle asked for
@@ -1658,10 +1763,17 @@ class FrameStream:
             kw["alpha"] = cfg.alpha if kw.get("alpha") is None else kw["alpha"]
             kw["beta"] = cfg.beta if kw.get("beta") is None else kw["beta"]
             den = _denoise_struct(**kw)
-        if (sharp is not None and sharp.radius != 0 and sharp.amount != 0) or (
-                den is not None and den.radius != 0 and den.strength != 0):
-            self.window.grow(WINDOW_GRID)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        ch, self._chain_grid, reach = None, None, 0
+        if chain is not None:
+            with torch.cuda.device(self.device):
+                ch, self._chain_grid, reach = _chain_struct(cfg.width * cfg.scale, cfg.height * cfg.scale, chain.get("denoise"),
+                                                            chain.get("sharpen"), chain.get("local_tone"), self.device, cfg.alpha,
+                                                            cfg.beta)
+                torch.cuda.current_stream().synchronize()
+        if (sharp is not None and sharp.radius != 0 and sharp.amount != 0) or (
+                den is not None and den.radius != 0 and den.strength != 0) or reach > 0:
+            self.window.grow(WINDOW_GRID)
         nbytes = self.L.stream_workspace_bytes(ctypes.byref(cfg), radius)
         if nbytes == 0:
             raise ValueError("invalid mfsr_config / radius")
@@ -1687,6 +1799,9 @@ class FrameStream:
                 self.L.stream_set_sharpen(self._h, ctypes.byref(sharp))
             if den is not None:
                 self.L.stream_set_denoise(self._h, ctypes.byref(den))
+            if ch is not None:
+                self.L.stream_set_finish_chain(self._h, ctypes.byref(ch),
+                                               None if self._chain_grid is None else self._chain_grid.data_ptr())
 
     def close(self):
         if getattr(self, "_h", None):
