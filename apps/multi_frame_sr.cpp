@@ -39,6 +39,11 @@
 //   * MFSR_LOCAL_TONE="shadows[,highlights[,cell[,bins]]]" lifts the shadows of _sr_result locally inside the finish (a bilateral
 //     grid of gains measured on the merged image), with or without MFSR_CCM and MFSR_AUTO; it prints
 //     `local tone: cell C bins N pivot P gains LO .. HI` on stderr; not with MFSR_SHARPEN or MFSR_DENOISE; one GPU only.
+//   * MFSR_LENS="k1[,k2[,k3[,lateralR,lateralB]]]" and / or MFSR_OUT_SIZE="WxH" write _sr_result through the geometric finish
+//     (mfsr_burst_finish_geometry): resampled to W x H (default: the x2 size) with the radial
+//     distortion k1..k3 and the lateral magnifications of red and blue corrected (default: none), Catmull-Rom, with or without
+//     MFSR_CCM and MFSR_AUTO; _sr2_result stays the sharpenImg2 pass of the x2 image; not with MFSR_SHARPEN, MFSR_DENOISE or
+//     MFSR_LOCAL_TONE; one GPU only.
 //   * MFSR_AUTO=wb|tone|wb,tone measures white-balance gains and / or a tone table on the merged image and renders _sr_result
 //     with them, with or without MFSR_CCM and MFSR_SHARPEN; it prints `auto: gains R G B ... black K
 //     white W gamma G ...` to stderr; one GPU only.
@@ -470,7 +475,70 @@ int main(int argc, char** argv)
         fprintf(stderr, "MFSR_LOCAL_TONE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
     }
-    const bool rendered = ccm || sharpenOn || denoiseOn || autoOn || localToneOn;  // the 8-bit image comes out of the finish launch
+    // MFSR_LENS="k1[,k2[,k3[,lateralR,lateralB]]]" / MFSR_OUT_SIZE="WxH": _sr_result comes out of the geometric finish (DESIGN.md
+    // section 2.27) at W x H (default: the x2 size) with the lens profile's numbers as they are (default: none), Catmull-Rom.
+    // Either alone is allowed.  The description is checked by the library (mfsr_geometry_lens).
+    bool geometryOn = false;
+    mfsr_geometry geometry;
+    {
+        const int hrW0 = W * scale, hrH0 = H * scale;
+        int gw = hrW0, gh = hrH0;
+        double lensK[3] = {0.0, 0.0, 0.0}, lateral[2] = {1.0, 1.0};
+        if (const char* e = getenv("MFSR_OUT_SIZE")) {
+            char* end = nullptr;
+            const long w = strtol(e, &end, 10);
+            const bool okW = end != e && *end == 'x';
+            const char* p = end + 1;
+            const long h = okW ? strtol(p, &end, 10) : 0;
+            if (!okW || end == p || *end != '\0' || w < 1 || w > 32768 || h < 1 || h > 32768) {
+                fprintf(stderr, "MFSR_OUT_SIZE=%s: WxH expected, 1 <= W, H <= 32768\n", e);
+                return 1;
+            }
+            gw = (int)w;
+            gh = (int)h;
+            geometryOn = true;
+        }
+        if (const char* e = getenv("MFSR_LENS")) {
+            double v[5] = {0.0, 0.0, 0.0, 1.0, 1.0};
+            const char* p = e;
+            bool ok = true;
+            int n = 0;
+            for (; ok; n++) {
+                char* end = nullptr;
+                v[n] = strtod(p, &end);
+                ok = end != p && std::isfinite(v[n]);
+                p = end;
+                if (!ok || *p == '\0') break;
+                ok = *p == ',' && n < 4;
+                p++;
+            }
+            if (!ok || *p != '\0' || n == 3) {  // (n + 1 values: four would be one lateral magnification without the other)
+                fprintf(stderr, "MFSR_LENS=%s: k1[,k2[,k3[,lateralR,lateralB]]] expected: |k| <= 4, |lateral - 1| <= 0.25\n", e);
+                return 1;
+            }
+            for (int i = 0; i < 3; i++) lensK[i] = v[i];
+            lateral[0] = v[3];
+            lateral[1] = v[4];
+            geometryOn = true;
+        }
+        if (geometryOn && mfsr_geometry_lens(hrW0, hrH0, gw, gh, 1.0, lensK, lateral, MFSR_GEO_CUBIC, &geometry) != MFSR_OK) {
+            fprintf(stderr, "MFSR_LENS / MFSR_OUT_SIZE: |k| <= 4, |lateral - 1| <= 0.25 and an output between 1/8 and 8 times the x%d size "
+                            "expected\n", scale);
+            return 1;
+        }
+    }
+    if (geometryOn && (sharpenOn || denoiseOn || localToneOn)) {
+        fprintf(stderr, "MFSR_LENS / MFSR_OUT_SIZE is not supported with %s (the geometric finish knows no other stage: DESIGN.md section "
+                        "2.27)\n", sharpenOn ? "MFSR_SHARPEN" : (denoiseOn ? "MFSR_DENOISE" : "MFSR_LOCAL_TONE"));
+        return 1;
+    }
+    if (geometryOn && gpus > 1) {
+        fprintf(stderr, "MFSR_LENS / MFSR_OUT_SIZE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
+        return 1;
+    }
+    if (geometryOn) render.format = MFSR_OUT_RGB8;
+    // the 8-bit image comes out of the finish launch
+    const bool rendered = ccm || sharpenOn || denoiseOn || autoOn || localToneOn || geometryOn;
     if (denoiseOn && gpus > 1) {
         fprintf(stderr, "MFSR_DENOISE is not supported with MFSR_GPUS > 1 (the multi-GPU burst gathers 16-bit camera RGB)\n");
         return 1;
@@ -710,6 +778,8 @@ int main(int argc, char** argv)
 
     HIP_OK(hipMalloc((void**)&d8, (size_t)hrW * hrH * 3));
     HIP_OK(hipMalloc((void**)&d8s, (size_t)hrW * hrH * 3));
+    uint8_t* d8g = nullptr;  // MFSR_LENS / MFSR_OUT_SIZE: the geometric finish's 8-bit image
+    if (geometryOn) HIP_OK(hipMalloc((void**)&d8g, (size_t)geometry.outW * geometry.outH * 3));
     if (rendered) MFSR_OK_OR_DIE(mfsr_burst_set_render(b, &render));
     if (sharpenOn) MFSR_OK_OR_DIE(mfsr_burst_set_sharpen(b, &sharpen));
     if (denoiseOn) {
@@ -773,6 +843,9 @@ int main(int argc, char** argv)
         else
             MFSR_OK_OR_DIE(mfsr_burst_finish(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, (mfsr_float3*)outF,
                                              nullptr, nullptr));
+        if (geometryOn)  // _sr_result: one more launch on the same accumulators, with the same render description
+            MFSR_OK_OR_DIE(mfsr_burst_finish_geometry(b, (const mfsr_float3*)imgOut, (const mfsr_float3*)weights, &geometry, nullptr, 0,
+                                                      d8g, 3 * geometry.outW, nullptr));
     }
     HIP_OK(hipDeviceSynchronize());
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -791,7 +864,13 @@ int main(int argc, char** argv)
     MFSR_OK_OR_DIE(mfsr_sharpenImg2(d8, d8s, hrH, hrW, 3, hrW * 3, hrW * 3, nullptr));
     HIP_OK(hipMemcpy(h8.data(), d8, h8.size(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(h8s.data(), d8s, h8s.size(), hipMemcpyDeviceToHost));
-    if (!write_png(inputName + "_" + optFlowName + "_sr_result.png", h8.data(), hrW, hrH, 3) ||   // :207
+    std::vector<uint8_t> h8g;
+    if (geometryOn) {
+        h8g.resize((size_t)geometry.outW * geometry.outH * 3);
+        HIP_OK(hipMemcpy(h8g.data(), d8g, h8g.size(), hipMemcpyDeviceToHost));
+    }
+    if (!(geometryOn ? write_png(inputName + "_" + optFlowName + "_sr_result.png", h8g.data(), geometry.outW, geometry.outH, 3)
+                     : write_png(inputName + "_" + optFlowName + "_sr_result.png", h8.data(), hrW, hrH, 3)) ||  // :207
         !write_png(inputName + "_" + optFlowName + "_sr2_result.png", h8s.data(), hrW, hrH, 3)) {  // :209
         fprintf(stderr, "cannot write result PNGs\n");
         return 1;

@@ -1683,6 +1683,94 @@ int mfsr_stream_set_finish_chain(mfsr_stream* s, const mfsr_finish_chain* chain,
 /* *finishes = the launches of mfsr_finishChain this burst has made since mfsr_burst_begin (as mfsr_burst_debug_denoised) */
 int mfsr_burst_debug_chained(const mfsr_burst* b, int* finishes);
 
+/* ---- the geometric finish: any output size, lens distortion and lateral chromatic aberration as ONE resample of the value the
+ * finish holds.  Off unless asked for: its own entry points; every other entry point produces the bits
+ * and the launches it always did.  All arithmetic is float32 with one rounding per operation and no contraction, in exactly the
+ * order written.  For pixel (X, Y) of the FULL outW x outH output (a launch on a sub-rectangle adds its colOffset / rowOffset
+ * first, so a crop is the crop bit for bit) of a source of srcW x srcH pixels:
+ *   dx  = (((float)X + 0.5f) - ocx) * stepX          dy likewise with ocy, stepY
+ *   rho = (dx*dx + dy*dy) * rnorm2
+ *   per channel c, with (k0, k1, k2, k3) = k[c]:
+ *     m = ((k3*rho + k2)*rho + k1)*rho + k0
+ *     u = (scx + dx*m) - 0.5f ;  u = fminf(fmaxf(u, -1.0f), (float)srcW)      v likewise with scy, dy, srcH
+ *     ix = (int)floorf(u) ;  fx = u - (float)ix                                iy, fy likewise
+ *     s(i, j) = channel c of p at (clamp(i, 0, srcW-1), clamp(j, 0, srcH-1)),  NaN -> 0
+ *     bilinear: h_j = s(ix, j) + (s(ix+1, j) - s(ix, j)) * fx,  j = iy, iy+1 ;  o = h_iy + (h_iy+1 - h_iy) * fy
+ *     cubic (Catmull-Rom), the weights of f = fx (w) and of f = fy (wy):
+ *               w0 = ((-0.5f*f + 1.0f)*f - 0.5f)*f     w1 = ((1.5f*f - 2.5f)*f)*f + 1.0f
+ *               w2 = ((-1.5f*f + 2.0f)*f + 0.5f)*f     w3 = ((0.5f*f - 0.5f)*f)*f
+ *               h_j = (w0*s(ix-1,j) + w1*s(ix,j)) + (w2*s(ix+1,j) + w3*s(ix+2,j)),  j = iy-1 .. iy+2
+ *               o = (wy0*h_(iy-1) + wy1*h_iy) + (wy2*h_(iy+1) + wy3*h_(iy+2))
+ * p is the value section 2.19 calls p (after ApplyWeighting with the fallback, before gamma) at the SOURCE pixel's own
+ * coordinates in the full HR frame: the fallback resample of a low-weight source pixel is the one every other finish computes.
+ * o takes the place of p in steps 1-3 of the rendered output (matrix, tone, quantise); with no render description the steps are
+ * those of {MFSR_OUT_RGB16, no matrix, no table}.  The mapping has no square root and no division: the polynomial is in rho =
+ * r^2.  The coefficients are those of the usual FORWARD lens model (ideal -> distorted), which is also the direction a correcting
+ * resample needs (output -> source): a lens profile's numbers are passed as they are.  Borders replicate.  There is NO
+ * anti-alias prefilter: steps above 1 alias as any plain bilinear / bicubic does.  An inf among the taps is not cleaned (a
+ * weight of 0 times inf is NaN, as in the sharpen); the quantiser maps NaN to 0 and clamps inf as ever.
+ * mfsr_geometry_validate refuses (MFSR_E_INVALID, host only): extents outside 1 .. 32768, an unknown filter, any non-finite
+ * float, steps outside [1/8, 8], rnorm2 <= 0 or > 4 (a normalising radius under half a pixel), |k0 - 1| > 0.25, |k1|, |k2|,
+ * |k3| > 4, a centre outside [-extent, 2 extent] (ocx against outW, scx against srcW <= 32768: the source extent is known at
+ * the launch, which checks scx / scy; validate alone bounds them by [-32768, 65536]), non-zero reserved.
+ * With these bounds no NaN and no integer overflow can arise in the mapping: |X + 0.5 - ocx| <= 2^16, so |dx| <= 2^19 and
+ * rho <= 2^39 * 4 = 2^41; |m| <= 4 * 2^123 + 4 * 2^82 + 4 * 2^41 + 1.25 < 2^126 is finite, so dx * m is never 0 * inf; it may
+ * overflow to +-inf for such extreme values, scx + (+-inf) and the subtraction keep it, and the clamp maps it to srcW or -1 (a
+ * border pixel).  After the clamp u lies in [-1, srcW] with srcW <= 32768: ix lies in [-1, srcW], u - (float)ix is exact and
+ * lies in [0, 1).
+ * mfsr_geometry_lens (host only) fills a description from a lens profile, computing in double and rounding once: centres at
+ * the two image centres (dstW/2, dstH/2, srcW/2, srcH/2; outW x outH = dstW x dstH), stepX = stepY = min(srcW/dstW,
+ * srcH/dstH) / zoom, rnorm2 = 1 / ((srcW/2)^2 + (srcH/2)^2), k1 .. k3 = k[0 .. 2] for the three channels, k0 = (lateral[0], 1, lateral[1]); the result is
+ * validated.  mfsr_geometry_defaults: the identity (outW x outH = srcW x srcH, step 1, k0 = 1, cubic).
+ * mfsr_geometry_tile: the output tile one workgroup owns and the capacity of its LDS stage in source pixels (see DESIGN.md
+ * section 5: a workgroup whose exact box of source taps fits the stage evaluates p once per source pixel into LDS; one whose box
+ * does not reads every tap from memory and produces the same bits; MFSR_GEOMETRY_STAGE=0, read at every call, forces the latter
+ * everywhere). */
+#define MFSR_GEO_BILINEAR 0
+#define MFSR_GEO_CUBIC 1
+typedef struct {
+    int32_t outW, outH;   /* the full output extent, 1 .. 32768 each */
+    int32_t filter;       /* MFSR_GEO_BILINEAR or MFSR_GEO_CUBIC */
+    float ocx, ocy;       /* optical centre in output coordinates (pixel X covers [X, X+1)) */
+    float scx, scy;       /* optical centre in source (HR accumulator) coordinates */
+    float stepX, stepY;   /* source pixels per output pixel at the centre, [1/8, 8] */
+    float rnorm2;         /* 1 / (normalising radius in source pixels)^2, (0, 4] */
+    float k[3][4];        /* per channel: k0 (lateral magnification; 1 for green), k1, k2, k3 */
+    int32_t reserved[10]; /* zeros */
+} mfsr_geometry;
+int mfsr_geometry_validate(const mfsr_geometry* geometry);
+int mfsr_geometry_defaults(int srcW, int srcH, mfsr_geometry* out);
+int mfsr_geometry_lens(int srcW, int srcH, int dstW, int dstH, double zoom, const double k[3], const double lateral[2], int filter,
+                       mfsr_geometry* out);
+int mfsr_geometry_tile(int* tileW, int* tileH, int* stageW, int* stageH);
+/* mfsr_finishGeometry: the arguments of mfsr_finishRendered for the accumulator pair, the fallback, u0 .. v1, threshold and
+ * applyGamma; finalImg / weight are the FULL HR frame of srcW x srcH pixels.  The launch writes the rectangle (colOffset,
+ * rowOffset, w, h) of the outW x outH output to outImg (the float image the integers quantise) and / or out (the format's
+ * integers), whose pixel (0, 0) is the rectangle's first.  render may be NULL.  Not in place: no output may overlap the
+ * accumulators or the weights.  mfsr_geometryImage: the same on an existing float image (s = NaN-cleaned `in`); no output may
+ * overlap `in`.  Both check every argument on the host before any device call (MFSR_E_INVALID), allocate nothing, are
+ * asynchronous on `stream` (capturable) and refuse the two-plane formats.  The other stages combine with it at the image level,
+ * in this order: mfsr_finishChain (or mfsr_finishDenoised / mfsr_finishSharpened) to a float image with {no matrix, no table},
+ * then mfsr_geometryImage with the real render description. */
+int mfsr_finishGeometry(const mfsr_float3* finalImg, const mfsr_float3* weight, int imgRowBytes, const mfsr_float3* fallback,
+                        int fbRowBytes, int fbW, int fbH, float u0, float u1, float v0, float v1, int srcW, int srcH,
+                        mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes, const mfsr_render* render,
+                        const mfsr_geometry* geometry, float threshold, int applyGamma, int colOffset, int rowOffset, int w, int h,
+                        mfsr_stream_t stream);
+int mfsr_geometryImage(const mfsr_float3* in, int inRowBytes, int srcW, int srcH, mfsr_float3* outImg, int outImgRowBytes, void* out,
+                       int outRowBytes, const mfsr_render* render, const mfsr_geometry* geometry, int applyGamma, int colOffset,
+                       int rowOffset, int w, int h, mfsr_stream_t stream);
+/* The geometric finish of a burst: fuses whatever is waiting, as mfsr_burst_finish does, then runs ONE mfsr_finishGeometry over
+ * the whole outW x outH output with the burst's render description (or plainly), cfg.weightThreshold and cfg.applyGamma.  outImg
+ * (12 * outW bytes a row at least) and / or out (the format's rows; uint16_t RGB without a render description).  An explicit
+ * call, not a mode: the burst's own output extent and every other finish stay as they are (mfsr_burst_finish may follow and
+ * gives what it always gave), and the finish inside the burst launch is never taken by it.  Refused (MFSR_E_INVALID, before any
+ * work; the burst stays usable): a burst with a window; an installed sharpen, denoise, local-tone or chain description; a
+ * two-plane render format.  mfsr_burst_debug_geometry: its launches since mfsr_burst_begin. */
+int mfsr_burst_finish_geometry(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights, const mfsr_geometry* geometry,
+                               mfsr_float3* outImg, int outImgRowBytes, void* out, int outRowBytes, mfsr_stream_t stream);
+int mfsr_burst_debug_geometry(const mfsr_burst* b, int* finishes);
+
 /* HIP-event timing of the warp+fuse (accumulate) launches made by add_frame on
  * the caller's stream: timing(b,1) starts a series, timing_read synchronises with
  * the events and returns the summed kernel milliseconds, the launch count and the

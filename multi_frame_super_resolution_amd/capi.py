@@ -207,6 +207,20 @@ class FinishChain(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 7)]
 
 
+# mfsr_geometry.filter (include/mfsr.h)
+GEO_BILINEAR, GEO_CUBIC = 0, 1
+
+
+class Geometry(ctypes.Structure):
+    """mfsr_geometry (include/mfsr.h): output size, lens distortion and lateral chromatic aberration of
+    a geometric finish.  ``k[c]`` = (k0, k1, k2, k3) of channel c."""
+
+    _fields_ = [("outW", ctypes.c_int32), ("outH", ctypes.c_int32), ("filter", ctypes.c_int32), ("ocx", ctypes.c_float),
+                ("ocy", ctypes.c_float), ("scx", ctypes.c_float), ("scy", ctypes.c_float), ("stepX", ctypes.c_float),
+                ("stepY", ctypes.c_float), ("rnorm2", ctypes.c_float), ("k", (ctypes.c_float * 4) * 3),
+                ("reserved", ctypes.c_int32 * 10)]
+
+
 _BY_VALUE = {
     "mfsr_float2": Float2, "mfsr_float3": Float3, "mfsr_float4": Float4, "mfsr_tex2d": Tex2D,
     "int": ctypes.c_int, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t,

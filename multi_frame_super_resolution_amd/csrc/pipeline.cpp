@@ -403,6 +403,7 @@ struct mfsr_burst {
     const float* chainGrid;  // the caller's device memory, or null without the chain's local tone
     int chainReach;          // R_d + R_s of the installed chain
     int chainedFinishes;     // launches of mfsr_finishChain since mfsr_burst_begin (mfsr_burst_debug_chained)
+    int geometryFinishes;    // launches of mfsr_finishGeometry since mfsr_burst_begin (mfsr_burst_debug_geometry)
     // a host burst captured into a graph (host_epoch): the capture the per-slot events above were recorded in (0 = none, the
     // eager launch sequence), and the event that forks the copy and the download stream off the caller's when that changes
     unsigned long long hostEpoch;
@@ -660,6 +661,7 @@ extern "C" int mfsr_burst_create(mfsr_burst** out, const mfsr_config* cfg, void*
     b->chainGrid = nullptr;
     b->chainReach = 0;
     b->chainedFinishes = 0;
+    b->geometryFinishes = 0;
     b->robustGroupLaunches = 0;
     b->finishOut16 = nullptr;
     b->finishTaken = false;
@@ -2045,7 +2047,7 @@ extern "C" int mfsr_burst_begin(mfsr_burst* b, mfsr_float3* imgOut, mfsr_float3*
     MFSR_REQUIRE(b && imgOut && totalWeights);
     TRY(flush_pending(b, stream));  // whatever was still waiting belongs to the previous burst
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = b->geometryFinishes = 0;
     b->robustGroupLaunches = 0;
     b->fusedFinishes = 0;
     b->burstLaunches = b->burstGroups = 0;
@@ -2489,6 +2491,37 @@ extern "C" int mfsr_burst_finish(mfsr_burst* b, const mfsr_float3* imgOut, const
     }
     if (c.applyGamma) TRY(mfsr_GammasRGB(outImg, L.hrW, L.hrH, pitch, stream));
     if (out16) TRY(mfsr_quantize(outImg, pitch, out16, nullptr, L.hrW, L.hrH, 65535.0f, stream));
+    return MFSR_OK;
+}
+
+// ---- the geometric finish: an explicit call beside mfsr_burst_finish, never a mode of it --------------------
+extern "C" int mfsr_burst_finish_geometry(mfsr_burst* b, const mfsr_float3* imgOut, const mfsr_float3* totalWeights,
+                                          const mfsr_geometry* geometry, mfsr_float3* outImg, int outImgRowBytes, void* out,
+                                          int outRowBytes, mfsr_stream_t stream)
+{
+    MFSR_REQUIRE(b && imgOut && totalWeights && geometry && (outImg || out));
+    MFSR_REQUIRE(b->haveRef);
+    // before any work: the launch reads the whole HR frame and knows none of the other stages
+    MFSR_REQUIRE(!b->win.on);
+    MFSR_REQUIRE(!b->sharpenOn && !b->denoiseOn && !b->localToneOn && !b->chainOn);
+    MFSR_REQUIRE(!yuv_on(b));
+    TRY(mfsr_geometry_validate(geometry));
+    // (finishOut16 stays null: the finish inside the burst launch is never taken here)
+    b->finishTaken = false;
+    b->finishOut16 = nullptr;
+    TRY(flush_pending(b, stream));
+    const mfsr_config& c = b->cfg;
+    const FinishView v = finish_view(b, imgOut, totalWeights, 0, out_h(b));
+    b->geometryFinishes++;
+    return mfsr_finishGeometry(FINISH_SOURCE(b, v), b->L.hrW, b->L.hrH, outImg, outImgRowBytes, out, outRowBytes,
+                               b->renderOn ? &b->render : nullptr, geometry, c.weightThreshold, c.applyGamma, 0, 0, geometry->outW,
+                               geometry->outH, stream);
+}
+
+extern "C" int mfsr_burst_debug_geometry(const mfsr_burst* b, int* finishes)
+{
+    MFSR_REQUIRE(b && finishes);
+    *finishes = b->geometryFinishes;
     return MFSR_OK;
 }
 
@@ -3185,7 +3218,7 @@ extern "C" int mfsr_burst_calibrate_noise_temporal(mfsr_burst* b, int nFrames, c
     // a new burst on this handle (what mfsr_burst_begin resets; no accumulators: nothing is fused)
     TRY(flush_pending(b, stream));
     memset(b->paths, 0, sizeof(b->paths));
-    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = 0;
+    b->sharpenedFinishes = b->denoisedFinishes = b->chainedFinishes = b->geometryFinishes = 0;
     b->robustGroupLaunches = 0;
     b->fusedFinishes = 0;
     TRY(mfsr_burst_set_reference(b, frames[reference], stream));

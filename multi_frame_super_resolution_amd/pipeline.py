@@ -1083,6 +1083,56 @@ def finish_chain_image(img: torch.Tensor, count: Optional[torch.Tensor] = None, 
     return (out, fl) if want_float else out
 
 
+# ---- the geometric finish (include/mfsr.h, mfsr_geometry) --------------------------------------------
+_GEO_FILTERS = {"bilinear": capi.GEO_BILINEAR, "cubic": capi.GEO_CUBIC}
+
+
+def lens_geometry(src_w: int, src_h: int, out_w: int, out_h: int, zoom: float = 1.0, distortion=(0, 0, 0), lateral=(1, 1),
+                  filter: str = "cubic") -> capi.Geometry:
+    """The description of a geometric finish from a lens profile (mfsr_geometry_lens; host arithmetic in double, rounded once):
+    an ``out_w`` x ``out_h`` output of a ``src_w`` x ``src_h`` source around the two image centres, step = min(src_w / out_w,
+    src_h / out_h) / ``zoom``, ``distortion`` = (k1, k2, k3) of the forward radial model in r^2 normalised by the source's half
+    diagonal, ``lateral`` = the magnifications of red and blue against green, ``filter`` = "bilinear" or "cubic" (Catmull-Rom)."""
+    if filter not in _GEO_FILTERS:
+        raise ValueError('filter: "bilinear" or "cubic"')
+    k = [float(v) for v in distortion]
+    lat = [float(v) for v in lateral]
+    if len(k) != 3 or len(lat) != 2:
+        raise ValueError("distortion: (k1, k2, k3); lateral: (red, blue)")
+    g = capi.Geometry()
+    if capi.lib().raw["mfsr_geometry_lens"](int(src_w), int(src_h), int(out_w), int(out_h), float(zoom), (ctypes.c_double * 3)(*k),
+                                            (ctypes.c_double * 2)(*lat), _GEO_FILTERS[filter], ctypes.byref(g)) != 0:
+        raise ValueError("lens_geometry: extents 1 .. 32768, step in [1/8, 8], |lateral - 1| <= 0.25, |k| <= 4, all finite")
+    return g
+
+
+def geometry_image(img: torch.Tensor, geometry: capi.Geometry, format: Optional[int] = None, matrix=None, tone_lut=None, rect=None,
+                   apply_gamma: bool = False, want_float: bool = True):
+    """The geometric finish on an existing linear float image [h, w, 3] on the device (mfsr_geometryImage): resample by
+    ``geometry`` (``lens_geometry``), then the steps of ``render_image`` when ``format`` is given (single-plane formats).
+    ``rect`` = (x, y, w, h): that rectangle of the geometry's output only (None: all of it), bit for bit the crop.  Returns the
+    float image, or with ``format`` the tensor typed for it (and with ``want_float`` the pair (integers, float image)).  This is
+    how the other stages combine with it: ``finish_chain_image`` (or a burst's float image) first, then this."""
+    if not _dense_f3(img):
+        raise ValueError("img: a float32 device tensor [h, w, 3] with dense pixels")
+    src_h, src_w = int(img.shape[0]), int(img.shape[1])
+    x, y, w, h = (0, 0, geometry.outW, geometry.outH) if rect is None else (int(v) for v in rect)
+    with torch.cuda.device(img.device):
+        r, lut, out = None, None, None
+        if format is not None:
+            r, lut = _render_struct(format, matrix, tone_lut, img.device)
+            out = _render_buffer(format, h, w, img.device)
+        fl = torch.empty(h, w, 3, dtype=torch.float32, device=img.device) if (want_float or out is None) else None
+        capi.lib().geometryImage(img.data_ptr(), img.stride(0) * 4, src_w, src_h, None if fl is None else fl.data_ptr(), 12 * w,
+                                 None if out is None else out.data_ptr(), 0 if out is None else render_row_bytes(format, w),
+                                 None if r is None else ctypes.byref(r), ctypes.byref(geometry), 1 if apply_gamma else 0, x, y, w, h,
+                                 torch.cuda.current_stream().cuda_stream)
+        del lut
+    if out is None:
+        return fl
+    return (out, fl) if want_float else out
+
+
 class BurstPipeline:
     """One burst context on one device (ctx-per-device, not thread-safe; the
     reference is single-device/single-stream, kernel.cu:45)."""
@@ -1338,6 +1388,36 @@ class BurstPipeline:
         for a host burst, 0 without a chain."""
         n = ctypes.c_int(-1)
         self.L.burst_debug_chained(self._h, ctypes.byref(n))
+        return n.value
+
+    def finish_geometry(self, geometry: capi.Geometry, want_float: bool = True, want_int: bool = True):
+        """(float image, integer image) of the burst through the geometric finish (mfsr_burst_finish_geometry; DESIGN.md section
+        2.27): tensors of the geometry's output extent, [outH, outW, 3] float32 and the tensor typed for ``set_render``'s format
+        (int16 RGB without one).  An explicit call beside ``finish``, which may follow and returns what it always did.  Refused
+        (capi.MfsrError) with a zoom window, with ``set_sharpen`` / ``set_denoise`` / ``set_local_tone`` / ``set_finish_chain``
+        on, and with a two-plane format; ``geometry_image`` on a chained float image is the way to combine them."""
+        if not (want_float or want_int):
+            raise ValueError("finish_geometry: one output at least")
+        w, h = int(geometry.outW), int(geometry.outH)
+        with torch.cuda.device(self.device):
+            fl = torch.empty(h, w, 3, dtype=torch.float32, device=self.device) if want_float else None
+            out = None
+            if want_int:
+                if self._fmt in capi.YUV_FORMATS:   # (no buffer for it; the library's refusal names the reason)
+                    out = torch.empty(1, dtype=torch.uint8, device=self.device)
+                else:
+                    out = _render_buffer(self._fmt, h, w, self.device)
+            rb = 0 if out is None or self._fmt in capi.YUV_FORMATS else render_row_bytes(self._fmt, w)
+            self.L.burst_finish_geometry(self._h, self._img_out.data_ptr(), self._total_weights.data_ptr(), ctypes.byref(geometry),
+                                         None if fl is None else fl.data_ptr(), 12 * w, None if out is None else out.data_ptr(), rb,
+                                         self._stream())
+        self._held_frames.clear()
+        return fl, out
+
+    def geometry_finishes(self) -> int:
+        """Launches of mfsr_finishGeometry since ``begin_burst`` (mfsr_burst_debug_geometry): one per ``finish_geometry``."""
+        n = ctypes.c_int(-1)
+        self.L.burst_debug_geometry(self._h, ctypes.byref(n))
         return n.value
 
     def denoised_finishes(self) -> int:
