@@ -1,7 +1,9 @@
 """The geometric finish without a device: the numpy restatement (tests/geometry_ref.py) on the identity,
 mfsr_geometry_lens / _defaults / _validate (host-only entry points of the library) against a double-precision recomputation and
-every refusal the header lists, the header's no-NaN / no-overflow claim at the extreme corners, and what the correction does to
-a distorted dot grid (tools/geometry_quality.py)."""
+every refusal the header lists, the header's no-NaN / no-overflow claim at the extreme corners, what the correction does to
+a distorted dot grid (tools/geometry_quality.py), an affine ramp against the float64 value of the header's mapping (an anchor
+that does not share the restatement's coordinate code; tests/test_geometry_gpu.py holds the device to the same), and the search
+for launches whose boxes of source taps are exactly the stage's capacity and one more."""
 import ctypes
 import itertools
 
@@ -175,3 +177,118 @@ def test_correcting_a_distorted_dot_grid_moves_the_dots_back_and_closes_the_frin
     for filt in ("cubic", "bilinear"):
         assert r[filt]["displacement_px"] < r["before"]["displacement_px"], (filt, r)
         assert r[filt]["fringe_px"] < r["before"]["fringe_px"], (filt, r)
+
+
+# ---- 4. an anchor outside the restatement: affine ramps ----------------------------------------------------------------------
+# Both kernels reproduce an affine function exactly wherever no tap clamps (the bilinear weights and the Catmull-Rom weights
+# sum to 1 and have the first moment f), so there the output is the ramp at the source coordinate, whatever the restatement
+# says.  Dyadic coefficients: the ramp is exact in float32 on every source used here.
+RAMP_A, RAMP_B, RAMP_C = (0.5, 1.0, 0.25), (1 / 64, -1 / 128, 1 / 32), (1 / 128, 1 / 64, -1 / 64)
+ANCHOR_CASES = [(70, 37, 131, 67), (70, 37, 53, 29), (300, 200, 257, 129)]
+
+
+def affine_ramp(sw, sh):
+    yy, xx = np.mgrid[0:sh, 0:sw].astype(np.float64)
+    p = np.stack([a + b * xx + c * yy for a, b, c in zip(RAMP_A, RAMP_B, RAMP_C)], axis=-1)
+    assert np.array_equal(p.astype(f32).astype(np.float64), p)
+    return p.astype(f32)
+
+
+def anchor_description(sw, sh, ow, oh, filt):
+    return G.lens(sw, sh, ow, oh, distortion=(0.2, -0.05, 0.0), lateral=(1.004, 0.997), filter=filt)
+
+
+def anchor_expected(g, sw, sh):
+    """include/mfsr.h's mapping in float64 from the float32 fields of the description, without the clamp:
+    (the ramp at (u, v) [outH, outW, 3], the mask of pixels whose taps all lie inside the source by 0.01 px, the bound)."""
+    d = np.float64
+    X, Y = np.arange(g["outW"], dtype=d) + 0.5, np.arange(g["outH"], dtype=d) + 0.5
+    dx = ((X - d(g["ocx"])) * d(g["stepX"]))[None, :, None]
+    dy = ((Y - d(g["ocy"])) * d(g["stepY"]))[:, None, None]
+    rho = (dx * dx + dy * dy) * d(g["rnorm2"])
+    k = np.asarray(g["k"], d)
+    m = ((k[:, 3] * rho + k[:, 2]) * rho + k[:, 1]) * rho + k[:, 0]
+    u, v = d(g["scx"]) + dx * m - 0.5, d(g["scy"]) + dy * m - 0.5
+    want = np.asarray(RAMP_A) + np.asarray(RAMP_B) * u + np.asarray(RAMP_C) * v
+    before, after = (1, 2) if g["filter"] == G.CUBIC else (0, 1)       # the taps are floor(u) - before .. floor(u) + after
+    inside = ((u >= before + 0.01) & (u <= sw - after - 0.01) & (v >= before + 0.01) & (v <= sh - after - 0.01)).all(axis=-1)
+    slope = max(abs(b) + abs(c) for b, c in zip(RAMP_B, RAMP_C))
+    pmax = np.abs(affine_ramp(sw, sh)).max()
+    bound = slope * 32 * float(np.spacing(f32(max(sw, sh)))) + 16 * float(np.spacing(f32(pmax)))
+    return want, inside, bound
+
+
+def assert_affine_anchor(o, g, sw, sh, what):
+    """o [outH, outW, 3] float32 against the ramp at the float64 coordinate; returns (share compared, largest error, bound)"""
+    want, inside, bound = anchor_expected(g, sw, sh)
+    share = float(inside.mean())
+    err = float(np.abs(o.astype(np.float64) - want)[inside].max())
+    print(f"{what}: {share:.2f} of the output compared, largest error {err:.2e}, bound {bound:.2e}")
+    assert share >= 0.7, (what, share)
+    assert err <= bound, (what, err, bound)
+    return share, err, bound
+
+
+@pytest.mark.parametrize("filt", [G.BILINEAR, G.CUBIC], ids=["bilinear", "cubic"])
+@pytest.mark.parametrize("sw,sh,ow,oh", ANCHOR_CASES, ids=lambda v: str(v))
+def test_the_restatement_reproduces_an_affine_ramp_at_the_float64_coordinate(sw, sh, ow, oh, filt):
+    """A lens mapping with distortion (0.2, -0.05, 0) and lateral (1.004, 0.997): at every pixel none of whose taps clamps (at
+    least 70 % of the output) the restatement's output is a + b u + c v at the coordinate of include/mfsr.h evaluated in float64,
+    within max(|b| + |c|) * 32 ulp32(max(srcW, srcH)) + 16 ulp32(max |p|): the dozen float32 roundings of the coordinate chain,
+    each at most half an ulp of a quantity no larger than twice the source extent, times the ramp's slope, plus the
+    interpolation sums.  A wrong half-pixel convention moves the output by half a slope (4e-3 .. 2e-2), a wrong sign in a
+    Catmull-Rom weight by more: both are hundreds of bounds away."""
+    g = anchor_description(sw, sh, ow, oh, filt)
+    o = G.resample(affine_ramp(sw, sh), g)
+    share, err, bound = assert_affine_anchor(o, g, sw, sh, f"{sw}x{sh} -> {ow}x{oh} filter {filt}")
+    # the test can fail: half a pixel off is far outside the bound
+    shifted = dict(g, scx=f32(g["scx"] + 0.5))
+    want, inside, _ = anchor_expected(shifted, sw, sh)
+    assert np.abs(o.astype(np.float64) - want)[inside].max() > 100 * bound
+
+
+# ---- 5. launches at the capacity of the stage -------------------------------------------------------------------------------
+def geometry_tile():
+    v = [ctypes.c_int(0) for _ in range(4)]
+    assert capi.lib().raw["mfsr_geometry_tile"](*(ctypes.byref(x) for x in v)) == 0
+    return tuple(x.value for x in v)
+
+
+def capacity_edge(filt, axis):
+    """A launch in which one tile's box of source taps is exactly the stage's capacity along `axis` ("x": stageW columns, "y":
+    stageH rows), another tile's is one more, and every box fits along the other axis: (source width, source height, the
+    description, the (columns, rows) of every tile's box).  Centres at the middle, k = (1, 0, 0, 0), a step of 1 along the other
+    axis; the step along `axis` is the first of 1.300, 1.305 .. 2.495 that does it (the steps differ per filter: the cubic's
+    box is two taps wider).  Raises AssertionError when there is none."""
+    tw, th, stw, sth = geometry_tile()
+    (ow, oh), (fx, fy) = ((4 * tw, 3 * th), (1.5625, 2.5)) if axis == "x" else ((tw, 8 * th), (1.5625, 2.34375))
+    sw, sh = int(np.ceil(ow * fx)), int(np.ceil(oh * fy))
+    for step in np.arange(1.3, 2.5, 0.005):
+        g = dict(outW=ow, outH=oh, filter=filt, ocx=f32(ow / 2), ocy=f32(oh / 2), scx=f32(sw / 2), scy=f32(sh / 2),
+                 stepX=f32(step if axis == "x" else 1), stepY=f32(step if axis == "y" else 1),
+                 rnorm2=f32(1.0 / ((sw / 2) ** 2 + (sh / 2) ** 2)), k=np.array([[1, 0, 0, 0]] * 3, f32))
+        boxes = []
+        for ty in range(oh // th):
+            for tx in range(ow // tw):
+                x0, x1, y0, y1 = G.tap_box(g, sw, sh, (tx * tw, ty * th, tw, th))
+                boxes.append((x1 - x0 + 1, y1 - y0 + 1))
+        along, across = ([b[0] for b in boxes], [b[1] for b in boxes]) if axis == "x" else ([b[1] for b in boxes], [b[0] for b in boxes])
+        cap, other = (stw, sth) if axis == "x" else (sth, stw)
+        if cap in along and cap + 1 in along and max(across) <= other:
+            return sw, sh, g, boxes
+    raise AssertionError(f"no step puts boxes of {cap} and {cap + 1} along {axis} into one launch")
+
+
+@pytest.mark.parametrize("axis", ["x", "y"])
+@pytest.mark.parametrize("filt", [G.BILINEAR, G.CUBIC], ids=["bilinear", "cubic"])
+def test_a_launch_with_boxes_at_the_capacity_of_the_stage_and_one_beyond_exists(filt, axis):
+    """what tests/test_geometry_gpu.py's capacity-edge test launches: found, valid, and on both sides of `fits`"""
+    tw, th, stw, sth = geometry_tile()
+    sw, sh, g, boxes = capacity_edge(filt, axis)
+    print(f"filter {filt} axis {axis}: source {sw} x {sh}, output {g['outW']} x {g['outH']}, step ({g['stepX']}, {g['stepY']}), "
+          f"boxes {sorted(set(boxes))}")
+    assert capi.lib().raw["mfsr_geometry_validate"](ctypes.byref(_struct(g))) == 0
+    fits = [bw <= stw and bh <= sth for bw, bh in boxes]
+    assert any(fits) and not all(fits)
+    assert (stw, sth)[axis == "y"] in [b[axis == "y"] for b, f in zip(boxes, fits) if f]
+    assert (stw, sth)[axis == "y"] + 1 in [b[axis == "y"] for b, f in zip(boxes, fits) if not f]

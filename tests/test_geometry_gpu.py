@@ -1,8 +1,11 @@
 """The geometric finish on the device: k_geometryImage against the numpy restatement of
-tests/geometry_ref.py for both filters and the four formats, the staged path against the slow path (MFSR_GEOMETRY_STAGE=0) and a
-case whose blocks fall on both sides of the stage's capacity, k_finishGeometry against k_geometryImage of the plain finish's
-float image, crops against the whole, the identity against mfsr_finishRendered, bursts and their refusals, and the CLI.  Every
-comparison is bit for bit: uint32 views of floats, bytes of the integer outputs; outputs sit between canaries."""
+tests/geometry_ref.py for both filters and the four formats, the staged path against the slow path (MFSR_GEOMETRY_STAGE=0), a
+case whose blocks fall on both sides of the stage's capacity and launches with boxes of exactly the capacity and one more, both
+ways of reading the tone table, k_finishGeometry against k_geometryImage of the plain finish's float image, crops against the
+whole, the identity against mfsr_finishRendered, bursts and their refusals, and the CLI.  Every comparison is bit for bit: uint32
+views of floats, bytes of the integer outputs; outputs sit between canaries.  Two exceptions: the built-in gamma (powf: one LSB of
+the format), and the affine ramp, which is compared with the float64 value of include/mfsr.h's mapping and
+not with the restatement (tests/test_geometry_cpu.py derives the bound)."""
 import ctypes
 import os
 import subprocess
@@ -119,13 +122,13 @@ def _want_o(name, sw, sh, fname):
     return _resampled[key]
 
 
-def _geometry_image(L, d_in, sw, sh, g, r, rect, off, rb, in_pitch=None):
+def _geometry_image(L, d_in, sw, sh, g, r, rect, off, rb, in_pitch=None, gamma=0):
     """one launch with guarded outputs: (float image, integer bytes)"""
     x, y, w, h = rect
     d_f, check_f = guarded_upload(np.full((h, w, 3), -7.0, f32))
     d_q, check_q = guarded_upload(np.full(off + rb * h, CANARY, np.uint8))
     L.geometryImage(d_in.data_ptr(), 12 * sw if in_pitch is None else in_pitch, sw, sh, d_f.data_ptr(), 12 * w, d_q.data_ptr() + off, rb,
-                    None if r is None else ctypes.byref(r), ctypes.byref(g), 0, x, y, w, h, None)
+                    None if r is None else ctypes.byref(r), ctypes.byref(g), gamma, x, y, w, h, None)
     check_f("float image")
     check_q("integer image")
     return d_f.cpu().numpy(), d_q.cpu().numpy()
@@ -234,12 +237,14 @@ def _acc(hostile):
     return _accs[hostile]
 
 
-def _finish_geometry(L, ups, g, r, rect, off, rb):
+def _finish_geometry(L, ups, g, r, rect, off, rb, dims=(SW, SH, FBW, FBH)):
+    """dims: (source width, source height, fallback width, fallback height) of `ups`"""
     (d_fin, _), (d_wt, _), (d_fb, _) = ups
+    sw, sh, fbw, fbh = dims
     x, y, w, h = rect
     d_f, check_f = guarded_upload(np.full((h, w, 3), -7.0, f32))
     d_q, check_q = guarded_upload(np.full(off + rb * h, CANARY, np.uint8))
-    L.finishGeometry(d_fin.data_ptr(), d_wt.data_ptr(), 12 * SW, d_fb.data_ptr(), 12 * FBW, FBW, FBH, 0.0, 1.0, 0.0, 1.0, SW, SH,
+    L.finishGeometry(d_fin.data_ptr(), d_wt.data_ptr(), 12 * sw, d_fb.data_ptr(), 12 * fbw, fbw, fbh, 0.0, 1.0, 0.0, 1.0, sw, sh,
                      d_f.data_ptr(), 12 * w, d_q.data_ptr() + off, rb, None if r is None else ctypes.byref(r), ctypes.byref(g), THR, 0,
                      x, y, w, h, None)
     check_f("float image")
@@ -247,11 +252,12 @@ def _finish_geometry(L, ups, g, r, rect, off, rb):
     return d_f.cpu().numpy(), d_q.cpu().numpy()
 
 
-def _plain_finish(L, ups):
+def _plain_finish(L, ups, dims=(SW, SH, FBW, FBH)):
     (d_fin, _), (d_wt, _), (d_fb, _) = ups
-    d_lin, chk = guarded_upload(np.zeros((SH, SW, 3), f32))
-    L.finishFusedWindow(d_fin.data_ptr(), d_wt.data_ptr(), 12 * SW, d_fb.data_ptr(), 12 * FBW, FBW, FBH, 0.0, 1.0, 0.0, 1.0,
-                        d_lin.data_ptr(), 12 * SW, None, SW, SH, THR, 0, 65535.0, 0, 0, SW, SH, None)
+    sw, sh, fbw, fbh = dims
+    d_lin, chk = guarded_upload(np.zeros((sh, sw, 3), f32))
+    L.finishFusedWindow(d_fin.data_ptr(), d_wt.data_ptr(), 12 * sw, d_fb.data_ptr(), 12 * fbw, fbw, fbh, 0.0, 1.0, 0.0, 1.0,
+                        d_lin.data_ptr(), 12 * sw, None, sw, sh, THR, 0, 65535.0, 0, 0, sw, sh, None)
     chk("plain finish")
     return d_lin
 
@@ -332,6 +338,138 @@ def test_the_identity_geometry_gives_the_rendered_finish(fname):
         got = _finish_geometry(L, ups, g, r, (0, 0, SW, SH), 0, rb)
         assert np.array_equal(got[0].view(np.uint32), d_f.cpu().numpy().view(np.uint32)), NAMES[fmt]
         assert np.array_equal(got[1], d_q.cpu().numpy()), NAMES[fmt]
+
+
+# ---- 5b. the stage at its capacity, the table forms, the built-in gamma, and an anchor outside the restatement -----------------
+@pytest.mark.parametrize("axis", ["x", "y"])
+@pytest.mark.parametrize("fname", list(FILTERS))
+def test_boxes_of_exactly_the_stage_and_of_one_more_give_the_restatement(fname, axis, monkeypatch):
+    """tests/test_geometry_cpu.py::capacity_edge finds, per filter, a launch in which one tile's box is exactly stageW columns
+    wide and another's stageW + 1 (every box fits in height), and one with stageH and stageH + 1 rows (every box fits in width):
+    the staged path at the last size it takes and the slow path at the first it must.  The default, MFSR_GEOMETRY_STAGE=0 and the
+    restatement agree bit for bit, for RGB16 and RGB8 (one and four pixels a lane), for mfsr_geometryImage and for
+    mfsr_finishGeometry.  (A stage that took one row too many would put row stageH of a channel's plane on row 0 of the next
+    channel's; one column too many would still sit in the padded row pitch of stageW + 1 floats, two would not.)"""
+    from tests.test_geometry_cpu import capacity_edge
+    L = capi.lib()
+    sw, sh, gd, boxes = capacity_edge(FILTERS[fname], axis)
+    g = _struct(gd)
+    w, h = gd["outW"], gd["outH"]
+    p, (d_in, check_in) = _src(sw, sh)
+    dims = (sw, sh, sw // 2 + 1, sh // 2 + 1)
+    fin, wt, fb = TD._accumulators(sw, sh, dims[2], dims[3], THR)
+    fin[3, 5, 1] = np.nan
+    ups = [guarded_upload(a) for a in (fin, wt, fb)]
+    lin = _plain_finish(L, ups, dims).cpu().numpy()
+    want = {"image": G.resample(p, gd), "finish": G.resample(lin, gd)}
+    assert not np.array_equal(want["image"].view(np.uint32), want["finish"].view(np.uint32))
+    for fmt in (R.RGB16, R.RGB8):
+        off, rb = _layouts(fmt, w)[0]
+        for entry in ("image", "finish"):
+            results = []
+            for stage in (None, "0"):
+                if stage is None:
+                    monkeypatch.delenv("MFSR_GEOMETRY_STAGE", raising=False)
+                else:
+                    monkeypatch.setenv("MFSR_GEOMETRY_STAGE", stage)
+                if entry == "image":
+                    got = _geometry_image(L, d_in, sw, sh, g, _render(fmt, False, None), (0, 0, w, h), off, rb)
+                else:
+                    got = _finish_geometry(L, ups, g, _render(fmt, False, None), (0, 0, w, h), off, rb, dims)
+                _assert_equal(got, want[entry], fmt, False, off, rb,
+                              f"{fname} {axis} {NAMES[fmt]} {entry} stage={stage} boxes {sorted(set(boxes))}")
+                results.append(got)
+            assert np.array_equal(results[0][0].view(np.uint32), results[1][0].view(np.uint32)) and np.array_equal(results[0][1], results[1][1])
+    check_in(f"{fname} {axis}", unchanged=True)
+    for _, chk in ups:
+        chk(f"{fname} {axis}", unchanged=True)
+
+
+@pytest.mark.parametrize("how", ["lds", "cache"])
+@pytest.mark.parametrize("fmt", FORMATS, ids=NAMES.get)
+def test_geometry_with_the_table_in_lds_and_through_the_cache(fmt, how, monkeypatch):
+    """MFSR_RENDER_LUT=lds | cache forces one way of reading the tone table (unset, the geometric kernels read it through the
+    cache): the lens and the up case of test_geometryImage_equals_the_restatement and one mfsr_finishGeometry launch, with
+    matrix + table, both filters, every format.  Both give the restatement's bits."""
+    monkeypatch.setenv("MFSR_RENDER_LUT", how)
+    monkeypatch.delenv("MFSR_GEOMETRY_STAGE", raising=False)
+    L = capi.lib()
+    lut_dev = torch.from_numpy(LUT).to(DEV)
+    assert lut_dev.numel() - 1 <= 8192          # a longer table is read through the cache whatever is asked
+    r = _render(fmt, True, lut_dev)
+    fin, wt, fb, ups = _acc(True)
+    lin = _plain_finish(L, ups).cpu().numpy()
+    for fname, filt in FILTERS.items():
+        for name, sw, sh in (CASES[2], CASES[1]):
+            p, (d_in, check_in) = _src(sw, sh)
+            gd = _mapping(name, sw, sh, filt)
+            w, h = gd["outW"], gd["outH"]
+            off, rb = _layouts(fmt, w)[0]
+            got = _geometry_image(L, d_in, sw, sh, _struct(gd), r, (0, 0, w, h), off, rb)
+            _assert_equal(got, _want_o(name, sw, sh, fname), fmt, True, off, rb, f"{how} {NAMES[fmt]} {name} {fname}")
+            check_in(name, unchanged=True)
+        gd = _mapping("lens", SW, SH, filt)
+        off, rb = _layouts(fmt, SW)[0]
+        got = _finish_geometry(L, ups, _struct(gd), r, (0, 0, SW, SH), off, rb)
+        _assert_equal(got, G.resample(lin, gd), fmt, True, off, rb, f"{how} {NAMES[fmt]} finishGeometry {fname}")
+    for _, chk in ups:
+        chk("accumulators", unchanged=True)
+
+
+def _unpack(got, fmt, w, h, off, rb):
+    """the integer image of _geometry_image as [h, w, 3] int64 samples (alpha asserted opaque)"""
+    rows = np.ascontiguousarray(got[off:].reshape(h, rb)[:, :R.row_bytes(fmt, w)])
+    if fmt == R.RGB10A2:
+        d = rows.view(np.uint32).reshape(h, w).astype(np.int64)
+        assert (d >> 30 == 3).all()
+        return np.stack([d & 1023, d >> 10 & 1023, d >> 20 & 1023], axis=-1)
+    if fmt == R.RGB16:
+        return rows.view(np.uint16).reshape(h, w, 3).astype(np.int64)
+    px = rows.reshape(h, w, -1).astype(np.int64)
+    assert fmt == R.RGB8 or (px[..., 3] == 255).all()
+    return px[..., :3]
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=NAMES.get)
+def test_geometry_builtin_gamma_within_one_lsb(fmt):
+    """applyGamma = 1 without a table, as tests/test_render_gpu.py::test_renderImage_builtin_gamma_within_one_lsb: powf is the only
+    inexact operation, so the integers are within one LSB of the format of numpy's pow applied to the restatement's o (DESIGN.md
+    section 3.1), and equal wherever o lies on the linear segment (o <= 0.0031308; NaN and negatives included: they clamp to 0).
+    The left third of the source is scaled into the linear segment."""
+    L = capi.lib()
+    sw, sh = 70, 37
+    p = _source(sh, sw, 77)
+    p[:, :24] = (np.abs(p[:, :24]) * f32(0.003)).astype(f32)
+    d_in, check_in = guarded_upload(p)
+    gd = _mapping("up", sw, sh, G.CUBIC if FORMATS.index(fmt) % 2 else G.BILINEAR)
+    w, h = gd["outW"], gd["outH"]
+    o = G.resample(p, gd)
+    off, rb = _layouts(fmt, w)[0]
+    got_f, got_q = _geometry_image(L, d_in, sw, sh, _struct(gd), _render(fmt, False, None), (0, 0, w, h), off, rb, gamma=1)
+    check_in("gamma", unchanged=True)
+    diff = np.abs(_unpack(got_q, fmt, w, h, off, rb) - R.quantise(R.gamma(o), fmt))
+    with np.errstate(invalid="ignore"):
+        linear = ~(o > f32(0.0031308))
+        assert int((linear & (o > 0)).sum()) > 1000 and int((~linear).sum()) > 1000
+    print(f"{NAMES[fmt]}: max difference {diff.max()} LSB, {int((diff > 0).sum())} of {diff.size} samples differ")
+    assert diff.max() <= 1
+    assert diff[linear].max() == 0
+    assert np.array_equal(got_f[linear].view(np.uint32), R.gamma(o)[linear].view(np.uint32))
+
+
+@pytest.mark.parametrize("fname", list(FILTERS))
+def test_geometryImage_reproduces_an_affine_ramp_at_the_float64_coordinate(fname):
+    """The device against the float64 value of include/mfsr.h's mapping directly, not against the restatement: an affine ramp
+    under a lens mapping with distortion and a lateral scale, compared wherever no tap clamps, with the bound derived in
+    tests/test_geometry_cpu.py (which holds the restatement to the same)."""
+    from tests.test_geometry_cpu import ANCHOR_CASES, affine_ramp, anchor_description, assert_affine_anchor
+    L = capi.lib()
+    for sw, sh, ow, oh in ANCHOR_CASES:
+        d_in, check_in = guarded_upload(affine_ramp(sw, sh))
+        gd = anchor_description(sw, sh, ow, oh, FILTERS[fname])
+        got_f, _ = _geometry_image(L, d_in, sw, sh, _struct(gd), None, (0, 0, ow, oh), 2, 6 * ow + 2)
+        check_in("ramp", unchanged=True)
+        assert_affine_anchor(got_f, gd, sw, sh, f"device {sw}x{sh} -> {ow}x{oh} {fname}")
 
 
 # ---- 6. bursts ----------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,13 @@
-"""Coverage gate of tests/test_kernel_edges_gpu.py: every entry point of include/mfsr.h that takes a pitch or a width is in
-the edge sweep or the row-stripe tests there, or is listed here with the reason it is not.  A kernel added later without
-either fails this test.  Also what the sweep decides from the oracle alone (the robustness seeds), checked on the CPU."""
+"""Coverage gate of tests/test_kernel_edges_gpu.py and tests/test_finish_edges_gpu.py: every entry point of include/mfsr.h that
+takes a pitch, a width or a ``...RowBytes`` is in the edge sweep or the row-stripe tests of the first, in the sweep of the second,
+or is listed here with the reason it is not.  A kernel added later without either fails this test.  Also what the sweeps decide
+without a device: the robustness seeds from the oracle alone, and which path the geometric finish's tiles take."""
 import re
 
 import numpy as np
 
 from multi_frame_super_resolution_amd.capi import parse_header
+from tests import test_finish_edges_gpu as finish
 from tests import test_kernel_edges_gpu as edges
 
 PIPELINE = "burst / stream driver, covered by tests/test_pipeline_gpu.py"
@@ -63,9 +65,12 @@ EXCLUDED = {
     "mfsr_burst_fuse_rows": "multi-GPU stripe driver, covered by tests/test_dist_local_gpu.py",
     "mfsr_burst_field_dims": "host function: reports sizes",
     "mfsr_stream_set_window": PIPELINE,
+    "mfsr_burst_set_host_row_bytes": "host function: stores the row pitch of the host frames; " + PIPELINE,
+    "mfsr_burst_finish_geometry": "burst driver of the swept mfsr_finishGeometry, tests/test_geometry_gpu.py::"
+                                  "test_burst_finish_geometry_equals_the_restatement_of_the_plain_float_image",
 }
 
-GEOMETRY = re.compile(r"pitch|stride|^width$|^imgWidth$|^dimX$|^outW$|^cols$|^step", re.I)
+GEOMETRY = re.compile(r"pitch|stride|^width$|^imgWidth$|^dimX$|^outW$|^cols$|^step|RowBytes$", re.I)
 
 
 def _geometry_entries():
@@ -77,9 +82,10 @@ def _geometry_entries():
 
 
 def test_every_pitched_entry_point_is_swept_or_excluded():
-    covered = set(edges.SWEEP) | set(edges.ROW_STRIPE_TESTS)
+    covered = set(edges.SWEEP) | set(edges.ROW_STRIPE_TESTS) | set(finish.SWEEP)
     names = _geometry_entries()
-    assert len(names) > 60
+    assert len(names) > 105           # 83 by a pitch, a stride or a width, 23 more by ``...RowBytes``
+    assert not set(edges.SWEEP) & set(finish.SWEEP)
     missing = [n for n in names if n not in covered and n not in EXCLUDED]
     assert not missing, f"neither in the edge sweep nor in EXCLUDED: {missing}"
     both = [n for n in EXCLUDED if n in covered]
@@ -92,6 +98,8 @@ def test_every_pitched_entry_point_is_swept_or_excluded():
         assert case in edges.CASES
     for n, test in edges.ROW_STRIPE_TESTS.items():
         assert callable(getattr(edges, test))
+    for n, case in finish.SWEEP.items():
+        assert case in finish.CASES
 
 
 def test_shapes_stay_small_and_cross_the_block():
@@ -112,3 +120,74 @@ def test_robustness_seeds_keep_the_oracle_off_the_threshold(orc):
         for uv_scale in (1, 2):
             seed, mo = edges.robustness_seed(orc, w, h, uv_scale)
             assert np.abs(mo[1:-1, 1:-1, 3] - edges.THRESHOLD_M).min(initial=1.0) > 1e-5
+
+
+# ---------------------------------------------------------------- tests/test_finish_edges_gpu.py
+def test_finish_shapes_stay_small_and_cross_the_tile():
+    for name, (fn, shp) in finish.CASES.items():
+        assert 1 <= len(shp) <= 14 and len(set(shp)) == len(shp), name
+        for s in shp:
+            assert max(s) <= 300 and sorted(s)[-2] <= 120, (name, s)
+    # the stencil kernels' tiles are what their queries say, and every list has tile - 1, tile and tile + 1 in both axes
+    for name in ("sharpen", "denoise", "chain", "geometry"):
+        tw, th = finish._tile(name)[:2]
+        for entry in (f"mfsr_{name}Image", {"sharpen": "mfsr_finishSharpened", "denoise": "mfsr_finishDenoised", "chain": "mfsr_finishChain",
+                                           "geometry": "mfsr_finishGeometry"}[name]):
+            shp = finish.CASES[finish.SWEEP[entry]][1]
+            assert shp[0] == (1, 1) and {(tw + dx, th + dy) for dx in (-1, 0, 1) for dy in (-1, 0, 1)} <= set(shp), entry
+            assert {s[0] for s in shp} >= {4 * tw - 1, 4 * tw, 4 * tw + 1}, entry       # an RGB8 lane owns four pixels
+    for entry in ("mfsr_renderImage", "mfsr_finishRendered", "mfsr_localToneImage", "mfsr_finishLocalTone"):
+        shp = finish.CASES[finish.SWEEP[entry]][1]
+        assert {(64 + dx, 4 + dy) for dx in (-1, 0, 1) for dy in (-1, 0, 1)} <= set(shp) and {s[0] for s in shp} >= {255, 256, 257}, entry
+    # the two-plane formats: even sizes on both sides of 256 columns and of 8 rows (pairs of rows of a 64 x 4 block)
+    for name in ("c_renderImageYuv", "c_finishRenderedYuv", "c_chainImage_two_plane", "c_finishChain_two_plane"):
+        assert all(w % 2 == 0 and h % 2 == 0 for w, h in finish.CASES[name][1]), name
+    assert {(256 + dx, 8 + dy) for dx in (-2, 0, 2) for dy in (-2, 0, 2)} <= set(finish.YUV)
+    # the shapes that also run both ways of reading the tone table: the smallest, tile + 1 both ways, the odd one
+    for name, (fn, shp) in finish.CASES.items():
+        if len(shp) >= 11 and name not in ("c_imageStats", "c_toneGridStats"):
+            (w9, h9), (w0, h0) = shp[9], shp[5]                # shp[5]: exactly one tile
+            assert w9 > w0 and h9 > h0 and shp[10][0] > 128 and shp[10][1] > h9, name
+
+
+def test_finish_sweeps_full_geometry_tiles_take_the_staged_path():
+    """What tests/test_finish_edges_gpu.py's geometry cases rely on: at every shape with a full tile, for both mappings and both
+    filters, the validated description has a step of about 1.25 and every FULL tile of the launched rectangle has a tap box
+    inside the stage (mfsr_geometry_tile), so the staged path runs; the lens mapping gives the channels different source pixels
+    (the shared-coordinate shortcut is off) and the plain one does not."""
+    from tests import geometry_ref as G
+    tw, th, stw, sth = finish._tile("geometry")
+    full_tiles = 0
+    for w, h in finish.GEOMETRY:
+        for mapping in finish.LENS:
+            for filt in finish.FILTERS.values():
+                sw, sh, gd, (x0, y0, _, _) = finish.geometry_case(w, h, mapping, filt)
+                finish._geometry_struct(gd)                       # mfsr_geometry_validate accepts it
+                assert 1.0 <= gd["stepX"] <= 1.4, (w, h, gd["stepX"])
+                for ty in range(h // th):
+                    for tx in range(w // tw):
+                        bx0, bx1, by0, by1 = G.tap_box(gd, sw, sh, (x0 + tx * tw, y0 + ty * th, tw, th))
+                        assert bx1 - bx0 + 1 <= stw and by1 - by0 + 1 <= sth, (w, h, mapping, tx, ty)
+                        full_tiles += 1
+                m = G.coords(gd, sw, sh, (x0, y0, w, h))
+                apart = bool((m["u"][..., 0] != m["u"][..., 2]).any() or (m["v"][..., 0] != m["v"][..., 2]).any())
+                assert apart == (mapping == "lens") or (w, h) == (1, 1), (w, h, mapping)
+    assert full_tiles >= 2 * 2 * 8
+
+
+def test_finish_sweeps_borrowed_comparisons_are_not_vacuous():
+    """tests/test_robustness_group_gpu.py asserts that its planted flows put pixels outside the image, and
+    tests/test_noise_temporal_gpu.py that pairs are accepted: both hold at the sweep's shapes, from the inputs alone."""
+    from tests.noise_temporal_ref import DEFAULT_TOL, stats_temporal_rule
+    from tests.test_noise_cpu import BLACK, SAT, full_rect
+    from tests.test_noise_temporal_gpu import _block_flow, _const, _noise
+    from tests.test_robustness_group_gpu import _planted_flow
+    for w, h in finish.CASES["c_robustnessMaskGroup"][1]:
+        if (w, h) != (3, 3):
+            for n in (1, 2, 3, 4):
+                assert min(_planted_flow(w, h, 31 * w + 5 * n + k)[1] for k in range(n)) > 0, (w, h, n)
+    for w, h in finish.NOISE_TEMPORAL:
+        host = _noise(3, w, h, 30 + w)
+        flows = [_block_flow(w, h, False, _const(w, h, *s)) for s in ((0, 0), (1, -1), (-3, 2))]
+        terms = int(stats_temporal_rule(host, flows, full_rect(w, h), DEFAULT_TOL, BLACK, SAT)[2][0].sum())
+        assert terms >= (0 if (w, h) == (8, 8) else 3), (w, h, terms)
