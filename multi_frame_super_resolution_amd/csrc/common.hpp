@@ -59,6 +59,13 @@ static inline bool mfsr_window_ok(int hrW, int hrH, int x0, int y0, int w, int h
     return true;
 }
 static inline unsigned mfsr_cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
+// ceil(log2 v) for v >= 1; the callers pass powers of two (pyramid factors, the local-tone grid's cell and bins)
+static inline int ilog2(int v)
+{
+    int s = 0;
+    while ((1 << s) < v) s++;
+    return s;
+}
 // the host checks of a render description (format, matrix coefficients, tone table size): MFSR_OK or MFSR_E_INVALID; render.hip
 int mfsr_render_validate(const mfsr_render* r);
 // without a render description: the plain finish's steps (no matrix, no table, uint16_t RGB)

@@ -20,23 +20,16 @@
 // The count n and the fade are needed at the lane's own pixels only: they are read from global memory there, not staged.
 // R is a runtime argument: one set of kernels.  The dy and dx loops are unrolled over -kMaxR .. kMaxR with a uniform test
 // against R, so every window index is a constant (no scratch) and the row sums of different dy are independent chains.
+// The steps clean_value, clean_count, fade_of and denoise_inv_tolerance are finish_stages.hpp's, which the finish chain
+// (finish_chain.hip) calls too; its denoise_at restates the one-pixel form of the window loop below, tap weight and blend
+// included: change both together.
+#include "finish_stages.hpp"
 #include "stencil_host.hpp"
 
 namespace {
 
-constexpr int kTW = 64, kTH = 16, kMaxR = 3, kPad = 4, kLanes = 256;
+constexpr int kMaxR = kMaxRd, kPad = 4;
 constexpr int kSW = kTW + 2 * kPad, kSH = kTH + 2 * kMaxR;  // the staged extent at R = 3 (columns: padded to the alignment)
-
-struct DenoiseArgs {
-    float gain, alpha, beta, hh;  // hh = strength * strength
-    float wHi, rSpan;             // the fade; used when fade != 0
-    int fade;
-    int R;
-    int yLo, yHi;  // valid rows [yLo, yHi] relative to the launch's first row
-};
-
-// step 1 of section 2.24
-__device__ __forceinline__ float clean_value(float p) { return isnan(p) ? 0.0f : fminf(fmaxf(p, -65536.0f), 65536.0f); }
 
 // 16 bytes of LDS at a 16-byte aligned address as ONE ds_read_b128.  The load is volatile: a plain float4 load is narrowed by
 // the optimiser to the elements a given R uses and sunk into the uniform branches on R (dword and 8-byte reads at a lane
@@ -50,12 +43,6 @@ __device__ __forceinline__ void lds_load16(const float* p, float* v)
     v[1] = f.y;
     v[2] = f.z;
     v[3] = f.w;
-}
-
-// step 3 of section 2.24 on the cleaned count
-__device__ __forceinline__ float fade_of(float n, const DenoiseArgs& a)
-{
-    return a.fade ? fminf(fmaxf((a.wHi - n) * a.rSpan, 0.0f), 1.0f) : 1.0f;
 }
 
 // The tile of the workgroup at (tileX0, tileY0): fetch(x, y) is p of section 2.24 at a valid pixel of the launch, count(x, y)
@@ -110,7 +97,7 @@ __device__ __forceinline__ void denoise_tile(const Fetch& fetch, const Count& co
             const float n3[3] = {nv.x, nv.y, nv.z};
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                n[k][c] = isnan(n3[c]) ? 0.0f : n3[c];
+                n[k][c] = clean_count(n3[c]);
                 need = need || (valid && fade_of(n[k][c], a) != 0.0f);
             }
         }
@@ -124,10 +111,7 @@ __device__ __forceinline__ void denoise_tile(const Fetch& fetch, const Count& co
 #pragma unroll
             for (int k = 0; k < PPL; k++) {
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float v = fmaxf((a.gain * (a.alpha * fmaxf(s[k][c], 0.0f) + a.beta)) / fmaxf(n[k][c], 1e-6f), 1e-20f);
-                    rr[k][c] = 1.0f / (a.hh * v);
-                }
+                for (int c = 0; c < 3; c++) rr[k][c] = denoise_inv_tolerance(s[k][c], n[k][c], a);
                 G[k] = S[k][0] = S[k][1] = S[k][2] = 0.0f;
             }
 #pragma unroll
@@ -230,24 +214,6 @@ __global__ void __launch_bounds__(kLanes)
         return n;
     };
     denoise_tile<FORMAT>(fetch, count, s_s, outImg, outPitch, out, outRowBytes, width, height, a, r, lut);
-}
-
-bool denoise_on(const mfsr_denoise* d) { return d->radius != 0 && d->strength != 0.0f; }
-
-DenoiseArgs denoise_args(const mfsr_denoise* d, int yLo, int yHi)
-{
-    DenoiseArgs a;
-    a.gain = d->gain;
-    a.alpha = d->alpha;
-    a.beta = d->beta;
-    a.hh = d->strength * d->strength;
-    a.fade = d->wHi > d->wLo;
-    a.wHi = d->wHi;
-    a.rSpan = a.fade ? 1.0f / (d->wHi - d->wLo) : 0.0f;
-    a.R = d->radius;
-    a.yLo = yLo;
-    a.yHi = yHi;
-    return a;
 }
 
 }  // namespace

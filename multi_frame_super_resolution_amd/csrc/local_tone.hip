@@ -18,9 +18,12 @@
 // The slice reads eight gains per pixel: four (y, x) corners times an adjacent pair along luma.  Two forms (MFSR_LOCAL_TONE_GRID =
 // lds | cache, as MFSR_RENDER_LUT): the workgroup stages the few corner columns its tile touches as (g[k], g[k + 1]) pairs in
 // LDS, so that a corner is one aligned 8-byte read whatever the parity of k; or every lane reads the grid through the cache.
+// The lookup itself (slice_gain, with SliceArgs and the staged Tile it reads) is finish_stages.hpp's, which the finish chain
+// (finish_chain.hip) calls in the through-the-cache form.
 #include <thread>
 #include <vector>
 
+#include "finish_stages.hpp"
 #include "stats_common.hpp"
 
 namespace {
@@ -28,13 +31,6 @@ namespace {
 constexpr int kGridEntries = 4096;             // (cell, bin) entries of one item in LDS
 constexpr int kTileCols = 18, kTileRows = 3;   // corner columns / rows a 256 x 16 pixel tile can touch at C >= 16
 constexpr int kTilePairs = kTileCols * kTileRows * 32;
-
-struct GridGeom {
-    int cellShift;                             // log2 C
-    int nz, nzShift;                           // luma bins and log2 of them
-    int gx, gy;                                // cells of the full frame
-    int colOffset, rowOffset;                  // the launch's pixel (0, 0) in the full frame
-};
 
 struct ToneStatsArgs {
     float m[9];
@@ -169,40 +165,7 @@ __global__ void __launch_bounds__(kStatsThreads)
 }
 
 // ---- the slice ----------------------------------------------------------------------------------------------------------
-struct SliceArgs {
-    const float* grid;                         // GX GY NZ floats: luma fastest, then x, then y
-    GridGeom g;
-    float invCell;                             // 1 / C (a power of two: exact)
-    float fnz;                                 // (float)NZ
-};
-
-struct Axis {
-    int i0, i1;
-    float a;
-};
-
-// fx = (X + 0.5f) (1 / C) - 0.5f clamped to [0, n - 1]; monotone in X
-__device__ __forceinline__ Axis grid_axis(int X, float invCell, int n)
-{
-    float fx = ((float)X + 0.5f) * invCell - 0.5f;
-    fx = fminf(fmaxf(fx, 0.0f), (float)(n - 1));
-    Axis r;
-    r.i0 = (int)fx;
-    r.i1 = min(r.i0 + 1, n - 1);
-    r.a = fx - (float)r.i0;
-    return r;
-}
-
-// a pair of gains as one 64-bit word: the LDS read of a corner is then one 8-byte access (a float2 is read as two dwords, at
-// twice the LDS cycles)
-__device__ __forceinline__ u64 pack_pair(float a, float b) { return (u64)__float_as_uint(a) | ((u64)__float_as_uint(b) << 32); }
-__device__ __forceinline__ float2 unpack_pair(u64 v) { return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32))); }
-
-// The corner columns of the workgroup's tile, staged as pairs: sPair[(row - j0) * cols + (col - i0)][k] = (g[k], g[min(k+1, NZ-1)])
-struct Tile {
-    int i0, j0, cols;                          // cols = 0: not staged, read the grid through the cache
-};
-
+// the corner columns of the workgroup's tile as pairs in sPair (Tile, finish_stages.hpp)
 template <int GL>
 __device__ __forceinline__ Tile stage_grid(const SliceArgs& t, u64* sPair, int tileX0, int tileX1, int tileY0, int tileY1)
 {
@@ -226,45 +189,6 @@ __device__ __forceinline__ Tile stage_grid(const SliceArgs& t, u64* sPair, int t
     }
     __syncthreads();
     return tl;
-}
-
-// steps 1-3 of section 2.25: the gain of the pixel p at (x, y) of the launch
-template <int GL>
-__device__ __forceinline__ float slice_gain(pix3 p, int x, int y, const RenderArgs& r, const SliceArgs& t, const Tile& tl,
-                                            const u64* sPair)
-{
-    const pix3 q = r.useMatrix ? matrix_pixel(p, r.m) : p;          // uniform
-    const float v0 = isnan(q.x) ? 0.0f : fminf(fmaxf(q.x, 0.0f), 1.0f);
-    const float v1 = isnan(q.y) ? 0.0f : fminf(fmaxf(q.y, 0.0f), 1.0f);
-    const float v2 = isnan(q.z) ? 0.0f : fminf(fmaxf(q.z, 0.0f), 1.0f);
-    const float l = ((54.0f * v0 + 183.0f * v1) + 19.0f * v2) * (1.0f / 256.0f);
-    const Axis ax = grid_axis(x + t.g.colOffset, t.invCell, t.g.gx);
-    const Axis ay = grid_axis(y + t.g.rowOffset, t.invCell, t.g.gy);
-    float fz = l * t.fnz - 0.5f;
-    fz = fminf(fmaxf(fz, 0.0f), (float)(t.g.nz - 1));
-    const int k0 = (int)fz;
-    const float az = fz - (float)k0;
-    float2 c00, c01, c10, c11;                                      // (y, x) corners: the pair (g[k0], g[k1]) of each
-    if (GL && tl.cols) {                                            // uniform
-        const int r0 = (ay.i0 - tl.j0) * tl.cols - tl.i0, r1 = (ay.i1 - tl.j0) * tl.cols - tl.i0;
-        c00 = unpack_pair(sPair[((r0 + ax.i0) << t.g.nzShift) + k0]);
-        c01 = unpack_pair(sPair[((r0 + ax.i1) << t.g.nzShift) + k0]);
-        c10 = unpack_pair(sPair[((r1 + ax.i0) << t.g.nzShift) + k0]);
-        c11 = unpack_pair(sPair[((r1 + ax.i1) << t.g.nzShift) + k0]);
-    } else {
-        const int k1 = min(k0 + 1, t.g.nz - 1);
-        const float* g0 = t.grid + (((size_t)ay.i0 * t.g.gx) << t.g.nzShift);
-        const float* g1 = t.grid + (((size_t)ay.i1 * t.g.gx) << t.g.nzShift);
-        const int o0 = ax.i0 << t.g.nzShift, o1 = ax.i1 << t.g.nzShift;
-        c00 = make_float2(g0[o0 + k0], g0[o0 + k1]);
-        c01 = make_float2(g0[o1 + k0], g0[o1 + k1]);
-        c10 = make_float2(g1[o0 + k0], g1[o0 + k1]);
-        c11 = make_float2(g1[o1 + k0], g1[o1 + k1]);
-    }
-    const float z00 = c00.x + (c00.y - c00.x) * az, z01 = c01.x + (c01.y - c01.x) * az;
-    const float z10 = c10.x + (c10.y - c10.x) * az, z11 = c11.x + (c11.y - c11.x) * az;
-    const float x0 = z00 + (z01 - z00) * ax.a, x1 = z10 + (z11 - z10) * ax.a;
-    return x0 + (x1 - x0) * ay.a;
 }
 
 __device__ __forceinline__ pix3 scale3(pix3 p, float g)
@@ -325,13 +249,6 @@ __global__ void __launch_bounds__(LDS ? 1024 : 256)
     };
     render_span<FORMAT>(src, outImg ? row_ptr(outImg, outPitch, y) : nullptr, out ? out + (size_t)outRowBytes * (size_t)y : nullptr,
                         x0, width, r, lut);
-}
-
-int ilog2(int v)
-{
-    int s = 0;
-    while ((1 << s) < v) s++;
-    return s;
 }
 
 bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }

@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "raw_stage.hpp"
+#include "stencil_host.hpp"
 
 namespace {
 
@@ -124,13 +125,6 @@ struct Bump {
         return im;
     }
 };
-
-int ilog2(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) l++;
-    return l;
-}
 
 int validate(const mfsr_config* c)
 {
@@ -2070,8 +2064,8 @@ static size_t out_row_bytes(const mfsr_burst* b)
     return b->renderOn ? (size_t)mfsr_render_row_bytes(b->render.format, out_w(b)) : (size_t)out_w(b) * 6;
 }
 
-// a two-plane 4:2:0 format: the output buffer holds out_h rows of Y, then out_h / 2 rows of chroma, one pitch
-static bool yuv_format(int format) { return format == MFSR_OUT_NV12 || format == MFSR_OUT_P010; }
+// a two-plane 4:2:0 format (yuv_format, render_common.hpp): the output buffer holds out_h rows of Y, then
+// out_h / 2 rows of chroma, one pitch
 static bool yuv_on(const mfsr_burst* b) { return b->renderOn && yuv_format(b->render.format); }
 
 // bytes of the burst's dense integer output
@@ -2184,7 +2178,7 @@ extern "C" int mfsr_burst_set_sharpen(mfsr_burst* b, const mfsr_sharpen* sharpen
         return MFSR_OK;
     }
     TRY(mfsr_sharpen_validate(sharpen));
-    const bool on = sharpen->radius != 0 && sharpen->amount != 0.0f;
+    const bool on = sharpen_on(sharpen);
     MFSR_REQUIRE(!(on && yuv_on(b)));  // the sharpen tile kernel renders single rows: no two-plane output
     MFSR_REQUIRE(!(on && b->denoiseOn));  // one stencil per finish: whichever setter comes second is refused
     MFSR_REQUIRE(!(on && b->localToneOn));  // the local-tone finish is pointwise: no stencil
@@ -2203,7 +2197,7 @@ extern "C" int mfsr_burst_set_denoise(mfsr_burst* b, const mfsr_denoise* denoise
         return MFSR_OK;
     }
     TRY(mfsr_denoise_validate(denoise));
-    const bool on = denoise->radius != 0 && denoise->strength != 0.0f;
+    const bool on = denoise_on(denoise);
     MFSR_REQUIRE(!(on && yuv_on(b)));     // the denoise tile kernel renders single rows, as the sharpen one
     MFSR_REQUIRE(!(on && b->sharpenOn));  // one stencil per finish
     MFSR_REQUIRE(!(on && b->localToneOn));  // (as mfsr_burst_set_sharpen)

@@ -14,36 +14,16 @@
 // a one-pixel-per-lane format reads 64 consecutive dwords of one row (no bank conflict in either 32-lane half).  An RGB8 lane
 // owns four consecutive columns: it reads them as one float4 per row, channel and tap (ds_read_b128; four dword reads would
 // put the 32 lanes of a half on 8 banks, a 4-way conflict), computes its four pixels, and then hands them to render_span.
-// R is a runtime argument: one set of kernels.
+// R is a runtime argument: one set of kernels.  The arithmetic of the steps (sharpen_clean, sharpen_tap, sharpen_core) and
+// load_span are finish_stages.hpp's, which the finish chain (finish_chain.hip) calls too; the chain restates the loops of the
+// two passes around them (its stage 3 and sharpened_span): change both together.
+#include "finish_stages.hpp"
 #include "stencil_host.hpp"
 
 namespace {
 
-constexpr int kTW = 64, kTH = 16, kMaxR = 4, kLanes = 256;
+constexpr int kMaxR = kMaxRs;
 constexpr int kSW = kTW + 2 * kMaxR, kSH = kTH + 2 * kMaxR;  // the staged extent at R = 4
-
-struct SharpenArgs {
-    float k[kMaxR + 1];
-    float amount, threshold;
-    int R;
-    int yLo, yHi;  // valid rows [yLo, yHi] relative to the launch's first row
-};
-
-// N consecutive floats of an LDS row; N = 4: one 16-byte read (the address is 16-byte aligned, see the file's header)
-template <int N>
-__device__ __forceinline__ void load_span(const float* p, float (&v)[N])
-{
-    if constexpr (N == 4) {
-        const float4 q = *(const float4*)p;
-        v[0] = q.x;
-        v[1] = q.y;
-        v[2] = q.z;
-        v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = p[k];
-    }
-}
 
 // The tile of the workgroup at (tileX0, tileY0): fetch(x, y) is p of section 2.20 at a valid pixel of the launch.
 template <int FORMAT, class Fetch>
@@ -61,9 +41,9 @@ __device__ __forceinline__ void sharpen_tile(const Fetch& fetch, float (*s_s)[kS
         const int gy = min(max(tileY0 + ly - R, a.yLo), a.yHi);
         const pix3 p = fetch(gx, gy);
         const int c0 = lx + (kMaxR - R);  // (the tile's column 0 at float kMaxR of the row)
-        s_s[0][ly][c0] = isnan(p.x) ? 0.0f : p.x;
-        s_s[1][ly][c0] = isnan(p.y) ? 0.0f : p.y;
-        s_s[2][ly][c0] = isnan(p.z) ? 0.0f : p.z;
+        s_s[0][ly][c0] = sharpen_clean(p.x);
+        s_s[1][ly][c0] = sharpen_clean(p.y);
+        s_s[2][ly][c0] = sharpen_clean(p.z);
     }
     __syncthreads();
     // 2. the horizontal pass on every staged row
@@ -73,7 +53,7 @@ __device__ __forceinline__ void sharpen_tile(const Fetch& fetch, float (*s_s)[kS
         for (int c = 0; c < 3; c++) {
             const float* row = &s_s[c][ly][lx + kMaxR];
             float h = a.k[0] * row[0];
-            for (int d = 1; d <= R; d++) h = h + a.k[d] * (row[-d] + row[d]);
+            for (int d = 1; d <= R; d++) h = sharpen_tap(h, a.k[d], row[-d], row[d]);
             s_h[c][ly][lx] = h;
         }
     }
@@ -97,15 +77,10 @@ __device__ __forceinline__ void sharpen_tile(const Fetch& fetch, float (*s_s)[kS
                 load_span<PPL>(&s_h[c][ly + R - d][lx0], up);
                 load_span<PPL>(&s_h[c][ly + R + d][lx0], dn);
 #pragma unroll
-                for (int k = 0; k < PPL; k++) b[k] = b[k] + a.k[d] * (up[k] + dn[k]);
+                for (int k = 0; k < PPL; k++) b[k] = sharpen_tap(b[k], a.k[d], up[k], dn[k]);
             }
 #pragma unroll
-            for (int k = 0; k < PPL; k++) {
-                const float e = s[k] - b[k];
-                const float t = fabsf(e) - a.threshold;
-                const float g = t > 0.0f ? copysignf(t, e) : 0.0f;
-                o[k][c] = s[k] + a.amount * g;
-            }
+            for (int k = 0; k < PPL; k++) o[k][c] = sharpen_core(s[k], b[k], a);
         }
         auto src = [&](int x) {
             pix3 q = {o[0][0], o[0][1], o[0][2]};
@@ -145,20 +120,6 @@ __global__ void __launch_bounds__(kLanes)
     // k_finishRendered's value (finish_value_at: one definition); y may be negative (rowsAbove)
     auto fetch = [&](int x, int y) { return finish_value_at(finalImg, weight, imgPitch, x, y, f); };
     sharpen_tile<FORMAT>(fetch, s_s, s_h, outImg, outPitch, out, outRowBytes, width, height, a, r, lut);
-}
-
-bool sharpen_on(const mfsr_sharpen* s) { return s->radius != 0 && s->amount != 0.0f; }
-
-SharpenArgs sharpen_args(const mfsr_sharpen* s, int yLo, int yHi)
-{
-    SharpenArgs a;
-    for (int d = 0; d <= kMaxR; d++) a.k[d] = d <= s->radius ? s->taps[d] : 0.0f;
-    a.amount = s->amount;
-    a.threshold = s->threshold;
-    a.R = s->radius;
-    a.yLo = yLo;
-    a.yHi = yHi;
-    return a;
 }
 
 }  // namespace

@@ -1,13 +1,20 @@
 // stencil_host.hpp -- the host side that the two stencil finishes share: sharpen.hip and denoise.hip
 // (section 2.24).  Both run a tile kernel with a halo on the value the finish holds and hand its pixels to render_span, so
 // their entry points take the same arguments and refuse the same things: one definition of the argument checks, of the
-// "no output may overlap what the stencil reads" rule, of the tone-table decision and of the format dispatch.  Host code only:
-// no kernel is defined or changed here.
+// "no output may overlap what the stencil reads" rule, of the tone-table decision and of the format dispatch; the finish chain
+// (finish_chain.hip, section 2.26) takes the same, and pipeline.cpp the two "is the stage on" tests.  Host code only: no kernel
+// is defined or changed here (the stages' device steps are finish_stages.hpp's).
 #pragma once
 
 #include "render_common.hpp"
 
 namespace {
+
+// Whether a description's stage does anything (a radius or a strength / amount of 0: the plain finish).  The stand-alone entry
+// points refuse a description that is off, the chain (finish_chain.hip) skips the stage, and the burst's setters (pipeline.cpp)
+// keep the plain finish.
+bool denoise_on(const mfsr_denoise* d) { return d->radius != 0 && d->strength != 0.0f; }
+bool sharpen_on(const mfsr_sharpen* s) { return s->radius != 0 && s->amount != 0.0f; }
 
 bool ranges_overlap(const void* a, long long aBytes, const void* b, long long bBytes)
 {
